@@ -22,6 +22,9 @@ script itself when nobody did; anything else exits non-zero (launch_plan).  `n_g
 `ranks_seen` a sum of ones through the collective library.  At one GPU the line also carries `sharded_path_w1`: the
 code path of W > 1 (both layouts) timed with every collective forced through RCCL at world size 1.
 
+`--dump-outputs DIR` writes what the headline's last timed step returned (for c4 the Bulyan vector and its selection) as
+DIR/<name>.npy, so that two builds can be compared output for output: the inputs are seeded and the same for the same arguments.
+
 Added objects: "roofline" for the dominant kernel (live HIP-event timing around every launch of that kernel on
 the stream it is launched on, via the library's byz_timing_* entry points) and "cpu_baseline" (the numpy
 oracle -- a port of the reference's defences.py -- timed on this box's host cores on a bounded sample).
@@ -65,7 +68,15 @@ def parse_args(argv=None):
                    help='where the full record goes (every leg, every kernel table); stdout carries only the compact line')
     p.add_argument('--extras-steps', type=int, default=10, help='timed rounds of each small side workload')
     p.add_argument('--north-star-steps', type=int, default=2, help='timed rounds of the c5s / c5u legs')
-    return p.parse_args(argv)
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, '
+                        'at most 64 MB in all: a seeded sample of the elements beyond that)')
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.warmup < 0:
+        p.error('--warmup must not be negative')
+    return args
 
 
 # ---- launching: `python bench.py --gpus N` must BE an N-rank run or fail -----------------------------------------
@@ -203,6 +214,7 @@ class Workload:
 
 class BulyanSharded(Workload):
     """configs[3] (and the Bulyan half of configs[4]): column-sharded Bulyan through ShardedAggregator."""
+    output_names = ('aggregate', 'selection', 'krum_index')
 
     def __init__(self, torch, agg, eng, n, d_total, device, seed, with_attack=False, layout='columns', distinct=False, g=None):
         self.torch, self.agg, self.eng = torch, agg, eng
@@ -328,6 +340,7 @@ class BulyanSharded(Workload):
 
 class TrimmedMeanC3(Workload):
     name, defence = 'c3', 'TrimmedMean'
+    output_names = ('aggregate',)
 
     def __init__(self, torch, eng, n, d, device, seed):
         self.eng, self.n, self.d, self.c = eng, n, d, n // 5
@@ -350,6 +363,7 @@ class TrimmedMeanC3(Workload):
 
 class KrumC2(Workload):
     name, defence = 'c2', 'Krum'
+    output_names = ('krum',)
 
     def __init__(self, torch, eng, n, d, device, seed):
         self.eng, self.n, self.d, self.f = eng, n, d, int(n * MAL_PROP)
@@ -384,6 +398,7 @@ class KrumC2(Workload):
 
 class AttackOnly(Workload):
     name, defence = 'attack', 'DriftAttack'
+    output_names = ('drift', 'mean', 'stdev')
 
     def __init__(self, torch, eng, m, d, device, seed):
         self.eng, self.m, self.d = eng, m, d
@@ -952,6 +967,56 @@ def compact_line(detail, budget=LINE_BUDGET):
     return text
 
 
+DUMP_LIMIT = 64 << 20     # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(torch, wl, directory, limit=DUMP_LIMIT):
+    """--dump-outputs: the arrays the timed path handed back in its last step (`wl.last`, named by `wl.output_names`) as
+    DIR/<name>.npy -- floating point as float32 / float64, indices as float64.  Arrays too large for `limit` together are
+    cut to the same seeded sample of elements on every run, whose flat positions go to DIR/<name>.sample_index.npy.
+    Returns {name: what was written}."""
+    parts = wl.last if isinstance(wl.last, tuple) else (wl.last,)
+    arrays = {}
+    for name, x in zip(wl.output_names, parts):
+        if x is None:
+            continue
+        if hasattr(x, 'detach'):
+            narrow = x.dtype.is_floating_point and x.dtype != torch.float64
+        else:
+            x = np.asarray(x)
+            narrow = np.issubdtype(x.dtype, np.floating) and x.dtype != np.float64
+        dtype = np.float32 if narrow else np.float64      # indices: exact in float64
+        arrays[name] = (x, dtype, int(np.prod(x.shape)) * np.dtype(dtype).itemsize)
+    total = sum(nbytes for _, _, nbytes in arrays.values())
+    small = sum(nbytes for _, _, nbytes in arrays.values() if nbytes <= limit // 16)
+    large = total - small
+    os.makedirs(directory, exist_ok=True)
+    record = {}
+    for name, (x, dtype, nbytes) in arrays.items():
+        size, item = int(np.prod(x.shape)), np.dtype(dtype).itemsize
+        index = None
+        if total > limit and nbytes > limit // 16:
+            keep = int((limit - small - 4096) * (nbytes / large)) // (item + 8)     # 4 KiB: the .npy headers
+            index = np.sort(np.random.default_rng(20240611).choice(size, keep, replace=False))
+        if hasattr(x, 'detach'):
+            flat = x.detach().reshape(-1)
+            if index is not None:
+                flat = flat[torch.from_numpy(index).to(flat.device)]
+            host = flat.cpu().numpy()
+        else:
+            flat = np.asarray(x).reshape(-1)
+            host = flat[index] if index is not None else flat
+        host = host.astype(dtype, copy=False)
+        if index is None:
+            host = host.reshape(tuple(x.shape))
+        np.save(os.path.join(directory, name + '.npy'), host)
+        record[name] = {'dtype': np.dtype(dtype).name, 'shape': list(x.shape)}
+        if index is not None:
+            np.save(os.path.join(directory, name + '.sample_index.npy'), index.astype(np.float64))
+            record[name]['sampled'] = len(index)
+    return record
+
+
 def emit(detail, path):
     """Full record -> the detail file (best effort: a read-only tree must not cost the run its line); compact line -> the
     last line of stdout.  Nothing of the record goes to stderr: the driver's tail is stdout + stderr together."""
@@ -1056,6 +1121,7 @@ def main(argv=None):
 
     elapsed, per_kernel = timed_steps(torch, dist, wl, eng, args.steps, args.warmup, world, agg=agg)
     ms_per_step = elapsed / args.steps * 1e3
+    dumped = dump_outputs(torch, wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     line = {
         'metric': 'aggregation rounds/sec at N clients x D params (%s)' % wl.defence,
         'value': args.steps / elapsed, 'unit': 'rounds/s', 'n_gpus': n_gpus, 'ranks_seen': seen, 'steps': args.steps,
@@ -1066,6 +1132,8 @@ def main(argv=None):
         'kernels': kernel_table(per_kernel, args.steps),
         'collectives': collectives_table(agg, args.steps),
     }
+    if dumped is not None:
+        line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     if one_device:
         line['rehearsal'] = ('BYZ_BENCH_ONE_DEVICE=1: %d rank(s) share GPU 0, collectives over gloo -- a rehearsal of the launch '
                              'path, NOT a multi-GPU measurement' % world)

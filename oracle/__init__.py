@@ -11,8 +11,9 @@ Two tiers:
 * ``oracle.faithful`` -- restates ``/root/reference/defences.py`` and
   ``malicious.py`` operation by operation in numpy fp32 (same numpy calls, same
   evaluation order, same tie rules).  Pinned bit-for-bit against the reference
-  itself (``tests/test_oracle_vs_reference.py``, runs where ``/root/reference``
-  exists) and against golden vectors minted from the reference
+  itself (``tests/test_oracle_vs_reference.py``, on the reference's outputs
+  recorded by ``tests/golden/make_golden_oracle_vs_reference.py``) and against
+  golden vectors minted from the reference
   (``tests/golden/*.npz``, made by ``tests/golden/make_golden.py``).
 * ``oracle.ideal`` -- the same selection rules evaluated in fp64 with vectorised
   numpy (dgemm Gram, ``np.sort``).  It is what large GPU runs are compared with,

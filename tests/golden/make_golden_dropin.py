@@ -1,32 +1,44 @@
-"""The reference's own `main.main` and `Server.defend`, unmodified, driven through this repo's drop-in modules.
+#!/usr/bin/env python3
+"""The reference's own `main.main` and `Server.defend`, unmodified, driven through this repo's drop-in modules -- and
+the golden record of its rounds that the test suite replays.
 
-`/root/reference` exists only in the build container, which has no GPU; the GPU box has the GPU and no reference.
-So the claim "drops into main.py unchanged" (BASELINE.json north_star) is split where the two boxes split it:
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_dropin.py REFERENCE_CHECKOUT [--mint]
 
-  here (marker `reference`)  the unmodified main.py / server.py / user.py run two rounds with `dropin/` first on
-        sys.path.  Their `import defences`, `import malicious` bind this repo's modules; every call goes through the
-        drop-in signatures, return types and the attacker's rebinding protocol.  Behind the modules sits the real engine
-        when an MI355X is visible and otherwise a test double with the engine's method surface computing with the CPU
-        oracle -- so what is under test on a CPU box is the boundary, bit for bit, not the kernels.
-        The same rounds with the reference's OWN defences/malicious give the trajectory to compare with, and a small
-        golden record of it is committed (tests/golden/dropin_rounds.npz, written by this file with
-        BYZ_MINT_GOLDEN=1).
-  GPU box (marker `gpu`)  tests/test_gpu_parity.py::test_golden_dropin_rounds replays the recorded rounds through the same
-        drop-in modules on the real engine and must land on the recorded weights.
+The claim "drops into main.py unchanged" (BASELINE.json north_star) needs the reference's driver files, which are not
+part of this repository, so it is checked here, against a reference checkout, and what the suite needs of it is
+recorded:
+
+  check 1  the unmodified main.py / server.py / user.py run two rounds with `dropin/` first on sys.path.  Their
+           `import defences`, `import malicious` bind this repo's modules; every call goes through the drop-in
+           signatures, return types and the attacker's rebinding protocol.  Behind the modules sits the real engine
+           when an MI355X is visible and otherwise a test double with the engine's method surface computing with the
+           CPU oracle -- so what is under test on a CPU host is the boundary, bit for bit, not the kernels.  The same
+           rounds with the reference's OWN defences/malicious give the trajectory to compare with.
+  check 2  `Server.defend` alone (server.py:86-90) on a hand-made server object through the drop-in modules.
+  record   tests/golden/dropin_rounds.npz: the matrices the unmodified main loop handed to `Server.defend`, cut to
+           3000 columns, and what the reference's own `Server.defend` makes of them over two rounds with momentum.
+           Checked against the committed file, or (re)written with --mint.  The suite replays it on the CPU oracle
+           (tests/test_oracle_golden.py::test_golden_dropin_rounds_are_the_oracle_rounds) and through the drop-in
+           modules on the MI355X (tests/test_gpu_parity.py::test_golden_dropin_rounds).
 """
+import contextlib
 import os
+import sys
 import tempfile
 
 import numpy as np
-import pytest
 
-from oracle import faithful
+sys.dont_write_bytecode = True
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'dropin_rounds.npz')
+import reference_harness as harness  # noqa: E402
+from oracle import faithful  # noqa: E402
+
+GOLDEN = os.path.join(HERE, 'dropin_rounds.npz')
 DEFENCES = ['NoDefense', 'Krum', 'TrimmedMean', 'Bulyan']
-
-pytestmark = pytest.mark.reference
 
 
 class OracleBackedEngine:
@@ -60,9 +72,9 @@ class OracleBackedEngine:
         return out
 
 
-@pytest.fixture(scope='module')
+@contextlib.contextmanager
 def engine_in_use():
-    """The real engine when this box has an MI355X (then this IS the end-to-end drop-in run), else the double."""
+    """The real engine when this host has an MI355X (then this IS the end-to-end drop-in run), else the double."""
     from attacking_federate_learning_amd import engine as engine_module
     saved = engine_module._default
     kind = 'hip'
@@ -72,27 +84,21 @@ def engine_in_use():
     except Exception:
         engine_module._default = OracleBackedEngine()
         kind = 'oracle-double'
-    yield kind
-    engine_module._default = saved
+    try:
+        yield kind
+    finally:
+        engine_module._default = saved
 
 
-@pytest.fixture(scope='module')
-def harness():
-    if not os.path.isfile('/root/reference/main.py'):
-        pytest.skip('reference checkout not present on this box')
-    from tests import reference_harness
-    return reference_harness
-
-
-@pytest.mark.parametrize('defense', DEFENCES)
-def test_reference_main_runs_unchanged_on_the_dropin_modules(harness, engine_in_use, defense):
+def check_reference_main_runs_unchanged_on_the_dropin_modules(engine_in_use, defense):
     with tempfile.TemporaryDirectory() as tmp:
         own = harness.run_reference_main(False, defense, os.path.join(tmp, 'own'))
         ours = harness.run_reference_main(True, defense, os.path.join(tmp, 'dropin'))
     # the unmodified driver files in both runs; only `defences` / `malicious` differ
-    assert own['modules']['main'] == ours['modules']['main'] == '/root/reference/main.py'
-    assert own['modules']['server'] == ours['modules']['server'] == '/root/reference/server.py'
-    assert own['modules']['defences'] == '/root/reference/defences.py'
+    ref = os.path.realpath(harness.REFERENCE_DIR)
+    assert own['modules']['main'] == ours['modules']['main'] == os.path.join(ref, 'main.py')
+    assert own['modules']['server'] == ours['modules']['server'] == os.path.join(ref, 'server.py')
+    assert own['modules']['defences'] == os.path.join(ref, 'defences.py')
     assert ours['modules']['defences'].endswith('attacking_federate_learning_amd/dropin/defences.py')
     assert ours['modules']['malicious'].endswith('attacking_federate_learning_amd/dropin/malicious.py')
     assert len(own['weights']) == len(ours['weights']) == 2
@@ -111,7 +117,7 @@ def test_reference_main_runs_unchanged_on_the_dropin_modules(harness, engine_in_
     assert not np.array_equal(own['weights'][0], own['weights'][1])
 
 
-def test_server_defend_of_the_reference_calls_the_dropin_signature(harness, engine_in_use):
+def check_server_defend_of_the_reference_calls_the_dropin_signature(engine_in_use):
     """`Server.defend` alone (server.py:86-90) on a hand-made server object: the exact call of server.py:87."""
     with harness.reference_imports(True):
         import server as ref_server
@@ -136,12 +142,11 @@ def test_server_defend_of_the_reference_calls_the_dropin_signature(harness, engi
         assert bound.defend is bound.defend and set(bound.defend) == set(DEFENCES)
 
 
-def test_mint_or_check_the_golden_rounds(harness):
-    """A compact record of the reference's rounds for the GPU box (which has no reference): the matrices the unmodified
-    main loop handed to `Server.defend` (client gradients of the reference's own `User.step`, drifted by its own
-    `DriftAttack`), cut to 3000 columns, and what the reference's own `Server.defend` (server.py:86-90, its own
-    defences.py) makes of them over two rounds with momentum.  tests/test_gpu_parity.py replays exactly that through
-    the drop-in modules on the MI355X."""
+def mint_or_check_the_golden_rounds(mint):
+    """A compact record of the reference's rounds: the matrices the unmodified main loop handed to `Server.defend`
+    (client gradients of the reference's own `User.step`, drifted by its own `DriftAttack`), cut to 3000 columns, and
+    what the reference's own `Server.defend` (server.py:86-90, its own defences.py) makes of them over two rounds with
+    momentum."""
     with tempfile.TemporaryDirectory() as tmp:
         runs = {d: harness.run_reference_main(False, d, os.path.join(tmp, d)) for d in DEFENCES}
     record = {}
@@ -166,9 +171,27 @@ def test_mint_or_check_the_golden_rounds(harness):
                 srv.users_grads = record[key].copy()
                 srv.defend(d, e)
                 record['%s/weights%d' % (d, e)] = srv.current_weights.copy()
-    if os.environ.get('BYZ_MINT_GOLDEN') == '1' or not os.path.exists(GOLDEN):
+    if mint or not os.path.exists(GOLDEN):
         np.savez_compressed(GOLDEN, **record)
     z = np.load(GOLDEN)
     assert sorted(z.files) == sorted(record)
     for key in record:
         assert np.array_equal(z[key], record[key]), key
+
+
+def main(argv):
+    if len(argv) not in (1, 2) or argv[1:] not in ([], ['--mint']):
+        raise SystemExit('usage: make_golden_dropin.py REFERENCE_CHECKOUT [--mint]')
+    harness.REFERENCE_DIR = os.path.realpath(argv[0])
+    with engine_in_use() as kind:
+        for defense in DEFENCES:
+            check_reference_main_runs_unchanged_on_the_dropin_modules(kind, defense)
+            print('main.py on the drop-in modules (%s): %s ok' % (kind, defense))
+        check_server_defend_of_the_reference_calls_the_dropin_signature(kind)
+        print('Server.defend on the drop-in modules (%s): ok' % kind)
+    mint_or_check_the_golden_rounds('--mint' in argv)
+    print('%s: %s' % (GOLDEN, 'written' if '--mint' in argv else 'matches the reference'))
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])

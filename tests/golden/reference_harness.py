@@ -1,8 +1,9 @@
-"""Runs the UNMODIFIED reference (`/root/reference/main.py`, `server.py`, `user.py`, `data_sets.py`) inside the test
-process, with its `defences` / `malicious` imports resolving either to the reference's own files or to this repo's
-drop-in shims (`attacking_federate_learning_amd/dropin/`).  TEST INFRASTRUCTURE ONLY.
+"""Runs the UNMODIFIED reference (`main.py`, `server.py`, `user.py`, `data_sets.py` of a reference checkout) inside the
+calling process, with its `defences` / `malicious` imports resolving either to the reference's own files or to this
+repo's drop-in shims (`attacking_federate_learning_amd/dropin/`).  Used by tests/golden/make_golden_dropin.py, which
+sets REFERENCE_DIR.
 
-The reference needs two packages this image lacks and a dataset it would download:
+The reference needs two packages the project does not depend on, and a dataset it would download:
   * `tensorflow`   imported by server.py:10, never used on the lines exercised -> an empty stub module;
   * `torchvision`  data_sets.py:4 -> a stub whose `datasets.MNIST` is a seeded synthetic set of MNIST's shape
                    (1 x 28 x 28 floats, labels 0..9) and whose `transforms` do what the two used ones do to a tensor.
@@ -16,8 +17,8 @@ import types
 import numpy as np
 import torch
 
-REFERENCE_DIR = '/root/reference'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REFERENCE_DIR = None     # the reference checkout, set by the caller
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 DROPIN_DIR = os.path.join(ROOT, 'attacking_federate_learning_amd', 'dropin')
 REFERENCE_MODULES = ('main', 'server', 'user', 'data_sets', 'defences', 'malicious', 'backdoor')
 
@@ -85,7 +86,7 @@ def reference_imports(use_dropin):
     malicious` are the reference's own (use_dropin=False) or this repo's shims (use_dropin=True)."""
     saved_path = list(sys.path)
     saved_flag = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True           # /root/reference is read-only
+    sys.dont_write_bytecode = True           # the reference checkout may be read-only
     stubs = _stub_modules()
     scoped = REFERENCE_MODULES + tuple(stubs)
     saved_modules = {name: sys.modules.pop(name) for name in scoped if name in sys.modules}

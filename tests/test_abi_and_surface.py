@@ -1,6 +1,7 @@
 """CPU checks of the boundary: the shared library exports what include/byzagg.h declares, the drop-in modules
 expose the reference's names and signatures, and the product refuses to run without its HIP path."""
 import inspect
+import json
 import os
 import re
 
@@ -111,20 +112,22 @@ def test_product_never_imports_the_oracle():
                 assert 'oracle/' not in src or f == 'sharded.py' or 'tests/' in src, f
 
 
-def test_drop_in_surface_matches_the_reference(reference_modules):
+def test_drop_in_surface_matches_the_reference():
+    """Against the reference's signatures, recorded in tests/golden/reference_surface.json
+    (tests/golden/make_golden_oracle_vs_reference.py)."""
     from attacking_federate_learning_amd import defences, malicious
-    ref_d, ref_m = reference_modules['defences'], reference_modules['malicious']
-    for name in ('no_defense', '_krum_create_distances', 'krum', 'trimmed_mean', 'bulyan'):
-        assert str(inspect.signature(getattr(defences, name))) == str(inspect.signature(getattr(ref_d, name))), name
-    assert list(defences.defend) == list(ref_d.defend)
-    for attr in ('NoDefense', 'Krum', 'TrimmedMean', 'Bulyan'):
-        assert getattr(defences.DefenseTypes, attr) == getattr(ref_d.DefenseTypes, attr)
-    for cls in ('Attack', 'DriftAttack'):
-        for meth in ('__init__', 'attack'):
-            assert str(inspect.signature(getattr(getattr(malicious, cls), meth))) == \
-                str(inspect.signature(getattr(getattr(ref_m, cls), meth)))
-    assert str(inspect.signature(malicious.DriftAttack._attack_grads)) == \
-        str(inspect.signature(ref_m.DriftAttack._attack_grads))
+    with open(os.path.join(ROOT, 'tests', 'golden', 'reference_surface.json')) as fh:
+        ref = json.load(fh)
+    assert len(ref['defences']) == 5 and len(ref['DefenseTypes']) == 4 and len(ref['malicious']) == 4
+    for name, want in ref['defences'].items():
+        assert str(inspect.signature(getattr(defences, name))) == want, name
+    assert list(defences.defend) == ref['defend']
+    for attr, want in ref['DefenseTypes'].items():
+        assert getattr(defences.DefenseTypes, attr) == want
+    for qualname, want in ref['malicious'].items():
+        cls, meth = qualname.split('.')
+        assert str(inspect.signature(getattr(getattr(malicious, cls), meth))) == want, qualname
+    assert str(inspect.signature(malicious.DriftAttack._attack_grads)) == ref['DriftAttack._attack_grads']
     assert issubclass(malicious.DriftAttack, malicious.Attack)
     att = malicious.Attack(1.5)
     assert (att.num_std, att.grads_mean, att.grads_stdev) == (1.5, None, None)

@@ -115,7 +115,7 @@ def test_golden_attack(eng, golden, case):
 @pytest.mark.parametrize('name', ['NoDefense', 'Krum', 'TrimmedMean', 'Bulyan'])
 def test_golden_dropin_rounds(defences, name):
     """Two rounds of `Server.defend` (server.py:86-90) on the matrices the UNMODIFIED reference main loop produced
-    (recorded by tests/test_dropin_reference.py where /root/reference exists): the drop-in `defences.defend[...]` call
+    (recorded by tests/golden/make_golden_dropin.py): the drop-in `defences.defend[...]` call
     of server.py:87 with its exact arguments, then the momentum step, must land on the reference's weights."""
     import os
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dropin_rounds.npz')

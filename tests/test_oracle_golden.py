@@ -149,3 +149,27 @@ def test_the_loops_as_shipped_equal_the_vectorised_restatement():
     d = shipped.dict_from_dense(faithful.distance_matrix(g))
     assert list(d.keys()) == faithful.visit_order(n)
     assert shipped.krum(g, n, f, distances=d, return_index=True) == faithful.krum(g, n, f, return_index=True)
+
+
+def test_golden_dropin_rounds_are_the_oracle_rounds():
+    """tests/golden/dropin_rounds.npz holds two rounds of the reference's own `Server.defend` (server.py:86-90, its own
+    defences.py) on the matrices its unmodified main loop produced, for every defence (tests/golden/make_golden_dropin.py).
+    The oracle, pinned bit for bit to the reference's defences, followed by the same momentum step, must land on those
+    weights exactly; the GPU replays the same rounds through the drop-in modules (tests/test_gpu_parity.py)."""
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dropin_rounds.npz')
+    z = np.load(path)
+    aggregates = {'NoDefense': faithful.no_defense, 'Krum': faithful.krum, 'TrimmedMean': faithful.trimmed_mean,
+                  'Bulyan': faithful.bulyan}
+    assert sorted('%s/weights1' % name for name in aggregates) == sorted(k for k in z.files if k.endswith('/weights1'))
+    mal_prop, momentum, learning_rate = float(z['mal_prop']), 0.9, 0.1
+    for name, aggregate in aggregates.items():
+        weights = z['weights_start'].copy()
+        velocity = np.zeros_like(weights)
+        for e, key in enumerate(('round0_grads', '%s/round1_grads' % name)):
+            users_grads = z[key]
+            n = len(users_grads)
+            current_grads = aggregate(users_grads, n, int(n * mal_prop))        # server.py:87
+            velocity = momentum * velocity - learning_rate * current_grads      # server.py:89
+            weights += velocity                                                # server.py:90
+            assert same(weights, z['%s/weights%d' % (name, e)]), (name, e)

@@ -1,31 +1,31 @@
 """Randomised bit-for-bit checks of oracle.faithful against the reference itself.
 
-Runs only where /root/reference exists (the build container); the GPU box relies on
-the golden vectors instead.
+The inputs are seeded and regenerated here; what the unmodified reference returned for each of them is stored in
+tests/golden/oracle_vs_reference.npz (minted by tests/golden/make_golden_oracle_vs_reference.py from a checkout of
+the reference, with exactly the cases and inputs of this module), so these checks need nothing outside the repository.
 """
+import contextlib
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
 from oracle import faithful, ideal
 
-pytestmark = pytest.mark.reference
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'oracle_vs_reference.npz')
+
+KINDS = ['iid', 'dup', 'quantised']
+KRUM_CASES = [(2, 5, 0), (3, 17, 1), (9, 64, 2), (16, 33, 3), (31, 257, 7)]
+TRIMMED_MEAN_CASES = [(4, 9, 1), (7, 40, 2), (10, 33, 2), (25, 19, 6), (64, 12, 15)]
+BULYAN_CASES = [(3, 8, 0), (7, 30, 1), (11, 50, 2), (19, 21, 4), (27, 100, 6)]
+ATTACK_CASES = [(1, 10, 1.5), (4, 77, 1.5), (13, 300, 0.3), (5, 20, 0.0)]
+BACKDOOR_CASES = [(1, 1.5, 0.1), (257, 1.5, 0.1), (1000, 0.3, 0.1 * 10 / 13), (4096, 3.0, 0.01)]
 
 
 class FakeUser:
     def __init__(self, grads):
         self.grads, self.original_params, self.learning_rate = grads, None, None
-
-
-def ref_selection(ref, g, n, f):
-    dist = ref._krum_create_distances(g)
-    picks = []
-    while len(picks) < n - 2 * f:
-        idx = ref.krum(g, n - len(picks), f, dist, True)
-        picks.append(idx)
-        dist.pop(idx)
-        for r in dist:
-            dist[r].pop(idx)
-    return picks
 
 
 def matrices(seed, n, d, kind):
@@ -38,156 +38,170 @@ def matrices(seed, n, d, kind):
     return g
 
 
-@pytest.mark.parametrize('kind', ['iid', 'dup', 'quantised'])
-@pytest.mark.parametrize('n,d,f', [(2, 5, 0), (3, 17, 1), (9, 64, 2), (16, 33, 3), (31, 257, 7)])
-def test_krum_and_distances(reference_modules, kind, n, d, f):
-    ref = reference_modules['defences']
-    g = matrices(100 + n, n, d, kind)
-    dist_ref = ref._krum_create_distances(g)
-    assert list(dist_ref.keys()) == faithful.visit_order(n)
-    dist = faithful.distance_matrix(g)
-    for i in dist_ref:
-        for j, v in dist_ref[i].items():
-            assert dist[i, j] == v and type(v) is np.float32
-    assert faithful.krum(g, n, f, return_index=True) == ref.krum(g, n, f, return_index=True)
-    if n >= 2 * f + 1:
-        assert np.array_equal(faithful.krum(g, n, f), ref.krum(g, n, f))
+def attack_rows(m, d):
+    return matrices(400 + m, m, d, 'iid') * 2 + 1
 
 
-@pytest.mark.parametrize('kind', ['iid', 'dup', 'quantised'])
-@pytest.mark.parametrize('n,d,c', [(4, 9, 1), (7, 40, 2), (10, 33, 2), (25, 19, 6), (64, 12, 15)])
-def test_trimmed_mean(reference_modules, kind, n, d, c):
-    ref = reference_modules['defences']
-    g = matrices(200 + n, n, d, kind)
-    want = ref.trimmed_mean(g, n, c)
-    assert np.array_equal(faithful.trimmed_mean(g, n, c), want)
-    assert np.allclose(ideal.trimmed_mean(g, c), want, rtol=1e-6, atol=1e-6)
-
-
-@pytest.mark.parametrize('kind', ['iid', 'dup', 'quantised'])
-@pytest.mark.parametrize('n,d,f', [(3, 8, 0), (7, 30, 1), (11, 50, 2), (19, 21, 4), (27, 100, 6)])
-def test_bulyan(reference_modules, kind, n, d, f):
-    ref = reference_modules['defences']
-    g = matrices(300 + n, n, d, kind)
-    agg, picked = faithful.bulyan(g, n, f, return_selection=True)
-    assert picked == ref_selection(ref, g, n, f)
-    assert np.array_equal(agg, ref.bulyan(g, n, f))
-
-
-def test_assertions_match(reference_modules):
-    ref = reference_modules['defences']
-    g = matrices(1, 6, 10, 'iid')
-    for fn_ref, fn in ((ref.krum, faithful.krum), (ref.bulyan, faithful.bulyan)):
-        with pytest.raises(AssertionError):
-            fn_ref(g, 6, 3)
-        with pytest.raises(AssertionError):
-            fn(g, 6, 3)
-    # the Krum assert is skipped when only the index is requested (defences.py:24)
-    assert faithful.krum(g, 6, 3, return_index=True) == ref.krum(g, 6, 3, return_index=True)
-
-
-@pytest.mark.parametrize('m,d,z', [(1, 10, 1.5), (4, 77, 1.5), (13, 300, 0.3), (5, 20, 0.0)])
-def test_attack(reference_modules, m, d, z):
-    ref = reference_modules['malicious']
-    g = matrices(400 + m, m, d, 'iid') * 2 + 1
-    users = [FakeUser(r.copy()) for r in g]
-    att = ref.DriftAttack(z)
-    att.attack(users)
-    vec = faithful.drift_vector(g, z)
-    if z == 0:
-        assert vec is None and np.array_equal(users[0].grads, g[0])
-    else:
-        assert np.array_equal(vec, users[0].grads)
-    assert np.array_equal(faithful.attack_statistics(g)[1], att.grads_stdev)
-
-
-@pytest.fixture(scope='module')
-def reference_backdoor(reference_modules):
-    """backdoor.py imports `malicious` (the reference's, handed in here), plus `data_sets` and `user`, which
-    need torchvision: those two are stubbed for the duration of the import and none of their code runs."""
-    import importlib.util
-    import os
-    import sys
-    import types
-    path = os.path.join('/root/reference', 'backdoor.py')
-    saved = {name: sys.modules.get(name) for name in ('malicious', 'data_sets', 'user')}
-    try:
-        sys.modules['malicious'] = reference_modules['malicious']
-        for name, attrs in (('data_sets', {'MNIST': 'MNIST', 'CIFAR10': 'CIFAR10'}),
-                            ('user', {'flatten_params': None, 'row_into_parameters': None, 'cycle': None})):
-            mod = types.ModuleType(name)
-            mod.__dict__.update(attrs)
-            sys.modules[name] = mod
-        spec = importlib.util.spec_from_file_location('reference_backdoor', path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        for name, old in saved.items():
-            if old is None:
-                sys.modules.pop(name, None)
-            else:
-                sys.modules[name] = old
-    return mod
-
-
-@pytest.mark.parametrize('d,z,lr', [(1, 1.5, 0.1), (257, 1.5, 0.1), (1000, 0.3, 0.1 * 10 / 13), (4096, 3.0, 0.01)])
-def test_backdoor_hook(reference_backdoor, d, z, lr):
+def backdoor_inputs(d):
     rng = np.random.default_rng(900 + d)
     mean = rng.standard_normal(d).astype(np.float32)
     stdev = np.abs(rng.standard_normal(d)).astype(np.float32)
     params = rng.standard_normal(d).astype(np.float32)
     mal = (params + rng.standard_normal(d)).astype(np.float32)
-    att = object.__new__(reference_backdoor.BackdoorAttack)   # the constructor builds data loaders
-    att.num_std = z
-    starts = []
-    att.train_malicious_network = lambda start: (starts.append(start.copy()), mal)[1]
-    want = att._attack_grads(mean.copy(), stdev.copy(), params.copy(), lr)
-    assert np.array_equal(starts[0], faithful.backdoor_initial_params(params, lr, mean))
-    assert np.array_equal(want, faithful.backdoor_attack_grads(mean, stdev, params, lr, z, mal), equal_nan=True)
+    return mean, stdev, params, mal
 
 
-def test_client_step_against_user_step():
-    """oracle.clients against the reference's own User.step / MnistNet (torchvision stubbed for the import only)."""
-    import importlib.util
-    import os
-    import sys
-    import types
-    if not os.path.isfile('/root/reference/user.py'):
-        pytest.skip('reference checkout not present on this box')
-    torch = pytest.importorskip('torch')
-    from oracle import clients
-    tv = types.ModuleType('torchvision')
-    tv.datasets, tv.transforms = types.ModuleType('torchvision.datasets'), types.ModuleType('torchvision.transforms')
-    stubs = {'torchvision': tv, 'torchvision.datasets': tv.datasets, 'torchvision.transforms': tv.transforms}
-    saved = {name: sys.modules.get(name) for name in list(stubs) + ['data_sets']}
-    try:
-        sys.modules.update(stubs)
-        mods = {}
-        for name in ('data_sets', 'user'):
-            spec = importlib.util.spec_from_file_location(name if name == 'data_sets' else 'reference_user',
-                                                          os.path.join('/root/reference', name + '.py'))
-            mods[name] = importlib.util.module_from_spec(spec)
-            if name == 'data_sets':
-                sys.modules['data_sets'] = mods[name]      # user.py does `import data_sets`
-            spec.loader.exec_module(mods[name])
-    finally:
-        for name, old in saved.items():
-            if old is None:
-                sys.modules.pop(name, None)
-            else:
-                sys.modules[name] = old
-    ref_data_sets, ref_user = mods['data_sets'], mods['user']
+def client_step_inputs():
     rng = np.random.default_rng(7)
     weights = (0.1 * rng.standard_normal(79510)).astype(np.float32)
     data = rng.standard_normal((4, 9, 1, 28, 28)).astype(np.float32)
     target = rng.integers(0, 10, size=(4, 9))
-    want = []
-    for c in range(4):
-        usr = types.SimpleNamespace(user_id=c, is_malicious=False, momentum=0.9, data_set=ref_data_sets.MNIST,
-                                    net=ref_data_sets.MnistNet(), criterion=torch.nn.NLLLoss(),
-                                    train_iterator=iter([(torch.from_numpy(data[c]), torch.from_numpy(target[c]))]))
-        usr.train = types.MethodType(ref_user.User.train, usr)
-        ref_user.User.step(usr, weights, 0.1)
-        want.append(usr.grads)
-    got = clients.all_client_gradients(clients.MnistNet(), weights, torch.from_numpy(data), torch.from_numpy(target))
-    assert np.array_equal(got, np.stack(want))      # same torch ops in the same order: bit-identical
+    return weights, data, target
+
+
+@contextlib.contextmanager
+def one_torch_thread():
+    """The client step's bits depend on how many threads torch splits its CPU reductions over; the record is minted on
+    one, so the step is compared on one."""
+    import torch
+    saved = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(saved)
+
+
+def torch_arithmetic_canary():
+    """The client step's op mix (linear, relu, log-softmax, NLL loss, backward) through torch.nn.functional on other fixed
+    inputs, as the SHA-256 of its gradients' bytes.  Recorded with the golden: a host that reproduces its bits rounds these
+    torch CPU kernels as the minting host did, so there the client step must be the reference's bit for bit."""
+    import torch
+    import torch.nn.functional as F
+    rng = np.random.default_rng(11)
+    params = [torch.tensor((0.05 * rng.standard_normal(shape)).astype(np.float32), requires_grad=True)
+              for shape in ((100, 784), (100,), (10, 100), (10,))]
+    x = torch.from_numpy(rng.standard_normal((9, 784)).astype(np.float32))
+    y = torch.from_numpy(rng.integers(0, 10, size=9))
+    w1, b1, w2, b2 = params
+    F.nll_loss(F.log_softmax(F.linear(F.relu(F.linear(x, w1, b1)), w2, b2), dim=1), y).backward()
+    return digest(np.concatenate([p.grad.numpy().ravel() for p in params]))
+
+
+def client_step_sample():
+    """Flat gradient positions recorded in full for the client step: fc1.bias, fc2.weight and fc2.bias whole (the last
+    1,110), and a seeded 2,048 of fc1.weight's 78,400."""
+    fc1 = np.sort(np.random.default_rng(12).choice(78400, 2048, replace=False))
+    return np.concatenate([fc1, np.arange(78400, 79510)])
+
+
+def digest(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def case_key(*parts):
+    return '/'.join(str(p) for p in parts)
+
+
+@pytest.fixture(scope='module')
+def reference_out():
+    """`reference_out(prefix)` -> {field: what the reference returned} for one case of the golden record."""
+    z = np.load(GOLDEN)
+    record = {key: z[key] for key in z.files}
+
+    def case(prefix):
+        fields = {key[len(prefix) + 1:]: value for key, value in record.items() if key.startswith(prefix + '/')}
+        assert fields, 'no golden case %s' % prefix
+        return fields
+    return case
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n,d,f', KRUM_CASES)
+def test_krum_and_distances(reference_out, kind, n, d, f):
+    ref = reference_out(case_key('krum', kind, n, d, f))
+    g = matrices(100 + n, n, d, kind)
+    assert ref['keys'].tolist() == faithful.visit_order(n)
+    dist = faithful.distance_matrix(g)
+    assert ref['all_float32'] and dist.dtype == np.float32
+    assert len(ref['pairs']) == n * (n - 1)
+    for (i, j), v in zip(ref['pairs'].tolist(), ref['values']):
+        assert dist[i, j] == v
+    assert faithful.krum(g, n, f, return_index=True) == int(ref['index'])
+    if n >= 2 * f + 1:
+        assert np.array_equal(faithful.krum(g, n, f), ref['krum'])
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n,d,c', TRIMMED_MEAN_CASES)
+def test_trimmed_mean(reference_out, kind, n, d, c):
+    want = reference_out(case_key('trimmed_mean', kind, n, d, c))['out']
+    g = matrices(200 + n, n, d, kind)
+    assert np.array_equal(faithful.trimmed_mean(g, n, c), want)
+    assert np.allclose(ideal.trimmed_mean(g, c), want, rtol=1e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n,d,f', BULYAN_CASES)
+def test_bulyan(reference_out, kind, n, d, f):
+    ref = reference_out(case_key('bulyan', kind, n, d, f))
+    g = matrices(300 + n, n, d, kind)
+    agg, picked = faithful.bulyan(g, n, f, return_selection=True)
+    assert picked == ref['selection'].tolist()
+    assert np.array_equal(agg, ref['out'])
+
+
+def test_assertions_match(reference_out):
+    ref = reference_out('assertions')
+    g = matrices(1, 6, 10, 'iid')
+    assert ref['krum_raises'] and ref['bulyan_raises']     # the reference asserts on (6, 3) in both
+    for fn in (faithful.krum, faithful.bulyan):
+        with pytest.raises(AssertionError):
+            fn(g, 6, 3)
+    # the Krum assert is skipped when only the index is requested (defences.py:24)
+    assert faithful.krum(g, 6, 3, return_index=True) == int(ref['krum_index'])
+
+
+@pytest.mark.parametrize('m,d,z', ATTACK_CASES)
+def test_attack(reference_out, m, d, z):
+    ref = reference_out(case_key('attack', m, d, z))
+    g = attack_rows(m, d)
+    vec = faithful.drift_vector(g, z)
+    if z == 0:
+        assert vec is None and np.array_equal(ref['grads0'], g[0])
+    else:
+        assert np.array_equal(vec, ref['grads0'])
+    assert np.array_equal(faithful.attack_statistics(g)[1], ref['stdev'])
+
+
+@pytest.mark.parametrize('d,z,lr', BACKDOOR_CASES)
+def test_backdoor_hook(reference_out, d, z, lr):
+    ref = reference_out(case_key('backdoor', d, z, lr))
+    mean, stdev, params, mal = backdoor_inputs(d)
+    assert np.array_equal(ref['start'], faithful.backdoor_initial_params(params, lr, mean))
+    assert np.array_equal(ref['grads'], faithful.backdoor_attack_grads(mean, stdev, params, lr, z, mal), equal_nan=True)
+
+
+def test_client_step_against_user_step(reference_out):
+    """oracle.clients against the reference's own User.step / MnistNet on the same weights and batches.  The record holds
+    the SHA-256 of the reference's gradient bytes, a fixed sample of them (`client_step_sample`), and every client's fp64
+    sum, norm and largest magnitude."""
+    torch = pytest.importorskip('torch')
+    from oracle import clients
+    ref = reference_out('client_step')
+    weights, data, target = client_step_inputs()
+    with one_torch_thread():
+        got = clients.all_client_gradients(clients.MnistNet(), weights, torch.from_numpy(data), torch.from_numpy(target))
+        same_rounding = torch_arithmetic_canary() == str(ref['canary'])
+    assert got.shape == tuple(ref['shape']) and got.dtype == np.float32
+    if same_rounding:
+        assert digest(got) == str(ref['sha256'])     # same torch ops in the same order: bit-identical
+    else:
+        # this host's torch CPU kernels round differently from the minting host's (the canary differs): the same ops
+        # agree up to fp32 summation order -- a few ulps of each client's largest gradient (another thread count on one
+        # host moves them by up to 8e-7 of it)
+        sample = got[:, client_step_sample()]
+        assert np.all(np.abs(sample - ref['sample']) <= 1e-5 * np.abs(ref['sample']) + 4e-6 * ref['row_max'][:, None])
+        rows = got.astype(np.float64)
+        assert np.allclose(rows.sum(axis=1), ref['row_sums'], rtol=1e-4, atol=1e-5)
+        assert np.allclose(np.sqrt((rows ** 2).sum(axis=1)), ref['row_norms'], rtol=1e-5)
