@@ -17,17 +17,13 @@ BUILD = os.path.join(HERE, 'csrc', 'build')
 LIB = os.path.join(HERE, 'libbyzagg.so')
 ARCH = 'gfx950'
 
-SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'trimmed_mean.hip', 'median_window.hip',
+SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_window.hip',
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip']
-# The sorting network only orders finite values and +/-inf padding; NaN inputs are unspecified in the
-# reference as well.  Without this flag every v_min/v_max is preceded by a
-# canonicalising v_max (sNaN quieting), +30% VALU work in the hot kernel.
-EXTRA_FLAGS = {'trimmed_mean.hip': ['-fno-honor-nans'],
-               # median_window.hip keeps its tile in registers: every loop over the register array must be
-               # fully unrolled (a dynamic index would demote the array to scratch), and the staging loop of
-               # the larger instantiations exceeds LLVM's default budget for `#pragma unroll`.  NaN semantics
-               # stay on in this file (the padding rows are +inf; a NaN anywhere in a column makes its result NaN).
-               'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000'],
+# median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
+# dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
+# LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a
+# NaN anywhere in a column makes its result NaN).
+EXTRA_FLAGS = {'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000'],
                'gram.hip': ['-mllvm', '-pragma-unroll-threshold=1000000'],
                'gram_planes.hip': ['-mllvm', '-pragma-unroll-threshold=1000000'],
                'window_lean.hip': ['-mllvm', '-pragma-unroll-threshold=1000000'],

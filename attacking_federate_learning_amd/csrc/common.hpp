@@ -133,7 +133,7 @@ struct byz_ctx {
     byz::Buffer row_top;         // n fp64: sum of a row's largest `drop` finite distances; then n counts of non-finite ones
     byz::Buffer scores;          // n fp32 Krum scores
     // large_rows.hip: more than 16,384 rows
-    byz::Buffer large_keys;      // 64-bit sort keys of one batch of rows / columns
+    byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
     byz::Buffer large_rank;      // n x n uint32: rank of column w in row u, [u][w]
     byz::Buffer large_rank_t;    // n x n uint32: the same transposed, [w][u]: a pick reads the winner's row of it
@@ -285,12 +285,10 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
                        int64_t users_count, int64_t corrupted, int32_t* selection_dev, int32_t* status_dev,
                        hipStream_t stream);
 
-// large_rows.hip: beyond the LDS-resident kernels' 16,384 rows (BYZ_SELECT_LARGE=1 / BYZ_TM_LARGE=1 take these paths at any size)
+// large_rows.hip: beyond the LDS-resident kernels' 16,384 rows (BYZ_SELECT_LARGE=1 takes these paths at any size)
 constexpr int64_t kLargeMaxRows = int64_t{1} << 20;
 bool select_large_applies(int64_t n);
 int segment_sort_u64(byz_ctx* ctx, unsigned long long* keys, int64_t n_segments, int64_t n_pad, hipStream_t stream);
-int segment_sort_u32(byz_ctx* ctx, uint32_t* keys, int64_t n_segments, int64_t n_pad, hipStream_t stream);
-size_t large_key_scratch_bytes();
 int launch_row_sort_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t prefix_len, int64_t drop_count, bool want_tables,
                           hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
@@ -299,19 +297,16 @@ int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t
 
 int launch_trimmed_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
                         const int32_t* row_index, int64_t keep, float* out, hipStream_t stream);
-int64_t trimmed_mean_max_rows();
-bool trimmed_mean_large_applies(int64_t n_rows);
 // tall_select.hip: more rows than the register kernels hold (5,632): order statistics by radix select, the column streamed from HBM
-bool trimmed_mean_tall_applies(int64_t n_rows);
+int64_t trimmed_mean_max_rows();
 int launch_trimmed_mean_tall(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                              int64_t keep, float* out, hipStream_t stream);
-int launch_trimmed_mean_large(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
-                              int64_t keep, float* out, hipStream_t stream);
 // window_lean.hip: the row-split ring selection, first stage of the trimmed mean (round 3)
 int launch_window_lean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        int64_t keep, float* out, int32_t* redo, hipStream_t stream);
 int64_t select_max_rows();
 
+// median_window.hip: lane_exchange.hpp's exchanges over the lane ids
 int launch_lane_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_patterns, hipStream_t stream);
 
 // krum_small.hip: the whole of Krum for N <= 128 in five launches

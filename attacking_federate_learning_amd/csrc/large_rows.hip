@@ -1,4 +1,4 @@
-// More rows than the LDS-resident kernels hold (select.hip, trimmed_mean.hip: 16,384).  The reference has no limit
+// More rows than the LDS-resident kernels hold (select.hip: 16,384).  The reference has no limit
 // (defences.py:23-70 are loops over Python lists); no BASELINE configuration goes beyond N = 10,000, so this file is first of
 // all about BEING THERE with the reference's results: a textbook sort on global memory, 32-bit indices throughout -- and then
 // about not being slow (EXPERIMENTS.md L1: the Bulyan loop went from 7.1 to 0.9 s at N = 20,000).
@@ -41,7 +41,7 @@ __device__ __forceinline__ float from_ordered_bits(uint32_t o) {
 __device__ __forceinline__ int visit_position(int u) { return u == 0 ? 1 : (u == 1 ? 0 : u); }
 
 // FIRST: every merge k = 2 .. len of one chunk; else the levels j = len / 2 .. 1 of the merge of size k_merge.  A chunk is 32 KiB of
-// keys: 4096 of 64 bits (value | column: the selection), 8192 of 32 bits (values alone: the trimmed mean).
+// keys: 4096 of 64 bits (value | column: the selection), 8192 of 32 bits (values alone: Krum).
 template <typename K>
 constexpr int chunk_keys() { return static_cast<int>(32768 / sizeof(K)); }
 

@@ -931,10 +931,23 @@ int launch_ring(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
     return check_launch("median_window_kernel<redo>");
 }
 
+// every lane_xor pattern over the lane ids (tests/test_gpu_parity.py checks the exchange against lane ^ mask)
+__global__ void lane_selftest_kernel(int32_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int masks[11] = {1, 2, 3, 4, 7, 8, 15, 16, 31, 32, 63};
+    const float me = static_cast<float>(lane);
+#pragma unroll
+    for (int p = 0; p < 11; ++p) out[p * 64 + lane] = static_cast<int32_t>(lane_xor(me, masks[p], lane));
+}
+
 }  // namespace
 
-int launch_trimmed_mean_sorted(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
-                               const int32_t* row_index, int64_t keep, float* out, hipStream_t stream);
+int launch_lane_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_patterns, hipStream_t stream) {
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+    lane_selftest_kernel<<<1, 64, 0, stream>>>(out);
+    *n_patterns = 11;
+    return check_launch("lane_selftest_kernel");
+}
 
 int launch_trimmed_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
                         const int32_t* row_index, int64_t keep, float* out, hipStream_t stream) {
@@ -944,17 +957,9 @@ int launch_trimmed_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_
     BYZ_REQUIRE(ceil_div(n_cols, kCols) <= 0x7fffffff, "trimmed_mean: too many columns");
     KernelTimer t(ctx, BYZ_K_TRIMMED_MEAN, stream);
     ctx->redo_valid = false;
-    {
-        // beyond the register kernels' 5,632 rows: a radix select over the column streamed from HBM (tall_select.hip); BYZ_TM_LARGE=1
-        // forces the global-memory sort at every height, BYZ_TM_TALL=0 leaves the heights to the two sorts of rounds 3-6
-        const char* forced_sort = std::getenv("BYZ_TM_LARGE");
-        const bool sort_anyway = forced_sort != nullptr && std::atoi(forced_sort) != 0;
-        if (!sort_anyway && trimmed_mean_tall_applies(n_rows))
-            return launch_trimmed_mean_tall(ctx, G, n_rows, n_cols, ld, row_index, keep, out, stream);
-    }
-    if (trimmed_mean_large_applies(n_rows)) return launch_trimmed_mean_large(ctx, G, n_rows, n_cols, ld, row_index, keep, out, stream);
     const int64_t rpl = ceil_div(n_rows, 64);
-    if (rpl > 88) return launch_trimmed_mean_sorted(ctx, G, n_rows, n_cols, ld, row_index, keep, out, stream);
+    // beyond the register kernels' 5,632 rows: a radix select over the column streamed from HBM (tall_select.hip)
+    if (rpl > 88) return launch_trimmed_mean_tall(ctx, G, n_rows, n_cols, ld, row_index, keep, out, stream);
     // the ring selection (window_lean.hip) with this file's general kernel behind it: 129 .. 5376 rows
     // (BYZ_TM_RING=0 keeps the general kernel for everything: the comparison, and tests of the general kernel itself)
     {

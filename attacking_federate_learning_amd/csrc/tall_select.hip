@@ -19,8 +19,6 @@
 // column walking the rows in order; a NaN anywhere in the column makes the result NaN, like np.median.
 #include "common.hpp"
 
-#include <cstdlib>
-
 namespace byz {
 namespace {
 
@@ -266,12 +264,7 @@ __global__ __launch_bounds__(kTileCols * kWaves) void tall_select_kernel(const f
 
 }  // namespace
 
-// BYZ_TM_TALL=0: the sorts of rounds 3-6 (trimmed_mean_lds_kernel up to 16,384 rows, the global-memory segment sort beyond)
-bool trimmed_mean_tall_applies(int64_t n_rows) {
-    if (n_rows <= 5632) return false;
-    const char* e = std::getenv("BYZ_TM_TALL");     // (read per call: the tests flip it inside one process)
-    return e == nullptr || std::atoi(e) != 0;
-}
+int64_t trimmed_mean_max_rows() { return kLargeMaxRows; }
 
 int launch_trimmed_mean_tall(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                              int64_t keep, float* out, hipStream_t stream) {

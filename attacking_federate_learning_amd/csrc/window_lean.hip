@@ -42,8 +42,6 @@
 
 #include "lane_exchange.hpp"
 
-#include <cstdlib>
-
 namespace byz {
 namespace {
 
@@ -137,15 +135,6 @@ __device__ __forceinline__ int wave_sum_i(int x) {
            __builtin_amdgcn_readlane(x, 48);
 }
 
-// why tiles went to the general kernel (development aid: BYZ_TM_LEAN_DEBUG=1 makes the launcher print and reset them):
-//  0 non-finite input / keep < 1   1 degenerate or too fine a range   2 median ranks buckets apart   3 more candidates than
-//  the sort takes   4 need out of range   5 a ring touches an end bucket of the sampled range   6 a lane's stack overflowed
-//  7 gather and histogram disagree   8 ties at the window's edge   9 threshold NaN
-__device__ unsigned int g_lean_reasons[16];
-// development aid (BYZ_TM_LEAN_TIMING=1): s_memtime stamps of the phases of the first 256 tiles, taken by thread 0
-constexpr int kStampTiles = 256, kStamps = 12;
-__device__ unsigned long long g_lean_stamps[kStampTiles * kStamps];
-
 // Register rows are loaded (and then swept) in this order: the three sampled ones first, so that the range phase can start
 // while the rest of the tile is still on its way (memory returns loads in order).
 template <int RPW>
@@ -178,11 +167,10 @@ struct ColumnPlan {   // written by the search (the first lane of the column's g
 // W waves, RPW 16-row blocks per wave (rows <= 16 W RPW), B buckets, SR sort registers per lane (64 SR candidates per column),
 // LS stack slots per lane and column.  EXACT: the bucket range is the column's true [min, max] (one more sweep); otherwise
 // it is taken from a sample and the end buckets collect what falls outside.
-template <int W, int RPW, int B, int SR, int LS, bool EXACT, bool PIPE>
+template <int W, int RPW, int B, int SR, int LS, bool EXACT>
 __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __restrict__ G, int n_rows, int64_t n_cols,
                                                                 int64_t ld, const int32_t* __restrict__ row_index, int keep,
-                                                                float* __restrict__ out, int32_t* __restrict__ redo,
-                                                                int by_xcd, int stamp_from) {
+                                                                float* __restrict__ out, int32_t* __restrict__ redo) {
     constexpr int T = 64 * W;
     constexpr int NCW = kTileCols / W;          // columns an owner wave resolves: 4, 2 or 1
     constexpr int CAP = 64 * SR;
@@ -209,21 +197,13 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
     // different XCDs (each with its own L2): with tile = blockIdx.x the two halves of every line are fetched by two L2s at
     // different times.  Instead XCD x (blockIdx.x & 7, an affinity the dispatcher follows but does not promise: only speed
     // depends on it) takes the x-th eighth of the tiles in order, so that neighbouring tiles are neighbours in time on ONE L2.
-    // Same-box A/B (scripts/tm_ab.py BYZ_TM_LEAN_XCD 0,1): 1000 rows 0.375 -> 0.354 ms per 2^18 columns, 2080 rows 0.471 ->
-    // 0.410 per 2^17, 5200 rows 0.766 -> 0.625 per 2^16; groups of 2 / 4 / 16 / 64 tiles per XCD instead of eighths: worse or equal.
+    // Same-box A/B against tile = blockIdx.x: 1000 rows 0.375 -> 0.354 ms per 2^18 columns, 2080 rows 0.471 -> 0.410 per 2^17,
+    // 5200 rows 0.766 -> 0.625 per 2^16; groups of 2 / 4 / 16 / 64 tiles per XCD instead of eighths: worse or equal.
+    const int64_t per = gridDim.x >> 3;
     int64_t tile = blockIdx.x;
-    if (by_xcd != 0) {
-        const int64_t per = gridDim.x >> 3;
-        if (tile < (per << 3)) tile = (tile & 7) * per + (tile >> 3);
-    }
+    if (tile < (per << 3)) tile = (tile & 7) * per + (tile >> 3);
     const int64_t c_base = tile * kTileCols;
     const float pinf = __builtin_inff();
-    // stamp_from = 1 + first stamped tile (0: off).  A kernel argument: as a flag in device memory it was a dependent scalar load
-    // that every workgroup waited for before its first instruction of substance.
-    const int64_t stamp_tile = tile - (stamp_from - 1);
-    const bool stamping = stamp_from != 0 && stamp_tile >= 0 && stamp_tile < kStampTiles && tid == 0;
-#define BYZ_STAMP(i) do { if (stamping) g_lean_stamps[stamp_tile * kStamps + (i)] = __builtin_readcyclecounter(); } while (0)
-    BYZ_STAMP(0);
 
     // ---- loads.  No branch around a load (rows past the matrix re-read the last row and are masked where they are used).
     // A wave cannot get past its load instructions while the CU's memory pipeline is full -- measured: the 16 loads of a
@@ -232,7 +212,9 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
     // requesting rows a few ahead of their use inside sweep A instead was measured SLOWER there (0.442 vs 0.400 ms at 1000
     // rows, 0.918 vs 0.881 ms at 2080).  The 16-wave shapes have the CU to themselves: there only the three SAMPLED register
     // rows are requested up front and the others under the range phase and the histogram (1.526 -> 1.409 ms at 5200 rows).
-    // (EXACT needs every row for the range: everything up front.)
+    // With the tiles ordered by XCD that pays for the 8-wave shapes as well: 2080 rows 0.398 -> 0.376 ms per 2^17 columns,
+    // 5200 rows 0.675 -> 0.626 per 2^16, 1000 rows (4 waves) 0.351 -> 0.345 per 2^18 -- inside the noise, so the 4-wave
+    // shapes keep loading at once.  (EXACT needs every row for the range: everything up front.)
     // A ragged last tile (n_cols not a multiple of 16) is the general kernel's: its scalar, guarded loads have no place here.
     if (c_base + kTileCols > n_cols) {   // uniform
         if (tid == 0) redo[1 + atomicAdd(redo, 1)] = static_cast<int32_t>(tile);
@@ -251,11 +233,10 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
     auto fetch = [&](int j) __attribute__((always_inline)) {
         x[j] = *reinterpret_cast<const f32x4u*>(col_base + static_cast<uint64_t>(src[j]) * pitch);
     };
-    constexpr int PRE = (EXACT || !PIPE) ? RPW : 3;   // positions (in lean_order) requested before the range phase
+    constexpr int PRE = (EXACT || W < 8) ? RPW : 3;   // positions (in lean_order) requested before the range phase
     constexpr int AHEAD = 4;               // ... and how far sweep A requests ahead of what it counts
 #pragma unroll
     for (int i = 0; i < PRE; ++i) fetch(lean_order<RPW>(i));
-    BYZ_STAMP(8);   // (the first loads issued)
     // LDS set-up while the loads fly
     for (int i = tid; i < 8 * PS / 4; i += T) reinterpret_cast<uint4*>(un)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < kTileCols) {
@@ -264,7 +245,6 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
     }
     if (tid < 2) flags[tid] = 0;
     __syncthreads();
-    BYZ_STAMP(1);   // loads issued, LDS cleared
 
     // ---- the bucket range: true minimum / maximum (EXACT) or those of a sample of the rows
     {
@@ -295,7 +275,6 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         }
     }
     __syncthreads();
-    BYZ_STAMP(2);   // (the first use of the loaded values: load latency ends here)
 
     // ---- sweep A: histograms.  bucket = round(x * inv + nlo) clamped to [0, B - 1]; column 4 q + e counts in the
     // low (e even) or high (e odd) half of word [column pair 2 q + e / 2][bucket]
@@ -379,12 +358,8 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         }
     }
     __syncthreads();
-    BYZ_STAMP(3);   // sweep A done
     if (flags[0] != 0 || keep < 1) {   // uniform: non-finite input is the general kernel's business
-        if (tid == 0) {
-            redo[1 + atomicAdd(redo, 1)] = static_cast<int32_t>(tile);
-            atomicAdd(&g_lean_reasons[0], 1u);
-        }
+        if (tid == 0) redo[1 + atomicAdd(redo, 1)] = static_cast<int32_t>(tile);
         return;
     }
 
@@ -418,7 +393,6 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         if (gl == 0) h[B] = base;   // entry B: every live value of the two columns (the searches clamp their index to 0 .. B)
     }
     __syncthreads();
-    BYZ_STAMP(4);   // scan done
 
     // ---- search: 16 lanes per column (waves 0 .. 3, four columns each) on the prefix sums.  Every step of a search
     // probes 16 positions at once, so the bucket of a rank or the ring j* takes three dependent LDS round trips where a
@@ -485,12 +459,7 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         // a sampled range: the end buckets also hold whatever fell outside it -- no ring may touch them
         if constexpr (!EXACT) ok = ok && first_left >= 1 && bm2 + ring_hi <= B - 2;
         if (t == 0) {
-            if (!ok) {
-                const int why = !range_ok ? 1 : bm2 - bm1 > 8 ? 2 : expected > CAP ? 3
-                                : (need < 1 || need > n_upto_hi - n_in) ? 4 : 5;
-                atomicAdd(&g_lean_reasons[why], 1u);
-                flags[1] = 1;
-            }
+            if (!ok) flags[1] = 1;
             ColumnPlan p;
             p.sum_b = static_cast<float>(bm1 + bm2);
             p.mid = static_cast<float>(ring_lo + s - 1);
@@ -507,7 +476,6 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         }
     }
     __syncthreads();   // plans written; the prefix sums are dead: their memory becomes the gather stacks
-    BYZ_STAMP(5);   // search done
     if (flags[1] != 0) {   // uniform
         if (tid == 0) redo[1 + atomicAdd(redo, 1)] = static_cast<int32_t>(tile);
         return;
@@ -569,13 +537,9 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
                 part_sum[wave * kTileCols + 4 * q + 2 * ep + 1] = acc1;
             }
         }
-        if (overflow) {
-            flags[1] = 1;
-            atomicAdd(&g_lean_reasons[6], 1u);
-        }
+        if (overflow) flags[1] = 1;
     }
     __syncthreads();
-    BYZ_STAMP(6);   // sweep B done
 
     // ---- owners: wave w resolves columns NCW w .. NCW w + NCW - 1: compact the stacks of the column's 16 W lanes, sort,
     // median, merge, threshold, and the sum over the kept gathered values
@@ -619,10 +583,7 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
             }
         }
         if (__ballot(!all_ok) != 0ull) {
-            if (lane == 0) {
-                flags[1] = 1;
-                atomicAdd(&g_lean_reasons[7], 1u);
-            }
+            if (lane == 0) flags[1] = 1;
         } else {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -694,23 +655,18 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
                 // ... plus the decided-in rings, summed by sweep B: the partials in a fixed order
                 for (int p = 0; p < W; ++p) sum = __fadd_rn(sum, part_sum[p * kTileCols + c]);
                 if (lane == 0) {
-                    if (n_within != need[k] || !(thr == thr)) {
-                        flags[1] = 1;
-                        atomicAdd(&g_lean_reasons[thr == thr ? 8 : 9], 1u);
-                    }
+                    if (n_within != need[k] || !(thr == thr)) flags[1] = 1;
                     colres[c] = __fadd_rn(__fdiv_rn(sum, static_cast<float>(keep)), pivot);   // defences.py:51
                 }
             }
         }
     }
     __syncthreads();
-    BYZ_STAMP(7);   // owners done
     if (flags[1] != 0) {
         if (tid == 0) redo[1 + atomicAdd(redo, 1)] = static_cast<int32_t>(tile);
     } else if (tid < kTileCols && c_base + tid < n_cols) {
         out[c_base + tid] = colres[tid];
     }
-#undef BYZ_STAMP
 }
 
 template <int W, int RPW, int B, int SR, int LS>
@@ -722,56 +678,17 @@ int launch_lean_shape(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     // the sampled range resolves a column only while its window stays clear of the end buckets: columns that keep nearly
     // all of their rows (and short columns, where the sample is most of the column anyway) sweep for the true range
     const bool exact = keep * 10 > n_rows * 9 || n_rows < 192;
-    const char* timing_env = std::getenv("BYZ_TM_LEAN_TIMING");
-    // (tiles from the middle of the launch: the chip is in its steady state there)
-    const int timing = timing_env != nullptr && std::atoi(timing_env) != 0 ? 1 + static_cast<int>(n_tiles > 2 * kStampTiles ? n_tiles / 2 : 0) : 0;
-    const char* xcd_env = std::getenv("BYZ_TM_LEAN_XCD");   // 0: tile = blockIdx.x (the comparison)
-    const int by_xcd = xcd_env != nullptr ? std::atoi(xcd_env) : 1;
-    // PIPE: request the tile's rows under the range phase and the histogram instead of all at once.  Same box, tiles ordered by
-    // XCD (scripts/tm_ab.py BYZ_TM_LEAN_PIPE 0,1): 2080 rows 0.398 -> 0.376 ms per 2^17 columns, 5200 rows 0.675 -> 0.626 per
-    // 2^16, 1000 rows 0.351 -> 0.345 per 2^18 (inside the noise: the 4-wave shapes keep loading at once).  Before the tile
-    // order it paid for the 16-wave shapes only.  BYZ_TM_LEAN_PIPE=0|1 forces it either way: the comparison.
-    const char* pipe_env = std::getenv("BYZ_TM_LEAN_PIPE");
-    const bool pipe = pipe_env != nullptr ? std::atoi(pipe_env) != 0 : W >= 8;
-#define BYZ_LEAN(E, P)                                                                                              \
-    do {                                                                                                            \
-        BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&window_lean_kernel<W, RPW, B, SR, LS, E, P>),  \
-                                  static_cast<int>(lds)));                                                          \
-        window_lean_kernel<W, RPW, B, SR, LS, E, P><<<static_cast<unsigned>(n_tiles), 64 * W, lds, stream>>>(        \
-            G, static_cast<int>(n_rows), n_cols, ld, row_index, static_cast<int>(keep), out, redo, by_xcd, timing); \
+#define BYZ_LEAN(E)                                                                                                     \
+    do {                                                                                                                \
+        BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&window_lean_kernel<W, RPW, B, SR, LS, E>),         \
+                                  static_cast<int>(lds)));                                                              \
+        window_lean_kernel<W, RPW, B, SR, LS, E><<<static_cast<unsigned>(n_tiles), 64 * W, lds, stream>>>(               \
+            G, static_cast<int>(n_rows), n_cols, ld, row_index, static_cast<int>(keep), out, redo);                      \
     } while (0)
-    if (exact) BYZ_LEAN(true, false);
-    else if (pipe) BYZ_LEAN(false, true);
-    else BYZ_LEAN(false, false);
+    if (exact) BYZ_LEAN(true);
+    else BYZ_LEAN(false);
 #undef BYZ_LEAN
-    BYZ_TRY(check_launch("window_lean_kernel"));
-    if (timing) {
-        static unsigned long long stamps[kStampTiles * kStamps];
-        BYZ_HIP(hipStreamSynchronize(stream));
-        BYZ_HIP(hipMemcpyFromSymbol(stamps, HIP_SYMBOL(g_lean_stamps), sizeof(stamps)));
-        const int tiles = n_tiles < kStampTiles ? static_cast<int>(n_tiles) : kStampTiles;
-        double sum[kStamps] = {0};
-        for (int t = 0; t < tiles; ++t)
-            for (int i = 1; i < 8; ++i) sum[i] += static_cast<double>(stamps[t * kStamps + i] - stamps[t * kStamps + i - 1]);
-        {
-            double issue_only = 0;
-            for (int t = 0; t < tiles; ++t) issue_only += static_cast<double>(stamps[t * kStamps + 8] - stamps[t * kStamps + 0]);
-            std::fprintf(stderr, "lean: the load instructions alone take %.0f ticks of the first phase\n", issue_only / tiles);
-        }
-        std::fprintf(stderr, "lean W=%d RPW=%d phases (s_memtime ticks, mean of %d tiles): issue %.0f | load wait + range %.0f | sweep A %.0f | scan %.0f | search %.0f | sweep B %.0f | owners %.0f\n",
-                     W, RPW, tiles, sum[1] / tiles, sum[2] / tiles, sum[3] / tiles, sum[4] / tiles, sum[5] / tiles, sum[6] / tiles, sum[7] / tiles);
-    }
-    if (const char* dbg = std::getenv("BYZ_TM_LEAN_DEBUG"); dbg != nullptr && std::atoi(dbg) != 0) {
-        unsigned int host[16] = {0};
-        BYZ_HIP(hipStreamSynchronize(stream));
-        BYZ_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_lean_reasons), sizeof(host)));
-        std::fprintf(stderr, "lean W=%d RPW=%d %s: %lld tiles; not resolved because of", W, RPW, exact ? "exact" : "sampled", (long long)n_tiles);
-        for (int i = 0; i < 10; ++i) std::fprintf(stderr, " [%d] %u", i, host[i]);
-        std::fprintf(stderr, "\n");
-        const unsigned int zero[16] = {0};
-        BYZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lean_reasons), zero, sizeof(zero)));
-    }
-    return BYZ_OK;
+    return check_launch("window_lean_kernel");
 }
 
 }  // namespace

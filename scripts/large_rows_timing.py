@@ -1,6 +1,7 @@
-"""What the kernels beyond 16,384 rows (csrc/large_rows.hip) cost: wall time of Krum's selection, Bulyan's selection and the trimmed
-mean at 16,500 / 20,000 / 32,000 rows, and of the SAME calls through the forced large path at configs[3]'s and configs[4]'s row counts
-next to the production kernels (what "built to be there, not to be fast" amounts to).  Needs an MI355X.
+"""What the kernels beyond 16,384 rows cost: wall time of Krum's selection and Bulyan's selection (csrc/large_rows.hip) at 16,500 /
+20,000 / 32,000 rows, and of the SAME calls through the forced large path at configs[3]'s and configs[4]'s row counts next to the
+production kernels (what "built to be there, not to be fast" amounts to); the trimmed mean (csrc/tall_select.hip beyond 5,632 rows)
+at 5,200 .. 40,000 rows.  Needs an MI355X.
 
     python scripts/large_rows_timing.py [--quick]
 """
@@ -66,13 +67,9 @@ def main():
     for n, cols in [(5200, 65536), (16384, 16384), (16385, 16384), (20001, 16384)] + ([] if quick else [(40000, 16384)]):
         g = eng.to_device(rng.standard_normal((n, cols), dtype=np.float32))
         c = int(0.48 * n)
-        for forced in ((False, True) if n <= 16384 else (None,)):
-            if forced:
-                os.environ['BYZ_TM_LARGE'] = '1'
-            ms, _ = timed(eng, lambda: eng.trimmed_mean(g, n, c))
-            print('%-26s %12.2f %12.1f   %s' % ('%d x %d' % (n, cols), ms, 4.0 * n * cols / ms / 1e6,
-                                                'large_rows.hip' + (' (forced)' if forced else '') if forced is not False else 'trimmed_mean.hip / window_lean.hip'))
-            os.environ.pop('BYZ_TM_LARGE', None)
+        ms, _ = timed(eng, lambda: eng.trimmed_mean(g, n, c))
+        print('%-26s %12.2f %12.1f   %s' % ('%d x %d' % (n, cols), ms, 4.0 * n * cols / ms / 1e6,
+                                            'window_lean.hip' if n <= 5632 else 'tall_select.hip'))
         del g
 
 

@@ -1,12 +1,12 @@
 """More rows than the LDS-resident kernels hold: csrc/large_rows.hip (needs an MI355X).
 
-The reference has no row limit (defences.py:23-70 are loops over Python lists); the kernels of select.hip / trimmed_mean.hip stop at
+The reference has no row limit (defences.py:23-70 are loops over Python lists); the kernels of select.hip stop at
 16,384 rows.  Beyond that the rows (columns) are sorted in global memory and the Bulyan loop decides batches of picks on exact fp64
 scores, with every contender inside the rigorous rounding band scored again the reference's way and a batch cut where a guess fails.  Two halves:
 
-  * the large path FORCED at sizes the C oracle recomputes completely (BYZ_SELECT_LARGE=1 / BYZ_TM_LARGE=1): the selection pick for pick
+  * the large path FORCED at sizes the C oracle recomputes completely (BYZ_SELECT_LARGE=1): the selection pick for pick
     against oracle/scale.py (defences.py:26-37, :59-68 restated in C) and against the production kernels, on contested data, twins, exact
-    ties, other prefix lengths, non-finite and negative entries, the reference's KeyError; the trimmed mean against oracle.faithful;
+    ties, other prefix lengths, non-finite and negative entries, the reference's KeyError;
   * the path at its own sizes (16,385 .. 20,001 rows): Krum's index against the oracle, Bulyan's selection through sampled picks
     (each one the reference's full scoring pass in the state of that pick), the trimmed mean against oracle.faithful.
 """
@@ -55,7 +55,6 @@ def selection_or_error(fn, *args):
 @pytest.fixture
 def large(monkeypatch):
     monkeypatch.setenv('BYZ_SELECT_LARGE', '1')
-    monkeypatch.setenv('BYZ_TM_LARGE', '1')
     return monkeypatch
 
 
@@ -173,25 +172,6 @@ def test_forced_large_batches_select_the_same(eng, large, batch):
     assert selection_or_error(eng.bulyan_select, odd, 512, 100) == selection_or_error(scale.bulyan_selection, odd, 512, 100)
 
 
-@pytest.mark.parametrize('n,cols,c', [(50, 37, 10), (129, 8, 40), (1000, 23, 480), (2080, 9, 1920), (5000, 6, 2400)])
-def test_forced_large_trimmed_mean(eng, large, n, cols, c):
-    rng = np.random.default_rng(6100 + n)
-    # quarter-integer data: exact +t / -t ties at the window edge, resolved by row order (defences.py:50)
-    g = (np.round(rng.standard_normal((n, cols)) * 64) / 64).astype(np.float32)
-    assert close(eng.trimmed_mean(eng.to_device(g), n, c).numpy(), faithful.trimmed_mean(g, n, c))
-    g2 = rng.standard_normal((n, cols)).astype(np.float32)
-    order = rng.permutation(n)[:n - c // 2].astype(np.int32)
-    got = eng.trimmed_mean(eng.to_device(g2), n, c // 2, row_index=order).numpy()
-    assert close(got, faithful.trimmed_mean(g2[order], len(order), c // 2))
-    g2[3, 1] = np.nan          # np.median of a column with a NaN is NaN, and so is everything after it
-    g2[n - 1, 2] = -np.nan
-    got = eng.trimmed_mean(eng.to_device(g2), n, c).numpy()
-    want = faithful.trimmed_mean(g2, n, c)
-    assert np.isnan(got[1]) and np.isnan(got[2]) and close(np.delete(got, [1, 2]), np.delete(want, [1, 2]))
-    large.setenv('BYZ_LARGE_SCRATCH_MB', '1')       # several batches of columns
-    assert close(eng.trimmed_mean(eng.to_device(g), n, c).numpy(), faithful.trimmed_mean(g, n, c))
-
-
 # ---- beyond 16,384 rows ------------------------------------------------------------------------------------------------------------
 def test_limits_say_so(eng):
     from attacking_federate_learning_amd import _native
@@ -278,21 +258,18 @@ def test_the_defences_end_to_end_beyond_the_lds_kernels(eng, attacked):
     assert close(out.numpy()[cols], want)
 
 
-# ---- tall columns: the radix select of csrc/tall_select.hip (5,633 rows and more, the default there) --------------------------------
+# ---- tall columns: the radix select of csrc/tall_select.hip (every height of 5,633 rows and more) --------------------------------
 @pytest.mark.parametrize('n,cols,c', [(5633, 70, 1400), (6000, 64, 2880), (7001, 33, 1), (8192, 65, 4000), (10000, 130, 4800), (16384, 9, 7000)])
-def test_tall_select_is_the_reference_trimmed_mean(eng, monkeypatch, n, cols, c):
+def test_tall_select_is_the_reference_trimmed_mean(eng, n, cols, c):
     """defences.py:44-52 on columns taller than the register kernels hold: odd and even counts (one or two middle values), quarter-integer
     data (exact +t / -t ties at the window's edge: row order decides, defences.py:50), continuous data, a selection's row order, the
-    extremes of the trim, a NaN, infinities; against oracle.faithful, and the sort kernels of rounds 3-6 (BYZ_TM_TALL=0) agree."""
+    extremes of the trim, a NaN, infinities; against oracle.faithful."""
     rng = np.random.default_rng(9000 + n)
     g = (np.round(rng.standard_normal((n, cols)) * 64) / 64).astype(np.float32)
     want = faithful.trimmed_mean(g, n, c)
     gd = eng.to_device(g)
     got = eng.trimmed_mean(gd, n, c).numpy()
     assert close(got, want)
-    monkeypatch.setenv('BYZ_TM_TALL', '0')
-    assert close(eng.trimmed_mean(gd, n, c).numpy(), want)
-    monkeypatch.delenv('BYZ_TM_TALL')
     g2 = rng.standard_normal((n, cols)).astype(np.float32) * np.exp(rng.uniform(-3, 3, cols)).astype(np.float32)
     order = rng.permutation(n)[:max(5633, n - 300)].astype(np.int32)
     c2 = len(order) // 3

@@ -491,6 +491,24 @@ def test_trimmed_mean_row_index_orders_the_rows(eng):
     assert close(got, want)
 
 
+@pytest.mark.parametrize('n,cols,c', [(50, 37, 10), (129, 8, 40), (1000, 23, 480), (2080, 9, 1920), (5000, 6, 2400)])
+def test_trimmed_mean_ties_row_index_and_nan(eng, n, cols, c):
+    """The default kernels from 50 to 5,000 rows: ring selection (window_lean.hip) and general kernel (median_window.hip)."""
+    rng = np.random.default_rng(6100 + n)
+    # quarter-integer data: exact +t / -t ties at the window edge, resolved by row order (defences.py:50)
+    g = (np.round(rng.standard_normal((n, cols)) * 64) / 64).astype(np.float32)
+    assert close(eng.trimmed_mean(eng.to_device(g), n, c).numpy(), faithful.trimmed_mean(g, n, c))
+    g2 = rng.standard_normal((n, cols)).astype(np.float32)
+    order = rng.permutation(n)[:n - c // 2].astype(np.int32)
+    got = eng.trimmed_mean(eng.to_device(g2), n, c // 2, row_index=order).numpy()
+    assert close(got, faithful.trimmed_mean(g2[order], len(order), c // 2))
+    g2[3, 1] = np.nan          # np.median of a column with a NaN is NaN, and so is everything after it
+    g2[n - 1, 2] = -np.nan
+    got = eng.trimmed_mean(eng.to_device(g2), n, c).numpy()
+    want = faithful.trimmed_mean(g2, n, c)
+    assert np.isnan(got[1]) and np.isnan(got[2]) and close(np.delete(got, [1, 2]), np.delete(want, [1, 2]))
+
+
 @pytest.mark.parametrize('n,d,f', [(11, 50, 2), (40, 3000, 9), (100, 20000, 24), (301, 5000, 74),
                                    (1000, 2000, 240)])
 def test_bulyan_vs_fp64_oracle(eng, n, d, f):

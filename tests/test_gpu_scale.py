@@ -498,8 +498,8 @@ def gaussian(seed, n, d):
     return np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
 
 
-def test_trimmed_mean_lds_kernel_returns_nan_for_a_column_with_nan(eng):
-    """Above 5632 rows the LDS bitonic kernel takes over; a NaN anywhere in a column makes np.median -- and with it the
+def test_tall_trimmed_mean_returns_nan_for_a_column_with_nan(eng):
+    """Above 5632 rows the radix select takes over; a NaN anywhere in a column makes np.median -- and with it the
     reference's result -- NaN there, as it does below 5632 rows, and leaves the other columns alone."""
     n, d, c = 6000, 10, 100
     g = gaussian(61, n, d)
