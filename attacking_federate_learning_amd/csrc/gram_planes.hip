@@ -8,11 +8,12 @@
 //                          FRAGMENT ORDER: for every (32-row block, 16-column step, plane) the 1 KiB image that the 64
 //                          lanes of a wave hold as the A/B operand of v_mfma_f32_32x32x16_{bf16,f16} (lane l: row l & 31,
 //                          columns 8 (l >> 5) .. + 7).  HBM bound.
-//   gram_planes_kernel     one workgroup = 8 waves = a 256 x 128 tile of C = G G^T (two 128 x 128 slabs of gram.hip's
-//                          slab format), each wave a 64 x 64 sub-tile.  A 16-column stage of the 12 row blocks reaches LDS
-//                          by LDS-DMA as contiguous 1 KiB pieces (lane-linear on both sides: perfectly coalesced,
+//   gram_planes_kernel     (bf16x3) one workgroup = 8 waves = a 256 x 128 tile of C = G G^T (two 128 x 128 slabs of
+//                          gram.hip's slab format), each wave a 64 x 64 sub-tile.  A 16-column stage of the 12 row blocks
+//                          reaches LDS by LDS-DMA as contiguous 1 KiB pieces (lane-linear on both sides: perfectly coalesced,
 //                          conflict-free ds_read_b128, no swizzle), NBUF stages of LDS, the DMA NBUF stages ahead, and the
 //                          MFMAs of stage s run from registers while the fragments of stage s + 1 are read.
+//   gram_planes16_kernel   (f16x2) the same tile, planes and ring on v_mfma_f32_16x16x32_f16, 32 columns per step.
 //
 // Two arithmetics (BYZ_GRAM_MODE):
 //   f16x2  (default here)  per (row, 8192-column chunk) the values are scaled by a power of two so that the chunk's
@@ -28,9 +29,11 @@
 //          the fused kernel's; tests/test_gpu_scale.py::test_plane_gram_is_bitwise_the_fused_gram holds it to that.
 //
 // The super-chunk SC (a multiple of the 8192-column chunk) is sized by a memory budget; per super-chunk one split launch
-// and one tile launch, stream-ordered.  Inside a launch the schedule is gram.hip's chunked one: chunks of 8192 columns,
-// all chunks of a tile add in chunk order into the tile's fp64 slabs (ticket per tile), XCD-partitioned tile list in
-// super-block order, rounds that start together.
+// and one tile launch, stream-ordered.  Inside a launch a workgroup computes one (tile, 8192-column chunk) unit, and all
+// chunks of a tile add in chunk order into the tile's fp64 slabs: behind a ticket per tile inside the tile kernel, or
+// (f16x2, deferred) in chunk_reduce_kernel after it.  Rounds of one workgroup per CU start together.  bf16x3 keeps
+// gram.hip's schedule: a tile list in 8 x 8 super-blocks, a contiguous share of it per XCD.  f16x2 lists the tiles in bands
+// of four 256-row blocks and the XCDs claim runs of units from one counter.
 #include "common.hpp"
 
 #include <cstdlib>
@@ -50,7 +53,7 @@ constexpr int kChunkCols = 8192;        // must match gram.hip's chunk (the fp32
 constexpr int kChunkSteps = kChunkCols / 16;
 constexpr int kFlushSteps = 16;         // 256-column MFMA chains (the 16-bit MFMAs accumulate with truncation)
 constexpr int kStatusLostTicket = 1;
-constexpr int kDefaultSpan = 1;        // chunks a workgroup of the deferred tile kernel walks (BYZ_GRAM_KSPAN; round 6 A/B)
+constexpr int kSpareRoundsPercent = 10;  // spare rounds per XCD of the f16x2 tile kernel (5, 12 and 30 % measured alike: G8)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -369,49 +372,29 @@ __device__ __forceinline__ void wait_vmcnt_dyn(int n) {   // n is wave-uniform; 
     }
 }
 
-template <int PLANES, int MB>
-struct Frags;
-template <int MB>
-struct Frags<3, MB> {
-    typedef bf16x8 frag_t;
-    bf16x8 a[3][MB], b[3][2];   // [plane h, m, l][block]
-};
-template <int MB>
-struct Frags<2, MB> {
-    typedef f16x8 frag_t;
-    f16x8 a[2][MB], b[2][2];    // [plane h, m][block]
+struct Frags {
+    bf16x8 a[3][2], b[3][2];   // [plane h, m, l][32-row block]
 };
 
-// PLANES = 3: bf16x3 (gram.hip's arithmetic), 2: f16x2.  NBUF stages of LDS; the DMA runs NBUF stages ahead.
-// DBG (timing experiments only, wrong results; scripts/gram_ab.py): bit 0 no DMA after the first NBUF stages,
-// bit 1 no MFMA, bit 2 no workgroup barrier in the steady loop, bit 3 no LDS reads after stage 0, bit 4 no slab update,
-// bit 5 every workgroup's DMA reads tile (0, 0) (the L2 -> LDS rate without misses).
-// MB = 32-row blocks of a wave's sub-tile along the A side: 2 -> eight waves of 64 x 64, two per SIMD.  (MB = 4, four waves of
-// 128 x 64, was built in round 4, is bitwise equal and lost by 8.6 %: EXPERIMENTS.md G4; only MB = 2 is instantiated.)
-// DEFER (round 5, f16x2): a chunk does not read-modify-write its tile's fp64 slabs (512 KB through the fabric per workgroup
-// and chunk, behind a ticket, with the matrix pipe idle: 8 % of the kernel, EXPERIMENTS.md G3) but WRITES its level-1 sums as
-// they are -- fp32, 128 KB, no read, no ticket -- into `chunk_sums`; chunk_reduce_kernel adds them into the slabs afterwards,
-// in chunk order, in the same fp64 operations: the Gram is bitwise the same.
-template <int PLANES, int NBUF, int DBG, int MB = 2, bool DEFER = false>
-__global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x4* __restrict__ planes, int64_t n_steps,
-                                                                  const double* __restrict__ unscale, int64_t rows_pad,
-                                                                  double* __restrict__ partial, int n_tiles,
-                                                                  const int2* __restrict__ tile_order, int n_chunks,
-                                                                  int* __restrict__ tickets, int round_size, int t128,
-                                                                  int slab_live0, int n_blocks32,
-                                                                  int32_t* __restrict__ device_status,
-                                                                  float* __restrict__ chunk_sums,
-                                                                  float* __restrict__ ragged_sums, int kspan, int pin, int map_round) {
-    (void)pin;   // (gram_planes16_kernel's knob: one launch signature for both kernels)
+// bf16x3 (gram.hip's arithmetic).  NBUF stages of LDS; the DMA runs NBUF stages ahead.  Eight waves of 64 x 64, two per
+// SIMD: each wave's sub-tile is 2 x 2 blocks of 32 x 32.  (Four waves of 128 x 64, built in round 4, are bitwise equal and
+// lost by 8.6 %: EXPERIMENTS.md G4.)
+template <int NBUF>
+__global__ __launch_bounds__(512, 1) void gram_planes_kernel(const u32x4* __restrict__ planes, int64_t n_steps,
+                                                             double* __restrict__ partial, int n_tiles,
+                                                             const int2* __restrict__ tile_order, int n_chunks,
+                                                             int* __restrict__ tickets, int round_size, int t128,
+                                                             int slab_live0, int n_blocks32,
+                                                             int32_t* __restrict__ device_status) {
+    constexpr int PLANES = 3;
     constexpr int kRbBytes = PLANES * kFragBytes;           // one 32-row block, one stage: [plane][1 KiB]
-    constexpr int kStage = kRowBlocks * kRbBytes;           // 36,864 (bf16x3) / 24,576 (f16x2)
-    constexpr int NW = 16 / MB;                             // waves of the workgroup
+    constexpr int kStage = kRowBlocks * kRbBytes;           // 36,864
+    constexpr int NW = 8;                                   // waves of the workgroup
     constexpr int kPieces = kRowBlocks * PLANES;            // 1 KiB pieces per stage
     constexpr int kPerWave = (kPieces + NW - 1) / NW;       // DMA instructions per wave and stage (the last may be idle)
     constexpr int kFullWaves = kPieces % NW == 0 ? NW : kPieces % NW;   // waves that issue all kPerWave
     constexpr int kLead = NBUF;
-    typedef Frags<PLANES, MB> frags_t;
-    typedef typename frags_t::frag_t frag_t;
+    typedef bf16x8 frag_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [NBUF][12 row blocks][planes][1 KiB]
 
     // workgroup -> (tile, chunk): XCD x owns a contiguous share of the tile list and works through it chunk by chunk
@@ -420,13 +403,7 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
     const int base = n_tiles >> 3, rem = n_tiles & 7;
     const int mine = base + (xcd < rem ? 1 : 0);
     const int first = xcd * base + (xcd < rem ? xcd : rem);
-    // (DEFER, round 6) a workgroup owns a tile over a SPAN of `kspan` consecutive chunks: the planes of a row block are
-    // contiguous along K, so the DMA ring runs on across the chunk boundaries -- one launch, one ramp, one drain per span -- and
-    // at every boundary the chunk's level-1 sums leave for `chunk_sums` exactly as a one-chunk workgroup writes them: the Gram
-    // is bitwise the same for every kspan.  `chunk` below is the FIRST chunk of the span.
-    const int n_spans = DEFER ? (n_chunks + kspan - 1) / kspan : n_chunks;
-    const int span = mine > 0 ? seq / mine : n_spans;
-    const int chunk = DEFER ? span * kspan : span;
+    const int chunk = mine > 0 ? seq / mine : n_chunks;
     int* done = tickets + n_tiles + xcd;
     {
         // rounds: a workgroup starts only when every workgroup of the earlier rounds of its XCD has finished, so that the
@@ -440,12 +417,12 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
             }
         }
         __syncthreads();
-        if (span >= n_spans) {
+        if (chunk >= n_chunks) {
             if (threadIdx.x == 0) __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
     }
-    const int t_list = first + (seq - span * mine);
+    const int t_list = first + (seq - chunk * mine);
     const int2 tt = tile_order[t_list];
     const int bi = __builtin_amdgcn_readfirstlane(tt.x);   // 256-row block of the A side
     const int tj = __builtin_amdgcn_readfirstlane(tt.y);   // 128-row block of the B side
@@ -454,9 +431,9 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    const int ti = 2 * bi + (wr * MB) / 4;             // this wave's slab row
-    const int row_in_slab = ((wr * MB) % 4) * 32;      // and where its sub-tile starts inside it
-    // Which of the wave's MB x 2 output blocks (32 x 32) anybody reads: block (m, n) covers 32-row block `rblk` of the A side and
+    const int ti = 2 * bi + wr / 2;                    // this wave's slab row
+    const int row_in_slab = (wr % 2) * 64;             // and where its 64 x 64 sub-tile starts inside it
+    // Which of the wave's 2 x 2 output blocks (32 x 32) anybody reads: block (m, n) covers 32-row block `rblk` of the A side and
     // `cblk` of the B side.  Not needed: blocks of rows past the matrix (N = 4000 pads to 4096: three quarters of the last slab
     // row; N = 10,000 to 10,112), and blocks strictly above the diagonal (gram_reduce_kernel reads a diagonal slab's lower
     // triangle only).  Round 4 skipped at slab granularity only and issued 8 % more MFMAs than 3 N^2 D / 32768 at N = 4000
@@ -464,29 +441,25 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
     // that are computed go through the same MFMA chain in the same order as before: the Gram is bitwise the same.
     unsigned live_blocks = 0;
     if (tj <= ti && ti < t128 && n_blocks32 < 0) {
-        live_blocks = (1u << (MB * 2)) - 1u;     // BYZ_GRAM_BLOCK_SKIP=0: round 4's slab-granular rule, for the same-box A/B
+        live_blocks = 15u;     // BYZ_GRAM_BLOCK_SKIP=0: round 4's slab-granular rule
     } else if (tj <= ti && ti < t128) {     // the upper half of a tile that straddles the diagonal is not needed
 #pragma unroll
-        for (int m = 0; m < MB; ++m)
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const int rblk = ti * 4 + row_in_slab / 32 + m, cblk = tj * 4 + wc * 2 + n;
                 if (rblk < n_blocks32 && cblk <= rblk) live_blocks |= 1u << (m * 2 + n);
             }
     }
-    // The K loop is instantiated once per mask that can occur (MB = 2, bit m * 2 + n): all four blocks; the row block m = 0
-    // only (the last valid row block of the matrix is the first of its wave); a diagonal 64 x 64 sub-tile without its upper
-    // block; both; nothing (a dead wave still takes part in the DMA and the barriers).  A run-time test per MFMA instead cost the
+    // The K loop is instantiated once per mask that can occur (bit m * 2 + n): all four blocks; the row block m = 0 only (the
+    // last valid row block of the matrix is the first of its wave); a diagonal 64 x 64 sub-tile without its upper block;
+    // both; nothing (a dead wave still takes part in the DMA and the barriers).  A run-time test per MFMA instead cost the
     // compiler its schedule (a wait for ALL pending LDS reads in front of every MFMA).
-    static_assert(MB == 2, "the mask set below is the one of 64 x 64 wave tiles");
     const bool live_wave = live_blocks != 0;
 
     const int step0 = chunk * kChunkSteps;
     int n_stages = static_cast<int>(n_steps) - step0;
-    {
-        const int span_steps = DEFER ? kspan * kChunkSteps : kChunkSteps;
-        if (n_stages > span_steps) n_stages = span_steps;
-    }
+    if (n_stages > kChunkSteps) n_stages = kChunkSteps;
 
     // LDS-DMA: piece q = wave + 8 i of the stage (row block q / PLANES, plane q % PLANES): a wave-uniform byte offset from
     // `planes` plus 16 bytes per lane; the LDS image of a stage is piece-linear, and so is a row block's stage in HBM
@@ -496,14 +469,12 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
         int q = wave + NW * i;
         if (q >= kPieces) q = kPieces - 1;
         const int rbl = q / PLANES, piece = q % PLANES;
-        int64_t rb = rbl < 8 ? static_cast<int64_t>(bi) * 8 + rbl : static_cast<int64_t>(tj) * 4 + (rbl - 8);
-        if (DBG & 32) rb = rbl < 8 ? rbl : rbl - 8;
+        const int64_t rb = rbl < 8 ? static_cast<int64_t>(bi) * 8 + rbl : static_cast<int64_t>(tj) * 4 + (rbl - 8);
         piece_off[i] = (((rb * n_steps + step0) * PLANES + piece) * 64) * 16;
     }
     const unsigned char* lane_base = reinterpret_cast<const unsigned char*>(planes) + lane * 16;
     const int my_dmas = wave < kFullWaves ? kPerWave : kPerWave - 1;
     auto dma = [&](int s) __attribute__((always_inline)) {
-        if ((DBG & 1) && s >= NBUF) return;
         unsigned char* dst = lds + (s % NBUF) * kStage + wave * kFragBytes;
 #pragma unroll
         for (int i = 0; i < kPerWave; ++i) {
@@ -514,9 +485,9 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
         }
     };
 
-    f32x16 acc[MB][2], acc2[MB][2];
+    f32x16 acc[2][2], acc2[2][2];
 #pragma unroll
-    for (int m = 0; m < MB; ++m)
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -525,71 +496,39 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
                 acc2[m][n][e] = 0.0f;
             }
 
-    auto read_frags = [&](int s, frags_t& f, auto mask_c) __attribute__((always_inline)) {
+    auto read_frags = [&](int s, Frags& f, auto mask_c) __attribute__((always_inline)) {
         constexpr unsigned MASK = decltype(mask_c)::value;     // only the fragments a live block multiplies
-        if ((DBG & 8) && s > 0) return;
-        const unsigned char* A = lds + (s % NBUF) * kStage + (MB * wr) * kRbBytes + lane * 16;
+        const unsigned char* A = lds + (s % NBUF) * kStage + (2 * wr) * kRbBytes + lane * 16;
         const unsigned char* B = lds + (s % NBUF) * kStage + (8 + 2 * wc) * kRbBytes + lane * 16;
 #pragma unroll
         for (int p = 0; p < PLANES; ++p) {
 #pragma unroll
-            for (int m = 0; m < MB; ++m)
+            for (int m = 0; m < 2; ++m)
                 if (((MASK >> (m * 2)) & 3u) != 0) f.a[p][m] = *reinterpret_cast<const frag_t*>(A + m * kRbBytes + p * kFragBytes);
 #pragma unroll
             for (int n = 0; n < 2; ++n)
                 if (((MASK >> n) & 5u) != 0) f.b[p][n] = *reinterpret_cast<const frag_t*>(B + n * kRbBytes + p * kFragBytes);
         }
     };
-    // TERMS of the split product, smallest first, term-major over the accumulators (bf16x3: the order of gram.hip's split mode)
-    auto mfma_term = [&](const frags_t& f, int t, int m, int n) __attribute__((always_inline)) {
-        if constexpr (PLANES == 3) {
-            // h h' + h m' + m h' + m m' + h l' + l h'
-            constexpr int pa[6] = {2, 0, 1, 1, 0, 0};
-            constexpr int pb[6] = {0, 2, 1, 0, 1, 0};
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[pa[t]][m], f.b[pb[t]][n], acc[m][n], 0, 0, 0);
-        } else {
-            constexpr int pa[3] = {1, 0, 0};   // m h' + h m' + h h'
-            constexpr int pb[3] = {0, 1, 0};
-            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[pa[t]][m], f.b[pb[t]][n], acc[m][n], 0, 0, 0);
-        }
-    };
-    constexpr int kTerms = PLANES == 3 ? 6 : 3;
-    auto multiply = [&](const frags_t& f, auto mask_c) __attribute__((always_inline)) {
+    // the six terms of the split product, smallest first, term-major over the accumulators (the order of gram.hip's split
+    // mode): h h' + h m' + m h' + m m' + h l' + l h'
+    auto multiply = [&](const Frags& f, auto mask_c) __attribute__((always_inline)) {
         constexpr unsigned MASK = decltype(mask_c)::value;
+        constexpr int pa[6] = {2, 0, 1, 1, 0, 0};
+        constexpr int pb[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
-        for (int t = 0; t < kTerms; ++t)
+        for (int t = 0; t < 6; ++t)
 #pragma unroll
-            for (int m = 0; m < MB; ++m)
+            for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
-                    if (((MASK >> (m * 2 + n)) & 1u) != 0) mfma_term(f, t, m, n);   // folds: the loops are unrolled
+                    if (((MASK >> (m * 2 + n)) & 1u) != 0)   // folds: the loops are unrolled
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[pa[t]][m], f.b[pb[t]][n], acc[m][n], 0, 0, 0);
     };
-    // this wave's level-1 sums of chunk `c` -> chunk_sums (slab `sel` of workgroup tile t_list; element (i, j) where the fp64
-    // slab has it); only the blocks somebody reads
-    auto store_chunk = [&](int c, auto mask_c) __attribute__((always_inline)) {
-        constexpr unsigned MASK = decltype(mask_c)::value;
-        const int sel = (wr * MB) / 4;
-        // The addresses are formed HERE, from values the compiler cannot see through: hoisted out of the K loop they cost 52
-        // registers and 248 bytes of scratch per lane in the hot loop (256 VGPRs against 204).
-        int lane_o = lane, c_o = c;
-        asm volatile("" : "+v"(lane_o));
-        asm volatile("" : "+s"(c_o));
-        float* out = chunk_sums + ((static_cast<int64_t>(c_o) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab) +
-                     (row_in_slab + 4 * (lane_o >> 5)) * kSlab + wc * 64 + (lane_o & 31);
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                if (((MASK >> (m * 2 + n)) & 1u) == 0) continue;
-#pragma unroll
-                for (int e = 0; e < 16; ++e)      // element (i, j): i = row_in_slab + 32 m + (e & 3) + 8 (e >> 2) + 4 (lane >> 5), j = 64 wc + 32 n + (lane & 31)
-                    out[(m * 32 + (e & 3) + 8 * (e >> 2)) * kSlab + n * 32] = acc2[m][n][e];
-            }
-    };
-    auto flush = [&](int s, auto mask_c) __attribute__((always_inline)) {
+    auto flush = [&](int s) __attribute__((always_inline)) {
         if ((s + 1) % kFlushSteps == 0) {
 #pragma unroll
-            for (int m = 0; m < MB; ++m)
+            for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -597,28 +536,13 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
                         acc2[m][n][e] += acc[m][n][e];
                         acc[m][n][e] = 0.0f;
                     }
-            if constexpr (DEFER) {
-                // a chunk of the span ends here and another follows (the span's last chunk leaves in the epilogue)
-                if ((s + 1) % kChunkSteps == 0 && s + 1 < n_stages) {
-                    store_chunk(chunk + (s + 1) / kChunkSteps - 1, mask_c);
-#pragma unroll
-                    for (int m = 0; m < MB; ++m)
-#pragma unroll
-                        for (int n = 0; n < 2; ++n)
-#pragma unroll
-                            for (int e = 0; e < 16; ++e) acc2[m][n][e] = 0.0f;
-                    // stores count in vmcnt like the DMA's loads, and the counted waits of the ring assume that whatever is
-                    // outstanding returns in issue order: nothing of either kind stays in flight across the boundary
-                    wait_vmcnt<0>();
-                }
-            }
         }
     };
     // one stage: multiply `cur` (stage s, in registers), read stage s + 1 into `next`, keep the DMA kLead stages ahead
-    auto steady = [&](int s, const frags_t& cur, frags_t& next, auto mask_c) __attribute__((always_inline)) {
+    auto steady = [&](int s, const Frags& cur, Frags& next, auto mask_c) __attribute__((always_inline)) {
         constexpr bool kLive = decltype(mask_c)::value != 0;
         dma(s + kLead);                       // into the buffer of stage s, whose last readers passed the previous barrier
-        if (kLive && !(DBG & 2)) {
+        if (kLive) {
             read_frags(s + 1, next, mask_c);
             multiply(cur, mask_c);
         }
@@ -626,14 +550,13 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
         // outstanding (memory reads return in order, so that is a vmcnt bound)
         if (kFullWaves == NW || wave < kFullWaves) wait_vmcnt<(kLead - 2) * kPerWave>();
         else wait_vmcnt<(kLead - 2) * (kPerWave - 1)>();
-        if (DBG & 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kLive) flush(s, mask_c);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (kLive) flush(s);
     };
-    auto drain = [&](int s, const frags_t& cur, frags_t& next, auto mask_c) __attribute__((always_inline)) {
+    auto drain = [&](int s, const Frags& cur, Frags& next, auto mask_c) __attribute__((always_inline)) {
         constexpr bool kLive = decltype(mask_c)::value != 0;
         if (s + kLead < n_stages) dma(s + kLead);
-        if (kLive && !(DBG & 2)) {
+        if (kLive) {
             if (s + 1 < n_stages) read_frags(s + 1, next, mask_c);
             multiply(cur, mask_c);
         }
@@ -641,7 +564,7 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
         const int ahead = last - (s + 2);
         wait_vmcnt_dyn((ahead > 0 ? ahead : 0) * my_dmas);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kLive) flush(s, mask_c);
+        if (kLive) flush(s);
     };
 
     for (int a = 0; a < kLead && a < n_stages; ++a) dma(a);
@@ -652,8 +575,8 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
     asm volatile("s_barrier" ::: "memory");
     auto k_loop = [&](auto mask_c) __attribute__((always_inline)) {
         constexpr bool kLive = decltype(mask_c)::value != 0;
-        frags_t x, y;
-        if (kLive && !(DBG & 2) && n_stages > 0) read_frags(0, x, mask_c);
+        Frags x, y;
+        if (kLive && n_stages > 0) read_frags(0, x, mask_c);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // everybody has read stage 0: its buffer may be refilled
         int s = 0;
         for (; s + 1 + kLead < n_stages; s += 2) {
@@ -675,34 +598,6 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
     }
     auto block_live = [&](int m, int n) __attribute__((always_inline)) { return ((live_blocks >> (m * 2 + n)) & 1u) != 0; };
 
-    if constexpr (DEFER) {
-        // this chunk's level-1 sums, as they are: slab `sel` of workgroup tile t_list, chunk `chunk`; element (i, j) where the
-        // fp64 slab has it.  A chunk whose last MFMA chain has not been flushed (n_stages not a multiple of kFlushSteps: only
-        // the ragged last chunk of the matrix) leaves that chain's sums next to them.
-        if (live_wave) {
-            const int sel = (wr * MB) / 4;
-            const bool unflushed = (n_stages % kFlushSteps) != 0;
-            const int last_chunk = chunk + (n_stages - 1) / kChunkSteps;
-            float* out = chunk_sums + ((static_cast<int64_t>(last_chunk) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab);
-            float* rag = ragged_sums + (static_cast<int64_t>(t_list) * 2 + sel) * (kSlab * kSlab);
-#pragma unroll
-            for (int m = 0; m < MB; ++m)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    if (!block_live(m, n)) continue;
-                    const int j = wc * 64 + n * 32 + (lane & 31);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int i = row_in_slab + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                        out[i * kSlab + j] = acc2[m][n][e];
-                        if (unflushed) rag[i * kSlab + j] = acc[m][n][e];
-                    }
-                }
-        }
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
     // epilogue: chunks of a tile add into its slabs in chunk order (gram.hip's ticket protocol)
     bool lost = false;
     if (chunk > 0) {
@@ -723,33 +618,20 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
         // ... and must not be papered over: without the ticket the slab is not ours to update (the host turns the
         // status word into BYZ_E_HIP)
         if (tid == 0) atomicOr(device_status, kStatusLostTicket);
-    } else if (live_wave && (DBG & 16)) {
-        float all = 0.0f;   // keeps the accumulators alive without the slab traffic
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) all += acc[m][n][e] + acc2[m][n][e];
-        if (all == 1.2345e38f) partial[tid] = all;
     } else if (live_wave) {
         const bool slab_live = chunk > 0 || slab_live0 != 0;
         double* out = partial + (static_cast<int64_t>(ti) * (ti + 1) / 2 + tj) * (kSlab * kSlab);
-        const double* un = PLANES == 2 ? unscale + static_cast<int64_t>(chunk) * rows_pad : nullptr;
 #pragma unroll
-        for (int m = 0; m < MB; ++m)
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 if (!block_live(m, n)) continue;     // nobody reads this block of the slab
                 const int j = wc * 64 + n * 32 + (lane & 31);
-                double uj = 1.0;
-                if constexpr (PLANES == 2) uj = un[static_cast<int64_t>(tj) * kSlab + j];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int i = row_in_slab + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                     double v = static_cast<double>(acc2[m][n][e]);
                     v += static_cast<double>(acc[m][n][e]);
-                    if constexpr (PLANES == 2) v *= un[static_cast<int64_t>(ti) * kSlab + i] * uj;   // powers of two: exact
                     if (slab_live) v += out[i * kSlab + j];
                     out[i * kSlab + j] = v;
                 }
@@ -766,10 +648,10 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
 }
 
 // ---- the f16x2 tile kernel on v_mfma_f32_16x16x32_f16 (round 6) ------------------------------------------------------------
-// Same workgroup tile (256 x 128), same wave tile (64 x 64), same planes, same LDS-DMA ring, same schedule of workgroups and
-// the same fp32 level-1 / fp64 slab hierarchy as gram_planes_kernel<2, ...> above -- but the matrix instruction is the
-// 16 x 16 x 32 one: per MAC it reads and writes HALF the accumulator registers and twice the operand registers of the
-// 32 x 32 x 16 form, and at the socket's power cap (which is what bounds this kernel: EXPERIMENTS.md G6) that is worth 12-14 % of
+// Same workgroup tile (256 x 128), same wave tile (64 x 64), same plane images, same LDS-DMA ring and the same fp32 level-1 /
+// fp64 slab hierarchy as gram_planes_kernel above -- but on fp16 planes, and the matrix instruction is the 16 x 16 x 32 one:
+// per MAC it reads and writes HALF the accumulator registers and twice the operand registers of the 32 x 32 x 16 form
+// (round 5's f16x2 kernel, 6.6 % slower at N = 4000: EXPERIMENTS.md G7), and at the socket's power cap (which is what bounds this kernel: EXPERIMENTS.md G6) that is worth 12-14 % of
 // MFMA throughput on random fp16 data (scripts/ubench/mfma_shapes.hip: 1430 -> 1610 TF with the operands re-read from LDS every
 // step, 1580 -> 1800 TF with them in registers; on all-zero data, where nothing is power-bound, the two shapes tie).
 //
@@ -784,47 +666,43 @@ __global__ __launch_bounds__(64 * 16 / MB, 1) void gram_planes_kernel(const u32x
 // 16 + 16).  The B side is walked in two halves of 32 columns: the first half's 24 MFMAs cover the reads of the second half's
 // B fragments, the second half's 24 MFMAs cover the reads of the NEXT super-stage's A and first-half B fragments.  One
 // workgroup barrier per super-stage (half as many as the 16-column form).
+//
+// DEFER (round 5): a chunk does not read-modify-write its tile's fp64 slabs (512 KB through the fabric per workgroup and
+// chunk, behind a ticket, with the matrix pipe idle: 8 % of the kernel, EXPERIMENTS.md G3) but WRITES its level-1 sums as they
+// are -- fp32, 128 KB, no read, no ticket -- into `chunk_sums`; chunk_reduce_kernel adds them into the slabs afterwards, in
+// chunk order, in the same fp64 operations: the Gram is bitwise the same.  DEFER = false is the fallback where the sums do
+// not fit beside the matrix.
 template <int NBUF, bool DEFER>
 __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __restrict__ planes, int64_t n_steps,
                                                             const double* __restrict__ unscale, int64_t rows_pad,
                                                             double* __restrict__ partial, int n_tiles,
                                                             const int2* __restrict__ tile_order, int n_chunks,
-                                                            int* __restrict__ tickets, int round_size, int t128,
+                                                            int* __restrict__ tickets, int round_size, int run, int t128,
                                                             int slab_live0, int n_blocks32,
                                                             int32_t* __restrict__ device_status,
                                                             float* __restrict__ chunk_sums,
-                                                            float* __restrict__ ragged_sums, int kspan, int pin, int map_round) {
+                                                            float* __restrict__ ragged_sums) {
     constexpr int PLANES = 2;
     constexpr int kRbBytes = PLANES * kFragBytes;           // one 32-row block, one stage: [plane][1 KiB]
     constexpr int kStage = kRowBlocks * kRbBytes;           // 24,576
     constexpr int NW = 8;
     constexpr int kPerWave = kRowBlocks * PLANES / NW;      // 3 DMA instructions per wave and stage
     constexpr int kSuperFlush = kFlushSteps / 2;            // super-stages per 256-column MFMA chain
-    constexpr int kSuperChunk = kChunkSteps / 2;            // super-stages per 8192-column chunk
     static_assert(kRowBlocks * PLANES % NW == 0 && NBUF == 6, "ring arithmetic below");
     typedef f16x8 frag_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [NBUF][12 row blocks][2 planes][1 KiB]
 
-    // workgroup -> (tile, span of chunks): exactly gram_planes_kernel's mapping
+    // workgroup -> (chunk, tile) unit: the units of the launch form ONE sequence, chunk-major, cut into runs of `run` units, and
+    // every round of an XCD CLAIMS the next run from one counter as it gets there -- `run` CONSECUTIVE tiles of the list on (but
+    // for one round in n_tiles / run) ONE chunk, so with the list in bands of four 256-row blocks a round touches 16 row blocks
+    // of 128: the fewest 32 tiles of 256 x 128 can.  The XCDs of one chip do not run at one speed: an XCD whose rounds held the
+    // cheaper diagonal tiles takes more runs, and the launch ends with every XCD busy (EXPERIMENTS.md G8).
     const int xcd = blockIdx.x & 7;
     const int seq = blockIdx.x >> 3;
-    const int base = n_tiles >> 3, rem = n_tiles & 7;
-    const int mine = base + (xcd < rem ? 1 : 0);
-    const int first = xcd * base + (xcd < rem ? xcd : rem);
-    const int n_spans = DEFER ? (n_chunks + kspan - 1) / kspan : n_chunks;
-    // map_round > 0 (round 6, the default): the (span, tile) units of the launch form ONE sequence, span-major, and the XCDs take
-    // its runs of `map_round` units in turn -- every round of an XCD is `map_round` CONSECUTIVE tiles of the list on (but for one
-    // round in n_tiles / map_round) ONE chunk, so with the list in bands of four 256-row blocks a round touches 16 row blocks of
-    // 128: the fewest 32 tiles of 256 x 128 can.  (map_round == 0: gram_planes_kernel's mapping -- a contiguous share of the tile
-    // list per XCD, whose rounds straddle two chunks nearly always.)
-    // (map_round < 0: rounds of -map_round units CLAIMED from one counter as the XCDs get to them instead of dealt in turn: an XCD
-    // whose rounds held the cheaper diagonal tiles takes more of them, and the launch ends with every XCD busy.)
-    int span = mine > 0 ? seq / mine : n_spans;
-    int t_in_share = seq - span * mine;
-    const int mr = map_round < 0 ? -map_round : map_round;
     int* done = tickets + n_tiles + xcd;
     __shared__ int claimed_round;
     {
+        // rounds: a workgroup starts only when every workgroup of the earlier rounds of its XCD has finished (gram.hip)
         const int round = round_size > 0 ? seq / round_size : 0;
         if (round > 0 && threadIdx.x == 0) {
             unsigned spins = 0;
@@ -833,9 +711,9 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                 if (++spins > (1u << 20)) break;   // only speed depends on the gate
             }
         }
-        if (map_round < 0 && threadIdx.x == 0) {
-            // the first workgroup of this XCD's round `seq / mr` to get here claims the next run of units for all of them
-            int* slot = tickets + n_tiles + 9 + xcd * static_cast<int>(gridDim.x / (8u * static_cast<unsigned>(mr))) + seq / mr;
+        if (threadIdx.x == 0) {
+            // the first workgroup of this XCD's round `seq / run` to get here claims the next run of units for all of them
+            int* slot = tickets + n_tiles + 9 + xcd * static_cast<int>(gridDim.x / (8u * static_cast<unsigned>(run))) + seq / run;
             int v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (v == 0) {
                 int expected = 0;
@@ -853,19 +731,16 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
             claimed_round = v - 1;
         }
         __syncthreads();
-        if (mr > 0) {
-            const int round_global = map_round < 0 ? claimed_round : (seq / mr) * 8 + xcd;
-            const int unit = round_global * mr + seq % mr;
-            span = unit / n_tiles;
-            t_in_share = unit - span * n_tiles - first;
-        }
-        if (span >= n_spans) {
-            if (threadIdx.x == 0) __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
     }
-    const int chunk = DEFER ? span * kspan : span;
-    const int t_list = first + t_in_share;
+    // (integer division runs on the vector ALU: readfirstlane keeps the unit's numbers in scalar registers -- left in vector
+    // registers they live through the K loop and push it from 251 / 254 VGPRs to 256 and a spill)
+    const int unit = __builtin_amdgcn_readfirstlane(claimed_round * run + seq % run);
+    const int chunk = __builtin_amdgcn_readfirstlane(unit / n_tiles);
+    if (chunk >= n_chunks) {   // a spare round: every unit was claimed before it got here
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const int t_list = unit - chunk * n_tiles;
     const int2 tt = tile_order[t_list];
     const int bi = __builtin_amdgcn_readfirstlane(tt.x);   // 256-row block of the A side
     const int tj = __builtin_amdgcn_readfirstlane(tt.y);   // 128-row block of the B side
@@ -893,10 +768,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
 
     const int step0 = chunk * kChunkSteps;
     int n_stages = static_cast<int>(n_steps) - step0;       // even: n_steps counts whole 32-column pairs, chunks are even
-    {
-        const int span_steps = DEFER ? kspan * kChunkSteps : kChunkSteps;
-        if (n_stages > span_steps) n_stages = span_steps;
-    }
+    if (n_stages > kChunkSteps) n_stages = kChunkSteps;
     const int n_super = n_stages / 2;
 
     // LDS-DMA: piece q = wave + 8 i of a stage (row block q / 2, plane q % 2)
@@ -975,25 +847,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                     if (((MASK >> ((m / 2) * 2 + HALF)) & 1u) != 0)
                         acc[m][2 * HALF + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.v[pa[t]][m], b.v[pb[t]][n], acc[m][2 * HALF + n], 0, 0, 0);
     };
-    // element (i, j) of the wave's sub-tile that acc[m][n][e] holds: i = 16 m + 4 (lane >> 4) + e, j = 16 n + (lane & 15)
-    auto store_chunk = [&](int c, auto mask_c) __attribute__((always_inline)) {
-        constexpr unsigned MASK = decltype(mask_c)::value;
-        const int sel = wr / 2;
-        int lane_o = lane, c_o = c;
-        asm volatile("" : "+v"(lane_o));      // (the addresses are formed here, not hoisted out of the K loop)
-        asm volatile("" : "+s"(c_o));
-        float* out = chunk_sums + ((static_cast<int64_t>(c_o) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab) +
-                     (row_in_slab + 4 * (lane_o >> 4)) * kSlab + wc * 64 + (lane_o & 15);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                if (((MASK >> ((m / 2) * 2 + n / 2)) & 1u) == 0) continue;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) out[(16 * m + e) * kSlab + 16 * n] = acc2[m][n][e];
-            }
-    };
-    auto flush = [&](int sp, auto mask_c) __attribute__((always_inline)) {
+    auto flush = [&](int sp) __attribute__((always_inline)) {
         if ((sp + 1) % kSuperFlush == 0) {
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -1004,18 +858,6 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                         acc2[m][n][e] += acc[m][n][e];
                         acc[m][n][e] = 0.0f;
                     }
-            if constexpr (DEFER) {
-                if ((sp + 1) % kSuperChunk == 0 && sp + 1 < n_super) {   // a chunk of the span ends here and another follows
-                    store_chunk(chunk + (sp + 1) / kSuperChunk - 1, mask_c);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-#pragma unroll
-                        for (int n = 0; n < 4; ++n)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc2[m][n][e] = 0.0f;
-                    wait_vmcnt<0>();   // stores count in vmcnt like the ring's loads: nothing of either kind crosses the boundary
-                }
-            }
         }
     };
 
@@ -1060,14 +902,14 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                     if ((MASK & 5u) != 0) read_b(sp + 1, 0, b0, mask_c);
                 }
                 if ((MASK & 10u) != 0) multiply_half(a, b1, h1, mask_c);
-                flush(sp, mask_c);
+                flush(sp);
             }
         };
         // The steady state of a FULL wave (all sixteen blocks live, both stages of super-stage sp + 3 still to be requested) with its
-        // instructions in a PINNED order (BYZ_GRAM_PIN=0: the compiler's): behind the barrier six groups of {one DMA piece, two
-        // fragment reads of super-stage sp + 1, four MFMAs of this super-stage's second half}.  Left to itself hipcc issues the
-        // six DMA pieces and the twelve reads first -- both waves of every SIMD at once, right behind the barrier, with the
-        // matrix pipe idle -- and the 24 MFMAs behind them (same box: 45.6 -> 42.3 ms per launch at N = 4000, bitwise).
+        // instructions in a PINNED order: behind the barrier six groups of {one DMA piece, two fragment reads of super-stage
+        // sp + 1, four MFMAs of this super-stage's second half}.  Left to itself hipcc issues the six DMA pieces and the twelve
+        // reads first -- both waves of every SIMD at once, right behind the barrier, with the matrix pipe idle -- and the 24
+        // MFMAs behind them (45.6 -> 42.3 ms per launch at N = 4000, bitwise: EXPERIMENTS.md G7).
         // (Three other pinned orders -- the four MFMAs in front of the DMA piece, twelve groups of {two MFMAs, a DMA piece every
         // other group, one read}, the first half pinned as well -- were alternated on one box: 41.3 .. 41.8 ms, all four:
         // profiles/r06o_gram_pin_orders_ab.txt.  What pays is that the DMA pieces and the reads are spread AT ALL.)
@@ -1125,43 +967,29 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                     for (int n = 2; n < 4; ++n)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc2[m][n][e] += acc[m][n][e];
-                if constexpr (DEFER) {
-                    if ((sp + 1) % kSuperChunk == 0) {        // a chunk of the span ends here and another follows (steady state)
-                        store_chunk(chunk + (sp + 1) / kSuperChunk - 1, mask_c);
-#pragma unroll
-                        for (int m = 0; m < 4; ++m)
-#pragma unroll
-                            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) acc2[m][n][e] = 0.0f;
-                        wait_vmcnt<0>();
-                    }
-                }
             }
         };
         int sp = 0;
         if constexpr (MASK == 15u) {
-            if (pin != 0) {
-                bool any = false;
-                for (; 2 * (sp + 7) + NBUF + 1 < n_stages && sp + 8 < n_super; sp += 8) {
-                    super8(sp + 0, a0, a1, std::integral_constant<int, 0>{});
-                    super8(sp + 1, a1, a0, std::integral_constant<int, 1>{});
-                    super8(sp + 2, a0, a1, std::integral_constant<int, 2>{});
-                    super8(sp + 3, a1, a0, std::integral_constant<int, 3>{});
-                    super8(sp + 4, a0, a1, std::integral_constant<int, 4>{});
-                    super8(sp + 5, a1, a0, std::integral_constant<int, 5>{});
-                    super8(sp + 6, a0, a1, std::integral_constant<int, 6>{});
-                    super8(sp + 7, a1, a0, std::integral_constant<int, 7>{});
-                    any = true;
-                }
-                if (any) {     // the trips leave the accumulators as the last chain left them: what follows starts from zero
+            bool any = false;
+            for (; 2 * (sp + 7) + NBUF + 1 < n_stages && sp + 8 < n_super; sp += 8) {
+                super8(sp + 0, a0, a1, std::integral_constant<int, 0>{});
+                super8(sp + 1, a1, a0, std::integral_constant<int, 1>{});
+                super8(sp + 2, a0, a1, std::integral_constant<int, 2>{});
+                super8(sp + 3, a1, a0, std::integral_constant<int, 3>{});
+                super8(sp + 4, a0, a1, std::integral_constant<int, 4>{});
+                super8(sp + 5, a1, a0, std::integral_constant<int, 5>{});
+                super8(sp + 6, a0, a1, std::integral_constant<int, 6>{});
+                super8(sp + 7, a1, a0, std::integral_constant<int, 7>{});
+                any = true;
+            }
+            if (any) {     // the trips leave the accumulators as the last chain left them: what follows starts from zero
 #pragma unroll
-                    for (int m = 0; m < 4; ++m)
+                for (int m = 0; m < 4; ++m)
 #pragma unroll
-                        for (int n = 0; n < 4; ++n)
+                    for (int n = 0; n < 4; ++n)
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[m][n][e] = 0.0f;
-                }
+                        for (int e = 0; e < 4; ++e) acc[m][n][e] = 0.0f;
             }
         }
         for (; sp + 1 < n_super; sp += 2) {
@@ -1180,11 +1008,14 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
     auto block_live = [&](int m, int n) __attribute__((always_inline)) { return ((live_blocks >> ((m / 2) * 2 + n / 2)) & 1u) != 0; };
 
     if constexpr (DEFER) {
+        // this chunk's level-1 sums, as they are: slab `sel` of workgroup tile t_list; element (i, j) where the fp64 slab has
+        // it.  A chunk whose last MFMA chain has not been flushed (n_super not a multiple of kSuperFlush: only the ragged last
+        // chunk of the matrix) leaves that chain's sums in `ragged_sums`, for chunk_reduce_kernel to add as the in-kernel
+        // update does: (double) level-1 + (double) chain.
         if (live_wave) {
             const int sel = wr / 2;
             const bool unflushed = (n_super % kSuperFlush) != 0;
-            const int last_chunk = chunk + (n_stages - 1) / kChunkSteps;
-            float* out = chunk_sums + ((static_cast<int64_t>(last_chunk) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab);
+            float* out = chunk_sums + ((static_cast<int64_t>(chunk) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab);
             float* rag = ragged_sums + (static_cast<int64_t>(t_list) * 2 + sel) * (kSlab * kSlab);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -1337,16 +1168,13 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     const int64_t t128 = ceil_div(n_rows, kSlab);
     const int64_t t256 = ceil_div(t128, 2);
     const int64_t rows_pad = t256 * kWgRows;
-    // BYZ_GRAM_MFMA=32: the f16x2 tile kernel on v_mfma_f32_32x32x16_f16 (rounds 2-5; the same-box A/B) instead of 16x16x32
-    const bool shape16 = f16 && env_int("BYZ_GRAM_MFMA", 16) != 32;
-    // The tile list.  BYZ_GRAM_ORDER=1 (the 16x16x32 kernel's default): bands of four 256-row blocks, inside a band column block
-    // by column block -- ANY 32 consecutive tiles are (4 or 5) x (8 or 9) tiles on at most ~17 row blocks of 128, and the kernel
-    // hands out runs of 32 consecutive (chunk, tile) units to the XCDs in turn.  BYZ_GRAM_ORDER=0 (rounds 2-5, and the other
-    // kernels): 8 x 8 super-blocks of slabs = 4 x 8 workgroup tiles, a contiguous share of the list per XCD -- the rounds of an XCD
-    // then straddle two chunks and two or three super-blocks: 106 GB through the fabric per 1M-column launch at N = 4000 if every
-    // line were shared perfectly inside a round, against 70 GB for the bands (scripts/gram_order_footprint.py; EXPERIMENTS.md G8).
-    const int order_mode = shape16 && env_int("BYZ_GRAM_ORDER", 1) != 0 ? 1 : 0;
-    const int64_t order_key = static_cast<int64_t>(order_mode) * (1ll << 40) + share_count * 65536 + share_index;
+    // The tile list.  f16x2: bands of four 256-row blocks, inside a band column block by column block -- ANY 32 consecutive
+    // tiles are (4 or 5) x (8 or 9) tiles on at most ~17 row blocks of 128, and the kernel hands out runs of consecutive
+    // (chunk, tile) units to the XCDs.  bf16x3: 8 x 8 super-blocks of slabs = 4 x 8 workgroup tiles, a contiguous share of the
+    // list per XCD (the rounds of an XCD then straddle two chunks and two or three super-blocks: 106 GB through the fabric per
+    // 1M-column launch at N = 4000 if every line were shared perfectly inside a round, against 70 GB for the bands;
+    // scripts/gram_order_footprint.py, EXPERIMENTS.md G8).  The key tells the two lists apart: one engine may alternate.
+    const int64_t order_key = static_cast<int64_t>(f16 ? 1 : 0) * (1ll << 40) + share_count * 65536 + share_index;
     if (ctx->plane_order_T != t128 || ctx->plane_order_share != order_key) {
         ctx->plane_order_host.clear();
         int64_t position = 0;
@@ -1355,7 +1183,7 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
             ctx->plane_order_host.push_back(static_cast<int32_t>(bi));
             ctx->plane_order_host.push_back(static_cast<int32_t>(tj));
         };
-        if (order_mode == 1) {
+        if (f16) {
             // (the bands cut into column panels of 16 / 24 / 32 / 40 slabs, so that at N = 10,000 -- a chunk of planes is 335 MB --
             // the rounds in flight stay inside the 256 MB Infinity Cache: measured, 91.7 -> 91.5 ms per launch: nothing; removed)
             for (int64_t b0 = 0; b0 < t256; b0 += 4)
@@ -1404,43 +1232,14 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     chunks_per_sc = ceil_div(chunks_total, n_sc);
     const int64_t sc_cols = chunks_per_sc * kChunkCols;
     BYZ_TRY(ctx->gram_planes.ensure(static_cast<size_t>(rows_pad) * 2 * n_planes * sc_cols));
-    BYZ_TRY(ctx->gram_tickets.ensure(static_cast<size_t>(n_tiles + 8) * sizeof(int)));
     double* unscale = nullptr;
     if (f16) {
         BYZ_TRY(ctx->plane_unscale.ensure(static_cast<size_t>(rows_pad) * chunks_per_sc * sizeof(double)));
         unscale = ctx->plane_unscale.as<double>();
     }
-    int* tickets = ctx->gram_tickets.as<int>();
     u32x4* planes = ctx->gram_planes.as<u32x4>();
-    typedef void (*kernel_t)(const u32x4*, int64_t, const double*, int64_t, double*, int, const int2*, int, int*, int, int,
-                             int, int, int32_t*, float*, float*, int, int, int);
-    // BYZ_GRAM_DEFER=0: round 4's in-kernel slab update (the same-box A/B and the bitwise comparison of the tests)
+    // BYZ_GRAM_DEFER=0: round 4's in-kernel slab update (the bitwise comparison of the tests)
     bool defer = f16 && env_int("BYZ_GRAM_DEFER", 1) != 0;
-    kernel_t kernel = !f16 ? &gram_planes_kernel<3, 4, 0>
-                      : shape16 ? (defer ? &gram_planes16_kernel<6, true> : &gram_planes16_kernel<6, false>)
-                                : (defer ? &gram_planes_kernel<2, 6, 0, 2, true> : &gram_planes_kernel<2, 6, 0>);
-    int nbuf = f16 ? 6 : 4;
-    const int threads = kThreads;
-#ifdef BYZ_GRAM_DEBUG_VARIANTS
-    // Timing experiments with WRONG results (the DBG bits of the kernel, times ten; scripts/gram_ab.py, EXPERIMENTS.md G1-G3).
-    // Not compiled into the shipped library: build with -DBYZ_GRAM_DEBUG_VARIANTS to get them back.
-    {
-        const int variant = env_int("BYZ_GRAM_PLANES_VARIANT", 0);
-        if (variant != 0) defer = false;
-        if (f16) {
-            kernel = variant == 10 ? &gram_planes_kernel<2, 6, 1> : variant == 20 ? &gram_planes_kernel<2, 6, 2>
-                     : variant == 50 ? &gram_planes_kernel<2, 6, 5>      // no DMA, no barrier
-                     : variant == 90 ? &gram_planes_kernel<2, 6, 9>      // no DMA, no LDS reads
-                     : variant == 130 ? &gram_planes_kernel<2, 6, 13>    // the MFMAs, the loop and the slab update only
-                     : variant == 160 ? &gram_planes_kernel<2, 6, 16>    // everything but the slab update
-                     : variant == 340 ? &gram_planes_kernel<2, 6, 34>    // DMA only, every workgroup the same tile
-                     : variant == 320 ? &gram_planes_kernel<2, 6, 32>    // everything, every workgroup the same tile
-                                      : kernel;
-        } else {
-            kernel = variant == 10 ? &gram_planes_kernel<3, 4, 1> : variant == 20 ? &gram_planes_kernel<3, 4, 2> : kernel;
-        }
-    }
-#endif
     float* chunk_sums = nullptr;
     float* ragged_sums = nullptr;
     if (defer) {
@@ -1451,10 +1250,7 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
         const size_t want = per_chunk * static_cast<size_t>(chunks_per_sc + 1);
         size_t free_now = 0, total_now = 0;
         BYZ_HIP(hipMemGetInfo(&free_now, &total_now));
-        if (want > ctx->gram_chunk_sums.bytes && want - ctx->gram_chunk_sums.bytes > free_now / 2) {
-            defer = false;
-            kernel = shape16 ? &gram_planes16_kernel<6, false> : &gram_planes_kernel<2, 6, 0>;
-        }
+        if (want > ctx->gram_chunk_sums.bytes && want - ctx->gram_chunk_sums.bytes > free_now / 2) defer = false;
     }
     if (defer) {
         const size_t per_chunk = static_cast<size_t>(n_tiles) * 2 * kSlab * kSlab * sizeof(float);
@@ -1462,9 +1258,13 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
         chunk_sums = ctx->gram_chunk_sums.as<float>();
         ragged_sums = chunk_sums + (per_chunk / sizeof(float)) * static_cast<size_t>(chunks_per_sc);
     }
-    const size_t lds_bytes = static_cast<size_t>(nbuf) * kRowBlocks * n_planes * kFragBytes;
-    BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), static_cast<int>(lds_bytes)));
+    auto kernel16 = defer ? &gram_planes16_kernel<6, true> : &gram_planes16_kernel<6, false>;
+    const void* kernel = f16 ? reinterpret_cast<const void*>(kernel16) : reinterpret_cast<const void*>(&gram_planes_kernel<4>);
+    const size_t lds_bytes = static_cast<size_t>(f16 ? 6 : 4) * kRowBlocks * n_planes * kFragBytes;
+    BYZ_HIP(allow_dynamic_lds(ctx, kernel, static_cast<int>(lds_bytes)));
     const int round_size = env_int("BYZ_GRAM_ROUND", ctx->num_cus / 8);   // one workgroup per CU
+    // f16x2: runs of whole rounds (one workgroup per CU of an XCD), claimed by the XCDs as they get to them
+    const int run = round_size > 0 ? round_size : ctx->num_cus / 8;
     const int n_blocks32 = env_int("BYZ_GRAM_BLOCK_SKIP", 1) != 0 ? static_cast<int>(ceil_div(n_rows, 32)) : -1;
     const int64_t per_xcd = ceil_div(n_tiles, 8);
     for (int64_t sc = 0; sc < n_sc; ++sc) {
@@ -1502,47 +1302,37 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
             BYZ_TRY(check_launch("plane_split_kernel"));
         }
         {
-            // chunks per workgroup (DEFER only): BYZ_GRAM_KSPAN as given, else kDefaultSpan -- but never so many that the launch
-            // has fewer than ~8 workgroups per CU (the tail of the last round would cost more than the turnover saves)
-            int64_t kspan = 1;
-            if (defer) {
-                kspan = env_int("BYZ_GRAM_KSPAN", 0);
-                if (kspan > n_chunks) kspan = n_chunks;   // (a span longer than the launch is the launch; keeps span x steps inside an int)
-                if (kspan < 1) {
-                    kspan = kDefaultSpan;
-                    while (kspan > 1 && 8 * per_xcd * ceil_div(n_chunks, kspan) < static_cast<int64_t>(ctx->num_cus) * 8) kspan /= 2;
-                }
+            // f16x2: every XCD is launched the same number of rounds, kSpareRoundsPercent more than its share; a faster XCD
+            // claims more runs and the surplus rounds of the others find nothing left and leave at once
+            int64_t rounds_per_xcd = 0;
+            if (f16) {
+                rounds_per_xcd = ceil_div(ceil_div(n_tiles * n_chunks, run), 8);
+                rounds_per_xcd += rounds_per_xcd * kSpareRoundsPercent / 100;
             }
-            // (order_mode 1: whole rounds of `map_round` units, dealt to the XCDs in turn)
-            const int run = order_mode == 1 ? (round_size > 0 ? round_size : ctx->num_cus / 8) : 0;
-            const int64_t n_units = n_tiles * ceil_div(n_chunks, kspan);
-            int64_t rounds_per_xcd = run > 0 ? ceil_div(ceil_div(n_units, run), 8) : 0;
-            // BYZ_GRAM_SPARE: spare rounds per XCD, in percent (default 10).  Every XCD is launched the same number of rounds; with
-            // claims and a few rounds to spare a faster XCD takes more runs and the surplus rounds of the others find nothing left
-            // and leave at once (same box: 37.57 -> 37.30 ms per launch at N = 4000, 92.1 -> 90.9 at N = 10,000; 100 %: 37.87)
-            if (run > 0) rounds_per_xcd += rounds_per_xcd * env_int("BYZ_GRAM_SPARE", 10) / 100;
-            const int64_t grid = run > 0 ? 8 * run * rounds_per_xcd : 8 * per_xcd * ceil_div(n_chunks, kspan);
-            // BYZ_GRAM_CLAIM=0: the XCDs take the runs in turn; default: every round of an XCD CLAIMS the next run from one counter.
-            // The XCDs of one chip do not run at one speed: dealt in turn, the launch waits for its slowest XCD with the others
-            // idle (same box, N = 4000: 41.4 -> 39.1 ms per launch; N = 10,000: 100.8 -> 98.6; profiles/r06w_*)
-            const bool claim = run > 0 && env_int("BYZ_GRAM_CLAIM", 1) != 0;
-            const int map_round = claim ? -run : run;
+            const int64_t grid = f16 ? 8 * run * rounds_per_xcd : 8 * per_xcd * n_chunks;
             // tickets: [n_tiles] chunk order of a tile (in-kernel update), [8] workgroups done per XCD, [1] runs claimed,
             // [8][rounds_per_xcd] the run each round of an XCD claimed (+ 1; 0: not yet)
             const size_t ticket_ints = static_cast<size_t>(n_tiles + 9 + 8 * rounds_per_xcd);
             BYZ_TRY(ctx->gram_tickets.ensure(ticket_ints * sizeof(int)));
-            tickets = ctx->gram_tickets.as<int>();
+            int* tickets = ctx->gram_tickets.as<int>();
             BYZ_HIP(hipMemsetAsync(tickets, 0, ticket_ints * sizeof(int), stream));
             KernelTimer t(ctx, BYZ_K_GRAM, stream);
             if (grid > 0x7fffffff) {
                 set_error("gram: grid too large");
                 return BYZ_E_UNSUPPORTED;
             }
-            kernel<<<static_cast<unsigned>(grid), threads, lds_bytes, stream>>>(
-                planes, n_steps, unscale, rows_pad, slabs, static_cast<int>(n_tiles), ctx->plane_order.as<int2>(),
-                static_cast<int>(n_chunks), tickets, round_size, static_cast<int>(t128), sc > 0 ? 1 : 0,
-                n_blocks32, device_status_word(ctx), chunk_sums, ragged_sums, static_cast<int>(kspan), env_int("BYZ_GRAM_PIN", 1),
-                map_round);
+            const int2* tile_order = ctx->plane_order.as<int2>();
+            const int slab_live0 = sc > 0 ? 1 : 0;
+            if (!f16) {
+                gram_planes_kernel<4><<<static_cast<unsigned>(grid), kThreads, lds_bytes, stream>>>(
+                    planes, n_steps, slabs, static_cast<int>(n_tiles), tile_order, static_cast<int>(n_chunks), tickets,
+                    round_size, static_cast<int>(t128), slab_live0, n_blocks32, device_status_word(ctx));
+            } else {
+                kernel16<<<static_cast<unsigned>(grid), kThreads, lds_bytes, stream>>>(
+                    planes, n_steps, unscale, rows_pad, slabs, static_cast<int>(n_tiles), tile_order, static_cast<int>(n_chunks),
+                    tickets, round_size, run, static_cast<int>(t128), slab_live0, n_blocks32, device_status_word(ctx),
+                    chunk_sums, ragged_sums);
+            }
             BYZ_TRY(check_launch("gram_planes_kernel"));
         }
         if (defer) {

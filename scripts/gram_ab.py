@@ -2,7 +2,7 @@
 alternated, and whether the Gram is bitwise the first setting's.
 
     python scripts/gram_ab.py BYZ_GRAM_BLOCK_SKIP=0,BYZ_GRAM_BLOCK_SKIP=1 4000 262224
-    python scripts/gram_ab.py 0,20 ...          a bare number is a BYZ_GRAM_PLANES_VARIANT (needs a -DBYZ_GRAM_DEBUG_VARIANTS build)
+    python scripts/gram_ab.py BYZ_GRAM_DEFER=1:r0,BYZ_GRAM_DEFER=0:r0 ...   a ":r0" suffix runs the setting without the round gate
 """
 import os
 import sys
@@ -14,7 +14,7 @@ from attacking_federate_learning_amd.engine import Engine   # noqa: E402
 
 
 def main():
-    variants = sys.argv[1].split(',') if len(sys.argv) > 1 else ['0', '2']
+    variants = sys.argv[1].split(',') if len(sys.argv) > 1 else ['BYZ_GRAM_DEFER=1', 'BYZ_GRAM_DEFER=0']
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 4000
     d = int(sys.argv[3]) if len(sys.argv) > 3 else 262144 + 80
     kind = sys.argv[4] if len(sys.argv) > 4 else 'normal'   # zeros / ones: how much of the time is the DATA (switching power)
@@ -35,12 +35,9 @@ def main():
     ref = None
     for rep in range(2):
         for v in variants:
-            opts = v.split(':')                                           # "0:r0" = variant 0 without the round gate
-            if '=' in opts[0]:
-                key, val = opts[0].split('=', 1)
-                os.environ[key] = val
-            else:
-                os.environ['BYZ_GRAM_PLANES_VARIANT'] = opts[0]
+            opts = v.split(':')                                           # "KEY=VALUE:r0": the setting without the round gate
+            key, val = opts[0].split('=', 1)
+            os.environ[key] = val
             os.environ['BYZ_GRAM_ROUND'] = '0' if 'r0' in opts[1:] else '32'
             res = eng.gram(buf)
             eng.check()
