@@ -44,7 +44,7 @@ __device__ __forceinline__ float from_ordered_bits(uint32_t o) {
 __device__ __forceinline__ int visit_position(int u) { return u == 0 ? 1 : (u == 1 ? 0 : u); }
 
 // (defined with the Bulyan re-score below; row_sort_kernel's Krum score uses it too)
-__device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex)[8], float s, int lane, unsigned long long& n_passes);
+__device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex)[8], float s, int lane);
 
 // ---- the row sort's bitonic network, register-blocked (round 6) ----------------------------------------------------------
 // The textbook form below (one compare-exchange level per pass over LDS, a barrier behind each) takes log2(n)(log2(n) + 1) / 2
@@ -268,7 +268,6 @@ __global__ void row_sort_kernel(const float* __restrict__ dist, int n, int n_pad
         }
         bool odd = false;   // a negative value, or -0.0: the passes take non-negative distances
         for (int r = lane; r < head_n; r += 64) odd = odd || (from_ordered_bits(static_cast<uint32_t>(keys[r] >> 32)) < 0.0f);
-        unsigned long long n_passes = 0;
         for (int r0 = 512; r0 < prefix_len && __ballot(odd) == 0ull; r0 += 512) {
             uint32_t M[8];
             int ex[8];
@@ -282,7 +281,7 @@ __global__ void row_sort_kernel(const float* __restrict__ dist, int n, int n_pad
                 M[j] = e != 0u ? ((xb & 0x7fffffu) | 0x800000u) : (xb & 0x7fffffu);
             }
             if (__ballot(odd) == 0ull) {
-                s = integer_passes(M, ex, s, lane, n_passes);
+                s = integer_passes(M, ex, s, lane);
             }
         }
         if (__ballot(odd) != 0ull || !(__builtin_fabsf(s) <= 3.4028234663852886e38f)) {
@@ -658,12 +657,13 @@ __device__ __forceinline__ bool gather_granule_pair(const unsigned long long* sl
 // (zeros for removed columns and past the prefix: adding +0.0 is exact) go to LDS in order, and every lane of the wave adds
 // them up left to right from broadcast reads -- the reference's loop, literally.
 //
-// Since round 3 this is the COMPARISON (BYZ_BULYAN_RESCORE=plain) and the fallback for rows the integer passes refuse (a
-// sign bit on a live entry); the default re-score is reference_score_marked below.  Two earlier attempts to beat this form
-// were measured, selections identical in every case (profiles/r02q .. r02t, r03a, r03k): round 2's integer rule per 64
-// entries with every chunk that held a tie or a binade crossing falling back to a 63-step DPP chain, and a version per 512
-// entries with a checkpoint behind every row's first 512 entries: 260 / 234 ms at N = 10,000 against this form's 253.  What
-// they lacked is what the passes below have: ties and crossings handled INSIDE the parallel pass, and no staging at all.
+// Since round 3 this is only the fallback for rows the integer passes refuse (a sign bit on a live entry); the re-score is
+// reference_score_marked below (tests/golden/rescore_chain.npz holds this form's selections from when every re-score could take
+// it).  Two earlier attempts to beat this form were measured, selections identical in every case (profiles/r02q .. r02t, r03a,
+// r03k): round 2's integer rule per 64 entries with every chunk that held a tie or a binade crossing falling back to a 63-step DPP
+// chain, and a version per 512 entries with a checkpoint behind every row's first 512 entries: 260 / 234 ms at N = 10,000 against
+// this form's 253.  What they lacked is what the passes below have: ties and crossings handled INSIDE the parallel pass, and no
+// staging at all.
 __device__ __forceinline__ float reference_score_plain(const float* __restrict__ sorted_val, const uint16_t* __restrict__ sorted_idx,
                                                        const uint32_t* removed, int n, int u, int take, int lane,
                                                        float* __restrict__ stage) {
@@ -778,14 +778,13 @@ __device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {   // inclusive, 
 // a = floor(x / q) in the high word and the remainder, left-aligned, in the low word -- above half a unit iff it exceeds
 // 0x80000000, a tie iff it equals it.  Lanes without a tie (nearly all) have their increment at once, and its parity is
 // their "xor"; only lanes that hold a tie walk their eight entries under both incoming parities.
-__device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex)[8], float s, int lane, unsigned long long& n_passes) {
+__device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex)[8], float s, int lane) {
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (;;) {
         // (s is the same in every lane; saying so keeps the pass's bookkeeping on the scalar unit and its branches uniform)
         const uint32_t sbits = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(s))));
         const int e0 = static_cast<int>(sbits >> 23);
         if (e0 >= 255) break;   // inf / NaN: it stays what it is as far as "< 1e20" goes
-        ++n_passes;
         const int es = e0 != 0 ? e0 : 1;
         const uint32_t I = e0 != 0 ? ((sbits & 0x7fffffu) | 0x800000u) : (sbits & 0x7fffffu);
         uint32_t a[8], y[8];
@@ -878,8 +877,9 @@ __device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex
     return s;
 }
 
-// development aid (BYZ_BULYAN_CLOCKS=1): re-scores, their batches, integer passes and cycles
-__device__ unsigned long long g_rescore_clock[14];
+// 64-entry chunks of a re-score that go through the literal chain before the passes take over (measured, N = 4000 / 10,000
+// scaled / 10,000 attack: 1 chunk 32.7 / 163 / 95.7 ms, 4 chunks 30.9 / 158 / 95.8, 8 chunks 30.4 / 157 / 94.1)
+constexpr int kHeadChunks = 8;
 
 // One wave; wave-uniform result; `ok` = false when the row holds a negative value (the passes assume distances: the caller
 // then takes the literal chain).  `head`: 512 floats of LDS for the literal chain over the first entries.
@@ -890,16 +890,13 @@ __device__ unsigned long long g_rescore_clock[14];
 // EXTRA (the speculative loop, bulyan_spec_kernel): `egone` is a bitmap over the POSITIONS of this row's table (LDS, the wave's own;
 // bit p set: the entry at position p is gone although the table does not say so yet -- the winners of the earlier picks of a batch that
 // is still being verified).  A lane's eight entries start at a multiple of eight: one byte of it.
-template <bool CLOCKS, bool EXTRA = false>
+template <bool EXTRA = false>
 __device__ __forceinline__ float reference_score_marked(const float* sorted_val, int n, int u, int take, int lane,
-                                                        float* __restrict__ head, int head_chunks, bool& ok,
-                                                        uint16_t* __restrict__ front, const uint8_t* __restrict__ egone = nullptr) {
-    constexpr bool clocks = CLOCKS;   // (development: a compile-time switch -- what is compiled into this loop costs even when it never runs)
+                                                        float* __restrict__ head, bool& ok, uint16_t* __restrict__ front,
+                                                        const uint8_t* __restrict__ egone = nullptr) {
     typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const uint32_t* vals = reinterpret_cast<const uint32_t*>(sorted_val + static_cast<int64_t>(u) * n);
-    const unsigned long long c_begin = clocks ? __builtin_readcyclecounter() : 0ull;
-    unsigned long long n_passes = 0, n_batches = 0, c_passes = 0;
     struct Batch {
         uint32_t x[8];
     };
@@ -911,9 +908,9 @@ __device__ __forceinline__ float reference_score_marked(const float* sorted_val,
         b.x[4] = hi.x, b.x[5] = hi.y, b.x[6] = hi.z, b.x[7] = hi.w;
     };
     float s = 0.0f;
-    int got = 0, literal_left = head_chunks;
+    int got = 0, literal_left = kHeadChunks;
     bool negative = false;
-    const int first_batch = front != nullptr ? __builtin_amdgcn_readfirstlane(static_cast<int>(*front)) : 0;   // (uniform)
+    const int first_batch = __builtin_amdgcn_readfirstlane(static_cast<int>(*front));   // (uniform)
     int empty_in_front = first_batch;   // batches known to hold only marks once this re-score is done
     bool in_front = true;
     // returns true behind the last batch of the prefix
@@ -940,7 +937,6 @@ __device__ __forceinline__ float reference_score_marked(const float* sorted_val,
         if (total == 0) {
             // nothing live in these 512 entries: the winners of the picks so far are every row's NEAREST neighbours, so late in the
             // loop the front of the table is one run of marks -- up to ten such batches at N = 10,000 -- and there is nothing to add
-            ++n_batches;
             if (in_front) ++empty_in_front;
             return r0 + 512 >= n;
         }
@@ -1002,11 +998,8 @@ __device__ __forceinline__ float reference_score_marked(const float* sorted_val,
                 M[j] = e != 0u ? ((xb[j] & 0x7fffffu) | 0x800000u) : xb[j];
                 if (8 * lane + j < start) M[j] = 0u;
             }
-            const unsigned long long c0 = clocks ? __builtin_readcyclecounter() : 0ull;
-            s = integer_passes(M, ex, s, lane, n_passes);
-            if (clocks) c_passes += __builtin_readcyclecounter() - c0;
+            s = integer_passes(M, ex, s, lane);
         }
-        ++n_batches;
         return got >= take || r0 + 512 >= n;
     };
     Batch b0, b1, b2;
@@ -1023,14 +1016,7 @@ __device__ __forceinline__ float reference_score_marked(const float* sorted_val,
         fetch(b2, r0 + 5 * 512);
     }
     ok = __ballot(negative) == 0ull;
-    if (front != nullptr && lane == 0) *front = static_cast<uint16_t>(empty_in_front);
-    if (clocks && lane == 0) {
-        atomicAdd(&g_rescore_clock[0], 1ull);
-        atomicAdd(&g_rescore_clock[1], n_batches);
-        atomicAdd(&g_rescore_clock[2], n_passes);
-        atomicAdd(&g_rescore_clock[3], __builtin_readcyclecounter() - c_begin);
-        atomicAdd(&g_rescore_clock[4], c_passes);
-    }
+    if (lane == 0) *front = static_cast<uint16_t>(empty_in_front);
     return s;
 }
 
@@ -1040,15 +1026,87 @@ struct GridDecision {
     double threshold;
 };
 
+// The prefix the reference sums at pick t: sorted(...)[: users_count - t - f] of the n - t - 1 live entries.
+__device__ __forceinline__ int take_at(int t, int n, int users_count, int corrupted) {
+    const int live_entries = n - t - 1;
+    const int keep = users_count - t - corrupted;
+    return keep >= 0 ? (keep < live_entries ? keep : live_entries) : (live_entries + keep > 0 ? live_entries + keep : 0);
+}
+
+// Every row whose exact score lies at or below this may be the reference's winner of a pick whose smallest score rounds down
+// to m1: the rigorous band 2.2 delta, delta = u (take + 1) / 2, above the largest double that rounds down to m1.  Part of the
+// parity proof, and the same bits in both loops: the band is rounded after its product and again after its
+// sum, the threshold once, by a fused multiply-add.
+__device__ __forceinline__ double band_threshold(float m1, int take) {
+#pragma clang fp contract(off)
+    const double u24 = 5.9604644775390625e-08;
+    const double band = 1.1 * u24 * static_cast<double>(take + 1) + 1e-9;
+    const double ub = double_above(m1);
+    return fma(fabs(ub), take <= 1 ? 1e-12 : band, ub);
+}
+
+// Row u's place in the speculative loop: T (its distances to the rows still present), Top (the `drop` largest of them), its live
+// non-finite distances, and the boundary of its `drop` largest in sorted_idx -- step 4 of bulyan_grid_kernel, whose own copy stays
+// inline (measured: 1.10 against 1.15 - 1.29 ms for the loop at N = 700 through this struct).  Plain registers: a batch snapshots
+// and restores the whole struct (no padding: a copied padding byte would live in memory).
+struct BulyanRow {
+    double tot, top;
+    int u, bad, ptr, alive;
+
+    // the row's sums from the row sort, and the mark of its own diagonal in the table of ascending values
+    __device__ __forceinline__ void init(int row, int n, int drop, const double* __restrict__ row_total, const double* __restrict__ row_top,
+                                         const uint16_t* __restrict__ rank_t, float* sorted_val) {
+        u = row;
+        alive = u < n;
+        tot = alive ? row_total[u] : 0.0;
+        top = (alive && drop > 0) ? row_top[u] : 0.0;
+        bad = alive ? static_cast<int>(row_top[n + u]) : 0;   // live non-finite distances of this row
+        ptr = n - 1 - drop;
+        if (alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(u) * n + u]] = __uint_as_float(kGoneBits);
+    }
+
+    // Winner w leaves the row in O(1) through the rank table (`removed` already has w's bit).  Its mark in the table of ascending
+    // values waits for the batch's commit.
+    __device__ __forceinline__ void remove(int w, int n, int drop, const float* __restrict__ dist, const uint16_t* __restrict__ sorted_idx,
+                                           const uint16_t* __restrict__ rank_t, const uint32_t* removed) {
+        if (!alive) return;
+        if (u == w) {
+            alive = 0;
+            return;
+        }
+        const float dwf = dist[static_cast<int64_t>(w) * n + u];   // symmetric: d[w][u] == d[u][w]
+        const bool dw_finite = __builtin_fabsf(dwf) <= 3.4028234663852886e38f;
+        const double dw = dw_finite ? static_cast<double>(dwf) : 0.0;
+        if (!dw_finite) --bad;
+        const int r = rank_t[static_cast<int64_t>(w) * n + u];                          // rank of column w inside row u
+        tot -= dw;
+        if (drop > 0 && r >= ptr) {
+            // w was one of this row's `drop` largest: the largest survivor below the boundary joins them
+            top -= dw;
+            int p = ptr - 1;
+            const uint16_t* order = sorted_idx + static_cast<int64_t>(u) * n;
+            while (p >= 0) {
+                const int col = order[p];
+                if (!((removed[col >> 5] >> (col & 31)) & 1u)) break;
+                --p;
+            }
+            if (p >= 0) {
+                const float joins = dist[static_cast<int64_t>(u) * n + order[p]];
+                if (__builtin_fabsf(joins) <= 3.4028234663852886e38f) top += static_cast<double>(joins);
+            }
+            ptr = p;
+        }
+    }
+};
+
 // (Round 4's exact incremental re-score -- a contender re-scored from a record of its previous chain, rows near the band kept
 // scored -- was built, measured and REMOVED in round 5: EXPERIMENTS.md S2.)
-template <bool DEV>
 __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
     const float* __restrict__ dist, int n, int theta, int drop, int users_count, int corrupted,
     const uint16_t* __restrict__ sorted_idx, const uint16_t* __restrict__ rank_t, float* sorted_val,
     const double* __restrict__ row_total, const double* __restrict__ row_top, const int32_t* __restrict__ cls,
-    unsigned long long* __restrict__ xchg, float band_scale, int32_t* __restrict__ selection,
-    int32_t* __restrict__ status, int32_t* __restrict__ rescored, int rescore_mode, int head_chunks, int skip_front) {
+    unsigned long long* __restrict__ xchg, int32_t* __restrict__ selection, int32_t* __restrict__ status,
+    int32_t* __restrict__ rescored) {
     __shared__ __attribute__((aligned(16))) float rescore_stage[kGridThreads / 64][512];
     __shared__ Candidate slots[kGridThreads / 64];
     __shared__ double second_slots[kGridThreads / 64];
@@ -1064,23 +1122,17 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
     for (int i = tid; i < kMaxSelectRows / 32; i += kGridThreads) removed[i] = 0u;
     front_batches[tid] = 0;
 
+    // (BulyanRow holds the same state for the speculative loop; here it stays inline, see there)
     bool alive = u < n;
     double tot = alive ? row_total[u] : 0.0;
     double top = (alive && drop > 0) ? row_top[u] : 0.0;
     int bad = alive ? static_cast<int>(row_top[n + u]) : 0;   // live non-finite distances of this row
     int ptr = n - 1 - drop;
+    // the table of ascending values carries the removals (-0.0); first of all the row's own diagonal
+    if (alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(u) * n + u]] = __uint_as_float(kGoneBits);
     const int my_class = alive ? cls[u] : 0;
     const int my_pos = visit_position(u);
     int n_rescored = 0;
-    // rescore_mode >= 1: the table of ascending values carries the removals (-0.0); first of all the row's own diagonal
-    const bool marked = rescore_mode >= 1;
-    if (marked && alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(u) * n + u]] = __uint_as_float(kGoneBits);
-    auto take_at = [&](int t) __attribute__((always_inline)) -> int {
-        // the prefix the reference sums at pick t: sorted(...)[: users_count - t - f] of the n - t - 1 live entries
-        const int live_entries = n - t - 1;
-        const int keep = users_count - t - corrupted;
-        return keep >= 0 ? (keep < live_entries ? keep : live_entries) : (live_entries + keep > 0 ? live_entries + keep : 0);
-    };
     __syncthreads();
 
     // exchange slots: [parity][kind A, B, R][workgroup]
@@ -1094,7 +1146,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
         const uint32_t tag = static_cast<uint32_t>((t >> 1) & 7) + 1u;
         const uint32_t tag18 = static_cast<uint32_t>(t + 1);
         const int parity = t & 1;
-        const int take = take_at(t);
+        const int take = take_at(t, n, users_count, corrupted);
         // ---- 1. the workgroup's best row, and its best score outside that row's twin class
         const double score = tot - top;
         // (a non-finite distance inside the summed prefix makes the reference's score inf / NaN: never below 1e20)
@@ -1146,13 +1198,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
                 d.mode = 2;
             } else {
                 // every row whose exact score lies within the band of the smallest one may be the reference's winner
-                // band_scale >= 0: the rigorous bound 2.2 delta, delta = u (m + 1) / 2 (x band_scale);
-                // band_scale <  0: |band_scale| u sqrt(m + 1), the random-walk size of the same error (not a bound)
-                const double u24 = 5.9604644775390625e-08;
-                const double band = (band_scale >= 0.0f ? static_cast<double>(band_scale) * 1.1 * u24 * static_cast<double>(take + 1)
-                                                        : -static_cast<double>(band_scale) * u24 * sqrt(static_cast<double>(take + 1))) + 1e-9;
-                const double ub = double_above(m1);
-                const double thr = ub + fabs(ub) * (take <= 1 ? 1e-12 : band);
+                const double thr = band_threshold(m1, take);
                 d.threshold = thr;
                 const bool in_a = static_cast<double>(a) <= thr;
                 const bool in_b = static_cast<double>(b) <= thr;
@@ -1194,14 +1240,12 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
             __syncthreads();
             const int n_lead = n_leaders;
             for (int k = wave; k < n_lead; k += kGridThreads / 64) {
-                const int row = __builtin_amdgcn_readfirstlane(wg * kGridThreads + leaders[k]);
-                float s32 = 0.0f;
+                const int v = __builtin_amdgcn_readfirstlane(wg * kGridThreads + leaders[k]);
                 bool done = false;
-                if (marked) s32 = reference_score_marked<DEV>(sorted_val, n, row, take, lane, rescore_stage[wave], head_chunks, done,
-                                                              skip_front != 0 ? &front_batches[leaders[k]] : nullptr);
-                if (!done) s32 = reference_score_plain(sorted_val, sorted_idx, removed, n, row, take, lane, rescore_stage[wave]);
+                float s32 = reference_score_marked(sorted_val, n, v, take, lane, rescore_stage[wave], done, &front_batches[leaders[k]]);
+                if (!done) s32 = reference_score_plain(sorted_val, sorted_idx, removed, n, v, take, lane, rescore_stage[wave]);
                 if (s32 < kKrumInit) {
-                    Candidate o{static_cast<double>(s32), visit_position(row), row};
+                    Candidate o{static_cast<double>(s32), visit_position(v), v};
                     if (better(o, r)) r = o;
                 }
             }
@@ -1257,7 +1301,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
                 const double dw = dw_finite ? static_cast<double>(dwf) : 0.0;
                 if (!dw_finite) --bad;
                 const int r = rank_t[static_cast<int64_t>(w) * n + u];                          // rank of column w inside row u
-                if (marked) sorted_val[static_cast<int64_t>(u) * n + r] = __uint_as_float(kGoneBits);
+                sorted_val[static_cast<int64_t>(u) * n + r] = __uint_as_float(kGoneBits);
                 tot -= dw;
                 if (drop > 0 && r >= ptr) {
                     // w was one of this row's `drop` largest: the largest survivor below the boundary joins them
@@ -1371,11 +1415,6 @@ __global__ __launch_bounds__(kGridThreads) void spec_owner_kernel(const double* 
     owner[wg * kGridThreads + local] = u;
 }
 
-__global__ __launch_bounds__(kGridThreads) void spec_identity_kernel(int n, int32_t* __restrict__ owner) {
-    const int u = blockIdx.x * kGridThreads + threadIdx.x;
-    if (u < n) owner[u] = u;
-}
-
 struct SpecVerdict {
     int k_bad;      // first pick of the batch whose optimistic winner is not the reference's (-1: none)
     int winner;     // the reference's winner there (-1: no row scores below 1e20)
@@ -1389,9 +1428,8 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
     const float* __restrict__ dist, int n, int theta, int drop, int users_count, int corrupted,
     const uint16_t* __restrict__ sorted_idx, const uint16_t* __restrict__ rank_t, float* sorted_val,
     const double* __restrict__ row_total, const double* __restrict__ row_top, const int32_t* __restrict__ cls,
-    unsigned long long* __restrict__ xchg, float band_scale, int32_t* __restrict__ selection,
-    int32_t* __restrict__ status, int32_t* __restrict__ rescored, int head_chunks, int skip_front, int batch_picks,
-    int32_t* __restrict__ spec_stats, const int32_t* __restrict__ owner) {
+    unsigned long long* __restrict__ xchg, int32_t* __restrict__ selection, int32_t* __restrict__ status,
+    int32_t* __restrict__ rescored, int batch_picks, const int32_t* __restrict__ owner) {
     __shared__ __attribute__((aligned(16))) float rescore_stage[kSpecThreads / 64][512];
     __shared__ Candidate slots[kSpecThreads / 64];
     __shared__ double second_slots[kSpecThreads / 64];
@@ -1420,20 +1458,11 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
     }
     if (tid < kGridThreads) front_batches[tid] = 0;
 
-    bool alive = u < n;
-    double tot = alive ? row_total[u] : 0.0;
-    double top = (alive && drop > 0) ? row_top[u] : 0.0;
-    int bad = alive ? static_cast<int>(row_top[n + u]) : 0;   // live non-finite distances of this row
-    int ptr = n - 1 - drop;
-    const int my_class = alive ? cls[u] : 0;
+    BulyanRow row;
+    row.init(u, n, drop, row_total, row_top, rank_t, sorted_val);
+    const int my_class = row.alive ? cls[u] : 0;
     const int my_pos = visit_position(u);
-    int n_rescored = 0, n_batches = 0, n_rollbacks = 0, n_wasted = 0;
-    if (alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(u) * n + u]] = __uint_as_float(kGoneBits);
-    auto take_at = [&](int t) __attribute__((always_inline)) -> int {
-        const int live_entries = n - t - 1;
-        const int keep = users_count - t - corrupted;
-        return keep >= 0 ? (keep < live_entries ? keep : live_entries) : (live_entries + keep > 0 ? live_entries + keep : 0);
-    };
+    int n_rescored = 0;
     __syncthreads();
 
     // exchange slots: [parity][kind A, B, (R of bulyan_grid_kernel: unused)][workgroup], then [parity][pick of the batch][workgroup]
@@ -1441,37 +1470,11 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
     auto batch_slot = [&](int parity, int k) { return xchg + (6 + parity * kSpecMax + k) * kGridMaxWgs; };
     const unsigned long long none_a = (static_cast<unsigned long long>(kInfBits) << 32) | (static_cast<unsigned long long>(kNoRow) << 18);
 
-    // step 4 of bulyan_grid_kernel without the mark: the winner leaves every row's sums
+    // step 4 of bulyan_grid_kernel: the winner leaves every row's sums
     auto remove_winner = [&](int w) __attribute__((always_inline)) {
         if (tid == 0) removed[w >> 5] |= 1u << (w & 31);
         __syncthreads();
-        if (alive) {
-            if (u == w) {
-                alive = false;
-            } else {
-                const float dwf = dist[static_cast<int64_t>(w) * n + u];   // symmetric: d[w][u] == d[u][w]
-                const bool dw_finite = __builtin_fabsf(dwf) <= 3.4028234663852886e38f;
-                const double dw = dw_finite ? static_cast<double>(dwf) : 0.0;
-                if (!dw_finite) --bad;
-                const int r = rank_t[static_cast<int64_t>(w) * n + u];                          // rank of column w inside row u
-                tot -= dw;
-                if (drop > 0 && r >= ptr) {
-                    top -= dw;
-                    int p = ptr - 1;
-                    const uint16_t* order = sorted_idx + static_cast<int64_t>(u) * n;
-                    while (p >= 0) {
-                        const int col = order[p];
-                        if (!((removed[col >> 5] >> (col & 31)) & 1u)) break;
-                        --p;
-                    }
-                    if (p >= 0) {
-                        const float joins = dist[static_cast<int64_t>(u) * n + order[p]];
-                        if (__builtin_fabsf(joins) <= 3.4028234663852886e38f) top += static_cast<double>(joins);
-                    }
-                    ptr = p;
-                }
-            }
-        }
+        row.remove(w, n, drop, dist, sorted_idx, rank_t, removed);
     };
 
     int result = (n < 2 && theta > 0) ? 1 : 0;
@@ -1480,9 +1483,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
     uint32_t batch_seq = 0;  // batches verified so far
     while (t < theta && result == 0) {
         // ---- the batch's start: every row's snapshot
-        const bool s_alive = alive;
-        const double s_tot = tot, s_top = top;
-        const int s_bad = bad, s_ptr = ptr;
+        const BulyanRow snapshot = row;
         const int t0 = t;
         const int kmax = theta - t0 < batch_picks ? theta - t0 : batch_picks;
         uint32_t cmask = 0;       // picks of this batch at which this row is a contender
@@ -1493,10 +1494,10 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
             const uint32_t tag = ((seq >> 1) & 7u) + 1u;
             const uint32_t tag18 = (seq + 1u) & 0x3ffffu;
             const int parity = static_cast<int>(seq & 1u);
-            const int take = take_at(tt);
+            const int take = take_at(tt, n, users_count, corrupted);
             // ---- 1. the workgroup's best row, and its best score outside that row's twin class (bulyan_grid_kernel)
-            const double score = tot - top;
-            const bool candidate = alive && bad <= drop && score < static_cast<double>(kKrumInit);   // false for NaN
+            const double score = row.tot - row.top;
+            const bool candidate = row.alive && row.bad <= drop && score < static_cast<double>(kKrumInit);   // false for NaN
             Candidate c{static_cast<double>(kKrumInit), 0x7fffffff, -1, -1};
             if (candidate) c = Candidate{score, my_pos, u, my_class};
             const Candidate best = block_best(c, slots);
@@ -1543,11 +1544,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                 } else if (!(m1 < __builtin_inff())) {
                     d.mode = 2;
                 } else {
-                    const double u24 = 5.9604644775390625e-08;
-                    const double band = (band_scale >= 0.0f ? static_cast<double>(band_scale) * 1.1 * u24 * static_cast<double>(take + 1)
-                                                            : -static_cast<double>(band_scale) * u24 * sqrt(static_cast<double>(take + 1))) + 1e-9;
-                    const double ub = double_above(m1);
-                    const double thr = ub + fabs(ub) * (take <= 1 ? 1e-12 : band);
+                    const double thr = band_threshold(m1, take);
                     d.threshold = thr;
                     const bool in_a = static_cast<double>(a) <= thr;
                     const bool in_b = static_cast<double>(b) <= thr;
@@ -1618,20 +1615,19 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                 const int it = __builtin_amdgcn_readfirstlane(static_cast<int>(items[i]));
                 const int k = it >> 8;
                 const int lt = it & 255;
-                const int row = __builtin_amdgcn_readfirstlane(owner[wg * kGridThreads + lt]);
+                const int v = __builtin_amdgcn_readfirstlane(owner[wg * kGridThreads + lt]);
                 // the batch's earlier winners are gone from this row in the state of pick k: their positions, on the wave's bitmap
                 int pos_gone = -1;
                 if (lane < k) {
-                    pos_gone = rank_t[static_cast<int64_t>(winners[lane]) * n + row];
+                    pos_gone = rank_t[static_cast<int64_t>(winners[lane]) * n + v];
                     atomicOr(&my_bits[pos_gone >> 5], 1u << (pos_gone & 31));
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 bool done = false;
-                float s32 = reference_score_marked<false, true>(sorted_val, n, row, take_at(t0 + k), lane, rescore_stage[wave], head_chunks, done,
-                                                                skip_front != 0 ? &front_batches[lt] : nullptr,
-                                                                reinterpret_cast<const uint8_t*>(my_bits));
+                float s32 = reference_score_marked<true>(sorted_val, n, v, take_at(t0 + k, n, users_count, corrupted), lane, rescore_stage[wave],
+                                                         done, &front_batches[lt], reinterpret_cast<const uint8_t*>(my_bits));
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 if (pos_gone >= 0) my_bits[pos_gone >> 5] = 0u;
@@ -1648,7 +1644,8 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    s32 = reference_score_plain(sorted_val, sorted_idx, my_bits, n, row, take_at(t0 + k), lane, rescore_stage[wave]);
+                    s32 = reference_score_plain(sorted_val, sorted_idx, my_bits, n, v, take_at(t0 + k, n, users_count, corrupted), lane,
+                                                rescore_stage[wave]);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     __builtin_amdgcn_wave_barrier();
                     for (int j = lane; j < kMaxSelectRows / 32; j += 64) my_bits[j] = 0u;
@@ -1656,7 +1653,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 if (s32 < kKrumInit && lane == 0) {
-                    const Candidate o{static_cast<double>(s32), visit_position(row), row, 0};
+                    const Candidate o{static_cast<double>(s32), visit_position(v), v, 0};
                     if (better(o, wave_bests[wave][k])) wave_bests[wave][k] = o;
                 }
             }
@@ -1724,9 +1721,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
         }
         if (k_bad >= 0) {
             // ---- back to the snapshot; the picks in front of the wrong one again (their winners stand), then the reference's winner
-            ++n_rollbacks;
-            n_wasted += n_done - k_bad;
-            alive = s_alive, tot = s_tot, top = s_top, bad = s_bad, ptr = s_ptr;
+            row = snapshot;
             __syncthreads();
             if (tid == 0) {
                 for (int k = 0; k < n_done; ++k) removed[winners[k] >> 5] &= ~(1u << (winners[k] & 31));
@@ -1742,21 +1737,15 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
         for (int k = 0; k < n_done; ++k) {
             const int w = winners[k];
             if (wg == 0 && tid == 0) selection[t0 + k] = w;
-            if (alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(w) * n + u]] = __uint_as_float(kGoneBits);
+            if (row.alive) sorted_val[static_cast<int64_t>(u) * n + rank_t[static_cast<int64_t>(w) * n + u]] = __uint_as_float(kGoneBits);
         }
         t = t0 + n_done;
-        ++n_batches;
         if (pending != 0) result = 1;
         __syncthreads();   // (winners[] is rewritten by the next batch)
     }
     if (tid == 0) {
         if (result != 0) atomicMax(status, result);
         if (n_rescored) atomicAdd(rescored, n_rescored);
-        if (wg == 0 && spec_stats != nullptr) {
-            spec_stats[0] = n_batches;
-            spec_stats[1] = n_rollbacks;
-            spec_stats[2] = n_wasted;
-        }
     }
 }
 
@@ -1839,36 +1828,12 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
     BYZ_REQUIRE(dist && selection_dev && status_dev && n > 0 && theta >= 0 && theta <= n,
                 "bulyan loop: bad arguments (n=%lld theta=%lld)", (long long)n, (long long)theta);
     BYZ_TRY(ctx->twin_class.ensure(static_cast<size_t>(2 * n) * sizeof(int32_t)));
-    // granules: [2][A, B, R][64 workgroups], then the speculative loop's [2][32 picks of a batch][64], then its three counters
+    // granules: [2][A, B, R][64 workgroups], then the speculative loop's [2][32 picks of a batch][64]
     constexpr size_t kGranules = static_cast<size_t>(2 * 3 + 2 * kSpecMax) * kGridMaxWgs;
-    BYZ_TRY(ctx->xchg.ensure((kGranules + 2) * sizeof(unsigned long long)));
+    BYZ_TRY(ctx->xchg.ensure(kGranules * sizeof(unsigned long long)));
     int32_t* cls_tmp = ctx->twin_class.as<int32_t>();
     int32_t* cls = cls_tmp + n;
-    // which arithmetic decides a pick whose contenders lie within rounding of each other (see bulyan_grid_kernel):
-    //   BYZ_BULYAN_BAND unset / "rigorous"  every row that CAN beat the minimum in sequential fp32 is re-scored
-    //   BYZ_BULYAN_BAND=<x> (x > 0)          the rigorous band scaled by x; (x < 0) |x| u sqrt(m): statistical, not a bound
-    float band_scale = 1.0f;
-    if (const char* e = std::getenv("BYZ_BULYAN_BAND")) {
-        if (std::strcmp(e, "rigorous") != 0) band_scale = static_cast<float>(std::atof(e));
-    }
-    // BYZ_BULYAN_RESCORE=plain: the literal chain of additions with liveness from the bitmap (round 2: the form the C oracle
-    // was checked against); default: the marked table and the integer passes -- the same bits
-    int rescore_mode = 1;
-    if (const char* e = std::getenv("BYZ_BULYAN_RESCORE")) rescore_mode = std::strcmp(e, "plain") == 0 ? 0 : 1;
-    // 64-entry chunks of a re-score that go through the literal chain before the passes take over (measured, N = 4000 / 10,000
-    // scaled / 10,000 attack: 1 chunk 32.7 / 163 / 95.7 ms, 4 chunks 30.9 / 158 / 95.8, 8 chunks 30.4 / 157 / 94.1)
-    const int head_chunks = 8;
-    // BYZ_BULYAN_FRONT=0: every re-score starts at the row's first entry (round 5's behaviour: the same-box A/B)
-    int skip_front = 1;
-    if (const char* e = std::getenv("BYZ_BULYAN_FRONT")) skip_front = std::atoi(e) != 0 ? 1 : 0;
-    const char* clocks_env = std::getenv("BYZ_BULYAN_CLOCKS");
-    const bool clocks = rescore_mode != 0 && clocks_env != nullptr && std::atoi(clocks_env) != 0;
-    if (clocks) {
-        rescore_mode += 1;
-        const unsigned long long zero[14] = {0};
-        BYZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rescore_clock), zero, sizeof(zero)));
-    }
-    BYZ_HIP(hipMemsetAsync(ctx->xchg.ptr, 0, (kGranules + 2) * sizeof(unsigned long long), stream));
+    BYZ_HIP(hipMemsetAsync(ctx->xchg.ptr, 0, kGranules * sizeof(unsigned long long), stream));
     BYZ_HIP(hipMemsetAsync(status_dev, 0, 3 * sizeof(int32_t), stream));   // status, rows re-scored, (unused)
     KernelTimer t(ctx, BYZ_K_BULYAN_LOOP, stream);
     twin_class_kernel<<<static_cast<unsigned>(ceil_div(n, 4)), 256, 0, stream>>>(dist, (int)n, cls_tmp);
@@ -1879,8 +1844,8 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
         return launch_bulyan_loop_large(ctx, dist, n, theta, drop_count, users_count, corrupted, cls, selection_dev, status_dev, stream);
     const unsigned n_wgs = static_cast<unsigned>(ceil_div(n, kGridThreads));   // <= 64: all resident, they wait for each other
     // BYZ_BULYAN_BATCH=<k>: picks decided optimistically before their contested ones are verified together (bulyan_spec_kernel;
-    // default 32 from 1000 rows, 16 from 6000; at most 32); 0: bulyan_grid_kernel, every contested pick re-scored before the next one (rounds 2-5; also taken for
-    // BYZ_BULYAN_RESCORE=plain and BYZ_BULYAN_CLOCKS).  The same selection, pick for pick.
+    // default 32 from 1000 rows, 16 from 6000; at most 32); 0: bulyan_grid_kernel, every contested pick re-scored before the next
+    // one (rounds 2-5).  The same selection, pick for pick.
     // (measured, same box, N = 4000 / N = 10,000 on hard data: batches of 8: 15.8 / 101.0 ms, 16: 14.0 / 102.2, 24: 13.55 / 103.4, 32: 13.47 / 103.5;
     // a batch that grows behind a batch that stood and halves behind a roll-back: 13.7 / 102.6 -- not kept.  Below ~1000 rows few picks
     // are contested and the batches' bookkeeping costs more than it saves: N = 300: 0.49 -> 0.58 ms, N = 700: 1.40 -> 1.52; N = 1000: 2.18 -> 2.08)
@@ -1889,53 +1854,25 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
     int batch = n >= 6000 ? 16 : (n >= 1000 ? 32 : 0);
     if (const char* e = std::getenv("BYZ_BULYAN_BATCH")) batch = std::atoi(e);
     if (batch > kSpecMax) batch = kSpecMax;
-    if (batch >= 1 && rescore_mode == 1 && !clocks) {
-        int32_t* stats = reinterpret_cast<int32_t*>(ctx->xchg.as<unsigned long long>() + kGranules);
+    if (batch >= 1) {
         BYZ_TRY(ctx->spec_owner.ensure(static_cast<size_t>(n_wgs) * kGridThreads * sizeof(int32_t)));
         int32_t* owner = ctx->spec_owner.as<int32_t>();
         BYZ_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(owner), static_cast<int>(n), static_cast<size_t>(n_wgs) * kGridThreads, stream));
-        // BYZ_BULYAN_DEAL=0: slot (g, i) owns row 256 g + i (the comparison)
-        const char* deal_env = std::getenv("BYZ_BULYAN_DEAL");
-        if (deal_env == nullptr || std::atoi(deal_env) != 0) {
-            spec_owner_kernel<<<static_cast<unsigned>(ceil_div(n, 64)), kGridThreads, 0, stream>>>(
-                ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls, (int)n, (int)drop_count, (int)n_wgs, owner);
-        } else {
-            spec_identity_kernel<<<n_wgs, kGridThreads, 0, stream>>>((int)n, owner);
-        }
+        spec_owner_kernel<<<static_cast<unsigned>(ceil_div(n, 64)), kGridThreads, 0, stream>>>(
+            ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls, (int)n, (int)drop_count, (int)n_wgs, owner);
         BYZ_TRY(check_launch("spec_owner_kernel"));
         auto* spec = n >= 6000 ? &bulyan_spec_kernel<512> : &bulyan_spec_kernel<256>;
         spec<<<n_wgs, n >= 6000 ? 512 : 256, 0, stream>>>(
             dist, (int)n, (int)theta, (int)drop_count, (int)users_count, (int)corrupted, ctx->sorted_idx.as<uint16_t>(),
             ctx->rank_t.as<uint16_t>(), ctx->sorted_val.as<float>(), ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls,
-            ctx->xchg.as<unsigned long long>(), band_scale, selection_dev, status_dev, status_dev + 1, head_chunks, skip_front, batch, stats,
-            owner);
-        BYZ_TRY(check_launch("bulyan_spec_kernel"));
-        if (const char* e = std::getenv("BYZ_BULYAN_STATS"); e != nullptr && std::atoi(e) != 0) {
-            int32_t host[4] = {0, 0, 0, 0};
-            BYZ_HIP(hipStreamSynchronize(stream));
-            BYZ_HIP(hipMemcpy(host, stats, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
-            BYZ_HIP(hipMemcpy(host + 3, status_dev + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "bulyan (speculative, batches of %d): %d picks in %d batches, %d rolled back (%d picks decided again), %d re-scores\n",
-                         batch, (int)theta, host[0], host[1], host[2], host[3]);
-        }
-        return BYZ_OK;
+            ctx->xchg.as<unsigned long long>(), selection_dev, status_dev, status_dev + 1, batch, owner);
+        return check_launch("bulyan_spec_kernel");
     }
-    auto* kernel = clocks ? &bulyan_grid_kernel<true> : &bulyan_grid_kernel<false>;
-    kernel<<<n_wgs, kGridThreads, 0, stream>>>(
+    bulyan_grid_kernel<<<n_wgs, kGridThreads, 0, stream>>>(
         dist, (int)n, (int)theta, (int)drop_count, (int)users_count, (int)corrupted, ctx->sorted_idx.as<uint16_t>(),
         ctx->rank_t.as<uint16_t>(), ctx->sorted_val.as<float>(), ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls,
-        ctx->xchg.as<unsigned long long>(), band_scale, selection_dev, status_dev, status_dev + 1, rescore_mode, head_chunks,
-        skip_front);
-    BYZ_TRY(check_launch("bulyan_grid_kernel"));
-    if (clocks) {
-        unsigned long long c[14];
-        BYZ_HIP(hipStreamSynchronize(stream));
-        BYZ_HIP(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_rescore_clock), sizeof(c)));
-        const double r = c[0] ? static_cast<double>(c[0]) : 1.0;
-        std::fprintf(stderr, "bulyan re-scores: %llu; per re-score: %.1f batches, %.1f integer passes, %.0f cycles (%.0f inside the passes)\n",
-                     c[0], c[1] / r, c[2] / r, c[3] / r, c[4] / r);
-    }
-    return BYZ_OK;
+        ctx->xchg.as<unsigned long long>(), selection_dev, status_dev, status_dev + 1);
+    return check_launch("bulyan_grid_kernel");
 }
 
 }  // namespace byz

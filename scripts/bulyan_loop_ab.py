@@ -1,7 +1,7 @@
 """Same-box A/B of the Bulyan selection loop by environment settings (torch-free): the loop's kernel time on the distances of a
 `scaled` matrix (N x 4096), alternated, and whether the selection is the first setting's.
 
-    python scripts/bulyan_loop_ab.py 4000 BYZ_BULYAN_FRONT=0 BYZ_BULYAN_FRONT=1
+    python scripts/bulyan_loop_ab.py 4000 BYZ_BULYAN_BATCH=0 BYZ_BULYAN_BATCH=16
     ATTACK=1: the first 0.24 N rows are one vector (the attack's exact ties)
 """
 import os

@@ -7,6 +7,8 @@ oracle/scale.py (C restatement of defences.py:26-37 and :59-68, pinned against o
 tests/test_oracle_scale.py) -- the reference's own arithmetic (sequential fp32 sums), so given one distance matrix the
 indices must be IDENTICAL, not merely within a margin.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -124,15 +126,13 @@ def lattice_distances(seed, n, bits=9):
     return dist
 
 
-@pytest.mark.parametrize('n,family', [(333, 'lattice'), (1500, 'lattice'), (3000, 'lattice'), (1500, 'points'), (1500, 'ties'),
-                                      (2049, 'zeros'), (700, 'negative'), (700, 'inf'), (1500, 'nan')])
-def test_bulyan_rescore_integer_passes_are_the_literal_chain(eng, monkeypatch, n, family):
-    """The default re-score evaluates the reference's sequential fp32 sum in integer passes over a table marked with the
-    removals (csrc/select.hip); BYZ_BULYAN_RESCORE=plain is the literal chain of additions over bitmap-tested entries.
-    Same selections, pick for pick -- on round-to-even ties at every other addition (lattice), exact-zero distances
-    between live rows, a matrix with negative entries (which the passes hand back to the chain), and clients at an infinite /
-    NaN distance from everybody (non-finite gradients: they sort last and are never picked) -- and both are the C oracle's
-    (the reference's loop)."""
+CHAIN_CASES = [(333, 'lattice'), (1500, 'lattice'), (3000, 'lattice'), (1500, 'points'), (1500, 'ties'),
+               (2049, 'zeros'), (700, 'negative'), (700, 'inf'), (1500, 'nan')]
+CHAIN_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'rescore_chain.npz')
+
+
+def chain_case(n, family):
+    """The distance matrix of one re-score case (tests/golden/make_golden_rescore_chain.py mints the fixture from these)."""
     f = int(n * MAL_PROP)
     if family == 'lattice':
         dist = lattice_distances(4400 + n, n)
@@ -156,10 +156,23 @@ def test_bulyan_rescore_integer_passes_are_the_literal_chain(eng, monkeypatch, n
         dist = point_distances(4400 + n, n)
         dist[5, 9] = dist[9, 5] = -0.25
         dist[40, 41] = dist[41, 40] = -0.0
-    monkeypatch.setenv('BYZ_BULYAN_RESCORE', 'plain')
-    plain = eng.bulyan_select(dist, n, f).tolist()
-    rescored = eng.bulyan_rescored()
-    monkeypatch.delenv('BYZ_BULYAN_RESCORE')
+    return dist
+
+
+@pytest.mark.parametrize('n,family', CHAIN_CASES)
+def test_bulyan_rescore_integer_passes_are_the_literal_chain(eng, monkeypatch, n, family):
+    """The re-score evaluates the reference's sequential fp32 sum in integer passes over a table marked with the removals
+    (csrc/select.hip).  tests/golden/rescore_chain.npz holds the selection and the re-score count of the literal chain of
+    additions over bitmap-tested entries (round 2's form, minted by this library before that form was retired).  Same
+    selections, pick for pick -- on round-to-even ties at every other addition (lattice), exact-zero distances between live
+    rows, a matrix with negative entries (which the passes hand back to the chain), and clients at an infinite / NaN distance
+    from everybody (non-finite gradients: they sort last and are never picked) -- and both are the C oracle's (the
+    reference's loop)."""
+    f = int(n * MAL_PROP)
+    dist = chain_case(n, family)
+    with np.load(CHAIN_FIXTURE) as z:
+        plain = z['%d_%s/selection' % (n, family)].tolist()
+        rescored = int(z['%d_%s/rescored' % (n, family)])
     monkeypatch.setenv('BYZ_BULYAN_BATCH', '0')     # the sequential loop: the same pairs are re-scored, by the passes
     got = eng.bulyan_select(dist, n, f).tolist()
     assert eng.bulyan_rescored() == rescored
@@ -190,7 +203,6 @@ MARGIN_CEILINGS = {'c4_n4000_d4096': 110, 'long_k_n3000': 80}      # measured (r
 
 def margin_protocol(name, dist64, n, f, sel, ceiling, want=None, margins=None):
     import json
-    import os
     d32 = np.ascontiguousarray(dist64, dtype=np.float32)
     excess, margin, argmin = scale.replay_selection(d32, n, f, sel, mode='ideal')
     contested = int((margin <= TAU).sum())
@@ -523,7 +535,6 @@ def test_reserve_covers_the_small_path(eng):
 def test_near_duplicate_rows_agree_to_rounding_with_and_without_the_identical_row_shortcut(eng):
     """VERDICT r1 (weak 3): the pair (near-duplicate row, group of identical rows) is re-evaluated on the difference itself
     (defences.py:20) in both paths, so the two distance matrices agree to fp32 rounding everywhere -- no 2e-2 allowance."""
-    import os
     n, d = 700, 40000
     rng = np.random.default_rng(123)
     g = scaled(124, n, d)

@@ -141,7 +141,7 @@ def test_gpu_bulyan_is_the_references_at_large_sizes(eng, large, name, monkeypat
     torch = pytest.importorskip('torch')
     case, want = BY_NAME[name], large[name]
     n, f = case['n'], case['f']
-    for key in ('BYZ_GRAM_MODE', 'BYZ_GRAM_PLANES', 'BYZ_DEDUP', 'BYZ_BULYAN_RESCORE'):
+    for key in ('BYZ_GRAM_MODE', 'BYZ_GRAM_PLANES', 'BYZ_DEDUP'):
         monkeypatch.delenv(key, raising=False)
     host = attacked_on_the_gpu(name, large, eng)
     g = torch.from_numpy(host).cuda()
