@@ -47,10 +47,15 @@ _PROTOTYPES = {
     'byz_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_krum_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32), c_vp, c_vp],
     'byz_bulyan_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_mean_rows_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
+    'byz_multi_krum_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_multi_krum_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
     # (the byz_allreduce_f64_fn callback and its `user` word are passed as plain pointers: ALLREDUCE_F64_FN builds the callback)
     'byz_pairwise_distances_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_krum_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, _P(c_i32), c_vp],
     'byz_bulyan_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_multi_krum_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp],
     'byz_drift_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp, c_int, c_vp],
     'byz_column_chain_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_column_finish_dev': [c_vp, c_vp, c_vp, c_i64, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp],
@@ -67,6 +72,7 @@ _PROTOTYPES = {
     'byz_pairwise_distances_host': [c_vp, c_vp, c_i64, c_i64, c_vp],
     'byz_krum_select_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32)],
     'byz_drift_attack_host': [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp],
+    'byz_multi_krum_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_timing_enable': [c_vp, c_int],
     'byz_timing_reset': [c_vp],
     'byz_timing_read': [c_vp, c_int, _P(ctypes.c_double), _P(c_i64)],

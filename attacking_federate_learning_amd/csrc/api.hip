@@ -137,6 +137,37 @@ int bulyan_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_coun
     return BYZ_OK;
 }
 
+// Multi-Krum (Blanchard et al. 2017, section 4): the Krum score of every row (krum_select: defences.py:33-34, prefix users_count -
+// corrupted_count), rows ranked by (score, visit position), the first m taken.  selection_dev (optional): the m rows in ranking
+// order; ctx->multi_krum_rows: the same rows ascending, the list the row-list mean walks.
+int check_multi_krum_m(int64_t n, int64_t m) {
+    if (m < 1 || m > n) {
+        set_error("multi_krum: m = %lld outside 1..%lld (the row count)", (long long)m, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+int multi_krum_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_count, int64_t corrupted, int64_t m,
+                      int32_t* selection_dev, hipStream_t stream) {
+    BYZ_TRY(check_multi_krum_m(n, m));
+    if (n > kLargeMaxRows) {
+        set_error("selection kernels support at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    BYZ_TRY(ctx->multi_krum_rows.ensure(static_cast<size_t>(n) * sizeof(int32_t)));
+    BYZ_TRY(krum_select(ctx, dist, n, users_count, corrupted, ctx->small.as<int32_t>(), stream));
+    return launch_multi_krum_rank(ctx, n, m, selection_dev, ctx->multi_krum_rows.as<int32_t>(), stream);
+}
+
+int check_krum_assert(int check_assert, int64_t users_count, int64_t corrupted_count) {
+    if (check_assert && !(users_count >= 2 * corrupted_count + 1)) {  // defences.py:25
+        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count, (long long)corrupted_count);
+        return BYZ_E_PRECONDITION;
+    }
+    return BYZ_OK;
+}
+
 }  // namespace
 }  // namespace byz
 
@@ -220,6 +251,8 @@ void byz_ctx_destroy(byz_ctx* ctx) {
     ctx->row_total.release();
     ctx->row_top.release();
     ctx->scores.release();
+    ctx->multi_krum.release();
+    ctx->multi_krum_rows.release();
     ctx->selection.release();
     ctx->twin_class.release();
     ctx->redo_tiles.release();
@@ -523,6 +556,42 @@ int byz_bulyan_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols,
     return launch_trimmed_mean(ctx, G, theta, n_cols, ld, sel, keep, out, s);
 }
 
+// ---- Multi-Krum (Blanchard et al. 2017, section 4; beyond the reference) -----------------------------------------------------
+int byz_mean_rows_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                      int64_t count, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "mean_rows"));
+    BYZ_REQUIRE(row_index && out && count >= 1, "mean_rows: null row list or output, or count %lld < 1", (long long)count);
+    return launch_column_mean_rows(ctx, G, row_index, count, n_cols, ld, out, as_stream(stream));
+}
+
+int byz_multi_krum_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t users_count, int64_t corrupted_count,
+                              int64_t m, int32_t* selection, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && selection && n_rows > 0, "multi_krum_select: bad arguments");
+    return multi_krum_select(ctx, dist, n_rows, users_count, corrupted_count, m, selection, as_stream(stream));
+}
+
+int byz_multi_krum_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+                       int64_t corrupted_count, int64_t m, int check_assert, float* out, int32_t* selection, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "multi_krum"));
+    BYZ_REQUIRE(out, "multi_krum: null output");
+    BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
+    BYZ_TRY(check_multi_krum_m(n_rows, m));
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+    if (krum_small_applies(n_rows, n_cols)) {
+        ctx->row_map_rows = 0;
+        BYZ_TRY(launch_small_distances(ctx, G, n_rows, n_cols, ld, ctx->dist.as<float>(), s));
+    } else {
+        BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
+        BYZ_TRY(launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, ctx->dist.as<float>(), s, G, n_cols, ld));
+    }
+    BYZ_TRY(multi_krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, m, selection, s));
+    return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
+}
+
 // ---- multi-GPU, columns layout: the one exchange of the path through the host's all-reduce -------------------
 namespace {
 
@@ -623,6 +692,22 @@ int byz_bulyan_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
     // defences.py:70 on the local columns of the selected rows
     const int64_t keep = python_prefix_len(theta, theta - 2 * corrupted_count - 1);
     return launch_trimmed_mean(ctx, G, theta, n_cols, ld, sel, keep, out, s);
+}
+
+int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+                               int64_t corrupted_count, int64_t m, int check_assert, byz_allreduce_f64_fn allreduce, void* user,
+                               float* out, int32_t* selection, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "multi_krum_sharded"));
+    BYZ_REQUIRE(out && allreduce, "multi_krum_sharded: null output or null all-reduce");
+    BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
+    BYZ_TRY(check_multi_krum_m(n_rows, m));
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+    BYZ_TRY(sharded_distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+    BYZ_TRY(multi_krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, m, selection, s));
+    // the selection is the same on every rank (one all-reduced Gram); each rank averages its own columns of the selected rows
+    return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
 }
 
 int byz_drift_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,
@@ -830,6 +915,30 @@ int byz_drift_attack_host(byz_ctx* ctx, const float* rows_host, int64_t n_rows, 
     if (drift_host) BYZ_HIP(hipMemcpyAsync(drift_host, out, vec, hipMemcpyDeviceToHost, s));
     if (mean_host) BYZ_HIP(hipMemcpyAsync(mean_host, out + n_cols, vec, hipMemcpyDeviceToHost, s));
     if (std_host) BYZ_HIP(hipMemcpyAsync(std_host, out + 2 * n_cols, vec, hipMemcpyDeviceToHost, s));
+    int32_t words[32];
+    return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+}
+
+int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count,
+                        int64_t corrupted_count, int64_t m, float* out_host, int32_t* selection_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "multi_krum"));
+    BYZ_REQUIRE(out_host || selection_host, "multi_krum: neither an output nor a selection asked for");
+    // the aggregate asserts as defences.krum does; a selection alone does not (krum(..., return_index=True))
+    BYZ_TRY(check_krum_assert(out_host != nullptr, users_count, corrupted_count));
+    BYZ_TRY(check_multi_krum_m(n_rows, m));
+    hipStream_t s = nullptr;
+    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+    BYZ_TRY(ctx->stage_in.ensure(bytes));
+    BYZ_TRY(ctx->stage_out.ensure(static_cast<size_t>(n_cols) * 3 * sizeof(float)));
+    BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    int32_t* sel = ctx->selection.as<int32_t>();
+    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
+    BYZ_TRY(byz_multi_krum_dev(ctx, G, n_rows, n_cols, n_cols, users_count, corrupted_count, m, 0, out, sel, s));
+    if (selection_host) BYZ_TRY(read_i32(ctx, sel, selection_host, m, s));
+    if (out_host) BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     int32_t words[32];
     return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
 }

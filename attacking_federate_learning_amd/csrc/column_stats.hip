@@ -55,14 +55,18 @@ __device__ __forceinline__ void load_columns(const float* __restrict__ p, bool f
     }
 }
 
-// MODE 0: mean only (no_defense).  MODE 1: mean, std, drift (the attack).
+// MODE 0: mean only (no_defense).  MODE 1: mean, std, drift (the attack).  MODE 2: the mean of the n_rows rows that row_list
+// names, in list order (Multi-Krum's aggregate over its selected rows, ascending): row r of the chain is G[row_list[r]].
+// The list is the same for every lane and is indexed by the uniform loop counter, so its entries arrive through scalar loads
+// (a run's kRowRun indices in one s_load) and every row's address is a scalar base plus the lane's column: the loads of a run
+// are issued together as in MODE 0.
 // carry_in (optional, [VEC columns]): the chain continues a sum begun over earlier rows that live elsewhere (another rank's
 // clients); `total_rows` is the divisor (all rows of the chain, not only the local ones).
 template <int VEC, int MODE>
 __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
     const float* __restrict__ G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,
     float* __restrict__ mean_out, float* __restrict__ std_out, float* __restrict__ drift_out,
-    const int32_t* __restrict__ redo_gate) {
+    const int32_t* __restrict__ redo_gate, const int32_t* __restrict__ row_list) {
     // redo_gate (optional): this launch stands behind the register-resident kernel and runs only if a wave of that kernel
     // gave up waiting for its turn (the word is then non-zero): the same bits, the slow way, instead of an invalid vector
     if (redo_gate != nullptr && __hip_atomic_load(redo_gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -74,11 +78,18 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
 #pragma unroll
     for (int v = 0; v < VEC; ++v) s[v] = 0.0f;
     const float* p = G + c0;
+    auto row_at = [&](int64_t r) __attribute__((always_inline)) {
+        if constexpr (MODE == 2) return p + static_cast<int64_t>(row_list[r]) * ld;
+        else return p + r * ld;
+    };
     int64_t r = 0;
     for (; r + kRowRun <= n_rows; r += kRowRun) {
+        const float* q[kRowRun];                           // (MODE 2: the run's indices first, then its loads back to back)
+#pragma unroll
+        for (int u = 0; u < kRowRun; ++u) q[u] = row_at(r + u);
         float x[kRowRun][VEC];
 #pragma unroll
-        for (int u = 0; u < kRowRun; ++u) load_columns<VEC>(p + (r + u) * ld, full, c0, n_cols, x[u]);
+        for (int u = 0; u < kRowRun; ++u) load_columns<VEC>(q[u], full, c0, n_cols, x[u]);
 #pragma unroll
         for (int u = 0; u < kRowRun; ++u)
 #pragma unroll
@@ -86,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
     }
     for (; r < n_rows; ++r) {
         float x[VEC];
-        load_columns<VEC>(p + r * ld, full, c0, n_cols, x);
+        load_columns<VEC>(row_at(r), full, c0, n_cols, x);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) s[v] = s[v] + x[v];
     }
@@ -459,8 +470,9 @@ __global__ __launch_bounds__(kThreads) void copy_row_kernel(const float* __restr
     if (c < n_cols) out[c] = G[r * ld + c];
 }
 
+// row_list (optional; not with `stats`): the n_rows rows of the chain are G[row_list[0]], G[row_list[1]], ... (MODE 2)
 int column_pass(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, bool stats,
-                float num_std, float* mean, float* stdev, float* drift, hipStream_t stream) {
+                float num_std, float* mean, float* stdev, float* drift, hipStream_t stream, const int32_t* row_list = nullptr) {
     BYZ_REQUIRE(G && n_rows > 0 && n_cols > 0 && ld >= n_cols, "column statistics: bad shape %lld x %lld ld %lld",
                 (long long)n_rows, (long long)n_cols, (long long)ld);
     // 16-byte loads when every row starts 16-byte aligned and the columns alone fill the chip; one column per thread otherwise
@@ -504,17 +516,23 @@ int column_pass(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
 #undef BYZ_RESIDENT
         BYZ_TRY(check_launch("column_resident_kernel"));
         const dim3 redo_grid(static_cast<unsigned>(col_blocks));
-        if (vec4) column_sequential_kernel<4, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx));
-        else column_sequential_kernel<1, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx));
+        if (vec4) column_sequential_kernel<4, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx), nullptr);
+        else column_sequential_kernel<1, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx), nullptr);
         return check_launch("column_sequential_kernel (redo)");
     }
     const dim3 grid(static_cast<unsigned>(col_blocks));
+    if (row_list != nullptr) {
+        BYZ_REQUIRE(!stats, "column statistics: a row list is for the mean alone");
+        if (vec4) column_sequential_kernel<4, 2><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, row_list);
+        else column_sequential_kernel<1, 2><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, row_list);
+        return check_launch("column_sequential_kernel (row list)");
+    }
     if (stats) {
-        if (vec4) column_sequential_kernel<4, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr);
-        else column_sequential_kernel<1, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr);
+        if (vec4) column_sequential_kernel<4, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr, nullptr);
+        else column_sequential_kernel<1, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr, nullptr);
     } else {
-        if (vec4) column_sequential_kernel<4, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr);
-        else column_sequential_kernel<1, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr);
+        if (vec4) column_sequential_kernel<4, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, nullptr);
+        else column_sequential_kernel<1, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, nullptr);
     }
     return check_launch("column_sequential_kernel");
 }
@@ -525,6 +543,12 @@ int launch_column_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
                        hipStream_t stream) {
     BYZ_REQUIRE(out, "no_defense: null output");
     return column_pass(ctx, G, n_rows, n_cols, ld, false, 0.0f, out, nullptr, nullptr, stream);
+}
+
+int launch_column_mean_rows(byz_ctx* ctx, const float* G, const int32_t* row_list, int64_t count, int64_t n_cols, int64_t ld,
+                            float* out, hipStream_t stream) {
+    BYZ_REQUIRE(out && row_list, "mean of rows: null output or null row list");
+    return column_pass(ctx, G, count, n_cols, ld, false, 0.0f, out, nullptr, nullptr, stream, row_list);
 }
 
 int launch_column_drift(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,

@@ -132,6 +132,8 @@ struct byz_ctx {
     byz::Buffer row_total;       // n fp64: sum of a row's finite distances
     byz::Buffer row_top;         // n fp64: sum of a row's largest `drop` finite distances; then n counts of non-finite ones
     byz::Buffer scores;          // n fp32 Krum scores
+    byz::Buffer multi_krum;      // Multi-Krum's ranking: n_pad sort keys, then n row flags
+    byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -243,6 +245,9 @@ int launch_server_update(byz_ctx* ctx, float* w, float* v, const float* agg, int
                          float lr, hipStream_t stream);
 int launch_copy_row(byz_ctx* ctx, const float* G, int64_t ld, int64_t n_rows, int64_t n_cols,
                     const int32_t* index_dev, float* out, hipStream_t stream);
+// out[c] = mean over the rows G[row_list[0]], G[row_list[1]], ... in list order, no_defense's arithmetic
+int launch_column_mean_rows(byz_ctx* ctx, const float* G, const int32_t* row_list, int64_t count, int64_t n_cols, int64_t ld,
+                            float* out, hipStream_t stream);
 
 // round_edges.hip: the steps either side of the path
 constexpr int kMaxSegments = 32;   // tensors one assemble launch can place (more take further launches)
@@ -291,6 +296,9 @@ bool select_large_applies(int64_t n);
 int segment_sort_u64(byz_ctx* ctx, unsigned long long* keys, int64_t n_segments, int64_t n_pad, hipStream_t stream);
 int launch_row_sort_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t prefix_len, int64_t drop_count, bool want_tables,
                           hipStream_t stream);
+// multi_krum.hip: ctx->scores ranked (score, visit position), the first m rows in ranking order (selection_dev, optional)
+// and in ascending order (rows_asc_dev)
+int launch_multi_krum_rank(byz_ctx* ctx, int64_t n, int64_t m, int32_t* selection_dev, int32_t* rows_asc_dev, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

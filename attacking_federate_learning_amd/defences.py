@@ -56,6 +56,20 @@ def bulyan(users_grads, users_count, corrupted_count):
     return get_engine().bulyan(users_grads, users_count, corrupted_count)
 
 
+def multi_krum(users_grads, users_count, corrupted_count, m=None, distances=None, return_index=False):
+    """Multi-Krum (Blanchard et al. 2017, section 4; not in the reference): every client scored the Krum way (the
+    reference's n - f smallest distances, so that m = 1 is Krum), the m best (default users_count - corrupted_count)
+    averaged.  The mean is np.mean(users_grads[np.sort(selection)], axis=0).  `return_index=True` returns the selection,
+    best first, instead (and, as `krum` does, skips the users_count >= 2*corrupted_count + 1 assertion).  Not one of the
+    `defend` keys: the reference's main.py offers only those four."""
+    engine = get_engine()
+    if return_index:
+        if distances is None:
+            distances = engine.pairwise_distances(users_grads)
+        return engine.multi_krum_select(distances, users_count, corrupted_count, m)
+    return engine.multi_krum(users_grads, users_count, corrupted_count, m=m, distances=distances)
+
+
 defend = {DefenseTypes.Krum: krum,
           DefenseTypes.TrimmedMean: trimmed_mean, DefenseTypes.NoDefense: no_defense,
           DefenseTypes.Bulyan: bulyan}

@@ -552,6 +552,78 @@ class Engine:
                                        int(corrupted_count), _vp(ptr), _vp(sel_ptr), _vp(m.stream)))
         return (out, sel) if return_selection else out
 
+    # ---- Multi-Krum (Blanchard et al. 2017, section 4; not in the reference) -------------------
+    @staticmethod
+    def _multi_krum_m(users_count, corrupted_count, m):
+        """Blanchard's default: the users_count - corrupted_count best-scored rows."""
+        return int(users_count) - int(corrupted_count) if m is None else int(m)
+
+    def multi_krum_select(self, distances, users_count, corrupted_count, m=None, on_device=False):
+        """The m best Krum-scored rows of a distance matrix (a `Distances` handle, the reference's dict, or a dense matrix),
+        in ranking order: ascending score (defences.py:33-34's, as `krum` forms it), a tie broken by the visit order 1, 0, 2,
+        ..., every NaN last.  `on_device=True` leaves them in a DeviceBuffer (int32)."""
+        d, keys = self._as_distances(distances)
+        m = self._multi_krum_m(users_count, corrupted_count, m)
+        sel = DeviceBuffer(self, (max(m, 1),), np.int32)
+        _check(self.lib.byz_multi_krum_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count), m,
+                                                  _vp(sel.ptr), None))
+        if on_device and keys is None:
+            return sel
+        picked = sel.numpy()[:m]
+        return picked if keys is None else np.asarray([keys[i] for i in picked], dtype=np.int32)
+
+    def mean_rows(self, g, row_index, validate_index=True):
+        """Column mean of the rows `row_index` names, in that order, with no_defense's arithmetic (sequential fp32 from
+        +0.0, then / count).  `g` is device-resident; indices are checked against its height unless the caller vouches."""
+        m = self._device_matrix(g)
+        if m is None:
+            raise ValueError('mean_rows() takes a device-resident matrix')
+        idx_ptr, count, keep = self._row_index(row_index, m, validate_index)
+        if count == 0:
+            raise ValueError('row_index selects no rows')
+        out, ptr = self._out_like(m, m.cols)
+        _check(self.lib.byz_mean_rows_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(idx_ptr), int(count), _vp(ptr),
+                                          _vp(m.stream)))
+        if keep is not None and not _is_torch(keep):
+            self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
+        return out
+
+    def multi_krum(self, g, users_count, corrupted_count, m=None, distances=None, return_selection=False):
+        """Multi-Krum: np.mean(g[np.sort(selection)], axis=0) over the m (default users_count - corrupted_count) best
+        Krum-scored rows; m = 1 is Krum's row, m = n_rows is no_defense.  The selection (ranking order) comes back as
+        numpy for a host matrix, on the device (int32) for a device-resident one."""
+        assert users_count >= 2 * corrupted_count + 1, (
+            'users_count>=2*corrupted_count + 3', users_count, corrupted_count)
+        mm = self._multi_krum_m(users_count, corrupted_count, m)
+        dm = self._device_matrix(g)
+        if distances is not None:
+            selection = self.multi_krum_select(distances, users_count, corrupted_count, mm)
+            rows = np.sort(selection)
+            if dm is None:
+                stage = self.to_device(self._host_matrix(g))
+                out = self.mean_rows(stage, rows).numpy()
+            else:
+                out = self.mean_rows(g, rows)
+                if dm.torch_like is not None:
+                    import torch
+                    selection = torch.from_numpy(selection).to(dm.torch_like.device)
+            return (out, selection) if return_selection else out
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            out = np.empty(d, dtype=np.float32)
+            sel = np.full(max(mm, 1), -1, dtype=np.int32)
+            _check(self.lib.byz_multi_krum_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, int(users_count),
+                                                int(corrupted_count), mm, out.ctypes.data_as(ctypes.c_void_p),
+                                                sel.ctypes.data_as(ctypes.c_void_p)))
+            return (out, sel[:mm]) if return_selection else out
+        out, ptr = self._out_like(dm, dm.cols)
+        sel, sel_ptr = self._out_like(dm, max(mm, 1), np.int32) if return_selection else (None, None)
+        _check(self.lib.byz_multi_krum_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, int(users_count),
+                                           int(corrupted_count), mm, 0, _vp(ptr), _vp(sel_ptr), _vp(dm.stream)))
+        self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
+        return (out, sel) if return_selection else out
+
     # ---- malicious.py ------------------------------------------------------------------------
     def drift_attack(self, rows, num_std, write_back=False):
         """(drift, mean, std) over the rows; device inputs may be overwritten in place (write_back)."""

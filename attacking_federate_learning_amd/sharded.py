@@ -73,6 +73,12 @@ class HipKernels:
     def krum_bulyan_select(self, dist, users_count, corrupted_count, on_device=False):
         return self.engine.krum_bulyan_select(dist, users_count, corrupted_count, on_device=on_device)
 
+    def multi_krum_select(self, dist, users_count, corrupted_count, m=None):
+        return self.engine.multi_krum_select(dist, users_count, corrupted_count, m)
+
+    def mean_rows(self, g_local, row_index):
+        return self.engine.mean_rows(g_local, row_index)
+
     def trimmed_mean(self, g_local, corrupted_count, row_index=None):
         # row_index comes from this package (a selection the kernels produced): no bounds re-check, no host sync
         return self.engine.trimmed_mean(g_local, g_local.shape[0], corrupted_count, row_index=row_index,
@@ -284,6 +290,18 @@ class ShardedAggregator:
             return out, np.asarray(host, dtype=np.int32)
         return out
 
+    def multi_krum(self, g_local, users_count, corrupted_count, m=None, gather=False, return_selection=False,
+                   total_columns=None):
+        """Multi-Krum, columns layout: the distances' one all-reduce, the selection replicated on every rank, then every
+        rank's mean of its own columns of the selected rows in ascending row order."""
+        assert users_count >= 2 * corrupted_count + 1, (
+            'users_count>=2*corrupted_count + 3', users_count, corrupted_count)
+        dist_m = self.global_distances(g_local)
+        selection = np.asarray(self.kernels.multi_krum_select(dist_m, users_count, corrupted_count, m), dtype=np.int32)
+        out = self.kernels.mean_rows(g_local, np.sort(selection))
+        out = self._maybe_gather(out, gather, total_columns)
+        return (out, selection) if return_selection else out
+
     # ---- defences.py, clients layout ----------------------------------------------------------------------------------
     def _row_owner(self, rows_per_rank):
         offsets = np.concatenate([[0], np.cumsum(rows_per_rank)]).astype(np.int64)
@@ -323,6 +341,19 @@ class ShardedAggregator:
         out = self.kernels.trimmed_mean(cols, 2 * corrupted_count, row_index=row_index)
         out = self._maybe_gather(out, True, total=rows_local.shape[1])
         return (out, selection.astype(np.int32)) if return_selection else out
+
+    def multi_krum_clients(self, rows_local, rows_per_rank, users_count, corrupted_count, m=None, return_selection=False):
+        """Multi-Krum over client-sharded rows: all-gather distances, replicated selection, the selected rows (ascending)
+        re-sharded to column slices, the row-list mean per slice, all-gather of the D-vector."""
+        assert users_count >= 2 * corrupted_count + 1, (
+            'users_count>=2*corrupted_count + 3', users_count, corrupted_count)
+        dist_m = self.client_distances(rows_local, rows_per_rank)
+        selection = np.asarray(self.kernels.multi_krum_select(dist_m, users_count, corrupted_count, m), dtype=np.int32)
+        rows = np.sort(selection)
+        cols, row_index = self.reshard_rows_to_columns(rows_local, rows_per_rank, rows)
+        out = self.kernels.mean_rows(cols, np.arange(len(rows), dtype=np.int32) if row_index is None else row_index)
+        out = self._maybe_gather(out, True, total=rows_local.shape[1])
+        return (out, selection) if return_selection else out
 
     # ---- malicious.py --------------------------------------------------------------------------------------------------
     def drift_attack(self, g_local, n_malicious, num_std, write_back=True, gather=False, total_columns=None):

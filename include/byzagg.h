@@ -169,6 +169,31 @@ int byz_bulyan_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_c
                    int64_t users_count, int64_t corrupted_count, float* out_dev,
                    int32_t* selection_dev, void* stream);
 
+/* ---- Multi-Krum (Blanchard et al. 2017, section 4; not in the reference) ----------------- */
+/* Every row's Krum score s_i -- exactly what byz_krum_select_dev writes to scores_dev: the    */
+/* sequential fp32 sum of row i's first min(n_rows - 1, users_count - corrupted_count)         */
+/* ascending distances (the reference's n - f, so that m = 1 is Krum) -- ranks the rows by     */
+/* (s_i, visit position 1, 0, 2, 3, ...): every NaN after every number, -0.0 as +0.0, scores   */
+/* >= 1e20 and +inf by value.  selection_dev: the first m rows in RANKING order; selection[0]  */
+/* is Krum's index whenever Krum has one (it returns -1 when no score is below 1e20, Multi-Krum */
+/* still ranks those rows).  The aggregate is np.mean(G[np.sort(selection)], axis=0): the      */
+/* selected rows summed in ascending row order, sequential fp32 from +0.0, divided by (float)m  */
+/* -- m = n_rows gives byz_no_defense_dev's bits.  1 <= m <= n_rows (BYZ_E_INVALID otherwise); */
+/* n_rows up to byz_limits' selection limit.                                                   */
+/* The mean of the rows row_index_dev[0..count) of G (device int32, each in [0, n_rows): the   */
+/* caller vouches for it) in list order, no_defense's arithmetic; row_index in ascending order */
+/* is Multi-Krum's aggregate.  The clients layout calls it on its re-sharded slices.           */
+int byz_mean_rows_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                      const int32_t* row_index_dev, int64_t count, float* out_dev, void* stream);
+/* Selection only, on a distance matrix (selection_dev: m int32).                            */
+int byz_multi_krum_select_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int64_t users_count,
+                              int64_t corrupted_count, int64_t m, int32_t* selection_dev, void* stream);
+/* Whole function.  check_assert != 0 applies `users_count >= 2*corrupted_count + 1` as Krum  */
+/* does.  out_dev: n_cols floats; selection_dev (optional): m int32 in ranking order.          */
+int byz_multi_krum_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                       int64_t users_count, int64_t corrupted_count, int64_t m, int check_assert,
+                       float* out_dev, int32_t* selection_dev, void* stream);
+
 /* ---- multi-GPU, columns layout: one context per GPU, the HOST owns the communicator ---- */
 /* SURVEY.md 8(e)'s "cheaper equivalent": every rank holds ALL n_rows clients over its own slice of the      */
 /* columns (G_local: n_rows x n_cols_local).  The path has ONE exchange: the n_rows x n_rows fp64 Gram of    */
@@ -200,6 +225,13 @@ int byz_bulyan_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_row
                            int64_t ld, int64_t users_count, int64_t corrupted_count,
                            byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
                            int32_t* selection_dev, void* stream);
+
+/* Multi-Krum over the slices: the same selection on every rank (selection_dev optional, m     */
+/* int32 in ranking order), out_local_dev = this rank's n_cols_local columns of the aggregate.  */
+int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local,
+                               int64_t ld, int64_t users_count, int64_t corrupted_count, int64_t m,
+                               int check_assert, byz_allreduce_f64_fn allreduce, void* user,
+                               float* out_local_dev, int32_t* selection_dev, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
@@ -291,6 +323,13 @@ int byz_krum_select_host(byz_ctx* ctx, const float* dist_host, int64_t n_rows, i
                          int64_t corrupted_count, int32_t* index_host);
 int byz_drift_attack_host(byz_ctx* ctx, const float* rows_host, int64_t n_rows, int64_t n_cols,
                           float num_std, float* drift_host, float* mean_host, float* std_host);
+
+/* Multi-Krum on a host matrix: out_host (optional, n_cols floats), selection_host (optional, */
+/* m int32, ranking order), at least one of them.  The aggregate asserts users_count >=         */
+/* 2*corrupted_count + 1; a selection alone does not (as krum(..., return_index=True)).        */
+int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                        int64_t users_count, int64_t corrupted_count, int64_t m, float* out_host,
+                        int32_t* selection_host);
 
 /* ---- per-kernel timing (bench.py's roofline leg) --------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on its own stream.          */
