@@ -14,6 +14,13 @@ KERNELS = ('column_stats', 'gram_tile', 'gram_reduce', 'distances', 'row_sort', 
 c_i64, c_i32, c_int, c_f32, c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 _P = ctypes.POINTER
 
+
+
+class GeomedParams(ctypes.Structure):
+    """byz_geomed_params: the geometric median's smoothing, update budget and stopping tolerance."""
+    _fields_ = [('nu', ctypes.c_double), ('max_iter', c_i64), ('ftol', ctypes.c_double)]
+
+
 # name -> argument types (everything returns int unless listed in _RESTYPES)
 _PROTOTYPES = {
     'byz_abi_version': [],
@@ -73,6 +80,12 @@ _PROTOTYPES = {
     'byz_krum_select_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32)],
     'byz_drift_attack_host': [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp],
     'byz_multi_krum_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_row_sqdist_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_weighted_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_geometric_median_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp],
+    'byz_geometric_median_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double)],
+    'byz_geometric_median_host': [c_vp, c_vp, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp],
+    'byz_geometric_median_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_timing_enable': [c_vp, c_int],
     'byz_timing_reset': [c_vp],
     'byz_timing_read': [c_vp, c_int, _P(ctypes.c_double), _P(c_i64)],

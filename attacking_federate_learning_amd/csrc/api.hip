@@ -253,6 +253,7 @@ void byz_ctx_destroy(byz_ctx* ctx) {
     ctx->scores.release();
     ctx->multi_krum.release();
     ctx->multi_krum_rows.release();
+    ctx->geomed.release();
     ctx->selection.release();
     ctx->twin_class.release();
     ctx->redo_tiles.release();
@@ -710,6 +711,145 @@ int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int
     return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
 }
 
+// ---- geometric median (smoothed Weiszfeld; RFA, Pillutla et al.; beyond the reference) ------------------------------------
+namespace {
+
+int check_geomed(const byz_geomed_params* params, int64_t n_rows, const char* who) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    // (written so that a NaN fails every test)
+    if (!(params->nu > 0.0) || params->max_iter < 0 || !(params->ftol >= 0.0)) {
+        set_error("%s: nu = %g must be > 0, max_iter = %lld >= 0, ftol = %g >= 0", who, params->nu, (long long)params->max_iter,
+                  params->ftol);
+        return BYZ_E_INVALID;
+    }
+    if (n_rows > kLargeMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kLargeMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    // every update's launches are enqueued up front, stop or no stop: the cap bounds what a call can queue
+    if (params->max_iter > BYZ_GEOMED_MAX_ITER) {
+        set_error("%s: max_iter = %lld beyond %d (every update's launches are enqueued whatever the stop)", who,
+                  (long long)params->max_iter, BYZ_GEOMED_MAX_ITER);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+struct GeomedScratch {
+    double* partials;   // chunks x n: the (row, column chunk) partials of rowsq
+    double* sq;         // n + 1 (the fallback's flag behind the rows)
+    double* w;          // n
+};
+
+// sized by the chunks geomed_chunks picks for this shape: at most 64 per row, about num_cus * 256 + n in all
+int geomed_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, GeomedScratch* out) {
+    int64_t chunk_cols = 0;
+    const int64_t partials = static_cast<int64_t>(geomed_chunks(ctx, n, n_cols, &chunk_cols)) * n;
+    BYZ_TRY(ctx->geomed.ensure(static_cast<size_t>(partials + (n + 1) + n) * sizeof(double)));
+    out->partials = ctx->geomed.as<double>();
+    out->sq = out->partials + partials;
+    out->w = out->sq + (n + 1);
+    return BYZ_OK;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device.
+int geometric_median(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_geomed_params* params,
+                     byz_allreduce_f64_fn allreduce, void* user, float* out, double* weights, void* stream) {
+    hipStream_t s = as_stream(stream);
+    GeomedScratch t;
+    BYZ_TRY(geomed_scratch(ctx, n, n_cols, &t));
+    int32_t* words = geomed_words(ctx);
+    const int32_t* done = words + kGeomedDone;
+    const int32_t* fallback = words + kGeomedFallback;
+    BYZ_HIP(hipMemsetAsync(words + kGeomedDone, 0, 6 * sizeof(int32_t), s));     // [20, 26): done .. objective
+    ctx->geomed_stream = s;
+    // mean0: no_defense's kernel, then its finiteness; the fallback's launches return at once when it is finite
+    BYZ_TRY(launch_column_mean(ctx, G, n, n_cols, ld, out, s));
+    if (allreduce == nullptr) {
+        BYZ_TRY(launch_geomed_finite_check(ctx, out, n_cols, nullptr, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, t.sq, nullptr, fallback, s));
+        BYZ_TRY(launch_geomed_fallback(ctx, t.sq, n, t.w, nullptr, s));
+    } else {
+        // a rank whose own columns are finite adds 0 to every row's squared norm (finite: the sum's finiteness is the
+        // others'); the flag rides behind the rows, so that the decision is taken on all-reduced data on every rank
+        BYZ_HIP(hipMemsetAsync(t.sq, 0, static_cast<size_t>(n + 1) * sizeof(double), s));
+        BYZ_TRY(launch_geomed_finite_check(ctx, out, n_cols, t.sq + n, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, t.sq, nullptr, fallback, s));
+        BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n + 1, stream, "geometric median (finiteness)"));
+        BYZ_TRY(launch_geomed_fallback(ctx, t.sq, n, t.w, t.sq + n, s));
+    }
+    BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, t.w, out, nullptr, fallback, s));
+    // the objective at the start, then the updates
+    for (int64_t k = 0; k <= params->max_iter; ++k) {
+        if (k > 0) BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, t.w, out, done, nullptr, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, t.sq, done, nullptr, s));
+        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n, stream, "geometric median (distances)"));
+        BYZ_TRY(launch_geomed_step(ctx, t.sq, n, t.w, params->nu, params->ftol, k, params->max_iter, s));
+    }
+    if (weights != nullptr) BYZ_TRY(launch_geomed_weights(ctx, t.w, n, weights, s));
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_row_sqdist_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* z, double* sq,
+                       void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_sqdist"));
+    BYZ_REQUIRE(z && sq, "row_sqdist: null vector or output");
+    if (n_rows > kLargeMaxRows) {
+        set_error("row_sqdist: at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    GeomedScratch t;
+    BYZ_TRY(geomed_scratch(ctx, n_rows, n_cols, &t));
+    return launch_row_sqdist(ctx, G, n_rows, n_cols, ld, z, t.partials, sq, nullptr, nullptr, as_stream(stream));
+}
+
+int byz_weighted_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w, float* out,
+                          void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "weighted_mean"));
+    BYZ_REQUIRE(w && out, "weighted_mean: null weights or output");
+    if (n_rows > kLargeMaxRows) {
+        set_error("weighted_mean: at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return launch_weighted_mean(ctx, G, n_rows, n_cols, ld, w, out, nullptr, nullptr, as_stream(stream));
+}
+
+int byz_geometric_median_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                             const byz_geomed_params* params, float* out, double* weights, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "geometric_median"));
+    BYZ_REQUIRE(out, "geometric_median: null output");
+    BYZ_TRY(check_geomed(params, n_rows, "geometric_median"));
+    return geometric_median(ctx, G, n_rows, n_cols, ld, params, nullptr, nullptr, out, weights, stream);
+}
+
+int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                     const byz_geomed_params* params, byz_allreduce_f64_fn allreduce, void* user, float* out,
+                                     double* weights, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "geometric_median_sharded"));
+    BYZ_REQUIRE(out && allreduce, "geometric_median_sharded: null output or null all-reduce");
+    BYZ_TRY(check_geomed(params, n_rows, "geometric_median_sharded"));
+    return geometric_median(ctx, G, n_rows, n_cols, ld, params, allreduce, user, out, weights, stream);
+}
+
+int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* excluded_rows, double* objective) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[32];
+    BYZ_TRY(read_small(ctx, words, ctx->geomed_stream));   // synchronises the last call's stream
+    if (iterations) *iterations = words[kGeomedIterations];
+    if (excluded_rows) *excluded_rows = words[kGeomedExcluded];
+    if (objective) std::memcpy(objective, words + kGeomedObjective, sizeof(double));
+    return BYZ_OK;
+}
+
 int byz_drift_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,
                          float* drift, float* mean, float* stdev, int write_back, void* stream) {
     BYZ_TRY(enter(ctx));
@@ -939,6 +1079,29 @@ int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64
     BYZ_TRY(byz_multi_krum_dev(ctx, G, n_rows, n_cols, n_cols, users_count, corrupted_count, m, 0, out, sel, s));
     if (selection_host) BYZ_TRY(read_i32(ctx, sel, selection_host, m, s));
     if (out_host) BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    int32_t words[32];
+    return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+}
+
+int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_geomed_params* params,
+                              float* out_host, double* weights_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "geometric_median"));
+    BYZ_REQUIRE(out_host, "geometric_median: null output");
+    BYZ_TRY(check_geomed(params, n_rows, "geometric_median"));
+    hipStream_t s = nullptr;
+    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the weights 8-byte aligned)
+    BYZ_TRY(ctx->stage_in.ensure(bytes));
+    BYZ_TRY(ctx->stage_out.ensure(out_bytes + static_cast<size_t>(n_rows) * sizeof(double)));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    double* weights = weights_host ? reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes) : nullptr;
+    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
+    BYZ_TRY(byz_geometric_median_dev(ctx, G, n_rows, n_cols, n_cols, params, out, weights, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (weights_host)
+        BYZ_HIP(hipMemcpyAsync(weights_host, weights, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
     int32_t words[32];
     return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
 }

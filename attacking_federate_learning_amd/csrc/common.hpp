@@ -134,6 +134,8 @@ struct byz_ctx {
     byz::Buffer scores;          // n fp32 Krum scores
     byz::Buffer multi_krum;      // Multi-Krum's ranking: n_pad sort keys, then n row flags
     byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
+    byz::Buffer geomed;          // geometric median: 64 fp64 partials per row, then sq (n + 1) and the weights (n)
+    hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -187,9 +189,13 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 //   [17] number of near-duplicate pairs listed by the last distance kernel
 //   [18] non-zero: the register-resident column statistics of the CURRENT call gave up a turn; the two-pass kernel queued
 //        behind them recomputes the call's columns (zeroed before every such launch; bit 4 above is no longer set)
+//   [20] geometric median: done (the launches still queued return at once)   [21] its iterations   [22] its excluded rows
+//   [23] geometric median: mean0 was not finite (the fallback ran)   [24, 25] its objective (fp64)
 inline int32_t* device_status_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 16; }
 inline int32_t* attack_redo_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 18; }
 inline int32_t* near_pair_count_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 17; }
+constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kGeomedFallback = 23, kGeomedObjective = 24;
+inline int32_t* geomed_words(byz_ctx* ctx) { return ctx->small.as<int32_t>(); }
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).
 struct KernelTimer {
@@ -299,6 +305,19 @@ int launch_row_sort_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t pr
 // multi_krum.hip: ctx->scores ranked (score, visit position), the first m rows in ranking order (selection_dev, optional)
 // and in ascending order (rows_asc_dev)
 int launch_multi_krum_rank(byz_ctx* ctx, int64_t n, int64_t m, int32_t* selection_dev, int32_t* rows_asc_dev, hipStream_t stream);
+// geomed.hip: the geometric median's passes (row distances to a vector, weighted row mean) and its small loop kernels.
+// skip_if_set / run_if_set (optional device words): the launch returns at once if *skip_if_set != 0, or if *run_if_set == 0.
+// the column chunks of rowsq for this shape (at most 64: the partials are chunks x n_rows fp64)
+int geomed_chunks(byz_ctx* ctx, int64_t n_rows, int64_t n_cols, int64_t* chunk_cols);
+int launch_row_sqdist(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* z, double* partials,
+                      double* sq, const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream);
+int launch_weighted_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w, float* out,
+                         const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream);
+int launch_geomed_finite_check(byz_ctx* ctx, const float* v, int64_t n, double* flag_f64, hipStream_t stream);
+int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w, const double* global_flag, hipStream_t stream);
+int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
+                       hipStream_t stream);
+int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

@@ -1,0 +1,360 @@
+// The geometric median by smoothed Weiszfeld iterations (RFA: Pillutla, Kakade and Harchaoui, "Robust Aggregation for
+// Federated Learning"): two streaming passes over G per iteration, nothing of order N^2.
+//
+//   rowsq   sq[i] = sum_c ((double)x_ic - (double)z_c)^2 in fp64, on the difference (never |x|^2 - 2 x.z + |z|^2, which
+//           cancels when the rows cluster round z).  Workgroups take (block of 32 rows, chunk of columns); each wave owns 8
+//           rows and walks its chunk in windows of 1024 columns: a lane keeps its 16 floats of z in registers across the 8
+//           rows and loads dwordx4.  Every (row, chunk) partial comes from one wave (lane sums, then a fixed butterfly), so
+//           partials[chunk][row] needs no atomics; the finishing kernel adds a row's chunks in chunk order.  At most
+//           kMaxChunks chunks: the scratch is O(n_rows) whatever n_cols is.
+//   wmean   out[c] = fl32(S_c / W), S_c = sum over rows with w_i != 0 of w_i * (double)x_ic, W = sum w_i, both sequential in
+//           row order with no fused multiply-add (this file is compiled with -ffp-contract=off).  One thread walks the rows
+//           for VEC columns as column_sequential_kernel does; the weights are uniform and arrive through scalar loads.  A row
+//           of weight 0 is neither loaded nor multiplied, so 0 * inf never reaches a column.
+//   step    one workgroup: d_i = sqrt(sq_i), F = sum of d over the active rows (fixed order), the stop test
+//           |F_old - F| <= ftol * F, beta_i = 1 / max(nu, d_i).
+// Every launch of the loop is enqueued up front; after the stop the remaining launches read the done word and return at once
+// (the redo_gate idiom of column_sequential_kernel).  The state lives in the context's small area (common.hpp).
+#include "common.hpp"
+
+#include <algorithm>
+
+namespace byz {
+namespace {
+
+constexpr int kThreads = 256;                       // rowsq and wmean workgroups
+constexpr int kWaves = kThreads / 64;
+constexpr int kRowsPerWave = 8;
+constexpr int kRowBlock = kWaves * kRowsPerWave;    // rows of one rowsq workgroup
+constexpr int kSegs = 4;                            // dwordx4 loads per lane and row in one window
+constexpr int kWindow = 64 * 4 * kSegs;             // columns a wave covers at once (1024)
+constexpr int kMaxChunks = 64;                      // fp64 partials per row at most
+constexpr int kRowRun = 8;                          // wmean: rows whose loads are issued together
+constexpr int kStepThreads = 1024;
+
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
+
+// run unless *skip_if_set != 0; with run_if_set, only if *run_if_set != 0
+__device__ __forceinline__ bool gated_out(const int32_t* skip_if_set, const int32_t* run_if_set) {
+    if (skip_if_set != nullptr && __hip_atomic_load(skip_if_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
+    if (run_if_set != nullptr && __hip_atomic_load(run_if_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return true;
+    return false;
+}
+
+// four consecutive floats at column c (of a window that ends at c_end): dwordx4 when whole and aligned, masked otherwise
+template <bool VEC4>
+__device__ __forceinline__ void load4(const float* __restrict__ p, int64_t c, int64_t c_end, float (&x)[4]) {
+    if (VEC4 && c + 4 <= c_end) {
+        const float4u q = *reinterpret_cast<const float4u*>(p + c);
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+    } else {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) x[v] = c + v < c_end ? p[c + v] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// partials[chunk * n_rows + row]; z == nullptr: the distance to the origin
+template <bool VEC4>
+__global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols,
+                                                                 int64_t ld, const float* __restrict__ z, int64_t chunk_cols,
+                                                                 double* __restrict__ partials, const int32_t* skip_if_set,
+                                                                 const int32_t* run_if_set) {
+    if (gated_out(skip_if_set, run_if_set)) return;
+    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kRowBlock + wave * kRowsPerWave;
+    if (row0 >= n_rows) return;
+    const int64_t c_begin = static_cast<int64_t>(blockIdx.y) * chunk_cols;
+    const int64_t c_end = c_begin + chunk_cols < n_cols ? c_begin + chunk_cols : n_cols;
+    double acc[kRowsPerWave];
+#pragma unroll
+    for (int r = 0; r < kRowsPerWave; ++r) acc[r] = 0.0;
+    for (int64_t w0 = c_begin; w0 < c_end; w0 += kWindow) {
+        double zs[kSegs][4];
+#pragma unroll
+        for (int k = 0; k < kSegs; ++k) {
+            float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (z != nullptr) load4<VEC4>(z, w0 + k * 256 + lane * 4, c_end, t);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) zs[k][v] = static_cast<double>(t[v]);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsPerWave; ++r) {
+            if (row0 + r < n_rows) {
+                const float* p = G + (row0 + r) * ld;
+                float x[kSegs][4];
+#pragma unroll
+                for (int k = 0; k < kSegs; ++k) load4<VEC4>(p, w0 + k * 256 + lane * 4, c_end, x[k]);
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < kSegs; ++k)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const double d = static_cast<double>(x[k][v]) - zs[k][v];
+                        s = s + d * d;
+                    }
+                acc[r] = acc[r] + s;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kRowsPerWave; ++r) {
+        const double s = wave_sum(acc[r]);
+        if (lane == 0 && row0 + r < n_rows) partials[static_cast<int64_t>(blockIdx.y) * n_rows + row0 + r] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void rowsq_finish_kernel(const double* __restrict__ partials, int64_t n_rows, int chunks,
+                                                           double* __restrict__ sq, const int32_t* skip_if_set,
+                                                           const int32_t* run_if_set) {
+    if (gated_out(skip_if_set, run_if_set)) return;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n_rows) return;
+    double s = 0.0;
+    for (int p = 0; p < chunks; ++p) s = s + partials[p * n_rows + i];
+    sq[i] = s;
+}
+
+template <int VEC>
+__device__ __forceinline__ void load_cols(const float* __restrict__ p, bool full, int64_t c0, int64_t n_cols, float (&x)[VEC]) {
+    if constexpr (VEC == 4) {
+        if (full) {
+            const float4u q = *reinterpret_cast<const float4u*>(p);
+            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) x[v] = (c0 + v < n_cols) ? p[v] : 0.0f;
+        }
+    } else {
+        x[0] = p[0];
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void wmean_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                                         const double* __restrict__ w, float* __restrict__ out,
+                                                         const int32_t* skip_if_set, const int32_t* run_if_set) {
+    if (gated_out(skip_if_set, run_if_set)) return;
+    const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * VEC;
+    if (c0 >= n_cols) return;
+    const bool full = c0 + VEC <= n_cols;
+    const float* p = G + c0;
+    double acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
+    double W = 0.0;
+    int64_t r = 0;
+    for (; r + kRowRun <= n_rows; r += kRowRun) {
+        double wr[kRowRun];
+#pragma unroll
+        for (int u = 0; u < kRowRun; ++u) wr[u] = w[r + u];          // uniform: one scalar load for the run
+        float x[kRowRun][VEC];
+#pragma unroll
+        for (int u = 0; u < kRowRun; ++u) {
+            if (wr[u] != 0.0) load_cols<VEC>(p + (r + u) * ld, full, c0, n_cols, x[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kRowRun; ++u) {
+            if (wr[u] != 0.0) {
+                W = W + wr[u];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = acc[v] + wr[u] * static_cast<double>(x[u][v]);
+            }
+        }
+    }
+    for (; r < n_rows; ++r) {
+        const double wu = w[r];
+        if (wu != 0.0) {
+            float x[VEC];
+            load_cols<VEC>(p + r * ld, full, c0, n_cols, x);
+            W = W + wu;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = acc[v] + wu * static_cast<double>(x[v]);
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v)
+        if (c0 + v < n_cols) out[c0 + v] = static_cast<float>(acc[v] / W);
+}
+
+// ---- the loop's small kernels (state in ctx->small, common.hpp) ----------------------------------------------------------
+__device__ __forceinline__ double* objective_of(int32_t* words) { return reinterpret_cast<double*>(words + kGeomedObjective); }
+
+// fixed-order sum over one workgroup of kStepThreads threads (every thread gets the total)
+__device__ double block_sum(double v, double* lds) {
+    const int tid = threadIdx.x;
+    lds[tid] = v;
+    __syncthreads();
+    for (int step = kStepThreads / 2; step >= 1; step >>= 1) {
+        if (tid < step) lds[tid] = lds[tid] + lds[tid + step];
+        __syncthreads();
+    }
+    const double total = lds[0];
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(256) void finite_check_kernel(const float* __restrict__ v, int64_t n, int32_t* words,
+                                                           double* flag_f64) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = v[i];
+    if (!__builtin_isfinite(x)) {
+        __hip_atomic_store(words + kGeomedFallback, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (flag_f64 != nullptr) *flag_f64 = 1.0;
+    }
+}
+
+// mean0 was not finite: the active rows are those with a finite sq0 (the fp64 squared norm), their weights 1, the others 0
+__global__ __launch_bounds__(kStepThreads) void geomed_fallback_kernel(const double* __restrict__ sq0, int64_t n, double* w,
+                                                                       int32_t* words, const double* global_flag) {
+    __shared__ double lds[kStepThreads];
+    const bool fallback = global_flag != nullptr ? *global_flag > 0.0
+                                                 : __hip_atomic_load(words + kGeomedFallback, __ATOMIC_RELAXED,
+                                                                     __HIP_MEMORY_SCOPE_AGENT) != 0;
+    if (global_flag != nullptr && threadIdx.x == 0) words[kGeomedFallback] = fallback ? 1 : 0;
+    if (!fallback) return;
+    double excluded = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kStepThreads) {
+        const bool active = __builtin_isfinite(sq0[i]);
+        w[i] = active ? 1.0 : 0.0;
+        if (!active) excluded = excluded + 1.0;
+    }
+    const double total = block_sum(excluded, lds);
+    if (threadIdx.x == 0) {
+        const int64_t ex = static_cast<int64_t>(total);
+        words[kGeomedExcluded] = static_cast<int32_t>(ex);
+        if (ex == n) words[kGeomedDone] = 1;          // no row left: the output is wmean's NaN, iterations 0
+    }
+}
+
+// k = 0: the objective at the starting point; k >= 1: after the k-th update.  Active rows: every row unless the fallback
+// flag is set, then those with a non-zero weight (a beta of an active row is never 0).  k < max_iter and no stop: the weights
+// of update k + 1.
+__global__ __launch_bounds__(kStepThreads) void geomed_step_kernel(const double* __restrict__ sq, int64_t n, double* w,
+                                                                   int32_t* words, double nu, double ftol, int64_t k,
+                                                                   int64_t max_iter) {
+    __shared__ double lds[kStepThreads];
+    if (__hip_atomic_load(words + kGeomedDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+    const bool fallback = words[kGeomedFallback] != 0;
+    const int64_t per = (n + kStepThreads - 1) / kStepThreads;
+    const int64_t lo = threadIdx.x * per < n ? threadIdx.x * per : n;
+    const int64_t hi = lo + per < n ? lo + per : n;
+    double f = 0.0;
+    for (int64_t i = lo; i < hi; ++i)
+        if (!fallback || w[i] != 0.0) f = f + sqrt(sq[i]);
+    const double F = block_sum(f, lds);
+    const double F_old = *objective_of(words);
+    const bool stop = k > 0 && fabs(F_old - F) <= ftol * F;
+    __syncthreads();                                  // every thread has read F_old
+    if (threadIdx.x == 0) {
+        *objective_of(words) = F;
+        words[kGeomedIterations] = static_cast<int32_t>(k);
+        if (stop) words[kGeomedDone] = 1;
+    }
+    if (stop || k >= max_iter) return;
+    for (int64_t i = lo; i < hi; ++i) {
+        const bool active = !fallback || w[i] != 0.0;
+        const double d = sqrt(sq[i]);
+        w[i] = active ? 1.0 / (d > nu ? d : nu) : 0.0;
+    }
+}
+
+// weights_out = beta / sum(beta) of the last update, or uniform over the active rows when there was none
+__global__ __launch_bounds__(kStepThreads) void geomed_weights_kernel(const double* __restrict__ w, int64_t n,
+                                                                      const int32_t* words, double* __restrict__ out) {
+    __shared__ double lds[kStepThreads];
+    const bool fallback = words[kGeomedFallback] != 0;
+    const bool updated = words[kGeomedIterations] > 0;
+    const int64_t per = (n + kStepThreads - 1) / kStepThreads;
+    const int64_t lo = threadIdx.x * per < n ? threadIdx.x * per : n;
+    const int64_t hi = lo + per < n ? lo + per : n;
+    double s = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+        if (updated) s = s + w[i];
+        else if (!fallback || w[i] != 0.0) s = s + 1.0;
+    }
+    const double total = block_sum(s, lds);
+    for (int64_t i = lo; i < hi; ++i) {
+        const bool active = !fallback || w[i] != 0.0;
+        if (total == 0.0) out[i] = 0.0;
+        else if (updated) out[i] = w[i] / total;
+        else out[i] = active ? 1.0 / total : 0.0;
+    }
+}
+
+bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+}  // namespace
+
+int geomed_chunks(byz_ctx* ctx, int64_t n_rows, int64_t n_cols, int64_t* chunk_cols) {
+    const int64_t row_blocks = ceil_div(n_rows, kRowBlock);
+    const int64_t target = static_cast<int64_t>(ctx->num_cus) * 8;       // workgroups of four waves: 32 waves per CU
+    int64_t p = std::max<int64_t>(1, ceil_div(target, row_blocks));
+    p = std::min<int64_t>({p, static_cast<int64_t>(kMaxChunks), ceil_div(n_cols, kWindow)});
+    const int64_t chunk = ceil_div(ceil_div(n_cols, p), kWindow) * kWindow;
+    *chunk_cols = chunk;
+    return static_cast<int>(ceil_div(n_cols, chunk));
+}
+
+int launch_row_sqdist(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* z, double* partials,
+                      double* sq, const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream) {
+    BYZ_REQUIRE(G && partials && sq && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols,
+                "row distances: bad arguments");
+    int64_t chunk = 0;
+    const int chunks = geomed_chunks(ctx, n_rows, n_cols, &chunk);
+    const bool vec4 = (ld % 4 == 0) && aligned16(G) && (z == nullptr || aligned16(z));
+    const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+    if (vec4) rowsq_partial_kernel<true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    else rowsq_partial_kernel<false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    BYZ_TRY(check_launch("rowsq_partial_kernel"));
+    rowsq_finish_kernel<<<static_cast<unsigned>(ceil_div(n_rows, 256)), 256, 0, stream>>>(partials, n_rows, chunks, sq,
+                                                                                        skip_if_set, run_if_set);
+    return check_launch("rowsq_finish_kernel");
+}
+
+int launch_weighted_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w, float* out,
+                         const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream) {
+    BYZ_REQUIRE(G && w && out && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols,
+                "weighted mean: bad arguments");
+    // 16-byte loads when every row starts 16-byte aligned and the columns alone fill the chip (column_pass's rule)
+    const bool vec4 = (ld % 4 == 0) && aligned16(G) && n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
+    const int64_t blocks = ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1));
+    if (blocks >= (int64_t{1} << 31)) {
+        set_error("weighted mean: %lld columns is beyond one launch", (long long)n_cols);
+        return BYZ_E_UNSUPPORTED;
+    }
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+    if (vec4) wmean_kernel<4><<<static_cast<unsigned>(blocks), kThreads, 0, stream>>>(G, n_rows, n_cols, ld, w, out, skip_if_set, run_if_set);
+    else wmean_kernel<1><<<static_cast<unsigned>(blocks), kThreads, 0, stream>>>(G, n_rows, n_cols, ld, w, out, skip_if_set, run_if_set);
+    return check_launch("wmean_kernel");
+}
+
+int launch_geomed_finite_check(byz_ctx* ctx, const float* v, int64_t n, double* flag_f64, hipStream_t stream) {
+    finite_check_kernel<<<static_cast<unsigned>(ceil_div(n, 256)), 256, 0, stream>>>(v, n, geomed_words(ctx), flag_f64);
+    return check_launch("finite_check_kernel");
+}
+
+int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w, const double* global_flag, hipStream_t stream) {
+    geomed_fallback_kernel<<<1, kStepThreads, 0, stream>>>(sq0, n, w, geomed_words(ctx), global_flag);
+    return check_launch("geomed_fallback_kernel");
+}
+
+int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
+                       hipStream_t stream) {
+    geomed_step_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, w, geomed_words(ctx), nu, ftol, k, max_iter);
+    return check_launch("geomed_step_kernel");
+}
+
+int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream) {
+    geomed_weights_kernel<<<1, kStepThreads, 0, stream>>>(w, n, geomed_words(ctx), out);
+    return check_launch("geomed_weights_kernel");
+}
+
+}  // namespace byz

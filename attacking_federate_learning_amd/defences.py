@@ -70,6 +70,14 @@ def multi_krum(users_grads, users_count, corrupted_count, m=None, distances=None
     return engine.multi_krum(users_grads, users_count, corrupted_count, m=m, distances=distances)
 
 
+def geometric_median(users_grads, users_count, corrupted_count, nu=1e-6, max_iter=10, ftol=1e-6):
+    """The geometric median of the clients' gradients (smoothed Weiszfeld iterations: RFA, Pillutla, Kakade and
+    Harchaoui; not in the reference).  The reference's signature, so that it drops into Server.defend-style calls;
+    users_count and corrupted_count are accepted and unused (the median needs no count).  nu, max_iter and ftol are this
+    package's defaults.  Not one of the `defend` keys: the reference's main.py offers only those four."""
+    return get_engine().geometric_median(users_grads, nu=nu, max_iter=max_iter, ftol=ftol)
+
+
 defend = {DefenseTypes.Krum: krum,
           DefenseTypes.TrimmedMean: trimmed_mean, DefenseTypes.NoDefense: no_defense,
           DefenseTypes.Bulyan: bulyan}

@@ -624,6 +624,120 @@ class Engine:
         self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
         return (out, sel) if return_selection else out
 
+    # ---- geometric median (smoothed Weiszfeld; RFA, Pillutla et al.; not in the reference) ----
+    def _f64_vector(self, v, n):
+        """A length-n fp64 vector for a kernel: (device pointer, keepalive).  torch CUDA tensors are used in place (made
+        contiguous fp64 on the matrix's device); anything else is uploaded."""
+        if _is_torch(v) and v.is_cuda:
+            import torch
+            t = v.reshape(-1).to(dtype=torch.float64).contiguous()
+            if t.device.index != self.device:
+                raise ValueError('the vector lives on %s, this engine drives cuda:%d' % (t.device, self.device))
+            if t.numel() != n:
+                raise ValueError('expected %d values, got %d' % (n, t.numel()))
+            return t.data_ptr(), t
+        if isinstance(v, DeviceBuffer):
+            if v.dtype != np.float64 or int(np.prod(v.shape)) != n:
+                raise ValueError('a DeviceBuffer here must hold %d float64 values' % n)
+            return v.ptr, v
+        host = np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1))
+        if host.size != n:
+            raise ValueError('expected %d values, got %d' % (n, host.size))
+        buf = self.to_device(host)
+        return buf.ptr, buf
+
+    def _staged(self, g):
+        """(_Matrix, keepalive, host?) for a device-resident matrix or a host one staged to the device."""
+        m = self._device_matrix(g)
+        if m is not None:
+            return m, None, False
+        stage = self.to_device(self._host_matrix(g))
+        return self._device_matrix(stage), stage, True
+
+    def row_sqdist(self, g, z):
+        """sq[i] = sum_c ((double)g[i, c] - (double)z[c])^2 in fp64 (fixed order; on the difference, not through the
+        Gram identity).  fp64 out: a torch tensor for a torch input, numpy for a host input, a DeviceBuffer otherwise."""
+        m, stage, host = self._staged(g)
+        (zp,), n, _, keep, _ = self._vectors(z)
+        if n != m.cols:
+            raise ValueError('z has %d entries, the matrix %d columns' % (n, m.cols))
+        if m.torch_like is not None:
+            import torch
+            out = torch.empty(m.rows, dtype=torch.float64, device=m.torch_like.device)
+            optr = out.data_ptr()
+        else:
+            out = DeviceBuffer(self, (m.rows,), np.float64)
+            optr = out.ptr
+        _check(self.lib.byz_row_sqdist_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(zp), _vp(optr), _vp(m.stream)))
+        if host or any(isinstance(k, DeviceBuffer) for k in keep):
+            self.synchronize(m.stream)   # staged copies must outlive the kernel
+        return out.numpy() if host else out
+
+    def weighted_mean(self, g, weights, validate=True):
+        """out[c] = fl32(S_c / W): S_c the sequential fp64 sum, in row order, of w_i * g[i, c] over the rows with w_i != 0,
+        W = sum w_i.  The weights must be finite and >= 0; all zero gives NaN.  validate=True checks them here: for
+        device-resident weights that is one reduction and a host synchronisation.  validate=False is for a caller that
+        vouches for them (the kernel would carry a NaN or a negative weight into the mean)."""
+        m, stage, host = self._staged(g)
+        wp, wkeep = self._f64_vector(weights, m.rows)
+        if validate:
+            if _is_torch(wkeep):
+                import torch
+                bad = bool((~torch.isfinite(wkeep) | (wkeep < 0)).any().item())
+            else:
+                w_host = np.asarray(weights.numpy() if isinstance(weights, DeviceBuffer) else weights, dtype=np.float64)
+                bad = bool((~np.isfinite(w_host) | (w_host < 0)).any())
+            if bad:
+                raise ValueError('weights must be finite and >= 0')
+        out, optr = self._out_like(m, m.cols)
+        _check(self.lib.byz_weighted_mean_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(wp), _vp(optr), _vp(m.stream)))
+        if host or isinstance(wkeep, DeviceBuffer):
+            self.synchronize(m.stream)
+        return out.numpy() if host else out
+
+    @staticmethod
+    def _geomed_params(nu, max_iter, ftol):
+        return _native.GeomedParams(float(nu), int(max_iter), float(ftol))
+
+    def geometric_median_info(self):
+        """(iterations, excluded_rows, objective) of the last geometric median on this engine (synchronises)."""
+        it, ex, obj = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        _check(self.lib.byz_geometric_median_info(self.ctx, ctypes.byref(it), ctypes.byref(ex), ctypes.byref(obj)))
+        return int(it.value), int(ex.value), float(obj.value)
+
+    def geometric_median(self, g, nu=1e-6, max_iter=10, ftol=1e-6, return_info=False):
+        """The geometric median of the rows by smoothed Weiszfeld iterations (RFA), started at no_defense's mean; rows with
+        a non-finite entry are left out when the mean is not finite.  nu = 1e-6, max_iter = 10 and ftol = 1e-6 are this
+        package's defaults, not the paper's.  return_info=True also returns {iterations, objective, excluded_rows, weights}
+        (weights: fp64, one per row, summing to 1 over the rows of the last update)."""
+        params = self._geomed_params(nu, max_iter, ftol)
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            out = np.empty(d, dtype=np.float32)
+            weights = np.empty(n, dtype=np.float64) if return_info else None
+            _check(self.lib.byz_geometric_median_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                                      out.ctypes.data_as(ctypes.c_void_p),
+                                                      weights.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+        else:
+            out, ptr = self._out_like(dm, dm.cols)
+            weights, wptr = None, None
+            if return_info:
+                if dm.torch_like is not None:
+                    import torch
+                    weights = torch.empty(dm.rows, dtype=torch.float64, device=dm.torch_like.device)
+                    wptr = weights.data_ptr()
+                else:
+                    weights = DeviceBuffer(self, (dm.rows,), np.float64)
+                    wptr = weights.ptr
+            _check(self.lib.byz_geometric_median_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                                     _vp(ptr), _vp(wptr), _vp(dm.stream)))
+        if not return_info:
+            return out
+        iterations, excluded, objective = self.geometric_median_info()
+        return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
+
     # ---- malicious.py ------------------------------------------------------------------------
     def drift_attack(self, rows, num_std, write_back=False):
         """(drift, mean, std) over the rows; device inputs may be overwritten in place (write_back)."""

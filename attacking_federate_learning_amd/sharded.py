@@ -79,6 +79,13 @@ class HipKernels:
     def mean_rows(self, g_local, row_index):
         return self.engine.mean_rows(g_local, row_index)
 
+    def row_sqdist(self, g_local, z):
+        return self.engine.row_sqdist(g_local, z)             # (N,) float64: this rank's part over its columns
+
+    def weighted_mean(self, g_local, weights):
+        # the weights come from this package (0/1 flags, 1 / max(nu, d)): no check, no host sync
+        return self.engine.weighted_mean(g_local, weights, validate=False)
+
     def trimmed_mean(self, g_local, corrupted_count, row_index=None):
         # row_index comes from this package (a selection the kernels produced): no bounds re-check, no host sync
         return self.engine.trimmed_mean(g_local, g_local.shape[0], corrupted_count, row_index=row_index,
@@ -301,6 +308,56 @@ class ShardedAggregator:
         out = self.kernels.mean_rows(g_local, np.sort(selection))
         out = self._maybe_gather(out, gather, total_columns)
         return (out, selection) if return_selection else out
+
+    def geometric_median(self, g_local, nu=1e-6, max_iter=10, ftol=1e-6, gather=False, return_info=False,
+                         total_columns=None):
+        """The geometric median (smoothed Weiszfeld, Engine.geometric_median's contract), columns layout: every rank
+        holds all rows over its own columns.  A rank's squared distances to z cover its columns: one all-reduce of N
+        doubles per iteration makes them whole, and the objective, the stop and the weights are then the same on every
+        rank.  One more all-reduce of N + 1 doubles first decides the finiteness fallback on all-reduced data."""
+        import torch
+        n = g_local.shape[0]
+        dev = g_local.device
+        z = self.kernels.no_defense(g_local)
+        ex = torch.zeros(n + 1, dtype=torch.float64, device=dev)
+        if not bool(torch.isfinite(z).all().item()):
+            # (a rank whose columns are finite adds 0: the sum's finiteness is the other ranks')
+            ex[:n] = self.kernels.row_sqdist(g_local, torch.zeros_like(z))
+            ex[n] = 1.0
+        self._all_reduce('allreduce_geomed_finite', ex)
+        fallback = bool(ex[n].item() > 0)
+        active = torch.isfinite(ex[:n]) if fallback else torch.ones(n, dtype=torch.bool, device=dev)
+        excluded = int((~active).sum().item())
+        if fallback:
+            z = self.kernels.weighted_mean(g_local, active.to(torch.float64))
+
+        def distances(z):
+            sq = self.kernels.row_sqdist(g_local, z)
+            self._all_reduce('allreduce_geomed_distances', sq)
+            d = torch.sqrt(sq)
+            return d, float(d[active].sum().item())
+
+        iterations, objective, beta = 0, 0.0, None
+        if excluded < n:
+            d, objective = distances(z)
+            for k in range(1, int(max_iter) + 1):
+                beta = torch.where(active, 1.0 / torch.clamp(d, min=float(nu)), torch.zeros_like(d))
+                z = self.kernels.weighted_mean(g_local, beta)
+                d, f_new = distances(z)
+                stop = abs(objective - f_new) <= float(ftol) * f_new
+                objective, iterations = f_new, k
+                if stop:
+                    break
+        out = self._maybe_gather(z, gather, total_columns)
+        if not return_info:
+            return out
+        if beta is not None:
+            weights = beta / beta.sum()
+        elif excluded < n:
+            weights = active.to(torch.float64) / float(n - excluded)
+        else:
+            weights = torch.zeros(n, dtype=torch.float64, device=dev)
+        return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
 
     # ---- defences.py, clients layout ----------------------------------------------------------------------------------
     def _row_owner(self, rows_per_rank):

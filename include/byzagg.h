@@ -194,6 +194,55 @@ int byz_multi_krum_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t
                        int64_t users_count, int64_t corrupted_count, int64_t m, int check_assert,
                        float* out_dev, int32_t* selection_dev, void* stream);
 
+/* ---- geometric median (smoothed Weiszfeld; RFA, Pillutla et al.; not in the reference) --- */
+/* G: n_rows x n_cols fp32, leading dimension ld; n_rows up to byz_limits' selection limit    */
+/* (BYZ_E_UNSUPPORTED beyond), n_cols any.  The pieces:                                       */
+/*   wmean(G, w)[c] = fl32(S_c / W): S_c the fp64 sum over the rows with w_i != 0 of          */
+/*     w_i * (double)x_ic, W = sum w_i, both added sequentially in row order, no fused        */
+/*     multiply-add; a row of weight 0 is skipped, not multiplied (0 * inf never reaches a     */
+/*     column).  Every weight 0: the output is NaN.                                            */
+/*   rowsq(G, z)[i] = sum_c ((double)x_ic - (double)z_c)^2 in fp64, on the difference (not    */
+/*     |x|^2 - 2 x.z + |z|^2), in a fixed order: two calls give the same bits.                 */
+/* The median:                                                                                 */
+/*   mean0 = byz_no_defense_dev's bits.  Every mean0[c] finite: every row active, z = mean0.   */
+/*   Otherwise s0 = rowsq(G, 0), active_i = isfinite(s0_i), z = wmean(G, active ? 1 : 0).     */
+/*   No active row: out all NaN, iterations 0.  d = sqrt(rowsq(G, z)), F = sum of d over the   */
+/*   active rows; for k = 1 .. max_iter: beta_i = active ? 1 / max(nu, d_i) : 0,               */
+/*   z = wmean(G, beta) (fp32), d = sqrt(rowsq(G, z)), F_new = sum of active d,                */
+/*   stop = |F - F_new| <= ftol * F_new, F = F_new, break on stop.  out = z.                   */
+/* F, the stop test and beta are fp64 on the device: nothing synchronises, every launch of the */
+/* loop is enqueued and those after the stop return at once.  A finite input costs            */
+/* 2 + 2 * iterations passes over G.  weights_dev (optional, n_rows fp64): beta / sum(beta) of */
+/* the last update, or uniform over the active rows when there was none (all 0 when no row is  */
+/* active).  nu > 0, max_iter >= 0, ftol >= 0 (BYZ_E_INVALID otherwise, NaN included).  The    */
+/* parameters travel in a struct: the ABI's by-value arguments are int, int64_t, float and     */
+/* pointers.  Cost: 4 launches per update are enqueued for all max_iter updates, whatever the   */
+/* stop (a launch after the stop returns in a few microseconds), so a large max_iter with       */
+/* ftol > 0 still pays for its launches; max_iter beyond BYZ_GEOMED_MAX_ITER returns            */
+/* BYZ_E_UNSUPPORTED.                                                                          */
+#define BYZ_GEOMED_MAX_ITER 65536
+typedef struct byz_geomed_params {
+    double nu;          /* smoothing: the distances are floored at nu                          */
+    int64_t max_iter;   /* Weiszfeld updates at most                                           */
+    double ftol;        /* relative change of the objective that stops the loop                */
+} byz_geomed_params;
+/* One rank's part of rowsq over its columns (z_dev: n_cols floats; sq_dev: n_rows fp64).     */
+int byz_row_sqdist_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                       const float* z_dev, double* sq_dev, void* stream);
+/* wmean (w_dev: n_rows fp64; the caller vouches that they are finite and >= 0).              */
+int byz_weighted_mean_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                          const double* w_dev, float* out_dev, void* stream);
+/* The median (out_dev: n_cols floats).  Asynchronous; byz_geometric_median_info reads back   */
+/* the last call's iterations, excluded (inactive) rows and objective F, and synchronises.     */
+int byz_geometric_median_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                             const byz_geomed_params* params, float* out_dev, double* weights_dev,
+                             void* stream);
+int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* excluded_rows,
+                              double* objective);
+/* The median of a host matrix (out_host: n_cols floats; weights_host optional, n_rows fp64). */
+int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                              const byz_geomed_params* params, float* out_host, double* weights_host);
+
 /* ---- multi-GPU, columns layout: one context per GPU, the HOST owns the communicator ---- */
 /* SURVEY.md 8(e)'s "cheaper equivalent": every rank holds ALL n_rows clients over its own slice of the      */
 /* columns (G_local: n_rows x n_cols_local).  The path has ONE exchange: the n_rows x n_rows fp64 Gram of    */
@@ -232,6 +281,16 @@ int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n
                                int64_t ld, int64_t users_count, int64_t corrupted_count, int64_t m,
                                int check_assert, byz_allreduce_f64_fn allreduce, void* user,
                                float* out_local_dev, int32_t* selection_dev, void* stream);
+
+/* The geometric median over the slices: out_local_dev = this rank's columns of the median.   */
+/* One all-reduce of n_rows + 1 doubles for the finiteness fallback (every rank's squared      */
+/* norms where its own columns are not finite, and its flag), then one of n_rows per-row       */
+/* partials per rowsq: 2 + max_iter calls in all, on every rank, whatever the iteration the    */
+/* loop stops at (the stop is decided on all-reduced data, the same on every rank).            */
+int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows,
+                                     int64_t n_cols_local, int64_t ld, const byz_geomed_params* params,
+                                     byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
+                                     double* weights_dev, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
