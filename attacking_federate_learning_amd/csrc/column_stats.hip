@@ -14,16 +14,9 @@
 #include "common.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace byz {
 namespace {
-
-int env_int(const char* name, int fallback) {
-    const char* v = std::getenv(name);
-    return v ? std::atoi(v) : fallback;
-}
-
 
 constexpr int kThreads = 256;
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -393,15 +386,15 @@ __global__ __launch_bounds__(NW * 64) void column_resident_kernel(
 }
 
 // vec -> every row of G (malicious.py:26-27: all malicious clients get ONE array).  VEC = 4: 16-byte stores (rows and the
-// vector 16-byte aligned), a workgroup owns RUN x 4 KiB CONSECUTIVE bytes of every row it visits -- with one 4 KiB piece per
-// row visit (round 3) every wave's next store lay a whole row further on and HBM saw 1 KiB writes scattered over thousands of
-// rows: 8.0 ms for 2400 rows x 3.125e6 columns (30 GB), 6.9 / 6.1 / 5.9 ms with RUN = 4 / 8 / 16 (5.1 TB/s;
-// scripts/broadcast_probe.py, BYZ_BROADCAST_RUN); VEC = 1: any alignment.
-template <int VEC, int RUN>
+// vector 16-byte aligned), a workgroup owns kBroadcastRun x 4 KiB CONSECUTIVE bytes of every row it visits (launch_broadcast_rows
+// says why); VEC = 1: any alignment.
+constexpr int kBroadcastRun = 16;
+template <int VEC>
 __global__ __launch_bounds__(kThreads) void broadcast_rows_kernel(float* __restrict__ G, int64_t n_rows,
                                                                   int64_t n_cols, int64_t ld,
                                                                   const float* __restrict__ vec) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    constexpr int RUN = kBroadcastRun;
     const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * RUN * kThreads + threadIdx.x) * VEC;
     if constexpr (VEC == 4) {
         f32x4 v[RUN];
@@ -589,31 +582,17 @@ int launch_broadcast_rows(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols
                           hipStream_t stream) {
     KernelTimer t(ctx, BYZ_K_MISC, stream);
     const bool wide = ld % 4 == 0 && (reinterpret_cast<uintptr_t>(G) & 15u) == 0 && (reinterpret_cast<uintptr_t>(vec) & 15u) == 0;
-    // 4 KiB pieces of a row a workgroup writes back to back: one of the instantiated 1, 2, 4, 8, 16 (anything else is 16 --
-    // the grid below must be sized for the RUN that is launched)
-    int run = env_int("BYZ_BROADCAST_RUN", 16);
-    if (run != 1 && run != 2 && run != 4 && run != 8) run = 16;
-    const int64_t per_wg = static_cast<int64_t>(kThreads) * (wide ? 4 : 1) * run;
+    // kBroadcastRun = 16 pieces of 4 KiB of a row that a workgroup writes back to back.  With one piece per row visit (round 3)
+    // every wave's next store lay a whole row further on and HBM saw 1 KiB writes scattered over thousands of rows: 8.0 ms
+    // for 2400 rows x 3.125e6 columns (30 GB); 6.9 / 6.1 / 5.9 ms with runs of 4 / 8 / 16 pieces (5.1 TB/s).
+    const int64_t per_wg = static_cast<int64_t>(kThreads) * (wide ? 4 : 1) * kBroadcastRun;
     const unsigned blocks = static_cast<unsigned>(ceil_div(n_cols, per_wg));
     unsigned ysplit = static_cast<unsigned>(ceil_div(static_cast<int64_t>(ctx->num_cus) * 8, blocks));
     if (ysplit > n_rows) ysplit = static_cast<unsigned>(n_rows);
     if (ysplit < 1) ysplit = 1;
     const dim3 grid(blocks, ysplit);
-#define BYZ_BC(V, R) broadcast_rows_kernel<V, R><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, vec)
-    if (wide) {
-        if (run == 1) BYZ_BC(4, 1);
-        else if (run == 2) BYZ_BC(4, 2);
-        else if (run == 4) BYZ_BC(4, 4);
-        else if (run == 8) BYZ_BC(4, 8);
-        else BYZ_BC(4, 16);
-    } else {
-        if (run == 1) BYZ_BC(1, 1);
-        else if (run == 2) BYZ_BC(1, 2);
-        else if (run == 4) BYZ_BC(1, 4);
-        else if (run == 8) BYZ_BC(1, 8);
-        else BYZ_BC(1, 16);
-    }
-#undef BYZ_BC
+    if (wide) broadcast_rows_kernel<4><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, vec);
+    else broadcast_rows_kernel<1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, vec);
     return check_launch("broadcast_rows_kernel");
 }
 

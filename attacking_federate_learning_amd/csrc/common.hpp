@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -232,6 +233,12 @@ inline int64_t next_pow2(int64_t v) {
     int64_t p = 1;
     while (p < v) p <<= 1;
     return p;
+}
+
+// an integer environment switch: `fallback` when the variable is unset
+inline int env_int(const char* name, int fallback) {
+    const char* v = std::getenv(name);
+    return v ? std::atoi(v) : fallback;
 }
 
 // ---- kernel launchers (one per .hip file) -------------------------------------------------------

@@ -47,6 +47,8 @@ constexpr int LDS_STRIDE = BK + 4;   // 36 floats = 144 B: 16-byte aligned, conf
 constexpr int THREADS = 256;
 constexpr int kFlushK = 2048;        // longest fp32 accumulation chain
 constexpr int kLevel1 = 8;           // level-0 chains per level-1 fp32 sum
+constexpr int kChunkStages = 8192 / BK;   // K stages per chunk of the chunked schedule: 8192 columns, which end before level 1
+                                          // spills to the slab (gram_planes.hip's kChunkCols is the same chunk)
 constexpr int TILE_FLOATS = TM * LDS_STRIDE;
 constexpr int kStatusLostTicket = 1;     // bits of the context's sticky device status word
 constexpr int kStatusPairOverflow = 2;
@@ -806,11 +808,6 @@ __global__ __launch_bounds__(256) void duplicate_copy_kernel(float* __restrict__
     dist[i * n + j] = ri == rj ? 0.0f : dist[static_cast<int64_t>(ri) * n + rj];
 }
 
-int env_int(const char* name, int fallback) {
-    const char* v = std::getenv(name);
-    return v ? std::atoi(v) : fallback;
-}
-
 }  // namespace
 
 // Gram of the n_rows logical rows G[row_index[r]] (row_index == nullptr: the rows themselves)
@@ -851,8 +848,7 @@ static int launch_gram_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_
     const int64_t slots = static_cast<int64_t>(ctx->num_cus) * 2;
     // few tiles and a short K (the reference's own sizes: N = 100, D = 79,510 is ONE tile): allow slabs of 128
     // columns so that the tile count x slab count still covers the chip
-    int64_t min_stages = env_int("BYZ_GRAM_MIN_STAGES", 0);
-    if (min_stages <= 0) min_stages = plan_tiles * (stages / 16) < slots ? 4 : 16;
+    const int64_t min_stages = plan_tiles * (stages / 16) < slots ? 4 : 16;
     int64_t max_splits = stages / min_stages;
     if (max_splits < 1) max_splits = 1;
     if (max_splits > 4096) max_splits = 4096;
@@ -875,11 +871,6 @@ static int launch_gram_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_
     // and in the reduction than they gain in streaming parallelism (measured at N = 100, D = 79,510: 85 us per Krum
     // round with 256 slabs, 100 us with 512, 97 us with 128)
     if (plan_tiles == 1 && splits > ctx->num_cus) splits = ctx->num_cus;
-    const int forced = env_int("BYZ_GRAM_SPLITS", 0);
-    if (forced > 0) splits = forced;
-    if (splits < 1) splits = 1;
-    if (splits > stages) splits = stages;
-    if (splits > 65535) splits = 65535;
     // Arithmetic of the contraction (BYZ_GRAM_MODE overrides):
     //   exact   fp32-input MFMA, bit-for-bit an fmaf chain; the default while the problem is at most two tiles wide
     //           (N <= 256), where the kernel is launch/HBM bound anyway;
@@ -889,12 +880,10 @@ static int launch_gram_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_
     const std::string mode_s = mode_env ? mode_env : (n_tiles_all >= 4 ? "split" : "exact");
     const bool dma = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(G) % 16 == 0) && env_int("BYZ_GRAM_NO_DMA", 0) == 0;
     const bool split_mode = dma && (mode_s == "split" || mode_s == "f16x2");   // f16x2 exists only on pre-split operands
-    // chunked schedule (see the kernel): many tiles and a long K
-    const int64_t chunk_stages = env_int("BYZ_GRAM_CHUNK_COLS", 8192) / BK;
-    const bool chunked = plan_tiles >= 256 && stages > 2 * chunk_stages && env_int("BYZ_GRAM_NO_CHUNKS", 0) == 0 &&
-                         chunk_stages * BK <= 8192;   // a chunk must end before level 1 spills to the slab
-    if (chunked) splits = ceil_div(stages, chunk_stages);
-    const int64_t stages_per_split = chunked ? chunk_stages : ceil_div(stages, splits);
+    // chunked schedule (see the kernel): many tiles and a long K, chunks of kChunkStages
+    const bool chunked = plan_tiles >= 256 && stages > 2 * kChunkStages;
+    if (chunked) splits = ceil_div(stages, kChunkStages);
+    const int64_t stages_per_split = chunked ? kChunkStages : ceil_div(stages, splits);
     splits = ceil_div(stages, stages_per_split);
     // the fp32 slab format is only for K ranges that fit ONE level-0 chain
     const bool wide = chunked || stages_per_split * BK > (split_mode ? 256 : kFlushK);
@@ -942,7 +931,7 @@ static int launch_gram_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_
     // long K and many tiles: the operands are split ONCE into 16-bit planes (gram_planes.hip) instead of once per tile.
     //   BYZ_GRAM_MODE unset / f16x2: two fp16 planes, three MFMAs per block (error 6e-8, see gram_planes.hip);
     //   BYZ_GRAM_MODE=split:         three bf16 planes, bitwise the fused split kernel's slabs
-    const bool planes_ok = chunked && dma && chunk_stages * BK == 8192 && gram_planes_enabled();
+    const bool planes_ok = chunked && dma && gram_planes_enabled();
     const bool f16 = planes_ok && (mode_env == nullptr || mode_s == "f16x2");
     const bool planes = planes_ok && (f16 || split_mode);
     if (planes) {

@@ -36,7 +36,6 @@
 // of four 256-row blocks and the XCDs claim runs of units from one counter.
 #include "common.hpp"
 
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -1149,11 +1148,6 @@ __global__ __launch_bounds__(256) void chunk_reduce_kernel(const float* __restri
         }
         *reinterpret_cast<f64x4*>(out + idx) = v;
     }
-}
-
-int env_int(const char* name, int fallback) {
-    const char* v = std::getenv(name);
-    return v ? std::atoi(v) : fallback;
 }
 
 }  // namespace

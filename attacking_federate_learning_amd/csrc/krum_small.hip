@@ -30,8 +30,6 @@
 #include "common.hpp"
 #include "lane_exchange.hpp"
 
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 namespace byz {
@@ -90,8 +88,7 @@ __device__ __forceinline__ f32x4 load4_guarded(const float* __restrict__ row, in
 template <bool TINY, int PER>
 __global__ __launch_bounds__(kThreads, 1) void small_gram_kernel(const float* __restrict__ G, int n_rows, int64_t n_cols,
                                                                  int64_t ld, int n_slices, float* __restrict__ slabs,
-                                                                 float* __restrict__ diag_slabs, float* __restrict__ score_board,
-                                                                 int dbg) {
+                                                                 float* __restrict__ diag_slabs, float* __restrict__ score_board) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -209,13 +206,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_gram_kernel(const float* __
     auto split_to = [&](f32x4 (&v)[8], int s, unsigned char* buf, auto masked_c) __attribute__((always_inline)) {
         constexpr bool kMasked = decltype(masked_c)::value;
         int* shifts = reinterpret_cast<int*>(buf + 2 * kPlaneBytes);
-        if (dbg & 2) {           // timing experiment: the loads are consumed, nothing is split
-            float any = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) any += v[k][0];
-            if (any == 1.2345e38f) shifts[r_local] = 1;
-            return;
-        }
         if constexpr (kMasked && !TINY) {
             // columns of the ragged slice's window that belong to the slice before it
             const int64_t k0 = static_cast<int64_t>(s) * kSlice;
@@ -254,7 +244,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_gram_kernel(const float* __
         }
     };
     auto multiply_from = [&](const unsigned char* buf) __attribute__((always_inline)) {
-        if (dbg & 1) return;     // timing experiment: no MFMAs (BYZ_KRUM_SMALL_DBG)
         if (nb == 2) multiply(std::integral_constant<int, 2>{}, buf);
         else if (nb == 1) multiply(std::integral_constant<int, 1>{}, buf);
     };
@@ -409,23 +398,13 @@ __device__ double pair_sq_distance(const float* __restrict__ a, const float* __r
     return total;
 }
 
-// development aid (BYZ_KRUM_SMALL_TIMING=1): s_memtime stamps of K2's phases, taken by thread 0 of every workgroup
-constexpr int kRowStamps = 8;
-__device__ unsigned long long g_rows_stamps[kMaxRows * kRowStamps];
-#define BYZ_STAMP(k)                                                                              \
-    do {                                                                                          \
-        if (timing && threadIdx.x == 0) g_rows_stamps[blockIdx.x * kRowStamps + (k)] = __builtin_amdgcn_s_memtime();   \
-    } while (0)
-
 constexpr uint32_t kScoreSentinel = 0xffc0dead;   // "no score yet": K1 writes it, K2's rows overwrite it (never a published score)
 constexpr int kGroups = 16;                       // thread groups of the slab sums (32 threads x 4 columns each)
 constexpr int kMaxPerGroup = 256 / kGroups;       // K1 launches at most 256 workgroups: at most 16 slabs per group
 
-// TIMING (BYZ_KRUM_SMALL_TIMING): the phase stamps.  A template parameter: as a flag in device memory it was a dependent scalar
-// load at the head of a 10 us kernel.
 // PG: slabs per thread group, a multiple of 4 with 16 PG >= n_slabs (the loads of a group are all issued before its first add:
 // with fewer slabs than 256 the shorter forms issue fewer of them).
-template <bool TIMING, int PG>
+template <int PG>
 __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
     static_assert(PG % 4 == 0 && PG >= 4 && PG <= kMaxPerGroup, "slabs per group");
     __shared__ double part[2][kGroups][kMaxRows];   // [row entries | diagonal][group][column]
@@ -437,8 +416,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x;
     const int n = p.n;
-    constexpr bool timing = TIMING;
-    BYZ_STAMP(0);
 
     // ---- 1. the row of the Gram and the diagonal
     {
@@ -495,7 +472,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
     }
     if (tid == 0) words[0] = 0;
     __syncthreads();
-    BYZ_STAMP(1);
 
     // ---- 2. distances; what the Gram identity cannot resolve
     if (tid < kMaxRows) {
@@ -537,7 +513,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
         __syncthreads();
     }
     if (tid < n) p.dist[static_cast<int64_t>(i) * n + tid] = d_row[tid];
-    BYZ_STAMP(2);
     if (p.prefix_len < 0) return;
 
     // ---- 3. the score: one wave sorts the row in registers (two values per lane, bitonic network); the prefix is then added
@@ -564,7 +539,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
         if (sc != sc) sc = __uint_as_float(0x7fc00000u);
         if (lane == 0) __hip_atomic_store(p.scores + i, sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    BYZ_STAMP(3);
     if (p.out_row == nullptr && i != 0) return;     // only the index is wanted: workgroup 0 reports it
     // Everybody who needs the winner polls the n scores until none is the sentinel and runs the argmin on what it polled
     // (128 scores, two per lane).  All n <= 128 workgroups are resident: the spin is bounded, a time-out sets the status word.
@@ -585,7 +559,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
             __builtin_amdgcn_s_sleep(1);
         }
         if (!ok && lane == 0) atomicOr(p.status, kStatusSmallTimeout);
-        if (timing && lane == 0) g_rows_stamps[blockIdx.x * kRowStamps + 4] = __builtin_amdgcn_s_memtime();
         // argmin in visit order 1, 0, 2, ... with a strict '<' against 1e20 (defences.py:27-37) = the smallest 64-bit key
         // (order-preserving score bits << 32 | visit position) among the scores below 1e20 (NaN and +inf are not; + 0.0f
         // folds a -0.0 onto +0.0, which compare equal)
@@ -623,7 +596,6 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
         }
     }
     __syncthreads();
-    BYZ_STAMP(5);
     if (p.out_row == nullptr || words[2] < 0) return;
     // ---- everybody copies its share of the winning row
     const float* src = p.G + static_cast<int64_t>(words[2]) * p.ld;
@@ -631,9 +603,7 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
     const int64_t k0 = per * blockIdx.x;
     const int64_t k1 = k0 + per < p.n_cols ? k0 + per : p.n_cols;
     for (int64_t k = k0 + tid; k < k1; k += kThreads) p.out_row[k] = src[k];
-    BYZ_STAMP(6);
 }
-#undef BYZ_STAMP
 
 // ---- K4 ---------------------------------------------------------------------------------------------------------------
 // One wave per row: the row's n - 1 distances (+inf in the self slot and past n) sorted ascending in registers, two per
@@ -722,10 +692,14 @@ __global__ __launch_bounds__(256) void small_pick_kernel(const float* __restrict
 // on the GPU is K1 (16.0 us: 31.8 MB at 2.0 TB/s) plus four trivial dependent kernels at ~4.5 us EACH -- the price of a
 // kernel boundary with its cache write-back on this part, not their work.)
 
-int env_int(const char* name, int fallback) {
-    const char* v = std::getenv(name);
-    return v ? std::atoi(v) : fallback;
-}
+// K1's ten forms: TINY, then PER = 0 (the loop form), 1, ..., 8
+constexpr decltype(&small_gram_kernel<true, 0>) kGramForms[] = {
+    small_gram_kernel<true, 0>,  small_gram_kernel<false, 0>, small_gram_kernel<false, 1>, small_gram_kernel<false, 2>,
+    small_gram_kernel<false, 3>, small_gram_kernel<false, 4>, small_gram_kernel<false, 5>, small_gram_kernel<false, 6>,
+    small_gram_kernel<false, 7>, small_gram_kernel<false, 8>};
+// K2's forms: PG = 4, 8, 12, 16 slabs per thread group
+constexpr decltype(&small_rows_kernel<4>) kRowsForms[] = {small_rows_kernel<4>, small_rows_kernel<8>, small_rows_kernel<12>,
+                                                          small_rows_kernel<16>};
 
 }  // namespace
 
@@ -757,11 +731,10 @@ static int small_round(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
                 "small distances: bad shape %lld x %lld ld %lld", (long long)n_rows, (long long)n_cols, (long long)ld);
     const int n = static_cast<int>(n_rows);
     const int64_t n_slices = ceil_div(n_cols, kSlice);
-    // one workgroup per CU at most; the grid is sized so that everybody gets the same number of slices (+- 1)
-    // BYZ_KRUM_SMALL_GRID (experiments): a cap on K1's workgroups below 256 -- fewer, longer-lived workgroups, fewer slabs for K2
-    int cap = env_int("BYZ_KRUM_SMALL_GRID", 256);
-    cap = cap < 1 ? 1 : (cap > 256 ? 256 : cap);
-    if (ctx->num_cus < cap) cap = ctx->num_cus;
+    // one workgroup per CU at most; the grid is sized so that everybody gets the same number of slices (+- 1).  256 workgroups
+    // on the MI355X: fewer, longer-lived ones (and fewer slabs for K2) were slower from the first step (EXPERIMENTS.md K1:
+    // 26.3 us per round at 256, 28.0 at 160, 30.5 at 128)
+    const int cap = ctx->num_cus < 256 ? ctx->num_cus : 256;
     const int grid = static_cast<int>(ceil_div(n_slices, ceil_div(n_slices, cap)));
     const int64_t per = ceil_div(n_slices, grid);   // (per - 1) * grid < n_slices: only a workgroup's last slice can be ragged or missing
     // one full 128 x 128 slab per workgroup, then one compact diagonal per workgroup
@@ -771,51 +744,25 @@ static int small_round(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     float* slabs = ctx->gram_partials.as<float>();
     float* diag_slabs = slabs + slab_floats;
     if (!ctx->small_configured) {   // per context: the attribute belongs to the (function, device) pair
-#define BYZ_ATTR(T, P)                                                                            \
-    BYZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&small_gram_kernel<T, P>),          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kGramLds))
-        BYZ_ATTR(true, 0);
-        BYZ_ATTR(false, 0);
-        BYZ_ATTR(false, 1);
-        BYZ_ATTR(false, 2);
-        BYZ_ATTR(false, 3);
-        BYZ_ATTR(false, 4);
-        BYZ_ATTR(false, 5);
-        BYZ_ATTR(false, 6);
-        BYZ_ATTR(false, 7);
-        BYZ_ATTR(false, 8);
-#undef BYZ_ATTR
+        for (auto kernel : kGramForms)
+            BYZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGramLds));
         ctx->small_configured = true;
     }
-    // BYZ_KRUM_SMALL_SKIP (timing experiments only, WRONG results): bit 0 no K1, bit 1 no K2 (scripts/c2_skip_probe.sh)
-    const int skip = env_int("BYZ_KRUM_SMALL_SKIP", 0);
-    if (!(skip & 1)) {
+    const bool tiny = n_cols < kSlice;
+    {
         KernelTimer t(ctx, BYZ_K_GRAM, stream);
-        const int unrolled = env_int("BYZ_KRUM_SMALL_UNROLL", 1) != 0 && per <= 8 ? static_cast<int>(per) : 0;
-#define BYZ_K1(T, P)                                                                               \
-    small_gram_kernel<T, P><<<static_cast<unsigned>(T ? 1 : grid), kThreads, kGramLds, stream>>>(    \
-        G, n, n_cols, ld, static_cast<int>(T ? 1 : n_slices), slabs, diag_slabs, ctx->scores.as<float>(), env_int("BYZ_KRUM_SMALL_DBG", 0))
-        if (n_cols < kSlice) BYZ_K1(true, 0);
-        else switch (unrolled) {
-            case 1: BYZ_K1(false, 1); break;
-            case 2: BYZ_K1(false, 2); break;
-            case 3: BYZ_K1(false, 3); break;
-            case 4: BYZ_K1(false, 4); break;
-            case 5: BYZ_K1(false, 5); break;
-            case 6: BYZ_K1(false, 6); break;
-            case 7: BYZ_K1(false, 7); break;
-            case 8: BYZ_K1(false, 8); break;
-            default: BYZ_K1(false, 0); break;
-        }
-#undef BYZ_K1
+        // PER = per slices unrolled; beyond eight (more than 2^18 columns, or fewer than 256 CUs) the loop form, PER = 0
+        const int unrolled = per <= 8 ? static_cast<int>(per) : 0;
+        kGramForms[tiny ? 0 : 1 + unrolled]<<<static_cast<unsigned>(tiny ? 1 : grid), kThreads, kGramLds, stream>>>(
+            G, n, n_cols, ld, static_cast<int>(tiny ? 1 : n_slices), slabs, diag_slabs, ctx->scores.as<float>());
         BYZ_TRY(check_launch("small_gram_kernel"));
     }
-    if (!(skip & 2)) {
+    {
         KernelTimer t(ctx, prefix_len >= 0 ? BYZ_K_ROW_SORT : BYZ_K_DISTANCES, stream);
         RowsArgs p;
         p.slabs = slabs;
         p.diag_slabs = diag_slabs;
-        p.n_slabs = n_cols < kSlice ? 1 : grid;
+        p.n_slabs = tiny ? 1 : grid;
         p.n = n;
         p.G = G;
         p.n_cols = n_cols;
@@ -826,34 +773,9 @@ static int small_round(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
         p.winner = winner_dev;
         p.out_row = out_row;
         p.status = device_status_word(ctx);
-        const bool stamps = env_int("BYZ_KRUM_SMALL_TIMING", 0) != 0;
-        const int pg = 4 * static_cast<int>(ceil_div(p.n_slabs, 4 * kGroups));   // 4, 8, 12 or 16 slabs per thread group
-#define BYZ_K2(TM)                                                                                 \
-    switch (pg) {                                                                                 \
-        case 4: small_rows_kernel<TM, 4><<<static_cast<unsigned>(n), kThreads, 0, stream>>>(p); break;   \
-        case 8: small_rows_kernel<TM, 8><<<static_cast<unsigned>(n), kThreads, 0, stream>>>(p); break;   \
-        case 12: small_rows_kernel<TM, 12><<<static_cast<unsigned>(n), kThreads, 0, stream>>>(p); break; \
-        default: small_rows_kernel<TM, 16><<<static_cast<unsigned>(n), kThreads, 0, stream>>>(p); break; \
-    }
-        if (stamps) { BYZ_K2(true) } else { BYZ_K2(false) }
-#undef BYZ_K2
+        const int64_t quads = ceil_div(p.n_slabs, 4 * kGroups);   // PG = 4 quads = 4, 8, 12 or 16 slabs per thread group
+        kRowsForms[quads - 1]<<<static_cast<unsigned>(n), kThreads, 0, stream>>>(p);
         BYZ_TRY(check_launch("small_rows_kernel"));
-        if (stamps) {
-            static unsigned long long host[kMaxRows * kRowStamps];
-            BYZ_HIP(hipStreamSynchronize(stream));
-            BYZ_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rows_stamps), sizeof(host)));
-            const char* names[7] = {"", "slab sums", "distances", "sort + score + ticket", "wait for all", "argmin", "row copy"};
-            for (int k = 1; k <= 6; ++k) {
-                if (k == 4 && prefix_len < 0) break;
-                double sum = 0, mx = 0;
-                for (int w = 0; w < n; ++w) {
-                    const double dt = static_cast<double>(host[w * kRowStamps + k] - host[w * kRowStamps + k - 1]);
-                    sum += dt;
-                    if (dt > mx) mx = dt;
-                }
-                std::fprintf(stderr, "small_rows %-22s mean %8.0f  max %8.0f ticks\n", names[k], sum / n, mx);
-            }
-        }
     }
     return BYZ_OK;
 }
