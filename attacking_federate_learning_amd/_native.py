@@ -50,6 +50,8 @@ _PROTOTYPES = {
     'byz_krum_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32), c_vp, c_vp],
     'byz_krum_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, _P(c_i32), c_vp],
     'byz_trimmed_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
+    'byz_coordinate_median_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_rank_trimmed_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
     'byz_trimmed_mean_redone': [c_vp, _P(c_i64), c_vp],
     'byz_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_krum_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32), c_vp, c_vp],
@@ -80,6 +82,8 @@ _PROTOTYPES = {
     'byz_krum_select_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32)],
     'byz_drift_attack_host': [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp],
     'byz_multi_krum_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_coordinate_median_host': [c_vp, c_vp, c_i64, c_i64, c_vp],
+    'byz_rank_trimmed_mean_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp],
     'byz_row_sqdist_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_weighted_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_geometric_median_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp],

@@ -496,6 +496,18 @@ int byz_trimmed_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n
     return launch_trimmed_mean(ctx, G, n_rows, n_cols, ld, row_index, keep, out, as_stream(stream));
 }
 
+int byz_coordinate_median_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                              float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    return launch_rank_select(ctx, G, n_rows, n_cols, ld, row_index, 0, true, out, as_stream(stream));
+}
+
+int byz_rank_trimmed_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                              int64_t trim_count, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    return launch_rank_select(ctx, G, n_rows, n_cols, ld, row_index, trim_count, false, out, as_stream(stream));
+}
+
 int byz_trimmed_mean_redone(byz_ctx* ctx, int64_t* tiles_host, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(tiles_host, "trimmed_mean_redone: null output");
@@ -1081,6 +1093,36 @@ int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64
     if (out_host) BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     int32_t words[32];
     return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+}
+
+// the two coordinate-wise rank rules on a host matrix (median: trim_count ignored)
+static int rank_select_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t trim_count, bool median,
+                            float* out_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, median ? "coordinate_median" : "rank_trimmed_mean"));
+    BYZ_REQUIRE(out_host, "%s: null output", median ? "coordinate_median" : "rank_trimmed_mean");
+    if (n_rows > kLargeMaxRows || (!median && (trim_count < 0 || 2 * trim_count >= n_rows)))      // refused before anything is staged
+        return launch_rank_select(ctx, G_host, n_rows, n_cols, n_cols, nullptr, trim_count, median, out_host, nullptr);
+    hipStream_t s = nullptr;
+    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+    BYZ_TRY(ctx->stage_in.ensure(bytes));
+    BYZ_TRY(ctx->stage_out.ensure(static_cast<size_t>(n_cols) * sizeof(float)));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
+    BYZ_TRY(launch_rank_select(ctx, G, n_rows, n_cols, n_cols, nullptr, trim_count, median, out, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    BYZ_HIP(hipStreamSynchronize(s));
+    return BYZ_OK;
+}
+
+int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, float* out_host) {
+    return rank_select_host(ctx, G_host, n_rows, n_cols, 0, true, out_host);
+}
+
+int byz_rank_trimmed_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t trim_count,
+                               float* out_host) {
+    return rank_select_host(ctx, G_host, n_rows, n_cols, trim_count, false, out_host);
 }
 
 int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_geomed_params* params,

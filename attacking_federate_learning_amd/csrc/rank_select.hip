@@ -1,0 +1,295 @@
+// The coordinate-wise median and the rank-trimmed mean (Yin et al. 2018; not in the reference), DESIGN.md 3.3b.
+//
+//   median        out[c] = np.median(col)                      fp32; even count -> fl(fl(a + b) * 0.5f); a NaN anywhere -> NaN
+//   rank-trimmed  kept = np.sort(col)[b : n - b]               NaN of either sign sorts behind +inf, as np.sort has it
+//                 out[c] = fl32(sum of kept in fp64 / (n - 2 b))
+//
+// Both are TWO order statistics of the SAME keys: ranks (n - 1) / 2 and n / 2, or ranks b and n - 1 - b.  One radix select finds
+// them together, 8 bits per pass: the keys are tall_select.hip's order-preserving bits with every NaN mapped to one key behind +inf's; while the
+// two ranks' prefixes agree a key is counted once for both, and once they part each rank counts the keys that match its own prefix.
+// Heights up to 65,535 keep both counts in ONE word of hist[digit][column] (16 bits each, one LDS atomic per key whatever it
+// matches); beyond that each rank has a histogram of 32-bit counters.  Nothing depends on row order: tied keys at a rank's edge are
+// equal values, so with lo / hi the two order statistics the kept multiset is {lo < x < hi} plus c_lo copies of lo and c_hi of hi,
+//     S = sum{x : lo < x < hi} + c_lo * lo + c_hi * hi        (fp64, a fixed order; c_lo, c_hi >= 1: never 0 * inf)
+// and lo == hi (every kept value equal) returns that value as it is.
+//
+// Two shapes of one kernel template:
+//   streamed   RPT == 0: 64 columns per workgroup, sixteen waves split the rows, the column read from HBM once per pass: four
+//              select passes and the sums, FIVE passes (the median: four, its values are read off the keys);
+//   resident   RPT  > 0: the workgroup's COLS x n tile is loaded ONCE into registers as keys (thread (tx, ty) holds rows ty,
+//              ty + RG, ...), the four passes and the sums run over the registers: 4 n D + 4 D bytes of traffic.
+// The dispatcher picks by height alone (pick_shape).
+#include "common.hpp"
+
+namespace byz {
+namespace {
+
+// Every NaN takes one key above +inf's; a resident tile's rows beyond the column's height take the key above that one, so that
+// they sit behind every rank asked for and need no predicate.  (Both are bit patterns of NaNs: no other float maps onto them.)
+constexpr uint32_t kNanKey = 0xfffffffeu;
+constexpr uint32_t kPadKey = 0xffffffffu;
+constexpr int kStreamUnroll = 8;
+constexpr int kResidentBatch = 4;
+constexpr int kSegments = 16;                  // the walk to a rank's digit: sixteen 16-digit segment sums, then 16 + 16 steps
+
+__device__ __forceinline__ uint32_t rank_key(float v) {
+    const uint32_t b = __float_as_uint(v);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return kNanKey;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) {      // (kNanKey -> 0x7ffffffe, a NaN)
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+constexpr int lds_words(int cols, bool wide) { return 256 * cols * (wide ? 2 : 1) + (2 * kSegments + 7) * cols; }
+
+// One workgroup: COLS columns x RG row groups.  WIDE: 32-bit counters, a histogram per rank (more than 65,535 rows).
+template <int COLS, int RG, int RPT, bool WIDE, bool MEDIAN>
+__global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __restrict__ G, int n_rows, int64_t n_cols, int64_t ld,
+                                                                const int32_t* __restrict__ row_index, int rank_lo, int rank_hi,
+                                                                int64_t tiles, float* __restrict__ out) {
+    static_assert(RG >= kSegments && RG <= 128, "sixteen row groups sum the segments; the fp64 partials fit the dead histogram");
+    static_assert(!WIDE || RPT == 0, "a resident tile never needs the wide counters");
+    constexpr int kThreads = COLS * RG;
+    constexpr int kHist = 256 * COLS;
+    extern __shared__ uint32_t lds[];
+    uint32_t* const hist = lds;                                      // [256][COLS]; WIDE: the low rank's
+    uint32_t* const hist_hi = lds + (WIDE ? kHist : 0);              // WIDE: the high rank's, once the prefixes have parted
+    uint32_t* const seg = lds + kHist * (WIDE ? 2 : 1);              // [2][kSegments][COLS]
+    uint32_t* const found = seg + 2 * kSegments * COLS;              // [2][COLS]: the digits found so far
+    int* const left = reinterpret_cast<int*>(found + 2 * COLS);      // [2][COLS]: the rank left inside them
+    uint32_t* const run = reinterpret_cast<uint32_t*>(left + 2 * COLS);   // [2][COLS]: keys equal to the answer
+    uint32_t* const nan_seen = run + 2 * COLS;                       // [COLS]
+    const int tid = threadIdx.x;
+    const int tx = tid % COLS, ty = tid / COLS;
+
+    int64_t tile = blockIdx.x;
+    if constexpr (COLS < 64) {
+        // a row segment of a narrow tile is a part of a 128-byte line: workgroups b and b + 8 (one XCD, dispatched together) take
+        // neighbouring tiles so that the parts of a line meet in one L2
+        const int64_t per = (tiles + 7) / 8;
+        tile = static_cast<int64_t>(blockIdx.x % 8) * per + blockIdx.x / 8;
+        if (tile >= tiles) return;
+    }
+    const int64_t col_raw = tile * COLS + tx;
+    const bool real = col_raw < n_cols;
+    const int64_t col = real ? col_raw : n_cols - 1;
+    const int last_row = n_rows - 1;
+    auto load = [&](int r) -> float {
+        const int rr = r < last_row ? r : last_row;
+        const int64_t src = row_index ? row_index[rr] : rr;
+        return G[src * ld + col];
+    };
+
+    // ---- the resident tile: kept as keys
+    uint32_t keys[RPT > 0 ? RPT : 1];
+    if constexpr (RPT > 0) {
+        static_assert(RPT % kResidentBatch == 0, "the tile is loaded in whole batches");
+#pragma unroll
+        for (int j0 = 0; j0 < RPT; j0 += kResidentBatch) {      // (a batch of loads in flight per thread; the waves cover the rest)
+            float v[kResidentBatch];
+#pragma unroll
+            for (int j = 0; j < kResidentBatch; ++j) v[j] = load(ty + (j0 + j) * RG);
+#pragma unroll
+            for (int j = 0; j < kResidentBatch; ++j) keys[j0 + j] = ty + (j0 + j) * RG < n_rows ? rank_key(v[j]) : kPadKey;
+        }
+    }
+
+    if (ty == 0) {
+        found[tx] = 0u;
+        found[COLS + tx] = 0u;
+        left[tx] = rank_lo;
+        left[COLS + tx] = rank_hi;
+        nan_seen[tx] = 0u;
+    }
+
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int i = tid; i < kHist * (WIDE ? 2 : 1); i += kThreads) lds[i] = 0u;
+        __syncthreads();
+        const uint32_t prefix_lo = found[tx], prefix_hi = found[COLS + tx];
+        const bool shared = prefix_lo == prefix_hi;      // (the first pass: both empty)
+        uint32_t nan = 0u;
+        auto count = [&](uint32_t key, bool valid) {
+            const uint32_t above = pass == 0 ? 0u : key >> ((shift + 8) & 31);
+            const bool m_lo = valid && above == prefix_lo, m_hi = valid && above == prefix_hi;
+            const uint32_t slot = ((key >> shift) & 255u) * COLS + tx;
+            if constexpr (WIDE) {
+                if (m_lo) atomicAdd(&hist[slot], 1u);
+                if (m_hi && !shared) atomicAdd(&hist_hi[slot], 1u);
+            } else {
+                const uint32_t add = (m_lo ? 1u : 0u) | (m_hi ? 0x10000u : 0u);
+                if (add != 0u) atomicAdd(&hist[slot], add);
+            }
+            if (MEDIAN && pass == 0) nan |= valid && key == kNanKey ? 1u : 0u;
+        };
+        if constexpr (RPT > 0) {
+#pragma unroll
+            for (int j = 0; j < RPT; ++j) count(keys[j], true);      // (the padding is counted: behind every rank)
+        } else {
+            for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
+                float v[kStreamUnroll];
+#pragma unroll
+                for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
+#pragma unroll
+                for (int j = 0; j < kStreamUnroll; ++j) count(rank_key(v[j]), r0 + j * RG < n_rows);
+            }
+        }
+        if (MEDIAN && pass == 0 && nan != 0u) atomicOr(&nan_seen[tx], 1u);
+        __syncthreads();
+        // the counters of rank `which` (0: low, 1: high)
+        auto counter = [&](int which, int slot) -> uint32_t {
+            if constexpr (WIDE) return (which != 0 && !shared ? hist_hi : hist)[slot];
+            else return which != 0 ? hist[slot] >> 16 : hist[slot] & 0xffffu;
+        };
+        if (ty < kSegments) {
+            uint32_t s_lo = 0u, s_hi = 0u;
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                s_lo += counter(0, (16 * ty + b) * COLS + tx);
+                s_hi += counter(1, (16 * ty + b) * COLS + tx);
+            }
+            seg[ty * COLS + tx] = s_lo;
+            seg[(kSegments + ty) * COLS + tx] = s_hi;
+        }
+        __syncthreads();
+        if (ty < 2) {      // one thread per column and rank walks 16 + 16 counters to the digit that holds the rank
+            const int which = ty;
+            int want = left[which * COLS + tx];
+            int s16 = kSegments - 1;
+            for (int g = 0; g < kSegments; ++g) {
+                const int cnt = static_cast<int>(seg[(which * kSegments + g) * COLS + tx]);
+                if (want < cnt) {
+                    s16 = g;
+                    break;
+                }
+                want -= cnt;
+            }
+            int digit = 16 * s16 + 15;
+            uint32_t cnt = 0u;
+            for (int b = 16 * s16; b < 16 * s16 + 16; ++b) {
+                cnt = counter(which, b * COLS + tx);
+                if (want < static_cast<int>(cnt)) {
+                    digit = b;
+                    break;
+                }
+                want -= static_cast<int>(cnt);
+            }
+            found[which * COLS + tx] = ((which ? prefix_hi : prefix_lo) << 8) | static_cast<uint32_t>(digit);
+            left[which * COLS + tx] = want;
+            run[which * COLS + tx] = cnt;
+        }
+        __syncthreads();
+    }
+
+    const uint32_t key_lo = found[tx], key_hi = found[COLS + tx];
+    if constexpr (MEDIAN) {
+        if (ty != 0 || !real) return;
+        const float lo = key_value(key_lo), hi = key_value(key_hi);
+        float med = rank_lo == rank_hi ? lo : __fmul_rn(__fadd_rn(lo, hi), 0.5f);
+        if (nan_seen[tx] != 0u) med = __uint_as_float(0x7fc00000u);
+        out[col] = med;
+    } else {
+        // ---- the sums: everything strictly between the two order statistics
+        double sum = 0.0;
+        if constexpr (RPT > 0) {
+#pragma unroll
+            for (int j = 0; j < RPT; ++j) {
+                const bool in = keys[j] > key_lo && keys[j] < key_hi;
+                if (in) sum += static_cast<double>(key_value(keys[j]));
+            }
+        } else {
+            for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
+                float v[kStreamUnroll];
+#pragma unroll
+                for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
+#pragma unroll
+                for (int j = 0; j < kStreamUnroll; ++j) {
+                    const uint32_t key = rank_key(v[j]);
+                    const bool in = r0 + j * RG < n_rows && key > key_lo && key < key_hi;
+                    if (in) sum += static_cast<double>(v[j]);
+                }
+            }
+        }
+        double* const part = reinterpret_cast<double*>(hist);      // [RG][COLS], over the dead histogram
+        part[ty * COLS + tx] = sum;
+        __syncthreads();
+        if (ty != 0 || !real) return;
+        const float lo = key_value(key_lo), hi = key_value(key_hi);
+        float result = lo;                     // every kept value equal (a NaN key: NaN)
+        if (key_lo != key_hi) {
+            double total = 0.0;
+            for (int w = 0; w < RG; ++w) total += part[w * COLS + tx];      // a fixed order: the same bits every run
+            // kept copies of lo: from its rank to the end of its run; of hi: from the start of its run to its rank
+            const double c_lo = static_cast<double>(static_cast<int>(run[tx]) - left[tx]);
+            const double c_hi = static_cast<double>(left[COLS + tx] + 1);
+            total += c_lo * static_cast<double>(lo);
+            total += c_hi * static_cast<double>(hi);
+            result = static_cast<float>(total / static_cast<double>(rank_hi - rank_lo + 1));
+        }
+        out[col] = result;
+    }
+}
+
+template <int COLS, int RG, int RPT, bool WIDE, bool MEDIAN>
+int launch_shape(byz_ctx* ctx, const float* G, int n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index, int rank_lo,
+                 int rank_hi, float* out, hipStream_t stream) {
+    const int64_t tiles = ceil_div(n_cols, COLS);
+    const int64_t grid = COLS < 64 ? ceil_div(tiles, 8) * 8 : tiles;
+    BYZ_REQUIRE(grid <= 0x7fffffff, "rank select: too many columns");
+    constexpr int lds_bytes = lds_words(COLS, WIDE) * 4;
+    auto* kernel = &rank_select_kernel<COLS, RG, RPT, WIDE, MEDIAN>;
+    BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), lds_bytes));
+    kernel<<<static_cast<unsigned>(grid), COLS * RG, lds_bytes, stream>>>(G, n_rows, n_cols, ld, row_index, rank_lo, rank_hi, tiles, out);
+    return check_launch("rank_select_kernel");
+}
+
+// Which shape takes a column height: by height alone, never by data (DESIGN.md 3.3b has the timings behind the edges).
+enum Shape { kResident256, kResident1024, kResident2304, kResident4096, kStreamed, kStreamedWide };
+constexpr int kResidentMaxRows = 4096;
+Shape pick_shape(int64_t n_rows) {
+    if (n_rows <= 256) return kResident256;
+    if (n_rows <= 1024) return kResident1024;
+    if (n_rows <= 2304) return kResident2304;
+    if (n_rows <= kResidentMaxRows) return kResident4096;
+    return n_rows <= 65535 ? kStreamed : kStreamedWide;
+}
+
+template <bool MEDIAN>
+int launch_picked(byz_ctx* ctx, const float* G, int n, int64_t n_cols, int64_t ld, const int32_t* row_index, int rank_lo, int rank_hi,
+                  float* out, hipStream_t stream) {
+    switch (pick_shape(n)) {
+        case kResident256: return launch_shape<64, 16, 16, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+        case kResident1024: return launch_shape<16, 32, 32, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+        case kResident2304: return launch_shape<16, 64, 36, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+        case kResident4096: return launch_shape<16, 64, 64, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+        case kStreamed: return launch_shape<64, 16, 0, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+        case kStreamedWide: break;
+    }
+    return launch_shape<64, 16, 0, true, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+}
+
+}  // namespace
+
+int64_t rank_select_resident_max_rows() { return kResidentMaxRows; }
+
+int launch_rank_select(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                       int64_t trim_count, bool median, float* out, hipStream_t stream) {
+    const char* who = median ? "coordinate_median" : "rank_trimmed_mean";
+    BYZ_REQUIRE(G && out && n_rows > 0 && n_cols > 0 && ld >= n_cols, "%s: bad arguments (%lld x %lld, ld %lld)", who,
+                (long long)n_rows, (long long)n_cols, (long long)ld);
+    if (n_rows > kLargeMaxRows) {
+        set_error("%s supports at most %lld rows, got %lld", who, (long long)kLargeMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    const int n = static_cast<int>(n_rows);
+    KernelTimer t(ctx, BYZ_K_TRIMMED_MEAN, stream);
+    if (median) return launch_picked<true>(ctx, G, n, n_cols, ld, row_index, (n - 1) / 2, n / 2, out, stream);
+    BYZ_REQUIRE(trim_count >= 0 && 2 * trim_count < n_rows, "rank_trimmed_mean: trim_count %lld must satisfy 0 <= 2 b < %lld rows",
+                (long long)trim_count, (long long)n_rows);
+    const int b = static_cast<int>(trim_count);
+    return launch_picked<false>(ctx, G, n, n_cols, ld, row_index, b, n - 1 - b, out, stream);
+}
+
+}  // namespace byz

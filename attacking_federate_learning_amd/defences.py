@@ -78,6 +78,22 @@ def geometric_median(users_grads, users_count, corrupted_count, nu=1e-6, max_ite
     return get_engine().geometric_median(users_grads, nu=nu, max_iter=max_iter, ftol=ftol)
 
 
+def coordinate_median(users_grads, users_count, corrupted_count):
+    """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
+    reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the
+    reference's main.py offers only those four."""
+    return get_engine().coordinate_median(users_grads)
+
+
+def rank_trimmed_mean(users_grads, users_count, corrupted_count):
+    """The beta-trimmed mean of Yin et al. 2018 (not in the reference): per column the corrupted_count smallest and the
+    corrupted_count largest values dropped, the rest averaged (in fp64, rounded once).  A different rule from
+    `trimmed_mean`, which keeps the values closest to the median.  Not one of the `defend` keys."""
+    assert users_grads.shape[0] >= 2 * corrupted_count + 1, (
+        'rows>=2*corrupted_count + 1', users_grads.shape[0], corrupted_count)
+    return get_engine().rank_trimmed_mean(users_grads, corrupted_count)
+
+
 defend = {DefenseTypes.Krum: krum,
           DefenseTypes.TrimmedMean: trimmed_mean, DefenseTypes.NoDefense: no_defense,
           DefenseTypes.Bulyan: bulyan}

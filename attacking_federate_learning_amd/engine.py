@@ -492,6 +492,52 @@ class Engine:
             self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
         return out
 
+    def _rank_rule(self, g, trim_count, row_index, validate_index):
+        """The two coordinate-wise rank rules share their plumbing: trim_count None is the median."""
+        m = self._device_matrix(g)
+        if m is None:
+            g = self._host_matrix(g)
+            if row_index is not None:
+                g = np.ascontiguousarray(g[np.asarray(row_index)])
+            n, d = g.shape
+            if n == 0:
+                raise ValueError('row_index selects no rows')
+            out = np.empty(d, dtype=np.float32)
+            if trim_count is None:
+                _check(self.lib.byz_coordinate_median_host(self.ctx, g.ctypes.data_as(ctypes.c_void_p), n, d,
+                                                           out.ctypes.data_as(ctypes.c_void_p)))
+            else:
+                _check(self.lib.byz_rank_trimmed_mean_host(self.ctx, g.ctypes.data_as(ctypes.c_void_p), n, d, int(trim_count),
+                                                           out.ctypes.data_as(ctypes.c_void_p)))
+            return out
+        n_rows, idx_ptr, keep = m.rows, None, None
+        if row_index is not None:
+            idx_ptr, n_rows, keep = self._row_index(row_index, m, validate_index)
+            if n_rows == 0:
+                raise ValueError('row_index selects no rows')
+        out, ptr = self._out_like(m, m.cols)
+        if trim_count is None:
+            _check(self.lib.byz_coordinate_median_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr), _vp(ptr),
+                                                      _vp(m.stream)))
+        else:
+            _check(self.lib.byz_rank_trimmed_mean_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
+                                                      int(trim_count), _vp(ptr), _vp(m.stream)))
+        if keep is not None and not _is_torch(keep):
+            self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
+        return out
+
+    def coordinate_median(self, g, row_index=None, validate_index=True):
+        """Per column np.median of the float32 rows (of g[row_index] when given), bit for bit; a NaN anywhere in a column
+        makes it NaN.  Device tensors, strided views and host matrices as `trimmed_mean` takes them."""
+        return self._rank_rule(g, None, row_index, validate_index)
+
+    def rank_trimmed_mean(self, g, trim_count, row_index=None, validate_index=True):
+        """Per column the mean of np.sort(col)[b : n - b], b = trim_count (0 <= b, 2 b < n), summed in fp64 and rounded to
+        float32 once.  NaN sorts behind +inf (np.sort): up to b of them are trimmed away like any other large value."""
+        if trim_count is None:
+            raise ValueError('rank_trimmed_mean needs a trim count')
+        return self._rank_rule(g, trim_count, row_index, validate_index)
+
     def trimmed_mean_redone(self, stream=None):
         """16-column tiles of the last trimmed mean that the ring selection handed to the general kernel."""
         tiles = ctypes.c_int64(0)

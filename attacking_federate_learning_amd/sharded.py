@@ -91,6 +91,12 @@ class HipKernels:
         return self.engine.trimmed_mean(g_local, g_local.shape[0], corrupted_count, row_index=row_index,
                                         validate_index=False)
 
+    def coordinate_median(self, g_local, row_index=None):
+        return self.engine.coordinate_median(g_local, row_index=row_index, validate_index=False)
+
+    def rank_trimmed_mean(self, g_local, trim_count, row_index=None):
+        return self.engine.rank_trimmed_mean(g_local, trim_count, row_index=row_index, validate_index=False)
+
     def no_defense(self, g_local):
         return self.engine.no_defense(g_local)
 
@@ -274,6 +280,17 @@ class ShardedAggregator:
 
     def trimmed_mean(self, g_local, users_count, corrupted_count, gather=False, total_columns=None):
         return self._maybe_gather(self.kernels.trimmed_mean(g_local, corrupted_count), gather, total_columns)
+
+    def coordinate_median(self, g_local, users_count=None, corrupted_count=None, gather=False, total_columns=None):
+        """columns layout: np.median per column of the rank's own slice; no collective."""
+        return self._maybe_gather(self.kernels.coordinate_median(g_local), gather, total_columns)
+
+    def rank_trimmed_mean(self, g_local, users_count, corrupted_count, gather=False, total_columns=None):
+        """columns layout: per column of the rank's own slice the corrupted_count smallest and largest values dropped, the
+        rest averaged; no collective."""
+        assert g_local.shape[0] >= 2 * corrupted_count + 1, (
+            'rows>=2*corrupted_count + 1', g_local.shape[0], corrupted_count)
+        return self._maybe_gather(self.kernels.rank_trimmed_mean(g_local, corrupted_count), gather, total_columns)
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

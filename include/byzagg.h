@@ -147,6 +147,30 @@ int byz_trimmed_mean_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64
 /* handed to the general kernel (ties at the window edge, outliers, non-finite values); synchronises.    */
 int byz_trimmed_mean_redone(byz_ctx* ctx, int64_t* tiles_host, void* stream);
 
+/* ---- the coordinate-wise median and the rank-trimmed mean (Yin et al. 2018; not in the reference) ---- */
+/* Per column of the logical matrix (row r is G[row_index[r]] when row_index_dev is given), n = n_rows:   */
+/*   median        np.median(col) for float32 input, bit for bit: the middle value for odd n, for even n  */
+/*                 fl32(fl32(a + b) * 0.5f) of the two middle values; NaN if the column holds a NaN of    */
+/*                 either sign.  +0.0 and -0.0 compare equal: which of the two comes back is unspecified. */
+/*   rank-trimmed  kept = np.sort(col)[b : n - b] with b = trim_count, 0 <= b and 2 b < n (else           */
+/*                 BYZ_E_INVALID); out = fl32(sum of kept in fp64 / (n - 2 b)).  NaN of either sign sorts */
+/*                 behind +inf as np.sort has it, so up to b NaNs or infinities on a side are trimmed     */
+/*                 away; a NaN that survives makes the column NaN, +inf and -inf both kept give NaN, one  */
+/*                 of them kept gives that infinity.  The sum is S = sum{x : lo < x < hi} + c_lo * lo +   */
+/*                 c_hi * hi in fp64 in a fixed order (lo, hi the order statistics of ranks b and         */
+/*                 n - 1 - b, c_lo, c_hi >= 1 their kept copies), rounded to fp32 once after the division:*/
+/*                 the same bits on every run and for every matrix width.  With ref the exactly rounded   */
+/*                 mean of kept and mabs the mean of |kept|:                                              */
+/*                 |out - ref| <= 2^-23 |ref| + 2^-30 mabs + 2^-149.  A column whose kept values are all  */
+/*                 equal returns that value exactly; b = 0 is the column mean (in fp64: not no_defense's  */
+/*                 bits); for NaN-free columns, odd n and b = (n - 1) / 2 it is the median exactly.       */
+/* More than 2^20 rows (byz_limits' trimmed figure): BYZ_E_UNSUPPORTED.  Asynchronous on `stream`.        */
+int byz_coordinate_median_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols,
+                              int64_t ld, const int32_t* row_index_dev, float* out_dev, void* stream);
+int byz_rank_trimmed_mean_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols,
+                              int64_t ld, const int32_t* row_index_dev, int64_t trim_count,
+                              float* out_dev, void* stream);
+
 /* ---- defences.bulyan (reference defences.py:55-70) ------------------------------------- */
 /* Selection loop on a distance matrix: theta = users_count - 2*corrupted_count picks, each */
 /* the Krum winner among the rows still present.  Exact fp64 running scores pick the winner  */
@@ -389,6 +413,13 @@ int byz_drift_attack_host(byz_ctx* ctx, const float* rows_host, int64_t n_rows, 
 int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                         int64_t users_count, int64_t corrupted_count, int64_t m, float* out_host,
                         int32_t* selection_host);
+
+/* The coordinate-wise median and the rank-trimmed mean of a host matrix (C-contiguous fp32);  */
+/* out_host: n_cols floats.  Synchronous.                                                      */
+int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                               float* out_host);
+int byz_rank_trimmed_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                               int64_t trim_count, float* out_host);
 
 /* ---- per-kernel timing (bench.py's roofline leg) --------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on its own stream.          */
