@@ -44,33 +44,61 @@ int read_i32(byz_ctx* ctx, const int32_t* dev, int32_t* host, int64_t count, hip
 
 // The device-side scalars (common.hpp: layout of ctx->small) in one read-back; the sticky status word is checked and
 // cleared here, so that every entry point that synchronises anyway also reports what a kernel could only flag.
-int read_small(byz_ctx* ctx, int32_t (&words)[32], hipStream_t stream) {
-    BYZ_TRY(read_i32(ctx, ctx->small.as<int32_t>(), words, 32, stream));
-    const int32_t sticky = words[16];
+int read_small(byz_ctx* ctx, int32_t (&words)[kSmallWords], hipStream_t stream) {
+    BYZ_TRY(read_i32(ctx, ctx->small.as<int32_t>(), words, kSmallWords, stream));
+    const int32_t sticky = words[kWordStatus];
     if (sticky != 0) {
         BYZ_HIP(hipMemsetAsync(device_status_word(ctx), 0, sizeof(int32_t), stream));
-        if (sticky & 1) {
+        if (sticky & kStatusLostTicket) {
             set_error("gram: a K chunk never received its tile's ticket (workgroups dispatched out of order or the GPU is "
                       "shared); the distance matrix of this call is invalid");
             return BYZ_E_HIP;
         }
-        if (sticky & 8) {
+        if (sticky & kStatusSmallTimeout) {
             set_error("krum (N <= 128): not every row's workgroup reported its score in time (GPU shared with another "
                       "process?); the result of this call is invalid");
             return BYZ_E_HIP;
         }
-        if (sticky & 16) {
+        if (sticky & kStatusNoTurn) {
             set_error("column statistics: a wave of the register-resident kernel never got its turn; the statistics of this "
                       "call are invalid (please report the shape)");
             return BYZ_E_HIP;
         }
-        if (sticky & 4) {
+        if (sticky & kStatusFalseTwin) {
             set_error("distances: two rows have bitwise equal Gram entries but differ; their near-duplicate pairs were not "
                       "re-evaluated (please report the input)");
             return BYZ_E_UNSUPPORTED;
         }
         set_error("distances: %d near-duplicate pairs exceed the list capacity (BYZ_NEAR_PAIR_CAPACITY); their distances "
-                  "were not re-evaluated", words[17]);
+                  "were not re-evaluated", words[kWordNearPairs]);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+// read_small where nothing but the flagged failures is of interest: synchronises; a kernel that flagged one makes the call fail
+int check_small(byz_ctx* ctx, hipStream_t stream) {
+    int32_t words[kSmallWords];
+    return read_small(ctx, words, stream);
+}
+
+// the Krum winner's index to the host, when the caller asked for it (one synchronisation, the status word with it)
+int read_winner(byz_ctx* ctx, int32_t* index_host, hipStream_t stream) {
+    if (!index_host) return BYZ_OK;
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, stream));
+    *index_host = words[kWordKrumWinner];
+    return BYZ_OK;
+}
+
+// the near-duplicate pairs the last distance kernel listed, refused when the list could not hold them
+int near_pair_count(byz_ctx* ctx, int64_t* count, hipStream_t stream) {
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, stream));
+    *count = words[kWordNearPairs];
+    if (*count > ctx->near_pair_capacity) {
+        set_error("distances: %lld near-duplicate pairs exceed the list capacity %lld (BYZ_NEAR_PAIR_CAPACITY)", (long long)*count,
+                  (long long)ctx->near_pair_capacity);
         return BYZ_E_UNSUPPORTED;
     }
     return BYZ_OK;
@@ -88,6 +116,42 @@ int check_matrix(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, con
                   (long long)n_cols, (long long)ld);
         return BYZ_E_INVALID;
     }
+    return BYZ_OK;
+}
+
+int check_krum_assert(int check_assert, int64_t users_count, int64_t corrupted_count) {
+    if (check_assert && !(users_count >= 2 * corrupted_count + 1)) {  // defences.py:25
+        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count, (long long)corrupted_count);
+        return BYZ_E_PRECONDITION;
+    }
+    return BYZ_OK;
+}
+
+int check_bulyan_precondition(int64_t users_count, int64_t corrupted_count) {
+    if (!(users_count >= 4 * corrupted_count + 3)) {  // defences.py:56
+        set_error("bulyan: users_count >= 4*corrupted_count + 3 violated (%lld, %lld)", (long long)users_count,
+                  (long long)corrupted_count);
+        return BYZ_E_PRECONDITION;
+    }
+    return BYZ_OK;
+}
+
+// the row-count ceiling of the geometric median's family
+int check_row_ceiling(const char* who, int64_t n_rows) {
+    if (n_rows > kLargeMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kLargeMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+// A *_host entry point's staging: ctx->stage_in sized for the host matrix and filled (queued on `stream`), ctx->stage_out sized
+// for the result.
+int stage_host_matrix(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, size_t out_bytes, hipStream_t stream) {
+    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+    BYZ_TRY(ctx->stage_in.ensure(bytes));
+    BYZ_TRY(ctx->stage_out.ensure(out_bytes));
+    BYZ_HIP(hipMemcpyAsync(ctx->stage_in.ptr, G_host, bytes, hipMemcpyHostToDevice, stream));
     return BYZ_OK;
 }
 
@@ -120,17 +184,17 @@ int bulyan_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_coun
     const int64_t krum_prefix = krum_winner_dev != nullptr ? python_prefix_len(n - 1, users_count - corrupted) : 0;
     BYZ_TRY(launch_row_sort(ctx, dist, n, krum_prefix, drop, true, stream));
     if (krum_winner_dev != nullptr) BYZ_TRY(launch_krum_argmin(ctx, n, krum_winner_dev, stream));
-    int32_t* status_dev = ctx->small.as<int32_t>() + 8;
+    int32_t* status_dev = ctx->small.as<int32_t>() + kWordBulyanStatus;   // (the re-scored rows' count is the word behind it)
     BYZ_TRY(launch_bulyan_loop(ctx, dist, n, theta, drop, users_count, corrupted, selection_dev, status_dev, stream));
-    int32_t words[32];
+    int32_t words[kSmallWords];
     BYZ_TRY(read_small(ctx, words, stream));
-    const int32_t status[2] = {words[8], words[9]};
-    ctx->bulyan_rescored = status[1];
-    if (status[0] == 2) {
+    const int32_t status = words[kWordBulyanStatus];
+    ctx->bulyan_rescored = words[kWordBulyanRescored];
+    if (status == 2) {
         set_error("bulyan: the selection loop's workgroups lost contact with each other (exchange timed out)");
         return BYZ_E_HIP;
     }
-    if (status[0] != 0) {
+    if (status != 0) {
         set_error("bulyan: no row scored below 1e20 (the reference raises KeyError(-1) here)");
         return BYZ_E_NO_WINNER;
     }
@@ -156,16 +220,123 @@ int multi_krum_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_
         return BYZ_E_UNSUPPORTED;
     }
     BYZ_TRY(ctx->multi_krum_rows.ensure(static_cast<size_t>(n) * sizeof(int32_t)));
-    BYZ_TRY(krum_select(ctx, dist, n, users_count, corrupted, ctx->small.as<int32_t>(), stream));
+    BYZ_TRY(krum_select(ctx, dist, n, users_count, corrupted, krum_winner_word(ctx), stream));
     return launch_multi_krum_rank(ctx, n, m, selection_dev, ctx->multi_krum_rows.as<int32_t>(), stream);
 }
 
-int check_krum_assert(int check_assert, int64_t users_count, int64_t corrupted_count) {
-    if (check_assert && !(users_count >= 2 * corrupted_count + 1)) {  // defences.py:25
-        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count, (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
+// ---- multi-GPU, columns layout (SURVEY.md 8(e)): the one exchange of the path through the host's all-reduce -------------------
+int reduce_over_ranks(byz_allreduce_f64_fn allreduce, void* user, double* buf, int64_t count, void* stream, const char* what) {
+    const int rc = allreduce(user, buf, count, stream);
+    if (rc != 0) {
+        set_error("%s: the caller's all-reduce returned %d", what, rc);
+        return BYZ_E_COLLECTIVE;
     }
     return BYZ_OK;
+}
+
+// dist (n x n) from the column slices of all ranks: Gram of the local slice -> all-reduce -> distances -> the near-duplicate
+// pairs of the all-reduced Gram re-evaluated on the difference (per-rank sums over the local columns -> all-reduce -> apply).
+// The sequence of sharded.py's global_distances + engine.distances_from_gram, in one call.
+int sharded_distances(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, byz_allreduce_f64_fn allreduce,
+                      void* user, float* dist, void* stream) {
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
+    double* gram = ctx->gram.as<double>();
+    BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, gram, s));
+    // rows that are identical in THIS slice need not be identical in the others: what launch_gram's duplicate search proved
+    // holds for the local columns only, and the all-reduced Gram is an external one as far as the distances are concerned
+    ctx->row_map_rows = 0;
+    BYZ_TRY(reduce_over_ranks(allreduce, user, gram, n_rows * n_rows, stream, "sharded distances (Gram)"));
+    BYZ_TRY(launch_distances_from_gram(ctx, gram, n_rows, dist, s, nullptr, 0, 0));
+    int64_t count = 0;
+    BYZ_TRY(near_pair_count(ctx, &count, s));   // (the same all-reduced Gram on every rank: the same count, the same list)
+    if (count > 0) {
+        double* sq = ctx->near_sq.as<double>();
+        BYZ_TRY(launch_near_pair_sqdist(ctx, G, n_cols, ld, nullptr, sq, s));
+        BYZ_TRY(reduce_over_ranks(allreduce, user, sq, count, stream, "sharded distances (near pairs)"));
+        BYZ_TRY(launch_near_pair_apply(ctx, sq, n_rows, dist, s));
+    }
+    return BYZ_OK;
+}
+
+// ---- one composition per defence; allreduce == nullptr: one GPU holds every column ---------------------------------------------
+// dist (n x n) of G's rows: over the ranks' column slices when an all-reduce is given, by the small-N kernel where it applies
+// (no Gram, no duplicate search: the row map describes nothing afterwards), else the Gram and the distances from it.
+int distances(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, byz_allreduce_f64_fn allreduce, void* user,
+              float* dist, void* stream) {
+    if (allreduce != nullptr) return sharded_distances(ctx, G, n_rows, n_cols, ld, allreduce, user, dist, stream);
+    hipStream_t s = as_stream(stream);
+    if (krum_small_applies(n_rows, n_cols)) {
+        ctx->row_map_rows = 0;
+        return launch_small_distances(ctx, G, n_rows, n_cols, ld, dist, s);
+    }
+    BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
+    BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
+    return launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, dist, s, G, n_cols, ld);
+}
+
+int krum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count, int64_t corrupted_count,
+         byz_allreduce_f64_fn allreduce, void* user, float* out_row, int32_t* index_host, void* stream) {
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+    float* dist = ctx->dist.as<float>();
+    int32_t* winner = krum_winner_word(ctx);
+    if (allreduce == nullptr && krum_small_applies(n_rows, n_cols)) {
+        // the reference's own sizes: two launches (krum_small.hip), the row copy is part of the second
+        ctx->row_map_rows = 0;
+        const int64_t prefix = python_prefix_len(n_rows - 1, users_count - corrupted_count);
+        if (ctx->num_cus >= n_rows) {
+            BYZ_TRY(launch_small_krum(ctx, G, n_rows, n_cols, ld, dist, prefix, winner, out_row, s));
+        } else {
+            // the two-launch form has every row's workgroup wait for all the others' scores: they must all be resident at once
+            // (one workgroup per CU).  On a device or partition with fewer CUs than rows (a CPX partition has 32) the first wave
+            // of workgroups would spin to the limit and the call fail with the status word set (ADVICE r4): take the
+            // four-launch form, which has no wait across workgroups.
+            BYZ_TRY(launch_small_distances(ctx, G, n_rows, n_cols, ld, dist, s));
+            BYZ_TRY(launch_small_select(ctx, dist, n_rows, prefix, G, n_cols, ld, winner, out_row, s));
+        }
+    } else {
+        BYZ_TRY(distances(ctx, G, n_rows, n_cols, ld, allreduce, user, dist, stream));
+        BYZ_TRY(krum_select(ctx, dist, n_rows, users_count, corrupted_count, winner, s));
+        if (out_row) BYZ_TRY(launch_copy_row(ctx, G, ld, n_rows, n_cols, winner, out_row, s));
+    }
+    return read_winner(ctx, index_host, s);
+}
+
+int bulyan(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count, int64_t corrupted_count,
+           byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* selection_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    const int64_t theta = users_count - 2 * corrupted_count;
+    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+    BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
+    BYZ_TRY(distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+    int32_t* sel = ctx->selection.as<int32_t>();
+    BYZ_TRY(bulyan_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, sel, s));
+    if (selection_out)
+        BYZ_HIP(hipMemcpyAsync(selection_out, sel, static_cast<size_t>(theta) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    // defences.py:70: trimmed_mean(np.array(selection_set), len(selection_set), 2*corrupted_count); sharded: on the local columns
+    // of the selected rows
+    const int64_t keep = python_prefix_len(theta, theta - 2 * corrupted_count - 1);
+    return launch_trimmed_mean(ctx, G, theta, n_cols, ld, sel, keep, out, s);
+}
+
+int multi_krum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+               int64_t corrupted_count, int64_t m, byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* selection,
+               void* stream) {
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+    BYZ_TRY(distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+    BYZ_TRY(multi_krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, m, selection, s));
+    // sharded: the selection is the same on every rank (one all-reduced Gram); each rank averages its own columns of the selected rows
+    return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
+}
+
+int gram_share(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index, int share_count,
+               int share_index, double* gram, bool accumulate, void* stream) {
+    BYZ_TRY(enter(ctx));
+    // with row_index the logical matrix has n_rows rows taken from anywhere in G: only the pointer and ld are checkable
+    BYZ_REQUIRE(G && n_rows > 0 && n_cols > 0 && ld >= n_cols, "%s: bad matrix", accumulate ? "gram_share_add" : "gram_share");
+    return launch_gram_share(ctx, G, n_rows, n_cols, ld, row_index, share_count, share_index, gram, as_stream(stream), accumulate);
 }
 
 }  // namespace
@@ -201,7 +372,7 @@ int byz_ctx_create(int device, byz_ctx** out) {
     ctx->device = device;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (ctx->small.ensure(256) != BYZ_OK || hipMemset(ctx->small.ptr, 0, 256) != hipSuccess) {
-        delete ctx;
+        delete ctx;   // (frees what was allocated)
         set_error("byz_ctx_create: cannot allocate the device scalars");
         return BYZ_E_HIP;
     }
@@ -214,55 +385,8 @@ void byz_ctx_destroy(byz_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     byz_timing_reset(ctx);
-    ctx->assemble_table.release();
     if (ctx->assemble_copied != nullptr) (void)hipEventDestroy(ctx->assemble_copied);
-    ctx->gram_partials.release();
-    ctx->gram.release();
-    ctx->tile_order.release();
-    ctx->tile_owned.release();
-    ctx->gram_tickets.release();
-    ctx->gram_planes.release();
-    ctx->plane_order.release();
-    ctx->split_redo.release();
-    ctx->plane_unscale.release();
-    ctx->gram_chunk_sums.release();
-    ctx->dup_rep.release();
-    ctx->row_signature.release();
-    ctx->unique_rows.release();
-    ctx->row_map.release();
-    ctx->gram_compact.release();
-    ctx->dist.release();
-    ctx->near_pairs.release();
-    ctx->near_rows.release();
-    ctx->gram_rep.release();
-    ctx->near_sq.release();
-    ctx->near_partial.release();
-    ctx->sorted_idx.release();
-    ctx->large_keys.release();
-    ctx->large_idx.release();
-    ctx->large_rank.release();
-    ctx->large_rank_t.release();
-    ctx->large_dist_t.release();
-    ctx->large_state.release();
-    ctx->large_grid.release();
-    ctx->rank_t.release();
-    ctx->rank_rows.release();
-    ctx->sorted_val.release();
-    ctx->row_total.release();
-    ctx->row_top.release();
-    ctx->scores.release();
-    ctx->multi_krum.release();
-    ctx->multi_krum_rows.release();
-    ctx->geomed.release();
-    ctx->selection.release();
-    ctx->twin_class.release();
-    ctx->redo_tiles.release();
-    ctx->xchg.release();
-    ctx->small.release();
-    ctx->stage_in.release();
-    ctx->stage_out.release();
-    ctx->pinned.release();
-    delete ctx;
+    delete ctx;   // every workspace frees itself (common.hpp: Buffer)
 }
 
 int byz_ctx_device(const byz_ctx* ctx) { return ctx ? ctx->device : -1; }
@@ -354,17 +478,12 @@ int byz_gram_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, i
 
 int byz_gram_share_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
                        const int32_t* row_index, int share_count, int share_index, double* gram, void* stream) {
-    BYZ_TRY(enter(ctx));
-    // with row_index the logical matrix has n_rows rows taken from anywhere in G: only the pointer and ld are checkable
-    BYZ_REQUIRE(G && n_rows > 0 && n_cols > 0 && ld >= n_cols, "gram_share: bad matrix");
-    return launch_gram_share(ctx, G, n_rows, n_cols, ld, row_index, share_count, share_index, gram, as_stream(stream));
+    return gram_share(ctx, G, n_rows, n_cols, ld, row_index, share_count, share_index, gram, false, stream);
 }
 
 int byz_gram_share_add_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
                            const int32_t* row_index, int share_count, int share_index, double* gram, void* stream) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(G && n_rows > 0 && n_cols > 0 && ld >= n_cols, "gram_share_add: bad matrix");
-    return launch_gram_share(ctx, G, n_rows, n_cols, ld, row_index, share_count, share_index, gram, as_stream(stream), true);
+    return gram_share(ctx, G, n_rows, n_cols, ld, row_index, share_count, share_index, gram, true, stream);
 }
 
 int byz_distances_from_gram_dev(byz_ctx* ctx, const double* gram, int64_t n_rows, float* dist, void* stream) {
@@ -376,15 +495,7 @@ int byz_distances_from_gram_dev(byz_ctx* ctx, const double* gram, int64_t n_rows
 int byz_near_pairs_count(byz_ctx* ctx, int64_t* count_host, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(count_host, "near_pairs_count: null output");
-    int32_t words[32];
-    BYZ_TRY(read_small(ctx, words, as_stream(stream)));
-    *count_host = words[17];
-    if (words[17] > ctx->near_pair_capacity) {
-        set_error("distances: %d near-duplicate pairs exceed the list capacity %lld (BYZ_NEAR_PAIR_CAPACITY)", words[17],
-                  (long long)ctx->near_pair_capacity);
-        return BYZ_E_UNSUPPORTED;
-    }
-    return BYZ_OK;
+    return near_pair_count(ctx, count_host, as_stream(stream));
 }
 
 int byz_near_pairs_sqdist_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
@@ -403,8 +514,7 @@ int byz_near_pairs_apply_dev(byz_ctx* ctx, const double* sq_dev, int64_t n_rows,
 
 int byz_ctx_check(byz_ctx* ctx, void* stream) {
     BYZ_TRY(enter(ctx));
-    int32_t words[32];
-    return read_small(ctx, words, as_stream(stream));
+    return check_small(ctx, as_stream(stream));
 }
 
 int byz_bulyan_rescored(const byz_ctx* ctx, int64_t* rows_host) {
@@ -421,13 +531,7 @@ int byz_pairwise_distances_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "pairwise_distances"));
     BYZ_REQUIRE(dist, "pairwise_distances: null output");
-    if (krum_small_applies(n_rows, n_cols)) {
-        ctx->row_map_rows = 0;
-        return launch_small_distances(ctx, G, n_rows, n_cols, ld, dist, as_stream(stream));
-    }
-    BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
-    BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), as_stream(stream)));
-    return launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, dist, as_stream(stream), G, n_cols, ld);
+    return distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, dist, stream);
 }
 
 int byz_krum_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t users_count,
@@ -435,56 +539,19 @@ int byz_krum_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(dist && n_rows > 0, "krum_select: bad arguments");
     hipStream_t s = as_stream(stream);
-    BYZ_TRY(krum_select(ctx, dist, n_rows, users_count, corrupted_count, ctx->small.as<int32_t>(), s));
+    BYZ_TRY(krum_select(ctx, dist, n_rows, users_count, corrupted_count, krum_winner_word(ctx), s));
     if (scores_dev)
         BYZ_HIP(hipMemcpyAsync(scores_dev, ctx->scores.ptr, static_cast<size_t>(n_rows) * sizeof(float),
                                hipMemcpyDeviceToDevice, s));
-    if (index_host) {
-        int32_t words[32];
-        BYZ_TRY(read_small(ctx, words, s));
-        *index_host = words[0];
-    }
-    return BYZ_OK;
+    return read_winner(ctx, index_host, s);
 }
 
 int byz_krum_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
                  int64_t corrupted_count, int check_assert, float* out_row, int32_t* index_host, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "krum"));
-    if (check_assert && !(users_count >= 2 * corrupted_count + 1)) {  // defences.py:25
-        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count,
-                  (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
-    hipStream_t s = as_stream(stream);
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    int32_t* winner = ctx->small.as<int32_t>();
-    if (krum_small_applies(n_rows, n_cols)) {
-        // the reference's own sizes: two launches (krum_small.hip), the row copy is part of the second
-        ctx->row_map_rows = 0;
-        const int64_t prefix = python_prefix_len(n_rows - 1, users_count - corrupted_count);
-        if (ctx->num_cus >= n_rows) {
-            BYZ_TRY(launch_small_krum(ctx, G, n_rows, n_cols, ld, ctx->dist.as<float>(), prefix, winner, out_row, s));
-        } else {
-            // the two-launch form has every row's workgroup wait for all the others' scores: they must all be resident at once
-            // (one workgroup per CU).  On a device or partition with fewer CUs than rows (a CPX partition has 32) the first wave
-            // of workgroups would spin to the limit and the call fail with the status word set (ADVICE r4): take the
-            // four-launch form, which has no wait across workgroups.
-            BYZ_TRY(launch_small_distances(ctx, G, n_rows, n_cols, ld, ctx->dist.as<float>(), s));
-            BYZ_TRY(launch_small_select(ctx, ctx->dist.as<float>(), n_rows, prefix, G, n_cols, ld, winner, out_row, s));
-        }
-    } else {
-        BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
-        BYZ_TRY(launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, ctx->dist.as<float>(), s, G, n_cols, ld));
-        BYZ_TRY(krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, winner, s));
-        if (out_row) BYZ_TRY(launch_copy_row(ctx, G, ld, n_rows, n_cols, winner, out_row, s));
-    }
-    if (index_host) {
-        int32_t words[32];
-        BYZ_TRY(read_small(ctx, words, s));
-        *index_host = words[0];
-    }
-    return BYZ_OK;
+    BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
+    return krum(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, nullptr, nullptr, out_row, index_host, stream);
 }
 
 int byz_trimmed_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
@@ -531,11 +598,8 @@ int byz_krum_bulyan_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, 
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(dist && selection && krum_index_host && n_rows > 0, "krum_bulyan_select: bad arguments");
     hipStream_t s = as_stream(stream);
-    BYZ_TRY(bulyan_select(ctx, dist, n_rows, users_count, corrupted_count, selection, s, ctx->small.as<int32_t>()));
-    int32_t words[32];
-    BYZ_TRY(read_small(ctx, words, s));
-    *krum_index_host = words[0];
-    return BYZ_OK;
+    BYZ_TRY(bulyan_select(ctx, dist, n_rows, users_count, corrupted_count, selection, s, krum_winner_word(ctx)));
+    return read_winner(ctx, krum_index_host, s);
 }
 
 int byz_bulyan_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
@@ -543,30 +607,8 @@ int byz_bulyan_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols,
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "bulyan"));
     BYZ_REQUIRE(out, "bulyan: null output");
-    if (!(users_count >= 4 * corrupted_count + 3)) {  // defences.py:56
-        set_error("bulyan: users_count >= 4*corrupted_count + 3 violated (%lld, %lld)", (long long)users_count,
-                  (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
-    hipStream_t s = as_stream(stream);
-    const int64_t theta = users_count - 2 * corrupted_count;
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
-    if (krum_small_applies(n_rows, n_cols)) {
-        ctx->row_map_rows = 0;
-        BYZ_TRY(launch_small_distances(ctx, G, n_rows, n_cols, ld, ctx->dist.as<float>(), s));
-    } else {
-        BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
-        BYZ_TRY(launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, ctx->dist.as<float>(), s, G, n_cols, ld));
-    }
-    int32_t* sel = ctx->selection.as<int32_t>();
-    BYZ_TRY(bulyan_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, sel, s));
-    if (selection_out)
-        BYZ_HIP(hipMemcpyAsync(selection_out, sel, static_cast<size_t>(theta) * sizeof(int32_t),
-                               hipMemcpyDeviceToDevice, s));
-    // defences.py:70: trimmed_mean(np.array(selection_set), len(selection_set), 2*corrupted_count)
-    const int64_t keep = python_prefix_len(theta, theta - 2 * corrupted_count - 1);
-    return launch_trimmed_mean(ctx, G, theta, n_cols, ld, sel, keep, out, s);
+    BYZ_TRY(check_bulyan_precondition(users_count, corrupted_count));
+    return bulyan(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, nullptr, nullptr, out, selection_out, stream);
 }
 
 // ---- Multi-Krum (Blanchard et al. 2017, section 4; beyond the reference) -----------------------------------------------------
@@ -592,64 +634,10 @@ int byz_multi_krum_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     BYZ_REQUIRE(out, "multi_krum: null output");
     BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
     BYZ_TRY(check_multi_krum_m(n_rows, m));
-    hipStream_t s = as_stream(stream);
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    if (krum_small_applies(n_rows, n_cols)) {
-        ctx->row_map_rows = 0;
-        BYZ_TRY(launch_small_distances(ctx, G, n_rows, n_cols, ld, ctx->dist.as<float>(), s));
-    } else {
-        BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
-        BYZ_TRY(launch_distances_from_gram(ctx, ctx->gram.as<double>(), n_rows, ctx->dist.as<float>(), s, G, n_cols, ld));
-    }
-    BYZ_TRY(multi_krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, m, selection, s));
-    return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
+    return multi_krum(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, m, nullptr, nullptr, out, selection, stream);
 }
 
-// ---- multi-GPU, columns layout (SURVEY.md 8(e)): the one exchange of the path through the host's all-reduce -------------------
-namespace {
-
-int reduce_over_ranks(byz_allreduce_f64_fn allreduce, void* user, double* buf, int64_t count, void* stream, const char* what) {
-    const int rc = allreduce(user, buf, count, stream);
-    if (rc != 0) {
-        set_error("%s: the caller's all-reduce returned %d", what, rc);
-        return BYZ_E_COLLECTIVE;
-    }
-    return BYZ_OK;
-}
-
-// dist (n x n) from the column slices of all ranks: Gram of the local slice -> all-reduce -> distances -> the near-duplicate
-// pairs of the all-reduced Gram re-evaluated on the difference (per-rank sums over the local columns -> all-reduce -> apply).
-// The sequence of sharded.py's global_distances + engine.distances_from_gram, in one call.
-int sharded_distances(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, byz_allreduce_f64_fn allreduce,
-                      void* user, float* dist, void* stream) {
-    hipStream_t s = as_stream(stream);
-    BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
-    double* gram = ctx->gram.as<double>();
-    BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, gram, s));
-    // rows that are identical in THIS slice need not be identical in the others: what launch_gram's duplicate search proved
-    // holds for the local columns only, and the all-reduced Gram is an external one as far as the distances are concerned
-    ctx->row_map_rows = 0;
-    BYZ_TRY(reduce_over_ranks(allreduce, user, gram, n_rows * n_rows, stream, "sharded distances (Gram)"));
-    BYZ_TRY(launch_distances_from_gram(ctx, gram, n_rows, dist, s, nullptr, 0, 0));
-    int32_t words[32];
-    BYZ_TRY(read_small(ctx, words, s));   // (the same all-reduced Gram on every rank: the same count, the same list)
-    const int64_t count = words[17];
-    if (count > ctx->near_pair_capacity) {
-        set_error("distances: %lld near-duplicate pairs exceed the list capacity %lld (BYZ_NEAR_PAIR_CAPACITY)", (long long)count,
-                  (long long)ctx->near_pair_capacity);
-        return BYZ_E_UNSUPPORTED;
-    }
-    if (count > 0) {
-        double* sq = ctx->near_sq.as<double>();
-        BYZ_TRY(launch_near_pair_sqdist(ctx, G, n_cols, ld, nullptr, sq, s));
-        BYZ_TRY(reduce_over_ranks(allreduce, user, sq, count, stream, "sharded distances (near pairs)"));
-        BYZ_TRY(launch_near_pair_apply(ctx, sq, n_rows, dist, s));
-    }
-    return BYZ_OK;
-}
-
-}  // namespace
-
+// ---- multi-GPU, columns layout: the same compositions over the ranks' column slices ------------------------------------------
 int byz_pairwise_distances_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
                                        byz_allreduce_f64_fn allreduce, void* user, float* dist, void* stream) {
     BYZ_TRY(enter(ctx));
@@ -664,22 +652,8 @@ int byz_krum_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "krum_sharded"));
     BYZ_REQUIRE(allreduce, "krum_sharded: null all-reduce");
-    if (check_assert && !(users_count >= 2 * corrupted_count + 1)) {  // defences.py:25
-        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count, (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
-    hipStream_t s = as_stream(stream);
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_TRY(sharded_distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
-    int32_t* winner = ctx->small.as<int32_t>();
-    BYZ_TRY(krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, winner, s));
-    if (out_row) BYZ_TRY(launch_copy_row(ctx, G, ld, n_rows, n_cols, winner, out_row, s));
-    if (index_host) {
-        int32_t words[32];
-        BYZ_TRY(read_small(ctx, words, s));
-        *index_host = words[0];
-    }
-    return BYZ_OK;
+    BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
+    return krum(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, allreduce, user, out_row, index_host, stream);
 }
 
 int byz_bulyan_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
@@ -688,23 +662,8 @@ int byz_bulyan_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "bulyan_sharded"));
     BYZ_REQUIRE(out && allreduce, "bulyan_sharded: null output or null all-reduce");
-    if (!(users_count >= 4 * corrupted_count + 3)) {  // defences.py:56
-        set_error("bulyan: users_count >= 4*corrupted_count + 3 violated (%lld, %lld)", (long long)users_count,
-                  (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
-    hipStream_t s = as_stream(stream);
-    const int64_t theta = users_count - 2 * corrupted_count;
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
-    BYZ_TRY(sharded_distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
-    int32_t* sel = ctx->selection.as<int32_t>();
-    BYZ_TRY(bulyan_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, sel, s));
-    if (selection_out)
-        BYZ_HIP(hipMemcpyAsync(selection_out, sel, static_cast<size_t>(theta) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    // defences.py:70 on the local columns of the selected rows
-    const int64_t keep = python_prefix_len(theta, theta - 2 * corrupted_count - 1);
-    return launch_trimmed_mean(ctx, G, theta, n_cols, ld, sel, keep, out, s);
+    BYZ_TRY(check_bulyan_precondition(users_count, corrupted_count));
+    return bulyan(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, allreduce, user, out, selection_out, stream);
 }
 
 int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
@@ -715,12 +674,7 @@ int byz_multi_krum_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int
     BYZ_REQUIRE(out && allreduce, "multi_krum_sharded: null output or null all-reduce");
     BYZ_TRY(check_krum_assert(check_assert, users_count, corrupted_count));
     BYZ_TRY(check_multi_krum_m(n_rows, m));
-    hipStream_t s = as_stream(stream);
-    BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_TRY(sharded_distances(ctx, G, n_rows, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
-    BYZ_TRY(multi_krum_select(ctx, ctx->dist.as<float>(), n_rows, users_count, corrupted_count, m, selection, s));
-    // the selection is the same on every rank (one all-reduced Gram); each rank averages its own columns of the selected rows
-    return launch_column_mean_rows(ctx, G, ctx->multi_krum_rows.as<int32_t>(), m, n_cols, ld, out, s);
+    return multi_krum(ctx, G, n_rows, n_cols, ld, users_count, corrupted_count, m, allreduce, user, out, selection, stream);
 }
 
 // ---- geometric median (smoothed Weiszfeld; RFA, Pillutla et al.; beyond the reference) ------------------------------------
@@ -737,10 +691,7 @@ int check_geomed(const byz_geomed_params* params, int64_t n_rows, const char* wh
                   params->ftol);
         return BYZ_E_INVALID;
     }
-    if (n_rows > kLargeMaxRows) {
-        set_error("%s: at most %lld rows, got %lld", who, (long long)kLargeMaxRows, (long long)n_rows);
-        return BYZ_E_UNSUPPORTED;
-    }
+    BYZ_TRY(check_row_ceiling(who, n_rows));
     // every update's launches are enqueued up front, stop or no stop: the cap bounds what a call can queue
     if (params->max_iter > BYZ_GEOMED_MAX_ITER) {
         set_error("%s: max_iter = %lld beyond %d (every update's launches are enqueued whatever the stop)", who,
@@ -812,10 +763,7 @@ int byz_row_sqdist_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_sqdist"));
     BYZ_REQUIRE(z && sq, "row_sqdist: null vector or output");
-    if (n_rows > kLargeMaxRows) {
-        set_error("row_sqdist: at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n_rows);
-        return BYZ_E_UNSUPPORTED;
-    }
+    BYZ_TRY(check_row_ceiling("row_sqdist", n_rows));
     GeomedScratch t;
     BYZ_TRY(geomed_scratch(ctx, n_rows, n_cols, &t));
     return launch_row_sqdist(ctx, G, n_rows, n_cols, ld, z, t.partials, sq, nullptr, nullptr, as_stream(stream));
@@ -826,10 +774,7 @@ int byz_weighted_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t 
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "weighted_mean"));
     BYZ_REQUIRE(w && out, "weighted_mean: null weights or output");
-    if (n_rows > kLargeMaxRows) {
-        set_error("weighted_mean: at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n_rows);
-        return BYZ_E_UNSUPPORTED;
-    }
+    BYZ_TRY(check_row_ceiling("weighted_mean", n_rows));
     return launch_weighted_mean(ctx, G, n_rows, n_cols, ld, w, out, nullptr, nullptr, as_stream(stream));
 }
 
@@ -854,7 +799,7 @@ int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_row
 
 int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* excluded_rows, double* objective) {
     BYZ_TRY(enter(ctx));
-    int32_t words[32];
+    int32_t words[kSmallWords];
     BYZ_TRY(read_small(ctx, words, ctx->geomed_stream));   // synchronises the last call's stream
     if (iterations) *iterations = words[kGeomedIterations];
     if (excluded_rows) *excluded_rows = words[kGeomedExcluded];
@@ -981,21 +926,12 @@ int byz_defend_host(byz_ctx* ctx, int name, const float* G_host, int64_t n_rows,
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "defend"));
     BYZ_REQUIRE(name >= 0 && name <= 3, "defend: unknown defence %d", name);
     // preconditions first: the reference asserts before touching the data
-    if (name == 1 && check_assert && !(users_count >= 2 * corrupted_count + 1)) {
-        set_error("('users_count>=2*corrupted_count + 3', %lld, %lld)", (long long)users_count, (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
-    if (name == 3 && !(users_count >= 4 * corrupted_count + 3)) {
-        set_error("bulyan: users_count >= 4*corrupted_count + 3 violated (%lld, %lld)", (long long)users_count, (long long)corrupted_count);
-        return BYZ_E_PRECONDITION;
-    }
+    BYZ_TRY(check_krum_assert(name == 1 && check_assert, users_count, corrupted_count));
+    if (name == 3) BYZ_TRY(check_bulyan_precondition(users_count, corrupted_count));
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(static_cast<size_t>(n_cols) * 3 * sizeof(float)));
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * 3 * sizeof(float), s));
     float* G = ctx->stage_in.as<float>();
     float* out = ctx->stage_out.as<float>();
-    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
     int32_t index = 0;
     switch (name) {
         case 0: BYZ_TRY(byz_no_defense_dev(ctx, G, n_rows, n_cols, n_cols, out, s)); break;
@@ -1027,10 +963,8 @@ int byz_pairwise_distances_host(byz_ctx* ctx, const float* G_host, int64_t n_row
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "pairwise_distances"));
     BYZ_REQUIRE(dist_host, "pairwise_distances: null output");
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, 0, s));
     BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_HIP(hipMemcpyAsync(ctx->stage_in.ptr, G_host, bytes, hipMemcpyHostToDevice, s));
     BYZ_TRY(byz_pairwise_distances_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols,
                                        ctx->dist.as<float>(), s));
     BYZ_HIP(hipMemcpyAsync(dist_host, ctx->dist.ptr, static_cast<size_t>(n_rows) * n_rows * sizeof(float),
@@ -1056,19 +990,15 @@ int byz_drift_attack_host(byz_ctx* ctx, const float* rows_host, int64_t n_rows, 
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(rows_host, n_rows, n_cols, n_cols, "drift_attack"));
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
     const size_t vec = static_cast<size_t>(n_cols) * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(3 * vec));
+    BYZ_TRY(stage_host_matrix(ctx, rows_host, n_rows, n_cols, 3 * vec, s));
     float* out = ctx->stage_out.as<float>();
-    BYZ_HIP(hipMemcpyAsync(ctx->stage_in.ptr, rows_host, bytes, hipMemcpyHostToDevice, s));
     BYZ_TRY(launch_column_drift(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, num_std, out, out + n_cols,
                                 out + 2 * n_cols, s));
     if (drift_host) BYZ_HIP(hipMemcpyAsync(drift_host, out, vec, hipMemcpyDeviceToHost, s));
     if (mean_host) BYZ_HIP(hipMemcpyAsync(mean_host, out + n_cols, vec, hipMemcpyDeviceToHost, s));
     if (std_host) BYZ_HIP(hipMemcpyAsync(std_host, out + 2 * n_cols, vec, hipMemcpyDeviceToHost, s));
-    int32_t words[32];
-    return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+    return check_small(ctx, s);
 }
 
 int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count,
@@ -1080,19 +1010,15 @@ int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64
     BYZ_TRY(check_krum_assert(out_host != nullptr, users_count, corrupted_count));
     BYZ_TRY(check_multi_krum_m(n_rows, m));
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(static_cast<size_t>(n_cols) * 3 * sizeof(float)));
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * 3 * sizeof(float), s));
     BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
     float* G = ctx->stage_in.as<float>();
     float* out = ctx->stage_out.as<float>();
     int32_t* sel = ctx->selection.as<int32_t>();
-    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
     BYZ_TRY(byz_multi_krum_dev(ctx, G, n_rows, n_cols, n_cols, users_count, corrupted_count, m, 0, out, sel, s));
     if (selection_host) BYZ_TRY(read_i32(ctx, sel, selection_host, m, s));
     if (out_host) BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    int32_t words[32];
-    return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+    return check_small(ctx, s);
 }
 
 // the two coordinate-wise rank rules on a host matrix (median: trim_count ignored)
@@ -1104,12 +1030,9 @@ static int rank_select_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, i
     if (n_rows > kLargeMaxRows || (!median && (trim_count < 0 || 2 * trim_count >= n_rows)))      // refused before anything is staged
         return launch_rank_select(ctx, G_host, n_rows, n_cols, n_cols, nullptr, trim_count, median, out_host, nullptr);
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(static_cast<size_t>(n_cols) * sizeof(float)));
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * sizeof(float), s));
     float* G = ctx->stage_in.as<float>();
     float* out = ctx->stage_out.as<float>();
-    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
     BYZ_TRY(launch_rank_select(ctx, G, n_rows, n_cols, n_cols, nullptr, trim_count, median, out, s));
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     BYZ_HIP(hipStreamSynchronize(s));
@@ -1132,20 +1055,16 @@ int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows,
     BYZ_REQUIRE(out_host, "geometric_median: null output");
     BYZ_TRY(check_geomed(params, n_rows, "geometric_median"));
     hipStream_t s = nullptr;
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
     const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the weights 8-byte aligned)
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(out_bytes + static_cast<size_t>(n_rows) * sizeof(double)));
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + static_cast<size_t>(n_rows) * sizeof(double), s));
     float* G = ctx->stage_in.as<float>();
     float* out = ctx->stage_out.as<float>();
     double* weights = weights_host ? reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes) : nullptr;
-    BYZ_HIP(hipMemcpyAsync(G, G_host, bytes, hipMemcpyHostToDevice, s));
     BYZ_TRY(byz_geometric_median_dev(ctx, G, n_rows, n_cols, n_cols, params, out, weights, s));
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (weights_host)
         BYZ_HIP(hipMemcpyAsync(weights_host, weights, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
-    int32_t words[32];
-    return read_small(ctx, words, s);     // synchronises; a kernel that flagged a failure makes this call fail
+    return check_small(ctx, s);
 }
 
 // ---- timing --------------------------------------------------------------------------------------

@@ -255,7 +255,6 @@ __device__ __forceinline__ void lds_poke64(unsigned addr, unsigned long long v) 
     asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 // Bounded: a turn that never comes (it cannot, short of a bug) must not hang the device; the status word says so.
-constexpr int kStatusNoTurn = 16;
 
 template <int NW, int RB>
 __global__ __launch_bounds__(NW * 64) void column_resident_kernel(

@@ -43,10 +43,17 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 // A device buffer that only ever grows; growth happens between kernels, never inside the hot loop
-// once byz_ctx_reserve has been called with the largest shape.
+// once byz_ctx_reserve has been called with the largest shape.  It frees its memory with the context
+// (byz_ctx_destroy: `delete ctx`, on the context's device, after the device has gone idle).
 struct Buffer {
     void* ptr = nullptr;
     size_t bytes = 0;
+    Buffer() = default;
+    Buffer(const Buffer&) = delete;
+    Buffer& operator=(const Buffer&) = delete;
+    ~Buffer() {
+        if (ptr) (void)hipFree(ptr);
+    }
     int ensure(size_t need) {
         if (need <= bytes) return BYZ_OK;
         if (ptr) BYZ_HIP(hipFree(ptr));
@@ -56,11 +63,6 @@ struct Buffer {
         bytes = need;
         return BYZ_OK;
     }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
     template <typename T>
     T* as() const { return static_cast<T*>(ptr); }
 };
@@ -68,6 +70,12 @@ struct Buffer {
 struct PinnedBuffer {
     void* ptr = nullptr;
     size_t bytes = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    ~PinnedBuffer() {
+        if (ptr) (void)hipHostFree(ptr);
+    }
     int ensure(size_t need) {
         if (need <= bytes) return BYZ_OK;
         if (ptr) BYZ_HIP(hipHostFree(ptr));
@@ -76,11 +84,6 @@ struct PinnedBuffer {
         BYZ_HIP(hipHostMalloc(&ptr, need, hipHostMallocDefault));
         bytes = need;
         return BYZ_OK;
-    }
-    void release() {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
     }
 };
 
@@ -181,21 +184,28 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
     return e;
 }
 
-// ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars:
-//   [0] Krum winner   [8] Bulyan loop status   [9] rows the Bulyan loop re-scored
-//   [16] sticky device status (bit 0: a Gram chunk lost its ticket, bit 1: near-duplicate pair list overflowed,
-//        bit 2: two rows with bitwise equal Gram entries turned out to differ, bit 3: the row workgroups of the small-N
-//        path did not all report their scores in time, bit 4: a wave of the register-resident column statistics never got
-//        its turn)
-//   [17] number of near-duplicate pairs listed by the last distance kernel
-//   [18] non-zero: the register-resident column statistics of the CURRENT call gave up a turn; the two-pass kernel queued
-//        behind them recomputes the call's columns (zeroed before every such launch; bit 4 above is no longer set)
-//   [20] geometric median: done (the launches still queued return at once)   [21] its iterations   [22] its excluded rows
-//   [23] geometric median: mean0 was not finite (the fallback ran)   [24, 25] its objective (fp64)
-inline int32_t* device_status_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 16; }
-inline int32_t* attack_redo_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 18; }
-inline int32_t* near_pair_count_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + 17; }
+// ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
+constexpr int kSmallWords = 32;          // words one read-back fetches (read_small): every word below
+constexpr int kWordKrumWinner = 0;       // Krum winner
+constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
+constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
+constexpr int kWordStatus = 16;          // sticky device status: the kStatus* bits
+constexpr int kWordNearPairs = 17;       // number of near-duplicate pairs listed by the last distance kernel
+// non-zero: the register-resident column statistics of the CURRENT call gave up a turn; the two-pass kernel queued behind them
+// recomputes the call's columns (zeroed before every such launch; kStatusNoTurn is no longer set)
+constexpr int kWordAttackRedo = 18;
+// geometric median: done (the launches still queued return at once), its iterations, its excluded rows, mean0 was not finite (the
+// fallback ran), its objective (fp64: two words)
 constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kGeomedFallback = 23, kGeomedObjective = 24;
+constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
+constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
+constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
+constexpr int kStatusSmallTimeout = 8;   // the row workgroups of the small-N path did not all report their scores in time
+constexpr int kStatusNoTurn = 16;        // a wave of the register-resident column statistics never got its turn
+inline int32_t* device_status_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordStatus; }
+inline int32_t* attack_redo_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordAttackRedo; }
+inline int32_t* near_pair_count_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordNearPairs; }
+inline int32_t* krum_winner_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordKrumWinner; }
 inline int32_t* geomed_words(byz_ctx* ctx) { return ctx->small.as<int32_t>(); }
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).

@@ -50,9 +50,6 @@ constexpr int kLevel1 = 8;           // level-0 chains per level-1 fp32 sum
 constexpr int kChunkStages = 8192 / BK;   // K stages per chunk of the chunked schedule: 8192 columns, which end before level 1
                                           // spills to the slab (gram_planes.hip's kChunkCols is the same chunk)
 constexpr int TILE_FLOATS = TM * LDS_STRIDE;
-constexpr int kStatusLostTicket = 1;     // bits of the context's sticky device status word
-constexpr int kStatusPairOverflow = 2;
-constexpr int kStatusFalseTwin = 4;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

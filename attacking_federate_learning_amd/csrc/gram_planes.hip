@@ -51,7 +51,6 @@ constexpr int kRowBlocks = (kWgRows + kWgCols) / 32;  // 8 A + 4 B
 constexpr int kChunkCols = 8192;        // must match gram.hip's chunk (the fp32 level-1 sums never spill inside one)
 constexpr int kChunkSteps = kChunkCols / 16;
 constexpr int kFlushSteps = 16;         // 256-column MFMA chains (the 16-bit MFMAs accumulate with truncation)
-constexpr int kStatusLostTicket = 1;
 constexpr int kSpareRoundsPercent = 10;  // spare rounds per XCD of the f16x2 tile kernel (5, 12 and 30 % measured alike: G8)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

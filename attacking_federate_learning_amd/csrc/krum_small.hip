@@ -46,8 +46,6 @@ constexpr int kSlabFloats = kMaxRows * kMaxRows;    // a workgroup's partial Gra
 constexpr int kPairChunk = 8192;                    // columns per (pair, chunk) work item of the near-duplicate pass
 constexpr double kNearEps = 1.0 / 16.0;             // gram.hip's threshold
 constexpr float kKrumInit = 1e20f;                  // defences.py:27
-constexpr int kStatusFalseTwin = 4;                 // bits of the context's sticky status word (gram.hip)
-constexpr int kStatusSmallTimeout = 8;
 constexpr unsigned kSpinLimit = 1u << 18;   // ~0.1-0.3 s: the worker publishes within microseconds
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -185,15 +185,23 @@ class Engine:
             raise ValueError('expected a 2-D gradient matrix, got shape %r' % (g.shape,))
         return np.ascontiguousarray(g, dtype=np.float32)
 
-    def _out_like(self, m, n, dtype=np.float32):
-        """Output vector for a device-resident input: torch tensor for torch input, DeviceBuffer otherwise."""
-        if m.torch_like is not None:
+    def _out_like(self, like, shape, dtype=np.float32):
+        """Output array (a length or a shape) for a device-resident input -> (array, device pointer): a torch tensor where the
+        input (`like`: its _Matrix, or a torch tensor or None) was torch, a DeviceBuffer otherwise."""
+        example = like.torch_like if isinstance(like, _Matrix) else like
+        shape = tuple(int(n) for n in shape) if isinstance(shape, tuple) else (int(shape),)
+        if example is not None:
             import torch
-            tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32}[np.dtype(dtype)]
-            t = torch.empty(int(n), dtype=tdt, device=m.torch_like.device)
+            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=example.device)   # float32, int32, float64
             return t, t.data_ptr()
-        b = DeviceBuffer(self, (int(n),), dtype)
+        b = DeviceBuffer(self, shape, dtype)
         return b, b.ptr
+
+    def _sync_if_ours(self, keep, stream):
+        """`keep` is the index / staging buffer a call handed to its kernel: a DeviceBuffer we made is freed when the call
+        returns, so the temporary must outlive the kernel (torch orders its own tensors' memory)."""
+        if keep is not None and not _is_torch(keep):
+            self.synchronize(stream)
 
     # ---- defences.py -------------------------------------------------------------------------
     def defend_host(self, name, g, users_count, corrupted_count, check_assert=True, want_aux=False):
@@ -234,13 +242,7 @@ class Engine:
         m = self._device_matrix(g)
         if m is None:
             raise ValueError('gram() takes a device-resident matrix')
-        if m.torch_like is not None:
-            import torch
-            out = torch.empty((m.rows, m.rows), dtype=torch.float64, device=m.torch_like.device)
-            ptr = out.data_ptr()
-        else:
-            out = DeviceBuffer(self, (m.rows, m.rows), np.float64)
-            ptr = out.ptr
+        out, ptr = self._out_like(m, (m.rows, m.rows), np.float64)
         _check(self.lib.byz_gram_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(ptr), _vp(m.stream)))
         return out
 
@@ -272,8 +274,7 @@ class Engine:
             raise ValueError('the accumulator must be a torch CUDA tensor or a DeviceBuffer')
         _check(self.lib.byz_gram_share_add_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
                                                int(share_count), int(share_index), _vp(ptr), _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)
+        self._sync_if_ours(keep, m.stream)
         return gram
 
     def gram_share(self, panel, row_index, share_count, share_index):
@@ -286,17 +287,10 @@ class Engine:
         n_rows, idx_ptr, keep = m.rows, None, None
         if row_index is not None:
             idx_ptr, n_rows, keep = self._row_index(row_index, m, validate=False)
-        if m.torch_like is not None:
-            import torch
-            out = torch.empty((n_rows, n_rows), dtype=torch.float64, device=m.torch_like.device)
-            ptr = out.data_ptr()
-        else:
-            out = DeviceBuffer(self, (n_rows, n_rows), np.float64)
-            ptr = out.ptr
+        out, ptr = self._out_like(m, (n_rows, n_rows), np.float64)
         _check(self.lib.byz_gram_share_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
                                            int(share_count), int(share_index), _vp(ptr), _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)
+        self._sync_if_ours(keep, m.stream)
         return out
 
     def near_pairs_count(self, stream=None):
@@ -313,17 +307,10 @@ class Engine:
         idx_ptr, keep = None, None
         if row_index is not None:
             idx_ptr, _, keep = self._row_index(row_index, m, validate=False)
-        if m.torch_like is not None:
-            import torch
-            sq = torch.empty(int(count), dtype=torch.float64, device=m.torch_like.device)
-            sq_ptr = sq.data_ptr()
-        else:
-            sq = DeviceBuffer(self, (int(count),), np.float64)
-            sq_ptr = sq.ptr
+        sq, sq_ptr = self._out_like(m, count, np.float64)
         _check(self.lib.byz_near_pairs_sqdist_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(idx_ptr), _vp(sq_ptr),
                                                   _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)
+        self._sync_if_ours(keep, m.stream)
         return sq
 
     def near_pairs_apply(self, sq, distances, stream=None):
@@ -488,8 +475,7 @@ class Engine:
         out, ptr = self._out_like(m, m.cols)
         _check(self.lib.byz_trimmed_mean_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
                                              int(corrupted_count), _vp(ptr), _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
+        self._sync_if_ours(keep, m.stream)
         return out
 
     def _rank_rule(self, g, trim_count, row_index, validate_index):
@@ -522,8 +508,7 @@ class Engine:
         else:
             _check(self.lib.byz_rank_trimmed_mean_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
                                                       int(trim_count), _vp(ptr), _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
+        self._sync_if_ours(keep, m.stream)
         return out
 
     def coordinate_median(self, g, row_index=None, validate_index=True):
@@ -552,11 +537,16 @@ class Engine:
         sel = DeviceBuffer(self, (max(theta, 1),), np.int32)
         _check(self.lib.byz_bulyan_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count),
                                               _vp(sel.ptr), None))
+        return self._selection(sel, theta, keys, on_device)
+
+    def _selection(self, sel, count, keys, on_device):
+        """The first `count` rows a selection kernel wrote to `sel`, for the caller: under the caller's keys (_as_distances), or
+        left on the device when asked for (plain keys only)."""
         if on_device and keys is None:
-            sel.shape = (theta,)
-            sel.nbytes = theta * 4
+            sel.shape = (count,)
+            sel.nbytes = count * 4
             return sel
-        picked = sel.numpy()[:theta]
+        picked = sel.numpy()[:count]
         return picked if keys is None else np.asarray([keys[i] for i in picked], dtype=np.int32)
 
     def krum_bulyan_select(self, distances, users_count, corrupted_count, on_device=False):
@@ -570,12 +560,7 @@ class Engine:
                                                    ctypes.byref(idx), _vp(sel.ptr), None))
         index = int(idx.value)
         index = index if (keys is None or index < 0) else keys[index]
-        if on_device and keys is None:
-            sel.shape = (theta,)
-            sel.nbytes = theta * 4
-            return index, sel
-        picked = sel.numpy()[:theta]
-        return index, (picked if keys is None else np.asarray([keys[i] for i in picked], dtype=np.int32))
+        return index, self._selection(sel, theta, keys, on_device)
 
     def bulyan_rescored(self):
         """Rows the last Bulyan loop re-scored with the reference's sequential fp32 sums (0: every pick was clear)."""
@@ -613,10 +598,7 @@ class Engine:
         sel = DeviceBuffer(self, (max(m, 1),), np.int32)
         _check(self.lib.byz_multi_krum_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count), m,
                                                   _vp(sel.ptr), None))
-        if on_device and keys is None:
-            return sel
-        picked = sel.numpy()[:m]
-        return picked if keys is None else np.asarray([keys[i] for i in picked], dtype=np.int32)
+        return self._selection(sel, m, keys, on_device)
 
     def mean_rows(self, g, row_index, validate_index=True):
         """Column mean of the rows `row_index` names, in that order, with no_defense's arithmetic (sequential fp32 from
@@ -630,8 +612,7 @@ class Engine:
         out, ptr = self._out_like(m, m.cols)
         _check(self.lib.byz_mean_rows_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(idx_ptr), int(count), _vp(ptr),
                                           _vp(m.stream)))
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(m.stream)  # the temporary index buffer must outlive the kernel
+        self._sync_if_ours(keep, m.stream)
         return out
 
     def multi_krum(self, g, users_count, corrupted_count, m=None, distances=None, return_selection=False):
@@ -707,13 +688,7 @@ class Engine:
         (zp,), n, _, keep, _ = self._vectors(z)
         if n != m.cols:
             raise ValueError('z has %d entries, the matrix %d columns' % (n, m.cols))
-        if m.torch_like is not None:
-            import torch
-            out = torch.empty(m.rows, dtype=torch.float64, device=m.torch_like.device)
-            optr = out.data_ptr()
-        else:
-            out = DeviceBuffer(self, (m.rows,), np.float64)
-            optr = out.ptr
+        out, optr = self._out_like(m, m.rows, np.float64)
         _check(self.lib.byz_row_sqdist_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(zp), _vp(optr), _vp(m.stream)))
         if host or any(isinstance(k, DeviceBuffer) for k in keep):
             self.synchronize(m.stream)   # staged copies must outlive the kernel
@@ -768,15 +743,7 @@ class Engine:
                                                       weights.ctypes.data_as(ctypes.c_void_p) if return_info else None))
         else:
             out, ptr = self._out_like(dm, dm.cols)
-            weights, wptr = None, None
-            if return_info:
-                if dm.torch_like is not None:
-                    import torch
-                    weights = torch.empty(dm.rows, dtype=torch.float64, device=dm.torch_like.device)
-                    wptr = weights.data_ptr()
-                else:
-                    weights = DeviceBuffer(self, (dm.rows,), np.float64)
-                    wptr = weights.ptr
+            weights, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
             _check(self.lib.byz_geometric_median_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
                                                      _vp(ptr), _vp(wptr), _vp(dm.stream)))
         if not return_info:
@@ -898,19 +865,11 @@ class Engine:
             keep.append(v)
         return ptrs, n, stream, keep, example
 
-    def _vector_out(self, n, example):
-        if example is not None:
-            import torch
-            t = torch.empty(int(n), dtype=torch.float32, device=example.device)
-            return t, t.data_ptr()
-        b = DeviceBuffer(self, (int(n),), np.float32)
-        return b, b.ptr
-
     def backdoor_initial_params(self, original_params, grads_mean, learning_rate):
         """original_params - learning_rate * grads_mean (backdoor.py:54).  numpy in -> numpy out;
         device-resident in -> device-resident out."""
         (p, m), n, stream, keep, example = self._vectors(original_params, grads_mean)
-        out, optr = self._vector_out(n, example)
+        out, optr = self._out_like(example, n)
         _check(self.lib.byz_backdoor_initial_params_dev(self.ctx, _vp(p), _vp(m), n, float(np.float32(learning_rate)),
                                                         _vp(optr), _vp(stream)))
         host = example is None and not any(isinstance(v, DeviceBuffer) for v in (original_params, grads_mean))
@@ -920,7 +879,7 @@ class Engine:
         """The gradient that leads to `mal_net_params`, clipped to mean +- num_std * std (backdoor.py:57-63)."""
         args = (grads_mean, grads_stdev, original_params, mal_net_params)
         (m, s, p, q), n, stream, keep, example = self._vectors(*args)
-        out, optr = self._vector_out(n, example)
+        out, optr = self._out_like(example, n)
         _check(self.lib.byz_backdoor_clip_dev(self.ctx, _vp(m), _vp(s), _vp(p), _vp(q), n,
                                               float(np.float32(learning_rate)), float(np.float32(num_std)),
                                               _vp(optr), _vp(stream)))
@@ -939,22 +898,8 @@ class Engine:
         if m is None:
             raise ValueError('assemble_row() fills a device-resident matrix')
         if isinstance(grads, (list, tuple)):
-            ptrs, lens, keep = [], [], []
-            for t in grads:
-                if isinstance(t, DeviceBuffer):
-                    assert t.dtype == np.float32
-                    ptrs.append(t.ptr)
-                    lens.append(int(np.prod(t.shape)))
-                elif _is_torch(t) and t.is_cuda:
-                    import torch
-                    if t.dtype != torch.float32:
-                        raise ValueError('gradient tensors must be float32')
-                    t = t if t.is_contiguous() else t.contiguous()
-                    ptrs.append(t.data_ptr())
-                    lens.append(t.numel())
-                else:
-                    raise ValueError('a list of gradients must hold device tensors; pass host data as one flat vector')
-                keep.append(t)
+            ptrs, lens, keep = self._segments(grads, None, 'gradient tensors must be float32',
+                                              'a list of gradients must hold device tensors; pass host data as one flat vector')
             sync_after = self._order_after_torch(m, keep)
             table = (ctypes.c_void_p * len(ptrs))(*ptrs)
             lengths = (ctypes.c_int64 * len(lens))(*lens)
@@ -970,6 +915,29 @@ class Engine:
         _check(self.lib.byz_assemble_row_host(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(row),
                                               host.ctypes.data_as(ctypes.c_void_p), _vp(m.stream)))
         self.synchronize(m.stream)   # `host` may be a temporary
+
+    @staticmethod
+    def _segments(tensors, rows, not_float32, not_device):
+        """Device tensors (float32: torch CUDA tensors or DeviceBuffers) -> (pointers, lengths, keep-alives).  `rows`: None, or
+        the leading dimension every tensor must have (the lengths are then per row).  A torch tensor that is not contiguous is
+        replaced by a contiguous temporary: its keep-alive is then not the caller's tensor."""
+        ptrs, lens, keep = [], [], []
+        for t in tensors:
+            if isinstance(t, DeviceBuffer):
+                assert t.dtype == np.float32 and (rows is None or t.shape[0] == rows)
+                ptr, size = t.ptr, int(np.prod(t.shape))
+            elif _is_torch(t) and t.is_cuda:
+                import torch
+                if t.dtype != torch.float32 or (rows is not None and t.shape[0] != rows):
+                    raise ValueError(not_float32)
+                t = t if t.is_contiguous() else t.contiguous()
+                ptr, size = t.data_ptr(), t.numel()
+            else:
+                raise ValueError(not_device)
+            ptrs.append(ptr)
+            lens.append(size // (rows or 1))
+            keep.append(t)
+        return ptrs, lens, keep
 
     def _order_after_torch(self, m, tensors):
         """The launch goes to m.stream; torch tensors (and the .contiguous() temporaries made of them) belong to torch's
@@ -1028,25 +996,12 @@ class Engine:
         flat = list(itertools.chain.from_iterable(clients_grads))
         if len(flat) != n_clients * n_seg:
             raise ValueError('every client must hand over the same number of tensors')
-        ptrs, keep, lens, temporaries = [], [], None, False
+        ptrs, keep, lens = [], [], None
         for c in range(n_clients):
-            mine = []
-            for t in flat[c * n_seg:(c + 1) * n_seg]:
-                if isinstance(t, DeviceBuffer):
-                    assert t.dtype == np.float32
-                    ptrs.append(t.ptr)
-                    mine.append(int(np.prod(t.shape)))
-                elif _is_torch(t) and t.is_cuda:
-                    import torch
-                    if t.dtype != torch.float32:
-                        raise ValueError('gradient tensors must be float32')
-                    if not t.is_contiguous():
-                        t, temporaries = t.contiguous(), True
-                    ptrs.append(t.data_ptr())
-                    mine.append(t.numel())
-                else:
-                    raise ValueError('assemble_rows() takes device tensors; host vectors go through assemble_row()')
-                keep.append(t)
+            p, mine, k = self._segments(flat[c * n_seg:(c + 1) * n_seg], None, 'gradient tensors must be float32',
+                                        'assemble_rows() takes device tensors; host vectors go through assemble_row()')
+            ptrs += p
+            keep += k
             if lens is None:
                 lens = mine
             elif mine != lens:
@@ -1058,7 +1013,7 @@ class Engine:
                                               table, lengths, _vp(m.stream)))
         if sync_after:
             self.synchronize(m.stream)
-        if key is not None and not temporaries:
+        if key is not None and all(k is t for k, t in zip(keep, flat)):      # (no contiguous temporaries among them)
             self._assemble_key = key      # what the device table now holds
 
     def assemble_columns(self, g, batched_grads):
@@ -1067,22 +1022,8 @@ class Engine:
         m = self._device_matrix(g)
         if m is None:
             raise ValueError('assemble_columns() fills a device-resident matrix')
-        ptrs, lens, keep = [], [], []
-        for t in batched_grads:
-            if isinstance(t, DeviceBuffer):
-                assert t.dtype == np.float32 and t.shape[0] == m.rows
-                ptrs.append(t.ptr)
-                lens.append(int(np.prod(t.shape[1:])))
-            elif _is_torch(t) and t.is_cuda:
-                import torch
-                if t.dtype != torch.float32 or t.shape[0] != m.rows:
-                    raise ValueError('batched gradients must be float32 with one leading row per client')
-                t = t if t.is_contiguous() else t.contiguous()
-                ptrs.append(t.data_ptr())
-                lens.append(t.numel() // m.rows)
-            else:
-                raise ValueError('batched gradients must be device tensors')
-            keep.append(t)
+        ptrs, lens, keep = self._segments(batched_grads, m.rows, 'batched gradients must be float32 with one leading row per client',
+                                          'batched gradients must be device tensors')
         sync_after = self._order_after_torch(m, keep)
         table = (ctypes.c_void_p * len(ptrs))(*ptrs)
         lengths = (ctypes.c_int64 * len(lens))(*lens)
