@@ -21,6 +21,11 @@ class GeomedParams(ctypes.Structure):
     _fields_ = [('nu', ctypes.c_double), ('max_iter', c_i64), ('ftol', ctypes.c_double)]
 
 
+class DncParams(ctypes.Structure):
+    """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
+    _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
+
+
 # name -> argument types (everything returns int unless listed in _RESTYPES)
 _PROTOTYPES = {
     'byz_abi_version': [],
@@ -90,6 +95,12 @@ _PROTOTYPES = {
     'byz_geometric_median_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double)],
     'byz_geometric_median_host': [c_vp, c_vp, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp],
     'byz_geometric_median_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
+    'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_dnc_info': [c_vp, _P(c_i64), _P(c_i64)],
+    'byz_dnc_host': [c_vp, c_vp, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, _P(c_i64)],
+    'byz_dnc_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_timing_enable': [c_vp, c_int],
     'byz_timing_reset': [c_vp],
     'byz_timing_read': [c_vp, c_int, _P(ctypes.c_double), _P(c_i64)],

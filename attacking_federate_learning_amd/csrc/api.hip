@@ -807,6 +807,128 @@ int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* exclud
     return BYZ_OK;
 }
 
+// ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
+namespace {
+
+int check_dnc(const byz_dnc_params* params, int64_t n_rows, int64_t n_cols, const char* who) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (params->n_iters < 1 || params->sub_dim < 1 || params->sub_dim > n_cols || params->power_iters < 0 ||
+        params->remove_count < 0 || params->remove_count > n_rows - 1) {
+        set_error("%s: n_iters = %lld must be >= 1, sub_dim = %lld in 1..%lld (the columns), power_iters = %lld >= 0, remove_count = "
+                  "%lld in 0..%lld", who, (long long)params->n_iters, (long long)params->sub_dim, (long long)n_cols,
+                  (long long)params->power_iters, (long long)params->remove_count, (long long)(n_rows - 1));
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_row_ceiling(who, n_rows));
+    if (params->sub_dim > BYZ_DNC_MAX_SAMPLED / n_rows) {
+        set_error("%s: %lld rows x %lld sampled columns exceed the workspace bound of %lld values", who, (long long)n_rows,
+                  (long long)params->sub_dim, (long long)BYZ_DNC_MAX_SAMPLED);
+        return BYZ_E_UNSUPPORTED;
+    }
+    // every product's launches are enqueued up front
+    if (params->power_iters + 1 > BYZ_DNC_MAX_PRODUCTS / params->n_iters) {
+        set_error("%s: n_iters * (power_iters + 1) = %lld * %lld beyond %d", who, (long long)params->n_iters,
+                  (long long)(params->power_iters + 1), BYZ_DNC_MAX_PRODUCTS);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+// The selection of the whole call into the workspace (t.good, the count in the context's word); local_counts == nullptr: every
+// iteration has params->sub_dim columns.  Nothing here waits for the device.
+int dnc_select(byz_ctx* ctx, const float* G, int64_t n, int64_t ld, const byz_dnc_params* params, const int64_t* columns,
+               const int64_t* local_counts, byz_allreduce_f64_fn allreduce, void* user, int32_t* good_out, int32_t* count_out,
+               DncScratch* t, void* stream) {
+    hipStream_t s = as_stream(stream);
+    int64_t widest = local_counts ? 0 : params->sub_dim;
+    if (local_counts)
+        for (int64_t k = 0; k < params->n_iters; ++k) {
+            BYZ_REQUIRE(local_counts[k] >= 0 && local_counts[k] <= params->sub_dim, "dnc: local count %lld of iteration %lld outside 0..%lld",
+                        (long long)local_counts[k], (long long)k, (long long)params->sub_dim);
+            widest = local_counts[k] > widest ? local_counts[k] : widest;
+        }
+    BYZ_REQUIRE(columns || widest == 0, "dnc: null column list");
+    BYZ_TRY(dnc_workspace(ctx, n, widest, t));
+    ctx->dnc_stream = s;
+    const int64_t n_keep = n - params->remove_count;
+    const int64_t* cols = columns;
+    for (int64_t k = 0; k < params->n_iters; ++k) {
+        const int64_t b = local_counts ? local_counts[k] : params->sub_dim;
+        BYZ_TRY(launch_dnc_scores(ctx, *t, G, n, ld, cols, b, params->power_iters, allreduce, user, stream));
+        BYZ_TRY(launch_dnc_rank(ctx, *t, n, n_keep, k == 0, s));
+        cols += b;
+    }
+    return launch_dnc_compact(ctx, *t, n, good_out, count_out, s);
+}
+
+int dnc(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_dnc_params* params, const int64_t* columns,
+        const int64_t* local_counts, byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* good_out, void* stream) {
+    DncScratch t;
+    BYZ_TRY(dnc_select(ctx, G, n, ld, params, columns, local_counts, allreduce, user, good_out, nullptr, &t, stream));
+    // the kept rows are known on the device alone: the row-list mean reads their count there
+    return launch_column_mean_rows_counted(ctx, G, t.good, ctx->small.as<int32_t>() + kDncKept, n_cols, ld, out, as_stream(stream));
+}
+
+}  // namespace
+
+int byz_dnc_scores_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int64_t* columns,
+                       int64_t sub_dim, int64_t power_iters, double* scores, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "dnc_scores"));
+    BYZ_REQUIRE(columns && scores, "dnc_scores: null column list or output");
+    const byz_dnc_params params = {1, sub_dim, power_iters, 0};
+    BYZ_TRY(check_dnc(&params, n_rows, n_cols, "dnc_scores"));
+    DncScratch t;
+    BYZ_TRY(dnc_workspace(ctx, n_rows, sub_dim, &t));
+    BYZ_TRY(launch_dnc_scores(ctx, t, G, n_rows, ld, columns, sub_dim, power_iters, nullptr, nullptr, stream));
+    BYZ_HIP(hipMemcpyAsync(scores, t.scores, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return BYZ_OK;
+}
+
+int byz_dnc_select_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_dnc_params* params,
+                       const int64_t* columns, int32_t* good, int32_t* count, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "dnc_select"));
+    BYZ_REQUIRE(columns && good, "dnc_select: null column list or output");
+    BYZ_TRY(check_dnc(params, n_rows, n_cols, "dnc_select"));
+    DncScratch t;
+    return dnc_select(ctx, G, n_rows, ld, params, columns, nullptr, nullptr, nullptr, good, count, &t, stream);
+}
+
+int byz_dnc_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_dnc_params* params,
+                const int64_t* columns, float* out, int32_t* good, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "dnc"));
+    BYZ_REQUIRE(columns && out, "dnc: null column list or output");
+    BYZ_TRY(check_dnc(params, n_rows, n_cols, "dnc"));
+    return dnc(ctx, G, n_rows, n_cols, ld, params, columns, nullptr, nullptr, nullptr, out, good, stream);
+}
+
+int byz_dnc_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_dnc_params* params,
+                        const int64_t* columns_local, const int64_t* local_counts, byz_allreduce_f64_fn allreduce, void* user,
+                        float* out, int32_t* good, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "dnc_sharded"));
+    BYZ_REQUIRE(out && allreduce && local_counts, "dnc_sharded: null output, all-reduce or local counts");
+    // (sub_dim is the global figure here: it may exceed this rank's columns, the local counts may not)
+    BYZ_TRY(check_dnc(params, n_rows, INT64_MAX, "dnc_sharded"));
+    for (int64_t k = 0; k < params->n_iters; ++k)
+        BYZ_REQUIRE(local_counts[k] <= n_cols, "dnc_sharded: %lld local columns of %lld", (long long)local_counts[k], (long long)n_cols);
+    return dnc(ctx, G, n_rows, n_cols, ld, params, columns_local, local_counts, allreduce, user, out, good, stream);
+}
+
+int byz_dnc_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* inactive_rows) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->dnc_stream));   // synchronises the last call's stream
+    if (kept_rows) *kept_rows = words[kDncKept];
+    if (inactive_rows) *inactive_rows = words[kDncInactive];
+    return BYZ_OK;
+}
+
 int byz_drift_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,
                          float* drift, float* mean, float* stdev, int write_back, void* stream) {
     BYZ_TRY(enter(ctx));
@@ -1065,6 +1187,37 @@ int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows,
     if (weights_host)
         BYZ_HIP(hipMemcpyAsync(weights_host, weights, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
+}
+
+int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_dnc_params* params,
+                 const int64_t* columns_host, float* out_host, int32_t* good_host, int64_t* kept_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "dnc"));
+    BYZ_REQUIRE(columns_host && out_host, "dnc: null column list or output");
+    BYZ_TRY(check_dnc(params, n_rows, n_cols, "dnc"));
+    const int64_t listed = params->n_iters * params->sub_dim;
+    for (int64_t k = 0; k < listed; ++k) {
+        const int64_t c = columns_host[k];
+        const bool first = k % params->sub_dim == 0;
+        BYZ_REQUIRE(c >= 0 && c < n_cols && (first || c > columns_host[k - 1]),
+                    "dnc: column list entry %lld = %lld out of range or not ascending", (long long)k, (long long)c);
+    }
+    hipStream_t s = nullptr;
+    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the column list 8-byte aligned)
+    const size_t list_bytes = static_cast<size_t>(listed) * sizeof(int64_t);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + list_bytes + static_cast<size_t>(n_rows) * sizeof(int32_t), s));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    int64_t* columns = reinterpret_cast<int64_t*>(ctx->stage_out.as<char>() + out_bytes);
+    int32_t* good = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + out_bytes + list_bytes);
+    BYZ_HIP(hipMemcpyAsync(columns, columns_host, list_bytes, hipMemcpyHostToDevice, s));
+    BYZ_TRY(byz_dnc_dev(ctx, G, n_rows, n_cols, n_cols, params, columns, out, good_host ? good : nullptr, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (good_host) BYZ_HIP(hipMemcpyAsync(good_host, good, static_cast<size_t>(n_rows) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, s));
+    if (kept_host) *kept_host = words[kDncKept];
+    return BYZ_OK;
 }
 
 // ---- timing --------------------------------------------------------------------------------------

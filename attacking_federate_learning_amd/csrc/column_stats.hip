@@ -53,6 +53,8 @@ __device__ __forceinline__ void load_columns(const float* __restrict__ p, bool f
 // The list is the same for every lane and is indexed by the uniform loop counter, so its entries arrive through scalar loads
 // (a run's kRowRun indices in one s_load) and every row's address is a scalar base plus the lane's column: the loads of a run
 // are issued together as in MODE 0.
+// MODE 3: MODE 2 with the number of listed rows read from device memory (*redo_gate's slot carries the count: DnC's kept rows,
+// known only on the device); no row gives 0 / 0 = NaN in every column.
 // carry_in (optional, [VEC columns]): the chain continues a sum begun over earlier rows that live elsewhere (another rank's
 // clients); `total_rows` is the divisor (all rows of the chain, not only the local ones).
 template <int VEC, int MODE>
@@ -60,6 +62,10 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
     const float* __restrict__ G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,
     float* __restrict__ mean_out, float* __restrict__ std_out, float* __restrict__ drift_out,
     const int32_t* __restrict__ redo_gate, const int32_t* __restrict__ row_list) {
+    if constexpr (MODE == 3) {
+        n_rows = *redo_gate;            // (MODE 3 has no redo gate: the pointer is the device-side row count)
+        redo_gate = nullptr;
+    }
     // redo_gate (optional): this launch stands behind the register-resident kernel and runs only if a wave of that kernel
     // gave up waiting for its turn (the word is then non-zero): the same bits, the slow way, instead of an invalid vector
     if (redo_gate != nullptr && __hip_atomic_load(redo_gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -72,7 +78,7 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
     for (int v = 0; v < VEC; ++v) s[v] = 0.0f;
     const float* p = G + c0;
     auto row_at = [&](int64_t r) __attribute__((always_inline)) {
-        if constexpr (MODE == 2) return p + static_cast<int64_t>(row_list[r]) * ld;
+        if constexpr (MODE == 2 || MODE == 3) return p + static_cast<int64_t>(row_list[r]) * ld;
         else return p + r * ld;
     };
     int64_t r = 0;
@@ -541,6 +547,18 @@ int launch_column_mean_rows(byz_ctx* ctx, const float* G, const int32_t* row_lis
                             float* out, hipStream_t stream) {
     BYZ_REQUIRE(out && row_list, "mean of rows: null output or null row list");
     return column_pass(ctx, G, count, n_cols, ld, false, 0.0f, out, nullptr, nullptr, stream, row_list);
+}
+
+int launch_column_mean_rows_counted(byz_ctx* ctx, const float* G, const int32_t* row_list, const int32_t* count_dev, int64_t n_cols,
+                                    int64_t ld, float* out, hipStream_t stream) {
+    BYZ_REQUIRE(G && out && row_list && count_dev && n_cols > 0 && ld >= n_cols, "mean of rows: bad arguments");
+    const bool vec4 = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(G) % 16 == 0) &&
+                      n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
+    const dim3 grid(static_cast<unsigned>(ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1))));
+    KernelTimer t(ctx, BYZ_K_COLUMN_STATS, stream);
+    if (vec4) column_sequential_kernel<4, 3><<<grid, kThreads, 0, stream>>>(G, 0, n_cols, ld, 0.0f, out, nullptr, nullptr, count_dev, row_list);
+    else column_sequential_kernel<1, 3><<<grid, kThreads, 0, stream>>>(G, 0, n_cols, ld, 0.0f, out, nullptr, nullptr, count_dev, row_list);
+    return check_launch("column_sequential_kernel (counted row list)");
 }
 
 int launch_column_drift(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float num_std,

@@ -140,6 +140,8 @@ struct byz_ctx {
     byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
     byz::Buffer geomed;          // geometric median: 64 fp64 partials per row, then sq (n + 1) and the weights (n)
     hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
+    byz::Buffer dnc;             // DnC: the centred sample (n x sub_dim fp64), the column partials, the n-vectors, keep and good
+    hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -197,6 +199,8 @@ constexpr int kWordAttackRedo = 18;
 // geometric median: done (the launches still queued return at once), its iterations, its excluded rows, mean0 was not finite (the
 // fallback ran), its objective (fp64: two words)
 constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kGeomedFallback = 23, kGeomedObjective = 24;
+// DnC: the rows the last call kept, the rows its last iteration found inactive
+constexpr int kDncKept = 26, kDncInactive = 27;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -322,6 +326,23 @@ int launch_row_sort_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t pr
 // multi_krum.hip: ctx->scores ranked (score, visit position), the first m rows in ranking order (selection_dev, optional)
 // and in ascending order (rows_asc_dev)
 int launch_multi_krum_rank(byz_ctx* ctx, int64_t n, int64_t m, int32_t* selection_dev, int32_t* rows_asc_dev, hipStream_t stream);
+// the same with the count read from device memory (*count_dev rows of row_list; 0 rows: every column NaN)
+int launch_column_mean_rows_counted(byz_ctx* ctx, const float* G, const int32_t* row_list, const int32_t* count_dev, int64_t n_cols,
+                                    int64_t ld, float* out, hipStream_t stream);
+// dnc.hip: the spectral defence's pieces.  The workspace for n rows and b sampled columns (ctx->dnc):
+struct DncScratch {
+    double *C, *part, *w, *bad, *wt, *y, *u, *scores, *state;
+    int32_t *keep, *good;
+};
+int dnc_workspace(byz_ctx* ctx, int64_t n, int64_t b, DncScratch* out);
+// one iteration's scores into t.scores (allreduce == nullptr: this GPU holds every sampled column; otherwise 3 + power_iters
+// all-reduces of n doubles); b may be 0 on a rank that owns none of the sampled columns
+int launch_dnc_scores(byz_ctx* ctx, const DncScratch& t, const float* G, int64_t n, int64_t ld, const int64_t* columns, int64_t b,
+                      int64_t power_iters, byz_allreduce_f64_fn allreduce, void* user, void* stream);
+// t.keep (&)= the n_keep lowest (score, row); then the kept rows ascending into t.good (and good_out), their count into the
+// context's word (and count_out)
+int launch_dnc_rank(byz_ctx* ctx, const DncScratch& t, int64_t n, int64_t n_keep, bool first, hipStream_t stream);
+int launch_dnc_compact(byz_ctx* ctx, const DncScratch& t, int64_t n, int32_t* good_out, int32_t* count_out, hipStream_t stream);
 // geomed.hip: the geometric median's passes (row distances to a vector, weighted row mean) and its small loop kernels.
 // skip_if_set / run_if_set (optional device words): the launch returns at once if *skip_if_set != 0, or if *run_if_set == 0.
 // the column chunks of rowsq for this shape (at most 64: the partials are chunks x n_rows fp64)

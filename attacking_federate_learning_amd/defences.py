@@ -14,7 +14,7 @@ Differences a caller can observe, all documented in DESIGN.md:
   * `_krum_create_distances` returns a `Distances` handle (GPU-resident N x N matrix) instead of a dict
     of dicts; `krum(..., distances=handle)` accepts it, `handle.to_dict()` rebuilds the reference's form.
 """
-from .engine import Distances, get_engine  # noqa: F401
+from .engine import Distances, dnc_columns, get_engine  # noqa: F401
 
 
 class DefenseTypes:
@@ -92,6 +92,25 @@ def rank_trimmed_mean(users_grads, users_count, corrupted_count):
     assert users_grads.shape[0] >= 2 * corrupted_count + 1, (
         'rows>=2*corrupted_count + 1', users_grads.shape[0], corrupted_count)
     return get_engine().rank_trimmed_mean(users_grads, corrupted_count)
+
+
+def dnc(users_grads, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
+        columns=None, return_index=False):
+    """DnC, the spectral defence (Shejwalkar and Houmansadr, NDSS 2021, Algorithm 2; not in the reference): in each of
+    `niters` iterations the rows are scored on `sub_dim` sampled columns by their squared projection on the top singular
+    vector of the centred sample, the min(n - 1, int(filter_frac * corrupted_count)) highest scores removed; the rows every
+    iteration kept are averaged (np.mean(users_grads[good], axis=0)).  The samples come from `dnc_columns(D, sub_dim,
+    niters, seed)` unless `columns` gives them (one ascending list per iteration, which then sets niters and sub_dim).
+    `return_index=True` returns the kept rows, ascending, instead.  users_count is accepted and unused (the rows are
+    counted).  Not one of the `defend` keys: the reference's main.py offers only those four."""
+    n, d = users_grads.shape
+    remove_count = min(n - 1, int(filter_frac * corrupted_count))
+    if columns is None:
+        columns = dnc_columns(d, sub_dim, niters, seed)
+    engine = get_engine()
+    if return_index:
+        return engine.dnc_select(users_grads, remove_count, columns, power_iters=power_iters)
+    return engine.dnc(users_grads, remove_count, columns, power_iters=power_iters)
 
 
 defend = {DefenseTypes.Krum: krum,

@@ -19,6 +19,30 @@ from . import _native
 NAME_TO_ID = {'NoDefense': 0, 'Krum': 1, 'TrimmedMean': 2, 'Bulyan': 3}
 
 
+def dnc_columns(n_cols, sub_dim, n_iters=1, seed=0):
+    """DnC's column samples, drawn on the host so that the library stays deterministic: an (n_iters, min(sub_dim, n_cols))
+    int64 array, every row np.sort(rng.choice(n_cols, sub_dim, replace=False)) from ONE np.random.default_rng(seed), or
+    arange(n_cols) when sub_dim >= n_cols."""
+    n_cols, sub_dim, n_iters = int(n_cols), int(sub_dim), int(n_iters)
+    if n_iters < 1 or sub_dim < 1 or n_cols < 1:
+        raise ValueError('dnc_columns: n_iters, sub_dim and n_cols must be >= 1')
+    rng = np.random.default_rng(seed)
+    rows = []
+    for _ in range(n_iters):
+        if sub_dim >= n_cols:
+            rows.append(np.arange(n_cols, dtype=np.int64))
+        else:
+            rows.append(np.sort(rng.choice(n_cols, sub_dim, replace=False)).astype(np.int64))
+    return np.stack(rows)
+
+
+class _DeviceF64:
+    """A span of device doubles for torch.as_tensor (the all-reduce callback's buffer belongs to the library)."""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {'shape': (int(count),), 'typestr': '<f8', 'data': (int(ptr), False), 'version': 2}
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -750,6 +774,142 @@ class Engine:
             return out
         iterations, excluded, objective = self.geometric_median_info()
         return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
+
+    # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
+    def _dnc_lists(self, columns, n_cols, validate=True):
+        """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration
+        (2-D); host lists are checked here (range, strictly ascending) unless the caller vouches; a torch CUDA tensor is used
+        in place and checked with one reduction and a host synchronisation."""
+        if _is_torch(columns) and columns.is_cuda:
+            import torch
+            t = columns.reshape(1, -1) if columns.dim() == 1 else columns
+            if t.dim() != 2 or t.dtype != torch.int64 or t.device.index != self.device or t.numel() == 0:
+                raise ValueError('device column lists must be a non-empty 1-D or 2-D int64 tensor on cuda:%d' % self.device)
+            t = t.contiguous()
+            if validate:
+                bad = bool(((t < 0) | (t >= n_cols)).any().item()) or bool((t[:, 1:] <= t[:, :-1]).any().item())
+                if bad:
+                    raise ValueError('column lists must be in [0, %d) and strictly ascending' % n_cols)
+            return None, t
+        host = np.asarray(columns.detach().cpu().numpy() if _is_torch(columns) else columns)
+        if host.dtype.kind not in 'iu' or host.ndim not in (1, 2) or host.size == 0:
+            raise ValueError('column lists must be a non-empty 1-D or 2-D integer array')
+        host = np.ascontiguousarray(host.reshape(1, -1) if host.ndim == 1 else host, dtype=np.int64)
+        if validate and (host.min() < 0 or host.max() >= n_cols or (np.diff(host, axis=1) <= 0).any()):
+            raise ValueError('column lists must be in [0, %d) and strictly ascending' % n_cols)
+        return host, None
+
+    def _dnc_device_lists(self, columns, n_cols, validate):
+        """(device pointer, n_iters, sub_dim, keepalive)"""
+        host, t = self._dnc_lists(columns, n_cols, validate)
+        if t is not None:
+            return t.data_ptr(), int(t.shape[0]), int(t.shape[1]), t
+        keep = self.to_device(host)
+        return keep.ptr, int(host.shape[0]), int(host.shape[1]), keep
+
+    def dnc_info(self):
+        """(kept_rows, inactive_rows) of the last DnC call on this engine (synchronises)."""
+        kept, inactive = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.byz_dnc_info(self.ctx, ctypes.byref(kept), ctypes.byref(inactive)))
+        return int(kept.value), int(inactive.value)
+
+    def dnc_scores(self, g, columns, power_iters=32, validate_columns=True):
+        """One DnC iteration's scores for one list of sampled columns: the squared projection of every centred row on the
+        top right singular vector of the sampled, centred matrix (power iteration from the row of largest norm), +inf for a
+        row with a non-finite sampled value.  fp64: a torch tensor for a torch input, numpy for a host input."""
+        m, stage, host = self._staged(g)
+        ptr, n_iters, b, keep = self._dnc_device_lists(columns, m.cols, validate_columns)
+        if n_iters != 1:
+            raise ValueError('dnc_scores() takes one list of columns')
+        out, optr = self._out_like(m, m.rows, np.float64)
+        _check(self.lib.byz_dnc_scores_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(ptr), b, int(power_iters), _vp(optr),
+                                           _vp(m.stream)))
+        if host or isinstance(keep, DeviceBuffer):
+            self.synchronize(m.stream)   # staged copies must outlive the kernels
+        return out.numpy() if host else out
+
+    def dnc_select(self, g, remove_count, columns, power_iters=32, validate_columns=True):
+        """The rows DnC keeps, ascending: every iteration (one per list of `columns`) ranks the rows by (score, index) and
+        removes the `remove_count` highest; the kept sets are intersected.  int32: a torch tensor for a torch input, numpy
+        otherwise.  Synchronises (the count is read back)."""
+        m, stage, host = self._staged(g)
+        ptr, n_iters, b, keep = self._dnc_device_lists(columns, m.cols, validate_columns)
+        params = _native.DncParams(n_iters, b, int(power_iters), int(remove_count))
+        good, gptr = self._out_like(m, m.rows, np.int32)
+        _check(self.lib.byz_dnc_select_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, ctypes.byref(params), _vp(ptr), _vp(gptr),
+                                           None, _vp(m.stream)))
+        kept, _ = self.dnc_info()
+        return good.numpy()[:kept] if host or isinstance(good, DeviceBuffer) else good[:kept]
+
+    def dnc(self, g, remove_count, columns, power_iters=32, return_selection=False, validate_columns=True):
+        """DnC: np.mean(g[good], axis=0) over the rows every iteration kept (`dnc_select`'s).  `columns`: one ascending list
+        of distinct column indices per iteration (`dnc_columns` draws them).  No row kept: NaN.  Device input: nothing
+        synchronises unless the selection is asked for."""
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            cols, t = self._dnc_lists(columns, d, validate_columns)
+            if cols is None:
+                cols = t.cpu().numpy()
+            params = _native.DncParams(cols.shape[0], cols.shape[1], int(power_iters), int(remove_count))
+            out = np.empty(d, dtype=np.float32)
+            good = np.empty(n, dtype=np.int32)
+            kept = ctypes.c_int64(0)
+            _check(self.lib.byz_dnc_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                         cols.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+                                         good.ctypes.data_as(ctypes.c_void_p), ctypes.byref(kept)))
+            return (out, good[:kept.value]) if return_selection else out
+        ptr, n_iters, b, keep = self._dnc_device_lists(columns, dm.cols, validate_columns)
+        params = _native.DncParams(n_iters, b, int(power_iters), int(remove_count))
+        out, optr = self._out_like(dm, dm.cols)
+        good, gptr = self._out_like(dm, dm.rows, np.int32) if return_selection else (None, None)
+        _check(self.lib.byz_dnc_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params), _vp(ptr), _vp(optr),
+                                    _vp(gptr), _vp(dm.stream)))
+        self._sync_if_ours(keep, dm.stream)
+        if not return_selection:
+            return out
+        kept, _ = self.dnc_info()
+        return out, (good.numpy()[:kept] if isinstance(good, DeviceBuffer) else good[:kept])
+
+    def dnc_sharded(self, g_local, remove_count, local_columns, sub_dim, power_iters=32, all_reduce=None,
+                    return_selection=False):
+        """The columns layout's DnC on this rank's slice (byz_dnc_sharded_dev): local_columns is one ascending list per
+        iteration of the sampled columns this rank owns, as indices into its slice (a list may be empty); sub_dim the global
+        sample size; all_reduce(tensor) sums a CUDA fp64 tensor in place over the ranks on the current stream (None: one
+        rank).  Returns this rank's columns of the mean (and the kept rows, the same on every rank)."""
+        dm = self._device_matrix(g_local)
+        if dm is None:
+            raise ValueError('dnc_sharded() takes a device-resident matrix')
+        lists = [np.ascontiguousarray(np.asarray(c, dtype=np.int64).reshape(-1)) for c in local_columns]
+        for c in lists:
+            if c.size and (c.min() < 0 or c.max() >= dm.cols or (np.diff(c) <= 0).any()):
+                raise ValueError('local column lists must be in [0, %d) and strictly ascending' % dm.cols)
+        counts = (ctypes.c_int64 * len(lists))(*[int(c.size) for c in lists])
+        flat = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+        keep = self.to_device(flat) if flat.size else None
+        device = self.device
+
+        def reduce_on_ranks(user, buf, count, stream):
+            try:
+                if all_reduce is not None:
+                    import torch
+                    all_reduce(torch.as_tensor(_DeviceF64(buf, count), device='cuda:%d' % device))
+                return 0
+            except Exception:      # noqa: BLE001  (a Python exception must not unwind through the C frames)
+                return 1
+        callback = _native.ALLREDUCE_F64_FN(reduce_on_ranks)
+        params = _native.DncParams(len(lists), int(sub_dim), int(power_iters), int(remove_count))
+        out, optr = self._out_like(dm, dm.cols)
+        good, gptr = self._out_like(dm, dm.rows, np.int32) if return_selection else (None, None)
+        _check(self.lib.byz_dnc_sharded_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                            _vp(keep.ptr) if keep is not None else None, counts,
+                                            ctypes.cast(callback, ctypes.c_void_p), None, _vp(optr), _vp(gptr), _vp(dm.stream)))
+        self._sync_if_ours(keep, dm.stream)
+        if not return_selection:
+            return out
+        kept, _ = self.dnc_info()
+        return out, (good.numpy()[:kept] if isinstance(good, DeviceBuffer) else good[:kept])
 
     # ---- malicious.py ------------------------------------------------------------------------
     def drift_attack(self, rows, num_std, write_back=False):

@@ -86,6 +86,17 @@ class HipKernels:
         # the weights come from this package (0/1 flags, 1 / max(nu, d)): no check, no host sync
         return self.engine.weighted_mean(g_local, weights, validate=False)
 
+    def dnc_scores(self, g_local, columns, power_iters=32):
+        return self.engine.dnc_scores(g_local, columns, power_iters=power_iters)     # one rank holds the sampled columns
+
+    def dnc_select(self, g_local, remove_count, columns, power_iters=32):
+        return self.engine.dnc_select(g_local, remove_count, columns, power_iters=power_iters)
+
+    def dnc(self, g_local, remove_count, local_columns, sub_dim, power_iters=32, all_reduce=None, return_selection=False):
+        # this rank's columns of the mean; the n-vectors of every iteration go through all_reduce (None: one rank)
+        return self.engine.dnc_sharded(g_local, remove_count, local_columns, sub_dim, power_iters=power_iters,
+                                       all_reduce=all_reduce, return_selection=return_selection)
+
     def trimmed_mean(self, g_local, corrupted_count, row_index=None):
         # row_index comes from this package (a selection the kernels produced): no bounds re-check, no host sync
         return self.engine.trimmed_mean(g_local, g_local.shape[0], corrupted_count, row_index=row_index,
@@ -375,6 +386,35 @@ class ShardedAggregator:
         else:
             weights = torch.zeros(n, dtype=torch.float64, device=dev)
         return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
+
+    def dnc(self, g_local, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
+            columns=None, gather=False, return_index=False, total_columns=None):
+        """DnC (defences.dnc's contract), columns layout: every rank draws the SAME global sample (`dnc_columns(D, sub_dim,
+        niters, seed)`, or `columns`) and keeps the part that falls into its own slice -- possibly nothing.  Column means and
+        C^T u are local; the activity flags, the diagonal and every product are n-vectors summed over the ranks:
+        niters * (power_iters + 3) all-reduces of n doubles, whatever the data.  The selection is the same on every rank,
+        the mean is taken on the local columns.  total_columns (the full D) is needed beyond one rank."""
+        from .engine import dnc_columns
+        n, d_local = g_local.shape
+        if self.world > 1 and total_columns is None:
+            raise ValueError('dnc() over several ranks needs total_columns')
+        total = int(total_columns) if total_columns is not None else int(d_local)
+        lo, hi = self.column_slices(total)[self.rank] if self.world > 1 else (0, total)
+        assert hi - lo == d_local, (lo, hi, d_local)
+        if columns is None:
+            columns = dnc_columns(total, sub_dim, niters, seed)
+        columns = np.asarray(columns, dtype=np.int64)
+        columns = columns.reshape(1, -1) if columns.ndim == 1 else columns
+        if columns.min() < 0 or columns.max() >= total or (np.diff(columns, axis=1) <= 0).any():
+            raise ValueError('column lists must be in [0, %d) and strictly ascending' % total)
+        local = [row[(row >= lo) & (row < hi)] - lo for row in columns]
+        remove_count = min(n - 1, int(filter_frac * corrupted_count))
+        reduce = (lambda t: self._all_reduce('allreduce_dnc', t)) if self._collective() else None
+        out, good = self.kernels.dnc(g_local, remove_count, local, columns.shape[1], power_iters=power_iters,
+                                     all_reduce=reduce, return_selection=True)
+        if return_index:
+            return good
+        return self._maybe_gather(out, gather, total_columns)
 
     # ---- defences.py, clients layout ----------------------------------------------------------------------------------
     def _row_owner(self, rows_per_rank):

@@ -267,6 +267,59 @@ int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* exclud
 int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                               const byz_geomed_params* params, float* out_host, double* weights_host);
 
+/* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
+/* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
+/* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
+/* squared projection on that vector, computed on a sample of the columns, removes the highest scores, repeats */
+/* with fresh samples and averages the rows that every iteration kept.  The library draws nothing: the caller  */
+/* passes the sampled columns, so that a call is deterministic.                                                */
+/* Inputs: G (n x n_cols fp32, n = n_rows); n_iters >= 1; for every iteration t a list of sub_dim DISTINCT,    */
+/* ASCENDING column indices in [0, n_cols) -- columns_dev, one device int64 array of n_iters * sub_dim entries, */
+/* iteration-major; the caller vouches for range and order --; power_iters >= 0; 0 <= remove_count <= n - 1.   */
+/* For every iteration t, with x_ij the sampled values of row i:                                               */
+/*   row i is ACTIVE when every x_ij is finite; n_a = the number of active rows;                               */
+/*   mu_j = (sum over the active i, ascending, of (double)x_ij) / n_a;  c_ij = (double)x_ij - mu_j (fp64);     */
+/*   M = C C^T over the active rows (fp64);  i0 = the active row with the largest M_ii, the lowest index on a  */
+/*   tie;  u = e_i0;  power_iters times: y = M u, u = y / |y|_2;  then y = M u, lambda = u.y,                  */
+/*   s_i = y_i^2 / lambda -- the squared projection (c_i . v)^2 of centred row i on v = C^T u / |C^T u|, the   */
+/*   top right singular vector once the iteration has converged.  If M_i0i0, any |y| or lambda is 0, every     */
+/*   active score is 0.  An inactive row scores +inf.                                                          */
+/*   Rows are ranked by (s_i, i) ascending (exactly, on the fp64 scores); keep_t = the first n - remove_count.  */
+/* good = the intersection of the keep_t, ascending; out = the mean of the rows `good` with byz_mean_rows_dev's */
+/* arithmetic: the bits of np.mean(G[good], axis=0).  No row left (possible only when n_iters * remove_count   */
+/* >= n): out is NaN in every column, the kept count 0.  More inactive rows than remove_count: the lowest-      */
+/* indexed of them are kept, as the ranking says, and reach the mean.                                           */
+/* The device never forms M: y = M u is w = C^T u (over the sampled columns) then y = C w, both in fp64 in a     */
+/* fixed order (two calls give the same bits); the values differ from the N-space arithmetic above by fp64      */
+/* rounding only (measured: DESIGN.md 3.4d).  Nothing synchronises with the host: the kept count stays on the   */
+/* device until byz_dnc_info reads it.  Every launch is enqueued up front: 5 + 4 (power_iters + 1) + 2 per      */
+/* iteration.  Limits (BYZ_E_UNSUPPORTED beyond): n_rows up to byz_limits' selection limit; n_rows * sub_dim up  */
+/* to BYZ_DNC_MAX_SAMPLED values (the fp64 workspace: 8 bytes each); n_iters * (power_iters + 1) up to          */
+/* BYZ_DNC_MAX_PRODUCTS.  The parameters travel in a struct, as the geometric median's do.                      */
+#define BYZ_DNC_MAX_SAMPLED 268435456
+#define BYZ_DNC_MAX_PRODUCTS 65536
+typedef struct byz_dnc_params {
+    int64_t n_iters;       /* iterations: samples of the columns, intersected                              */
+    int64_t sub_dim;       /* sampled columns per iteration (1 .. n_cols)                                  */
+    int64_t power_iters;   /* normalised products before the scoring one                                   */
+    int64_t remove_count;  /* rows every iteration removes                                                 */
+} byz_dnc_params;
+/* One iteration's scores (scores_dev: n_rows fp64) for one list of sub_dim columns.                        */
+int byz_dnc_scores_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                       const int64_t* columns_dev, int64_t sub_dim, int64_t power_iters, double* scores_dev,
+                       void* stream);
+/* The selection: good_dev (n_rows int32) receives the kept rows ascending, -1 behind them; count_dev        */
+/* (optional, one device int32) their number.                                                                */
+int byz_dnc_select_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                       const byz_dnc_params* params, const int64_t* columns_dev, int32_t* good_dev,
+                       int32_t* count_dev, void* stream);
+/* The whole function (out_dev: n_cols floats; good_dev optional, as above).                                 */
+int byz_dnc_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                const byz_dnc_params* params, const int64_t* columns_dev, float* out_dev, int32_t* good_dev,
+                void* stream);
+/* The last call's kept rows and the rows its last iteration found inactive; synchronises that call's stream. */
+int byz_dnc_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* inactive_rows);
+
 /* ---- multi-GPU, columns layout: one context per GPU, the HOST owns the communicator ---- */
 /* SURVEY.md 8(e)'s "cheaper equivalent": every rank holds ALL n_rows clients over its own slice of the      */
 /* columns (G_local: n_rows x n_cols_local).  The path has ONE exchange: the n_rows x n_rows fp64 Gram of    */
@@ -315,6 +368,20 @@ int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int
                                      int64_t n_cols_local, int64_t ld, const byz_geomed_params* params,
                                      byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
                                      double* weights_dev, void* stream);
+
+/* DnC over the slices.  The caller maps every iteration's global sample onto the ranks: local_counts (HOST,  */
+/* n_iters entries) is the number of iteration t's sampled columns this rank owns -- 0 is allowed --, and      */
+/* columns_local_dev their indices within the slice, ascending, the iterations one after the other            */
+/* (sum of local_counts entries; may be NULL when that sum is 0).  params->sub_dim is the global figure and    */
+/* bounds every local count.  Column means and w = C^T u are local to the owner of a column; what is summed     */
+/* over the ranks are n_rows-vectors: the activity flags, the diagonal of M and every product y.  That is       */
+/* n_iters * (power_iters + 3) all-reduce calls of n_rows doubles each, on every rank, whatever the data.  The  */
+/* selection (good_dev optional, byz_dnc_info) is the same on every rank; out_local_dev = this rank's columns   */
+/* of the mean.  The scores differ from the single-GPU call's by the order of the fp64 partial sums only.       */
+int byz_dnc_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                        const byz_dnc_params* params, const int64_t* columns_local_dev,
+                        const int64_t* local_counts, byz_allreduce_f64_fn allreduce, void* user,
+                        float* out_local_dev, int32_t* good_dev, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
@@ -420,6 +487,12 @@ int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows
                                float* out_host);
 int byz_rank_trimmed_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                                int64_t trim_count, float* out_host);
+
+/* DnC on a host matrix: columns_host (n_iters * sub_dim int64, as byz_dnc_dev's list; checked here: each in  */
+/* [0, n_cols), strictly ascending within an iteration, BYZ_E_INVALID otherwise), out_host (n_cols floats),    */
+/* good_host (optional, n_rows int32: the kept rows ascending, then -1), kept_host (optional).  Synchronous.   */
+int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_dnc_params* params,
+                 const int64_t* columns_host, float* out_host, int32_t* good_host, int64_t* kept_host);
 
 /* ---- per-kernel timing (bench.py's roofline leg) --------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on its own stream.          */
