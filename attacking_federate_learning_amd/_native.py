@@ -21,6 +21,11 @@ class GeomedParams(ctypes.Structure):
     _fields_ = [('nu', ctypes.c_double), ('max_iter', c_i64), ('ftol', ctypes.c_double)]
 
 
+class CclipParams(ctypes.Structure):
+    """byz_cclip_params: centered clipping's radius and iteration count."""
+    _fields_ = [('tau', ctypes.c_double), ('iters', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -95,6 +100,11 @@ _PROTOTYPES = {
     'byz_geometric_median_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double)],
     'byz_geometric_median_host': [c_vp, c_vp, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp],
     'byz_geometric_median_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_clip_update_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_centered_clip_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(CclipParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_centered_clip_info': [c_vp, _P(c_i64), _P(c_i64)],
+    'byz_centered_clip_host': [c_vp, c_vp, c_i64, c_i64, _P(CclipParams), c_vp, c_vp, c_vp],
+    'byz_centered_clip_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(CclipParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

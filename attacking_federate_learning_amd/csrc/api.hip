@@ -807,6 +807,120 @@ int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* exclud
     return BYZ_OK;
 }
 
+// ---- centered clipping (Karimireddy, He and Jaggi 2021, Algorithm 2; beyond the reference) --------------------------------
+namespace {
+
+int check_cclip(const byz_cclip_params* params, int64_t n_rows, const char* who) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    // (written so that a NaN fails the test; +inf passes)
+    if (!(params->tau > 0.0) || params->iters < 0) {
+        set_error("%s: tau = %g must be > 0, iters = %lld >= 0", who, params->tau, (long long)params->iters);
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_row_ceiling(who, n_rows));
+    if (params->iters > BYZ_CCLIP_MAX_ITER) {
+        set_error("%s: iters = %lld beyond %d (every iteration's launches are enqueued up front)", who, (long long)params->iters,
+                  BYZ_CCLIP_MAX_ITER);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+// out must not overlap G (the update stores the new centre while other workgroups still read the matrix)
+int check_cclip_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* out, const char* who) {
+    const float* g_end = G + (n_rows - 1) * ld + n_cols;
+    if (out < g_end && out + n_cols > G) {
+        set_error("%s: the output overlaps the matrix", who);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+struct CclipScratch {
+    double* partials;   // rowsq's chunks x n
+    double* sq;         // n
+    double* s;          // n
+};
+
+int cclip_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, CclipScratch* out) {
+    int64_t unused = 0;
+    const int64_t slabs = geomed_chunks(ctx, n, n_cols, &unused);
+    BYZ_TRY(ctx->cclip.ensure(static_cast<size_t>(slabs * n + 2 * n) * sizeof(double)));
+    out->partials = ctx->cclip.as<double>();
+    out->sq = out->partials + slabs * n;
+    out->s = out->sq + n;
+    return BYZ_OK;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device.  The centre lives in
+// `out` throughout.  Per iteration rowsq, the scales, the update: 2 * iters passes over G.  Nothing measures the rows against the
+// final centre: the scales and the counts reported are those the last update used.
+int centered_clip(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_cclip_params* params,
+                  byz_allreduce_f64_fn allreduce, void* user, const float* start, float* out, double* scales, void* stream) {
+    hipStream_t s = as_stream(stream);
+    CclipScratch t;
+    BYZ_TRY(cclip_scratch(ctx, n, n_cols, &t));
+    ctx->cclip_stream = s;
+    const size_t vec_bytes = static_cast<size_t>(n_cols) * sizeof(float);
+    if (start == nullptr) BYZ_HIP(hipMemsetAsync(out, 0, vec_bytes, s));
+    else if (start != out) BYZ_HIP(hipMemcpyAsync(out, start, vec_bytes, hipMemcpyDeviceToDevice, s));
+    if (params->iters == 0) BYZ_TRY(launch_cclip_scales(ctx, nullptr, n, params->tau, t.s, s));      // scales 1, counts 0
+    for (int64_t l = 0; l < params->iters; ++l) {
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, t.sq, nullptr, nullptr, s));
+        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n, stream, "centered clipping (distances)"));
+        BYZ_TRY(launch_cclip_scales(ctx, t.sq, n, params->tau, t.s, s));
+        BYZ_TRY(launch_clip_update(ctx, G, n, n_cols, ld, out, t.s, out, s));
+    }
+    if (scales != nullptr)
+        BYZ_HIP(hipMemcpyAsync(scales, t.s, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_clip_update_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v,
+                        const double* scales, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "clip_update"));
+    BYZ_REQUIRE(v && scales && out, "clip_update: null vector, scales or output");
+    BYZ_TRY(check_row_ceiling("clip_update", n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "clip_update"));
+    return launch_clip_update(ctx, G, n_rows, n_cols, ld, v, scales, out, as_stream(stream));
+}
+
+int byz_centered_clip_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                          const byz_cclip_params* params, const float* start, float* out, double* scales, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "centered_clip"));
+    BYZ_REQUIRE(out, "centered_clip: null output");
+    BYZ_TRY(check_cclip(params, n_rows, "centered_clip"));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "centered_clip"));
+    return centered_clip(ctx, G, n_rows, n_cols, ld, params, nullptr, nullptr, start, out, scales, stream);
+}
+
+int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                  const byz_cclip_params* params, byz_allreduce_f64_fn allreduce, void* user, const float* start,
+                                  float* out, double* scales, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "centered_clip_sharded"));
+    BYZ_REQUIRE(out && allreduce, "centered_clip_sharded: null output or null all-reduce");
+    BYZ_TRY(check_cclip(params, n_rows, "centered_clip_sharded"));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "centered_clip_sharded"));
+    return centered_clip(ctx, G, n_rows, n_cols, ld, params, allreduce, user, start, out, scales, stream);
+}
+
+int byz_centered_clip_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->cclip_stream));   // synchronises the last call's stream
+    if (clipped_rows) *clipped_rows = words[kCclipClipped];
+    if (excluded_rows) *excluded_rows = words[kCclipExcluded];
+    return BYZ_OK;
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -1186,6 +1300,28 @@ int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows,
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (weights_host)
         BYZ_HIP(hipMemcpyAsync(weights_host, weights, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
+    return check_small(ctx, s);
+}
+
+int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_cclip_params* params,
+                           const float* start_host, float* out_host, double* scales_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "centered_clip"));
+    BYZ_REQUIRE(out_host, "centered_clip: null output");
+    BYZ_TRY(check_cclip(params, n_rows, "centered_clip"));
+    hipStream_t s = nullptr;
+    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the scales 8-byte aligned)
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + static_cast<size_t>(n_rows) * sizeof(double), s));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    double* scales = scales_host ? reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes) : nullptr;
+    // the start is staged into the output vector: the device call runs in place on it
+    if (start_host)
+        BYZ_HIP(hipMemcpyAsync(out, start_host, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyHostToDevice, s));
+    BYZ_TRY(byz_centered_clip_dev(ctx, G, n_rows, n_cols, n_cols, params, start_host ? out : nullptr, out, scales, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (scales_host)
+        BYZ_HIP(hipMemcpyAsync(scales_host, scales, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
 }
 

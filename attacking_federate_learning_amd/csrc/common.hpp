@@ -142,6 +142,8 @@ struct byz_ctx {
     hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
     byz::Buffer dnc;             // DnC: the centred sample (n x sub_dim fp64), the column partials, the n-vectors, keep and good
     hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
+    byz::Buffer cclip;           // centered clipping: rowsq's (row, chunk) fp64 partials, then sq (n) and the scales (n)
+    hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -201,6 +203,8 @@ constexpr int kWordAttackRedo = 18;
 constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kGeomedFallback = 23, kGeomedObjective = 24;
 // DnC: the rows the last call kept, the rows its last iteration found inactive
 constexpr int kDncKept = 26, kDncInactive = 27;
+// centered clipping: the rows its last iteration clipped (tau < d < inf) and excluded (d not finite)
+constexpr int kCclipClipped = 28, kCclipExcluded = 29;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -356,6 +360,11 @@ int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w
 int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
                        hipStream_t stream);
 int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream);
+// cclip.hip: centered clipping.  scales: s from sq (sq == nullptr: all 1), the counts into the context's words; update:
+// out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
+int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, double* s, hipStream_t stream);
+int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
+                       float* out, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

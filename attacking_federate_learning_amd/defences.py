@@ -78,6 +78,16 @@ def geometric_median(users_grads, users_count, corrupted_count, nu=1e-6, max_ite
     return get_engine().geometric_median(users_grads, nu=nu, max_iter=max_iter, ftol=ftol)
 
 
+def centered_clip(users_grads, users_count, corrupted_count, tau=10.0, iters=3, start=None):
+    """Centered clipping (Karimireddy, He and Jaggi, ICML 2021, Algorithm 2; not in the reference): from `start` (None: the
+    zero vector; the previous round's aggregate is the paper's choice) every client's vector is pulled towards the centre
+    and no client moves it by more than tau / n per iteration.  start=None with iters=1 is the norm-clipped mean, the
+    standard answer to the backdoor attack.  The reference's signature; users_count and corrupted_count are accepted and
+    unused.  tau = 10.0 and iters = 3 are this package's choices.  Not one of the `defend` keys: the reference's main.py
+    offers only those four."""
+    return get_engine().centered_clip(users_grads, tau=tau, iters=iters, start=start)
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -775,6 +775,68 @@ class Engine:
         iterations, excluded, objective = self.geometric_median_info()
         return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
 
+    # ---- centered clipping (Karimireddy, He and Jaggi 2021, Algorithm 2; not in the reference) ----
+    def clip_update(self, g, v, scales):
+        """out[c] = fl32(v[c] + S_c / n): S_c the sequential fp64 sum, in row order, of scales[i] * (g[i, c] - v[c]) over the
+        rows with scales[i] != 0 (a row of scale 0 is not read).  One iteration of centered clipping is row_sqdist, the
+        scales min(1, tau / d), then this.  The caller vouches that the scales are finite."""
+        m, stage, host = self._staged(g)
+        (vp,), n, _, keep, _ = self._vectors(v)
+        if n != m.cols:
+            raise ValueError('v has %d entries, the matrix %d columns' % (n, m.cols))
+        sp, skeep = self._f64_vector(scales, m.rows)
+        out, optr = self._out_like(m, m.cols)
+        _check(self.lib.byz_clip_update_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(vp), _vp(sp), _vp(optr),
+                                            _vp(m.stream)))
+        if host or isinstance(skeep, DeviceBuffer) or any(isinstance(k, DeviceBuffer) for k in keep):
+            self.synchronize(m.stream)   # staged copies must outlive the kernel
+        return out.numpy() if host else out
+
+    def centered_clip_info(self):
+        """(clipped_rows, excluded_rows) of the last iteration of the last centered clipping on this engine (synchronises)."""
+        clipped, excluded = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.byz_centered_clip_info(self.ctx, ctypes.byref(clipped), ctypes.byref(excluded)))
+        return int(clipped.value), int(excluded.value)
+
+    def centered_clip(self, g, tau=10.0, iters=3, start=None, return_info=False):
+        """Centered clipping: from v = start (None: the zero vector; the previous round's aggregate is the paper's choice),
+        `iters` times v <- v + mean_i((x_i - v) * min(1, tau / |x_i - v|)).  A row at a non-finite distance is excluded: it
+        adds nothing and still counts in the mean's divisor.  start=None with iters=1 is the norm-clipped mean.  tau = 10.0
+        and iters = 3 are this package's choices: the literature agrees on no defaults.  return_info=True also returns
+        {clipped_rows, excluded_rows, scales} of the last iteration (scales: fp64, one per row)."""
+        params = _native.CclipParams(float(tau), int(iters))
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            out = np.empty(d, dtype=np.float32)
+            scales = np.empty(n, dtype=np.float64) if return_info else None
+            s_host = None
+            if start is not None:
+                s_host = np.ascontiguousarray(start.detach().cpu().numpy() if _is_torch(start) else start, dtype=np.float32).ravel()
+                if s_host.size != d:
+                    raise ValueError('start has %d entries, the matrix %d columns' % (s_host.size, d))
+            _check(self.lib.byz_centered_clip_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                                   s_host.ctypes.data_as(ctypes.c_void_p) if s_host is not None else None,
+                                                   out.ctypes.data_as(ctypes.c_void_p),
+                                                   scales.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+        else:
+            sptr, keep = None, []
+            if start is not None:
+                (sptr,), n, _, keep, _ = self._vectors(start)
+                if n != dm.cols:
+                    raise ValueError('start has %d entries, the matrix %d columns' % (n, dm.cols))
+            out, ptr = self._out_like(dm, dm.cols)
+            scales, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
+            _check(self.lib.byz_centered_clip_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                                  _vp(sptr), _vp(ptr), _vp(wptr), _vp(dm.stream)))
+            if any(isinstance(k, DeviceBuffer) for k in keep):
+                self.synchronize(dm.stream)   # an uploaded start must outlive the kernels
+        if not return_info:
+            return out
+        clipped, excluded = self.centered_clip_info()
+        return out, {'clipped_rows': clipped, 'excluded_rows': excluded, 'scales': scales}
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

@@ -9,6 +9,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     collect_batched(net, x, y)      server.py:54-56 + user.py:76-92 for every client at once (clients.py)
     attack(attacker_rows, num_std)  main.py:68 -> malicious.py:10-36 on the first rows, in place
     defend(defence_method)          server.py:86-90   defences.defend[...] on the device matrix + fused momentum step
+    defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -31,6 +32,8 @@ class DeviceServer:
         self.users_grads = GradientMatrix(self.n_users, self.current_weights.numel(), engine=self.engine,
                                           torch_device=torch_device)
         self.velocity = torch.zeros_like(self.current_weights)
+        # centered clipping's history: the previous round's aggregate (zeros before the first round)
+        self.clip_centre = torch.zeros_like(self.current_weights)
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -55,6 +58,16 @@ class DeviceServer:
         current_grads = defences.defend[defence_method](self.users_grads.data, self.n_users,
                                                         int(self.n_users * self.mal_prop))
         # velocity = momentum * velocity - learning_rate * current_grads ; current_weights += velocity
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with centered clipping, the one defence that reads the round state -----------
+    def defend_centered_clip(self, tau=10.0, iters=3):
+        """Centered clipping of this round's gradients from `clip_centre`, the previous round's aggregate; the result is
+        the next round's centre.  Then server.py:89-90's momentum step, as `defend` takes it."""
+        current_grads = self.engine.centered_clip(self.users_grads.data, tau=tau, iters=iters, start=self.clip_centre)
+        self.clip_centre.copy_(current_grads)     # a copy: the caller owns the aggregate it gets back
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

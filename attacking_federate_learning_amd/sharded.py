@@ -86,6 +86,9 @@ class HipKernels:
         # the weights come from this package (0/1 flags, 1 / max(nu, d)): no check, no host sync
         return self.engine.weighted_mean(g_local, weights, validate=False)
 
+    def clip_update(self, g_local, v, scales):
+        return self.engine.clip_update(g_local, v, scales)    # this rank's columns of the moved centre
+
     def dnc_scores(self, g_local, columns, power_iters=32):
         return self.engine.dnc_scores(g_local, columns, power_iters=power_iters)     # one rank holds the sampled columns
 
@@ -386,6 +389,36 @@ class ShardedAggregator:
         else:
             weights = torch.zeros(n, dtype=torch.float64, device=dev)
         return out, {'iterations': iterations, 'objective': objective, 'excluded_rows': excluded, 'weights': weights}
+
+    def centered_clip(self, g_local, tau=10.0, iters=3, start=None, gather=False, return_info=False, total_columns=None):
+        """Centered clipping (Engine.centered_clip's contract), columns layout: every rank holds all rows over its own
+        columns of G and of `start` (None: zeros).  A rank's squared distances to the centre cover its columns: one
+        all-reduce of N doubles per iteration makes them whole -- `iters` in all --, the scales are then the same on every
+        rank and the update is local to the columns."""
+        import torch
+        tau, iters = float(tau), int(iters)
+        if not tau > 0.0 or iters < 0:
+            raise ValueError('centered_clip: tau = %r must be > 0, iters = %r >= 0' % (tau, iters))
+        n, d_local = g_local.shape
+        dev = g_local.device
+        v = torch.zeros(d_local, dtype=torch.float32, device=dev) if start is None else \
+            torch.as_tensor(start, dtype=torch.float32, device=dev).reshape(-1).clone()
+        scales = torch.ones(n, dtype=torch.float64, device=dev)
+        clipped = excluded = 0
+        for _ in range(iters):
+            sq = self.kernels.row_sqdist(g_local, v)
+            self._all_reduce('allreduce_cclip_distances', sq)
+            d = torch.sqrt(sq)
+            finite = torch.isfinite(d)
+            over = finite & (d > tau)
+            scales = torch.where(over, tau / d, torch.where(finite, torch.ones_like(d), torch.zeros_like(d)))
+            v = self.kernels.clip_update(g_local, v, scales)
+            if return_info:
+                clipped, excluded = int(over.sum().item()), int((~finite).sum().item())
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, {'clipped_rows': clipped, 'excluded_rows': excluded, 'scales': scales}
 
     def dnc(self, g_local, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
             columns=None, gather=False, return_index=False, total_columns=None):

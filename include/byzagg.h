@@ -267,6 +267,50 @@ int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* exclud
 int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                               const byz_geomed_params* params, float* out_host, double* weights_host);
 
+/* ---- centered clipping (Karimireddy, He & Jaggi, ICML 2021, Algorithm 2; not in the reference) ---- */
+/* Every row is pulled towards a centre and no row moves the aggregate by more than tau / n:             */
+/*   v_{l+1} = v_l + (1/n) sum_i (x_i - v_l) min(1, tau / |x_i - v_l|).                                 */
+/* The centre is the caller's: the previous round's aggregate (the history the paper's title speaks of), */
+/* or the zero vector, for which one iteration is the norm-clipped mean (Sun et al. 2019).              */
+/* G: n x n_cols fp32 (n = n_rows up to byz_limits' selection limit, BYZ_E_UNSUPPORTED beyond), leading  */
+/* dimension ld.  tau > 0, +inf allowed (NaN or tau <= 0: BYZ_E_INVALID); 0 <= iters (negative:          */
+/* BYZ_E_INVALID) <= BYZ_CCLIP_MAX_ITER (beyond: BYZ_E_UNSUPPORTED).  start_dev: n_cols floats, optional */
+/* (NULL: the zero vector); the caller vouches that it is finite.  From v_0 = start, for l = 0 .. iters-1:*/
+/*   q = rowsq(G, v_l) (the geometric median's contract above: fp64, on the difference, fixed order),    */
+/*   d_i = sqrt(q_i);  s_i = 1 if d_i <= tau, tau / d_i if tau < d_i < inf;                              */
+/*   a row whose d_i is not finite (inf or NaN) is EXCLUDED: s_i = 0 and the row is skipped, not          */
+/*   multiplied (0 * inf never reaches a column); it still counts in the divisor n -- a row clipped from  */
+/*   infinitely far away contributes nothing;                                                             */
+/*   v_{l+1}[c] = fl32((double)v_l[c] + S_c / n), S_c the fp64 sum over the rows with s_i != 0 of         */
+/*   s_i * ((double)x_ic - (double)v_l[c]): on the difference, in a fixed order, no fused multiply-add.   */
+/* out = v_iters (iters = 0: the bits of start).  Two calls give the same bits; so do a strided view and  */
+/* its dense copy.  out_dev may be start_dev; it must not overlap G (BYZ_E_INVALID).  scales_dev          */
+/* (optional, n fp64): the s of the LAST iteration (iters = 0: all 1).  byz_centered_clip_info reads that */
+/* iteration's clipped rows (tau < d_i < inf) and excluded rows (iters = 0: both 0) and synchronises;     */
+/* nothing else does: every launch is enqueued up front.  Cost: rowsq and the update per iteration, 2 *   */
+/* iters passes over G.  Nothing measures the rows against the final centre: the scales and counts       */
+/* reported are the ones the last update used.  The parameters travel in a struct: the ABI passes no      */
+/* doubles by value.                                                                                      */
+#define BYZ_CCLIP_MAX_ITER 65536
+typedef struct byz_cclip_params {
+    double tau;       /* clipping radius                                                                */
+    int64_t iters;    /* clipping iterations                                                            */
+} byz_cclip_params;
+/* The piece: out[c] = fl32((double)v[c] + S_c / n_rows) with the caller's scales (n_rows fp64, finite;  */
+/* a row of scale 0 is neither loaded nor multiplied), S_c added sequentially in row order.  out_dev may  */
+/* be v_dev.  With byz_row_sqdist_dev it composes the iteration for every height.                         */
+int byz_clip_update_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                        const float* v_dev, const double* scales_dev, float* out_dev, void* stream);
+int byz_centered_clip_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                          const byz_cclip_params* params, const float* start_dev, float* out_dev,
+                          double* scales_dev, void* stream);
+int byz_centered_clip_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows);
+/* Centered clipping of a host matrix (start_host optional, out_host: n_cols floats, scales_host          */
+/* optional: n_rows fp64).  Synchronous.                                                                  */
+int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                           const byz_cclip_params* params, const float* start_host, float* out_host,
+                           double* scales_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -368,6 +412,17 @@ int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int
                                      int64_t n_cols_local, int64_t ld, const byz_geomed_params* params,
                                      byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
                                      double* weights_dev, void* stream);
+
+/* Centered clipping over the slices: every rank holds its columns of G and of start             */
+/* (start_local_dev optional: zeros); out_local_dev = this rank's columns of the result.  A rank's  */
+/* row distances cover its own columns: one all-reduce of n_rows doubles (the per-row partials)     */
+/* per distance computation makes them whole -- `iters` calls in all, on every rank, whatever the   */
+/* data (none for iters = 0).  The scales (scales_dev optional) are then the same on every rank and */
+/* the update is local to the columns.                                                              */
+int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows,
+                                  int64_t n_cols_local, int64_t ld, const byz_cclip_params* params,
+                                  byz_allreduce_f64_fn allreduce, void* user, const float* start_local_dev,
+                                  float* out_local_dev, double* scales_dev, void* stream);
 
 /* DnC over the slices.  The caller maps every iteration's global sample onto the ranks: local_counts (HOST,  */
 /* n_iters entries) is the number of iteration t's sampled columns this rank owns -- 0 is allowed --, and      */
