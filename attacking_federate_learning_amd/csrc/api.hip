@@ -701,20 +701,21 @@ int check_geomed(const byz_geomed_params* params, int64_t n_rows, const char* wh
     return BYZ_OK;
 }
 
-struct GeomedScratch {
+// What the row-distance loops (the geometric median, centered clipping, byz_row_sqdist_dev) keep in ctx->rows.
+struct RowScratch {
     double* partials;   // chunks x n: the (row, column chunk) partials of rowsq
-    double* sq;         // n + 1 (the fallback's flag behind the rows)
-    double* w;          // n
+    double* a;          // n + 1: the squared distances (the geometric median's fallback flag behind the rows)
+    double* b;          // n: the weights, or the scales
 };
 
 // sized by the chunks geomed_chunks picks for this shape: at most 64 per row, about num_cus * 256 + n in all
-int geomed_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, GeomedScratch* out) {
+int row_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, RowScratch* out) {
     int64_t chunk_cols = 0;
     const int64_t partials = static_cast<int64_t>(geomed_chunks(ctx, n, n_cols, &chunk_cols)) * n;
-    BYZ_TRY(ctx->geomed.ensure(static_cast<size_t>(partials + (n + 1) + n) * sizeof(double)));
-    out->partials = ctx->geomed.as<double>();
-    out->sq = out->partials + partials;
-    out->w = out->sq + (n + 1);
+    BYZ_TRY(ctx->rows.ensure(static_cast<size_t>(partials + (n + 1) + n) * sizeof(double)));
+    out->partials = ctx->rows.as<double>();
+    out->a = out->partials + partials;
+    out->b = out->a + (n + 1);
     return BYZ_OK;
 }
 
@@ -722,8 +723,9 @@ int geomed_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, GeomedScratch* out) 
 int geometric_median(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_geomed_params* params,
                      byz_allreduce_f64_fn allreduce, void* user, float* out, double* weights, void* stream) {
     hipStream_t s = as_stream(stream);
-    GeomedScratch t;
-    BYZ_TRY(geomed_scratch(ctx, n, n_cols, &t));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
+    double *sq = t.a, *w = t.b;
     int32_t* words = geomed_words(ctx);
     const int32_t* done = words + kGeomedDone;
     const int32_t* fallback = words + kGeomedFallback;
@@ -733,26 +735,26 @@ int geometric_median(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, in
     BYZ_TRY(launch_column_mean(ctx, G, n, n_cols, ld, out, s));
     if (allreduce == nullptr) {
         BYZ_TRY(launch_geomed_finite_check(ctx, out, n_cols, nullptr, s));
-        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, t.sq, nullptr, fallback, s));
-        BYZ_TRY(launch_geomed_fallback(ctx, t.sq, n, t.w, nullptr, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, sq, nullptr, fallback, s));
+        BYZ_TRY(launch_geomed_fallback(ctx, sq, n, w, nullptr, s));
     } else {
         // a rank whose own columns are finite adds 0 to every row's squared norm (finite: the sum's finiteness is the
         // others'); the flag rides behind the rows, so that the decision is taken on all-reduced data on every rank
-        BYZ_HIP(hipMemsetAsync(t.sq, 0, static_cast<size_t>(n + 1) * sizeof(double), s));
-        BYZ_TRY(launch_geomed_finite_check(ctx, out, n_cols, t.sq + n, s));
-        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, t.sq, nullptr, fallback, s));
-        BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n + 1, stream, "geometric median (finiteness)"));
-        BYZ_TRY(launch_geomed_fallback(ctx, t.sq, n, t.w, t.sq + n, s));
+        BYZ_HIP(hipMemsetAsync(sq, 0, static_cast<size_t>(n + 1) * sizeof(double), s));
+        BYZ_TRY(launch_geomed_finite_check(ctx, out, n_cols, sq + n, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, nullptr, t.partials, sq, nullptr, fallback, s));
+        BYZ_TRY(reduce_over_ranks(allreduce, user, sq, n + 1, stream, "geometric median (finiteness)"));
+        BYZ_TRY(launch_geomed_fallback(ctx, sq, n, w, sq + n, s));
     }
-    BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, t.w, out, nullptr, fallback, s));
+    BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, w, out, nullptr, fallback, s));
     // the objective at the start, then the updates
     for (int64_t k = 0; k <= params->max_iter; ++k) {
-        if (k > 0) BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, t.w, out, done, nullptr, s));
-        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, t.sq, done, nullptr, s));
-        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n, stream, "geometric median (distances)"));
-        BYZ_TRY(launch_geomed_step(ctx, t.sq, n, t.w, params->nu, params->ftol, k, params->max_iter, s));
+        if (k > 0) BYZ_TRY(launch_weighted_mean(ctx, G, n, n_cols, ld, w, out, done, nullptr, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, sq, done, nullptr, s));
+        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, sq, n, stream, "geometric median (distances)"));
+        BYZ_TRY(launch_geomed_step(ctx, sq, n, w, params->nu, params->ftol, k, params->max_iter, s));
     }
-    if (weights != nullptr) BYZ_TRY(launch_geomed_weights(ctx, t.w, n, weights, s));
+    if (weights != nullptr) BYZ_TRY(launch_geomed_weights(ctx, w, n, weights, s));
     return BYZ_OK;
 }
 
@@ -764,8 +766,8 @@ int byz_row_sqdist_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_sqdist"));
     BYZ_REQUIRE(z && sq, "row_sqdist: null vector or output");
     BYZ_TRY(check_row_ceiling("row_sqdist", n_rows));
-    GeomedScratch t;
-    BYZ_TRY(geomed_scratch(ctx, n_rows, n_cols, &t));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n_rows, n_cols, &t));
     return launch_row_sqdist(ctx, G, n_rows, n_cols, ld, z, t.partials, sq, nullptr, nullptr, as_stream(stream));
 }
 
@@ -839,43 +841,28 @@ int check_cclip_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t l
     return BYZ_OK;
 }
 
-struct CclipScratch {
-    double* partials;   // rowsq's chunks x n
-    double* sq;         // n
-    double* s;          // n
-};
-
-int cclip_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, CclipScratch* out) {
-    int64_t unused = 0;
-    const int64_t slabs = geomed_chunks(ctx, n, n_cols, &unused);
-    BYZ_TRY(ctx->cclip.ensure(static_cast<size_t>(slabs * n + 2 * n) * sizeof(double)));
-    out->partials = ctx->cclip.as<double>();
-    out->sq = out->partials + slabs * n;
-    out->s = out->sq + n;
-    return BYZ_OK;
-}
-
 // The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device.  The centre lives in
 // `out` throughout.  Per iteration rowsq, the scales, the update: 2 * iters passes over G.  Nothing measures the rows against the
 // final centre: the scales and the counts reported are those the last update used.
 int centered_clip(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_cclip_params* params,
                   byz_allreduce_f64_fn allreduce, void* user, const float* start, float* out, double* scales, void* stream) {
     hipStream_t s = as_stream(stream);
-    CclipScratch t;
-    BYZ_TRY(cclip_scratch(ctx, n, n_cols, &t));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
+    double *sq = t.a, *scale = t.b;
     ctx->cclip_stream = s;
     const size_t vec_bytes = static_cast<size_t>(n_cols) * sizeof(float);
     if (start == nullptr) BYZ_HIP(hipMemsetAsync(out, 0, vec_bytes, s));
     else if (start != out) BYZ_HIP(hipMemcpyAsync(out, start, vec_bytes, hipMemcpyDeviceToDevice, s));
-    if (params->iters == 0) BYZ_TRY(launch_cclip_scales(ctx, nullptr, n, params->tau, t.s, s));      // scales 1, counts 0
+    if (params->iters == 0) BYZ_TRY(launch_cclip_scales(ctx, nullptr, n, params->tau, scale, s));      // scales 1, counts 0
     for (int64_t l = 0; l < params->iters; ++l) {
-        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, t.sq, nullptr, nullptr, s));
-        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.sq, n, stream, "centered clipping (distances)"));
-        BYZ_TRY(launch_cclip_scales(ctx, t.sq, n, params->tau, t.s, s));
-        BYZ_TRY(launch_clip_update(ctx, G, n, n_cols, ld, out, t.s, out, s));
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, sq, nullptr, nullptr, s));
+        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, sq, n, stream, "centered clipping (distances)"));
+        BYZ_TRY(launch_cclip_scales(ctx, sq, n, params->tau, scale, s));
+        BYZ_TRY(launch_clip_update(ctx, G, n, n_cols, ld, out, scale, out, s));
     }
     if (scales != nullptr)
-        BYZ_HIP(hipMemcpyAsync(scales, t.s, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToDevice, s));
+        BYZ_HIP(hipMemcpyAsync(scales, scale, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToDevice, s));
     return BYZ_OK;
 }
 

@@ -11,15 +11,14 @@
 // (the fp64 one-pass statistics of rounds 1-4 were 1 ulp off in a few columns, which moved median-window
 // decisions downstream).  The variance needs the mean first: the rows are walked twice.
 // Algorithmic traffic: 4*rows*cols bytes read + 4*cols written.
-#include "common.hpp"
+#include "row_walk.hpp"
 
 #include <algorithm>
 
 namespace byz {
 namespace {
 
-constexpr int kThreads = 256;
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int kThreads = kWalkThreads;
 
 // numpy's arithmetic for np.mean(rows, axis=0) and np.var(rows, axis=0) ** 0.5 on an (m, D) fp32 array, operation by operation
 // (tests/test_oracle_golden.py pins this model to numpy itself):
@@ -28,25 +27,10 @@ typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
 //     s2   = sum over rows, sequential fp32, of  fl(fl(x[r] - mean) * fl(x[r] - mean))
 //     std  = sqrt(s2 / float(m))                 (`** 0.5` on an fp32 array is np.sqrt)
 //     drift = mean - fl(float(z) * std)
-// One thread owns VEC columns and walks the rows; the loads of a run of rows are issued together, the additions follow in row
-// order.  The chain starts from +0.0f, add.reduce's identity (a column of -0.0 sums to +0.0 in numpy, and here).
+// One thread owns VEC columns and walks the rows (walk_rows, row_walk.hpp): the loads of a run of rows are issued together, the
+// additions follow in row order.  The chain starts from +0.0f, add.reduce's identity (a column of -0.0 sums to +0.0 in numpy,
+// and here).
 // This file is compiled with -ffp-contract=off: no multiply may fuse with the addition that follows it.
-constexpr int kRowRun = 8;
-
-template <int VEC>
-__device__ __forceinline__ void load_columns(const float* __restrict__ p, bool full, int64_t c0, int64_t n_cols, float (&x)[VEC]) {
-    if constexpr (VEC == 4) {
-        if (full) {
-            const float4u q = *reinterpret_cast<const float4u*>(p);
-            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) x[v] = (c0 + v < n_cols) ? p[v] : 0.0f;
-        }
-    } else {
-        x[0] = p[0];
-    }
-}
 
 // MODE 0: mean only (no_defense).  MODE 1: mean, std, drift (the attack).  MODE 2: the mean of the n_rows rows that row_list
 // names, in list order (Multi-Krum's aggregate over its selected rows, ascending): row r of the chain is G[row_list[r]].
@@ -71,35 +55,20 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
     if (redo_gate != nullptr && __hip_atomic_load(redo_gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
     const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * VEC;
     if (c0 >= n_cols) return;
-    const bool full = c0 + VEC <= n_cols;
     const float rows_f = static_cast<float>(n_rows);
     float s[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) s[v] = 0.0f;
     const float* p = G + c0;
-    auto row_at = [&](int64_t r) __attribute__((always_inline)) {
-        if constexpr (MODE == 2 || MODE == 3) return p + static_cast<int64_t>(row_list[r]) * ld;
-        else return p + r * ld;
+    auto row_of = [&](int64_t r) __attribute__((always_inline)) -> int64_t {
+        if constexpr (MODE == 2 || MODE == 3) return row_list[r];
+        else return r;
     };
-    int64_t r = 0;
-    for (; r + kRowRun <= n_rows; r += kRowRun) {
-        const float* q[kRowRun];                           // (MODE 2: the run's indices first, then its loads back to back)
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u) q[u] = row_at(r + u);
-        float x[kRowRun][VEC];
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u) load_columns<VEC>(q[u], full, c0, n_cols, x[u]);
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) s[v] = s[v] + x[u][v];
-    }
-    for (; r < n_rows; ++r) {
-        float x[VEC];
-        load_columns<VEC>(row_at(r), full, c0, n_cols, x);
+    auto every_row = [](int64_t) __attribute__((always_inline)) { return true; };
+    walk_rows<VEC>(p, ld, n_rows, c0, n_cols, row_of, every_row, [&](int64_t, bool, const float(&x)[VEC]) __attribute__((always_inline)) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) s[v] = s[v] + x[v];
-    }
+    });
     float mean[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
@@ -110,30 +79,14 @@ __global__ __launch_bounds__(kThreads) void column_sequential_kernel(
         float s2[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) s2[v] = 0.0f;
-        r = 0;
-        for (; r + kRowRun <= n_rows; r += kRowRun) {
-            float x[kRowRun][VEC];
-#pragma unroll
-            for (int u = 0; u < kRowRun; ++u) load_columns<VEC>(p + (r + u) * ld, full, c0, n_cols, x[u]);
-#pragma unroll
-            for (int u = 0; u < kRowRun; ++u)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    const float d = x[u][v] - mean[v];
-                    const float q = d * d;
-                    s2[v] = s2[v] + q;
-                }
-        }
-        for (; r < n_rows; ++r) {
-            float x[VEC];
-            load_columns<VEC>(p + r * ld, full, c0, n_cols, x);
+        walk_rows<VEC>(p, ld, n_rows, c0, n_cols, row_of, every_row, [&](int64_t, bool, const float(&x)[VEC]) __attribute__((always_inline)) {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 const float d = x[v] - mean[v];
                 const float q = d * d;
                 s2[v] = s2[v] + q;
             }
-        }
+        });
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             if (c0 + v >= n_cols) continue;
@@ -155,7 +108,6 @@ __global__ __launch_bounds__(kThreads) void column_chain_kernel(
     const float* __restrict__ mean, float* __restrict__ out) {
     const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * VEC;
     if (c0 >= n_cols) return;
-    const bool full = c0 + VEC <= n_cols;
     float s[VEC], mu[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
@@ -163,39 +115,21 @@ __global__ __launch_bounds__(kThreads) void column_chain_kernel(
         s[v] = (carry != nullptr && in) ? carry[c0 + v] : 0.0f;
         mu[v] = (SQUARES && in) ? mean[c0 + v] : 0.0f;
     }
-    const float* p = G + c0;
-    int64_t r = 0;
-    for (; r + kRowRun <= n_rows; r += kRowRun) {
-        float x[kRowRun][VEC];
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u) load_columns<VEC>(p + (r + u) * ld, full, c0, n_cols, x[u]);
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u)
+    walk_rows<VEC>(
+        G + c0, ld, n_rows, c0, n_cols, [](int64_t r) __attribute__((always_inline)) { return r; },
+        [](int64_t) __attribute__((always_inline)) { return true; },
+        [&](int64_t, bool, const float(&x)[VEC]) __attribute__((always_inline)) {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 if constexpr (SQUARES) {
-                    const float d = x[u][v] - mu[v];
+                    const float d = x[v] - mu[v];
                     const float q = d * d;
                     s[v] = s[v] + q;
                 } else {
-                    s[v] = s[v] + x[u][v];
+                    s[v] = s[v] + x[v];
                 }
             }
-    }
-    for (; r < n_rows; ++r) {
-        float x[VEC];
-        load_columns<VEC>(p + r * ld, full, c0, n_cols, x);
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            if constexpr (SQUARES) {
-                const float d = x[v] - mu[v];
-                const float q = d * d;
-                s[v] = s[v] + q;
-            } else {
-                s[v] = s[v] + x[v];
-            }
-        }
-    }
+        });
 #pragma unroll
     for (int v = 0; v < VEC; ++v)
         if (c0 + v < n_cols) out[c0 + v] = s[v];
@@ -473,11 +407,8 @@ int column_pass(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
                 float num_std, float* mean, float* stdev, float* drift, hipStream_t stream, const int32_t* row_list = nullptr) {
     BYZ_REQUIRE(G && n_rows > 0 && n_cols > 0 && ld >= n_cols, "column statistics: bad shape %lld x %lld ld %lld",
                 (long long)n_rows, (long long)n_cols, (long long)ld);
-    // 16-byte loads when every row starts 16-byte aligned and the columns alone fill the chip; one column per thread otherwise
-    // (few columns: four times the threads)
-    const bool vec4 = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(G) % 16 == 0) &&
-                      n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
-    const int64_t col_blocks = ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1));
+    WalkShape shape;
+    BYZ_TRY(walk_shape(ctx, G, ld, n_cols, "column statistics", &shape));
     KernelTimer t(ctx, BYZ_K_COLUMN_STATS, stream);
     // the attack over many rows: one pass over HBM with the tile resident in registers (BYZ_ATTACK_RESIDENT=0: the two-pass
     // kernel for everything -- the same bits, the A/B)
@@ -513,23 +444,23 @@ int column_pass(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
 #undef BYZ_RESIDENT_ALL
 #undef BYZ_RESIDENT
         BYZ_TRY(check_launch("column_resident_kernel"));
-        const dim3 redo_grid(static_cast<unsigned>(col_blocks));
-        if (vec4) column_sequential_kernel<4, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx), nullptr);
+        const dim3 redo_grid(static_cast<unsigned>(shape.blocks));
+        if (shape.vec4) column_sequential_kernel<4, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx), nullptr);
         else column_sequential_kernel<1, 1><<<redo_grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, attack_redo_word(ctx), nullptr);
         return check_launch("column_sequential_kernel (redo)");
     }
-    const dim3 grid(static_cast<unsigned>(col_blocks));
+    const dim3 grid(static_cast<unsigned>(shape.blocks));
     if (row_list != nullptr) {
         BYZ_REQUIRE(!stats, "column statistics: a row list is for the mean alone");
-        if (vec4) column_sequential_kernel<4, 2><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, row_list);
+        if (shape.vec4) column_sequential_kernel<4, 2><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, row_list);
         else column_sequential_kernel<1, 2><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, row_list);
         return check_launch("column_sequential_kernel (row list)");
     }
     if (stats) {
-        if (vec4) column_sequential_kernel<4, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr, nullptr);
+        if (shape.vec4) column_sequential_kernel<4, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr, nullptr);
         else column_sequential_kernel<1, 1><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, num_std, mean, stdev, drift, nullptr, nullptr);
     } else {
-        if (vec4) column_sequential_kernel<4, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, nullptr);
+        if (shape.vec4) column_sequential_kernel<4, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, nullptr);
         else column_sequential_kernel<1, 0><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, 0.0f, mean, nullptr, nullptr, nullptr, nullptr);
     }
     return check_launch("column_sequential_kernel");
@@ -552,11 +483,11 @@ int launch_column_mean_rows(byz_ctx* ctx, const float* G, const int32_t* row_lis
 int launch_column_mean_rows_counted(byz_ctx* ctx, const float* G, const int32_t* row_list, const int32_t* count_dev, int64_t n_cols,
                                     int64_t ld, float* out, hipStream_t stream) {
     BYZ_REQUIRE(G && out && row_list && count_dev && n_cols > 0 && ld >= n_cols, "mean of rows: bad arguments");
-    const bool vec4 = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(G) % 16 == 0) &&
-                      n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
-    const dim3 grid(static_cast<unsigned>(ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1))));
+    WalkShape shape;
+    BYZ_TRY(walk_shape(ctx, G, ld, n_cols, "mean of rows", &shape));
+    const dim3 grid(static_cast<unsigned>(shape.blocks));
     KernelTimer t(ctx, BYZ_K_COLUMN_STATS, stream);
-    if (vec4) column_sequential_kernel<4, 3><<<grid, kThreads, 0, stream>>>(G, 0, n_cols, ld, 0.0f, out, nullptr, nullptr, count_dev, row_list);
+    if (shape.vec4) column_sequential_kernel<4, 3><<<grid, kThreads, 0, stream>>>(G, 0, n_cols, ld, 0.0f, out, nullptr, nullptr, count_dev, row_list);
     else column_sequential_kernel<1, 3><<<grid, kThreads, 0, stream>>>(G, 0, n_cols, ld, 0.0f, out, nullptr, nullptr, count_dev, row_list);
     return check_launch("column_sequential_kernel (counted row list)");
 }
@@ -570,15 +501,15 @@ int launch_column_chain(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_
                         const float* mean, float* out, hipStream_t stream) {
     BYZ_REQUIRE(G && out && n_rows > 0 && n_cols > 0 && ld >= n_cols, "column chain: bad shape %lld x %lld ld %lld",
                 (long long)n_rows, (long long)n_cols, (long long)ld);
-    const bool vec4 = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(G) % 16 == 0) &&
-                      n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
-    const unsigned blocks = static_cast<unsigned>(ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1)));
+    WalkShape shape;
+    BYZ_TRY(walk_shape(ctx, G, ld, n_cols, "column chain", &shape));
+    const unsigned blocks = static_cast<unsigned>(shape.blocks);
     KernelTimer t(ctx, BYZ_K_COLUMN_STATS, stream);
     if (mean != nullptr) {
-        if (vec4) column_chain_kernel<4, true><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, mean, out);
+        if (shape.vec4) column_chain_kernel<4, true><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, mean, out);
         else column_chain_kernel<1, true><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, mean, out);
     } else {
-        if (vec4) column_chain_kernel<4, false><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, nullptr, out);
+        if (shape.vec4) column_chain_kernel<4, false><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, nullptr, out);
         else column_chain_kernel<1, false><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, carry, nullptr, out);
     }
     return check_launch("column_chain_kernel");

@@ -138,11 +138,11 @@ struct byz_ctx {
     byz::Buffer scores;          // n fp32 Krum scores
     byz::Buffer multi_krum;      // Multi-Krum's ranking: n_pad sort keys, then n row flags
     byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
-    byz::Buffer geomed;          // geometric median: 64 fp64 partials per row, then sq (n + 1) and the weights (n)
+    byz::Buffer rows;            // the row-distance loops (geometric median, centered clipping): rowsq's (chunk, row) fp64 partials
+                                 // (at most 64 per row), then sq (n + 1) and the weights or scales (n)
     hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
     byz::Buffer dnc;             // DnC: the centred sample (n x sub_dim fp64), the column partials, the n-vectors, keep and good
     hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
-    byz::Buffer cclip;           // centered clipping: rowsq's (row, chunk) fp64 partials, then sq (n) and the scales (n)
     hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
@@ -360,9 +360,9 @@ int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w
 int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
                        hipStream_t stream);
 int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream);
-// cclip.hip: centered clipping.  scales: s from sq (sq == nullptr: all 1), the counts into the context's words; update:
-// out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
+// cclip.hip: centered clipping's scales: s from sq (sq == nullptr: all 1), the counts into the context's words
 int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, double* s, hipStream_t stream);
+// geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,

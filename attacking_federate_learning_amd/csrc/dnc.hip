@@ -19,7 +19,7 @@
 //   compact  the kept rows in ascending order and their count (multi_krum.hip's flag compaction)
 // Every sum has a fixed order: two calls give the same bits.  Nothing synchronises with the host; the kept count stays in the
 // context's small area (common.hpp) until byz_dnc_info reads it.
-#include "common.hpp"
+#include "row_walk.hpp"
 
 #include <algorithm>
 
@@ -36,27 +36,6 @@ constexpr int kRowRun = 8;                          // colsum: rows whose loads 
 constexpr int kStateActive = 0;                     // n_a
 constexpr int kStateZero = 1;                       // != 0: M_i0i0, a |y| or lambda was 0 (or no row is active): active scores are 0
 constexpr int kStateWords = 4;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// fixed-order sum over one workgroup of THREADS threads (every thread gets the total)
-template <int THREADS>
-__device__ double block_sum(double v, double* lds) {
-    const int tid = threadIdx.x;
-    lds[tid] = v;
-    __syncthreads();
-    for (int step = THREADS / 2; step >= 1; step >>= 1) {
-        if (tid < step) lds[tid] = lds[tid] + lds[tid + step];
-        __syncthreads();
-    }
-    const double total = lds[0];
-    __syncthreads();
-    return total;
-}
 
 __global__ __launch_bounds__(kThreads) void dnc_gather_kernel(const float* __restrict__ G, int64_t ld,
                                                               const int64_t* __restrict__ columns, int64_t b,
@@ -84,7 +63,7 @@ __global__ __launch_bounds__(kOneThreads) void dnc_prepare_kernel(const double* 
         wt[i] = active ? 1.0 : 0.0;
         if (active) count = count + 1.0;
     }
-    const double n_a = block_sum<kOneThreads>(count, lds);
+    const double n_a = block_sum<double, kOneThreads>(count, lds);
     if (threadIdx.x == 0) {
         state[kStateActive] = n_a;
         state[kStateZero] = n_a == 0.0 ? 1.0 : 0.0;
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void dnc_centre_kernel(double* __restrict
         row[j] = c;
         acc = acc + c * c;
     }
-    const double total = block_sum<kThreads>(acc, lds);
+    const double total = block_sum<double, kThreads>(acc, lds);
     if (threadIdx.x == 0) diag[i] = total;
 }
 
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(kOneThreads) void dnc_step_kernel(const double* __r
     const int64_t hi = lo + per < n ? lo + per : n;
     double s = 0.0;
     for (int64_t i = lo; i < hi; ++i) s = s + (last ? u[i] * y[i] : y[i] * y[i]);
-    const double total = block_sum<kOneThreads>(s, lds);
+    const double total = block_sum<double, kOneThreads>(s, lds);
     const bool zero_before = state[kStateZero] != 0.0;
     __syncthreads();                                  // every thread has read the flag
     if (!last) {

@@ -9,37 +9,30 @@
 //           kMaxChunks chunks: the scratch is O(n_rows) whatever n_cols is.
 //   wmean   out[c] = fl32(S_c / W), S_c = sum over rows with w_i != 0 of w_i * (double)x_ic, W = sum w_i, both sequential in
 //           row order with no fused multiply-add (this file is compiled with -ffp-contract=off).  One thread walks the rows
-//           for VEC columns as column_sequential_kernel does; the weights are uniform and arrive through scalar loads.  A row
-//           of weight 0 is neither loaded nor multiplied, so 0 * inf never reaches a column.
+//           for VEC columns (walk_rows, row_walk.hpp); the weights are uniform and arrive through scalar loads.  A row of
+//           weight 0 is neither loaded nor multiplied, so 0 * inf never reaches a column.
+//   update  centered clipping's step (cclip.hip has its scales): out[c] = fl32((double)v[c] + S_c / n), S_c = sum over the
+//           rows with s_i != 0 of s_i * ((double)x_ic - (double)v[c]).  The same kernel template as wmean (weighted_rows_kernel,
+//           CENTRED): the same walk, the same launch shape, another product and another last line.
 //   step    one workgroup: d_i = sqrt(sq_i), F = sum of d over the active rows (fixed order), the stop test
 //           |F_old - F| <= ftol * F, beta_i = 1 / max(nu, d_i).
 // Every launch of the loop is enqueued up front; after the stop the remaining launches read the done word and return at once
 // (the redo_gate idiom of column_sequential_kernel).  The state lives in the context's small area (common.hpp).
-#include "common.hpp"
+#include "row_walk.hpp"
 
 #include <algorithm>
 
 namespace byz {
 namespace {
 
-constexpr int kThreads = 256;                       // rowsq and wmean workgroups
+constexpr int kThreads = kWalkThreads;              // rowsq and weighted_rows workgroups
 constexpr int kWaves = kThreads / 64;
 constexpr int kRowsPerWave = 8;
 constexpr int kRowBlock = kWaves * kRowsPerWave;    // rows of one rowsq workgroup
 constexpr int kSegs = 4;                            // dwordx4 loads per lane and row in one window
 constexpr int kWindow = 64 * 4 * kSegs;             // columns a wave covers at once (1024)
 constexpr int kMaxChunks = 64;                      // fp64 partials per row at most
-constexpr int kRowRun = 8;                          // wmean: rows whose loads are issued together
 constexpr int kStepThreads = 1024;
-
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
-
-// run unless *skip_if_set != 0; with run_if_set, only if *run_if_set != 0
-__device__ __forceinline__ bool gated_out(const int32_t* skip_if_set, const int32_t* run_if_set) {
-    if (skip_if_set != nullptr && __hip_atomic_load(skip_if_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
-    if (run_if_set != nullptr && __hip_atomic_load(run_if_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return true;
-    return false;
-}
 
 // four consecutive floats at column c (of a window that ends at c_end): dwordx4 when whole and aligned, masked otherwise
 template <bool VEC4>
@@ -51,12 +44,6 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int64_t c, in
 #pragma unroll
         for (int v = 0; v < 4; ++v) x[v] = c + v < c_end ? p[c + v] : 0.0f;
     }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // partials[chunk * n_rows + row]; z == nullptr: the distance to the origin
@@ -120,84 +107,46 @@ __global__ __launch_bounds__(256) void rowsq_finish_kernel(const double* __restr
     sq[i] = s;
 }
 
-template <int VEC>
-__device__ __forceinline__ void load_cols(const float* __restrict__ p, bool full, int64_t c0, int64_t n_cols, float (&x)[VEC]) {
-    if constexpr (VEC == 4) {
-        if (full) {
-            const float4u q = *reinterpret_cast<const float4u*>(p);
-            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) x[v] = (c0 + v < n_cols) ? p[v] : 0.0f;
-        }
-    } else {
-        x[0] = p[0];
-    }
-}
-
-template <int VEC>
-__global__ __launch_bounds__(kThreads) void wmean_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols, int64_t ld,
-                                                         const double* __restrict__ w, float* __restrict__ out,
-                                                         const int32_t* skip_if_set, const int32_t* run_if_set) {
+// CENTRED = false, the weighted mean: acc += w * (double)x, W += w, out = fl32(acc / W); v is not read.
+// CENTRED = true, centered clipping's update: acc += s * ((double)x - (double)v), out = fl32((double)v + acc / n_rows); v and out
+// may be the same buffer (a thread reads its own columns of v before it writes them).
+template <int VEC, bool CENTRED>
+__global__ __launch_bounds__(kThreads) void weighted_rows_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols,
+                                                                 int64_t ld, const float* v, const double* __restrict__ w,
+                                                                 float* out, const int32_t* skip_if_set,
+                                                                 const int32_t* run_if_set) {
     if (gated_out(skip_if_set, run_if_set)) return;
     const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * VEC;
     if (c0 >= n_cols) return;
-    const bool full = c0 + VEC <= n_cols;
-    const float* p = G + c0;
-    double acc[VEC];
+    double vd[VEC], acc[VEC];
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
+    for (int k = 0; k < VEC; ++k) {
+        vd[k] = CENTRED && c0 + k < n_cols ? static_cast<double>(v[c0 + k]) : 0.0;
+        acc[k] = 0.0;
+    }
     double W = 0.0;
-    int64_t r = 0;
-    for (; r + kRowRun <= n_rows; r += kRowRun) {
-        double wr[kRowRun];
+    walk_rows<VEC>(
+        G + c0, ld, n_rows, c0, n_cols, [](int64_t r) __attribute__((always_inline)) { return r; },
+        [&](int64_t r) __attribute__((always_inline)) { return w[r]; },          // uniform: one scalar load for a run
+        [&](int64_t, double wr, const float(&x)[VEC]) __attribute__((always_inline)) {
+            if constexpr (!CENTRED) W = W + wr;
 #pragma unroll
-        for (int u = 0; u < kRowRun; ++u) wr[u] = w[r + u];          // uniform: one scalar load for the run
-        float x[kRowRun][VEC];
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u) {
-            if (wr[u] != 0.0) load_cols<VEC>(p + (r + u) * ld, full, c0, n_cols, x[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kRowRun; ++u) {
-            if (wr[u] != 0.0) {
-                W = W + wr[u];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = acc[v] + wr[u] * static_cast<double>(x[u][v]);
+            for (int k = 0; k < VEC; ++k) {
+                if constexpr (CENTRED) acc[k] = acc[k] + wr * (static_cast<double>(x[k]) - vd[k]);
+                else acc[k] = acc[k] + wr * static_cast<double>(x[k]);
             }
-        }
-    }
-    for (; r < n_rows; ++r) {
-        const double wu = w[r];
-        if (wu != 0.0) {
-            float x[VEC];
-            load_cols<VEC>(p + r * ld, full, c0, n_cols, x);
-            W = W + wu;
+        });
+    const double divisor = CENTRED ? static_cast<double>(n_rows) : W;
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = acc[v] + wu * static_cast<double>(x[v]);
-        }
+    for (int k = 0; k < VEC; ++k) {
+        if (c0 + k >= n_cols) continue;
+        if constexpr (CENTRED) out[c0 + k] = static_cast<float>(vd[k] + acc[k] / divisor);
+        else out[c0 + k] = static_cast<float>(acc[k] / divisor);
     }
-#pragma unroll
-    for (int v = 0; v < VEC; ++v)
-        if (c0 + v < n_cols) out[c0 + v] = static_cast<float>(acc[v] / W);
 }
 
 // ---- the loop's small kernels (state in ctx->small, common.hpp) ----------------------------------------------------------
 __device__ __forceinline__ double* objective_of(int32_t* words) { return reinterpret_cast<double*>(words + kGeomedObjective); }
-
-// fixed-order sum over one workgroup of kStepThreads threads (every thread gets the total)
-__device__ double block_sum(double v, double* lds) {
-    const int tid = threadIdx.x;
-    lds[tid] = v;
-    __syncthreads();
-    for (int step = kStepThreads / 2; step >= 1; step >>= 1) {
-        if (tid < step) lds[tid] = lds[tid] + lds[tid + step];
-        __syncthreads();
-    }
-    const double total = lds[0];
-    __syncthreads();
-    return total;
-}
 
 __global__ __launch_bounds__(256) void finite_check_kernel(const float* __restrict__ v, int64_t n, int32_t* words,
                                                            double* flag_f64) {
@@ -225,7 +174,7 @@ __global__ __launch_bounds__(kStepThreads) void geomed_fallback_kernel(const dou
         w[i] = active ? 1.0 : 0.0;
         if (!active) excluded = excluded + 1.0;
     }
-    const double total = block_sum(excluded, lds);
+    const double total = block_sum<double, kStepThreads>(excluded, lds);
     if (threadIdx.x == 0) {
         const int64_t ex = static_cast<int64_t>(total);
         words[kGeomedExcluded] = static_cast<int32_t>(ex);
@@ -248,7 +197,7 @@ __global__ __launch_bounds__(kStepThreads) void geomed_step_kernel(const double*
     double f = 0.0;
     for (int64_t i = lo; i < hi; ++i)
         if (!fallback || w[i] != 0.0) f = f + sqrt(sq[i]);
-    const double F = block_sum(f, lds);
+    const double F = block_sum<double, kStepThreads>(f, lds);
     const double F_old = *objective_of(words);
     const bool stop = k > 0 && fabs(F_old - F) <= ftol * F;
     __syncthreads();                                  // every thread has read F_old
@@ -279,7 +228,7 @@ __global__ __launch_bounds__(kStepThreads) void geomed_weights_kernel(const doub
         if (updated) s = s + w[i];
         else if (!fallback || w[i] != 0.0) s = s + 1.0;
     }
-    const double total = block_sum(s, lds);
+    const double total = block_sum<double, kStepThreads>(s, lds);
     for (int64_t i = lo; i < hi; ++i) {
         const bool active = !fallback || w[i] != 0.0;
         if (total == 0.0) out[i] = 0.0;
@@ -287,8 +236,6 @@ __global__ __launch_bounds__(kStepThreads) void geomed_weights_kernel(const doub
         else out[i] = active ? 1.0 / total : 0.0;
     }
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 
@@ -319,21 +266,35 @@ int launch_row_sqdist(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     return check_launch("rowsq_finish_kernel");
 }
 
+// wmean (v == nullptr) or centered clipping's update (v: the centre); one launch shape for both
+static int launch_weighted_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v,
+                                const double* w, float* out, const int32_t* skip_if_set, const int32_t* run_if_set,
+                                const char* who, hipStream_t stream) {
+    BYZ_REQUIRE(G && w && out && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols, "%s: bad arguments", who);
+    WalkShape shape;
+    BYZ_TRY(walk_shape(ctx, G, ld, n_cols, who, &shape));
+    const unsigned blocks = static_cast<unsigned>(shape.blocks);
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+#define BYZ_WEIGHTED_ROWS(VEC, CENTRED) \
+    weighted_rows_kernel<VEC, CENTRED><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, v, w, out, skip_if_set, run_if_set)
+    if (v != nullptr) {
+        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, true); else BYZ_WEIGHTED_ROWS(1, true);
+    } else {
+        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, false); else BYZ_WEIGHTED_ROWS(1, false);
+    }
+#undef BYZ_WEIGHTED_ROWS
+    return check_launch("weighted_rows_kernel");
+}
+
 int launch_weighted_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w, float* out,
                          const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream) {
-    BYZ_REQUIRE(G && w && out && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols,
-                "weighted mean: bad arguments");
-    // 16-byte loads when every row starts 16-byte aligned and the columns alone fill the chip (column_pass's rule)
-    const bool vec4 = (ld % 4 == 0) && aligned16(G) && n_cols >= static_cast<int64_t>(4) * kThreads * ctx->num_cus * 2;
-    const int64_t blocks = ceil_div(n_cols, static_cast<int64_t>(kThreads) * (vec4 ? 4 : 1));
-    if (blocks >= (int64_t{1} << 31)) {
-        set_error("weighted mean: %lld columns is beyond one launch", (long long)n_cols);
-        return BYZ_E_UNSUPPORTED;
-    }
-    KernelTimer t(ctx, BYZ_K_MISC, stream);
-    if (vec4) wmean_kernel<4><<<static_cast<unsigned>(blocks), kThreads, 0, stream>>>(G, n_rows, n_cols, ld, w, out, skip_if_set, run_if_set);
-    else wmean_kernel<1><<<static_cast<unsigned>(blocks), kThreads, 0, stream>>>(G, n_rows, n_cols, ld, w, out, skip_if_set, run_if_set);
-    return check_launch("wmean_kernel");
+    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, nullptr, w, out, skip_if_set, run_if_set, "weighted mean", stream);
+}
+
+int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
+                       float* out, hipStream_t stream) {
+    BYZ_REQUIRE(v, "clip update: bad arguments");
+    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, v, s, out, nullptr, nullptr, "clip update", stream);
 }
 
 int launch_geomed_finite_check(byz_ctx* ctx, const float* v, int64_t n, double* flag_f64, hipStream_t stream) {

@@ -16,7 +16,7 @@
 // np.clip is minimum(maximum(x, lo), hi) with NaN propagating from either operand.
 //
 // Bytes per element: initial 12 (2 reads, 1 write); clip 20 (4 reads, 1 write); assembly 8 (1 read, 1 write).
-#include "common.hpp"
+#include "row_walk.hpp"     // aligned16
 
 #include <vector>
 
@@ -149,8 +149,6 @@ __global__ __launch_bounds__(kThreads) void assemble_rows_kernel(const int64_t* 
     copy_span(src[r * n_segments + seg], G + r * ld + begin, len, static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x,
               static_cast<int64_t>(gridDim.x) * kThreads);
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 

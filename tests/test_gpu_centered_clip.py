@@ -166,7 +166,8 @@ def test_two_calls_strided_views_and_host_matrices_give_the_same_bits(eng, torch
 
 def test_clip_update_alone(eng, torch):
     rng = np.random.default_rng(39)
-    for n, d in [(37, 3001), (300, 70000), (9, 5)]:
+    # (7, 129): no whole run of eight rows, the tail loop alone; (16, 1): whole runs, no tail, one column
+    for n, d in [(37, 3001), (300, 70000), (9, 5), (7, 129), (16, 1)]:
         g = rng.standard_normal((n, d)).astype(np.float32)
         v = rng.standard_normal(d).astype(np.float32)
         s = rng.random(n)
@@ -175,12 +176,13 @@ def test_clip_update_alone(eng, torch):
         want = restated_clip_update(g, v, s)
         gt = on_gpu(torch, eng, g)
         got = eng.clip_update(gt, on_gpu(torch, eng, v), on_gpu(torch, eng, s)).cpu().numpy()
-        assert np.isfinite(got).all() and close(got, want, g)
-        assert close(eng.clip_update(g, v, s), want, g)
+        assert np.isfinite(got).all() and np.array_equal(got, want)     # the restatement is the kernel's arithmetic: bits
+        assert np.array_equal(eng.clip_update(g, v, s), want)
 
 
 def test_wide_rows_take_the_four_wide_update(eng, torch):
-    # launch_clip_update takes clip_update_kernel<4> from 4 * 256 * num_cus * 2 = 524,288 columns on (ld % 4 == 0, aligned G)
+    # launch_clip_update takes weighted_rows_kernel<4, true> from 4 * 256 * num_cus * 2 = 524,288 columns on (ld % 4 == 0,
+    # aligned G): the weighted mean's template and launch rule
     n, wide = 13, 600_000
     rng = np.random.default_rng(40)
     g = rng.standard_normal((n, wide)).astype(np.float32)
@@ -191,7 +193,7 @@ def test_wide_rows_take_the_four_wide_update(eng, torch):
     gt, vt, st = on_gpu(torch, eng, g), on_gpu(torch, eng, v), on_gpu(torch, eng, s)
     for cols in (wide, wide - 1, wide - 1027):                       # whole, a masked tail, no multiple of 1024
         got = eng.clip_update(gt[:, :cols], vt[:cols].contiguous(), st).cpu().numpy()
-        assert close(got, restated_clip_update(g[:, :cols], v[:cols], s), g)
+        assert np.array_equal(got, restated_clip_update(g[:, :cols], v[:cols], s))
     odd = torch.empty((n, wide + 5), dtype=torch.float32, device=gt.device)[:, 1:wide + 1]
     odd.copy_(gt)
     assert torch.equal(eng.clip_update(odd, vt, st), eng.clip_update(gt, vt, st))      # the scalar kernel: the same bits

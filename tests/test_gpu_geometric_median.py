@@ -274,7 +274,7 @@ def test_argument_errors(eng, torch):
 
 
 # ---- the 4-wide paths: what realistic model sizes run ---------------------------------------------------------------
-# launch_weighted_mean takes wmean_kernel<4> from 4 * 256 * num_cus * 2 = 524,288 columns on (ld % 4 == 0, 16-byte
+# launch_weighted_mean takes weighted_rows_kernel<4, false> from 4 * 256 * num_cus * 2 = 524,288 columns on (ld % 4 == 0, 16-byte
 # aligned G); rowsq takes dwordx4 loads whenever ld % 4 == 0 and G and z are 16-byte aligned
 WIDE = 600_000
 
