@@ -105,6 +105,12 @@ _PROTOTYPES = {
     'byz_centered_clip_info': [c_vp, _P(c_i64), _P(c_i64)],
     'byz_centered_clip_host': [c_vp, c_vp, c_i64, c_i64, _P(CclipParams), c_vp, c_vp, c_vp],
     'byz_centered_clip_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(CclipParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_row_dots_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_scaled_rows_sum_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_fltrust_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_fltrust_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i32), _P(ctypes.c_double)],
+    'byz_fltrust_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_fltrust_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

@@ -701,21 +701,26 @@ int check_geomed(const byz_geomed_params* params, int64_t n_rows, const char* wh
     return BYZ_OK;
 }
 
-// What the row-distance loops (the geometric median, centered clipping, byz_row_sqdist_dev) keep in ctx->rows.
+// What the row-distance loops (the geometric median, centered clipping, FLTrust, byz_row_sqdist_dev, byz_row_dots_dev) keep in
+// ctx->rows.  planes = 2 is FLTrust's: two sums a row.
 struct RowScratch {
-    double* partials;   // chunks x n: the (row, column chunk) partials of rowsq
-    double* a;          // n + 1: the squared distances (the geometric median's fallback flag behind the rows)
-    double* b;          // n: the weights, or the scales
+    double* partials;   // planes x chunks x n: the (row, column chunk) partials of rowsq
+    double* a;          // planes * n + 1: the squared distances (the geometric median's fallback flag behind the rows); FLTrust:
+                        // p (n), q (n), q0 (1), one all-reduce's worth
+    double* b;          // planes * n: the weights, or the scales; FLTrust: ts (n), w (n)
+    double* root;       // planes = 2 only, 64: the chunk partials of the root's squared norm
 };
 
-// sized by the chunks geomed_chunks picks for this shape: at most 64 per row, about num_cus * 256 + n in all
-int row_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, RowScratch* out) {
+// sized by the chunks geomed_chunks picks for this shape: at most 64 per row and plane, about num_cus * 256 + n in all
+int row_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, RowScratch* out, int planes = 1) {
     int64_t chunk_cols = 0;
-    const int64_t partials = static_cast<int64_t>(geomed_chunks(ctx, n, n_cols, &chunk_cols)) * n;
-    BYZ_TRY(ctx->rows.ensure(static_cast<size_t>(partials + (n + 1) + n) * sizeof(double)));
+    const int64_t partials = static_cast<int64_t>(geomed_chunks(ctx, n, n_cols, &chunk_cols)) * n * planes;
+    const int64_t root = planes == 2 ? geomed_chunks(ctx, 1, n_cols, &chunk_cols) : 0;
+    BYZ_TRY(ctx->rows.ensure(static_cast<size_t>(partials + (planes * n + 1) + planes * n + root) * sizeof(double)));
     out->partials = ctx->rows.as<double>();
     out->a = out->partials + partials;
-    out->b = out->a + (n + 1);
+    out->b = out->a + (planes * n + 1);
+    out->root = out->b + planes * n;
     return BYZ_OK;
 }
 
@@ -905,6 +910,85 @@ int byz_centered_clip_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* exclude
     BYZ_TRY(read_small(ctx, words, ctx->cclip_stream));   // synchronises the last call's stream
     if (clipped_rows) *clipped_rows = words[kCclipClipped];
     if (excluded_rows) *excluded_rows = words[kCclipExcluded];
+    return BYZ_OK;
+}
+
+// ---- FLTrust (Cao, Fang, Liu and Gong, NDSS 2021; beyond the reference) -------------------------------------------------
+namespace {
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device.  Two passes over G:
+// the dots, then the sum; the root's squared norm and the trust scores are two tiny launches between them.
+int fltrust(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const float* root, byz_allreduce_f64_fn allreduce,
+            void* user, float* out, double* trust, double* weights, void* stream) {
+    hipStream_t s = as_stream(stream);
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n, n_cols, &t, 2));
+    double *pq = t.a, *ts = t.b, *w = t.b + n;
+    ctx->fltrust_stream = s;
+    BYZ_TRY(launch_row_sqdist(ctx, root, 1, n_cols, n_cols, nullptr, t.root, pq + 2 * n, nullptr, nullptr, s));
+    BYZ_TRY(launch_row_dots(ctx, G, n, n_cols, ld, root, t.partials, pq, pq + n, s));
+    if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, pq, 2 * n + 1, stream, "fltrust (dots and norms)"));
+    BYZ_TRY(launch_fltrust_trust(ctx, pq, n, ts, w, s));
+    const double* T = reinterpret_cast<const double*>(geomed_words(ctx) + kFltrustTrustSum);
+    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, w, T, out, s));      // (out may be root: its last reader is behind)
+    const size_t row_bytes = static_cast<size_t>(n) * sizeof(double);
+    if (trust != nullptr) BYZ_HIP(hipMemcpyAsync(trust, ts, row_bytes, hipMemcpyDeviceToDevice, s));
+    if (weights != nullptr) BYZ_HIP(hipMemcpyAsync(weights, w, row_bytes, hipMemcpyDeviceToDevice, s));
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_row_dots_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* r, double* dot,
+                     double* sq, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_dots"));
+    BYZ_REQUIRE(r && dot && sq, "row_dots: null vector or output");
+    BYZ_TRY(check_row_ceiling("row_dots", n_rows));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n_rows, n_cols, &t, 2));
+    return launch_row_dots(ctx, G, n_rows, n_cols, ld, r, t.partials, dot, sq, as_stream(stream));
+}
+
+int byz_scaled_rows_sum_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w,
+                            const double* divisor, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "scaled_rows_sum"));
+    BYZ_REQUIRE(w && divisor && out, "scaled_rows_sum: null weights, divisor or output");
+    BYZ_TRY(check_row_ceiling("scaled_rows_sum", n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "scaled_rows_sum"));
+    return launch_scaled_rows_sum(ctx, G, n_rows, n_cols, ld, w, divisor, out, as_stream(stream));
+}
+
+int byz_fltrust_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* root, float* out,
+                    double* trust, double* weights, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "fltrust"));
+    BYZ_REQUIRE(root && out, "fltrust: null root or output");
+    BYZ_TRY(check_row_ceiling("fltrust", n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "fltrust"));
+    return fltrust(ctx, G, n_rows, n_cols, ld, root, nullptr, nullptr, out, trust, weights, stream);
+}
+
+int byz_fltrust_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* root,
+                            byz_allreduce_f64_fn allreduce, void* user, float* out, double* trust, double* weights,
+                            void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "fltrust_sharded"));
+    BYZ_REQUIRE(root && out && allreduce, "fltrust_sharded: null root, output or all-reduce");
+    BYZ_TRY(check_row_ceiling("fltrust_sharded", n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "fltrust_sharded"));
+    return fltrust(ctx, G, n_rows, n_cols, ld, root, allreduce, user, out, trust, weights, stream);
+}
+
+int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows, int32_t* root_ok, double* trust_sum) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->fltrust_stream));   // synchronises the last call's stream
+    if (trusted_rows) *trusted_rows = words[kFltrustTrusted];
+    if (excluded_rows) *excluded_rows = words[kFltrustExcluded];
+    if (root_ok) *root_ok = words[kFltrustRootOk];
+    if (trust_sum) std::memcpy(trust_sum, words + kFltrustTrustSum, sizeof(double));
     return BYZ_OK;
 }
 
@@ -1309,6 +1393,30 @@ int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, in
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (scales_host)
         BYZ_HIP(hipMemcpyAsync(scales_host, scales, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
+    return check_small(ctx, s);
+}
+
+int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* root_host, float* out_host,
+                     double* trust_host, double* weights_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "fltrust"));
+    BYZ_REQUIRE(root_host && out_host, "fltrust: null root or output");
+    BYZ_TRY(check_row_ceiling("fltrust", n_rows));
+    hipStream_t s = nullptr;
+    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the scores 8-byte aligned)
+    const size_t row_bytes = static_cast<size_t>(n_rows) * sizeof(double);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + 2 * row_bytes, s));
+    float* G = ctx->stage_in.as<float>();
+    float* out = ctx->stage_out.as<float>();
+    double* trust = reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes);
+    double* weights = trust + n_rows;
+    // the root is staged into the output vector: the device call runs in place on it
+    BYZ_HIP(hipMemcpyAsync(out, root_host, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyHostToDevice, s));
+    BYZ_TRY(byz_fltrust_dev(ctx, G, n_rows, n_cols, n_cols, out, out, trust_host ? trust : nullptr,
+                            weights_host ? weights : nullptr, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (trust_host) BYZ_HIP(hipMemcpyAsync(trust_host, trust, row_bytes, hipMemcpyDeviceToHost, s));
+    if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
 }
 

@@ -5,7 +5,7 @@
 //           excluded); the clipped and excluded counts go to the context's small area (common.hpp).
 //   update  out[c] = fl32((double)v[c] + S_c / n), S_c = sum over the rows with s_i != 0 of s_i * ((double)x_ic - (double)v[c]),
 //           sequential in row order, no fused multiply-add; a row of scale 0 is neither loaded nor multiplied.  It is the
-//           weighted mean's kernel template with another product (weighted_rows_kernel<VEC, true>, geomed.hip, where
+//           weighted mean's kernel template with another product (weighted_rows_kernel<VEC, kRowsCentred>, geomed.hip, where
 //           launch_clip_update lives beside launch_weighted_mean).
 // One iteration is launch_row_sqdist (geomed.hip, reused as it is), scales, update: two passes over G.
 #include "row_walk.hpp"

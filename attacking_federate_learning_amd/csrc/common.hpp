@@ -138,12 +138,14 @@ struct byz_ctx {
     byz::Buffer scores;          // n fp32 Krum scores
     byz::Buffer multi_krum;      // Multi-Krum's ranking: n_pad sort keys, then n row flags
     byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
-    byz::Buffer rows;            // the row-distance loops (geometric median, centered clipping): rowsq's (chunk, row) fp64 partials
-                                 // (at most 64 per row), then sq (n + 1) and the weights or scales (n)
+    byz::Buffer rows;            // the row-distance loops (geometric median, centered clipping, FLTrust): rowsq's (chunk, row) fp64
+                                 // partials (at most 64 per row, FLTrust: twice that), then sq (n + 1; FLTrust: p, q, q0) and the
+                                 // weights or scales (n; FLTrust: ts and w)
     hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
     byz::Buffer dnc;             // DnC: the centred sample (n x sub_dim fp64), the column partials, the n-vectors, keep and good
     hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
     hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
+    hipStream_t fltrust_stream = nullptr;  // stream of the last FLTrust call (byz_fltrust_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -189,7 +191,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 32;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 36;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -205,6 +207,9 @@ constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kG
 constexpr int kDncKept = 26, kDncInactive = 27;
 // centered clipping: the rows its last iteration clipped (tau < d < inf) and excluded (d not finite)
 constexpr int kCclipClipped = 28, kCclipExcluded = 29;
+// FLTrust: the rows with a positive trust score, the rows with a non-finite dot product or norm, T = the sum of the trust scores
+// (fp64: two words, 8-byte aligned), the root's squared norm was finite and positive
+constexpr int kFltrustTrusted = 30, kFltrustExcluded = 31, kFltrustTrustSum = 32, kFltrustRootOk = 34;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -365,6 +370,14 @@ int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, d
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);
+// geomed.hip, rowsq's kernel template with two sums a row: dot[i] = x_i . r, sq[i] = |x_i|^2 (partials: 2 * chunks * n_rows)
+int launch_row_dots(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* r, double* partials,
+                    double* dot, double* sq, hipStream_t stream);
+// geomed.hip, the weighted mean's kernel template: out = *divisor > 0 ? sum_i w_i x_i / *divisor : 0
+int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w,
+                           const double* divisor, float* out, hipStream_t stream);
+// fltrust.hip: FLTrust's trust scores ts and weights w from pq = p (n), q (n), q0 (1); T and the counts into the context's words
+int launch_fltrust_trust(byz_ctx* ctx, const double* pq, int64_t n, double* ts, double* w, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

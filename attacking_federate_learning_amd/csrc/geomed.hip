@@ -13,7 +13,12 @@
 //           weight 0 is neither loaded nor multiplied, so 0 * inf never reaches a column.
 //   update  centered clipping's step (cclip.hip has its scales): out[c] = fl32((double)v[c] + S_c / n), S_c = sum over the
 //           rows with s_i != 0 of s_i * ((double)x_ic - (double)v[c]).  The same kernel template as wmean (weighted_rows_kernel,
-//           CENTRED): the same walk, the same launch shape, another product and another last line.
+//           kRowsCentred): the same walk, the same launch shape, another product and another last line.
+//   dots    FLTrust's first pass (fltrust.hip has its trust scores): p[i] = sum_c (double)x_ic * (double)r_c and
+//           q[i] = sum_c (double)x_ic^2 in one read of G.  rowsq's kernel template with two accumulators a row
+//           (rowsq_partial_kernel<VEC4, true>): the same geometry, the same order of additions, partials[2][chunk][row].
+//   scaled  FLTrust's second pass: out[c] = T > 0 ? fl32(S_c / T) : 0, S_c as wmean's, T read from one device double.
+//           weighted_rows_kernel's third mode (kRowsScaled).
 //   step    one workgroup: d_i = sqrt(sq_i), F = sum of d over the active rows (fixed order), the stop test
 //           |F_old - F| <= ftol * F, beta_i = 1 / max(nu, d_i).
 // Every launch of the loop is enqueued up front; after the stop the remaining launches read the done word and return at once
@@ -46,8 +51,10 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int64_t c, in
     }
 }
 
-// partials[chunk * n_rows + row]; z == nullptr: the distance to the origin
-template <bool VEC4>
+// DOTS = false: partials[chunk * n_rows + row]; z == nullptr: the distance to the origin.
+// DOTS = true: z is FLTrust's root (never null); partials[chunk * n_rows + row] is the row's dot product with it over the
+// chunk, partials[(chunks + chunk) * n_rows + row] the row's own squared norm (chunks = gridDim.y).
+template <bool VEC4, bool DOTS>
 __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols,
                                                                  int64_t ld, const float* __restrict__ z, int64_t chunk_cols,
                                                                  double* __restrict__ partials, const int32_t* skip_if_set,
@@ -59,8 +66,13 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
     const int64_t c_begin = static_cast<int64_t>(blockIdx.y) * chunk_cols;
     const int64_t c_end = c_begin + chunk_cols < n_cols ? c_begin + chunk_cols : n_cols;
     double acc[kRowsPerWave];
+    [[maybe_unused]] double acc_q[DOTS ? kRowsPerWave : 1];
 #pragma unroll
     for (int r = 0; r < kRowsPerWave; ++r) acc[r] = 0.0;
+    if constexpr (DOTS) {
+#pragma unroll
+        for (int r = 0; r < kRowsPerWave; ++r) acc_q[r] = 0.0;
+    }
     for (int64_t w0 = c_begin; w0 < c_end; w0 += kWindow) {
         double zs[kSegs][4];
 #pragma unroll
@@ -78,14 +90,22 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
 #pragma unroll
                 for (int k = 0; k < kSegs; ++k) load4<VEC4>(p, w0 + k * 256 + lane * 4, c_end, x[k]);
                 double s = 0.0;
+                [[maybe_unused]] double s_q = 0.0;
 #pragma unroll
                 for (int k = 0; k < kSegs; ++k)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
-                        const double d = static_cast<double>(x[k][v]) - zs[k][v];
-                        s = s + d * d;
+                        if constexpr (DOTS) {
+                            const double xd = static_cast<double>(x[k][v]);
+                            s = s + xd * zs[k][v];
+                            s_q = s_q + xd * xd;
+                        } else {
+                            const double d = static_cast<double>(x[k][v]) - zs[k][v];
+                            s = s + d * d;
+                        }
                     }
                 acc[r] = acc[r] + s;
+                if constexpr (DOTS) acc_q[r] = acc_q[r] + s_q;
             }
         }
     }
@@ -93,28 +113,38 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
     for (int r = 0; r < kRowsPerWave; ++r) {
         const double s = wave_sum(acc[r]);
         if (lane == 0 && row0 + r < n_rows) partials[static_cast<int64_t>(blockIdx.y) * n_rows + row0 + r] = s;
+        if constexpr (DOTS) {
+            const double s_q = wave_sum(acc_q[r]);
+            if (lane == 0 && row0 + r < n_rows)
+                partials[(static_cast<int64_t>(gridDim.y) + blockIdx.y) * n_rows + row0 + r] = s_q;
+        }
     }
 }
 
+// blockIdx.y = 1 (the dots pass alone): the second plane of partials into sq2
 __global__ __launch_bounds__(256) void rowsq_finish_kernel(const double* __restrict__ partials, int64_t n_rows, int chunks,
-                                                           double* __restrict__ sq, const int32_t* skip_if_set,
-                                                           const int32_t* run_if_set) {
+                                                           double* __restrict__ sq, double* __restrict__ sq2,
+                                                           const int32_t* skip_if_set, const int32_t* run_if_set) {
     if (gated_out(skip_if_set, run_if_set)) return;
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n_rows) return;
+    const double* plane = partials + static_cast<int64_t>(blockIdx.y) * chunks * n_rows;
     double s = 0.0;
-    for (int p = 0; p < chunks; ++p) s = s + partials[p * n_rows + i];
-    sq[i] = s;
+    for (int p = 0; p < chunks; ++p) s = s + plane[p * n_rows + i];
+    (blockIdx.y == 0 ? sq : sq2)[i] = s;
 }
 
-// CENTRED = false, the weighted mean: acc += w * (double)x, W += w, out = fl32(acc / W); v is not read.
-// CENTRED = true, centered clipping's update: acc += s * ((double)x - (double)v), out = fl32((double)v + acc / n_rows); v and out
+// kRowsMean, the weighted mean: acc += w * (double)x, W += w, out = fl32(acc / W); v and divisor are not read.
+// kRowsCentred, centered clipping's update: acc += s * ((double)x - (double)v), out = fl32((double)v + acc / n_rows); v and out
 // may be the same buffer (a thread reads its own columns of v before it writes them).
-template <int VEC, bool CENTRED>
+// kRowsScaled, FLTrust's sum: acc as the mean's, out = T > 0 ? fl32(acc / T) : 0 with T = *divisor (a device double).
+constexpr int kRowsMean = 0, kRowsCentred = 1, kRowsScaled = 2;
+template <int VEC, int MODE>
 __global__ __launch_bounds__(kThreads) void weighted_rows_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols,
                                                                  int64_t ld, const float* v, const double* __restrict__ w,
-                                                                 float* out, const int32_t* skip_if_set,
-                                                                 const int32_t* run_if_set) {
+                                                                 const double* __restrict__ divisor_dev, float* out,
+                                                                 const int32_t* skip_if_set, const int32_t* run_if_set) {
+    constexpr bool CENTRED = MODE == kRowsCentred;
     if (gated_out(skip_if_set, run_if_set)) return;
     const int64_t c0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * VEC;
     if (c0 >= n_cols) return;
@@ -129,18 +159,21 @@ __global__ __launch_bounds__(kThreads) void weighted_rows_kernel(const float* __
         G + c0, ld, n_rows, c0, n_cols, [](int64_t r) __attribute__((always_inline)) { return r; },
         [&](int64_t r) __attribute__((always_inline)) { return w[r]; },          // uniform: one scalar load for a run
         [&](int64_t, double wr, const float(&x)[VEC]) __attribute__((always_inline)) {
-            if constexpr (!CENTRED) W = W + wr;
+            if constexpr (MODE == kRowsMean) W = W + wr;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 if constexpr (CENTRED) acc[k] = acc[k] + wr * (static_cast<double>(x[k]) - vd[k]);
                 else acc[k] = acc[k] + wr * static_cast<double>(x[k]);
             }
         });
-    const double divisor = CENTRED ? static_cast<double>(n_rows) : W;
+    double divisor = W;
+    if constexpr (CENTRED) divisor = static_cast<double>(n_rows);
+    if constexpr (MODE == kRowsScaled) divisor = *divisor_dev;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
         if (c0 + k >= n_cols) continue;
         if constexpr (CENTRED) out[c0 + k] = static_cast<float>(vd[k] + acc[k] / divisor);
+        else if constexpr (MODE == kRowsScaled) out[c0 + k] = divisor > 0.0 ? static_cast<float>(acc[k] / divisor) : 0.0f;
         else out[c0 + k] = static_cast<float>(acc[k] / divisor);
     }
 }
@@ -258,29 +291,50 @@ int launch_row_sqdist(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     const bool vec4 = (ld % 4 == 0) && aligned16(G) && (z == nullptr || aligned16(z));
     const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
     KernelTimer t(ctx, BYZ_K_MISC, stream);
-    if (vec4) rowsq_partial_kernel<true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
-    else rowsq_partial_kernel<false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    if (vec4) rowsq_partial_kernel<true, false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    else rowsq_partial_kernel<false, false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
     BYZ_TRY(check_launch("rowsq_partial_kernel"));
-    rowsq_finish_kernel<<<static_cast<unsigned>(ceil_div(n_rows, 256)), 256, 0, stream>>>(partials, n_rows, chunks, sq,
+    rowsq_finish_kernel<<<static_cast<unsigned>(ceil_div(n_rows, 256)), 256, 0, stream>>>(partials, n_rows, chunks, sq, nullptr,
                                                                                         skip_if_set, run_if_set);
     return check_launch("rowsq_finish_kernel");
 }
 
-// wmean (v == nullptr) or centered clipping's update (v: the centre); one launch shape for both
+// dot[i] = x_i . r and sq[i] = |x_i|^2 in one read of G; partials: 2 * chunks * n_rows (geomed_chunks' chunks)
+int launch_row_dots(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* r, double* partials,
+                    double* dot, double* sq, hipStream_t stream) {
+    BYZ_REQUIRE(G && r && partials && dot && sq && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols,
+                "row dots: bad arguments");
+    int64_t chunk = 0;
+    const int chunks = geomed_chunks(ctx, n_rows, n_cols, &chunk);
+    const bool vec4 = (ld % 4 == 0) && aligned16(G) && aligned16(r);
+    const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+    if (vec4) rowsq_partial_kernel<true, true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
+    else rowsq_partial_kernel<false, true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
+    BYZ_TRY(check_launch("rowsq_partial_kernel (dots)"));
+    rowsq_finish_kernel<<<dim3(static_cast<unsigned>(ceil_div(n_rows, 256)), 2), 256, 0, stream>>>(partials, n_rows, chunks, dot, sq,
+                                                                                                 nullptr, nullptr);
+    return check_launch("rowsq_finish_kernel (dots)");
+}
+
+// wmean (v == nullptr), centered clipping's update (v: the centre) or FLTrust's sum (divisor: one device double); one launch
+// shape for the three
 static int launch_weighted_rows(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v,
-                                const double* w, float* out, const int32_t* skip_if_set, const int32_t* run_if_set,
-                                const char* who, hipStream_t stream) {
+                                const double* w, const double* divisor, float* out, const int32_t* skip_if_set,
+                                const int32_t* run_if_set, const char* who, hipStream_t stream) {
     BYZ_REQUIRE(G && w && out && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols, "%s: bad arguments", who);
     WalkShape shape;
     BYZ_TRY(walk_shape(ctx, G, ld, n_cols, who, &shape));
     const unsigned blocks = static_cast<unsigned>(shape.blocks);
     KernelTimer t(ctx, BYZ_K_MISC, stream);
-#define BYZ_WEIGHTED_ROWS(VEC, CENTRED) \
-    weighted_rows_kernel<VEC, CENTRED><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, v, w, out, skip_if_set, run_if_set)
+#define BYZ_WEIGHTED_ROWS(VEC, MODE) \
+    weighted_rows_kernel<VEC, MODE><<<blocks, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, v, w, divisor, out, skip_if_set, run_if_set)
     if (v != nullptr) {
-        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, true); else BYZ_WEIGHTED_ROWS(1, true);
+        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, kRowsCentred); else BYZ_WEIGHTED_ROWS(1, kRowsCentred);
+    } else if (divisor != nullptr) {
+        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, kRowsScaled); else BYZ_WEIGHTED_ROWS(1, kRowsScaled);
     } else {
-        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, false); else BYZ_WEIGHTED_ROWS(1, false);
+        if (shape.vec4) BYZ_WEIGHTED_ROWS(4, kRowsMean); else BYZ_WEIGHTED_ROWS(1, kRowsMean);
     }
 #undef BYZ_WEIGHTED_ROWS
     return check_launch("weighted_rows_kernel");
@@ -288,13 +342,20 @@ static int launch_weighted_rows(byz_ctx* ctx, const float* G, int64_t n_rows, in
 
 int launch_weighted_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w, float* out,
                          const int32_t* skip_if_set, const int32_t* run_if_set, hipStream_t stream) {
-    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, nullptr, w, out, skip_if_set, run_if_set, "weighted mean", stream);
+    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, nullptr, w, nullptr, out, skip_if_set, run_if_set, "weighted mean",
+                                stream);
 }
 
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream) {
     BYZ_REQUIRE(v, "clip update: bad arguments");
-    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, v, s, out, nullptr, nullptr, "clip update", stream);
+    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, v, s, nullptr, out, nullptr, nullptr, "clip update", stream);
+}
+
+int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w,
+                           const double* divisor, float* out, hipStream_t stream) {
+    BYZ_REQUIRE(divisor, "scaled rows sum: bad arguments");
+    return launch_weighted_rows(ctx, G, n_rows, n_cols, ld, nullptr, w, divisor, out, nullptr, nullptr, "scaled rows sum", stream);
 }
 
 int launch_geomed_finite_check(byz_ctx* ctx, const float* v, int64_t n, double* flag_f64, hipStream_t stream) {

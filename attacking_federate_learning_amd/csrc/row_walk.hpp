@@ -4,7 +4,7 @@
 // columns of a row in one coalesced request.  The rows go in runs of kRowRun: a run's loads are issued together, the additions
 // follow in row order.  That order (with -ffp-contract=off in the files that include this) is what makes the outputs numpy's
 // bits, so it is written once, here: column_sequential_kernel and column_chain_kernel (column_stats.hip) and
-// weighted_rows_kernel (geomed.hip: the weighted mean and centered clipping's update) are walk_rows with different `add`s.
+// weighted_rows_kernel (geomed.hip: the weighted mean, centered clipping's update and FLTrust's sum) are walk_rows with different `add`s.
 #pragma once
 
 #include "common.hpp"

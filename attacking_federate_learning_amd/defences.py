@@ -88,6 +88,17 @@ def centered_clip(users_grads, users_count, corrupted_count, tau=10.0, iters=3, 
     return get_engine().centered_clip(users_grads, tau=tau, iters=iters, start=start)
 
 
+def fltrust(users_grads, users_count, corrupted_count, root_grad, return_info=False):
+    """FLTrust (Cao, Fang, Liu and Gong, NDSS 2021; not in the reference): every client's vector is scored by the ReLU of its
+    cosine with `root_grad`, the gradient the server computed on its own small root dataset, rescaled to that gradient's
+    norm, and the scores weight the mean.  The one rule here that needs no honest majority: a vector pointing away from the
+    root gets no weight however many agree with it.  No trusted client, or a zero or non-finite root: the zero vector.  The
+    reference's leading signature; users_count and corrupted_count are accepted and unused.  return_info=True also returns
+    Engine.fltrust's info.  Not one of the `defend` keys: the reference's main.py offers only those four, and none of them
+    takes a root gradient."""
+    return get_engine().fltrust(users_grads, root_grad, return_info=return_info)
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

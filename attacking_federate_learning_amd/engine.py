@@ -837,6 +837,82 @@ class Engine:
         clipped, excluded = self.centered_clip_info()
         return out, {'clipped_rows': clipped, 'excluded_rows': excluded, 'scales': scales}
 
+    # ---- FLTrust (Cao, Fang, Liu and Gong 2021; not in the reference) ----
+    def row_dots(self, g, r):
+        """(dot, sq): dot[i] = sum_c (double)g[i, c] * (double)r[c] and sq[i] = sum_c (double)g[i, c]^2, both fp64 in a fixed
+        order, in ONE read of g (FLTrust's first pass; on one rank of the columns layout, its part over its columns).  fp64
+        out: torch tensors for a torch input, numpy for a host input, DeviceBuffers otherwise."""
+        m, stage, host = self._staged(g)
+        (rp,), n, _, keep, _ = self._vectors(r)
+        if n != m.cols:
+            raise ValueError('r has %d entries, the matrix %d columns' % (n, m.cols))
+        dot, dptr = self._out_like(m, m.rows, np.float64)
+        sq, sptr = self._out_like(m, m.rows, np.float64)
+        _check(self.lib.byz_row_dots_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(rp), _vp(dptr), _vp(sptr),
+                                         _vp(m.stream)))
+        if host or any(isinstance(k, DeviceBuffer) for k in keep):
+            self.synchronize(m.stream)   # staged copies must outlive the kernel
+        return (dot.numpy(), sq.numpy()) if host else (dot, sq)
+
+    def scaled_rows_sum(self, g, weights, divisor):
+        """out[c] = fl32(S_c / T) where T = divisor > 0, zeros otherwise: S_c the sequential fp64 sum, in row order, of
+        weights[i] * g[i, c] over the rows with weights[i] != 0 (a row of weight 0 is not read).  FLTrust's second pass; the
+        divisor is one fp64 value, on the host or the device.  The caller vouches that the weights are finite."""
+        m, stage, host = self._staged(g)
+        wp, wkeep = self._f64_vector(weights, m.rows)
+        tp, tkeep = self._f64_vector(divisor, 1)
+        out, optr = self._out_like(m, m.cols)
+        _check(self.lib.byz_scaled_rows_sum_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(wp), _vp(tp), _vp(optr),
+                                                _vp(m.stream)))
+        if host or isinstance(wkeep, DeviceBuffer) or isinstance(tkeep, DeviceBuffer):
+            self.synchronize(m.stream)   # staged copies must outlive the kernel
+        return out.numpy() if host else out
+
+    def fltrust_info(self):
+        """(trusted_rows, excluded_rows, root_ok, trust_sum) of the last FLTrust call on this engine (synchronises)."""
+        trusted, excluded, ok, total = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0.0)
+        _check(self.lib.byz_fltrust_info(self.ctx, ctypes.byref(trusted), ctypes.byref(excluded), ctypes.byref(ok),
+                                         ctypes.byref(total)))
+        return int(trusted.value), int(excluded.value), bool(ok.value), float(total.value)
+
+    def fltrust(self, g, root, return_info=False):
+        """FLTrust: every row's trust score is the ReLU of its cosine with `root`, the gradient the server computed on its own
+        root dataset; a trusted row is rescaled to the root's norm and the result is the trust-weighted mean of the rescaled
+        rows.  No row trusted, or a zero or non-finite root: the zero vector.  A row whose dot product or norm is not finite
+        is excluded.  return_info=True also returns {trusted_rows, excluded_rows, root_ok, trust_sum, trust, weights} (trust
+        and weights: fp64, one per row)."""
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            r_host = np.ascontiguousarray(root.detach().cpu().numpy() if _is_torch(root) else
+                                          (root.numpy() if isinstance(root, DeviceBuffer) else root), dtype=np.float32).ravel()
+            if r_host.size != d:
+                raise ValueError('root has %d entries, the matrix %d columns' % (r_host.size, d))
+            out = np.empty(d, dtype=np.float32)
+            trust = np.empty(n, dtype=np.float64) if return_info else None
+            weights = np.empty(n, dtype=np.float64) if return_info else None
+            _check(self.lib.byz_fltrust_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d,
+                                             r_host.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+                                             trust.ctypes.data_as(ctypes.c_void_p) if return_info else None,
+                                             weights.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+        else:
+            (rptr,), n, _, keep, _ = self._vectors(root)
+            if n != dm.cols:
+                raise ValueError('root has %d entries, the matrix %d columns' % (n, dm.cols))
+            out, ptr = self._out_like(dm, dm.cols)
+            trust, tptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
+            weights, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
+            _check(self.lib.byz_fltrust_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, _vp(rptr), _vp(ptr), _vp(tptr),
+                                            _vp(wptr), _vp(dm.stream)))
+            if any(isinstance(k, DeviceBuffer) for k in keep):
+                self.synchronize(dm.stream)   # an uploaded root must outlive the kernels
+        if not return_info:
+            return out
+        trusted, excluded, ok, total = self.fltrust_info()
+        return out, {'trusted_rows': trusted, 'excluded_rows': excluded, 'root_ok': ok, 'trust_sum': total, 'trust': trust,
+                     'weights': weights}
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

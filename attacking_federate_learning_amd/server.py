@@ -10,6 +10,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     attack(attacker_rows, num_std)  main.py:68 -> malicious.py:10-36 on the first rows, in place
     defend(defence_method)          server.py:86-90   defences.defend[...] on the device matrix + fused momentum step
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
+    defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -68,6 +69,20 @@ class DeviceServer:
         the next round's centre.  Then server.py:89-90's momentum step, as `defend` takes it."""
         current_grads = self.engine.centered_clip(self.users_grads.data, tau=tau, iters=iters, start=self.clip_centre)
         self.clip_centre.copy_(current_grads)     # a copy: the caller owns the aggregate it gets back
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with FLTrust, the one defence that takes the server's own gradient ------------
+    def defend_fltrust(self, root_grad):
+        """FLTrust of this round's gradients against `root_grad`, the gradient of the current weights on the server's own
+        root dataset; then server.py:89-90's momentum step, as `defend` takes it.  Computing the root gradient is the
+        caller's job; with clients.py it is one client's step on the root batch (root_x, root_y):
+
+            root_grad = torch.cat([t.reshape(-1) for t in
+                                   clients.per_client_gradients(net, server.current_weights, root_x[None], root_y[None])])
+        """
+        current_grads = self.engine.fltrust(self.users_grads.data, root_grad)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -89,6 +89,12 @@ class HipKernels:
     def clip_update(self, g_local, v, scales):
         return self.engine.clip_update(g_local, v, scales)    # this rank's columns of the moved centre
 
+    def row_dots(self, g_local, r):
+        return self.engine.row_dots(g_local, r)               # two (N,) float64: this rank's parts over its columns
+
+    def scaled_rows_sum(self, g_local, weights, divisor):
+        return self.engine.scaled_rows_sum(g_local, weights, divisor)     # this rank's columns of the sum over the divisor
+
     def dnc_scores(self, g_local, columns, power_iters=32):
         return self.engine.dnc_scores(g_local, columns, power_iters=power_iters)     # one rank holds the sampled columns
 
@@ -419,6 +425,37 @@ class ShardedAggregator:
         if not return_info:
             return out
         return out, {'clipped_rows': clipped, 'excluded_rows': excluded, 'scales': scales}
+
+    def fltrust(self, g_local, root_local, gather=False, return_info=False):
+        """FLTrust (Engine.fltrust's contract), columns layout: every rank holds all rows over its own columns of G and of
+        the root gradient.  A rank's dot products, squared norms and root norm cover its columns: ONE all-reduce of 2 N + 1
+        doubles makes them whole, the trust scores are then the same on every rank and the sum is local to the columns."""
+        import torch
+        n, d_local = g_local.shape
+        dev = g_local.device
+        root_local = torch.as_tensor(root_local, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        p, q = self.kernels.row_dots(g_local, root_local)
+        q0 = self.kernels.row_sqdist(root_local.reshape(1, -1), torch.zeros_like(root_local))
+        pq = torch.cat([p, q, q0])
+        self._all_reduce('allreduce_fltrust_dots', pq)
+        p, q, q0 = pq[:n], pq[n:2 * n], pq[2 * n]
+        # include/byzagg.h's order of operations, in fp64
+        root_ok = bool((torch.isfinite(q0) & (q0 > 0)).item())
+        finite = torch.isfinite(p) & torch.isfinite(q)
+        usable = finite & (q > 0)
+        norm = torch.sqrt(torch.where(usable, q, torch.ones_like(q)))
+        root_norm = torch.sqrt(q0)
+        c = p / (norm * root_norm)
+        zero = torch.zeros_like(c)
+        trust = torch.where(usable & (c > 0), c, zero) if root_ok else zero
+        weights = torch.where(trust != 0, trust * (root_norm / norm), zero)
+        total = trust.sum()
+        out = self.kernels.scaled_rows_sum(g_local, weights, total.reshape(1))
+        out = self._maybe_gather(out, gather)
+        if not return_info:
+            return out
+        return out, {'trusted_rows': int((trust > 0).sum().item()), 'excluded_rows': int((~finite).sum().item()),
+                     'root_ok': root_ok, 'trust_sum': float(total.item()), 'trust': trust, 'weights': weights}
 
     def dnc(self, g_local, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
             columns=None, gather=False, return_index=False, total_columns=None):

@@ -311,6 +311,47 @@ int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, in
                            const byz_cclip_params* params, const float* start_host, float* out_host,
                            double* scales_host);
 
+/* ---- FLTrust (Cao, Fang, Liu & Gong, NDSS 2021; not in the reference) ---- */
+/* Trust bootstrapping: every row is compared with a gradient r the SERVER computed on its own small root      */
+/* dataset.  A row's trust score is the ReLU of its cosine with r, a trusted row is rescaled to r's norm, and   */
+/* the aggregate is the trust-weighted mean of the rescaled rows.  The one rule here with no bound on the number */
+/* of malicious rows: a row pointing away from r gets no weight however many rows agree with it.  Computing r   */
+/* is the caller's job.  G: n x n_cols fp32 (n = n_rows up to byz_limits' selection limit, BYZ_E_UNSUPPORTED     */
+/* beyond), leading dimension ld; root_dev: n_cols fp32.  Everything below is fp64 on the device:               */
+/*   p_i = sum_c (double)x_ic * (double)r_c     q_i = sum_c (double)x_ic^2     q0 = sum_c (double)r_c^2          */
+/*   root_ok  = isfinite(q0) && q0 > 0                                                                          */
+/*   usable_i = isfinite(p_i) && isfinite(q_i) && q_i > 0                                                       */
+/*   c_i  = p_i / (sqrt(q_i) * sqrt(q0))            (this order of operations, no fused multiply-add)           */
+/*   ts_i = root_ok && usable_i && c_i > 0 ? c_i : 0    (the ReLU of the cosine; not clamped at 1)              */
+/*   w_i  = ts_i != 0 ? ts_i * (sqrt(q0) / sqrt(q_i)) : 0     (trust x rescaling to the root's norm)            */
+/*   T    = sum_i ts_i                              (a fixed order, the same on every call)                     */
+/*   S_c  = sum over the rows with w_i != 0 of w_i * (double)x_ic, added in row order, no fused multiply-add    */
+/*   out[c] = T > 0 ? fl32(S_c / T) : 0                                                                         */
+/* p, q and q0 are summed in rowsq's fixed order (lane sums, a fixed butterfly, the column chunks in chunk       */
+/* order): two calls give the same bits, and so do a strided view and its dense copy.  A row with w_i = 0 is     */
+/* neither loaded nor multiplied in the second pass (0 * inf never reaches a column).  The paper leaves the case */
+/* of no trusted row undefined; here it is a zero step: when no row is trusted, or the root is zero or not       */
+/* finite, out is 0 in every column and never NaN.  out_dev may be root_dev; it must not overlap G               */
+/* (BYZ_E_INVALID).  trust_dev and weights_dev (optional, n fp64 each): ts and w.  byz_fltrust_info reads the    */
+/* last call's trusted rows (ts_i > 0), excluded rows (p_i or q_i not finite), root_ok and T, and synchronises;  */
+/* nothing else does: every launch is enqueued up front.  Cost: two passes over G.                               */
+/* The first pass as a piece: dot_dev[i] = p_i and sq_dev[i] = q_i (n_rows fp64 each) in ONE read of G; on one    */
+/* rank of the columns layout, its partial sums over its columns.                                                */
+int byz_row_dots_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                     const float* r_dev, double* dot_dev, double* sq_dev, void* stream);
+/* The second pass as a piece: out[c] = T > 0 ? fl32(S_c / T) : 0 with the caller's weights (n_rows fp64, finite; */
+/* a row of weight 0 is neither loaded nor multiplied) and T = *divisor_dev (one device fp64).                   */
+int byz_scaled_rows_sum_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                            const double* w_dev, const double* divisor_dev, float* out_dev, void* stream);
+int byz_fltrust_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                    const float* root_dev, float* out_dev, double* trust_dev, double* weights_dev, void* stream);
+int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows, int32_t* root_ok,
+                     double* trust_sum);
+/* FLTrust of a host matrix and a host root (out_host: n_cols floats; trust_host and weights_host optional:      */
+/* n_rows fp64).  Synchronous.                                                                                  */
+int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* root_host,
+                     float* out_host, double* trust_host, double* weights_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -423,6 +464,14 @@ int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_
                                   int64_t n_cols_local, int64_t ld, const byz_cclip_params* params,
                                   byz_allreduce_f64_fn allreduce, void* user, const float* start_local_dev,
                                   float* out_local_dev, double* scales_dev, void* stream);
+
+/* FLTrust over the slices: every rank holds its columns of G and of the root; out_local_dev = this rank's       */
+/* columns of the result.  A rank's p, q and q0 cover its own columns: ONE all-reduce of 2 * n_rows + 1 doubles     */
+/* (p, q, q0, in that order) makes them whole -- one call, on every rank, whatever the data.  The trust scores      */
+/* (trust_dev, weights_dev optional) are then the same on every rank and the sum is local to the columns.           */
+int byz_fltrust_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                            const float* root_local_dev, byz_allreduce_f64_fn allreduce, void* user,
+                            float* out_local_dev, double* trust_dev, double* weights_dev, void* stream);
 
 /* DnC over the slices.  The caller maps every iteration's global sample onto the ranks: local_counts (HOST,  */
 /* n_iters entries) is the number of iteration t's sampled columns this rank owns -- 0 is allowed --, and      */
