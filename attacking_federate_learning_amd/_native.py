@@ -111,6 +111,12 @@ _PROTOTYPES = {
     'byz_fltrust_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i32), _P(ctypes.c_double)],
     'byz_fltrust_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_fltrust_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_nnm_neighbours_dev': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_nnm_mix_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
+    'byz_nnm_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
+    'byz_nnm_info': [c_vp, _P(c_i64), _P(c_i64)],
+    'byz_nnm_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_nnm_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

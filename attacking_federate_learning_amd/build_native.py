@@ -19,7 +19,7 @@ ARCH = 'gfx950'
 
 SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_window.hip',
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip',
-           'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip']
+           'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip', 'nnm.hip']
 # median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
 # dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
 # LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a

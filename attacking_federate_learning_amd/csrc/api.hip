@@ -992,6 +992,105 @@ int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows
     return BYZ_OK;
 }
 
+// ---- nearest-neighbour mixing (Allouah et al., AISTATS 2023; beyond the reference) -----------------------------------------
+namespace {
+
+// k = users_count - corrupted_count rows a list at most; the n x n keys and mask end at kNnmMaxRows rows (checked on the
+// arguments alone, before any pointer is looked at)
+int check_nnm(const char* who, int64_t n_rows, int64_t k) {
+    if (n_rows > kNnmMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kNnmMaxRows, (long long)n_rows);
+        return BYZ_E_UNSUPPORTED;
+    }
+    if (n_rows < 1 || k < 1 || k > n_rows) {
+        set_error("%s: k = users_count - corrupted_count = %lld outside 1..%lld (the row count)", who, (long long)k, (long long)n_rows);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// Y must not overlap G: a workgroup stores its tile of Y while others still read those rows of G
+int check_nnm_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* Y, int64_t ldy, const char* who) {
+    if (!Y || ldy < n_cols) {
+        set_error("%s: bad output (ptr %p, ldy %lld < %lld columns)", who, (const void*)Y, (long long)ldy, (long long)n_cols);
+        return BYZ_E_INVALID;
+    }
+    const float* g_end = G + (n_rows - 1) * ld + n_cols;
+    const float* y_end = Y + (n_rows - 1) * ldy + n_cols;
+    if (Y < g_end && y_end > G) {
+        set_error("%s: the output overlaps the matrix", who);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Distances (over the ranks' slices when sharded: the one
+// exchange), the lists -- the same on every rank --, the mix on the local columns.
+int nnm(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, int64_t k, byz_allreduce_f64_fn allreduce, void* user,
+        float* Y, int64_t ldy, int32_t* nbr_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ensure_distance_workspaces(ctx, n));
+    const size_t list_bytes = static_cast<size_t>(n) * k * sizeof(int32_t);
+    BYZ_TRY(ctx->nnm_lists.ensure(list_bytes + static_cast<size_t>(n) * sizeof(int32_t)));
+    int32_t* nbr = ctx->nnm_lists.as<int32_t>();
+    int32_t* counts = nbr + n * k;
+    ctx->nnm_stream = s;
+    BYZ_TRY(distances(ctx, G, n, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+    BYZ_TRY(launch_nnm_neighbours(ctx, ctx->dist.as<float>(), n, k, nbr, counts, s));
+    BYZ_TRY(launch_nnm_mix(ctx, G, n, n_cols, ld, nbr, counts, k, Y, ldy, s));
+    if (nbr_out != nullptr) BYZ_HIP(hipMemcpyAsync(nbr_out, nbr, list_bytes, hipMemcpyDeviceToDevice, s));
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_nnm_neighbours_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t k, int32_t* nbr, int32_t* counts, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_nnm("nnm_neighbours", n_rows, k));
+    BYZ_REQUIRE(dist && nbr, "nnm_neighbours: null distances or output");
+    ctx->nnm_stream = as_stream(stream);
+    return launch_nnm_neighbours(ctx, dist, n_rows, k, nbr, counts, as_stream(stream));
+}
+
+int byz_nnm_mix_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* nbr,
+                    const int32_t* counts, int64_t k, float* Y, int64_t ldy, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_nnm("nnm_mix", n_rows, k));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "nnm_mix"));
+    BYZ_REQUIRE(nbr, "nnm_mix: null neighbour lists");
+    BYZ_TRY(check_nnm_output(G, n_rows, n_cols, ld, Y, ldy, "nnm_mix"));
+    return launch_nnm_mix(ctx, G, n_rows, n_cols, ld, nbr, counts, k, Y, ldy, as_stream(stream));
+}
+
+int byz_nnm_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+                int64_t corrupted_count, float* Y, int64_t ldy, int32_t* nbr, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_nnm("nnm", n_rows, users_count - corrupted_count));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "nnm"));
+    BYZ_TRY(check_nnm_output(G, n_rows, n_cols, ld, Y, ldy, "nnm"));
+    return nnm(ctx, G, n_rows, n_cols, ld, users_count - corrupted_count, nullptr, nullptr, Y, ldy, nbr, stream);
+}
+
+int byz_nnm_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+                        int64_t corrupted_count, byz_allreduce_f64_fn allreduce, void* user, float* Y, int64_t ldy, int32_t* nbr,
+                        void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_nnm("nnm_sharded", n_rows, users_count - corrupted_count));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "nnm_sharded"));
+    BYZ_REQUIRE(allreduce, "nnm_sharded: null all-reduce");
+    BYZ_TRY(check_nnm_output(G, n_rows, n_cols, ld, Y, ldy, "nnm_sharded"));
+    return nnm(ctx, G, n_rows, n_cols, ld, users_count - corrupted_count, allreduce, user, Y, ldy, nbr, stream);
+}
+
+int byz_nnm_info(byz_ctx* ctx, int64_t* solo_rows, int64_t* short_rows) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->nnm_stream));   // synchronises the last call's stream
+    if (solo_rows) *solo_rows = words[kNnmSolo];
+    if (short_rows) *short_rows = words[kNnmShort];
+    return BYZ_OK;
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -1417,6 +1516,26 @@ int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t 
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (trust_host) BYZ_HIP(hipMemcpyAsync(trust_host, trust, row_bytes, hipMemcpyDeviceToHost, s));
     if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
+    return check_small(ctx, s);
+}
+
+int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count, int64_t corrupted_count,
+                 float* Y_host, int32_t* nbr_host) {
+    BYZ_TRY(enter(ctx));
+    const int64_t k = users_count - corrupted_count;
+    BYZ_TRY(check_nnm("nnm", n_rows, k));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "nnm"));
+    BYZ_REQUIRE(Y_host, "nnm: null output");
+    hipStream_t s = nullptr;
+    const size_t y_bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+    const size_t list_bytes = static_cast<size_t>(n_rows) * k * sizeof(int32_t);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, y_bytes + list_bytes, s));
+    float* Y = ctx->stage_out.as<float>();
+    int32_t* nbr = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + y_bytes);
+    BYZ_TRY(byz_nnm_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, users_count, corrupted_count, Y, n_cols,
+                        nbr_host ? nbr : nullptr, s));
+    BYZ_HIP(hipMemcpyAsync(Y_host, Y, y_bytes, hipMemcpyDeviceToHost, s));
+    if (nbr_host) BYZ_HIP(hipMemcpyAsync(nbr_host, nbr, list_bytes, hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
 }
 

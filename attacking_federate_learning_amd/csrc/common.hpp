@@ -146,6 +146,10 @@ struct byz_ctx {
     hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
     hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
     hipStream_t fltrust_stream = nullptr;  // stream of the last FLTrust call (byz_fltrust_info syncs it)
+    byz::Buffer nnm_keys;        // nearest-neighbour mixing: n segments of next_pow2(n) sort keys
+    byz::Buffer nnm_mask;        // its 0/1 fp32 mask, transposed ([j][i], padded to the mix kernel's tiles), then the n list lengths
+    byz::Buffer nnm_lists;       // its neighbour lists (n x k int32) and their lengths (n) when the caller passes no buffer
+    hipStream_t nnm_stream = nullptr;      // stream of the last neighbour search (byz_nnm_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -191,7 +195,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 36;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 38;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -210,6 +214,9 @@ constexpr int kCclipClipped = 28, kCclipExcluded = 29;
 // FLTrust: the rows with a positive trust score, the rows with a non-finite dot product or norm, T = the sum of the trust scores
 // (fp64: two words, 8-byte aligned), the root's squared norm was finite and positive
 constexpr int kFltrustTrusted = 30, kFltrustExcluded = 31, kFltrustTrustSum = 32, kFltrustRootOk = 34;
+// nearest-neighbour mixing: the rows whose list is themselves alone although k > 1, the rows whose list is shorter than k (adjacent:
+// one memset clears both)
+constexpr int kNnmSolo = 36, kNnmShort = 37;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -378,6 +385,12 @@ int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
                            const double* divisor, float* out, hipStream_t stream);
 // fltrust.hip: FLTrust's trust scores ts and weights w from pq = p (n), q (n), q0 (1); T and the counts into the context's words
 int launch_fltrust_trust(byz_ctx* ctx, const double* pq, int64_t n, double* ts, double* w, hipStream_t stream);
+// nnm.hip: nearest-neighbour mixing.  Lists: row i's k - 1 nearest rows at a finite distance and i itself, ascending, -1 behind
+// them (nbr: n x k int32; counts optional: n); the mix: Y[i] = mean of the listed rows of G, one MFMA accumulator chain in row order
+constexpr int64_t kNnmMaxRows = 16384;
+int launch_nnm_neighbours(byz_ctx* ctx, const float* dist, int64_t n, int64_t k, int32_t* nbr, int32_t* counts, hipStream_t stream);
+int launch_nnm_mix(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const int32_t* nbr, const int32_t* counts,
+                   int64_t k, float* Y, int64_t ldy, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

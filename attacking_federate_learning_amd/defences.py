@@ -14,7 +14,7 @@ Differences a caller can observe, all documented in DESIGN.md:
   * `_krum_create_distances` returns a `Distances` handle (GPU-resident N x N matrix) instead of a dict
     of dicts; `krum(..., distances=handle)` accepts it, `handle.to_dict()` rebuilds the reference's form.
 """
-from .engine import Distances, dnc_columns, get_engine  # noqa: F401
+from .engine import DeviceBuffer, Distances, dnc_columns, get_engine  # noqa: F401
 
 
 class DefenseTypes:
@@ -97,6 +97,25 @@ def fltrust(users_grads, users_count, corrupted_count, root_grad, return_info=Fa
     Engine.fltrust's info.  Not one of the `defend` keys: the reference's main.py offers only those four, and none of them
     takes a root gradient."""
     return get_engine().fltrust(users_grads, root_grad, return_info=return_info)
+
+
+def nnm(users_grads, users_count, corrupted_count, then=None, distances=None, **then_kwargs):
+    """Nearest-neighbour mixing (Allouah et al., "Fixing by Mixing", AISTATS 2023; not in the reference): every client's vector
+    is replaced by the mean of its users_count - corrupted_count nearest neighbours, itself included -- np.mean(users_grads[
+    list_i], axis=0) bit for bit, the list in ascending row order.  A pre-aggregation: with then=None the mixed n x D matrix
+    comes back; with a callable the result is then(mixed, users_count, corrupted_count, **then_kwargs) -- `krum`,
+    `trimmed_mean`, `coordinate_median`, `geometric_median`, ... -- and the mixed matrix stays on the device in between.
+    `distances` (optional): a `Distances` handle of users_grads.  Not one of the `defend` keys: the reference's main.py offers
+    only those four, and this is no rule by itself."""
+    engine = get_engine()
+    host = engine._device_matrix(users_grads) is None
+    if host and then is not None:
+        users_grads = engine.to_device(engine._host_matrix(users_grads))
+    mixed = engine.nnm(users_grads, users_count, corrupted_count, distances=distances)
+    if then is None:
+        return mixed
+    out = then(mixed, users_count, corrupted_count, **then_kwargs)
+    return out.numpy() if host and isinstance(out, DeviceBuffer) else out
 
 
 def coordinate_median(users_grads, users_count, corrupted_count):

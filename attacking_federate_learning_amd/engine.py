@@ -913,6 +913,115 @@ class Engine:
         return out, {'trusted_rows': trusted, 'excluded_rows': excluded, 'root_ok': ok, 'trust_sum': total, 'trust': trust,
                      'weights': weights}
 
+    # ---- nearest-neighbour mixing (Allouah et al., AISTATS 2023; not in the reference) ----
+    def _nnm_lists(self, lists, rows, cols=None):
+        """Neighbour lists or their lengths -> (device pointer of int32 data, shape, keepalive, ours): a DeviceBuffer or a
+        torch CUDA tensor is used where it is (torch: converted to contiguous int32), anything else is uploaded (ours)."""
+        if isinstance(lists, DeviceBuffer):
+            if lists.dtype != np.int32:
+                raise ValueError('a DeviceBuffer of neighbour lists must hold int32')
+            ptr, shape, keep, ours = lists.ptr, lists.shape, lists, False
+        elif _is_torch(lists) and lists.is_cuda:
+            import torch
+            if lists.device.index != self.device:
+                raise ValueError('the neighbour lists live on %s, this engine drives cuda:%d' % (lists.device, self.device))
+            keep = lists.to(torch.int32).contiguous()
+            ptr, shape, ours = keep.data_ptr(), tuple(keep.shape), False
+        else:
+            host = np.asarray(lists.cpu().numpy() if _is_torch(lists) else lists)
+            if host.dtype.kind not in 'iu':
+                raise ValueError('neighbour lists must hold integers, got %s' % host.dtype)
+            keep = self.to_device(host.astype(np.int32))
+            ptr, shape, ours = keep.ptr, keep.shape, True
+        if len(shape) != (1 if cols is None else 2) or shape[0] != rows:
+            raise ValueError('expected %d %s, got shape %r' % (rows, 'lengths' if cols is None else 'lists', tuple(shape)))
+        return ptr, shape, keep, ours
+
+    def nnm_neighbours(self, distances, k):
+        """(neighbours, counts) for a distance matrix (a `Distances` handle or a dense matrix, diagonal +inf): row i of
+        `neighbours` (n x k int32) is i and its k - 1 nearest rows at a finite distance, ASCENDING, then -1; counts[i] their
+        number.  Order: (distance, row index), -0.0 as +0.0, every NaN behind +inf.  DeviceBuffers for a `Distances` handle
+        (nothing leaves the device), numpy otherwise."""
+        on_device = isinstance(distances, Distances)
+        if isinstance(distances, dict):
+            raise ValueError('nnm_neighbours() takes a Distances handle or a dense matrix')
+        d, _ = self._as_distances(distances)
+        k = int(k)
+        nbr = DeviceBuffer(self, (d.n, max(k, 1)), np.int32)
+        counts = DeviceBuffer(self, (d.n,), np.int32)
+        _check(self.lib.byz_nnm_neighbours_dev(self.ctx, _vp(d.ptr), d.n, k, _vp(nbr.ptr), _vp(counts.ptr), None))
+        if on_device:
+            return nbr, counts
+        return nbr.numpy(), counts.numpy()      # (a download synchronises: the temporaries outlive the kernels)
+
+    def nnm_mix(self, g, neighbours, counts=None, out=None):
+        """Y[i] = np.mean(g[list_i], axis=0) bit for bit (the listed rows added in ascending row order, sequential fp32 from
+        +0.0, divided by the list's length); a list of one row copies that row verbatim.  `neighbours`: n x k integers, every
+        list ascending with -1 behind it (nnm_neighbours' form; `counts` optional).  `g` may be a column panel of a larger
+        matrix (a strided view), `out` (optional, device-resident, n x columns, may be strided too) receives the result: that
+        is how a matrix too large to hold twice is mixed.  The result stays on the device when `g` was there."""
+        m, stage, host = self._staged(g)
+        nptr, nshape, nkeep, nours = self._nnm_lists(neighbours, m.rows, cols=True)
+        cptr, ckeep, cours = None, None, False
+        if counts is not None:
+            cptr, _, ckeep, cours = self._nnm_lists(counts, m.rows)
+        if out is None:
+            y, yptr = self._out_like(m, (m.rows, m.cols))
+            ldy = m.cols
+        else:
+            om = self._device_matrix(out)
+            if om is None or (om.rows, om.cols) != (m.rows, m.cols):
+                raise ValueError('out must be a device-resident %d x %d float32 matrix' % (m.rows, m.cols))
+            y, yptr, ldy = out, om.ptr, om.ld
+        _check(self.lib.byz_nnm_mix_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(nptr), _vp(cptr), int(nshape[1]),
+                                        _vp(yptr), ldy, _vp(m.stream)))
+        if host or nours or cours:
+            self.synchronize(m.stream)   # staged copies must outlive the kernels
+        return y.numpy() if host and out is None else y
+
+    def nnm_info(self):
+        """(solo_rows, short_rows) of the last neighbour search on this engine: the rows whose list is themselves alone
+        although k > 1, and the rows whose list is shorter than k (synchronises)."""
+        solo, short = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.byz_nnm_info(self.ctx, ctypes.byref(solo), ctypes.byref(short)))
+        return int(solo.value), int(short.value)
+
+    def nnm(self, g, users_count, corrupted_count, distances=None, return_neighbours=False):
+        """Nearest-neighbour mixing: every row replaced by the mean of its users_count - corrupted_count nearest rows, itself
+        included (nnm_neighbours, then nnm_mix); the n x D result is what a rule such as krum, trimmed_mean or
+        coordinate_median then aggregates.  A row with a non-finite value mixes with nobody and comes back verbatim.  The
+        result (and the lists) stay on the device when `g` was there; numpy for a host matrix."""
+        k = int(users_count) - int(corrupted_count)
+        dm = self._device_matrix(g)
+        if distances is not None:
+            d, _ = self._as_distances(distances)
+            nbr, counts = self.nnm_neighbours(d, k)
+            y = self.nnm_mix(g, nbr, counts)
+            self.synchronize(dm.stream if dm is not None else None)   # the lists are ours: they must outlive the mix
+            if not return_neighbours:
+                return y
+            if dm is None:
+                nbr = nbr.numpy()
+            elif dm.torch_like is not None:
+                import torch
+                nbr = torch.from_numpy(nbr.numpy()).to(dm.torch_like.device)
+            return y, nbr
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            y = np.empty((n, d), dtype=np.float32)
+            nbr = np.full((n, max(k, 1)), -1, dtype=np.int32) if return_neighbours else None
+            _check(self.lib.byz_nnm_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, int(users_count),
+                                         int(corrupted_count), y.ctypes.data_as(ctypes.c_void_p),
+                                         nbr.ctypes.data_as(ctypes.c_void_p) if return_neighbours else None))
+            return (y, nbr) if return_neighbours else y
+        y, yptr = self._out_like(dm, (dm.rows, dm.cols))
+        nbr, nptr = self._out_like(dm, (dm.rows, max(k, 1)), np.int32) if return_neighbours else (None, None)
+        _check(self.lib.byz_nnm_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, int(users_count), int(corrupted_count),
+                                    _vp(yptr), dm.cols, _vp(nptr), _vp(dm.stream)))
+        self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
+        return (y, nbr) if return_neighbours else y
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

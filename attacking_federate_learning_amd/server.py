@@ -11,6 +11,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend(defence_method)          server.py:86-90   defences.defend[...] on the device matrix + fused momentum step
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
+    defend_nnm(then)                  the same step with nearest-neighbour mixing in front of the rule `then`
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -83,6 +84,20 @@ class DeviceServer:
                                    clients.per_client_gradients(net, server.current_weights, root_x[None], root_y[None])])
         """
         current_grads = self.engine.fltrust(self.users_grads.data, root_grad)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with nearest-neighbour mixing in front of a rule -------------------------------
+    def defend_nnm(self, then, **then_kwargs):
+        """Nearest-neighbour mixing of this round's gradients (every row the mean of its n - f nearest rows), the rule
+        `then(mixed, n_users, n_malicious, **then_kwargs)` on the mixed matrix -- defences.krum, trimmed_mean,
+        coordinate_median, geometric_median, ... --, then server.py:89-90's momentum step, as `defend` takes it.  The mixed
+        matrix never leaves the device."""
+        if not callable(then):
+            raise TypeError('defend_nnm needs the rule to apply to the mixed matrix, e.g. defences.trimmed_mean')
+        current_grads = defences.nnm(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), then=then,
+                                     **then_kwargs)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -79,6 +79,12 @@ class HipKernels:
     def mean_rows(self, g_local, row_index):
         return self.engine.mean_rows(g_local, row_index)
 
+    def nnm_neighbours(self, dist, k):
+        return self.engine.nnm_neighbours(dist, k)            # (lists n x k, lengths n): int32, on the device
+
+    def nnm_mix(self, g_local, neighbours, counts=None):
+        return self.engine.nnm_mix(g_local, neighbours, counts)     # this rank's columns of the mixed matrix
+
     def row_sqdist(self, g_local, z):
         return self.engine.row_sqdist(g_local, z)             # (N,) float64: this rank's part over its columns
 
@@ -345,6 +351,15 @@ class ShardedAggregator:
         out = self.kernels.mean_rows(g_local, np.sort(selection))
         out = self._maybe_gather(out, gather, total_columns)
         return (out, selection) if return_selection else out
+
+    def nnm(self, g_local, users_count, corrupted_count, return_neighbours=False):
+        """Nearest-neighbour mixing, columns layout: the distances' one all-reduce and nothing more; the neighbour lists are
+        then the same on every rank and every rank mixes its own columns.  Returns the local slice (n x local columns) of the
+        mixed matrix: the input of a rule of this class on the same layout.  A clients layout is not offered."""
+        dist_m = self.global_distances(g_local)
+        neighbours, counts = self.kernels.nnm_neighbours(dist_m, int(users_count) - int(corrupted_count))
+        mixed = self.kernels.nnm_mix(g_local, neighbours, counts)
+        return (mixed, neighbours) if return_neighbours else mixed
 
     def geometric_median(self, g_local, nu=1e-6, max_iter=10, ftol=1e-6, gather=False, return_info=False,
                          total_columns=None):

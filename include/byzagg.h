@@ -352,6 +352,46 @@ int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows
 int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* root_host,
                      float* out_host, double* trust_host, double* weights_host);
 
+/* ---- nearest-neighbour mixing, NNM (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot & Stephan, "Fixing by Mixing", AISTATS  */
+/* 2023; not in the reference) ----                                                                                        */
+/* A PRE-aggregation: every row of G is replaced by the mean of its k = users_count - corrupted_count nearest rows, itself  */
+/* included, and the mixed n x n_cols matrix Y is what Krum, a trimmed mean, the median or the geometric median then see;  */
+/* the paper shows that this makes those rules order-optimal under heterogeneous data.  G: n x n_cols fp32 (n = n_rows),    */
+/* leading dimension ld.  1 <= k <= n (BYZ_E_INVALID otherwise); n up to 16,384 (BYZ_E_UNSUPPORTED beyond, decided on the   */
+/* argument alone: the sort keys and the mask are n x n).                                                                  */
+/* Neighbour lists, from a distance matrix as byz_pairwise_distances_dev writes it (n x n fp32, diagonal +inf):             */
+/*   row i's candidates are the other rows j, ordered by the key (distance bits in order-preserving form, then j): -0.0     */
+/*   counts as +0.0 and every NaN sorts behind +inf; the first k - 1 candidates are taken, those whose distance is not      */
+/*   finite are dropped, i itself is added, and the list is stored in ASCENDING row order with its length k_i <= k.  The     */
+/*   key order is total, so ties (an attack's identical rows) are decided the same way on every run.  A row with a          */
+/*   non-finite value has only non-finite distances: it is in nobody's list and its own list is {i}.                        */
+/* Mix: Y[i] = np.mean(G[list_i], axis=0) bit for bit: the listed rows added in ascending row order, sequential fp32 from   */
+/*   +0.0, divided (a true division) by (float)k_i -- byz_mean_rows_dev's and byz_no_defense_dev's arithmetic.  list_i =    */
+/*   {i}: row i of Y is row i of G copied verbatim, NaN and inf included.  A value of a row outside list_i never reaches    */
+/*   Y[i] (0 * inf does not either).  So k = n makes every row of Y byz_no_defense_dev's bits, and k = 1 gives Y = G.       */
+/*   The sum is ONE accumulator chain of the fp32-input matrix instruction over j = 0 .. n - 1 (a multiplier of exactly 1    */
+/*   or 0: fma(1, x, c) = fl32(c + x), fma(0, x, c) = c); the rows of G are read through isfinite(x) ? x : 0, which changes  */
+/*   no value that is used.  Cost: 2 n^2 n_cols flops on the matrix pipe, whatever k.                                       */
+/* Y must not overlap G (BYZ_E_INVALID), ldy >= n_cols.  Everything is asynchronous on `stream`; only byz_nnm_info           */
+/* synchronises.                                                                                                           */
+/* The lists: nbr_dev n_rows x k int32, row i = list_i ascending, the unused tail -1; counts_dev (optional) n_rows int32.   */
+int byz_nnm_neighbours_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int64_t k, int32_t* nbr_dev,
+                           int32_t* counts_dev, void* stream);
+/* The mix for ANY lists of that form (each entry in [0, n_rows), ascending, no row twice: the caller vouches; an entry out  */
+/* of range is ignored).  counts_dev optional: without it a list ends at its first negative entry.  The caller may walk the  */
+/* columns in panels -- G_dev + c0, Y_dev + c0, the same ld and ldy -- which is how a matrix too large to hold twice is      */
+/* mixed; the panels' results are the one call's bits.                                                                      */
+int byz_nnm_mix_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* nbr_dev,
+                    const int32_t* counts_dev, int64_t k, float* Y_dev, int64_t ldy, void* stream);
+/* Distances, lists, mix.  nbr_dev (optional): n_rows x (users_count - corrupted_count) int32.                              */
+int byz_nnm_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t users_count,
+                int64_t corrupted_count, float* Y_dev, int64_t ldy, int32_t* nbr_dev, void* stream);
+/* The last neighbour search: solo_rows = rows with k_i == 1 < k, short_rows = rows with k_i < k; synchronises its stream.  */
+int byz_nnm_info(byz_ctx* ctx, int64_t* solo_rows, int64_t* short_rows);
+/* NNM of a host matrix (Y_host: n_rows x n_cols floats; nbr_host optional, as nbr_dev).  Synchronous.                      */
+int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count,
+                 int64_t corrupted_count, float* Y_host, int32_t* nbr_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -472,6 +512,13 @@ int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_
 int byz_fltrust_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
                             const float* root_local_dev, byz_allreduce_f64_fn allreduce, void* user,
                             float* out_local_dev, double* trust_dev, double* weights_dev, void* stream);
+
+/* NNM over the slices (the columns layout; a clients layout is not offered): byz_pairwise_distances_sharded_dev's exchange  */
+/* and nothing more.  The lists (nbr_dev optional) are then the same on every rank and the mix is local to the columns:        */
+/* Y_local_dev (n_rows x n_cols_local, leading dimension ldy) = this rank's columns of the mixed matrix.                       */
+int byz_nnm_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                        int64_t users_count, int64_t corrupted_count, byz_allreduce_f64_fn allreduce, void* user,
+                        float* Y_local_dev, int64_t ldy, int32_t* nbr_dev, void* stream);
 
 /* DnC over the slices.  The caller maps every iteration's global sample onto the ranks: local_counts (HOST,  */
 /* n_iters entries) is the number of iteration t's sampled columns this rank owns -- 0 is allowed --, and      */
