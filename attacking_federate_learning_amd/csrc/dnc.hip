@@ -16,9 +16,10 @@
 //   step     (y all-reduced) u = y / |y|, or after the last product lambda = u.y and the scores y_i^2 / lambda
 //   rank     keep_i = #{k : (s_k, k) < (s_i, i)} < n - remove_count, by counting: exact on the fp64 scores (every NaN behind
 //            +inf, -0.0 as +0.0), n^2 comparisons through LDS tiles; ANDed into the running intersection
-//   compact  the kept rows in ascending order and their count (multi_krum.hip's flag compaction)
+//   compact  the kept rows in ascending order and their count (block_exclusive_scan, order_keys.hpp)
 // Every sum has a fixed order: two calls give the same bits.  Nothing synchronises with the host; the kept count stays in the
 // context's small area (common.hpp) until byz_dnc_info reads it.
+#include "order_keys.hpp"
 #include "row_walk.hpp"
 
 #include <algorithm>
@@ -203,24 +204,16 @@ __global__ __launch_bounds__(kOneThreads) void dnc_step_kernel(const double* __r
     }
 }
 
-// order-preserving bits of a score: every NaN behind +inf, -0.0 as +0.0
-__device__ __forceinline__ unsigned long long score_key(double s) {
-    if (s != s) return ~0ull;
-    unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(s));
-    if (bits == 0x8000000000000000ull) bits = 0ull;
-    return (bits & 0x8000000000000000ull) ? ~bits : (bits | 0x8000000000000000ull);
-}
-
 // keep[i] (&)= rank of (s_i, i) < n_keep
 __global__ __launch_bounds__(kThreads) void dnc_rank_kernel(const double* __restrict__ scores, int64_t n, int64_t n_keep, int first,
                                                             int32_t* __restrict__ keep) {
     __shared__ unsigned long long tile[kThreads];
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-    const unsigned long long mine = i < n ? score_key(scores[i]) : 0ull;
+    const unsigned long long mine = i < n ? ordered_bits_total(scores[i]) : 0ull;
     int64_t below = 0;
     for (int64_t k0 = 0; k0 < n; k0 += kThreads) {
         const int64_t k = k0 + threadIdx.x;
-        tile[threadIdx.x] = k < n ? score_key(scores[k]) : ~0ull;
+        tile[threadIdx.x] = k < n ? ordered_bits_total(scores[k]) : ~0ull;
         __syncthreads();
         const int limit = n - k0 < kThreads ? static_cast<int>(n - k0) : kThreads;
         for (int t = 0; t < limit; ++t) {
@@ -241,8 +234,7 @@ __global__ __launch_bounds__(kOneThreads) void dnc_compact_kernel(const int32_t*
                                                                   int64_t n, int32_t* __restrict__ good,
                                                                   int32_t* __restrict__ count_word, int32_t* __restrict__ inactive_word,
                                                                   int32_t* __restrict__ count_out) {
-    __shared__ int offsets[kOneThreads];
-    __shared__ int inactive[kOneThreads];
+    __shared__ int lds[kOneThreads];
     const int tid = threadIdx.x;
     const int64_t chunk = (n + kOneThreads - 1) / kOneThreads;
     const int64_t lo = tid * chunk < n ? tid * chunk : n;
@@ -252,25 +244,15 @@ __global__ __launch_bounds__(kOneThreads) void dnc_compact_kernel(const int32_t*
         count += keep[r] != 0 ? 1 : 0;
         ina += bad[r] != 0.0 ? 1 : 0;
     }
-    offsets[tid] = count;
-    inactive[tid] = ina;
-    __syncthreads();
-    for (int step = 1; step < kOneThreads; step <<= 1) {  // inclusive Hillis-Steele scan
-        const int add = tid >= step ? offsets[tid - step] : 0;
-        const int add_i = tid >= step ? inactive[tid - step] : 0;
-        __syncthreads();
-        offsets[tid] += add;
-        inactive[tid] += add_i;
-        __syncthreads();
-    }
-    const int total = offsets[kOneThreads - 1];
-    int slot = offsets[tid] - count;
+    const int inactive = block_sum<int, kOneThreads>(ina, lds);
+    int total;
+    int slot = block_exclusive_scan<kOneThreads>(count, lds, &total);
     for (int64_t r = lo; r < hi; ++r)
         if (keep[r] != 0) good[slot++] = static_cast<int32_t>(r);
     for (int64_t r = total + tid; r < n; r += kOneThreads) good[r] = -1;
     if (tid == 0) {
         *count_word = total;
-        *inactive_word = inactive[kOneThreads - 1];
+        *inactive_word = inactive;
         if (count_out != nullptr) *count_out = total;
     }
 }

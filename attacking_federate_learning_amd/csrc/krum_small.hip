@@ -29,6 +29,7 @@
 // the machine balance of the 16-bit matrix pipe for every N <= 128); in fact cache latency and the one kernel boundary.
 #include "common.hpp"
 #include "lane_exchange.hpp"
+#include "order_keys.hpp"
 
 #include <type_traits>
 
@@ -54,8 +55,6 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int visit_position(int u) { return u == 0 ? 1 : (u == 1 ? 0 : u); }
 
 // 4 consecutive floats of a row starting at column k (any 4-byte alignment), zero past n_cols.  Branch-free: every lane
 // loads (a clamped address) and selects afterwards -- a branch around a load makes hipcc wait for each load in turn.
@@ -566,8 +565,7 @@ __global__ __launch_bounds__(kThreads, 1) void small_rows_kernel(RowsArgs p) {
             const int u = lane + 64 * r;
             const float sc = (r == 0 ? s0 : s1) + 0.0f;
             if (u < n && sc < kKrumInit) {     // false for NaN, as in the reference
-                const uint32_t bits = __float_as_uint(sc);
-                const uint32_t ordered = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);   // monotone in the value
+                const uint32_t ordered = ordered_bits(sc);   // monotone in the value
                 const unsigned long long k = (static_cast<unsigned long long>(ordered) << 32) | static_cast<unsigned>(visit_position(u));
                 key = k < key ? k : key;
             }

@@ -19,6 +19,7 @@
 //                               outside the band cannot win or tie, so the selection is the reference's, pick for pick.  Rows
 //                               with a negative or non-finite entry (an arbitrary caller-supplied matrix) always contend.
 #include "common.hpp"
+#include "order_keys.hpp"
 
 #include <hip/hip_cooperative_groups.h>
 
@@ -30,15 +31,6 @@ namespace {
 constexpr int kSortThreads = 1024;
 constexpr float kKrumInit = 1e20f;    // defences.py:27
 constexpr size_t kKeyScratchBytes = size_t{4} << 30;
-
-__device__ __forceinline__ uint32_t ordered_bits(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ int visit_position(int u) { return u == 0 ? 1 : (u == 1 ? 0 : u); }
 
 // FIRST: every merge k = 2 .. len of one chunk; else the levels j = len / 2 .. 1 of the merge of size k_merge.  A chunk is 32 KiB of
 // keys: 4096 of 64 bits (value | column: the selection), 8192 of 32 bits (values alone: Krum).

@@ -43,6 +43,7 @@
 #include "common.hpp"
 
 #include "lane_exchange.hpp"
+#include "order_keys.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -63,15 +64,6 @@ constexpr int kArithProbes = 12;          // value-space probes before switching
 constexpr int kCand = 16;                 // candidates per column handed to the sorting network
 constexpr float kAimOffset = 0.35f * kCand;   // ranks by which a probe aims past the wanted rank
 constexpr float kStallRatio = 0.85f;
-
-__device__ __forceinline__ uint32_t fkey(float v) {  // order-preserving map float -> uint32
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_fkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 template <bool ABS>
 __device__ __forceinline__ float mag(float v) { return ABS ? __builtin_fabsf(v) : v; }
@@ -170,7 +162,7 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
         // ---- next probe of every probing column
         {
             const bool active = state == 0;
-            const uint32_t klo = fkey(lo), khi = fkey(hi);
+            const uint32_t klo = ordered_bits(lo), khi = ordered_bits(hi);
             const bool adjacent = khi - klo <= 1u;       // no float strictly inside: every candidate equals hi
             const float cand = static_cast<float>(c_hi - c_lo);
             const float aim = want + (last > 0 ? -kAimOffset : kAimOffset);
@@ -178,8 +170,8 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
             f = __builtin_fminf(__builtin_fmaxf(f, 0.02f), 0.98f);
             f = stalled ? 0.5f : f;
             const float Ta = __builtin_fmaf(f, hi - lo, lo);
-            const bool arith = probes < kArithProbes && finite_f(lo) && finite_f(hi) && Ta > lo && Ta < hi;
-            const float Tk = from_fkey(klo + ((khi - klo) >> 1));
+            const bool arith = probes < kArithProbes && finite_bits(lo) && finite_bits(hi) && Ta > lo && Ta < hi;
+            const float Tk = from_ordered_bits(klo + ((khi - klo) >> 1));
             if (active) T = (arith ? Ta : Tk) + 0.0f;   // -0.0 would count +0.0 as greater; a split column keeps its T
             if (active && adjacent) {
                 state = 2;
@@ -203,7 +195,7 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
                                 const unsigned long long m = __ballot(a > lo_c && a <= hi_c);
                                 if (m) {
                                     pv = lane_value(a, __builtin_ctzll(m));
-                                    if (!(pv < hi_c)) pv = from_fkey(fkey(pv) - 1u);   // stay strictly inside
+                                    if (!(pv < hi_c)) pv = from_ordered_bits(ordered_bits(pv) - 1u);   // stay strictly inside
                                     have = pv > lo_c;
                                 }
                             }
@@ -285,7 +277,7 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         if ((to_sort >> c) & 1u) {
-            const float lo_next = uniform(from_fkey(fkey(lane_value(lo, c)) + 1u)), hi_c = lane_value(hi, c);
+            const float lo_next = uniform(from_ordered_bits(ordered_bits(lane_value(lo, c)) + 1u)), hi_c = lane_value(hi, c);
             int n_cand = 0;
 #pragma unroll
             for (int g = 0; g < RPL / GS; ++g) {
@@ -390,14 +382,14 @@ __device__ __forceinline__ void bucket_select(const float (&x)[NC][RPL], int gro
         below[c] = 0;
         plo[c] = 0.0f; pinv[c] = 0.0f; pb[c] = 0u;
         const float width = hi0[c] - lo0[c];
-        live[c] = want[c] && finite_f(lo0[c]) && finite_f(hi0[c]) && finite_f(width) && width > 0.0f;
-        if (want[c] && finite_f(lo0[c]) && hi0[c] == lo0[c]) {   // every value is the same
+        live[c] = want[c] && finite_bits(lo0[c]) && finite_bits(hi0[c]) && finite_bits(width) && width > 0.0f;
+        if (want[c] && finite_bits(lo0[c]) && hi0[c] == lo0[c]) {   // every value is the same
             ok[c] = true;
             res_a[c] = res_b[c] = lo0[c];
         }
         lo[c] = lo0[c];
         inv[c] = live[c] ? uniform(static_cast<float>(kBuckets) * (1.0f - 1.0f / 1048576.0f) / width) : 0.0f;
-        live[c] = live[c] && finite_f(inv[c]);
+        live[c] = live[c] && finite_bits(inv[c]);
     }
 #pragma unroll
     for (int level = 0; level < 2; ++level) {
@@ -479,7 +471,7 @@ __device__ __forceinline__ void bucket_select(const float (&x)[NC][RPL], int gro
                         const float w = 1.0f / inv[c];             // ~ bucket width
                         lo[c] = uniform(plo[c] + (static_cast<float>(tb[c]) - 0.01f) * w);
                         inv[c] = uniform(static_cast<float>(kBuckets) * (1.0f - 1.0f / 1048576.0f) / (1.02f * w));
-                        if (!finite_f(inv[c]) || !finite_f(lo[c])) live[c] = false;
+                        if (!finite_bits(inv[c]) || !finite_bits(lo[c])) live[c] = false;
                     } else {
                         live[c] = false;                          // too crowded: general path
                     }
@@ -637,7 +629,7 @@ __device__ __forceinline__ void finish_tile(float (&x)[NC][RPL], const float (&m
         q[c].hi = hi_x[c];
         q[c].c_hi = n_rows;
         q[c].c_lo = 0;
-        q[c].lo = uniform(from_fkey(fkey(lo_x[c]) - 1u));   // the float just below the minimum
+        q[c].lo = uniform(from_ordered_bits(ordered_bits(lo_x[c]) - 1u));   // the float just below the minimum
         q[c].a = q[c].b = 0.0f;
         if (!(lo_x[c] > -pinf) || dead[c]) {   // -inf in the data (or nothing to do): bracket by key space alone
             q[c].lo = -pinf;

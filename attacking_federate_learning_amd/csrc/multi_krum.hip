@@ -11,32 +11,21 @@
 //          selected rows in ASCENDING order -- the list the row-list mean walks (numpy's np.mean(G[np.sort(sel)], axis=0)).
 // Nothing here reads the distance matrix.  Work: O(n log^2 n) compare-exchanges in the sort, O(n) elsewhere.
 #include "common.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
 
 constexpr int kTakeThreads = 1024;
 
-__device__ __forceinline__ unsigned visit_position(int u) { return u == 0 ? 1u : (u == 1 ? 0u : static_cast<unsigned>(u)); }
-__device__ __forceinline__ int row_of_visit(unsigned vp) { return vp == 0 ? 1 : (vp == 1 ? 0 : static_cast<int>(vp)); }
-
 __global__ __launch_bounds__(256) void multi_krum_keys_kernel(const float* __restrict__ scores, int n, int64_t n_pad,
                                                               unsigned long long* __restrict__ keys) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n_pad) return;
     unsigned long long key = ~0ull;
-    if (i < n) {
-        const float s = scores[i];
-        uint32_t bits = __float_as_uint(s);
-        uint32_t ordered;
-        if (s != s) {
-            ordered = 0xffffffffu;                         // any NaN: behind +inf (0xff800000)
-        } else {
-            if (bits == 0x80000000u) bits = 0u;            // -0.0 == +0.0
-            ordered = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-        }
-        key = (static_cast<unsigned long long>(ordered) << 32) | visit_position(static_cast<int>(i));
-    }
+    if (i < n)
+        key = (static_cast<unsigned long long>(ordered_bits_total(scores[i])) << 32) |
+              static_cast<unsigned>(visit_position(static_cast<int>(i)));
     keys[i] = key;
 }
 
@@ -47,7 +36,7 @@ __global__ __launch_bounds__(kTakeThreads) void multi_krum_take_kernel(const uns
     __shared__ int offsets[kTakeThreads];
     const int tid = threadIdx.x;
     for (int k = tid; k < m; k += kTakeThreads) {
-        const int row = row_of_visit(static_cast<unsigned>(keys[k] & 0xffffffffull));
+        const int row = row_of_visit(static_cast<int>(keys[k] & 0xffffffffull));
         if (selection != nullptr) selection[k] = row;
         flags[row] = 1;
     }
@@ -58,15 +47,7 @@ __global__ __launch_bounds__(kTakeThreads) void multi_krum_take_kernel(const uns
     const int hi = lo + chunk < n ? lo + chunk : n;
     int count = 0;
     for (int r = lo; r < hi; ++r) count += flags[r];
-    offsets[tid] = count;
-    __syncthreads();
-    for (int step = 1; step < kTakeThreads; step <<= 1) {  // inclusive Hillis-Steele scan
-        const int add = tid >= step ? offsets[tid - step] : 0;
-        __syncthreads();
-        offsets[tid] += add;
-        __syncthreads();
-    }
-    int slot = offsets[tid] - count;
+    int slot = block_exclusive_scan<kTakeThreads>(count, offsets, nullptr);
     for (int r = lo; r < hi; ++r)
         if (flags[r] != 0 && slot < m) rows_asc[slot++] = r;
 }

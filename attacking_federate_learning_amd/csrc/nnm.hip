@@ -7,7 +7,7 @@
 //           order is total and ties (the attack's f identical rows) fall the same way on every run.
 //   sort    segment_sort_u64 (large_rows.hip): n segments of next_pow2(n) keys
 //   take    one workgroup a row: the first k - 1 keys whose distance is finite, and i itself, flagged in an LDS bitmap; the
-//           bitmap compacted to the ASCENDING list (multi_krum_take_kernel's scan, on words of 32 rows); the tail -1
+//           bitmap compacted to the ASCENDING list (block_exclusive_scan, on words of 32 rows); the tail -1
 //   mask    A^T as fp32 zeros and ones, [j][i], scattered from the lists: the mix takes ANY lists, so this is the one way in
 //   mix     Y = diag(1 / k_i) A G on v_mfma_f32_32x32x2_f32, which is bit for bit a k-ordered fmaf chain: with a multiplier of
 //           exactly 1 or 0, fma(1, x, c) = fl32(c + x) and fma(0, x, c) = c for finite x, so ONE accumulator chain over
@@ -23,6 +23,7 @@
 // block's global loads are issued before the current block's MFMAs.  Workgroups are numbered so that the row tiles of one
 // column panel run next to each other on ONE XCD: the panel is read from HBM once and then served by that XCD's L2.
 #include "common.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
@@ -36,17 +37,6 @@ constexpr int kMaxRows = static_cast<int>(kNnmMaxRows);   // 16,384: the keys an
 constexpr int kBitmapWords = kMaxRows / 32;           // 512
 constexpr int kWordsPerThread = kBitmapWords / kTakeThreads;   // 2
 
-constexpr uint32_t kOrderedPosInf = 0xff800000u;      // ordered bits of +inf: every finite positive value is below
-constexpr uint32_t kOrderedNegInf = 0x007fffffu;      // ordered bits of -inf
-
-__device__ __forceinline__ uint32_t ordered_bits(float d) {
-    if (d != d) return 0xffffffffu;                    // any NaN: behind +inf
-    uint32_t bits = __float_as_uint(d);
-    if (bits == 0x80000000u) bits = 0u;                // -0.0 == +0.0
-    return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
-__device__ __forceinline__ bool ordered_is_finite(uint32_t o) { return o < kOrderedPosInf && o != kOrderedNegInf; }
-
 // grid (n_pad / 256, n): keys[i * n_pad + r]
 __global__ __launch_bounds__(kKeyThreads) void nnm_keys_kernel(const float* __restrict__ dist, int n, int64_t n_pad,
                                                                unsigned long long* __restrict__ keys) {
@@ -55,7 +45,7 @@ __global__ __launch_bounds__(kKeyThreads) void nnm_keys_kernel(const float* __re
     if (r >= n_pad) return;
     unsigned long long key = ~0ull;
     if (r < n && r != i)
-        key = (static_cast<unsigned long long>(ordered_bits(dist[static_cast<int64_t>(i) * n + r])) << 32) |
+        key = (static_cast<unsigned long long>(ordered_bits_total(dist[static_cast<int64_t>(i) * n + r])) << 32) |
               static_cast<unsigned long long>(r);
     keys[static_cast<int64_t>(i) * n_pad + r] = key;
 }
@@ -83,16 +73,8 @@ __global__ __launch_bounds__(kTakeThreads) void nnm_take_kernel(const unsigned l
     int count = 0;
 #pragma unroll
     for (int w = 0; w < kWordsPerThread; ++w) count += __popc(bitmap[tid * kWordsPerThread + w]);
-    offsets[tid] = count;
-    __syncthreads();
-    for (int step = 1; step < kTakeThreads; step <<= 1) {   // inclusive Hillis-Steele scan
-        const int add = tid >= step ? offsets[tid - step] : 0;
-        __syncthreads();
-        offsets[tid] += add;
-        __syncthreads();
-    }
-    const int k_i = offsets[kTakeThreads - 1];
-    int slot = offsets[tid] - count;
+    int k_i;
+    int slot = block_exclusive_scan<kTakeThreads>(count, offsets, &k_i);
     int32_t* list = nbr + static_cast<int64_t>(i) * k;
 #pragma unroll
     for (int w = 0; w < kWordsPerThread; ++w) {

@@ -20,6 +20,7 @@
 //              ty + RG, ...), the four passes and the sums run over the registers: 4 n D + 4 D bytes of traffic.
 // The dispatcher picks by height alone (pick_shape).
 #include "common.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
@@ -33,13 +34,10 @@ constexpr int kResidentBatch = 4;
 constexpr int kSegments = 16;                  // the walk to a rank's digit: sixteen 16-digit segment sums, then 16 + 16 steps
 
 __device__ __forceinline__ uint32_t rank_key(float v) {
-    const uint32_t b = __float_as_uint(v);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return kNanKey;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    if ((__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u) return kNanKey;
+    return ordered_bits(v);
 }
-__device__ __forceinline__ float key_value(uint32_t k) {      // (kNanKey -> 0x7ffffffe, a NaN)
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+__device__ __forceinline__ float key_value(uint32_t k) { return from_ordered_bits(k); }   // (kNanKey -> 0x7ffffffe, a NaN)
 
 constexpr int lds_words(int cols, bool wide) { return 256 * cols * (wide ? 2 : 1) + (2 * kSegments + 7) * cols; }
 

@@ -24,6 +24,7 @@
 // sum, the contenders are re-scored in exactly that arithmetic (reference_score), so that given the same distance
 // matrix the selection is the reference's, pick for pick -- not a more accurate one.
 #include "common.hpp"
+#include "order_keys.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -33,15 +34,6 @@ namespace {
 
 constexpr int kMaxSelectRows = 16384;  // 128 KiB of 64-bit keys in LDS
 constexpr float kKrumInit = 1e20f;     // defences.py:27
-
-__device__ __forceinline__ uint32_t ordered_bits(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ int visit_position(int u) { return u == 0 ? 1 : (u == 1 ? 0 : u); }
 
 // (defined with the Bulyan re-score below; row_sort_kernel's Krum score uses it too)
 __device__ __forceinline__ float integer_passes(uint32_t (&M)[8], const int (&ex)[8], float s, int lane);
@@ -1207,7 +1199,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
                 const bool one_class = __ballot(in_b) == 0ull && __ballot(in_a && a_cls != lead_cls) == 0ull;
                 if (one_class) {
                     const int pos = wave_min_i(in_a ? visit_position(a_row) : 0x7fffffff);
-                    d.winner = pos == 0 ? 1 : (pos == 1 ? 0 : pos);   // visit_position is its own inverse
+                    d.winner = row_of_visit(pos);
                 } else {
                     d.mode = 1;
                 }
@@ -1554,7 +1546,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                     // one class in the band: its earliest member, proven.  Otherwise, OPTIMISTICALLY, the smallest exact score
                     // (the earliest of the workgroups whose best rounds down to the same float): verified behind the batch
                     const int pos = wave_min_i((one_class ? in_a : a == m1) ? visit_position(a_row) : 0x7fffffff);
-                    d.winner = pos == 0 ? 1 : (pos == 1 ? 0 : pos);   // visit_position is its own inverse
+                    d.winner = row_of_visit(pos);
                     is_contested = one_class ? 0 : 1;
                 }
                 if (lane == 0) {

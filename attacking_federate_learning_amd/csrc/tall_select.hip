@@ -18,6 +18,7 @@
 // Ties at the edge with both signs present (+t and -t: the only place where row order matters) are settled by one thread per
 // column walking the rows in order; a NaN anywhere in the column makes the result NaN, like np.median.
 #include "common.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
@@ -29,14 +30,6 @@ constexpr int kUnroll = 8;
 // far, the rank left, and the sixteen 16-digit segment sums of the walk to the rank's digit
 constexpr int kHistWords = 256 * kTileCols;
 constexpr int kLdsWords = kHistWords + kTileCols * (2 + kWaves + 3);
-
-__device__ __forceinline__ uint32_t ordered_bits(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 
 struct Column {
     const float* G;

@@ -41,6 +41,7 @@
 #include "common.hpp"
 
 #include "lane_exchange.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
@@ -54,14 +55,6 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int kTileCols = 16;
 constexpr float kMagic = 8388608.0f;   // 2^23: a float in [2^23, 2^24) has ulp 1 -- adding it rounds to an integer
 
-__device__ __forceinline__ uint32_t okey(float v) {   // order-preserving float -> uint32
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_okey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ bool is_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 // Sweep B keeps its predicates as LANE MASKS (what v_cmp writes: an SGPR pair) instead of per-lane booleans (round 6).  From
 // `acc += in ? d : 0; top += hit ? 1 : 0` hipcc makes two v_cndmask and a v_addc per value: it folds two steps' increments
 // into one add-with-carry and materialises the other step's as a 0 / 1 register.  With the masks in hand the increment is ONE
@@ -269,8 +262,8 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         if ((rr & 3) == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                atomicMin(&minmax[4 * q + e], okey(mn[e]));
-                atomicMax(&minmax[kTileCols + 4 * q + e], okey(mx[e]));
+                atomicMin(&minmax[4 * q + e], ordered_bits(mn[e]));
+                atomicMax(&minmax[kTileCols + 4 * q + e], ordered_bits(mx[e]));
             }
         }
     }
@@ -281,8 +274,8 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
     // (inv, nlo + 2^23) of a column: the same two numbers map a value to its bucket in both sweeps.  They are recomputed where
     // they are needed rather than kept: eight registers held across the phases were what pushed the tall shapes into scratch
     auto column_range = [&](int c, float& lo, float& hi) __attribute__((always_inline)) {
-        lo = from_okey(minmax[c]);
-        hi = from_okey(minmax[kTileCols + c]);
+        lo = from_ordered_bits(minmax[c]);
+        hi = from_ordered_bits(minmax[kTileCols + c]);
         if constexpr (!EXACT) {
             const float widen = 0.125f * (hi - lo);
             lo -= widen;
@@ -454,7 +447,7 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
         // a bucket must be many ulps of the values wide (differences x - med then order like the buckets do), and the
         // addend must keep its integer part: both follow from |value| * inv < 2^17
         const float big = __builtin_fmaxf(__builtin_fabsf(lo_c), __builtin_fabsf(hi_c)) * inv_c;
-        const bool range_ok = is_finite(lo_c) && is_finite(hi_c) && hi_c - lo_c > 0.0f && is_finite(inv_c) && big < 131072.0f;
+        const bool range_ok = finite_bits(lo_c) && finite_bits(hi_c) && hi_c - lo_c > 0.0f && finite_bits(inv_c) && big < 131072.0f;
         bool ok = range_ok && bm2 - bm1 <= 8 && expected <= CAP && need >= 1 && need <= n_upto_hi - n_in;
         // a sampled range: the end buckets also hold whatever fell outside it -- no ring may touch them
         if constexpr (!EXACT) ok = ok && first_left >= 1 && bm2 + ring_hi <= B - 2;

@@ -78,6 +78,31 @@ def test_row_counts_from_one_to_twenty_thousand(eng, torch, n, d, b):
     check_whole_call(eng, torch, g, f, sampled(d, b, n))
 
 
+def test_one_row_more_than_the_compaction_has_threads(eng, torch):
+    """1025 rows: the first size at which a thread of the compaction (1024 threads) owns two rows, so that thread 512 owns
+    one and every later thread none.  The whole call against the restatement, then the list as the kernel leaves it: the
+    kept rows ascending, -1 behind the count."""
+    from attacking_federate_learning_amd import _native
+    from attacking_federate_learning_amd.engine import _check, _vp
+    n, d, b, remove_count = 1025, 96, 32, 300
+    g = attacked(n, d, seed=n + d, mal_prop=0.24)
+    cols = sampled(d, b, n)
+    want_good = restated_dnc(g, remove_count, cols)[1]
+    assert len(want_good) == 725
+    check_whole_call(eng, torch, g, remove_count, cols)
+    assert eng.dnc_info()[0] == 725
+    gt = torch.from_numpy(g).to('cuda:%d' % eng.device)
+    cols_dev = eng.to_device(np.asarray(cols, dtype=np.int64))
+    good = eng.empty((n,), np.int32)
+    params = _native.DncParams(1, b, 32, remove_count)
+    _check(eng.lib.byz_dnc_select_dev(eng.ctx, _vp(gt.data_ptr()), n, d, d, ctypes.byref(params), _vp(cols_dev.ptr), _vp(good.ptr),
+                                      None, None))
+    assert eng.dnc_info()[0] == 725
+    good = good.numpy()
+    assert good[:725].tolist() == want_good.tolist() and (np.diff(good[:725]) > 0).all()
+    assert (good[725:] == -1).all()
+
+
 def test_remove_count_zero_is_no_defense(eng, torch):
     g = attacked(300, 5000, seed=3)
     gt = torch.from_numpy(g).to('cuda:%d' % eng.device)

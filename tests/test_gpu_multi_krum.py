@@ -160,6 +160,26 @@ def test_beyond_the_lds_resident_selection(eng, torch):
     assert np.array_equal(out.cpu().numpy(), np_mean_rows(g, want))
 
 
+def test_one_row_more_than_the_compaction_has_threads(eng, torch):
+    """1025 rows: the first size at which a thread of the take kernel's compaction (1024 threads) owns two rows, so that
+    thread 512 owns one and every later thread none.  The selection against the restated ranking of the engine's own scores,
+    the ascending list through the aggregate it is walked for, numpy's mean of the sorted selection bit for bit."""
+    n, d = 1025, 64
+    f = int(n * MAL_PROP)
+    g = attacked(n, d, f, seed=1025)
+    gt = torch.from_numpy(g).to('cuda:%d' % eng.device)
+    handle = eng.pairwise_distances(gt)
+    scores, krum_idx = engine_scores(eng, handle, n, f)
+    assert np.array_equal(scores, restated_scores(handle.numpy(), n, f))
+    for m in (1, 513, 1025):
+        want = restated_ranking(scores, m)
+        assert eng.multi_krum_select(handle, n, f, m=m).tolist() == want.tolist(), m
+        out, sel = eng.multi_krum(gt, n, f, m=m, return_selection=True)
+        assert sel.cpu().numpy().tolist() == want.tolist(), m
+        assert np.array_equal(out.cpu().numpy(), np_mean_rows(g, want)), m
+    assert restated_ranking(scores, 1).tolist() == [krum_idx]
+
+
 def test_distances_handle_strided_view_host_matrix_and_return_index(eng, torch):
     from attacking_federate_learning_amd import defences
     n, d, f = 200, 3001, 40

@@ -53,7 +53,8 @@ def bits(a):
 
 
 # ---- lists --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('n', [1, 2, 3, 31, 33, 100, 257, 1000, 4100])
+# (1025 rows are 33 bitmap words: one thread of the take kernel's compaction holds a single word, every later thread none)
+@pytest.mark.parametrize('n', [1, 2, 3, 31, 33, 100, 257, 1000, 1025, 4100])
 def test_lists_are_the_restatement_on_the_engines_own_distances(eng, n):
     d = 200
     f = int(n * MAL_PROP)
