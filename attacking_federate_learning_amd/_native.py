@@ -117,6 +117,11 @@ _PROTOTYPES = {
     'byz_nnm_info': [c_vp, _P(c_i64), _P(c_i64)],
     'byz_nnm_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_nnm_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
+    'byz_sign_votes_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_sign_flip_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp],
+    'byz_robust_lr_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_robust_lr_info': [c_vp, _P(c_i64)],
+    'byz_robust_lr_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

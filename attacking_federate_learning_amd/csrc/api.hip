@@ -1091,6 +1091,57 @@ int byz_nnm_info(byz_ctx* ctx, int64_t* solo_rows, int64_t* short_rows) {
     return BYZ_OK;
 }
 
+// ---- the robust learning rate (Ozdayi, Kantarcioglu and Gel, AAAI 2021; beyond the reference) ----------------------------------
+namespace {
+
+// theta counts clients: 0 .. n_rows (checked on the arguments alone)
+int check_rlr_theta(const char* who, int64_t theta, int64_t n_rows) {
+    if (theta < 0 || theta > n_rows) {
+        set_error("%s: theta = %lld outside 0..%lld (the row count)", who, (long long)theta, (long long)n_rows);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_sign_votes_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t* votes, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "sign_votes"));
+    BYZ_REQUIRE(votes, "sign_votes: null output");
+    BYZ_TRY(check_row_ceiling("sign_votes", n_rows));
+    ctx->rlr_stream = as_stream(stream);
+    return launch_sign_votes(ctx, G, n_rows, n_cols, ld, 0, nullptr, votes, as_stream(stream));
+}
+
+int byz_sign_flip_dev(byz_ctx* ctx, const float* agg, const int32_t* votes, int64_t n_cols, int64_t theta, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(agg && votes && out && n_cols > 0, "sign_flip: null vector or no columns (%lld)", (long long)n_cols);
+    BYZ_TRY(check_rlr_theta("sign_flip", theta, kLargeMaxRows));
+    ctx->rlr_stream = as_stream(stream);
+    return launch_sign_flip(ctx, agg, votes, n_cols, theta, out, as_stream(stream));
+}
+
+int byz_robust_lr_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t theta, float* out,
+                      int32_t* votes, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "robust_lr"));
+    BYZ_REQUIRE(out, "robust_lr: null output");
+    BYZ_TRY(check_row_ceiling("robust_lr", n_rows));
+    BYZ_TRY(check_rlr_theta("robust_lr", theta, n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "robust_lr"));
+    ctx->rlr_stream = as_stream(stream);
+    return launch_sign_votes(ctx, G, n_rows, n_cols, ld, theta, out, votes, as_stream(stream));
+}
+
+int byz_robust_lr_info(byz_ctx* ctx, int64_t* flipped_cols) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->rlr_stream));   // synchronises the last call's stream
+    if (flipped_cols) std::memcpy(flipped_cols, words + kRlrFlipped, sizeof(int64_t));
+    return BYZ_OK;
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -1536,6 +1587,24 @@ int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
                         nbr_host ? nbr : nullptr, s));
     BYZ_HIP(hipMemcpyAsync(Y_host, Y, y_bytes, hipMemcpyDeviceToHost, s));
     if (nbr_host) BYZ_HIP(hipMemcpyAsync(nbr_host, nbr, list_bytes, hipMemcpyDeviceToHost, s));
+    return check_small(ctx, s);
+}
+
+int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t theta, float* out_host,
+                       int32_t* votes_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "robust_lr"));
+    BYZ_REQUIRE(out_host, "robust_lr: null output");
+    BYZ_TRY(check_row_ceiling("robust_lr", n_rows));
+    BYZ_TRY(check_rlr_theta("robust_lr", theta, n_rows));
+    hipStream_t s = nullptr;
+    const size_t vec_bytes = static_cast<size_t>(n_cols) * sizeof(float);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, 2 * vec_bytes, s));
+    float* out = ctx->stage_out.as<float>();
+    int32_t* votes = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + vec_bytes);
+    BYZ_TRY(byz_robust_lr_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, theta, out, votes_host ? votes : nullptr, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, vec_bytes, hipMemcpyDeviceToHost, s));
+    if (votes_host) BYZ_HIP(hipMemcpyAsync(votes_host, votes, vec_bytes, hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
 }
 

@@ -150,6 +150,7 @@ struct byz_ctx {
     byz::Buffer nnm_mask;        // its 0/1 fp32 mask, transposed ([j][i], padded to the mix kernel's tiles), then the n list lengths
     byz::Buffer nnm_lists;       // its neighbour lists (n x k int32) and their lengths (n) when the caller passes no buffer
     hipStream_t nnm_stream = nullptr;      // stream of the last neighbour search (byz_nnm_info syncs it)
+    hipStream_t rlr_stream = nullptr;      // stream of the last sign vote or flip (byz_robust_lr_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -195,7 +196,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 38;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 40;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -217,6 +218,8 @@ constexpr int kFltrustTrusted = 30, kFltrustExcluded = 31, kFltrustTrustSum = 32
 // nearest-neighbour mixing: the rows whose list is themselves alone although k > 1, the rows whose list is shorter than k (adjacent:
 // one memset clears both)
 constexpr int kNnmSolo = 36, kNnmShort = 37;
+// robust learning rate: the columns the last call flipped (one 64-bit counter: two words, 8-byte aligned)
+constexpr int kRlrFlipped = 38;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -227,6 +230,9 @@ inline int32_t* attack_redo_word(byz_ctx* ctx) { return ctx->small.as<int32_t>()
 inline int32_t* near_pair_count_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordNearPairs; }
 inline int32_t* krum_winner_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordKrumWinner; }
 inline int32_t* geomed_words(byz_ctx* ctx) { return ctx->small.as<int32_t>(); }
+inline unsigned long long* rlr_flip_counter(byz_ctx* ctx) {
+    return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kRlrFlipped);
+}
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).
 struct KernelTimer {
@@ -391,6 +397,13 @@ constexpr int64_t kNnmMaxRows = 16384;
 int launch_nnm_neighbours(byz_ctx* ctx, const float* dist, int64_t n, int64_t k, int32_t* nbr, int32_t* counts, hipStream_t stream);
 int launch_nnm_mix(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const int32_t* nbr, const int32_t* counts,
                    int64_t k, float* Y, int64_t ldy, hipStream_t stream);
+// robust_lr.hip: the robust learning rate's sign vote (votes[c] = #positive - #negative, decided on the bits) and the flip of an
+// aggregate's sign bit where |votes[c]| < theta.  out == nullptr: the votes alone; otherwise out = no_defense's vector with the
+// flips applied, in the same walk (votes optional).  Both count the flipped columns into the context's counter.
+int launch_sign_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t theta, float* out,
+                      int32_t* votes, hipStream_t stream);
+int launch_sign_flip(byz_ctx* ctx, const float* agg, const int32_t* votes, int64_t n_cols, int64_t theta, float* out,
+                     hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

@@ -118,6 +118,36 @@ def nnm(users_grads, users_count, corrupted_count, then=None, distances=None, **
     return out.numpy() if host and isinstance(out, DeviceBuffer) else out
 
 
+def robust_lr(users_grads, users_count, corrupted_count, theta=None, then=None, return_votes=False, **then_kwargs):
+    """The robust learning rate (Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference), the defence designed for the
+    backdoor attack: per coordinate the clients' updates vote with their signs (votes = #positive - #negative; zeros and NaN
+    abstain), and where abs(votes) < theta the aggregate's sign bit is inverted -- with server.py:89-90's update that is the
+    paper's negated learning rate for that coordinate.  No rule by itself: it wraps an aggregate.  then=None wraps the plain
+    mean (no_defense's bits), vote and mean in one read of the matrix; with a callable the aggregate is then(users_grads,
+    users_count, corrupted_count, **then_kwargs) -- `trimmed_mean`, `coordinate_median`, `centered_clip`, ... -- on the
+    device-resident matrix (a host matrix is uploaded once) and the vote is a walk of its own.  theta: an integer in
+    [0, rows]; the default corrupted_count + 1 is the smallest threshold that corrupted_count colluding clients cannot reach
+    on their own -- this package's choice, the paper fixes no formula.  return_votes=True returns (aggregate, votes): the
+    int32 votes' sign is signSGD's majority vote.  Not one of the `defend` keys: the reference's main.py offers only those
+    four."""
+    engine = get_engine()
+    if theta is None:
+        theta = int(corrupted_count) + 1
+    theta = engine._theta(theta, int(users_grads.shape[0]))
+    if then is None:
+        return engine.robust_lr(users_grads, theta, return_votes=return_votes)
+    host = engine._device_matrix(users_grads) is None
+    if host:
+        users_grads = engine.to_device(engine._host_matrix(users_grads))
+    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
+    votes = engine.sign_votes(users_grads)
+    out = engine.sign_flip(agg, votes, theta)
+    if host:
+        out = out.numpy() if isinstance(out, DeviceBuffer) else out
+        votes = votes.numpy() if isinstance(votes, DeviceBuffer) else votes
+    return (out, votes) if return_votes else out
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

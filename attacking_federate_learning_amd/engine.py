@@ -1022,6 +1022,98 @@ class Engine:
         self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
         return (y, nbr) if return_neighbours else y
 
+    # ---- the robust learning rate (Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference) ----
+    def _i32_vector(self, v, n):
+        """A length-n int32 vector for a kernel -> (device pointer, keepalive, ours): a DeviceBuffer or a torch CUDA tensor
+        is used where it is (torch: made contiguous int32), anything else is uploaded (ours)."""
+        if isinstance(v, DeviceBuffer):
+            if v.dtype != np.int32 or int(np.prod(v.shape)) != n:
+                raise ValueError('a DeviceBuffer of votes must hold %d int32 values' % n)
+            return v.ptr, v, False
+        if _is_torch(v) and v.is_cuda:
+            import torch
+            if v.device.index != self.device:
+                raise ValueError('the votes live on %s, this engine drives cuda:%d' % (v.device, self.device))
+            t = v.reshape(-1).to(torch.int32).contiguous()
+            if t.numel() != n:
+                raise ValueError('expected %d votes, got %d' % (n, t.numel()))
+            return t.data_ptr(), t, False
+        host = np.asarray(v.cpu().numpy() if _is_torch(v) else v).reshape(-1)
+        if host.dtype.kind not in 'iu':
+            raise ValueError('votes must be integers, got %s' % host.dtype)
+        if host.size != n:
+            raise ValueError('expected %d votes, got %d' % (n, host.size))
+        buf = self.to_device(host.astype(np.int32))
+        return buf.ptr, buf, True
+
+    @staticmethod
+    def _theta(theta, n_rows=None):
+        if isinstance(theta, bool) or int(theta) != theta:
+            raise ValueError('theta must be an integer, got %r' % (theta,))
+        theta = int(theta)
+        if theta < 0 or (n_rows is not None and theta > n_rows):
+            raise ValueError('theta = %d outside 0..%s (the row count)' % (theta, 'n' if n_rows is None else n_rows))
+        return theta
+
+    def sign_votes(self, g):
+        """votes[c] = #{r : g[r, c] > 0} - #{r : g[r, c] < 0}, int32 of length D, in one read of g: +0.0, -0.0 and NaN cast
+        no vote, +-inf and denormals vote by their sign.  np.sign(votes) is signSGD's majority vote.  A torch tensor for a
+        torch input, numpy for a host input, a DeviceBuffer otherwise."""
+        m, stage, host = self._staged(g)
+        votes, vptr = self._out_like(m, m.cols, np.int32)
+        _check(self.lib.byz_sign_votes_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(vptr), _vp(m.stream)))
+        return votes.numpy() if host else votes      # (a download synchronises: the staged copy outlives the kernel)
+
+    def sign_flip(self, agg, votes, theta, out=None):
+        """out[c] = agg[c] with its sign bit inverted where abs(votes[c]) < theta, agg[c] verbatim elsewhere: the robust
+        learning rate applied to ANY aggregate.  out=agg (device-resident) flips in place.  numpy in -> numpy out;
+        device-resident in -> device-resident out."""
+        theta = self._theta(theta)
+        (aptr,), n, stream, keep, example = self._vectors(agg)
+        host = not (isinstance(agg, DeviceBuffer) or (_is_torch(agg) and agg.is_cuda))
+        vptr, vkeep, vours = self._i32_vector(votes, n)
+        if out is None:
+            res, optr = self._out_like(example, n)
+        else:
+            (optr,), n_out, _, _, _ = self._vectors(out)
+            if host or n_out != n or not (isinstance(out, DeviceBuffer) or (_is_torch(out) and out.is_cuda)):
+                raise ValueError('out must be a device-resident float32 vector of %d entries' % n)
+            res = out
+        _check(self.lib.byz_sign_flip_dev(self.ctx, _vp(aptr), _vp(vptr), n, theta, _vp(optr), _vp(stream)))
+        if host:
+            return res.numpy()                       # (a download synchronises)
+        if vours:
+            self.synchronize(stream)                 # uploaded votes must outlive the kernel
+        return res
+
+    def robust_lr_info(self):
+        """The number of columns the last sign_flip or robust_lr on this engine flipped (synchronises)."""
+        flipped = ctypes.c_int64(0)
+        _check(self.lib.byz_robust_lr_info(self.ctx, ctypes.byref(flipped)))
+        return int(flipped.value)
+
+    def robust_lr(self, g, theta, return_votes=False):
+        """The robust learning rate around the plain mean, fused: no_defense's vector (bit for bit) with the sign bit
+        inverted in every column where abs(votes) < theta, the vote counted in the same walk, so g is read once.  theta is
+        an integer in [0, rows]; 0 returns no_defense's bits.  return_votes=True also returns the int32 votes."""
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            theta = self._theta(theta, n)
+            out = np.empty(d, dtype=np.float32)
+            votes = np.empty(d, dtype=np.int32) if return_votes else None
+            _check(self.lib.byz_robust_lr_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, theta,
+                                               out.ctypes.data_as(ctypes.c_void_p),
+                                               votes.ctypes.data_as(ctypes.c_void_p) if return_votes else None))
+            return (out, votes) if return_votes else out
+        theta = self._theta(theta, dm.rows)
+        out, optr = self._out_like(dm, dm.cols)
+        votes, vptr = self._out_like(dm, dm.cols, np.int32) if return_votes else (None, None)
+        _check(self.lib.byz_robust_lr_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, theta, _vp(optr), _vp(vptr),
+                                          _vp(dm.stream)))
+        return (out, votes) if return_votes else out
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

@@ -12,6 +12,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
     defend_nnm(then)                  the same step with nearest-neighbour mixing in front of the rule `then`
+    defend_robust_lr(theta, then)     the same step with the robust learning rate round the mean or the rule `then`
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -98,6 +99,21 @@ class DeviceServer:
             raise TypeError('defend_nnm needs the rule to apply to the mixed matrix, e.g. defences.trimmed_mean')
         current_grads = defences.nnm(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), then=then,
                                      **then_kwargs)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with the robust learning rate round an aggregate ---------------------------------
+    def defend_robust_lr(self, theta=None, then=None, **then_kwargs):
+        """The robust learning rate on this round's gradients: the mean (then=None; vote and mean in one read of the matrix)
+        or the rule `then(grads, n_users, n_malicious, **then_kwargs)` -- defences.trimmed_mean, coordinate_median, ... --
+        with its sign inverted in every coordinate where the clients' sign vote stays below theta (default n_malicious + 1);
+        then server.py:89-90's momentum step, as `defend` takes it.  With velocity = momentum*velocity - lr*grads a negated
+        coordinate of grads is the paper's negated learning rate for that coordinate."""
+        if then is not None and not callable(then):
+            raise TypeError('defend_robust_lr: `then` is the rule to wrap, e.g. defences.trimmed_mean, or None for the mean')
+        current_grads = defences.robust_lr(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), theta=theta,
+                                           then=then, **then_kwargs)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

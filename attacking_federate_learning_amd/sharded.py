@@ -126,6 +126,12 @@ class HipKernels:
     def no_defense(self, g_local):
         return self.engine.no_defense(g_local)
 
+    def sign_votes(self, g_local):
+        return self.engine.sign_votes(g_local)                # this rank's columns of the votes: int32, on the device
+
+    def robust_lr(self, g_local, theta, return_votes=False):
+        return self.engine.robust_lr(g_local, theta, return_votes=return_votes)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -317,6 +323,13 @@ class ShardedAggregator:
         assert g_local.shape[0] >= 2 * corrupted_count + 1, (
             'rows>=2*corrupted_count + 1', g_local.shape[0], corrupted_count)
         return self._maybe_gather(self.kernels.rank_trimmed_mean(g_local, corrupted_count), gather, total_columns)
+
+    def robust_lr(self, g_local, users_count, corrupted_count, theta=None, gather=False, total_columns=None):
+        """The robust learning rate round the mean, columns layout: the sign vote and the mean are local to a column, so
+        every rank makes the single-GPU call on its own slice (default theta: corrupted_count + 1); no collective."""
+        if theta is None:
+            theta = int(corrupted_count) + 1
+        return self._maybe_gather(self.kernels.robust_lr(g_local, theta), gather, total_columns)
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

@@ -392,6 +392,44 @@ int byz_nnm_info(byz_ctx* ctx, int64_t* solo_rows, int64_t* short_rows);
 int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count,
                  int64_t corrupted_count, float* Y_host, int32_t* nbr_host);
 
+/* ---- the robust learning rate, RLR (Ozdayi, Kantarcioglu & Gel, "Defending against Backdoors in Federated Learning with  */
+/* Robust Learning Rate", AAAI 2021; not in the reference) ----                                                            */
+/* The defence designed for the backdoor attack.  Per coordinate the server sums the SIGNS of the clients' updates; where   */
+/* the absolute value of that sum is below a threshold theta, the learning rate of that coordinate is negated for the       */
+/* round.  No rule of its own: it wraps an aggregate (the paper wraps FedAvg, clipping and the median).  With the           */
+/* reference's update v = momentum v - lr agg, negating agg[c] is the negated learning rate of coordinate c.  G: n x n_cols  */
+/* fp32 (n = n_rows up to the selection limit of byz_limits, BYZ_E_UNSUPPORTED beyond), leading dimension ld:                */
+/*   votes[c] = #{ r : G[r][c] > 0 } - #{ r : G[r][c] < 0 }                                   (int32)                        */
+/*   flip[c]  = |votes[c]| < theta                                                                                          */
+/*   out[c]   = flip[c] ? agg[c] with its sign bit inverted : agg[c] verbatim                                                */
+/* A value's vote is decided on its bits with integer comparisons (sign bit; magnitude in (0, 0x7f800000]): +0.0, -0.0 and   */
+/* NaN cast no vote, +-inf and denormals vote by their sign, whatever the denormal mode.  The flip is an XOR of the sign     */
+/* bit: a zero becomes -0.0, a NaN keeps its payload; a non-finite aggregate passes through (agg is not sanitised).  theta   */
+/* is an integer in [0, n_rows] (BYZ_E_INVALID outside); theta = 0 returns agg's bits untouched.  The paper fixes no formula */
+/* for theta; corrupted_count + 1, the smallest threshold that corrupted_count colluding clients cannot reach on their own,  */
+/* is the Python layer's default and this package's choice.  sign(votes) is signSGD's majority vote (Bernstein et al. 2019). */
+/* Everything is asynchronous on `stream`; only byz_robust_lr_info synchronises.  The vote is local to a column: a rank of    */
+/* the columns layout calls these entry points on its own columns, so no sharded entry point exists (a panel's results are   */
+/* the one call's bits).                                                                                                    */
+/* The vote alone (votes_dev: n_cols int32): one read of G.                                                                 */
+int byz_sign_votes_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t* votes_dev,
+                       void* stream);
+/* The flip of ANY aggregate (agg_dev: n_cols fp32, e.g. a trimmed mean's or a median's result) by given votes; out_dev may   */
+/* be agg_dev.  0 <= theta <= the selection limit (the row count is not known here).                                         */
+int byz_sign_flip_dev(byz_ctx* ctx, const float* agg_dev, const int32_t* votes_dev, int64_t n_cols, int64_t theta,
+                      float* out_dev, void* stream);
+/* Fused, agg = the column mean: out_dev = byz_no_defense_dev's bits (a sequential fp32 chain from +0.0 in row order, then   */
+/* / (float)n_rows) with the flips applied, the vote counted in the same walk: G is read once.  votes_dev_or_null: n_cols    */
+/* int32.  out_dev must not overlap G (BYZ_E_INVALID).                                                                      */
+int byz_robust_lr_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t theta,
+                      float* out_dev, int32_t* votes_dev_or_null, void* stream);
+/* The columns flipped by the last of the three calls above on this context (byz_sign_votes_dev has no threshold: 0);        */
+/* synchronises that call's stream.                                                                                         */
+int byz_robust_lr_info(byz_ctx* ctx, int64_t* flipped_cols);
+/* The fused call on a host matrix (out_host: n_cols floats; votes_host_or_null: n_cols int32).  Synchronous.                */
+int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t theta, float* out_host,
+                       int32_t* votes_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -458,8 +496,8 @@ int byz_dnc_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* inactive_rows);
 /* through `user`.  Every rank makes the same calls in the same order (the pair count is read from the same    */
 /* all-reduced Gram on every rank).  A failing callback makes the call return BYZ_E_COLLECTIVE.  What          */
 /* attacking_federate_learning_amd/sharded.py composes in Python over torch.distributed, for hosts without it. */
-/* no_defense, trimmed_mean and the drift attack are independent per column: call the single-GPU entry         */
-/* points on the local slice.                                                                                  */
+/* no_defense, trimmed_mean, the drift attack and the robust learning rate's vote and flip are independent per */
+/* column: call the single-GPU entry points on the local slice.                                                */
 typedef int (*byz_allreduce_f64_fn)(void* user, double* buf_dev, int64_t count, void* stream);
 int byz_pairwise_distances_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows,
                                        int64_t n_cols_local, int64_t ld, byz_allreduce_f64_fn allreduce,
