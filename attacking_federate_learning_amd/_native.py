@@ -122,6 +122,8 @@ _PROTOTYPES = {
     'byz_robust_lr_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_robust_lr_info': [c_vp, _P(c_i64)],
     'byz_robust_lr_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_bucket_means_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
+    'byz_bucket_means_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

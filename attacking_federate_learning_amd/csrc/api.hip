@@ -1009,19 +1009,23 @@ int check_nnm(const char* who, int64_t n_rows, int64_t k) {
     return BYZ_OK;
 }
 
-// Y must not overlap G: a workgroup stores its tile of Y while others still read those rows of G
-int check_nnm_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* Y, int64_t ldy, const char* who) {
+// Y (y_rows x n_cols, leading dimension ldy) must not overlap G: a workgroup stores its part of Y while others still read G
+int check_matrix_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* Y, int64_t y_rows, int64_t ldy,
+                        const char* who) {
     if (!Y || ldy < n_cols) {
         set_error("%s: bad output (ptr %p, ldy %lld < %lld columns)", who, (const void*)Y, (long long)ldy, (long long)n_cols);
         return BYZ_E_INVALID;
     }
     const float* g_end = G + (n_rows - 1) * ld + n_cols;
-    const float* y_end = Y + (n_rows - 1) * ldy + n_cols;
+    const float* y_end = Y + (y_rows - 1) * ldy + n_cols;
     if (Y < g_end && y_end > G) {
         set_error("%s: the output overlaps the matrix", who);
         return BYZ_E_INVALID;
     }
     return BYZ_OK;
+}
+int check_nnm_output(const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* Y, int64_t ldy, const char* who) {
+    return check_matrix_output(G, n_rows, n_cols, ld, Y, n_rows, ldy, who);
 }
 
 // The whole call; allreduce == nullptr: one GPU holds every column.  Distances (over the ranks' slices when sharded: the one
@@ -1140,6 +1144,30 @@ int byz_robust_lr_info(byz_ctx* ctx, int64_t* flipped_cols) {
     BYZ_TRY(read_small(ctx, words, ctx->rlr_stream));   // synchronises the last call's stream
     if (flipped_cols) std::memcpy(flipped_cols, words + kRlrFlipped, sizeof(int64_t));
     return BYZ_OK;
+}
+
+// ---- s-bucketing (Karimireddy, He and Jaggi, ICLR 2022; beyond the reference) ---------------------------------------------------
+namespace {
+
+// the row ceiling first and on the arguments alone, then the shapes: 1 <= s <= n_rows
+int check_bucketing(const char* who, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t s) {
+    BYZ_TRY(check_row_ceiling(who, n_rows));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, who));
+    if (s < 1 || s > n_rows) {
+        set_error("%s: s = %lld outside 1..%lld (the row count)", who, (long long)s, (long long)n_rows);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_bucket_means_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* perm, int64_t s,
+                         float* Y, int64_t ldy, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_bucketing("bucket_means", G, n_rows, n_cols, ld, s));
+    BYZ_TRY(check_matrix_output(G, n_rows, n_cols, ld, Y, ceil_div(n_rows, s), ldy, "bucket_means"));
+    return launch_bucket_means(ctx, G, n_rows, n_cols, ld, perm, s, Y, ldy, as_stream(stream));
 }
 
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
@@ -1606,6 +1634,33 @@ int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_
     BYZ_HIP(hipMemcpyAsync(out_host, out, vec_bytes, hipMemcpyDeviceToHost, s));
     if (votes_host) BYZ_HIP(hipMemcpyAsync(votes_host, votes, vec_bytes, hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
+}
+
+int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const int32_t* perm_host, int64_t s,
+                          float* Y_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_bucketing("bucket_means", G_host, n_rows, n_cols, n_cols, s));
+    BYZ_REQUIRE(Y_host, "bucket_means: null output");
+    if (perm_host != nullptr) {     // a permutation of 0 .. n_rows - 1: every entry in range, none twice
+        std::vector<bool> seen(static_cast<size_t>(n_rows), false);
+        for (int64_t i = 0; i < n_rows; ++i) {
+            const int64_t e = perm_host[i];
+            BYZ_REQUIRE(e >= 0 && e < n_rows && !seen[static_cast<size_t>(e)],
+                        "bucket_means: perm is no permutation of 0..%lld (entry %lld is %lld)", (long long)(n_rows - 1), (long long)i,
+                        (long long)e);
+            seen[static_cast<size_t>(e)] = true;
+        }
+    }
+    hipStream_t s0 = nullptr;
+    const size_t y_bytes = static_cast<size_t>(ceil_div(n_rows, s)) * n_cols * sizeof(float);
+    const size_t perm_bytes = static_cast<size_t>(n_rows) * sizeof(int32_t);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, y_bytes + perm_bytes, s0));
+    float* Y = ctx->stage_out.as<float>();
+    int32_t* perm = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + y_bytes);
+    if (perm_host != nullptr) BYZ_HIP(hipMemcpyAsync(perm, perm_host, perm_bytes, hipMemcpyHostToDevice, s0));
+    BYZ_TRY(byz_bucket_means_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, perm_host ? perm : nullptr, s, Y, n_cols, s0));
+    BYZ_HIP(hipMemcpyAsync(Y_host, Y, y_bytes, hipMemcpyDeviceToHost, s0));
+    return check_small(ctx, s0);
 }
 
 int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_dnc_params* params,

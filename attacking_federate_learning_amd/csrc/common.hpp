@@ -404,6 +404,10 @@ int launch_sign_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
                       int32_t* votes, hipStream_t stream);
 int launch_sign_flip(byz_ctx* ctx, const float* agg, const int32_t* votes, int64_t n_cols, int64_t theta, float* out,
                      hipStream_t stream);
+// bucketing.hip: s-bucketing's means.  Y[b] = the mean of the rows perm[b s .. min((b + 1) s, n)) of G in list order, no_defense's
+// arithmetic (perm == nullptr: the identity); an entry of perm outside [0, n) is skipped, the divisor stays the bucket's length
+int launch_bucket_means(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* perm, int64_t s,
+                        float* Y, int64_t ldy, hipStream_t stream);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

@@ -14,7 +14,7 @@ Differences a caller can observe, all documented in DESIGN.md:
   * `_krum_create_distances` returns a `Distances` handle (GPU-resident N x N matrix) instead of a dict
     of dicts; `krum(..., distances=handle)` accepts it, `handle.to_dict()` rebuilds the reference's form.
 """
-from .engine import DeviceBuffer, Distances, dnc_columns, get_engine  # noqa: F401
+from .engine import DeviceBuffer, Distances, bucketing_permutation, dnc_columns, get_engine  # noqa: F401
 
 
 class DefenseTypes:
@@ -115,6 +115,34 @@ def nnm(users_grads, users_count, corrupted_count, then=None, distances=None, **
     if then is None:
         return mixed
     out = then(mixed, users_count, corrupted_count, **then_kwargs)
+    return out.numpy() if host and isinstance(out, DeviceBuffer) else out
+
+
+def bucketing(users_grads, users_count, corrupted_count, s=2, then=None, perm=None, seed=0, **then_kwargs):
+    """s-bucketing (Karimireddy, He and Jaggi, "Byzantine-Robust Learning on Heterogeneous Datasets via Bucketing", ICLR 2022;
+    not in the reference): the clients are shuffled and every s consecutive ones replaced by their mean --
+    np.mean(users_grads[perm[b*s:(b+1)*s]], axis=0) bit for bit; the last bucket may be short.  s is the bucket size: larger
+    buckets average more of the honest clients' heterogeneity away, and a bad client still spoils one bucket only, so at
+    most corrupted_count of the ceil(rows / s) buckets are bad; the paper's experiments use s = 2, the default here.  A
+    pre-aggregation: with then=None the bucketed ceil(rows / s) x D matrix comes back; with a callable the result is
+    then(bucketed, ceil(rows / s), corrupted_count, **then_kwargs) -- `krum`, `coordinate_median` (median-of-means),
+    `geometric_median`, `centered_clip`, ... -- with the corrupted count passed on unchanged, as the paper's bound has it
+    (the rule's own assertions decide whether s was too large for it), and the bucketed matrix stays on the device in
+    between; a host matrix is uploaded once and the answer comes back as numpy.  The shuffle is `perm` if given, else
+    bucketing_permutation(rows, seed), drawn on the host; the paper reshuffles every round, so pass a new seed per round.
+    Pre-aggregations chain: bucketing(..., then=functools.partial(nnm, then=rule)).  Not one of the `defend` keys: the
+    reference's main.py offers only those four, and this is no rule by itself."""
+    engine = get_engine()
+    rows = int(users_grads.shape[0])
+    if perm is None:
+        perm = bucketing_permutation(rows, seed)
+    host = engine._device_matrix(users_grads) is None
+    if host and then is not None:
+        users_grads = engine.to_device(engine._host_matrix(users_grads))
+    bucketed = engine.bucket_means(users_grads, s, perm)
+    if then is None:
+        return bucketed
+    out = then(bucketed, -(-rows // int(s)), corrupted_count, **then_kwargs)
     return out.numpy() if host and isinstance(out, DeviceBuffer) else out
 
 

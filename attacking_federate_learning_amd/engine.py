@@ -36,6 +36,15 @@ def dnc_columns(n_cols, sub_dim, n_iters=1, seed=0):
     return np.stack(rows)
 
 
+def bucketing_permutation(n, seed=0):
+    """Bucketing's shuffle of the n clients, drawn on the host so that the library stays deterministic:
+    np.random.default_rng(seed).permutation(n) as int32."""
+    n = int(n)
+    if n < 1:
+        raise ValueError('bucketing_permutation: n must be >= 1')
+    return np.random.default_rng(seed).permutation(n).astype(np.int32)
+
+
 class _DeviceF64:
     """A span of device doubles for torch.as_tensor (the all-reduce callback's buffer belongs to the library)."""
 
@@ -1023,26 +1032,26 @@ class Engine:
         return (y, nbr) if return_neighbours else y
 
     # ---- the robust learning rate (Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference) ----
-    def _i32_vector(self, v, n):
+    def _i32_vector(self, v, n, what='votes'):
         """A length-n int32 vector for a kernel -> (device pointer, keepalive, ours): a DeviceBuffer or a torch CUDA tensor
         is used where it is (torch: made contiguous int32), anything else is uploaded (ours)."""
         if isinstance(v, DeviceBuffer):
             if v.dtype != np.int32 or int(np.prod(v.shape)) != n:
-                raise ValueError('a DeviceBuffer of votes must hold %d int32 values' % n)
+                raise ValueError('a DeviceBuffer of %s must hold %d int32 values' % (what, n))
             return v.ptr, v, False
         if _is_torch(v) and v.is_cuda:
             import torch
             if v.device.index != self.device:
-                raise ValueError('the votes live on %s, this engine drives cuda:%d' % (v.device, self.device))
+                raise ValueError('the %s live on %s, this engine drives cuda:%d' % (what, v.device, self.device))
             t = v.reshape(-1).to(torch.int32).contiguous()
             if t.numel() != n:
-                raise ValueError('expected %d votes, got %d' % (n, t.numel()))
+                raise ValueError('expected %d %s, got %d' % (n, what, t.numel()))
             return t.data_ptr(), t, False
         host = np.asarray(v.cpu().numpy() if _is_torch(v) else v).reshape(-1)
         if host.dtype.kind not in 'iu':
-            raise ValueError('votes must be integers, got %s' % host.dtype)
+            raise ValueError('%s must be integers, got %s' % (what, host.dtype))
         if host.size != n:
-            raise ValueError('expected %d votes, got %d' % (n, host.size))
+            raise ValueError('expected %d %s, got %d' % (n, what, host.size))
         buf = self.to_device(host.astype(np.int32))
         return buf.ptr, buf, True
 
@@ -1113,6 +1122,46 @@ class Engine:
         _check(self.lib.byz_robust_lr_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, theta, _vp(optr), _vp(vptr),
                                           _vp(dm.stream)))
         return (out, votes) if return_votes else out
+
+    # ---- s-bucketing (Karimireddy, He and Jaggi, ICLR 2022; not in the reference) ----
+    def bucket_means(self, g, s, perm=None):
+        """The ceil(n / s) x D matrix of bucket means: row b is np.mean(g[perm[b*s:(b+1)*s]], axis=0) bit for bit (the
+        bucket's rows added in list order, sequential fp32 from +0.0, divided by the bucket's length; the last bucket may be
+        short).  `perm`: a permutation of range(n) (`bucketing_permutation`), None for the identity; a host array is checked,
+        a device-resident one (torch CUDA tensor, DeviceBuffer of int32) is the caller's word -- an entry out of range is
+        skipped by the kernel, never read.  s = n with the identity is no_defense's vector, s = 1 is g[perm].  `g` may be a
+        column panel of a larger matrix (a strided view).  The result stays on the device when `g` was there; numpy for a host
+        matrix."""
+        if isinstance(s, bool) or int(s) != s:
+            raise ValueError('s must be an integer, got %r' % (s,))
+        s = int(s)
+        dm = self._device_matrix(g)
+        h = self._host_matrix(g) if dm is None else None
+        n, d = (dm.rows, dm.cols) if dm is not None else h.shape
+        if s < 1 or s > n:
+            raise ValueError('s = %d outside 1..%d (the row count)' % (s, n))
+        buckets = -(-n // s)
+        on_device = isinstance(perm, DeviceBuffer) or (_is_torch(perm) and perm.is_cuda)
+        if perm is not None and not on_device:
+            perm = np.asarray(perm.numpy() if _is_torch(perm) else perm).reshape(-1)
+            if perm.dtype.kind not in 'iu' or perm.size != n or not np.array_equal(np.sort(perm), np.arange(n)):
+                raise ValueError('perm must be a permutation of range(%d)' % n)
+            perm = np.ascontiguousarray(perm, dtype=np.int32)
+        if dm is None:
+            if on_device:
+                perm = perm.numpy() if isinstance(perm, DeviceBuffer) else perm.cpu().numpy()
+                perm = np.ascontiguousarray(perm.reshape(-1), dtype=np.int32)
+            y = np.empty((buckets, d), dtype=np.float32)
+            _check(self.lib.byz_bucket_means_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d,
+                                                  perm.ctypes.data_as(ctypes.c_void_p) if perm is not None else None, s,
+                                                  y.ctypes.data_as(ctypes.c_void_p)))
+            return y
+        pptr, keep, ours = (None, None, False) if perm is None else self._i32_vector(perm, n, what='perm entries')
+        y, yptr = self._out_like(dm, (buckets, d))
+        _check(self.lib.byz_bucket_means_dev(self.ctx, _vp(dm.ptr), n, d, dm.ld, _vp(pptr), s, _vp(yptr), d, _vp(dm.stream)))
+        if ours:
+            self.synchronize(dm.stream)      # the uploaded permutation must outlive the kernel
+        return y
 
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):

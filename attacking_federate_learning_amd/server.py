@@ -13,6 +13,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
     defend_nnm(then)                  the same step with nearest-neighbour mixing in front of the rule `then`
     defend_robust_lr(theta, then)     the same step with the robust learning rate round the mean or the rule `then`
+    defend_bucketing(then, s)         the same step with s-bucketing, reshuffled every round, in front of the rule `then`
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -37,6 +38,8 @@ class DeviceServer:
         self.velocity = torch.zeros_like(self.current_weights)
         # centered clipping's history: the previous round's aggregate (zeros before the first round)
         self.clip_centre = torch.zeros_like(self.current_weights)
+        # bucketing's history: the calls of defend_bucketing so far (the default seed of the next shuffle)
+        self.bucketing_round = 0
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -114,6 +117,25 @@ class DeviceServer:
             raise TypeError('defend_robust_lr: `then` is the rule to wrap, e.g. defences.trimmed_mean, or None for the mean')
         current_grads = defences.robust_lr(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), theta=theta,
                                            then=then, **then_kwargs)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with s-bucketing in front of a rule ----------------------------------------------
+    def defend_bucketing(self, then, s=2, seed=None, **then_kwargs):
+        """s-bucketing of this round's gradients (the clients shuffled, every s consecutive ones replaced by their mean), the
+        rule `then(bucketed, ceil(n_users / s), n_malicious, **then_kwargs)` on the bucket means -- defences.krum,
+        coordinate_median, geometric_median, centered_clip, ... --, then server.py:89-90's momentum step, as `defend` takes
+        it.  The shuffle is bucketing_permutation(n_users, seed); seed=None takes `bucketing_round`, the number of earlier
+        calls of this method on this server, so that every round reshuffles, as the paper requires.  The bucketed matrix never
+        leaves the device."""
+        if not callable(then):
+            raise TypeError('defend_bucketing needs the rule to apply to the bucket means, e.g. defences.coordinate_median')
+        if seed is None:
+            seed = self.bucketing_round
+        self.bucketing_round += 1
+        current_grads = defences.bucketing(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), s=s,
+                                           then=then, seed=seed, **then_kwargs)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

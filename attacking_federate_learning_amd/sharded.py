@@ -85,6 +85,9 @@ class HipKernels:
     def nnm_mix(self, g_local, neighbours, counts=None):
         return self.engine.nnm_mix(g_local, neighbours, counts)     # this rank's columns of the mixed matrix
 
+    def bucket_means(self, g_local, s, perm):
+        return self.engine.bucket_means(g_local, s, perm)     # this rank's columns of the bucket means
+
     def row_sqdist(self, g_local, z):
         return self.engine.row_sqdist(g_local, z)             # (N,) float64: this rank's part over its columns
 
@@ -373,6 +376,17 @@ class ShardedAggregator:
         neighbours, counts = self.kernels.nnm_neighbours(dist_m, int(users_count) - int(corrupted_count))
         mixed = self.kernels.nnm_mix(g_local, neighbours, counts)
         return (mixed, neighbours) if return_neighbours else mixed
+
+    def bucketing(self, g_local, users_count, corrupted_count, s=2, perm=None, seed=0):
+        """s-bucketing, columns layout: a bucket's mean is local to a column, so every rank makes the single-GPU call on its
+        own slice; no collective.  EVERY RANK MUST PASS THE SAME `perm`, or the same `seed` (the shuffle is then
+        bucketing_permutation(rows, seed), drawn on each host alike): the buckets are then the same clients on every rank.
+        Returns the local slice (ceil(n / s) x local columns) of the bucketed matrix: the input of a rule of this class on the
+        same layout, called with ceil(n / s) users and the corrupted count unchanged.  A clients layout is not offered."""
+        from .engine import bucketing_permutation
+        if perm is None:
+            perm = bucketing_permutation(g_local.shape[0], seed)
+        return self.kernels.bucket_means(g_local, s, perm)
 
     def geometric_median(self, g_local, nu=1e-6, max_iter=10, ftol=1e-6, gather=False, return_info=False,
                          total_columns=None):

@@ -430,6 +430,35 @@ int byz_robust_lr_info(byz_ctx* ctx, int64_t* flipped_cols);
 int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t theta, float* out_host,
                        int32_t* votes_host_or_null);
 
+/* ---- s-bucketing (Karimireddy, He & Jaggi, "Byzantine-Robust Learning on Heterogeneous Datasets via Bucketing", ICLR      */
+/* 2022; not in the reference) ----                                                                                        */
+/* A PRE-aggregation: the clients are shuffled, every s consecutive ones are replaced by their mean, and the B = ceil(n/s)  */
+/* bucket means are what Krum, the median, the geometric median or centered clipping then see (behind the median it is      */
+/* median-of-means).  G: n x n_cols fp32 (n = n_rows up to byz_limits' selection limit, BYZ_E_UNSUPPORTED beyond, decided   */
+/* on the argument alone), leading dimension ld.  perm: a permutation of 0 .. n-1 as int32, NULL for the identity.          */
+/* 1 <= s <= n (BYZ_E_INVALID otherwise).  Bucket b holds the rows perm[b s .. min((b+1) s, n) - 1] in that order; the last  */
+/* bucket may be short; c_b is a bucket's length.                                                                           */
+/*   Y[b] = np.mean(G[perm[b*s : (b+1)*s]], axis=0) bit for bit: the bucket's rows added in list order, sequential fp32     */
+/*   from +0.0, divided (a true division) by (float)c_b -- byz_mean_rows_dev's and byz_no_defense_dev's arithmetic.  So     */
+/*   s = n with the identity makes the single row of Y byz_no_defense_dev's bits, and s = 1 makes Y a row-permuted copy of  */
+/*   G: x + 0.0 and then / 1.0f change no bit except that -0.0 becomes +0.0 (the chain starts at +0.0; not special-cased).  */
+/* Nothing is sanitised: a NaN or an infinity in a row reaches its bucket's mean in that column as IEEE arithmetic gives it, */
+/* and no other element of Y.  A poisoned row spoils one bucket, which the rule behind treats as one bad row: the paper's    */
+/* accounting, in which at most f of the B buckets are contaminated.                                                        */
+/* Y: B x n_cols, leading dimension ldy >= n_cols; it must not overlap G (BYZ_E_INVALID).  Everything is asynchronous on     */
+/* `stream`; nothing synchronises with the host.  Cost: one read of G and one write of Y.                                   */
+/* On the device entry point the caller vouches for perm; an entry outside [0, n) is skipped without being used as a row     */
+/* number (it cannot fault) and the divisor stays c_b.  The caller may walk the columns in panels -- G_dev + c0, Y_dev + c0, */
+/* the same ld and ldy --; the panels' results are the one call's bits.  The operation is local to a column: with the same   */
+/* perm on every rank, a rank of the columns layout calls this entry point on its own columns and no collective is needed,   */
+/* so no sharded entry point exists.                                                                                        */
+int byz_bucket_means_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                         const int32_t* perm_dev_or_null, int64_t s, float* Y_dev, int64_t ldy, void* stream);
+/* The same on a host matrix (Y_host: B x n_cols floats).  perm_host_or_null is checked: anything but a permutation of       */
+/* 0 .. n-1 is BYZ_E_INVALID.  Synchronous.                                                                                 */
+int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                          const int32_t* perm_host_or_null, int64_t s, float* Y_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
