@@ -1748,4 +1748,18 @@ int byz_selftest_lane_exchange_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_pa
     return launch_lane_selftest(ctx, out_dev, n_patterns_host, as_stream(stream));
 }
 
+int byz_gram_unit_table(int64_t n_rows, int32_t* units_host, int64_t capacity_units, int64_t* n_units) {
+    static_assert(kGramUnitWords == BYZ_GRAM_UNIT_WORDS, "the header describes GramUnit");
+    if (n_rows < 1 || n_rows > 32767ll * 128 || !n_units || capacity_units < 0) return BYZ_E_INVALID;
+    std::vector<GramUnit> units;
+    std::vector<int32_t> slot_slab;
+    build_gram_units(ceil_div(n_rows, 128), ceil_div(n_rows, 32), true, 1, 0, units, slot_slab);
+    *n_units = static_cast<int64_t>(units.size());
+    if (units_host) {
+        const int64_t count = *n_units < capacity_units ? *n_units : capacity_units;
+        std::memcpy(units_host, units.data(), static_cast<size_t>(count) * sizeof(GramUnit));
+    }
+    return BYZ_OK;
+}
+
 }  // extern "C"

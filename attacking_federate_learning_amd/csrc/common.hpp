@@ -110,9 +110,11 @@ struct byz_ctx {
     byz::Buffer plane_order;     // pre-split Gram: (256-row block, 128-row block) of every workgroup tile
     byz::Buffer spec_owner;      // speculative Bulyan loop: the row every (workgroup, thread) slot owns
     byz::Buffer split_redo;      // pre-split Gram: (chunk, row block) pairs whose sampled scale did not hold (count first)
-    std::vector<int32_t> plane_order_host;
+    std::vector<int32_t> plane_order_host;   // bf16x3: (bi, tj) pairs; f16x2: the unit table, then (ti, tj) of every sum slot
     int64_t plane_order_T = -1;
     int64_t plane_order_share = 1 * 65536 + 0;
+    int64_t plane_order_blocks = -2;         // f16x2: the live 32-row blocks the table's masks were made for
+    int64_t plane_units = 0, plane_sum_slots = 0;
     byz::Buffer row_signature;   // dedup: 64-bit signature of every row
     byz::Buffer unique_rows;     // dedup: the unique rows, ascending
     byz::Buffer row_map;         // dedup: position of every row's representative among the unique rows (+ scratch)
@@ -319,6 +321,24 @@ int launch_gram(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
 bool gram_planes_enabled();
 int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        double* slabs, int share_count, int share_index, uint8_t* owned_host, bool f16, hipStream_t stream);
+// One workgroup's work on one 8192-column chunk in the f16x2 tile kernel.  rb: the global 32-row block behind each of the
+// twelve row-block slots of an LDS stage.  Per wave: `where` = LDS slot of its first A row block | slot of its first B row
+// block << 8 | live 32 x 32 blocks of its 64 x 64 sub-tile (bit m32 * 2 + n32) << 16 | (row / 64) << 24 | (column / 64) << 25
+// of the sub-tile inside its slab; sum_slot: where the slab's level-1 sums of a chunk go; slab = ti | tj << 16.
+struct GramUnitWave {
+    uint32_t where;
+    int32_t sum_slot, slab;
+};
+struct GramUnit {
+    int32_t rb[12];
+    GramUnitWave wave[8];
+};
+constexpr int kGramUnitWords = static_cast<int>(sizeof(GramUnit) / sizeof(int32_t));
+// The unit table for t128 slabs per side of which n_blocks32 32-row blocks hold rows (negative: every block of a live slab
+// is multiplied), in launch order, and (ti, tj) of every sum slot (ti < 0: nobody writes it).  diagonal_units: the D1 / D2
+// units and one sum slot per lower-triangle slab; otherwise the (bi, tj) list, this share's part of it, two slots per tile.
+void build_gram_units(int64_t t128, int64_t n_blocks32, bool diagonal_units, int share_count, int share_index,
+                      std::vector<GramUnit>& units, std::vector<int32_t>& slot_slab);
 int launch_gram_share(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                       int share_count, int share_index, double* gram, hipStream_t stream, bool accumulate = false);
 // dedup.hip: identical rows found before the Gram

@@ -33,7 +33,8 @@
 // chunks of a tile add in chunk order into the tile's fp64 slabs: behind a ticket per tile inside the tile kernel, or
 // (f16x2, deferred) in chunk_reduce_kernel after it.  Rounds of one workgroup per CU start together.  bf16x3 keeps
 // gram.hip's schedule: a tile list in 8 x 8 super-blocks, a contiguous share of it per XCD.  f16x2 lists the tiles in bands
-// of four 256-row blocks and the XCDs claim runs of units from one counter.
+// of four 256-row blocks, as a table of units that says where every wave's operands and sub-tile are (build_gram_units: on
+// the diagonal two unit types of their own), and the XCDs claim runs of units from one counter.
 #include "common.hpp"
 
 #include <cstring>
@@ -674,9 +675,9 @@ template <int NBUF, bool DEFER>
 __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __restrict__ planes, int64_t n_steps,
                                                             const double* __restrict__ unscale, int64_t rows_pad,
                                                             double* __restrict__ partial, int n_tiles,
-                                                            const int2* __restrict__ tile_order, int n_chunks,
-                                                            int* __restrict__ tickets, int round_size, int run, int t128,
-                                                            int slab_live0, int n_blocks32,
+                                                            const GramUnit* __restrict__ units, int n_chunks,
+                                                            int* __restrict__ tickets, int round_size, int run,
+                                                            int slab_live0, int n_sum_slots,
                                                             int32_t* __restrict__ device_status,
                                                             float* __restrict__ chunk_sums,
                                                             float* __restrict__ ragged_sums) {
@@ -739,29 +740,20 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
         return;
     }
     const int t_list = unit - chunk * n_tiles;
-    const int2 tt = tile_order[t_list];
-    const int bi = __builtin_amdgcn_readfirstlane(tt.x);   // 256-row block of the A side
-    const int tj = __builtin_amdgcn_readfirstlane(tt.y);   // 128-row block of the B side
+    const GramUnit* __restrict__ my_unit = units + t_list;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int ti = 2 * bi + wr / 2;                    // this wave's slab row
-    const int row_in_slab = (wr % 2) * 64;             // and where its 64 x 64 sub-tile starts inside it
-    // live 32 x 32 blocks of the sub-tile (bit m32 * 2 + n32): the rule of gram_planes_kernel
-    unsigned live_blocks = 0;
-    if (tj <= ti && ti < t128 && n_blocks32 < 0) {
-        live_blocks = 15u;
-    } else if (tj <= ti && ti < t128) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const int rblk = ti * 4 + row_in_slab / 32 + m, cblk = tj * 4 + wc * 2 + n;
-                if (rblk < n_blocks32 && cblk <= rblk) live_blocks |= 1u << (m * 2 + n);
-            }
-    }
+    // this wave's entry of the unit table (build_gram_units): where its operands sit in a stage of LDS, which 32 x 32 blocks of
+    // its 64 x 64 sub-tile are live (bit m32 * 2 + n32) and where the sub-tile goes
+    const unsigned where = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(my_unit->wave[wave].where));
+    const int a_slot = static_cast<int>(where & 0xffu);           // LDS slot of its first A row block (two, consecutive)
+    const int b_slot = static_cast<int>((where >> 8) & 0xffu);    // ... of its first B row block (two, consecutive)
+    unsigned live_blocks = (where >> 16) & 0xffu;
+    const int row_in_slab = static_cast<int>((where >> 24) & 1u) * 64;   // where the sub-tile starts inside its slab
+    const int col_in_slab = static_cast<int>((where >> 25) & 1u) * 64;
+    const int sum_slot = __builtin_amdgcn_readfirstlane(my_unit->wave[wave].sum_slot);
     const bool live_wave = live_blocks != 0;
 
     const int step0 = chunk * kChunkSteps;
@@ -775,7 +767,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
     for (int i = 0; i < kPerWave; ++i) {
         const int q = wave + NW * i;
         const int rbl = q / PLANES, piece = q % PLANES;
-        const int64_t rb = rbl < 8 ? static_cast<int64_t>(bi) * 8 + rbl : static_cast<int64_t>(tj) * 4 + (rbl - 8);
+        const int64_t rb = __builtin_amdgcn_readfirstlane(my_unit->rb[rbl]);   // the global 32-row block of LDS slot rbl
         piece_off[i] = (((rb * n_steps + step0) * PLANES + piece) * 64) * 16;
     }
     const unsigned char* lane_base = reinterpret_cast<const unsigned char*>(planes) + lane * 16;
@@ -819,7 +811,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                if (((MASK >> ((m / 2) * 2)) & 3u) != 0) a.v[p][m] = frag_at(sp, 2 * wr + m / 2, m % 2, p);
+                if (((MASK >> ((m / 2) * 2)) & 3u) != 0) a.v[p][m] = frag_at(sp, a_slot + m / 2, m % 2, p);
     };
     auto read_b = [&](int sp, int half, BFrags& b, auto mask_c) __attribute__((always_inline)) {
         constexpr unsigned MASK = decltype(mask_c)::value;
@@ -827,7 +819,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int n = 0; n < 2; ++n) b.v[p][n] = frag_at(sp, 8 + 2 * wc + half, n, p);
+            for (int n = 0; n < 2; ++n) b.v[p][n] = frag_at(sp, b_slot + half, n, p);
         (void)MASK;
     };
     // the 24 MFMAs of one 32-column half: m h' + h m' + h h' per 16 x 16 block, term-major
@@ -926,7 +918,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
             const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                b1.v[g / 2][g % 2] = frag_at(sp, 8 + 2 * wc + 1, g % 2, g / 2);
+                b1.v[g / 2][g % 2] = frag_at(sp, b_slot + 1, g % 2, g / 2);
 #pragma unroll
                 for (int q = 6 * g; q < 6 * g + 6; ++q) {
                     const int t = q / 8, m = (q % 8) / 2, n = q % 2;
@@ -941,8 +933,8 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
                 dma_piece(2 * sp + NBUF + g / 3, g % 3);
 #pragma unroll
                 for (int r = 2 * g; r < 2 * g + 2; ++r) {
-                    if (r < 8) an.v[r / 4][r % 4] = frag_at(sp + 1, 2 * wr + (r % 4) / 2, (r % 4) % 2, r / 4);
-                    else b0.v[(r - 8) / 2][(r - 8) % 2] = frag_at(sp + 1, 8 + 2 * wc + 0, (r - 8) % 2, (r - 8) / 2);
+                    if (r < 8) an.v[r / 4][r % 4] = frag_at(sp + 1, a_slot + (r % 4) / 2, (r % 4) % 2, r / 4);
+                    else b0.v[(r - 8) / 2][(r - 8) % 2] = frag_at(sp + 1, b_slot, (r - 8) % 2, (r - 8) / 2);
                 }
 #pragma unroll
                 for (int q = 4 * g; q < 4 * g + 4; ++q) {
@@ -1006,21 +998,20 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
     auto block_live = [&](int m, int n) __attribute__((always_inline)) { return ((live_blocks >> ((m / 2) * 2 + n / 2)) & 1u) != 0; };
 
     if constexpr (DEFER) {
-        // this chunk's level-1 sums, as they are: slab `sel` of workgroup tile t_list; element (i, j) where the fp64 slab has
-        // it.  A chunk whose last MFMA chain has not been flushed (n_super not a multiple of kSuperFlush: only the ragged last
+        // this chunk's level-1 sums, as they are: slot `sum_slot` of the chunk (the table says which slab that is); element
+        // (i, j) where the fp64 slab has it.  A chunk whose last MFMA chain has not been flushed (n_super not a multiple of kSuperFlush: only the ragged last
         // chunk of the matrix) leaves that chain's sums in `ragged_sums`, for chunk_reduce_kernel to add as the in-kernel
         // update does: (double) level-1 + (double) chain.
         if (live_wave) {
-            const int sel = wr / 2;
             const bool unflushed = (n_super % kSuperFlush) != 0;
-            float* out = chunk_sums + ((static_cast<int64_t>(chunk) * n_tiles + t_list) * 2 + sel) * (kSlab * kSlab);
-            float* rag = ragged_sums + (static_cast<int64_t>(t_list) * 2 + sel) * (kSlab * kSlab);
+            float* out = chunk_sums + (static_cast<int64_t>(chunk) * n_sum_slots + sum_slot) * (kSlab * kSlab);
+            float* rag = ragged_sums + static_cast<int64_t>(sum_slot) * (kSlab * kSlab);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
                     if (!block_live(m, n)) continue;
-                    const int j = wc * 64 + 16 * n + (lane & 15);
+                    const int j = col_in_slab + 16 * n + (lane & 15);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int i = row_in_slab + 16 * m + 4 * (lane >> 4) + e;
@@ -1053,6 +1044,8 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
         if (tid == 0) atomicOr(device_status, kStatusLostTicket);
     } else if (live_wave) {
         const bool slab_live = chunk > 0 || slab_live0 != 0;
+        const int slab = __builtin_amdgcn_readfirstlane(my_unit->wave[wave].slab);
+        const int ti = slab & 0xffff, tj = slab >> 16;
         double* out = partial + (static_cast<int64_t>(ti) * (ti + 1) / 2 + tj) * (kSlab * kSlab);
         const double* un = unscale + static_cast<int64_t>(chunk) * rows_pad;
 #pragma unroll
@@ -1060,7 +1053,7 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 if (!block_live(m, n)) continue;
-                const int j = wc * 64 + 16 * n + (lane & 15);
+                const int j = col_in_slab + 16 * n + (lane & 15);
                 const double uj = un[static_cast<int64_t>(tj) * kSlab + j];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -1090,19 +1083,19 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
 // one dependent load per addition ran at 0.7 TB/s, 6 ms per launch).  Entries of blocks nobody computed are left alone.
 constexpr int kReduceRun = 8;
 __global__ __launch_bounds__(256) void chunk_reduce_kernel(const float* __restrict__ chunk_sums, const float* __restrict__ ragged_sums,
-                                                           int n_tiles, int n_chunks, int ragged_chunk,
-                                                           const int2* __restrict__ tile_order, const double* __restrict__ unscale,
+                                                           int n_sum_slots, int n_chunks, int ragged_chunk,
+                                                           const int2* __restrict__ slot_slab, const double* __restrict__ unscale,
                                                            int64_t rows_pad, double* __restrict__ partial, int slab_live0,
-                                                           int t128, int n_blocks32) {
+                                                           int n_blocks32) {
     typedef double f64x4 __attribute__((ext_vector_type(4)));
-    const int t_list = blockIdx.x >> 1, sel = blockIdx.x & 1;
-    const int2 tt = tile_order[t_list];
-    const int ti = 2 * tt.x + sel, tj = tt.y;
-    if (!(tj <= ti && ti < t128)) return;
+    const int slot = blockIdx.x;
+    const int2 tt = slot_slab[slot];
+    const int ti = tt.x, tj = tt.y;
+    if (ti < 0) return;     // (a slot of the (bi, tj) list whose slab lies above the diagonal or past the matrix)
     double* out = partial + (static_cast<int64_t>(ti) * (ti + 1) / 2 + tj) * (kSlab * kSlab);
-    const int64_t slab_stride = static_cast<int64_t>(n_tiles) * 2 * (kSlab * kSlab);
-    const float* in = chunk_sums + (static_cast<int64_t>(t_list) * 2 + sel) * (kSlab * kSlab);
-    const float* rag = ragged_sums + (static_cast<int64_t>(t_list) * 2 + sel) * (kSlab * kSlab);
+    const int64_t slab_stride = static_cast<int64_t>(n_sum_slots) * (kSlab * kSlab);
+    const float* in = chunk_sums + static_cast<int64_t>(slot) * (kSlab * kSlab);
+    const float* rag = ragged_sums + static_cast<int64_t>(slot) * (kSlab * kSlab);
     // blockIdx.y: a quarter of the slab's rows; a thread: row i, columns j .. j + 3 (all in one 32 x 32 block)
     const int i = static_cast<int>(blockIdx.y) * 32 + (threadIdx.x >> 3), j = (threadIdx.x & 7) * 4;
     for (int jb = 0; jb < kSlab; jb += 32) {
@@ -1153,6 +1146,99 @@ __global__ __launch_bounds__(256) void chunk_reduce_kernel(const float* __restri
 
 bool gram_planes_enabled() { return env_int("BYZ_GRAM_PLANES", 1) != 0; }
 
+// The units of the f16x2 tile kernel.  A 256-row block bi is a 4 x 4 grid of 64 x 64 sub-tiles (r, c) on the diagonal, ten of
+// them on or below it; a workgroup is eight waves (wr = wave / 2, wc = wave % 2) of one sub-tile each.
+//   plain  (bi, tj):  LDS slots 0..7 = the block's eight 32-row blocks, 8..11 = slab tj's four; wave (wr, wc) reads A from
+//                     slots 2 wr, 2 wr + 1 and B from 8 + 2 wc, 9 + 2 wc: sub-tile (wr % 2, wc) of slab (2 bi + wr / 2, tj).
+//   D1     (bi, 2 bi): the plain unit, whose wave (0, 1) -- strictly above the diagonal -- takes sub-tile (2, 2) instead: A AND B
+//                     from slots 4, 5 (A and B operands are one image layout), the top left of slab (2 bi + 1, 2 bi + 1).
+//   D2     (three consecutive bi):  slots 4 k .. 4 k + 3 = row blocks 4..7 of the k-th block; per block one full wave on
+//                     sub-tile (3, 2) (A slots 4 k + 2, B slots 4 k) and one mask-13 wave on (3, 3) (A and B slots 4 k + 2).
+//                     The full waves are waves 0, 1, 2: three SIMDs; the mask-13 ones 3, 7, 5.
+// D1 and D2 replace the plain units (bi, 2 bi) and (bi, 2 bi + 1), of which the second had five idle waves, three of them
+// beside a full one.  A D2 stands in the list where the (bi, 2 bi + 1) of its last block stood.  A last block with one slab
+// only (odd t128) has no (3, *) sub-tiles and joins no D2.
+void build_gram_units(int64_t t128, int64_t n_blocks32, bool diagonal_units, int share_count, int share_index,
+                      std::vector<GramUnit>& units, std::vector<int32_t>& slot_slab) {
+    units.clear();
+    slot_slab.clear();
+    const int64_t t256 = ceil_div(t128, 2);
+    // live 32 x 32 blocks (bit m32 * 2 + n32) of the sub-tile at (64 row64, 64 col64) of slab (ti, tj)
+    auto live_mask = [&](int64_t ti, int64_t tj, int row64, int col64) -> uint32_t {
+        if (!(tj <= ti && ti < t128)) return 0u;
+        if (n_blocks32 < 0) return 15u;      // the slab-granular rule
+        uint32_t mask = 0;
+        for (int m = 0; m < 2; ++m)
+            for (int n = 0; n < 2; ++n) {
+                const int64_t rblk = ti * 4 + row64 * 2 + m, cblk = tj * 4 + col64 * 2 + n;
+                if (rblk < n_blocks32 && cblk <= rblk) mask |= 1u << (m * 2 + n);
+            }
+        return mask;
+    };
+    auto set_wave = [&](GramUnit& u, int wave, int a_slot, int b_slot, int64_t ti, int64_t tj, int row64, int col64,
+                        int64_t sum_slot) {
+        const uint32_t mask = live_mask(ti, tj, row64, col64);
+        GramUnitWave& w = u.wave[wave];
+        w.where = static_cast<uint32_t>(a_slot) | static_cast<uint32_t>(b_slot) << 8 | mask << 16 |
+                  static_cast<uint32_t>(row64) << 24 | static_cast<uint32_t>(col64) << 25;
+        w.sum_slot = mask != 0 ? static_cast<int32_t>(sum_slot) : 0;
+        w.slab = mask != 0 ? static_cast<int32_t>(ti | tj << 16) : 0;
+    };
+    auto slab_slot = [](int64_t ti, int64_t tj) { return ti * (ti + 1) / 2 + tj; };
+    int64_t position = 0;
+    auto plain = [&](int64_t bi, int64_t tj, bool d1) {
+        if (position++ % share_count != share_index) return;
+        const int64_t t_list = static_cast<int64_t>(units.size());
+        GramUnit u{};
+        for (int s = 0; s < 12; ++s) u.rb[s] = static_cast<int32_t>(s < 8 ? bi * 8 + s : tj * 4 + (s - 8));
+        for (int wave = 0; wave < 8; ++wave) {
+            const int wr = wave / 2, wc = wave % 2;
+            const int64_t ti = 2 * bi + wr / 2;
+            set_wave(u, wave, 2 * wr, 8 + 2 * wc, ti, tj, wr % 2, wc, diagonal_units ? slab_slot(ti, tj) : 2 * t_list + wr / 2);
+        }
+        if (d1) set_wave(u, 1, 4, 4, 2 * bi + 1, 2 * bi + 1, 0, 0, slab_slot(2 * bi + 1, 2 * bi + 1));
+        units.push_back(u);
+        if (!diagonal_units)
+            for (int sel = 0; sel < 2; ++sel) {
+                const int64_t ti = 2 * bi + sel;
+                const bool live = tj <= ti && ti < t128;
+                slot_slab.push_back(static_cast<int32_t>(live ? ti : -1));
+                slot_slab.push_back(static_cast<int32_t>(live ? tj : -1));
+            }
+    };
+    auto d2 = [&](int64_t first, int64_t count) {
+        static const int partial_wave[3] = {3, 7, 5};
+        GramUnit u{};
+        for (int s = 0; s < 12; ++s) u.rb[s] = static_cast<int32_t>(first * 8 + 4);   // (a slot nobody reads still gets its DMA)
+        for (int64_t k = 0; k < count; ++k) {
+            const int64_t bi = first + k, t = 2 * bi + 1;
+            for (int s = 0; s < 4; ++s) u.rb[4 * k + s] = static_cast<int32_t>(bi * 8 + 4 + s);
+            set_wave(u, static_cast<int>(k), static_cast<int>(4 * k + 2), static_cast<int>(4 * k), t, t, 1, 0, slab_slot(t, t));
+            set_wave(u, partial_wave[k], static_cast<int>(4 * k + 2), static_cast<int>(4 * k + 2), t, t, 1, 1, slab_slot(t, t));
+        }
+        units.push_back(u);
+    };
+    const int64_t full_blocks = t128 / 2;     // 256-row blocks with both slabs
+    for (int64_t b0 = 0; b0 < t256; b0 += 4)
+        for (int64_t tj = 0; tj < t128 && tj <= 2 * (b0 + 3) + 1; ++tj)
+            for (int64_t bi = b0; bi < b0 + 4 && bi < t256; ++bi) {
+                if (tj > 2 * bi + 1) continue;
+                if (!diagonal_units) {
+                    plain(bi, tj, false);
+                } else if (tj == 2 * bi + 1) {
+                    if (bi % 3 == 2 || bi == full_blocks - 1) d2(bi - bi % 3, bi % 3 + 1);
+                } else {
+                    plain(bi, tj, tj == 2 * bi);
+                }
+            }
+    if (diagonal_units)
+        for (int64_t ti = 0; ti < t128; ++ti)
+            for (int64_t tj = 0; tj <= ti; ++tj) {
+                slot_slab.push_back(static_cast<int32_t>(ti));
+                slot_slab.push_back(static_cast<int32_t>(tj));
+            }
+}
+
 // Fills `slabs` (gram.hip's fp64 slab format: one 128 x 128 slab per lower-triangle tile ti (ti + 1) / 2 + tj) with the
 // Gram of the n_rows logical rows G[row_index[r]]; with share_count > 1 only this share's tiles (owned[] says which).
 // f16 = true: the f16x2 arithmetic, false: bf16x3 (bitwise gram.hip's split mode).
@@ -1166,44 +1252,75 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     // (chunk, tile) units to the XCDs.  bf16x3: 8 x 8 super-blocks of slabs = 4 x 8 workgroup tiles, a contiguous share of the
     // list per XCD (the rounds of an XCD then straddle two chunks and two or three super-blocks: 106 GB through the fabric per
     // 1M-column launch at N = 4000 if every line were shared perfectly inside a round, against 70 GB for the bands;
-    // scripts/gram_order_footprint.py, EXPERIMENTS.md G8).  The key tells the two lists apart: one engine may alternate.
-    const int64_t order_key = static_cast<int64_t>(f16 ? 1 : 0) * (1ll << 40) + share_count * 65536 + share_index;
-    if (ctx->plane_order_T != t128 || ctx->plane_order_share != order_key) {
-        ctx->plane_order_host.clear();
-        int64_t position = 0;
-        auto push = [&](int64_t bi, int64_t tj) {
-            if (position++ % share_count != share_index) return;
-            ctx->plane_order_host.push_back(static_cast<int32_t>(bi));
-            ctx->plane_order_host.push_back(static_cast<int32_t>(tj));
-        };
+    // scripts/gram_order_footprint.py, EXPERIMENTS.md G8).  The key tells the lists apart: one engine may alternate.
+    // BYZ_GRAM_DEFER=0: round 4's in-kernel slab update (the bitwise comparison of the tests)
+    bool defer = f16 && env_int("BYZ_GRAM_DEFER", 1) != 0;
+    const int n_blocks32 = env_int("BYZ_GRAM_BLOCK_SKIP", 1) != 0 ? static_cast<int>(ceil_div(n_rows, 32)) : -1;
+    // f16x2 keeps the list as a table of units (build_gram_units).  The diagonal units need the deferred update (the ticket of
+    // the in-kernel update orders the chunks of a (bi, tj) tile), the whole triangle (a share owns (bi, tj) tiles) and the
+    // block-granular rule (under the slab-granular one no wave of a diagonal tile is idle).
+    auto ensure_list = [&](bool diagonal_units) -> int {
+        const int64_t order_key = static_cast<int64_t>((f16 ? 1 : 0) + (diagonal_units ? 2 : 0)) * (1ll << 40) + share_count * 65536 + share_index;
+        const int64_t blocks_key = f16 ? n_blocks32 : -2;
+        if (ctx->plane_order_T != t128 || ctx->plane_order_share != order_key || ctx->plane_order_blocks != blocks_key) {
+            ctx->plane_order_host.clear();
+            if (f16) {
+                if (t128 > 0x7fff) {
+                    set_error("gram: more than 32767 slabs per side");
+                    return BYZ_E_UNSUPPORTED;
+                }
+                std::vector<GramUnit> units;
+                std::vector<int32_t> slot_slab;
+                build_gram_units(t128, n_blocks32, diagonal_units, share_count, share_index, units, slot_slab);
+                ctx->plane_units = static_cast<int64_t>(units.size());
+                ctx->plane_sum_slots = static_cast<int64_t>(slot_slab.size() / 2);
+                ctx->plane_order_host.resize(units.size() * kGramUnitWords);
+                if (!units.empty()) std::memcpy(ctx->plane_order_host.data(), units.data(), units.size() * sizeof(GramUnit));
+                ctx->plane_order_host.insert(ctx->plane_order_host.end(), slot_slab.begin(), slot_slab.end());
+            } else {
+                int64_t position = 0;
+                auto push = [&](int64_t bi, int64_t tj) {
+                    if (position++ % share_count != share_index) return;
+                    ctx->plane_order_host.push_back(static_cast<int32_t>(bi));
+                    ctx->plane_order_host.push_back(static_cast<int32_t>(tj));
+                };
+                const int64_t S = ceil_div(t128, 8);
+                for (int64_t I = 0; I < S; ++I)
+                    for (int64_t J = 0; J <= I; ++J)
+                        for (int64_t bi = I * 4; bi < I * 4 + 4 && bi < t256; ++bi)
+                            for (int64_t tj = J * 8; tj < J * 8 + 8 && tj <= 2 * bi + 1 && tj < t128; ++tj) push(bi, tj);
+                ctx->plane_units = static_cast<int64_t>(ctx->plane_order_host.size() / 2);
+                ctx->plane_sum_slots = 0;
+            }
+            BYZ_TRY(ctx->plane_order.ensure(ctx->plane_order_host.size() * sizeof(int32_t) + 16));
+            BYZ_HIP(hipMemcpyAsync(ctx->plane_order.ptr, ctx->plane_order_host.data(),
+                                   ctx->plane_order_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            BYZ_HIP(hipStreamSynchronize(stream));
+            ctx->plane_order_T = t128;
+            ctx->plane_order_share = order_key;
+            ctx->plane_order_blocks = blocks_key;
+        }
+        return BYZ_OK;
+    };
+    const bool diagonal_units = defer && share_count == 1 && n_blocks32 >= 0;
+    BYZ_TRY(ensure_list(diagonal_units));
+    int64_t n_tiles = ctx->plane_units;
+    int64_t n_sum_slots = ctx->plane_sum_slots;
+    const int32_t* slot_slab_host = ctx->plane_order_host.data() + n_tiles * kGramUnitWords;   // (f16x2)
+    if (owned_host != nullptr) {
         if (f16) {
-            // (the bands cut into column panels of 16 / 24 / 32 / 40 slabs, so that at N = 10,000 -- a chunk of planes is 335 MB --
-            // the rounds in flight stay inside the 256 MB Infinity Cache: measured, 91.7 -> 91.5 ms per launch: nothing; removed)
-            for (int64_t b0 = 0; b0 < t256; b0 += 4)
-                for (int64_t tj = 0; tj < t128 && tj <= 2 * (b0 + 3) + 1; ++tj)
-                    for (int64_t bi = b0; bi < b0 + 4 && bi < t256; ++bi)
-                        if (tj <= 2 * bi + 1) push(bi, tj);
+            for (int64_t s = 0; s < n_sum_slots; ++s) {
+                const int64_t ti = slot_slab_host[2 * s], tj = slot_slab_host[2 * s + 1];
+                if (ti >= 0) owned_host[ti * (ti + 1) / 2 + tj] = 1;
+            }
         } else {
-            const int64_t S = ceil_div(t128, 8);
-            for (int64_t I = 0; I < S; ++I)
-                for (int64_t J = 0; J <= I; ++J)
-                    for (int64_t bi = I * 4; bi < I * 4 + 4 && bi < t256; ++bi)
-                        for (int64_t tj = J * 8; tj < J * 8 + 8 && tj <= 2 * bi + 1 && tj < t128; ++tj) push(bi, tj);
+            for (int64_t t = 0; t < n_tiles; ++t) {
+                const int64_t bi = ctx->plane_order_host[2 * t], tj = ctx->plane_order_host[2 * t + 1];
+                for (int64_t ti = 2 * bi; ti < 2 * bi + 2 && ti < t128; ++ti)
+                    if (tj <= ti) owned_host[ti * (ti + 1) / 2 + tj] = 1;
+            }
         }
-        BYZ_TRY(ctx->plane_order.ensure(ctx->plane_order_host.size() * sizeof(int32_t) + 16));
-        BYZ_HIP(hipMemcpyAsync(ctx->plane_order.ptr, ctx->plane_order_host.data(),
-                               ctx->plane_order_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        BYZ_HIP(hipStreamSynchronize(stream));
-        ctx->plane_order_T = t128;
-        ctx->plane_order_share = order_key;
     }
-    const int64_t n_tiles = static_cast<int64_t>(ctx->plane_order_host.size() / 2);
-    if (owned_host != nullptr)
-        for (int64_t t = 0; t < n_tiles; ++t) {
-            const int64_t bi = ctx->plane_order_host[2 * t], tj = ctx->plane_order_host[2 * t + 1];
-            for (int64_t ti = 2 * bi; ti < 2 * bi + 2 && ti < t128; ++ti)
-                if (tj <= ti) owned_host[ti * (ti + 1) / 2 + tj] = 1;
-        }
     if (n_tiles == 0) return BYZ_OK;
 
     // super-chunk: as many 8192-column chunks as the plane budget holds
@@ -1231,22 +1348,25 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
         unscale = ctx->plane_unscale.as<double>();
     }
     u32x4* planes = ctx->gram_planes.as<u32x4>();
-    // BYZ_GRAM_DEFER=0: round 4's in-kernel slab update (the bitwise comparison of the tests)
-    bool defer = f16 && env_int("BYZ_GRAM_DEFER", 1) != 0;
     float* chunk_sums = nullptr;
     float* ragged_sums = nullptr;
     if (defer) {
-        // fp32 level-1 sums of every (chunk, tile, slab) of a launch + one more slab pair per tile for an unflushed chain
+        // fp32 level-1 sums of every (chunk, sum slot) of a launch + one more slab per slot for an unflushed chain
         // (4.3 GB at configs[3], 10 GB at configs[4]'s slice).  Where that does not fit beside the matrix the update stays
         // inside the tile kernel: slower, the same bits.
-        const size_t per_chunk = static_cast<size_t>(n_tiles) * 2 * kSlab * kSlab * sizeof(float);
+        const size_t per_chunk = static_cast<size_t>(n_sum_slots) * kSlab * kSlab * sizeof(float);
         const size_t want = per_chunk * static_cast<size_t>(chunks_per_sc + 1);
         size_t free_now = 0, total_now = 0;
         BYZ_HIP(hipMemGetInfo(&free_now, &total_now));
         if (want > ctx->gram_chunk_sums.bytes && want - ctx->gram_chunk_sums.bytes > free_now / 2) defer = false;
+        if (!defer && diagonal_units) {   // the in-kernel update runs on the (bi, tj) list
+            BYZ_TRY(ensure_list(false));
+            n_tiles = ctx->plane_units;
+            n_sum_slots = ctx->plane_sum_slots;
+        }
     }
     if (defer) {
-        const size_t per_chunk = static_cast<size_t>(n_tiles) * 2 * kSlab * kSlab * sizeof(float);
+        const size_t per_chunk = static_cast<size_t>(n_sum_slots) * kSlab * kSlab * sizeof(float);
         BYZ_TRY(ctx->gram_chunk_sums.ensure(per_chunk * static_cast<size_t>(chunks_per_sc + 1)));
         chunk_sums = ctx->gram_chunk_sums.as<float>();
         ragged_sums = chunk_sums + (per_chunk / sizeof(float)) * static_cast<size_t>(chunks_per_sc);
@@ -1258,7 +1378,6 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     const int round_size = env_int("BYZ_GRAM_ROUND", ctx->num_cus / 8);   // one workgroup per CU
     // f16x2: runs of whole rounds (one workgroup per CU of an XCD), claimed by the XCDs as they get to them
     const int run = round_size > 0 ? round_size : ctx->num_cus / 8;
-    const int n_blocks32 = env_int("BYZ_GRAM_BLOCK_SKIP", 1) != 0 ? static_cast<int>(ceil_div(n_rows, 32)) : -1;
     const int64_t per_xcd = ceil_div(n_tiles, 8);
     for (int64_t sc = 0; sc < n_sc; ++sc) {
         const int64_t k0 = sc * sc_cols;
@@ -1314,26 +1433,26 @@ int launch_gram_planes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
                 set_error("gram: grid too large");
                 return BYZ_E_UNSUPPORTED;
             }
-            const int2* tile_order = ctx->plane_order.as<int2>();
             const int slab_live0 = sc > 0 ? 1 : 0;
             if (!f16) {
                 gram_planes_kernel<4><<<static_cast<unsigned>(grid), kThreads, lds_bytes, stream>>>(
-                    planes, n_steps, slabs, static_cast<int>(n_tiles), tile_order, static_cast<int>(n_chunks), tickets,
+                    planes, n_steps, slabs, static_cast<int>(n_tiles), ctx->plane_order.as<int2>(), static_cast<int>(n_chunks), tickets,
                     round_size, static_cast<int>(t128), slab_live0, n_blocks32, device_status_word(ctx));
             } else {
                 kernel16<<<static_cast<unsigned>(grid), kThreads, lds_bytes, stream>>>(
-                    planes, n_steps, unscale, rows_pad, slabs, static_cast<int>(n_tiles), tile_order, static_cast<int>(n_chunks),
-                    tickets, round_size, run, static_cast<int>(t128), slab_live0, n_blocks32, device_status_word(ctx),
-                    chunk_sums, ragged_sums);
+                    planes, n_steps, unscale, rows_pad, slabs, static_cast<int>(n_tiles), ctx->plane_order.as<GramUnit>(),
+                    static_cast<int>(n_chunks), tickets, round_size, run, slab_live0, static_cast<int>(n_sum_slots),
+                    device_status_word(ctx), chunk_sums, ragged_sums);
             }
             BYZ_TRY(check_launch("gram_planes_kernel"));
         }
         if (defer) {
             KernelTimer t(ctx, BYZ_K_GRAM_REDUCE, stream);
             const int ragged_chunk = (n_steps % kChunkSteps) % kFlushSteps != 0 ? static_cast<int>(n_chunks) - 1 : -1;
-            chunk_reduce_kernel<<<dim3(static_cast<unsigned>(2 * n_tiles), 4), 256, 0, stream>>>(
-                chunk_sums, ragged_sums, static_cast<int>(n_tiles), static_cast<int>(n_chunks), ragged_chunk,
-                ctx->plane_order.as<int2>(), unscale, rows_pad, slabs, sc > 0 ? 1 : 0, static_cast<int>(t128), n_blocks32);
+            const int2* slot_slab = reinterpret_cast<const int2*>(ctx->plane_order.as<GramUnit>() + n_tiles);
+            chunk_reduce_kernel<<<dim3(static_cast<unsigned>(n_sum_slots), 4), 256, 0, stream>>>(
+                chunk_sums, ragged_sums, static_cast<int>(n_sum_slots), static_cast<int>(n_chunks), ragged_chunk, slot_slab,
+                unscale, rows_pad, slabs, sc > 0 ? 1 : 0, n_blocks32);
             BYZ_TRY(check_launch("chunk_reduce_kernel"));
         }
     }

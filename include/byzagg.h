@@ -729,6 +729,19 @@ const char* byz_kernel_name(int kernel);
 int byz_selftest_lane_exchange_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_patterns_host,
                                    void* stream);
 
+/* ---- the unit table of the long-K Gram's f16x2 tile kernel (host arithmetic; tests and scripts) -------------------- */
+/* What byz_gram_dev hands its tile kernel for a matrix of n_rows rows (the whole triangle, deferred slab update): one   */
+/* unit per workgroup and 8192-column chunk, in launch order, BYZ_GRAM_UNIT_WORDS int32 each:                            */
+/*   [0..11]    the global 32-row block behind each of the twelve row-block slots of an LDS stage                        */
+/*   [12 + 3w]  wave w: LDS slot of its first A row block | slot of its first B row block << 8 | live 32 x 32 blocks of  */
+/*              its 64 x 64 sub-tile (bit 2 m + n: rows 32 m.., columns 32 n..) << 16 | (row / 64) << 24 |               */
+/*              (column / 64) << 25 of the sub-tile inside its 128 x 128 slab                                            */
+/*   [13 + 3w]  the slab as ti (ti + 1) / 2 + tj        [14 + 3w]  the slab as ti | tj << 16   (both 0 for an idle wave) */
+/* units_host: NULL, or room for capacity_units units; n_units receives the count either way.  No GPU is touched.       */
+/* n_rows < 1 or more than 32767 * 128: BYZ_E_INVALID.                                                                   */
+#define BYZ_GRAM_UNIT_WORDS 36
+int byz_gram_unit_table(int64_t n_rows, int32_t* units_host, int64_t capacity_units, int64_t* n_units);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,3 +111,41 @@ if __name__ == '__main__':
         for name, T in (('super-blocks', tiles(n)), ('bands of 4', order_band(n)), ('panels 32 x bands', order_panels(n)), ('panels 16 x bands', order_panels(n, 16)),('panels 24 x bands', order_panels(n, 24))):
             assert sorted(T) == sorted(tiles(n))
             print('  N = %5d  %-18s  %6.1f  /  %6.1f   (unique planes %.1f GB)' % (n, name, floor_global(T, nch), hbm_bytes(T, nch), -(-n // 128) * 128 * cols * 4 / 1e9))
+
+
+def order_units(n, band=4):
+    """The unit list of build_gram_units (the D1 / D2 units on the diagonal): every unit as the set of 128-row blocks it loads."""
+    t128 = -(-n // 128); t256 = -(-t128 // 2); full = t128 // 2
+    out = []
+    for b0 in range(0, t256, band):
+        for tj in range(0, min(2 * (b0 + band - 1) + 2, t128)):
+            for bi in range(b0, min(b0 + band, t256)):
+                if tj > 2 * bi + 1:
+                    continue
+                if tj == 2 * bi + 1:       # where the D2 of the blocks bi - bi % 3 .. bi stands
+                    if bi % 3 == 2 or bi == full - 1:
+                        out.append({2 * b + 1 for b in range(bi - bi % 3, bi + 1)})
+                else:                      # plain, or D1 (tj == 2 bi: no row block beyond the block's own two)
+                    out.append({2 * bi, 2 * bi + 1, tj})
+    return out
+
+
+def floor_of_sets(U, nch, R=32):
+    """(GB through the fabric per launch, most 128-row blocks one run of R units touches)"""
+    nu = len(U); units = nu * nch; tot = 0; worst = 0
+    for r0 in range(0, units, R):
+        s = set()
+        for u in range(r0, min(r0 + R, units)):
+            for rb in U[u % nu]: s.add((rb, u // nu))
+        tot += len(s); worst = max(worst, len(s))
+    return tot * 128 * 8192 * 4 / 1e9, worst
+
+
+if __name__ == '__main__':
+    print('\nthe unit list (D1 / D2 on the diagonal) against the (bi, tj) list in bands of 4: units, GB per launch, most row blocks per run')
+    for n, cols in ((4000, 1000448), (10000, 401408)):
+        nch = cols // 8192
+        old = [set(r for _, r in rows_of(t)) for t in order_band(n)]
+        for name, U in (('(bi, tj) list', old), ('unit list', order_units(n))):
+            gb, worst = floor_of_sets(U, nch)
+            print('  N = %5d  %-14s %5d  %6.1f  %3d' % (n, name, len(U), gb, worst))
