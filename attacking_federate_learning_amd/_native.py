@@ -26,6 +26,15 @@ class CclipParams(ctypes.Structure):
     _fields_ = [('tau', ctypes.c_double), ('iters', c_i64)]
 
 
+SIGNGUARD_MAX_SAMPLES = 1024      # BYZ_SIGNGUARD_MAX_SAMPLES
+
+
+class SignGuardParams(ctypes.Structure):
+    """byz_signguard_params: SignGuard's census window, norm bounds, bandwidth (0: estimated) and sample size."""
+    _fields_ = [('window_start', c_i64), ('window_len', c_i64), ('lower', ctypes.c_double), ('upper', ctypes.c_double),
+                ('bandwidth', ctypes.c_double), ('n_sample', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -111,6 +120,14 @@ _PROTOTYPES = {
     'byz_fltrust_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i32), _P(ctypes.c_double)],
     'byz_fltrust_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_fltrust_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_row_signs_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_signguard_select_dev': [c_vp, c_vp, c_vp, c_i64, _P(SignGuardParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_signguard_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(SignGuardParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_signguard_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64), _P(ctypes.c_double),
+                           _P(ctypes.c_double)],
+    'byz_signguard_host': [c_vp, c_vp, c_i64, c_i64, _P(SignGuardParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_signguard_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(SignGuardParams), c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp],
     'byz_nnm_neighbours_dev': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_nnm_mix_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     'byz_nnm_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],

@@ -992,6 +992,123 @@ int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows
     return BYZ_OK;
 }
 
+// ---- SignGuard (Xu, Huang, Song and Lan, ICDCS 2022; beyond the reference) -------------------------------------------------
+namespace {
+
+int check_signguard(const byz_signguard_params* p, int64_t n_rows, const int32_t* sample, const char* who) {
+    if (!p) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_row_ceiling(who, n_rows));
+    if (!(p->lower >= 0.0) || !(p->upper > p->lower) || !(p->bandwidth >= 0.0) || p->window_start < 0 || p->window_len < 1) {
+        set_error("%s: lower = %g must be >= 0, upper = %g > lower, bandwidth = %g >= 0, window_start = %lld >= 0, window_len = "
+                  "%lld >= 1", who, p->lower, p->upper, p->bandwidth, (long long)p->window_start, (long long)p->window_len);
+        return BYZ_E_INVALID;
+    }
+    if (!(p->bandwidth > 0.0) && (!sample || p->n_sample < 1 || p->n_sample > BYZ_SIGNGUARD_MAX_SAMPLES || p->n_sample > n_rows)) {
+        set_error("%s: the bandwidth is estimated from 1..min(n_rows, %d) sampled rows, got %lld (sample %p)", who,
+                  BYZ_SIGNGUARD_MAX_SAMPLES, (long long)p->n_sample, (const void*)sample);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column and [win_start, win_start + win_len) is the window itself.
+// Nothing here waits for the device.  Two passes over G: the census, then the sum over the kept rows.
+int signguard(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_signguard_params* p, int64_t win_start,
+              int64_t win_len, const int32_t* sample, byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* keep,
+              double* weights, int32_t* labels, void* stream) {
+    hipStream_t s = as_stream(stream);
+    SgScratch t;
+    BYZ_TRY(signguard_workspace(ctx, n, n_cols, &t));
+    ctx->signguard_stream = s;
+    BYZ_TRY(launch_row_signs(ctx, t, G, n, n_cols, ld, win_start, win_len, nullptr, nullptr, t.pznq, s));
+    if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.pznq, 4 * n, stream, "signguard (counts and norms)"));
+    BYZ_TRY(launch_signguard_select(ctx, t, t.pznq, n, p->window_len, p->lower, p->upper, p->bandwidth, sample, p->n_sample,
+                                    keep ? keep : t.keep, t.w, labels ? labels : t.labels, nullptr, s));
+    const double* K = reinterpret_cast<const double*>(geomed_words(ctx) + kSgKeptF64);
+    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, t.w, K, out, s));
+    if (weights != nullptr)
+        BYZ_HIP(hipMemcpyAsync(weights, t.w, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_row_signs_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t window_start,
+                      int64_t window_len, int64_t* counts, double* q, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_signs"));
+    BYZ_REQUIRE(counts && q, "row_signs: null output");
+    BYZ_TRY(check_row_ceiling("row_signs", n_rows));
+    SgScratch t;
+    BYZ_TRY(signguard_workspace(ctx, n_rows, n_cols, &t));
+    return launch_row_signs(ctx, t, G, n_rows, n_cols, ld, window_start, window_len, reinterpret_cast<long long*>(counts), q, nullptr,
+                            as_stream(stream));
+}
+
+int byz_signguard_select_dev(byz_ctx* ctx, const int64_t* counts, const double* q, int64_t n_rows, const byz_signguard_params* params,
+                             const int32_t* sample, int32_t* keep, double* weights, int32_t* labels, double* mk, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(counts && q && n_rows > 0, "signguard_select: null counts or norms, or no rows");
+    BYZ_TRY(check_signguard(params, n_rows, sample, "signguard_select"));
+    hipStream_t s = as_stream(stream);
+    SgScratch t;
+    BYZ_TRY(signguard_workspace(ctx, n_rows, 0, &t));
+    ctx->signguard_stream = s;
+    BYZ_TRY(launch_signguard_counts_f64(ctx, reinterpret_cast<const long long*>(counts), q, n_rows, t.pznq, s));
+    return launch_signguard_select(ctx, t, t.pznq, n_rows, params->window_len, params->lower, params->upper, params->bandwidth, sample,
+                                   params->n_sample, keep ? keep : t.keep, weights ? weights : t.w, labels ? labels : t.labels, mk, s);
+}
+
+int byz_signguard_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_signguard_params* params,
+                      const int32_t* sample, float* out, int32_t* keep, double* weights, int32_t* labels, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "signguard"));
+    BYZ_REQUIRE(out, "signguard: null output");
+    BYZ_TRY(check_signguard(params, n_rows, sample, "signguard"));
+    BYZ_REQUIRE(params->window_start <= n_cols && params->window_len <= n_cols - params->window_start,
+                "signguard: the window [%lld, %lld + %lld) is outside the %lld columns", (long long)params->window_start,
+                (long long)params->window_start, (long long)params->window_len, (long long)n_cols);
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "signguard"));
+    return signguard(ctx, G, n_rows, n_cols, ld, params, params->window_start, params->window_len, sample, nullptr, nullptr, out, keep,
+                     weights, labels, stream);
+}
+
+int byz_signguard_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                              const byz_signguard_params* params, int64_t local_window_start, int64_t local_window_len,
+                              const int32_t* sample, byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* keep,
+                              double* weights, int32_t* labels, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "signguard_sharded"));
+    BYZ_REQUIRE(out && allreduce, "signguard_sharded: null output or all-reduce");
+    BYZ_TRY(check_signguard(params, n_rows, sample, "signguard_sharded"));
+    BYZ_REQUIRE(local_window_start >= 0 && local_window_len >= 0 && local_window_start <= n_cols &&
+                    local_window_len <= n_cols - local_window_start && local_window_len <= params->window_len,
+                "signguard_sharded: the local window [%lld, %lld + %lld) is outside the slice's %lld columns or longer than the "
+                "global window", (long long)local_window_start, (long long)local_window_start, (long long)local_window_len,
+                (long long)n_cols);
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "signguard_sharded"));
+    return signguard(ctx, G, n_rows, n_cols, ld, params, local_window_start, local_window_len, sample, allreduce, user, out, keep,
+                     weights, labels, stream);
+}
+
+int byz_signguard_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* norm_failed_rows, int64_t* outside_rows, int64_t* clusters,
+                       int64_t* seeds, double* bandwidth, double* median_norm) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->signguard_stream));   // synchronises the last call's stream
+    if (kept_rows) *kept_rows = words[kSgKept];
+    if (norm_failed_rows) *norm_failed_rows = words[kSgNormFailed];
+    if (outside_rows) *outside_rows = words[kSgOutside];
+    if (clusters) *clusters = words[kSgClusters];
+    if (seeds) *seeds = words[kSgSeeds];
+    if (bandwidth) std::memcpy(bandwidth, words + kSgBandwidth, sizeof(double));
+    if (median_norm) std::memcpy(median_norm, words + kSgMedian, sizeof(double));
+    return BYZ_OK;
+}
+
 // ---- nearest-neighbour mixing (Allouah et al., AISTATS 2023; beyond the reference) -----------------------------------------
 namespace {
 
@@ -1595,6 +1712,42 @@ int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t 
     BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
     if (trust_host) BYZ_HIP(hipMemcpyAsync(trust_host, trust, row_bytes, hipMemcpyDeviceToHost, s));
     if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
+    return check_small(ctx, s);
+}
+
+int byz_signguard_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_signguard_params* params,
+                       const int32_t* sample_host, float* out_host, int32_t* keep_host, double* weights_host, int32_t* labels_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "signguard"));
+    BYZ_REQUIRE(out_host, "signguard: null output");
+    BYZ_TRY(check_signguard(params, n_rows, sample_host, "signguard"));
+    const bool estimate = !(params->bandwidth > 0.0);
+    if (estimate) {
+        std::vector<char> seen(static_cast<size_t>(n_rows), 0);
+        for (int64_t j = 0; j < params->n_sample; ++j) {
+            const int32_t r = sample_host[j];
+            BYZ_REQUIRE(r >= 0 && r < n_rows && !seen[r], "signguard: sample[%lld] = %d is out of range or a repeat", (long long)j, r);
+            seen[r] = 1;
+        }
+    }
+    hipStream_t s = nullptr;
+    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the weights 8-byte aligned)
+    const size_t row_bytes = static_cast<size_t>(n_rows) * sizeof(double), flag_bytes = static_cast<size_t>(n_rows) * sizeof(int32_t);
+    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + row_bytes + 2 * flag_bytes, s));
+    SgScratch t;
+    BYZ_TRY(signguard_workspace(ctx, n_rows, n_cols, &t));
+    if (estimate)
+        BYZ_HIP(hipMemcpyAsync(t.sample, sample_host, static_cast<size_t>(params->n_sample) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    float* out = ctx->stage_out.as<float>();
+    double* weights = reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes);
+    int32_t* keep = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + out_bytes + row_bytes);
+    int32_t* labels = keep + n_rows;
+    BYZ_TRY(byz_signguard_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, params, estimate ? t.sample : nullptr, out, keep,
+                              weights, labels, s));
+    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (keep_host) BYZ_HIP(hipMemcpyAsync(keep_host, keep, flag_bytes, hipMemcpyDeviceToHost, s));
+    if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
+    if (labels_host) BYZ_HIP(hipMemcpyAsync(labels_host, labels, flag_bytes, hipMemcpyDeviceToHost, s));
     return check_small(ctx, s);
 }
 

@@ -153,6 +153,8 @@ struct byz_ctx {
     byz::Buffer nnm_lists;       // its neighbour lists (n x k int32) and their lengths (n) when the caller passes no buffer
     hipStream_t nnm_stream = nullptr;      // stream of the last neighbour search (byz_nnm_info syncs it)
     hipStream_t rlr_stream = nullptr;      // stream of the last sign vote or flip (byz_robust_lr_info syncs it)
+    byz::Buffer signguard;       // SignGuard: the census partials, then the selection's arrays (SgScratch)
+    hipStream_t signguard_stream = nullptr;   // stream of the last SignGuard selection (byz_signguard_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -198,7 +200,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 40;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 52;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -222,6 +224,11 @@ constexpr int kFltrustTrusted = 30, kFltrustExcluded = 31, kFltrustTrustSum = 32
 constexpr int kNnmSolo = 36, kNnmShort = 37;
 // robust learning rate: the columns the last call flipped (one 64-bit counter: two words, 8-byte aligned)
 constexpr int kRlrFlipped = 38;
+// SignGuard: the rows kept, failing the norm filter, outside the benign cluster; the clusters and the seeds; flat: the bandwidth was
+// 0, not finite or below kSgMinBandwidth and every row got label 0; then three fp64 (two words each, 8-byte aligned): the
+// bandwidth h, the median norm M, and K = the kept rows as the divisor of the sum
+constexpr int kSgKept = 40, kSgNormFailed = 41, kSgOutside = 42, kSgClusters = 43, kSgSeeds = 44, kSgFlat = 45;
+constexpr int kSgBandwidth = 46, kSgMedian = 48, kSgKeptF64 = 50;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -411,6 +418,26 @@ int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
                            const double* divisor, float* out, hipStream_t stream);
 // fltrust.hip: FLTrust's trust scores ts and weights w from pq = p (n), q (n), q0 (1); T and the counts into the context's words
 int launch_fltrust_trust(byz_ctx* ctx, const double* pq, int64_t n, double* ts, double* w, hipStream_t stream);
+// signguard.hip: SignGuard's census and selection.  The workspace for n rows (ctx->signguard):
+constexpr int kSgMaxSamples = BYZ_SIGNGUARD_MAX_SAMPLES;   // rows the bandwidth is estimated from at most
+constexpr int kSgMaxShifts = 300;                          // mean-shift updates of one seed at most
+constexpr double kSgMinBandwidth = 1.0 / (1 << 20);        // below it the bins no longer pack into 21 bits a coordinate
+struct SgScratch {
+    double *q_part, *pznq, *feat, *centres, *final_centres, *kth, *w;
+    long long* cnt_part;
+    unsigned long long *keys, *seeds;
+    void* state;
+    int32_t *norm_ok, *members, *order, *standing, *label_rows, *keep, *labels, *sample;
+};
+int signguard_workspace(byz_ctx* ctx, int64_t n, int64_t n_cols, SgScratch* out);
+// q[i] = |x_i|^2 (launch_row_dots' sq, bit for bit) and the counts of positive, zero and negative values over the columns
+// [win_start, win_start + win_len) in one read of G.  counts (3n int64), q (n) and pznq (4n fp64: pos, zero, neg, q) are optional.
+int launch_row_signs(byz_ctx* ctx, const SgScratch& t, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t win_start,
+                     int64_t win_len, long long* counts, double* q, double* pznq, hipStream_t stream);
+int launch_signguard_counts_f64(byz_ctx* ctx, const long long* counts, const double* q, int64_t n, double* pznq, hipStream_t stream);
+int launch_signguard_select(byz_ctx* ctx, const SgScratch& t, const double* pznq, int64_t n, int64_t window_len, double lower,
+                            double upper, double bandwidth, const int32_t* sample, int64_t n_sample, int32_t* keep, double* w,
+                            int32_t* labels, double* mk_out, hipStream_t stream);
 // nnm.hip: nearest-neighbour mixing.  Lists: row i's k - 1 nearest rows at a finite distance and i itself, ascending, -1 behind
 // them (nbr: n x k int32; counts optional: n); the mix: Y[i] = mean of the listed rows of G, one MFMA accumulator chain in row order
 constexpr int64_t kNnmMaxRows = 16384;

@@ -14,7 +14,8 @@ Differences a caller can observe, all documented in DESIGN.md:
   * `_krum_create_distances` returns a `Distances` handle (GPU-resident N x N matrix) instead of a dict
     of dicts; `krum(..., distances=handle)` accepts it, `handle.to_dict()` rebuilds the reference's form.
 """
-from .engine import DeviceBuffer, Distances, bucketing_permutation, dnc_columns, get_engine  # noqa: F401
+from .engine import (DeviceBuffer, Distances, bucketing_permutation, dnc_columns, get_engine,  # noqa: F401
+                     signguard_sample, signguard_window)
 
 
 class DefenseTypes:
@@ -97,6 +98,26 @@ def fltrust(users_grads, users_count, corrupted_count, root_grad, return_info=Fa
     Engine.fltrust's info.  Not one of the `defend` keys: the reference's main.py offers only those four, and none of them
     takes a root gradient."""
     return get_engine().fltrust(users_grads, root_grad, return_info=return_info)
+
+
+def signguard(users_grads, users_count, corrupted_count, frac=0.1, lower=0.1, upper=3.0, bandwidth=None, n_samples=50, seed=0,
+              window=None, sample=None, return_info=False):
+    """SignGuard (Xu, Huang, Song and Lan, "Byzantine-robust Federated Learning through Collaborative Malicious Gradient
+    Filtering", ICDCS 2022; not in the reference): the clients whose norm is outside (lower, upper) x the median norm are
+    filtered, the clients are clustered by mean shift on their shares of positive, zero and negative coordinates over a
+    random window of the coordinates, and the mean of the largest cluster's surviving vectors, each clipped to the median
+    norm, is returned.  It is built for the reference's own attack: an "A Little Is Enough" vector sits among the honest ones
+    in distance, and its sign shares give it away.  No client kept: the zero vector.
+    lower = 0.1 and upper = 3.0 are the paper's numbers.  The window of a tenth of the coordinates (frac), the bandwidth
+    quantile 0.5 and the 50 sampled clients (n_samples) are the authors' code's.  This package's: the window's start is
+    uniform in [0, D - m] with both ends included (the authors' upper end is exclusive and cannot express frac = 1), the
+    window and the sample are drawn on the host from `seed` (signguard_window, signguard_sample) unless `window` =
+    (start, length) or `sample` give them, and a bandwidth below 2^-20 counts as zero (one cluster).  The paper draws a new
+    window every round: pass a new seed per round (DeviceServer.defend_signguard does).  The reference's leading signature;
+    users_count and corrupted_count are accepted and unused.  return_info=True also returns Engine.signguard's info.  Not
+    one of the `defend` keys: the reference's main.py offers only those four."""
+    return get_engine().signguard(users_grads, frac=frac, lower=lower, upper=upper, bandwidth=bandwidth, n_samples=n_samples,
+                                  seed=seed, window=window, sample=sample, return_info=return_info)
 
 
 def nnm(users_grads, users_count, corrupted_count, then=None, distances=None, **then_kwargs):

@@ -36,6 +36,29 @@ def dnc_columns(n_cols, sub_dim, n_iters=1, seed=0):
     return np.stack(rows)
 
 
+def signguard_window(n_cols, frac=0.1, seed=0):
+    """SignGuard's census window, drawn on the host so that the library stays deterministic: (c0, m) with
+    m = max(1, int(frac * n_cols)) and c0 = np.random.default_rng(seed).integers(0, n_cols - m + 1), i.e. uniform in
+    [0, n_cols - m] with BOTH ends included.  The authors' code draws its start with an exclusive upper end and so cannot
+    express frac = 1; here frac = 1 is the whole row."""
+    n_cols, frac = int(n_cols), float(frac)
+    if n_cols < 1 or not 0.0 < frac <= 1.0:
+        raise ValueError('signguard_window: n_cols must be >= 1 and 0 < frac <= 1')
+    m = max(1, int(frac * n_cols))
+    return int(np.random.default_rng(seed).integers(0, n_cols - m + 1)), m
+
+
+def signguard_sample(n, n_samples=50, seed=0):
+    """The rows SignGuard estimates its bandwidth from, drawn on the host: min(n, n_samples) distinct row numbers as int32,
+    np.random.default_rng(seed).choice(n, size, replace=False), or arange(n) when n_samples >= n."""
+    n, n_samples = int(n), int(n_samples)
+    if n < 1 or n_samples < 1:
+        raise ValueError('signguard_sample: n and n_samples must be >= 1')
+    if n_samples >= n:
+        return np.arange(n, dtype=np.int32)
+    return np.random.default_rng(seed).choice(n, size=n_samples, replace=False).astype(np.int32)
+
+
 def bucketing_permutation(n, seed=0):
     """Bucketing's shuffle of the n clients, drawn on the host so that the library stays deterministic:
     np.random.default_rng(seed).permutation(n) as int32."""
@@ -921,6 +944,139 @@ class Engine:
         trusted, excluded, ok, total = self.fltrust_info()
         return out, {'trusted_rows': trusted, 'excluded_rows': excluded, 'root_ok': ok, 'trust_sum': total, 'trust': trust,
                      'weights': weights}
+
+    # ---- SignGuard (Xu, Huang, Song and Lan, ICDCS 2022; not in the reference) ----
+    def row_signs(self, g, window_start, window_len):
+        """(pos, zero, neg, q): the int64 counts of positive, zero and negative values of every row over the columns
+        [window_start, window_start + window_len), and q[i] = sum_c (double)g[i, c]^2 over ALL columns (row_dots' sq, bit for
+        bit), in ONE read of g.  A value is counted on its bits: +0.0 and -0.0 are zeros, denormals and infinities count by
+        their sign, a NaN counts nowhere.  window_len = 0 is allowed.  torch tensors for a torch input, numpy for a host input;
+        for a DeviceBuffer the counts come back as numpy and q as a DeviceBuffer."""
+        m, stage, host = self._staged(g)
+        counts, cptr = self._out_like(m, (3, m.rows), np.int64)
+        q, qptr = self._out_like(m, m.rows, np.float64)
+        _check(self.lib.byz_row_signs_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(window_start), int(window_len),
+                                          _vp(cptr), _vp(qptr), _vp(m.stream)))
+        if host:
+            self.synchronize(m.stream)   # the staged copy must outlive the kernel
+            counts, q = counts.numpy(), q.numpy()
+        elif m.torch_like is None:
+            counts = counts.numpy()      # (a DeviceBuffer has no row views: the three count vectors come back on the host)
+        return counts[0], counts[1], counts[2], q
+
+    @staticmethod
+    def _signguard_params(window_start, window_len, lower, upper, bandwidth, n_sample):
+        lower, upper = float(lower), float(upper)
+        bandwidth = 0.0 if bandwidth is None else float(bandwidth)
+        if not lower >= 0.0 or not upper > lower or not bandwidth >= 0.0 or int(window_start) < 0 or int(window_len) < 1:
+            raise ValueError('signguard: lower = %r must be >= 0, upper = %r > lower, bandwidth = %r >= 0 or None, the window '
+                             '(%r, %r) a start >= 0 and a length >= 1' % (lower, upper, bandwidth, window_start, window_len))
+        return _native.SignGuardParams(int(window_start), int(window_len), lower, upper, bandwidth, int(n_sample))
+
+    def _signguard_sample(self, sample, n_rows, n_samples, seed, bandwidth):
+        """The sampled rows as a checked host int32 array (None when the bandwidth is given)."""
+        if bandwidth is not None and float(bandwidth) > 0.0:
+            return None
+        if sample is None:
+            sample = signguard_sample(n_rows, min(int(n_samples), _native.SIGNGUARD_MAX_SAMPLES), seed)
+        sample = np.ascontiguousarray(np.asarray(sample.cpu().numpy() if _is_torch(sample) else sample).reshape(-1))
+        if sample.dtype.kind not in 'iu' or sample.size < 1 or sample.size > min(n_rows, _native.SIGNGUARD_MAX_SAMPLES) or \
+                sample.min() < 0 or sample.max() >= n_rows or np.unique(sample).size != sample.size:
+            raise ValueError('signguard: the sample must be 1..min(n, %d) distinct row numbers in [0, %d)'
+                             % (_native.SIGNGUARD_MAX_SAMPLES, n_rows))
+        return sample.astype(np.int32)
+
+    def signguard_info(self):
+        """The last SignGuard selection on this engine (synchronises): {kept_rows, norm_failed_rows, outside_rows, clusters,
+        seeds, bandwidth, median_norm}."""
+        vals = [ctypes.c_int64(0) for _ in range(5)]
+        h, med = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self.lib.byz_signguard_info(self.ctx, *[ctypes.byref(v) for v in vals], ctypes.byref(h), ctypes.byref(med)))
+        names = ('kept_rows', 'norm_failed_rows', 'outside_rows', 'clusters', 'seeds')
+        info = {k: int(v.value) for k, v in zip(names, vals)}
+        info.update(bandwidth=float(h.value), median_norm=float(med.value))
+        return info
+
+    def signguard_select(self, pos, zero, neg, q, window_len, lower=0.1, upper=3.0, bandwidth=None, sample=None, n_samples=50,
+                         seed=0):
+        """SignGuard's selection from row_signs' counts and squared norms (host or device vectors of n entries each):
+        {keep (int32 0 / 1), weights (fp64: min(1, M / norm) for a kept row, 0 otherwise), labels (int32, -1: no cluster),
+        median_norm, kept} as device-resident fp64 / int32 vectors and two device doubles `mk` = (M, K); include/byzagg.h has
+        the contract.  window_len is the m the shares are divided by.  Nothing synchronises; signguard_info() does."""
+        def host_of(v):
+            return v.detach().cpu().numpy() if _is_torch(v) else (v.numpy() if isinstance(v, DeviceBuffer) else np.asarray(v))
+        n = int(q.numel()) if _is_torch(q) else int(np.prod(q.shape)) if isinstance(q, DeviceBuffer) else int(np.asarray(q).size)
+        if _is_torch(q) and q.is_cuda:
+            import torch
+            counts = torch.stack([torch.as_tensor(v, device=q.device).reshape(-1).to(torch.int64) for v in (pos, zero, neg)]).contiguous()
+            if counts.shape != (3, n):
+                raise ValueError('expected three count vectors of %d entries' % n)
+            cptr, ckeep = counts.data_ptr(), counts
+            stream, like = torch.cuda.current_stream(q.device).cuda_stream, q
+        else:
+            counts = np.stack([host_of(v).reshape(-1).astype(np.int64) for v in (pos, zero, neg)])
+            if counts.shape != (3, n):
+                raise ValueError('expected three count vectors of %d entries' % n)
+            ckeep = self.to_device(counts)
+            cptr, stream, like = ckeep.ptr, None, None
+        qptr, qkeep = self._f64_vector(q, n)
+        sample = self._signguard_sample(sample, n, n_samples, seed, bandwidth)
+        params = self._signguard_params(0, window_len, lower, upper, bandwidth, 0 if sample is None else sample.size)
+        skeep = self.to_device(sample) if sample is not None else None
+        keep, kptr = self._out_like(like, n, np.int32)
+        weights, wptr = self._out_like(like, n, np.float64)
+        labels, lptr = self._out_like(like, n, np.int32)
+        mk, mptr = self._out_like(like, 2, np.float64)
+        _check(self.lib.byz_signguard_select_dev(self.ctx, _vp(cptr), _vp(qptr), n, ctypes.byref(params),
+                                                 _vp(skeep.ptr if skeep is not None else None), _vp(kptr), _vp(wptr), _vp(lptr),
+                                                 _vp(mptr), _vp(stream)))
+        if skeep is not None or isinstance(ckeep, DeviceBuffer) or isinstance(qkeep, DeviceBuffer):
+            self.synchronize(stream)     # uploaded inputs must outlive the kernels
+        return {'keep': keep, 'weights': weights, 'labels': labels, 'mk': mk}
+
+    def signguard(self, g, frac=0.1, lower=0.1, upper=3.0, bandwidth=None, n_samples=50, seed=0, window=None, sample=None,
+                  return_info=False):
+        """SignGuard: rows whose norm is outside (lower, upper) x the median norm are filtered, the rows are clustered (mean
+        shift, bandwidth estimated from `n_samples` sampled rows unless given) on their shares of positive, zero and negative
+        values over a window of the columns, and the mean of the largest cluster's surviving rows, each clipped to the median
+        norm, is returned.  No row kept: the zero vector.  The window is `window` = (start, length) or
+        signguard_window(D, frac, seed); the sampled rows are `sample` or signguard_sample(n, n_samples, seed).
+        return_info=True also returns signguard_info()'s dict with keep, weights and labels (one per row) and the window."""
+        dm = self._device_matrix(g)
+        n, d = (dm.rows, dm.cols) if dm is not None else self._host_matrix(g).shape
+        c0, m = window if window is not None else signguard_window(d, frac, seed)
+        if int(c0) < 0 or int(m) < 1 or int(c0) + int(m) > d:
+            raise ValueError('signguard: the window (%r, %r) is outside the %d columns' % (c0, m, d))
+        sample = self._signguard_sample(sample, n, n_samples, seed, bandwidth)
+        params = self._signguard_params(c0, m, lower, upper, bandwidth, 0 if sample is None else sample.size)
+        if dm is None:
+            h = self._host_matrix(g)
+            out = np.empty(d, dtype=np.float32)
+            keep = np.empty(n, dtype=np.int32) if return_info else None
+            weights = np.empty(n, dtype=np.float64) if return_info else None
+            labels = np.empty(n, dtype=np.int32) if return_info else None
+            _check(self.lib.byz_signguard_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                               sample.ctypes.data_as(ctypes.c_void_p) if sample is not None else None,
+                                               out.ctypes.data_as(ctypes.c_void_p),
+                                               keep.ctypes.data_as(ctypes.c_void_p) if return_info else None,
+                                               weights.ctypes.data_as(ctypes.c_void_p) if return_info else None,
+                                               labels.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+        else:
+            skeep = self.to_device(sample) if sample is not None else None
+            out, ptr = self._out_like(dm, dm.cols)
+            keep, kptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
+            weights, wptr = self._out_like(dm, n, np.float64) if return_info else (None, None)
+            labels, lptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
+            _check(self.lib.byz_signguard_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                              _vp(skeep.ptr if skeep is not None else None), _vp(ptr), _vp(kptr), _vp(wptr),
+                                              _vp(lptr), _vp(dm.stream)))
+            if skeep is not None:
+                self.synchronize(dm.stream)   # the uploaded sample must outlive the kernels
+        if not return_info:
+            return out
+        info = self.signguard_info()
+        info.update(keep=keep, weights=weights, labels=labels, window=(int(c0), int(m)))
+        return out, info
 
     # ---- nearest-neighbour mixing (Allouah et al., AISTATS 2023; not in the reference) ----
     def _nnm_lists(self, lists, rows, cols=None):

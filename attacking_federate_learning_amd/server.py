@@ -11,6 +11,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend(defence_method)          server.py:86-90   defences.defend[...] on the device matrix + fused momentum step
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
+    defend_signguard(frac, ...)       the same step with SignGuard, a new census window every round
     defend_nnm(then)                  the same step with nearest-neighbour mixing in front of the rule `then`
     defend_robust_lr(theta, then)     the same step with the robust learning rate round the mean or the rule `then`
     defend_bucketing(then, s)         the same step with s-bucketing, reshuffled every round, in front of the rule `then`
@@ -40,6 +41,8 @@ class DeviceServer:
         self.clip_centre = torch.zeros_like(self.current_weights)
         # bucketing's history: the calls of defend_bucketing so far (the default seed of the next shuffle)
         self.bucketing_round = 0
+        # SignGuard's history: the calls of defend_signguard so far (the default seed of the next window and sample)
+        self.signguard_round = 0
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -88,6 +91,20 @@ class DeviceServer:
                                    clients.per_client_gradients(net, server.current_weights, root_x[None], root_y[None])])
         """
         current_grads = self.engine.fltrust(self.users_grads.data, root_grad)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with SignGuard, whose window moves every round -----------------------------------
+    def defend_signguard(self, frac=0.1, lower=0.1, upper=3.0, bandwidth=None, n_samples=50, seed=None):
+        """SignGuard of this round's gradients (defences.signguard), then server.py:89-90's momentum step, as `defend` takes
+        it.  seed=None takes `signguard_round`, the number of earlier calls of this method on this server, so that every
+        round draws a new census window and a new sample, as the paper does."""
+        if seed is None:
+            seed = self.signguard_round
+        self.signguard_round += 1
+        current_grads = defences.signguard(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), frac=frac,
+                                           lower=lower, upper=upper, bandwidth=bandwidth, n_samples=n_samples, seed=seed)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -104,6 +104,13 @@ class HipKernels:
     def scaled_rows_sum(self, g_local, weights, divisor):
         return self.engine.scaled_rows_sum(g_local, weights, divisor)     # this rank's columns of the sum over the divisor
 
+    def row_signs(self, g_local, window_start, window_len):
+        # (pos, zero, neg, q): this rank's part of the counts over its part of the window, and of q over its columns
+        return self.engine.row_signs(g_local, window_start, window_len)
+
+    def signguard_select(self, pos, zero, neg, q, window_len, **kwargs):
+        return self.engine.signguard_select(pos, zero, neg, q, window_len, **kwargs)     # the same on every rank
+
     def dnc_scores(self, g_local, columns, power_iters=32):
         return self.engine.dnc_scores(g_local, columns, power_iters=power_iters)     # one rank holds the sampled columns
 
@@ -498,6 +505,43 @@ class ShardedAggregator:
             return out
         return out, {'trusted_rows': int((trust > 0).sum().item()), 'excluded_rows': int((~finite).sum().item()),
                      'root_ok': root_ok, 'trust_sum': float(total.item()), 'trust': trust, 'weights': weights}
+
+    def signguard(self, g_local, column_offset=0, total_columns=None, frac=0.1, lower=0.1, upper=3.0, bandwidth=None,
+                  n_samples=50, seed=0, window=None, sample=None, gather=False, return_info=False):
+        """SignGuard (defences.signguard's contract), columns layout: every rank holds all rows over its own columns,
+        `column_offset` being the global number of its first column and `total_columns` the full D (needed beyond one rank).
+        Every rank draws the SAME global window and sample (signguard_window, signguard_sample, or `window` / `sample`) and
+        counts the part of the window that falls into its slice -- possibly nothing.  ONE all-reduce of 4 N doubles (pos,
+        zero, neg, q; a count is exact as a double) makes them whole, the selection is then the same on every rank and the
+        sum is local to the columns."""
+        import torch
+        from .engine import signguard_sample, signguard_window
+        n, d_local = g_local.shape
+        if self.world > 1 and total_columns is None:
+            raise ValueError('signguard() over several ranks needs total_columns')
+        total = int(total_columns) if total_columns is not None else d_local
+        c0, m = window if window is not None else signguard_window(total, frac, seed)
+        c0, m, column_offset = int(c0), int(m), int(column_offset)
+        if c0 < 0 or m < 1 or c0 + m > total:
+            raise ValueError('signguard: the window (%d, %d) is outside the %d columns' % (c0, m, total))
+        lo, hi = max(c0, column_offset), min(c0 + m, column_offset + d_local)
+        local_len = max(0, hi - lo)
+        local_start = lo - column_offset if local_len else 0
+        if sample is None and not (bandwidth is not None and float(bandwidth) > 0.0):
+            sample = signguard_sample(n, n_samples, seed)
+        pos, zero, neg, q = self.kernels.row_signs(g_local, local_start, local_len)
+        pznq = torch.cat([torch.as_tensor(v, device=g_local.device).to(torch.float64).reshape(-1) for v in (pos, zero, neg, q)])
+        self._all_reduce('allreduce_signguard_census', pznq)
+        pos, zero, neg = (pznq[k * n:(k + 1) * n].to(torch.int64) for k in range(3))
+        sel = self.kernels.signguard_select(pos, zero, neg, pznq[3 * n:], m, lower=lower, upper=upper, bandwidth=bandwidth,
+                                            sample=sample)
+        out = self.kernels.scaled_rows_sum(g_local, sel['weights'], sel['mk'][1:2])
+        out = self._maybe_gather(out, gather, total_columns)
+        if not return_info:
+            return out
+        info = self.kernels.engine.signguard_info() if hasattr(self.kernels, 'engine') else {}
+        info.update(keep=sel['keep'], weights=sel['weights'], labels=sel['labels'], window=(c0, m))
+        return out, info
 
     def dnc(self, g_local, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
             columns=None, gather=False, return_index=False, total_columns=None):

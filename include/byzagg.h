@@ -352,6 +352,77 @@ int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows
 int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* root_host,
                      float* out_host, double* trust_host, double* weights_host);
 
+/* ---- SignGuard (Xu, Huang, Song & Lan, "Byzantine-robust Federated Learning through Collaborative Malicious Gradient       */
+/* Filtering", ICDCS 2022; not in the reference) ----                                                                       */
+/* A row built to sit among its neighbours in DISTANCE (the reference's "A Little Is Enough" attack, mean - z * std) still   */
+/* has visibly different shares of positive, zero and negative coordinates.  SignGuard filters the rows whose norm is far    */
+/* from the median norm, clusters the rows on those three shares taken over a window of the columns, keeps the largest       */
+/* cluster, clips the kept rows to the median norm and averages them.  Nothing is of order n^2: one read of G and one        */
+/* weighted sum over the kept rows.  The library draws nothing: the caller passes the window and the sampled rows, so that    */
+/* a call is deterministic.  G: n x n_cols fp32 (n = n_rows up to byz_limits' selection limit, BYZ_E_UNSUPPORTED beyond),     */
+/* leading dimension ld.  Everything after the census is fp64 on the device, in the stated order, no fused multiply-add.     */
+/* The census, over the window [window_start, window_start + window_len) of the columns (m = window_len):                    */
+/*   q_i = sum_c (double)x_ic^2 over ALL columns, in rowsq's fixed order: the bits of byz_row_dots_dev's sq_dev;             */
+/*   pos_i, zero_i, neg_i = the window's values that are > 0, == 0, < 0, decided on the BITS as the robust learning rate's   */
+/*   votes are: +0.0 and -0.0 are zeros, denormals and infinities count by their sign, a NaN counts nowhere.  Exact.         */
+/* The selection:                                                                                                           */
+/*   norm_i = sqrt(q_i);  M = np.median of the norms of the rows with a finite q_i (an even count: the mean of the two       */
+/*   middle values; no such row: M = NaN and no row passes);                                                                */
+/*   norm_ok_i = isfinite(q_i) && lower * M < norm_i && norm_i < upper * M          (both strict)                            */
+/*   P_i = pos_i / m, Z_i = zero_i / m, N_i = neg_i / m;                                                                    */
+/*   x_i = (P_i / (max_j P_j + 1e-8), Z_i / (max_j Z_j + 1e-8), N_i / (max_j N_j + 1e-8))  for EVERY row (the authors'        */
+/*   normalisation);  distances below are ((dx*dx + dy*dy) + dz*dz), compared squared against h*h.                           */
+/*   Bandwidth: h = params->bandwidth when that is > 0.  Otherwise, over the s = n_sample sampled rows (distinct row numbers, */
+/*   device int32; 1 <= s <= BYZ_SIGNGUARD_MAX_SAMPLES, BYZ_E_INVALID otherwise) and k = max(1, s / 2): h = the mean, in      */
+/*   sample order, of the k-th smallest of the s distances sqrt(.) from a sampled row to the sampled rows, itself included    */
+/*   -- scikit-learn's estimate_bandwidth(quantile = 0.5) on that sample.  If h is 0, not finite, or below 2^-20 (the bins    */
+/*   pack 21 bits a coordinate), the selection is FLAT: every row has label 0, one cluster, no seeds.                        */
+/*   Mean shift, flat kernel, bin seeding (scikit-learn's MeanShift(bandwidth = h, bin_seeding = True, cluster_all = False),  */
+/*   as the authors run it): the seeds are h * b for every distinct b = rint(x_i / h) (ties to even).  From a seed, the       */
+/*   members are the rows at squared distance <= h*h, the new centre is the members' sum (a fixed order) divided by their     */
+/*   count; stop when the move sqrt(.) is <= 1e-3 * h or after 300 updates.  A seed whose last member count is 0 is dropped. */
+/*   The centres are ordered by member count descending, then by their coordinates descending lexicographically; going        */
+/*   through them in that order, a centre still standing removes every later centre at squared distance <= h*h.  A row's      */
+/*   label is the number, in that order, of the nearest standing centre, the first on ties, or -1 when that centre is         */
+/*   farther than h.  benign = the label >= 0 with the most rows, the lowest on ties.                                        */
+/*   keep_i = norm_ok_i && label_i == benign;  K = the number of kept rows;  w_i = keep_i ? min(1, M / norm_i) : 0.          */
+/* The sum: out[c] = K > 0 ? fl32(S_c / K) : 0, S_c = the sum over the rows with w_i != 0 of w_i * (double)x_ic in row order  */
+/* (byz_scaled_rows_sum_dev).  No kept row gives the zero vector, never NaN (FLTrust's convention); a dropped row is neither  */
+/* loaded nor multiplied.  lower = 0.1 and upper = 3.0 are the paper's values; the window of a tenth of the columns, the      */
+/* quantile 0.5 and the 50 sampled rows are the authors' code's.  0 <= lower, lower < upper (+inf allowed), bandwidth >= 0    */
+/* (NaN anywhere: BYZ_E_INVALID); window_start >= 0, window_len >= 1, inside the columns.  out_dev must not overlap G.        */
+/* Everything is asynchronous on `stream`; only byz_signguard_info synchronises.  Two calls give the same bits; so do a       */
+/* strided view and its dense copy.  The parameters travel in a struct: the ABI passes no doubles by value.                  */
+#define BYZ_SIGNGUARD_MAX_SAMPLES 1024
+typedef struct byz_signguard_params {
+    int64_t window_start;   /* first column of the census window                                                          */
+    int64_t window_len;     /* m: its length, the divisor of the shares (sharded: the GLOBAL window's length)               */
+    double lower, upper;    /* the norm filter's bounds, in units of the median norm                                       */
+    double bandwidth;       /* > 0: h; 0: estimated from the sampled rows                                                   */
+    int64_t n_sample;       /* s: the sampled rows (read only when bandwidth is 0)                                          */
+} byz_signguard_params;
+/* The census as a piece: counts_dev = 3 * n_rows int64 (pos, then zero, then neg), q_dev = n_rows fp64, in ONE read of G.   */
+/* window_len = 0 is allowed (all counts 0); on one rank of the columns layout, its part of q and of the window.             */
+int byz_row_signs_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t window_start,
+                      int64_t window_len, int64_t* counts_dev, double* q_dev, void* stream);
+/* The selection as a piece, from counts and q of that form (the caller vouches that the counts are >= 0 and <= window_len): */
+/* keep_dev (n int32, 0 / 1), weights_dev (n fp64), labels_dev (n int32), each optional; mk_dev (optional): two fp64, M and K. */
+int byz_signguard_select_dev(byz_ctx* ctx, const int64_t* counts_dev, const double* q_dev, int64_t n_rows,
+                             const byz_signguard_params* params, const int32_t* sample_dev, int32_t* keep_dev,
+                             double* weights_dev, int32_t* labels_dev, double* mk_dev, void* stream);
+int byz_signguard_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                      const byz_signguard_params* params, const int32_t* sample_dev, float* out_dev, int32_t* keep_dev,
+                      double* weights_dev, int32_t* labels_dev, void* stream);
+/* The last selection on this context: the kept rows, the rows failing the norm filter, the rows outside the benign cluster,  */
+/* the clusters found, the seeds, h and M.  Synchronises that call's stream; nothing else does.                              */
+int byz_signguard_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* norm_failed_rows, int64_t* outside_rows, int64_t* clusters,
+                       int64_t* seeds, double* bandwidth, double* median_norm);
+/* SignGuard of a host matrix (sample_host: params->n_sample int32, checked: distinct and in range, BYZ_E_INVALID otherwise;  */
+/* out_host: n_cols floats; keep_host, weights_host, labels_host optional).  Synchronous.                                    */
+int byz_signguard_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_signguard_params* params,
+                       const int32_t* sample_host, float* out_host, int32_t* keep_host, double* weights_host,
+                       int32_t* labels_host);
+
 /* ---- nearest-neighbour mixing, NNM (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot & Stephan, "Fixing by Mixing", AISTATS  */
 /* 2023; not in the reference) ----                                                                                        */
 /* A PRE-aggregation: every row of G is replaced by the mean of its k = users_count - corrupted_count nearest rows, itself  */
@@ -579,6 +650,16 @@ int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_
 int byz_fltrust_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
                             const float* root_local_dev, byz_allreduce_f64_fn allreduce, void* user,
                             float* out_local_dev, double* trust_dev, double* weights_dev, void* stream);
+
+/* SignGuard over the slices: every rank holds its columns of G.  A rank counts the part of the GLOBAL window that falls in   */
+/* its slice -- local_window_start and local_window_len, within the slice; a length of 0 is allowed -- and params->window_len  */
+/* is the global m.  ONE all-reduce of 4 * n_rows doubles (pos, zero, neg, q, in that order; a count is exact as a double)     */
+/* makes them whole -- one call, on every rank, whatever the data.  The selection is then replicated on every rank and the    */
+/* sum is local to the columns.  The result differs from byz_signguard_dev's by the order of q's partial sums only.            */
+int byz_signguard_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                              const byz_signguard_params* params, int64_t local_window_start, int64_t local_window_len,
+                              const int32_t* sample_dev, byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
+                              int32_t* keep_dev, double* weights_dev, int32_t* labels_dev, void* stream);
 
 /* NNM over the slices (the columns layout; a clients layout is not offered): byz_pairwise_distances_sharded_dev's exchange  */
 /* and nothing more.  The lists (nbr_dev optional) are then the same on every rank and the mix is local to the columns:        */
