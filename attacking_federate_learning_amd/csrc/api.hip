@@ -145,15 +145,76 @@ int check_row_ceiling(const char* who, int64_t n_rows) {
     return BYZ_OK;
 }
 
-// A *_host entry point's staging: ctx->stage_in sized for the host matrix and filled (queued on `stream`), ctx->stage_out sized
-// for the result.
-int stage_host_matrix(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, size_t out_bytes, hipStream_t stream) {
-    const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    BYZ_TRY(ctx->stage_in.ensure(bytes));
-    BYZ_TRY(ctx->stage_out.ensure(out_bytes));
-    BYZ_HIP(hipMemcpyAsync(ctx->stage_in.ptr, G_host, bytes, hipMemcpyHostToDevice, stream));
-    return BYZ_OK;
-}
+// What a *_host entry point does around its _dev call, on the null stream: the host matrix goes to ctx->stage_in, the vectors
+// and lists the call reads or writes are carved out of ctx->stage_out (Carve: the first one at its base, each 16-byte aligned).
+// Declare the arrays, stage(), run the _dev call on G() and stream(), end with finish() or finish_sync().  Nothing is allocated
+// or copied before stage(), so every argument check of the wrapper runs first.
+class HostStage {
+  public:
+    explicit HostStage(byz_ctx* ctx) : ctx_(ctx) {}
+    // an optional output: carved, and copied to `host` by the ending, when host != nullptr; *dev = nullptr otherwise
+    template <typename T>
+    void out(T** dev, T* host, int64_t count) {
+        if (host != nullptr) inout<T>(dev, nullptr, host, count);
+        else *dev = nullptr;
+    }
+    // an optional input: carved, and uploaded by stage(), when host != nullptr; *dev = nullptr otherwise
+    template <typename T>
+    void in(T** dev, const T* host, int64_t count) {
+        if (host != nullptr) inout<T>(dev, host, nullptr, count);
+        else *dev = nullptr;
+    }
+    // always carved; uploaded from `from` and downloaded to `to` where they are not null: a start vector the call runs in place
+    // on, an output the device call writes whether or not the caller asked for it
+    template <typename T>
+    void inout(T** dev, const T* from, T* to, int64_t count) {
+        const int slot = carve_.slots();
+        carve_.take(dev, count);
+        if (carve_.slots() > slot) copies_[slot] = {from, to, static_cast<size_t>(count) * sizeof(T)};   // (a refused take fails stage())
+    }
+    // sizes stage_in and stage_out, binds every array, queues the matrix's upload and the inputs'
+    int stage(const float* G_host, int64_t n_rows, int64_t n_cols) {
+        const size_t bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
+        BYZ_TRY(ctx_->stage_in.ensure(bytes));
+        BYZ_TRY(carve_.commit(ctx_->stage_out));
+        BYZ_HIP(hipMemcpyAsync(ctx_->stage_in.ptr, G_host, bytes, hipMemcpyHostToDevice, stream()));
+        for (int i = 0; i < carve_.slots(); ++i)
+            if (copies_[i].from != nullptr)
+                BYZ_HIP(hipMemcpyAsync(at(i), copies_[i].from, copies_[i].bytes, hipMemcpyHostToDevice, stream()));
+        return BYZ_OK;
+    }
+    float* G() const { return ctx_->stage_in.as<float>(); }
+    hipStream_t stream() const { return nullptr; }
+    // the two endings.  finish: the downloads queued, then the device scalars read back and the status word checked (`words`: for
+    // a wrapper that reports one of them)
+    int finish(int32_t (&words)[kSmallWords]) {
+        BYZ_TRY(download());
+        return read_small(ctx_, words, stream());
+    }
+    int finish() {
+        int32_t words[kSmallWords];
+        return finish(words);
+    }
+    // finish_sync: the downloads queued, then the stream synchronised and nothing else
+    int finish_sync() {
+        BYZ_TRY(download());
+        BYZ_HIP(hipStreamSynchronize(stream()));
+        return BYZ_OK;
+    }
+
+  private:
+    struct Copy { const void* from; void* to; size_t bytes; };
+    char* at(int slot) const { return static_cast<char*>(ctx_->stage_out.ptr) + carve_.offset(slot); }   // as commit() bound it
+    int download() {
+        for (int i = 0; i < carve_.slots(); ++i)
+            if (copies_[i].to != nullptr)
+                BYZ_HIP(hipMemcpyAsync(copies_[i].to, at(i), copies_[i].bytes, hipMemcpyDeviceToHost, stream()));
+        return BYZ_OK;
+    }
+    byz_ctx* ctx_;
+    Carve carve_;
+    Copy copies_[Carve::kMaxSlots];
+};
 
 int krum_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_count, int64_t corrupted,
                 int32_t* winner_dev, hipStream_t stream) {
@@ -714,14 +775,13 @@ struct RowScratch {
 // sized by the chunks geomed_chunks picks for this shape: at most 64 per row and plane, about num_cus * 256 + n in all
 int row_scratch(byz_ctx* ctx, int64_t n, int64_t n_cols, RowScratch* out, int planes = 1) {
     int64_t chunk_cols = 0;
-    const int64_t partials = static_cast<int64_t>(geomed_chunks(ctx, n, n_cols, &chunk_cols)) * n * planes;
-    const int64_t root = planes == 2 ? geomed_chunks(ctx, 1, n_cols, &chunk_cols) : 0;
-    BYZ_TRY(ctx->rows.ensure(static_cast<size_t>(partials + (planes * n + 1) + planes * n + root) * sizeof(double)));
-    out->partials = ctx->rows.as<double>();
-    out->a = out->partials + partials;
-    out->b = out->a + (planes * n + 1);
-    out->root = out->b + planes * n;
-    return BYZ_OK;
+    const int64_t chunks = geomed_chunks(ctx, n, n_cols, &chunk_cols);
+    Carve c;
+    c.take(&out->partials, chunks * n * planes);
+    c.take(&out->a, planes * n + 1);
+    c.take(&out->b, planes * n);
+    c.take(&out->root, planes == 2 ? geomed_chunks(ctx, 1, n_cols, &chunk_cols) : 0);
+    return c.commit(ctx->rows);
 }
 
 // The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device.
@@ -1530,10 +1590,12 @@ int byz_defend_host(byz_ctx* ctx, int name, const float* G_host, int64_t n_rows,
     // preconditions first: the reference asserts before touching the data
     BYZ_TRY(check_krum_assert(name == 1 && check_assert, users_count, corrupted_count));
     if (name == 3) BYZ_TRY(check_bulyan_precondition(users_count, corrupted_count));
-    hipStream_t s = nullptr;
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * 3 * sizeof(float), s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
+    HostStage st(ctx);
+    float* out;
+    st.inout<float>(&out, nullptr, out_host, n_cols);   // (every defence but Krum writes it whether asked for or not)
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    float* G = st.G();
+    hipStream_t s = st.stream();
     int32_t index = 0;
     switch (name) {
         case 0: BYZ_TRY(byz_no_defense_dev(ctx, G, n_rows, n_cols, n_cols, out, s)); break;
@@ -1552,11 +1614,7 @@ int byz_defend_host(byz_ctx* ctx, int name, const float* G_host, int64_t n_rows,
             break;
         }
     }
-    if (out_host) {
-        BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-        BYZ_HIP(hipStreamSynchronize(s));
-    }
-    return BYZ_OK;
+    return out_host ? st.finish_sync() : BYZ_OK;   // (nothing to wait for when no vector goes back)
 }
 
 int byz_pairwise_distances_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
@@ -1564,11 +1622,11 @@ int byz_pairwise_distances_host(byz_ctx* ctx, const float* G_host, int64_t n_row
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "pairwise_distances"));
     BYZ_REQUIRE(dist_host, "pairwise_distances: null output");
-    hipStream_t s = nullptr;
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, 0, s));
+    HostStage st(ctx);   // (the matrix alone: the result is ctx->dist)
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    hipStream_t s = st.stream();
     BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
-    BYZ_TRY(byz_pairwise_distances_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols,
-                                       ctx->dist.as<float>(), s));
+    BYZ_TRY(byz_pairwise_distances_dev(ctx, st.G(), n_rows, n_cols, n_cols, ctx->dist.as<float>(), s));
     BYZ_HIP(hipMemcpyAsync(dist_host, ctx->dist.ptr, static_cast<size_t>(n_rows) * n_rows * sizeof(float),
                            hipMemcpyDeviceToHost, s));
     BYZ_HIP(hipStreamSynchronize(s));
@@ -1591,16 +1649,14 @@ int byz_drift_attack_host(byz_ctx* ctx, const float* rows_host, int64_t n_rows, 
                           float* drift_host, float* mean_host, float* std_host) {
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(rows_host, n_rows, n_cols, n_cols, "drift_attack"));
-    hipStream_t s = nullptr;
-    const size_t vec = static_cast<size_t>(n_cols) * sizeof(float);
-    BYZ_TRY(stage_host_matrix(ctx, rows_host, n_rows, n_cols, 3 * vec, s));
-    float* out = ctx->stage_out.as<float>();
-    BYZ_TRY(launch_column_drift(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, num_std, out, out + n_cols,
-                                out + 2 * n_cols, s));
-    if (drift_host) BYZ_HIP(hipMemcpyAsync(drift_host, out, vec, hipMemcpyDeviceToHost, s));
-    if (mean_host) BYZ_HIP(hipMemcpyAsync(mean_host, out + n_cols, vec, hipMemcpyDeviceToHost, s));
-    if (std_host) BYZ_HIP(hipMemcpyAsync(std_host, out + 2 * n_cols, vec, hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float *drift, *mean, *stdev;   // (the kernel writes all three, asked for or not)
+    st.inout<float>(&drift, nullptr, drift_host, n_cols);
+    st.inout<float>(&mean, nullptr, mean_host, n_cols);
+    st.inout<float>(&stdev, nullptr, std_host, n_cols);
+    BYZ_TRY(st.stage(rows_host, n_rows, n_cols));
+    BYZ_TRY(launch_column_drift(ctx, st.G(), n_rows, n_cols, n_cols, num_std, drift, mean, stdev, st.stream()));
+    return st.finish();
 }
 
 int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count,
@@ -1611,16 +1667,15 @@ int byz_multi_krum_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64
     // the aggregate asserts as defences.krum does; a selection alone does not (krum(..., return_index=True))
     BYZ_TRY(check_krum_assert(out_host != nullptr, users_count, corrupted_count));
     BYZ_TRY(check_multi_krum_m(n_rows, m));
-    hipStream_t s = nullptr;
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * 3 * sizeof(float), s));
+    HostStage st(ctx);
+    float* out;
+    st.inout<float>(&out, nullptr, out_host, n_cols);   // (the device call always forms the aggregate)
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(ctx->selection.ensure(static_cast<size_t>(n_rows) * sizeof(int32_t)));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
     int32_t* sel = ctx->selection.as<int32_t>();
-    BYZ_TRY(byz_multi_krum_dev(ctx, G, n_rows, n_cols, n_cols, users_count, corrupted_count, m, 0, out, sel, s));
-    if (selection_host) BYZ_TRY(read_i32(ctx, sel, selection_host, m, s));
-    if (out_host) BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    BYZ_TRY(byz_multi_krum_dev(ctx, st.G(), n_rows, n_cols, n_cols, users_count, corrupted_count, m, 0, out, sel, st.stream()));
+    if (selection_host) BYZ_TRY(read_i32(ctx, sel, selection_host, m, st.stream()));
+    return st.finish();
 }
 
 // the two coordinate-wise rank rules on a host matrix (median: trim_count ignored)
@@ -1631,14 +1686,12 @@ static int rank_select_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, i
     BYZ_REQUIRE(out_host, "%s: null output", median ? "coordinate_median" : "rank_trimmed_mean");
     if (n_rows > kLargeMaxRows || (!median && (trim_count < 0 || 2 * trim_count >= n_rows)))      // refused before anything is staged
         return launch_rank_select(ctx, G_host, n_rows, n_cols, n_cols, nullptr, trim_count, median, out_host, nullptr);
-    hipStream_t s = nullptr;
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, static_cast<size_t>(n_cols) * sizeof(float), s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
-    BYZ_TRY(launch_rank_select(ctx, G, n_rows, n_cols, n_cols, nullptr, trim_count, median, out, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    BYZ_HIP(hipStreamSynchronize(s));
-    return BYZ_OK;
+    HostStage st(ctx);
+    float* out;
+    st.out(&out, out_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(launch_rank_select(ctx, st.G(), n_rows, n_cols, n_cols, nullptr, trim_count, median, out, st.stream()));
+    return st.finish_sync();
 }
 
 int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, float* out_host) {
@@ -1656,17 +1709,14 @@ int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows,
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "geometric_median"));
     BYZ_REQUIRE(out_host, "geometric_median: null output");
     BYZ_TRY(check_geomed(params, n_rows, "geometric_median"));
-    hipStream_t s = nullptr;
-    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the weights 8-byte aligned)
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + static_cast<size_t>(n_rows) * sizeof(double), s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
-    double* weights = weights_host ? reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes) : nullptr;
-    BYZ_TRY(byz_geometric_median_dev(ctx, G, n_rows, n_cols, n_cols, params, out, weights, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (weights_host)
-        BYZ_HIP(hipMemcpyAsync(weights_host, weights, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float* out;
+    double* weights;
+    st.out(&out, out_host, n_cols);
+    st.out(&weights, weights_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_geometric_median_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, out, weights, st.stream()));
+    return st.finish();
 }
 
 int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_cclip_params* params,
@@ -1675,20 +1725,14 @@ int byz_centered_clip_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, in
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "centered_clip"));
     BYZ_REQUIRE(out_host, "centered_clip: null output");
     BYZ_TRY(check_cclip(params, n_rows, "centered_clip"));
-    hipStream_t s = nullptr;
-    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the scales 8-byte aligned)
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + static_cast<size_t>(n_rows) * sizeof(double), s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
-    double* scales = scales_host ? reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes) : nullptr;
-    // the start is staged into the output vector: the device call runs in place on it
-    if (start_host)
-        BYZ_HIP(hipMemcpyAsync(out, start_host, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyHostToDevice, s));
-    BYZ_TRY(byz_centered_clip_dev(ctx, G, n_rows, n_cols, n_cols, params, start_host ? out : nullptr, out, scales, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (scales_host)
-        BYZ_HIP(hipMemcpyAsync(scales_host, scales, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float* out;
+    double* scales;
+    st.inout(&out, start_host, out_host, n_cols);   // the start is staged into the output vector: the device call runs in place on it
+    st.out(&scales, scales_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_centered_clip_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, start_host ? out : nullptr, out, scales, st.stream()));
+    return st.finish();
 }
 
 int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* root_host, float* out_host,
@@ -1697,22 +1741,15 @@ int byz_fltrust_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t 
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "fltrust"));
     BYZ_REQUIRE(root_host && out_host, "fltrust: null root or output");
     BYZ_TRY(check_row_ceiling("fltrust", n_rows));
-    hipStream_t s = nullptr;
-    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the scores 8-byte aligned)
-    const size_t row_bytes = static_cast<size_t>(n_rows) * sizeof(double);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + 2 * row_bytes, s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
-    double* trust = reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes);
-    double* weights = trust + n_rows;
-    // the root is staged into the output vector: the device call runs in place on it
-    BYZ_HIP(hipMemcpyAsync(out, root_host, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyHostToDevice, s));
-    BYZ_TRY(byz_fltrust_dev(ctx, G, n_rows, n_cols, n_cols, out, out, trust_host ? trust : nullptr,
-                            weights_host ? weights : nullptr, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (trust_host) BYZ_HIP(hipMemcpyAsync(trust_host, trust, row_bytes, hipMemcpyDeviceToHost, s));
-    if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float* out;
+    double *trust, *weights;
+    st.inout(&out, root_host, out_host, n_cols);   // the root is staged into the output vector: the device call runs in place on it
+    st.out(&trust, trust_host, n_rows);
+    st.out(&weights, weights_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_fltrust_dev(ctx, st.G(), n_rows, n_cols, n_cols, out, out, trust, weights, st.stream()));
+    return st.finish();
 }
 
 int byz_signguard_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_signguard_params* params,
@@ -1730,25 +1767,23 @@ int byz_signguard_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_
             seen[r] = 1;
         }
     }
-    hipStream_t s = nullptr;
-    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the weights 8-byte aligned)
-    const size_t row_bytes = static_cast<size_t>(n_rows) * sizeof(double), flag_bytes = static_cast<size_t>(n_rows) * sizeof(int32_t);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + row_bytes + 2 * flag_bytes, s));
-    SgScratch t;
+    HostStage st(ctx);
+    float* out;
+    double* weights;
+    int32_t *keep, *labels;
+    st.out(&out, out_host, n_cols);
+    st.inout<double>(&weights, nullptr, weights_host, n_rows);   // (as before, the device call gets all three, asked for or not)
+    st.inout<int32_t>(&keep, nullptr, keep_host, n_rows);
+    st.inout<int32_t>(&labels, nullptr, labels_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    SgScratch t;   // the sample goes where the selection reads it, not into the staging area
     BYZ_TRY(signguard_workspace(ctx, n_rows, n_cols, &t));
     if (estimate)
-        BYZ_HIP(hipMemcpyAsync(t.sample, sample_host, static_cast<size_t>(params->n_sample) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    float* out = ctx->stage_out.as<float>();
-    double* weights = reinterpret_cast<double*>(ctx->stage_out.as<char>() + out_bytes);
-    int32_t* keep = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + out_bytes + row_bytes);
-    int32_t* labels = keep + n_rows;
-    BYZ_TRY(byz_signguard_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, params, estimate ? t.sample : nullptr, out, keep,
-                              weights, labels, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (keep_host) BYZ_HIP(hipMemcpyAsync(keep_host, keep, flag_bytes, hipMemcpyDeviceToHost, s));
-    if (weights_host) BYZ_HIP(hipMemcpyAsync(weights_host, weights, row_bytes, hipMemcpyDeviceToHost, s));
-    if (labels_host) BYZ_HIP(hipMemcpyAsync(labels_host, labels, flag_bytes, hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+        BYZ_HIP(hipMemcpyAsync(t.sample, sample_host, static_cast<size_t>(params->n_sample) * sizeof(int32_t), hipMemcpyHostToDevice,
+                               st.stream()));
+    BYZ_TRY(byz_signguard_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, estimate ? t.sample : nullptr, out, keep, weights, labels,
+                              st.stream()));
+    return st.finish();
 }
 
 int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t users_count, int64_t corrupted_count,
@@ -1758,17 +1793,14 @@ int byz_nnm_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
     BYZ_TRY(check_nnm("nnm", n_rows, k));
     BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "nnm"));
     BYZ_REQUIRE(Y_host, "nnm: null output");
-    hipStream_t s = nullptr;
-    const size_t y_bytes = static_cast<size_t>(n_rows) * n_cols * sizeof(float);
-    const size_t list_bytes = static_cast<size_t>(n_rows) * k * sizeof(int32_t);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, y_bytes + list_bytes, s));
-    float* Y = ctx->stage_out.as<float>();
-    int32_t* nbr = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + y_bytes);
-    BYZ_TRY(byz_nnm_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, users_count, corrupted_count, Y, n_cols,
-                        nbr_host ? nbr : nullptr, s));
-    BYZ_HIP(hipMemcpyAsync(Y_host, Y, y_bytes, hipMemcpyDeviceToHost, s));
-    if (nbr_host) BYZ_HIP(hipMemcpyAsync(nbr_host, nbr, list_bytes, hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float* Y;
+    int32_t* nbr;
+    st.out(&Y, Y_host, n_rows * n_cols);
+    st.out(&nbr, nbr_host, n_rows * k);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_nnm_dev(ctx, st.G(), n_rows, n_cols, n_cols, users_count, corrupted_count, Y, n_cols, nbr, st.stream()));
+    return st.finish();
 }
 
 int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t theta, float* out_host,
@@ -1778,15 +1810,14 @@ int byz_robust_lr_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_
     BYZ_REQUIRE(out_host, "robust_lr: null output");
     BYZ_TRY(check_row_ceiling("robust_lr", n_rows));
     BYZ_TRY(check_rlr_theta("robust_lr", theta, n_rows));
-    hipStream_t s = nullptr;
-    const size_t vec_bytes = static_cast<size_t>(n_cols) * sizeof(float);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, 2 * vec_bytes, s));
-    float* out = ctx->stage_out.as<float>();
-    int32_t* votes = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + vec_bytes);
-    BYZ_TRY(byz_robust_lr_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, theta, out, votes_host ? votes : nullptr, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, vec_bytes, hipMemcpyDeviceToHost, s));
-    if (votes_host) BYZ_HIP(hipMemcpyAsync(votes_host, votes, vec_bytes, hipMemcpyDeviceToHost, s));
-    return check_small(ctx, s);
+    HostStage st(ctx);
+    float* out;
+    int32_t* votes;
+    st.out(&out, out_host, n_cols);
+    st.out(&votes, votes_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_robust_lr_dev(ctx, st.G(), n_rows, n_cols, n_cols, theta, out, votes, st.stream()));
+    return st.finish();
 }
 
 int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const int32_t* perm_host, int64_t s,
@@ -1804,16 +1835,14 @@ int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int
             seen[static_cast<size_t>(e)] = true;
         }
     }
-    hipStream_t s0 = nullptr;
-    const size_t y_bytes = static_cast<size_t>(ceil_div(n_rows, s)) * n_cols * sizeof(float);
-    const size_t perm_bytes = static_cast<size_t>(n_rows) * sizeof(int32_t);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, y_bytes + perm_bytes, s0));
-    float* Y = ctx->stage_out.as<float>();
-    int32_t* perm = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + y_bytes);
-    if (perm_host != nullptr) BYZ_HIP(hipMemcpyAsync(perm, perm_host, perm_bytes, hipMemcpyHostToDevice, s0));
-    BYZ_TRY(byz_bucket_means_dev(ctx, ctx->stage_in.as<float>(), n_rows, n_cols, n_cols, perm_host ? perm : nullptr, s, Y, n_cols, s0));
-    BYZ_HIP(hipMemcpyAsync(Y_host, Y, y_bytes, hipMemcpyDeviceToHost, s0));
-    return check_small(ctx, s0);
+    HostStage st(ctx);
+    float* Y;
+    int32_t* perm;
+    st.out(&Y, Y_host, ceil_div(n_rows, s) * n_cols);
+    st.in(&perm, perm_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_bucket_means_dev(ctx, st.G(), n_rows, n_cols, n_cols, perm, s, Y, n_cols, st.stream()));
+    return st.finish();
 }
 
 int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_dnc_params* params,
@@ -1829,20 +1858,17 @@ int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
         BYZ_REQUIRE(c >= 0 && c < n_cols && (first || c > columns_host[k - 1]),
                     "dnc: column list entry %lld = %lld out of range or not ascending", (long long)k, (long long)c);
     }
-    hipStream_t s = nullptr;
-    const size_t out_bytes = static_cast<size_t>(ceil_div(n_cols, 2)) * 2 * sizeof(float);    // (the column list 8-byte aligned)
-    const size_t list_bytes = static_cast<size_t>(listed) * sizeof(int64_t);
-    BYZ_TRY(stage_host_matrix(ctx, G_host, n_rows, n_cols, out_bytes + list_bytes + static_cast<size_t>(n_rows) * sizeof(int32_t), s));
-    float* G = ctx->stage_in.as<float>();
-    float* out = ctx->stage_out.as<float>();
-    int64_t* columns = reinterpret_cast<int64_t*>(ctx->stage_out.as<char>() + out_bytes);
-    int32_t* good = reinterpret_cast<int32_t*>(ctx->stage_out.as<char>() + out_bytes + list_bytes);
-    BYZ_HIP(hipMemcpyAsync(columns, columns_host, list_bytes, hipMemcpyHostToDevice, s));
-    BYZ_TRY(byz_dnc_dev(ctx, G, n_rows, n_cols, n_cols, params, columns, out, good_host ? good : nullptr, s));
-    BYZ_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (good_host) BYZ_HIP(hipMemcpyAsync(good_host, good, static_cast<size_t>(n_rows) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HostStage st(ctx);
+    float* out;
+    int64_t* columns;
+    int32_t* good;
+    st.out(&out, out_host, n_cols);
+    st.in(&columns, columns_host, listed);
+    st.out(&good, good_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_dnc_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, columns, out, good, st.stream()));
     int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, s));
+    BYZ_TRY(st.finish(words));
     if (kept_host) *kept_host = words[kDncKept];
     return BYZ_OK;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/byzagg.h"
+#include "carve.hpp"
 
 namespace byz {
 
@@ -138,22 +139,24 @@ struct byz_ctx {
     byz::Buffer row_total;       // n fp64: sum of a row's finite distances
     byz::Buffer row_top;         // n fp64: sum of a row's largest `drop` finite distances; then n counts of non-finite ones
     byz::Buffer scores;          // n fp32 Krum scores
-    byz::Buffer multi_krum;      // Multi-Krum's ranking: n_pad sort keys, then n row flags
+    byz::Buffer multi_krum;      // Multi-Krum's ranking, carved (carve.hpp): n_pad sort keys; n row flags
     byz::Buffer multi_krum_rows; // Multi-Krum's selected rows in ascending order (the list the row-list mean walks)
-    byz::Buffer rows;            // the row-distance loops (geometric median, centered clipping, FLTrust): rowsq's (chunk, row) fp64
-                                 // partials (at most 64 per row, FLTrust: twice that), then sq (n + 1; FLTrust: p, q, q0) and the
-                                 // weights or scales (n; FLTrust: ts and w)
+    byz::Buffer rows;            // the row-distance loops (geometric median, centered clipping, FLTrust), carved into RowScratch's
+                                 // four arrays (api.hip: row_scratch): rowsq's (chunk, row) fp64 partials (at most 64 per row, FLTrust:
+                                 // twice that); sq (n + 1; FLTrust: p, q, q0); the weights or scales (n; FLTrust: ts and w); FLTrust's
+                                 // root partials
     hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
-    byz::Buffer dnc;             // DnC: the centred sample (n x sub_dim fp64), the column partials, the n-vectors, keep and good
+    byz::Buffer dnc;             // DnC, carved into DncScratch's arrays (dnc_workspace): the centred sample (n x sub_dim fp64), the
+                                 // column partials, the n-vectors, the state, keep and good (int32, an array each)
     hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
     hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
     hipStream_t fltrust_stream = nullptr;  // stream of the last FLTrust call (byz_fltrust_info syncs it)
     byz::Buffer nnm_keys;        // nearest-neighbour mixing: n segments of next_pow2(n) sort keys
-    byz::Buffer nnm_mask;        // its 0/1 fp32 mask, transposed ([j][i], padded to the mix kernel's tiles), then the n list lengths
+    byz::Buffer nnm_mask;        // carved: its 0/1 fp32 mask, transposed ([j][i], padded to the mix kernel's tiles); the n list lengths
     byz::Buffer nnm_lists;       // its neighbour lists (n x k int32) and their lengths (n) when the caller passes no buffer
     hipStream_t nnm_stream = nullptr;      // stream of the last neighbour search (byz_nnm_info syncs it)
     hipStream_t rlr_stream = nullptr;      // stream of the last sign vote or flip (byz_robust_lr_info syncs it)
-    byz::Buffer signguard;       // SignGuard: the census partials, then the selection's arrays (SgScratch)
+    byz::Buffer signguard;       // SignGuard, carved into SgScratch's arrays (signguard_workspace): the census partials, then the selection's
     hipStream_t signguard_stream = nullptr;   // stream of the last SignGuard selection (byz_signguard_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
@@ -426,7 +429,7 @@ struct SgScratch {
     double *q_part, *pznq, *feat, *centres, *final_centres, *kth, *w;
     long long* cnt_part;
     unsigned long long *keys, *seeds;
-    void* state;
+    char* state;
     int32_t *norm_ok, *members, *order, *standing, *label_rows, *keep, *labels, *sample;
 };
 int signguard_workspace(byz_ctx* ctx, int64_t n, int64_t n_cols, SgScratch* out);

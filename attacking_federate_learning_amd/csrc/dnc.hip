@@ -275,22 +275,16 @@ int colsum_chunks(byz_ctx* ctx, int64_t n, int64_t b, int64_t* chunk_rows) {
 }  // namespace
 
 int dnc_workspace(byz_ctx* ctx, int64_t n, int64_t b, DncScratch* out) {
-    // C, the colsum partials, w; then the n-vectors bad, wt, diag (also y), u, scores, the state; then keep and good (int32)
-    const int64_t doubles = n * b + static_cast<int64_t>(kMaxChunks) * b + b + 5 * n + kStateWords;
-    BYZ_TRY(ctx->dnc.ensure(static_cast<size_t>(doubles) * sizeof(double) + static_cast<size_t>(2 * n) * sizeof(int32_t)));
-    double* p = ctx->dnc.as<double>();
-    out->C = p;           p += n * b;
-    out->part = p;        p += static_cast<int64_t>(kMaxChunks) * b;
-    out->w = p;           p += b;
-    out->bad = p;         p += n;
-    out->wt = p;          p += n;
-    out->y = p;           p += n;
-    out->u = p;           p += n;
-    out->scores = p;      p += n;
-    out->state = p;       p += kStateWords;
-    out->keep = reinterpret_cast<int32_t*>(p);
-    out->good = out->keep + n;
-    return BYZ_OK;
+    // C, the colsum partials, w; then the n-vectors bad, wt, diag (also y), u, scores, the state; then keep and good
+    Carve c;
+    c.take(&out->C, n * b);
+    c.take(&out->part, static_cast<int64_t>(kMaxChunks) * b);
+    c.take(&out->w, b);
+    for (double** per_row : {&out->bad, &out->wt, &out->y, &out->u, &out->scores}) c.take(per_row, n);
+    c.take(&out->state, kStateWords);
+    c.take(&out->keep, n);
+    c.take(&out->good, n);
+    return c.commit(ctx->dnc);
 }
 
 // w_out = (C^T wt) [/ *divide_by]

@@ -59,9 +59,12 @@ int launch_multi_krum_rank(byz_ctx* ctx, int64_t n, int64_t m, int32_t* selectio
                 (long long)n, (long long)m);
     BYZ_REQUIRE(ctx->scores.bytes >= static_cast<size_t>(n) * sizeof(float), "multi-krum ranking: no scores (run krum_select first)");
     const int64_t n_pad = next_pow2(n < 2 ? 2 : n);
-    BYZ_TRY(ctx->multi_krum.ensure(static_cast<size_t>(n_pad) * 8 + static_cast<size_t>(n) * sizeof(int32_t)));
-    unsigned long long* keys = ctx->multi_krum.as<unsigned long long>();
-    int32_t* flags = reinterpret_cast<int32_t*>(keys + n_pad);
+    unsigned long long* keys = nullptr;
+    int32_t* flags = nullptr;
+    Carve c;
+    c.take(&keys, n_pad);
+    c.take(&flags, n);
+    BYZ_TRY(c.commit(ctx->multi_krum));
     KernelTimer t(ctx, BYZ_K_KRUM_ARGMIN, stream);
     BYZ_HIP(hipMemsetAsync(flags, 0, static_cast<size_t>(n) * sizeof(int32_t), stream));
     multi_krum_keys_kernel<<<static_cast<unsigned>(ceil_div(n_pad, 256)), 256, 0, stream>>>(ctx->scores.as<float>(), (int)n, n_pad, keys);

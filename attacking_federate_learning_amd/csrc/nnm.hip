@@ -273,9 +273,12 @@ int launch_nnm_mix(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int6
     const int64_t m_pad = ceil_div(n, BM) * BM;
     const int64_t k_pad = ceil_div(n, BK) * BK;
     const size_t mask_bytes = static_cast<size_t>(k_pad) * m_pad * sizeof(float);
-    BYZ_TRY(ctx->nnm_mask.ensure(mask_bytes + static_cast<size_t>(n) * sizeof(int32_t)));
-    float* mask_t = ctx->nnm_mask.as<float>();
-    int32_t* row_count = reinterpret_cast<int32_t*>(ctx->nnm_mask.as<char>() + mask_bytes);
+    float* mask_t = nullptr;
+    int32_t* row_count = nullptr;
+    Carve c;
+    c.take(&mask_t, k_pad * m_pad);
+    c.take(&row_count, n);
+    BYZ_TRY(c.commit(ctx->nnm_mask));
     const int tiles_m = static_cast<int>(m_pad / BM);
     const int64_t n_tiles = static_cast<int64_t>(tiles_m) * ceil_div(n_cols, BN);
     const int64_t grid = ceil_div(n_tiles, 8) * 8;

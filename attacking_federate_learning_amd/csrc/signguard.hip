@@ -497,7 +497,6 @@ __global__ __launch_bounds__(kStepThreads) void sg_result_kernel(const double* _
     }
 }
 
-int64_t align8(int64_t bytes) { return (bytes + 7) / 8 * 8; }
 int64_t padded_rows(int64_t n) { return std::max<int64_t>(2, next_pow2(n)); }      // segment_sort_u64 takes two keys at least
 
 }  // namespace
@@ -507,39 +506,20 @@ int signguard_workspace(byz_ctx* ctx, int64_t n, int64_t n_cols, SgScratch* out)
     int64_t chunk_cols = 0;
     const int64_t chunks = n_cols > 0 ? geomed_chunks(ctx, n, n_cols, &chunk_cols) : 0;
     const int64_t n_pad = padded_rows(n);
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t here = at;
-        at += align8(bytes);
-        return here;
-    };
-    const int64_t o_qpart = take(chunks * n * 8), o_cpart = take(3 * chunks * n * 8), o_pznq = take(4 * n * 8);
-    const int64_t o_keys = take(n_pad * 8), o_seeds = take(n * 8), o_feat = take(3 * n * 8), o_centres = take(3 * n * 8);
-    const int64_t o_final = take(3 * n * 8), o_kth = take(kSgMaxSamples * 8), o_w = take(n * 8), o_state = take(64);
-    const int64_t o_ok = take(n * 4), o_members = take(n * 4), o_order = take(n * 4), o_standing = take(n * 4);
-    const int64_t o_rows = take(n * 4), o_keep = take(n * 4), o_labels = take(n * 4), o_sample = take(kSgMaxSamples * 4);
-    BYZ_TRY(ctx->signguard.ensure(static_cast<size_t>(at)));
-    char* base = ctx->signguard.as<char>();
-    out->q_part = reinterpret_cast<double*>(base + o_qpart);
-    out->cnt_part = reinterpret_cast<long long*>(base + o_cpart);
-    out->pznq = reinterpret_cast<double*>(base + o_pznq);
-    out->keys = reinterpret_cast<unsigned long long*>(base + o_keys);
-    out->seeds = reinterpret_cast<unsigned long long*>(base + o_seeds);
-    out->feat = reinterpret_cast<double*>(base + o_feat);
-    out->centres = reinterpret_cast<double*>(base + o_centres);
-    out->final_centres = reinterpret_cast<double*>(base + o_final);
-    out->kth = reinterpret_cast<double*>(base + o_kth);
-    out->w = reinterpret_cast<double*>(base + o_w);
-    out->state = base + o_state;
-    out->norm_ok = reinterpret_cast<int32_t*>(base + o_ok);
-    out->members = reinterpret_cast<int32_t*>(base + o_members);
-    out->order = reinterpret_cast<int32_t*>(base + o_order);
-    out->standing = reinterpret_cast<int32_t*>(base + o_standing);
-    out->label_rows = reinterpret_cast<int32_t*>(base + o_rows);
-    out->keep = reinterpret_cast<int32_t*>(base + o_keep);
-    out->labels = reinterpret_cast<int32_t*>(base + o_labels);
-    out->sample = reinterpret_cast<int32_t*>(base + o_sample);
-    return BYZ_OK;
+    Carve c;
+    c.take(&out->q_part, chunks * n);
+    c.take(&out->cnt_part, 3 * chunks * n);
+    c.take(&out->pznq, 4 * n);
+    c.take(&out->keys, n_pad);
+    c.take(&out->seeds, n);
+    for (double** xyz : {&out->feat, &out->centres, &out->final_centres}) c.take(xyz, 3 * n);
+    c.take(&out->kth, kSgMaxSamples);
+    c.take(&out->w, n);
+    c.take(&out->state, 64);               // SgState (launch_signguard_select asserts that it fits)
+    for (int32_t** per_row : {&out->norm_ok, &out->members, &out->order, &out->standing, &out->label_rows, &out->keep, &out->labels})
+        c.take(per_row, n);
+    c.take(&out->sample, kSgMaxSamples);
+    return c.commit(ctx->signguard);
 }
 
 int launch_row_signs(byz_ctx* ctx, const SgScratch& t, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t win_start,
