@@ -35,6 +35,11 @@ class SignGuardParams(ctypes.Structure):
                 ('bandwidth', ctypes.c_double), ('n_sample', c_i64)]
 
 
+class SparsefedParams(ctypes.Structure):
+    """byz_sparsefed_params: SparseFed's clipping norm and the coordinates applied per round."""
+    _fields_ = [('clip', ctypes.c_double), ('k', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -141,6 +146,12 @@ _PROTOTYPES = {
     'byz_robust_lr_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_bucket_means_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
     'byz_bucket_means_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp],
+    'byz_topk_sparsify_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_topk_info': [c_vp, _P(c_i64), _P(ctypes.c_uint32), _P(c_i64), _P(c_i64)],
+    'byz_topk_sparsify_host': [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp],
+    'byz_sparsefed_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(SparsefedParams), c_vp, c_vp, c_vp],
+    'byz_sparsefed_host': [c_vp, c_vp, c_i64, c_i64, _P(SparsefedParams), c_vp, c_vp],
+    'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

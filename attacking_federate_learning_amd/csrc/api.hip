@@ -1347,6 +1347,81 @@ int byz_bucket_means_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n
     return launch_bucket_means(ctx, G, n_rows, n_cols, ld, perm, s, Y, ldy, as_stream(stream));
 }
 
+// ---- SparseFed: global top-k with error feedback (Panda et al., AISTATS 2022; beyond the reference) --------------------------------
+namespace {
+
+bool vectors_overlap(const float* a, const float* b, int64_t n) { return a && b && a < b + n && b < a + n; }
+
+// an output may coincide with ONE input exactly (residual with x, out with add); an output that touches anything else is refused
+int check_topk(const char* who, const float* x, const float* add, int64_t n, int64_t k_max, int64_t k, const float* out,
+               const float* residual) {
+    if (k < 0 || k > k_max) {
+        set_error("%s: k = %lld outside 0..%lld (the length)", who, (long long)k, (long long)k_max);
+        return BYZ_E_INVALID;
+    }
+    const bool bad = vectors_overlap(out, x, n) || (out != add && vectors_overlap(out, add, n)) || vectors_overlap(out, residual, n) ||
+                     (residual != x && vectors_overlap(residual, x, n)) || vectors_overlap(residual, add, n);
+    if (bad) {
+        set_error("%s: an output overlaps another vector (residual may be x, out may be add, nothing else)", who);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_topk_sparsify_dev(byz_ctx* ctx, const float* x, const float* add, int64_t n, int64_t k, float* out, float* residual,
+                          void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(x && out && n > 0, "topk_sparsify: null vector or no columns (%lld)", (long long)n);
+    BYZ_TRY(check_topk("topk_sparsify", x, add, n, n, k, out, residual));
+    ctx->topk_stream = as_stream(stream);
+    return launch_topk_sparsify(ctx, x, add, n, k, 0, 1, nullptr, nullptr, out, residual, 0, stream);
+}
+
+int byz_topk_sparsify_sharded_dev(byz_ctx* ctx, const float* x, const float* add, int64_t n_local, int64_t n_total, int64_t k,
+                                  int rank_index, int rank_count, byz_allreduce_f64_fn allreduce, void* user, float* out,
+                                  float* residual, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(allreduce, "topk_sparsify_sharded: null all-reduce");
+    BYZ_REQUIRE(n_total > 0 && n_local >= 0 && n_local <= n_total, "topk_sparsify_sharded: %lld local columns of %lld",
+                (long long)n_local, (long long)n_total);
+    BYZ_REQUIRE(rank_count >= 1 && rank_count <= 65536 && rank_index >= 0 && rank_index < rank_count,
+                "topk_sparsify_sharded: rank %d of %d", rank_index, rank_count);
+    BYZ_REQUIRE(n_local == 0 || (x && out), "topk_sparsify_sharded: null vector");
+    BYZ_TRY(check_topk("topk_sparsify_sharded", x, add, n_local, n_total, k, out, residual));
+    ctx->topk_stream = as_stream(stream);
+    return launch_topk_sparsify(ctx, x, add, n_local, k, rank_index, rank_count, allreduce, user, out, residual, 0, stream);
+}
+
+int byz_topk_info(byz_ctx* ctx, int64_t* selected, uint32_t* threshold_key, int64_t* ties, int64_t* ties_taken) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->topk_stream));   // synchronises the last call's stream
+    if (selected) std::memcpy(selected, words + kTopkSelected, sizeof(int64_t));
+    if (ties) std::memcpy(ties, words + kTopkTies, sizeof(int64_t));
+    if (ties_taken) std::memcpy(ties_taken, words + kTopkTaken, sizeof(int64_t));
+    if (threshold_key) std::memcpy(threshold_key, words + kTopkKey, sizeof(uint32_t));
+    return BYZ_OK;
+}
+
+int byz_sparsefed_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_sparsefed_params* params,
+                      float* residual, float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "sparsefed"));
+    BYZ_REQUIRE(params && residual && out, "sparsefed: null parameters, memory or output");
+    const byz_cclip_params clip = {params->clip, 1};
+    BYZ_TRY(check_cclip(&clip, n_rows, "sparsefed"));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "sparsefed"));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, residual, "sparsefed"));
+    BYZ_TRY(check_topk("sparsefed", residual, nullptr, n_cols, n_cols, params->k, out, nullptr));
+    float* agg = topk_aggregate_workspace(ctx, n_cols);
+    if (agg == nullptr) return BYZ_E_HIP;
+    BYZ_TRY(centered_clip(ctx, G, n_rows, n_cols, ld, &clip, nullptr, nullptr, nullptr, agg, nullptr, stream));
+    ctx->topk_stream = as_stream(stream);
+    return launch_topk_sparsify(ctx, residual, agg, n_cols, params->k, 0, 1, nullptr, nullptr, out, residual, n_cols, stream);
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -1842,6 +1917,38 @@ int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int
     st.in(&perm, perm_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_bucket_means_dev(ctx, st.G(), n_rows, n_cols, n_cols, perm, s, Y, n_cols, st.stream()));
+    return st.finish();
+}
+
+int byz_topk_sparsify_host(byz_ctx* ctx, const float* x_host, const float* add_host, int64_t n, int64_t k, float* out_host,
+                           float* residual_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(x_host && out_host && n > 0, "topk_sparsify: null vector or no columns (%lld)", (long long)n);
+    BYZ_TRY(check_topk("topk_sparsify", x_host, add_host, n, n, k, out_host, residual_host));
+    HostStage st(ctx);     // x is the staged "matrix" (one row); the device call is out of place, so the host vectors may coincide
+    float *add, *out, *residual;
+    st.in(&add, add_host, n);
+    st.out(&out, out_host, n);
+    st.out(&residual, residual_host, n);
+    BYZ_TRY(st.stage(x_host, 1, n));
+    BYZ_TRY(byz_topk_sparsify_dev(ctx, st.G(), add, n, k, out, residual, st.stream()));
+    return st.finish();
+}
+
+int byz_sparsefed_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_sparsefed_params* params,
+                       float* residual_host, float* out_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "sparsefed"));
+    BYZ_REQUIRE(params && residual_host && out_host, "sparsefed: null parameters, memory or output");
+    const byz_cclip_params clip = {params->clip, 1};
+    BYZ_TRY(check_cclip(&clip, n_rows, "sparsefed"));
+    BYZ_TRY(check_topk("sparsefed", residual_host, nullptr, n_cols, n_cols, params->k, out_host, nullptr));
+    HostStage st(ctx);
+    float *residual, *out;
+    st.inout(&residual, static_cast<const float*>(residual_host), residual_host, n_cols);
+    st.out(&out, out_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_sparsefed_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, residual, out, st.stream()));
     return st.finish();
 }
 

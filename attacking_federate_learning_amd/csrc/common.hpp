@@ -158,6 +158,9 @@ struct byz_ctx {
     hipStream_t rlr_stream = nullptr;      // stream of the last sign vote or flip (byz_robust_lr_info syncs it)
     byz::Buffer signguard;       // SignGuard, carved into SgScratch's arrays (signguard_workspace): the census partials, then the selection's
     hipStream_t signguard_stream = nullptr;   // stream of the last SignGuard selection (byz_signguard_info syncs it)
+    byz::Buffer topk;            // top-k along a vector, carved (topk.hip: TopkScratch): the three histograms and the state, the chunk
+                                 // arrays, the doubles of the columns layout, SparseFed's aggregate
+    hipStream_t topk_stream = nullptr;     // stream of the last top-k (byz_topk_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -203,7 +206,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 52;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 60;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -232,6 +235,8 @@ constexpr int kRlrFlipped = 38;
 // bandwidth h, the median norm M, and K = the kept rows as the divisor of the sum
 constexpr int kSgKept = 40, kSgNormFailed = 41, kSgOutside = 42, kSgClusters = 43, kSgSeeds = 44, kSgFlat = 45;
 constexpr int kSgBandwidth = 46, kSgMedian = 48, kSgKeptF64 = 50;
+// top-k along a vector: four 64-bit words (8-byte aligned): selected, the ties at the threshold, the ties taken, the threshold key
+constexpr int kTopkSelected = 52, kTopkTies = 54, kTopkTaken = 56, kTopkKey = 58;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -244,6 +249,10 @@ inline int32_t* krum_winner_word(byz_ctx* ctx) { return ctx->small.as<int32_t>()
 inline int32_t* geomed_words(byz_ctx* ctx) { return ctx->small.as<int32_t>(); }
 inline unsigned long long* rlr_flip_counter(byz_ctx* ctx) {
     return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kRlrFlipped);
+}
+
+inline unsigned long long* topk_info_words(byz_ctx* ctx) {
+    return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kTopkSelected);
 }
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).
@@ -458,6 +467,14 @@ int launch_sign_flip(byz_ctx* ctx, const float* agg, const int32_t* votes, int64
 // arithmetic (perm == nullptr: the identity); an entry of perm outside [0, n) is skipped, the divisor stays the bucket's length
 int launch_bucket_means(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* perm, int64_t s,
                         float* Y, int64_t ldy, hipStream_t stream);
+// topk.hip: the k columns of w = x (+ add) first in the order (key = bits & 0x7fffffff descending, column ascending) into out, the
+// rest into residual (optional); residual may be x and out may be add.  allreduce == nullptr: one GPU holds the vector (rank 0
+// of 1); otherwise this rank's slice of a vector of which k is the global count (four all-reduces: 2048, 1024, 1024 and
+// rank_count doubles).  keep_agg_cols: the floats of topk_aggregate_workspace that must survive the call (0: none).
+int launch_topk_sparsify(byz_ctx* ctx, const float* x, const float* add, int64_t n, int64_t k, int rank_index, int rank_count,
+                         byz_allreduce_f64_fn allreduce, void* user, float* out, float* residual, int64_t keep_agg_cols, void* stream);
+// n_cols floats of the top-k workspace for SparseFed's aggregate (nullptr: the allocation failed, the error text is set)
+float* topk_aggregate_workspace(byz_ctx* ctx, int64_t n_cols);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
                              int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
                              hipStream_t stream);

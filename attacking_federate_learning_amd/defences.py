@@ -197,6 +197,44 @@ def robust_lr(users_grads, users_count, corrupted_count, theta=None, then=None, 
     return (out, votes) if return_votes else out
 
 
+def sparsefed(users_grads, users_count, corrupted_count, k=None, clip=10.0, residual=None, then=None, return_residual=False,
+              **then_kwargs):
+    """SparseFed (Panda, Mahloujifar, Bhagoji, Chakraborty and Mittal, AISTATS 2022; not in the reference), the other defence
+    designed for model poisoning such as the backdoor attack: the aggregate is added to an error-feedback memory W and only
+    the k coordinates of W with the largest magnitude are applied; the rest stay in W for later rounds.  then=None is the
+    paper's rule -- every client clipped to norm `clip`, then the mean (centered_clip from zero with one iteration) -- and
+    runs as ONE library call.  With a callable the aggregate is then(users_grads, users_count, corrupted_count,
+    **then_kwargs) -- `coordinate_median`, `trimmed_mean`, ... -- on the device-resident matrix (a host matrix is uploaded
+    once) and the top-k a call of its own; `clip` is then unused.  `residual` is the caller's memory W, updated IN PLACE when
+    given (a writable float32 numpy vector for a host matrix, a device-resident one for a device matrix); None means a
+    zero memory.  k: an integer in [0, D]; the default max(1, D // 100) is this package's choice, the paper fixes no
+    formula.  The selection's order is total: magnitude by the bits (zeros tie, infinities above every finite value, NaN
+    above them, nothing sanitised), ties to the lower column.  return_residual=True returns (step, residual).  Not one of
+    the `defend` keys: the reference's main.py offers only those four."""
+    engine = get_engine()
+    d = int(users_grads.shape[1])
+    if k is None:
+        k = max(1, d // 100)
+    k = engine._topk_k(k, d)
+    if then is None:
+        out, res = engine.sparsefed(users_grads, k, clip=clip, residual=residual)
+        return (out, res) if return_residual else out
+    if not callable(then):
+        raise TypeError('sparsefed: `then` is the rule that supplies the aggregate, e.g. defences.coordinate_median, or None')
+    host = engine._device_matrix(users_grads) is None
+    if host:
+        users_grads = engine.to_device(engine._host_matrix(users_grads))
+    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
+    if residual is None:
+        out, res = engine.topk_sparsify(agg, k)              # a zero memory: W is the aggregate
+    else:
+        out, res = engine.topk_sparsify(residual, k, add=agg, residual=residual)
+    if host:
+        out = out.numpy() if isinstance(out, DeviceBuffer) else out
+        res = res.numpy() if isinstance(res, DeviceBuffer) else res
+    return (out, res) if return_residual else out
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

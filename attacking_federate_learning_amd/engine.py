@@ -1319,6 +1319,169 @@ class Engine:
             self.synchronize(dm.stream)      # the uploaded permutation must outlive the kernel
         return y
 
+    # ---- SparseFed: global top-k with error feedback (Panda et al., AISTATS 2022; not in the reference) ----
+    @staticmethod
+    def _topk_k(k, n=None):
+        if isinstance(k, bool) or int(k) != k:
+            raise ValueError('k must be an integer, got %r' % (k,))
+        k = int(k)
+        if k < 0 or (n is not None and k > n):
+            raise ValueError('k = %d outside 0..%s (the length)' % (k, 'n' if n is None else n))
+        return k
+
+    @staticmethod
+    def _on_device(v):
+        return isinstance(v, DeviceBuffer) or (_is_torch(v) and v.is_cuda)
+
+    @staticmethod
+    def _host_f32(v, n=None, writable=False):
+        """A flat C-contiguous float32 host vector: `v` itself where it already is one (required when the call writes it)."""
+        if writable:
+            if not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.flags.c_contiguous and v.flags.writeable):
+                raise ValueError('a host vector that is written must be a writable C-contiguous float32 numpy array')
+            host = v.reshape(-1)
+        else:
+            if isinstance(v, DeviceBuffer):
+                v = v.numpy()
+            host = np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float32).reshape(-1)
+        if n is not None and host.size != n:
+            raise ValueError('expected %d values, got %d' % (n, host.size))
+        return host
+
+    def _device_out(self, v, n, what):
+        if not self._on_device(v):
+            raise ValueError('%s must be a device-resident float32 vector of %d entries' % (what, n))
+        (ptr,), size, _, _, _ = self._vectors(v)
+        if size != n:
+            raise ValueError('%s has %d entries, expected %d' % (what, size, n))
+        return ptr
+
+    def topk_info(self):
+        """{selected, threshold_key, ties, ties_taken} of the last top-k on this engine (synchronises): selected == k, the
+        threshold key T = the k-th largest of bits & 0x7fffffff (0xffffffff for k = 0), the columns whose key is T and how
+        many of them were taken (the first in index order)."""
+        sel, ties, taken, key = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_uint32(0)
+        _check(self.lib.byz_topk_info(self.ctx, ctypes.byref(sel), ctypes.byref(key), ctypes.byref(ties), ctypes.byref(taken)))
+        return {'selected': int(sel.value), 'threshold_key': int(key.value), 'ties': int(ties.value),
+                'ties_taken': int(taken.value)}
+
+    def topk_sparsify(self, x, k, add=None, out=None, residual=None, return_info=False):
+        """(out, residual) of the global top-k of w = x (add=None) or fl32(x + add): the k columns first in the order (key =
+        bits(w) & 0x7fffffff descending, column ascending) keep w's bits in out and are +0.0 in residual, the others the
+        other way round.  Zeros of both signs tie at key 0, both infinities rank above every finite value and a NaN above
+        them; nothing is sanitised.  k: an integer in [0, n].  numpy in -> numpy out; device-resident x -> device-resident
+        out.  out / residual: vectors to write (device-resident for a device x); residual=x and out=add are the in-place
+        round.  return_info=True also returns topk_info()."""
+        if not self._on_device(x):
+            xh = self._host_f32(x)
+            n = xh.size
+            k = self._topk_k(k, n)
+            ah = self._host_f32(add, n) if add is not None else None
+            oh = self._host_f32(out, n, writable=True) if out is not None else np.empty(n, dtype=np.float32)
+            rh = self._host_f32(residual, n, writable=True) if residual is not None else np.empty(n, dtype=np.float32)
+            _check(self.lib.byz_topk_sparsify_host(self.ctx, xh.ctypes.data_as(ctypes.c_void_p),
+                                                   ah.ctypes.data_as(ctypes.c_void_p) if ah is not None else None, n, k,
+                                                   oh.ctypes.data_as(ctypes.c_void_p), rh.ctypes.data_as(ctypes.c_void_p)))
+            oh, rh = (out if out is not None else oh), (residual if residual is not None else rh)     # the caller's own arrays
+            return (oh, rh, self.topk_info()) if return_info else (oh, rh)
+        vectors = (x,) if add is None else (x, add)
+        ptrs, n, stream, keep, example = self._vectors(*vectors)
+        k = self._topk_k(k, n)
+        xptr, aptr = ptrs[0], (ptrs[1] if add is not None else None)
+        if out is None:
+            out, optr = self._out_like(example, n)
+        else:
+            optr = self._device_out(out, n, 'out')
+        if residual is None:
+            residual, rptr = self._out_like(example, n)
+        else:
+            rptr = self._device_out(residual, n, 'residual')
+        _check(self.lib.byz_topk_sparsify_dev(self.ctx, _vp(xptr), _vp(aptr), n, k, _vp(optr), _vp(rptr), _vp(stream)))
+        if add is not None and not self._on_device(add):
+            self.synchronize(stream)                 # an uploaded add must outlive the kernels
+        return (out, residual, self.topk_info()) if return_info else (out, residual)
+
+    def topk_sparsify_sharded(self, x_local, k, n_total, rank, world, add=None, all_reduce=None, out=None, residual=None,
+                              return_info=False):
+        """The columns layout's top-k on this rank's slice (byz_topk_sparsify_sharded_dev): rank `rank` of `world` holds
+        x_local, consecutive columns of a vector of n_total, the slices in rank order; k is the global count.
+        all_reduce(tensor) sums a CUDA fp64 tensor in place over the ranks on the current stream (None: one rank).  Four
+        all-reduces whatever the data: 2048, 1024, 1024 and `world` doubles.  Returns this rank's (out, residual); the
+        selected set is topk_sparsify's on the concatenated vector, bit for bit."""
+        if not self._on_device(x_local) or (add is not None and not self._on_device(add)):
+            raise ValueError('topk_sparsify_sharded() takes device-resident vectors')
+        vectors = (x_local,) if add is None else (x_local, add)
+        ptrs, n, stream, keep, example = self._vectors(*vectors)
+        n_total, rank, world = int(n_total), int(rank), int(world)
+        if world < 1 or not 0 <= rank < world or n > n_total:
+            raise ValueError('rank %d of %d with %d of %d columns' % (rank, world, n, n_total))
+        k = self._topk_k(k, n_total)
+        device = self.device
+
+        def reduce_on_ranks(user, buf, count, stream_):
+            try:
+                if all_reduce is not None:
+                    import torch
+                    all_reduce(torch.as_tensor(_DeviceF64(buf, count), device='cuda:%d' % device))
+                return 0
+            except Exception:      # noqa: BLE001  (a Python exception must not unwind through the C frames)
+                return 1
+        callback = _native.ALLREDUCE_F64_FN(reduce_on_ranks)
+        if out is None:
+            out, optr = self._out_like(example, n)
+        else:
+            optr = self._device_out(out, n, 'out')
+        if residual is None:
+            residual, rptr = self._out_like(example, n)
+        else:
+            rptr = self._device_out(residual, n, 'residual')
+        _check(self.lib.byz_topk_sparsify_sharded_dev(self.ctx, _vp(ptrs[0]), _vp(ptrs[1] if add is not None else None), n,
+                                                      n_total, k, rank, world, ctypes.cast(callback, ctypes.c_void_p), None,
+                                                      _vp(optr), _vp(rptr), _vp(stream)))
+        return (out, residual, self.topk_info()) if return_info else (out, residual)
+
+    def sparsefed(self, g, k, clip=10.0, residual=None, return_info=False):
+        """One round of SparseFed: agg = centered_clip(g, tau=clip, iters=1) (the norm-clipped mean: every row scaled to norm
+        `clip` at most, rows with a non-finite entry excluded and still counted in the divisor), W = residual + agg, the k
+        columns of W first in topk_sparsify's order are the step, the rest stay in the memory.  Returns (out, residual);
+        `residual` is the caller's memory W, updated IN PLACE when given (a writable float32 numpy vector for a host g, a
+        device-resident one for a device g); None is a zero memory and a fresh one comes back.  One library call.
+        return_info=True also returns topk_info() with centered_clip_info()'s clipped_rows and excluded_rows."""
+        params = _native.SparsefedParams(float(clip), 0)
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            params.k = self._topk_k(k, d)
+            if residual is not None and self._on_device(residual):
+                raise ValueError('a host matrix takes a host memory (a float32 numpy vector)')
+            res = self._host_f32(residual, d, writable=True) if residual is not None else np.zeros(d, dtype=np.float32)
+            out = np.empty(d, dtype=np.float32)
+            _check(self.lib.byz_sparsefed_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                               res.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p)))
+            res = residual if residual is not None else res       # the caller's own array
+        else:
+            d = dm.cols
+            params.k = self._topk_k(k, d)
+            if residual is None:
+                if dm.torch_like is not None:
+                    import torch
+                    res = torch.zeros(d, dtype=torch.float32, device=dm.torch_like.device)
+                    rptr = res.data_ptr()
+                else:
+                    res = self.to_device(np.zeros(d, dtype=np.float32))
+                    rptr = res.ptr
+            else:
+                res, rptr = residual, self._device_out(residual, d, 'residual')
+            out, optr = self._out_like(dm, d)
+            _check(self.lib.byz_sparsefed_dev(self.ctx, _vp(dm.ptr), dm.rows, d, dm.ld, ctypes.byref(params), _vp(rptr),
+                                              _vp(optr), _vp(dm.stream)))
+        if not return_info:
+            return out, res
+        info = self.topk_info()
+        info['clipped_rows'], info['excluded_rows'] = self.centered_clip_info()
+        return out, res, info
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

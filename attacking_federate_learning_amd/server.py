@@ -15,6 +15,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_nnm(then)                  the same step with nearest-neighbour mixing in front of the rule `then`
     defend_robust_lr(theta, then)     the same step with the robust learning rate round the mean or the rule `then`
     defend_bucketing(then, s)         the same step with s-bucketing, reshuffled every round, in front of the rule `then`
+    defend_sparsefed(k, clip, then)   the same step with SparseFed: only the k heaviest coordinates of an error-feedback memory
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -43,6 +44,8 @@ class DeviceServer:
         self.bucketing_round = 0
         # SignGuard's history: the calls of defend_signguard so far (the default seed of the next window and sample)
         self.signguard_round = 0
+        # SparseFed's history: the error-feedback memory W (zeros before the first round)
+        self.sparse_residual = torch.zeros_like(self.current_weights)
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -153,6 +156,24 @@ class DeviceServer:
         self.bucketing_round += 1
         current_grads = defences.bucketing(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), s=s,
                                            then=then, seed=seed, **then_kwargs)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with SparseFed, the one defence that keeps what it did not apply -------------------
+    def defend_sparsefed(self, k=None, clip=10.0, then=None, **then_kwargs):
+        """SparseFed on this round's gradients (defences.sparsefed): the clipped mean (then=None) or the rule `then(grads,
+        n_users, n_malicious, **then_kwargs)` is added to `sparse_residual`, the error-feedback memory this server keeps
+        (zeros at construction), the k coordinates of the memory with the largest magnitude (default max(1, D // 100)) are
+        taken out of it as the step, and server.py:89-90's momentum step runs on that sparse vector, as `defend` takes it.
+        With momentum = 0 this is the paper's Algorithm 1: a constant learning rate in front of W does not change which
+        coordinates are largest, so scaling the step after the selection equals scaling the aggregates before it.  The
+        paper's optional momentum sits BEFORE the memory (it smooths the aggregate that enters W); this server's sits AFTER
+        it, on the sparse step, because the velocity is the reference's and every defend_* shares it."""
+        if then is not None and not callable(then):
+            raise TypeError('defend_sparsefed: `then` is the rule that supplies the aggregate, or None for the clipped mean')
+        current_grads = defences.sparsefed(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), k=k, clip=clip,
+                                           residual=self.sparse_residual, then=then, **then_kwargs)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

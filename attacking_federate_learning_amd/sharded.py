@@ -142,6 +142,11 @@ class HipKernels:
     def robust_lr(self, g_local, theta, return_votes=False):
         return self.engine.robust_lr(g_local, theta, return_votes=return_votes)
 
+    def topk_sparsify_sharded(self, x_local, k, n_total, rank, world, add=None, all_reduce=None, residual=None):
+        # this rank's (step, memory) of the global top-k; the bins of every pass and the ranks' ties go through all_reduce
+        return self.engine.topk_sparsify_sharded(x_local, k, n_total, rank, world, add=add, all_reduce=all_reduce,
+                                                 residual=residual)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -340,6 +345,27 @@ class ShardedAggregator:
         if theta is None:
             theta = int(corrupted_count) + 1
         return self._maybe_gather(self.kernels.robust_lr(g_local, theta), gather, total_columns)
+
+    def sparsefed(self, g_local, users_count, corrupted_count, k, clip=10.0, residual_local=None, total_columns=None,
+                  gather=False):
+        """SparseFed (defences.sparsefed's contract with then=None), columns layout: the clipped mean is this aggregator's
+        centered_clip(iters=1) -- one all-reduce of N doubles --, and the top-k, the one step that is NOT local to a column,
+        is kernels.topk_sparsify_sharded: four all-reduces (2048, 1024, 1024 and `world` doubles) whatever the data.  k and
+        total_columns are the global figures (total_columns is needed beyond one rank); residual_local is this rank's slice
+        of the memory, updated in place when given (None: zeros).  Returns (step, residual), this rank's columns of each
+        (gather=True: the whole step)."""
+        import torch
+        n, d_local = g_local.shape
+        if self.world > 1 and total_columns is None:
+            raise ValueError('sparsefed() over several ranks needs total_columns')
+        total = int(total_columns) if total_columns is not None else int(d_local)
+        agg = self.centered_clip(g_local, tau=clip, iters=1)
+        if residual_local is None:
+            residual_local = torch.zeros(d_local, dtype=torch.float32, device=g_local.device)
+        reduce = (lambda t: self._all_reduce('allreduce_topk', t)) if self._collective() else None
+        out, res = self.kernels.topk_sparsify_sharded(residual_local, k, total, self.rank, self.world, add=agg, all_reduce=reduce,
+                                                      residual=residual_local)
+        return self._maybe_gather(out, gather, total_columns), res
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

@@ -530,6 +530,55 @@ int byz_bucket_means_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64
 int byz_bucket_means_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                           const int32_t* perm_host_or_null, int64_t s, float* Y_host);
 
+/* ---- SparseFed: global top-k with error feedback (Panda, Mahloujifar, Bhagoji, Chakraborty & Mittal, "SparseFed:          */
+/* Mitigating Model Poisoning Attacks in Federated Learning with Sparsification", AISTATS 2022; not in the reference) ----   */
+/* The second defence against the backdoor attack, certified against model poisoning: every client is clipped to norm L and  */
+/* the clipped updates are averaged; the average is added to an error-feedback memory W; only the k coordinates of W with    */
+/* the largest magnitude are applied and cleared, the rest stay in W for later rounds.                                       */
+/* The new piece is a selection ALONG a vector of n fp32 values, byz_topk_sparsify_dev:                                      */
+/*   w[c]   = add given ? fl32(x[c] + add[c]) : x[c]                    one fp32 addition: the error-feedback step fused in   */
+/*   key[c] = bits(w[c]) & 0x7fffffff                                   31 bits, compared as integers                         */
+/*   the k columns first in the order (key descending, column index ascending) are SELECTED                                  */
+/*   out[c] = selected ? w[c] : +0.0          residual[c] = selected ? +0.0 : w[c]            w's bits verbatim               */
+/* The key is decided on the bits whatever the denormal mode: +0.0 and -0.0 tie at key 0, denormals rank by their bits, both  */
+/* infinities rank above every finite value and a NaN of either sign above the infinities, where its bits fall.  NOTHING IS  */
+/* SANITISED (bucketing's and the robust learning rate's convention): a NaN in the memory is selected first and shows in the */
+/* step instead of being parked in W for ever; a selected -0.0 or NaN payload comes back as it is.  Equivalently, with T the */
+/* k-th largest key: every column with key > T is selected (`above` of them) and of the `ties` columns with key == T the      */
+/* first k - above in index order.  The order is total: two runs, an aligned and a misaligned caller and the sharded path    */
+/* select the same set.  k = 0: out all +0.0, residual = w.  k = n: out = w, residual all +0.0.                               */
+/* n >= 1, k in [0, n] (BYZ_E_INVALID outside); add_dev_or_null and residual_dev_or_null are optional.  residual_dev may be   */
+/* x_dev and out_dev may be add_dev (the in-place round: W updated where it lies, the step written over the aggregate); the   */
+/* two inputs may overlap each other; any other overlap of an output with another vector: BYZ_E_INVALID, nothing written.     */
+/* A three-pass radix select (11 + 10 + 10 bits) with integer atomics only, so no bit depends on the scheduling; every launch */
+/* is enqueued up front and nothing synchronises with the host.  Cost: four reads of x (and add), five when the ties at T    */
+/* are rationed, and one write of out (and residual).                                                                        */
+int byz_topk_sparsify_dev(byz_ctx* ctx, const float* x_dev, const float* add_dev_or_null, int64_t n, int64_t k,
+                          float* out_dev, float* residual_dev_or_null, void* stream);
+/* The last top-k call on this context: selected (== k), the threshold key T (0xffffffff for k = 0: above every key), the    */
+/* ties at T and how many of them were taken (the sharded call: the global figures).  Synchronises that call's stream.       */
+int byz_topk_info(byz_ctx* ctx, int64_t* selected, uint32_t* threshold_key, int64_t* ties, int64_t* ties_taken);
+/* The same on host vectors (out_host: n floats; add_host_or_null, residual_host_or_null optional; residual_host may be       */
+/* x_host and out_host may be add_host).  Synchronous.                                                                       */
+int byz_topk_sparsify_host(byz_ctx* ctx, const float* x_host, const float* add_host_or_null, int64_t n, int64_t k,
+                           float* out_host, float* residual_host_or_null);
+
+/* SparseFed's round.  agg = byz_centered_clip_dev(G, tau = clip, iters = 1, start = NULL) into a context workspace (its     */
+/* contract and its checks: clip > 0, +inf allowed; non-finite rows excluded and still counted in n), then                   */
+/* byz_topk_sparsify_dev(x = residual, add = agg, n_cols, k, out, residual) in place on residual_dev (n_cols floats, in/out,  */
+/* the caller's memory W; the caller zeroes it before the first round).  out_dev must not overlap G or residual_dev, and      */
+/* residual_dev must not overlap G (BYZ_E_INVALID).  byz_centered_clip_info and byz_topk_info describe the call.  No doubles  */
+/* by value, as elsewhere.                                                                                                   */
+typedef struct byz_sparsefed_params {
+    double clip;    /* the clients' norm bound L: > 0, +inf allowed */
+    int64_t k;      /* coordinates applied per round: 0 .. n_cols   */
+} byz_sparsefed_params;
+int byz_sparsefed_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                      const byz_sparsefed_params* params, float* residual_dev, float* out_dev, void* stream);
+/* The same on a host matrix (residual_host: n_cols floats, in/out; out_host: n_cols floats).  Synchronous.                  */
+int byz_sparsefed_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_sparsefed_params* params,
+                       float* residual_host, float* out_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -681,6 +730,21 @@ int byz_dnc_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, 
                         const byz_dnc_params* params, const int64_t* columns_local_dev,
                         const int64_t* local_counts, byz_allreduce_f64_fn allreduce, void* user,
                         float* out_local_dev, int32_t* good_dev, void* stream);
+
+/* Top-k over the slices: the one step here that is NOT local to a column.  Rank rank_index of rank_count holds n_local      */
+/* consecutive columns (0 is allowed; the vectors may then be NULL); the slices follow one another in rank order, so a        */
+/* column's global index is ordered by (rank, local index).  k and n_total are the GLOBAL figures (0 <= k <= n_total,         */
+/* n_local <= n_total, 0 <= rank_index < rank_count; BYZ_E_INVALID otherwise).  Per select pass ONE all-reduce of the pass's  */
+/* bins as doubles (a count is exact as a double), then ONE of rank_count doubles (every rank's ties at T in its own slot,    */
+/* zero elsewhere: a gather by summation) from which a rank takes its share of the tie quota after the ranks before it.       */
+/* That is FOUR calls, of 2048, 1024, 1024 and rank_count doubles in that order: constants of the build, the same on every   */
+/* rank whatever the data, k = 0 and k = n_total included.  The selected set is byz_topk_sparsify_dev's on the concatenated  */
+/* vector, bit for bit.  The overlap rules are byz_topk_sparsify_dev's.  There is no byz_sparsefed_sharded_dev: a host calls */
+/* byz_centered_clip_sharded_dev (iters = 1, no start) and then this entry point with x = its slice of W, add = its slice of */
+/* the aggregate.                                                                                                            */
+int byz_topk_sparsify_sharded_dev(byz_ctx* ctx, const float* x_local_dev, const float* add_local_dev_or_null, int64_t n_local,
+                                  int64_t n_total, int64_t k, int rank_index, int rank_count, byz_allreduce_f64_fn allreduce,
+                                  void* user, float* out_local_dev, float* residual_local_dev_or_null, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
