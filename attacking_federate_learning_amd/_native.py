@@ -40,6 +40,17 @@ class SparsefedParams(ctypes.Structure):
     _fields_ = [('clip', ctypes.c_double), ('k', c_i64)]
 
 
+class NoiseParams(ctypes.Structure):
+    """byz_noise_params: the noise's standard deviation and where in the Philox stream the vector lies."""
+    _fields_ = [('sigma', ctypes.c_double), ('seed', ctypes.c_uint64), ('round', ctypes.c_uint64), ('column_offset', c_i64)]
+
+
+class WeakDpParams(ctypes.Structure):
+    """byz_weak_dp_params: the norm bound (or adaptive: the median norm), the noise and its place in the stream."""
+    _fields_ = [('clip', ctypes.c_double), ('sigma', ctypes.c_double), ('adaptive', c_i64), ('seed', ctypes.c_uint64),
+                ('round', ctypes.c_uint64), ('column_offset', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -151,6 +162,13 @@ _PROTOTYPES = {
     'byz_topk_sparsify_host': [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_sparsefed_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(SparsefedParams), c_vp, c_vp, c_vp],
     'byz_sparsefed_host': [c_vp, c_vp, c_i64, c_i64, _P(SparsefedParams), c_vp, c_vp],
+    'byz_gaussian_noise_dev': [c_vp, c_vp, c_i64, _P(NoiseParams), c_vp, c_vp, c_vp],
+    'byz_noise_words_dev': [c_vp, _P(NoiseParams), c_i64, c_vp, c_vp],
+    'byz_gaussian_noise_host': [c_vp, c_vp, c_i64, _P(NoiseParams), c_vp],
+    'byz_clip_scales_dev': [c_vp, c_vp, c_i64, _P(WeakDpParams), c_vp, c_vp, c_vp],
+    'byz_weak_dp_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double)],
+    'byz_weak_dp_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(WeakDpParams), c_vp, c_vp],
+    'byz_weak_dp_host': [c_vp, c_vp, c_i64, c_i64, _P(WeakDpParams), c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

@@ -1422,6 +1422,104 @@ int byz_sparsefed_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     return launch_topk_sparsify(ctx, residual, agg, n_cols, params->k, 0, 1, nullptr, nullptr, out, residual, n_cols, stream);
 }
 
+// ---- clip and noise, "weak DP" (Sun et al. 2019; FLAME's last stage; beyond the reference) ------------------------------------------
+namespace {
+
+constexpr int64_t kNoiseMaxColumn = int64_t{1} << 62;
+
+// (written so that a NaN sigma fails the test)
+int check_noise(const char* who, double sigma, int64_t column_offset, int64_t n) {
+    if (!(sigma >= 0.0) || !__builtin_isfinite(sigma)) {
+        set_error("%s: sigma = %g must be finite and >= 0", who, sigma);
+        return BYZ_E_INVALID;
+    }
+    if (n < 1 || column_offset < 0 || n > kNoiseMaxColumn - column_offset) {
+        set_error("%s: %lld columns from global column %lld (at least one, from 0 on, up to 2^62)", who, (long long)n,
+                  (long long)column_offset);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+int check_weak_dp(const char* who, const byz_weak_dp_params* params, int64_t n_rows, int64_t n_cols) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!params->adaptive && !(params->clip > 0.0)) {      // (a NaN fails; +inf passes, as centered clipping's tau)
+        set_error("%s: clip = %g must be > 0 in the fixed mode", who, params->clip);
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_noise(who, params->sigma, params->column_offset, n_cols));
+    return check_row_ceiling(who, n_rows);
+}
+
+}  // namespace
+
+int byz_gaussian_noise_dev(byz_ctx* ctx, const float* x, int64_t n, const byz_noise_params* params, const double* scale_dev,
+                           float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(x && out && params, "gaussian_noise: null vector or parameters");
+    BYZ_TRY(check_noise("gaussian_noise", params->sigma, params->column_offset, n));
+    BYZ_REQUIRE(out == x || !vectors_overlap(x, out, n), "gaussian_noise: the output overlaps x (it may BE x, nothing else)");
+    hipStream_t s = as_stream(stream);
+    if (params->sigma == 0.0 && scale_dev == nullptr) {      // x's bits verbatim (an addition of 0.0 would turn -0.0 into +0.0)
+        if (out != x) BYZ_HIP(hipMemcpyAsync(out, x, static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return BYZ_OK;
+    }
+    return launch_gaussian_noise(ctx, x, n, params->sigma, params->seed, params->round, params->column_offset, scale_dev, out, s);
+}
+
+int byz_noise_words_dev(byz_ctx* ctx, const byz_noise_params* params, int64_t n, uint32_t* words, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(words && params, "noise_words: null output or parameters");
+    BYZ_TRY(check_noise("noise_words", 0.0, params->column_offset, n));
+    return launch_noise_words(ctx, params->seed, params->round, params->column_offset, n, words, as_stream(stream));
+}
+
+int byz_clip_scales_dev(byz_ctx* ctx, const double* sq, int64_t n_rows, const byz_weak_dp_params* params, double* scales,
+                        double* clip_dev, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(sq && scales && n_rows > 0, "clip_scales: null norms or scales, or no rows (%lld)", (long long)n_rows);
+    BYZ_REQUIRE(params && (params->adaptive || params->clip > 0.0), "clip_scales: null parameters, or clip not > 0 in the fixed mode");
+    BYZ_TRY(check_row_ceiling("clip_scales", n_rows));
+    ctx->weak_dp_stream = as_stream(stream);
+    return launch_clip_scales(ctx, sq, n_rows, params->clip, params->adaptive != 0, scales, clip_dev, as_stream(stream));
+}
+
+int byz_weak_dp_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows, double* clip) {
+    BYZ_TRY(enter(ctx));
+    int32_t words[kSmallWords];
+    BYZ_TRY(read_small(ctx, words, ctx->weak_dp_stream));   // synchronises the last call's stream
+    if (clipped_rows) *clipped_rows = words[kWeakDpClipped];
+    if (excluded_rows) *excluded_rows = words[kWeakDpExcluded];
+    if (clip) std::memcpy(clip, words + kWeakDpClip, sizeof(double));
+    return BYZ_OK;
+}
+
+// centered_clip's one iteration from zero with the scales' clip chosen by the mode, then the noise in place on out
+int byz_weak_dp_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_weak_dp_params* params,
+                    float* out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "weak_dp"));
+    BYZ_REQUIRE(out, "weak_dp: null output");
+    BYZ_TRY(check_weak_dp("weak_dp", params, n_rows, n_cols));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "weak_dp"));
+    hipStream_t s = as_stream(stream);
+    const bool adaptive = params->adaptive != 0;
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n_rows, n_cols, &t));
+    double *sq = t.a, *scale = t.b;
+    ctx->weak_dp_stream = s;
+    BYZ_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(n_cols) * sizeof(float), s));
+    BYZ_TRY(launch_row_sqdist(ctx, G, n_rows, n_cols, ld, out, t.partials, sq, nullptr, nullptr, s));
+    BYZ_TRY(launch_clip_scales(ctx, sq, n_rows, params->clip, adaptive, scale, nullptr, s));
+    BYZ_TRY(launch_clip_update(ctx, G, n_rows, n_cols, ld, out, scale, out, s));
+    if (params->sigma == 0.0) return BYZ_OK;               // the clipped mean's bits
+    return launch_gaussian_noise(ctx, out, n_cols, params->sigma, params->seed, params->round, params->column_offset,
+                                 adaptive ? weak_dp_clip_word(ctx) : nullptr, out, s);
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -1949,6 +2047,33 @@ int byz_sparsefed_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_
     st.out(&out, out_host, n_cols);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_sparsefed_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, residual, out, st.stream()));
+    return st.finish();
+}
+
+int byz_gaussian_noise_host(byz_ctx* ctx, const float* x_host, int64_t n, const byz_noise_params* params, float* out_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(x_host && out_host && params, "gaussian_noise: null vector or parameters");
+    BYZ_TRY(check_noise("gaussian_noise", params->sigma, params->column_offset, n));
+    BYZ_REQUIRE(out_host == x_host || !vectors_overlap(x_host, out_host, n), "gaussian_noise: the output overlaps x (it may BE x, nothing else)");
+    HostStage st(ctx);     // x is the staged "matrix" (one row); the device call is out of place, so the host vectors may coincide
+    float* out;
+    st.out(&out, out_host, n);
+    BYZ_TRY(st.stage(x_host, 1, n));
+    BYZ_TRY(byz_gaussian_noise_dev(ctx, st.G(), n, params, nullptr, out, st.stream()));
+    return st.finish();
+}
+
+int byz_weak_dp_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_weak_dp_params* params,
+                     float* out_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "weak_dp"));
+    BYZ_REQUIRE(out_host, "weak_dp: null output");
+    BYZ_TRY(check_weak_dp("weak_dp", params, n_rows, n_cols));
+    HostStage st(ctx);
+    float* out;
+    st.out(&out, out_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_weak_dp_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, out, st.stream()));
     return st.finish();
 }
 

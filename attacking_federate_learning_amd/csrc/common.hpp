@@ -161,6 +161,8 @@ struct byz_ctx {
     byz::Buffer topk;            // top-k along a vector, carved (topk.hip: TopkScratch): the three histograms and the state, the chunk
                                  // arrays, the doubles of the columns layout, SparseFed's aggregate
     hipStream_t topk_stream = nullptr;     // stream of the last top-k (byz_topk_info syncs it)
+    byz::Buffer weak_dp;         // weak DP's adaptive clip, carved (cclip.hip: launch_clip_scales): the sort keys of the rows' norms
+    hipStream_t weak_dp_stream = nullptr;  // stream of the last clip scales or weak DP (byz_weak_dp_info syncs it)
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -206,7 +208,7 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
 }
 
 // ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 60;          // words one read-back fetches (read_small): every word below
+constexpr int kSmallWords = 64;          // words one read-back fetches (read_small): every word below
 constexpr int kWordKrumWinner = 0;       // Krum winner
 constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
 constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
@@ -237,6 +239,9 @@ constexpr int kSgKept = 40, kSgNormFailed = 41, kSgOutside = 42, kSgClusters = 4
 constexpr int kSgBandwidth = 46, kSgMedian = 48, kSgKeptF64 = 50;
 // top-k along a vector: four 64-bit words (8-byte aligned): selected, the ties at the threshold, the ties taken, the threshold key
 constexpr int kTopkSelected = 52, kTopkTies = 54, kTopkTaken = 56, kTopkKey = 58;
+// weak DP (byz_clip_scales_dev, byz_weak_dp_dev): the rows clipped and excluded, the clip used (fp64: two words, 8-byte aligned).
+// The last words of the 256 bytes: the next scalar needs a larger ctx->small.
+constexpr int kWeakDpClipped = 60, kWeakDpExcluded = 61, kWeakDpClip = 62;
 constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
 constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
 constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
@@ -254,6 +259,8 @@ inline unsigned long long* rlr_flip_counter(byz_ctx* ctx) {
 inline unsigned long long* topk_info_words(byz_ctx* ctx) {
     return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kTopkSelected);
 }
+
+inline double* weak_dp_clip_word(byz_ctx* ctx) { return reinterpret_cast<double*>(ctx->small.as<int32_t>() + kWeakDpClip); }
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).
 struct KernelTimer {
@@ -419,6 +426,15 @@ int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, dou
 int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream);
 // cclip.hip: centered clipping's scales: s from sq (sq == nullptr: all 1), the counts into the context's words
 int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, double* s, hipStream_t stream);
+// weak DP's scales from sq: the clip is `clip`, or (adaptive) the np.median of the finite rows' norms; s has launch_cclip_scales'
+// bits in the fixed mode; the counts and the clip into the context's weak-DP words, the clip into clip_out (optional) as well
+int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, bool adaptive, double* s, double* clip_out,
+                       hipStream_t stream);
+// noise.hip: out[c] = fl32((double)x[c] + sigma * (scale_dev ? *scale_dev : 1) * z[offset + c]), z the Philox normals of the
+// global columns (philox.hpp); out may be x.  launch_noise_words: the stream's raw words of the same columns.
+int launch_gaussian_noise(byz_ctx* ctx, const float* x, int64_t n, double sigma, uint64_t seed, uint64_t round, int64_t offset,
+                          const double* scale_dev, float* out, hipStream_t stream);
+int launch_noise_words(byz_ctx* ctx, uint64_t seed, uint64_t round, int64_t offset, int64_t n, uint32_t* words, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

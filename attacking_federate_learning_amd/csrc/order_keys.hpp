@@ -17,6 +17,7 @@
 // Everything but block_exclusive_scan also compiles for the host with a plain C++17 compiler (tests/order_keys_check.cpp).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -46,6 +47,20 @@ BYZ_KEY_FN uint64_t ordered_bits_total(double v) {      // (no plain fp64 map to
     uint64_t b = __builtin_bit_cast(uint64_t, v);
     if (b == kSign) b = 0;
     return (b & kSign) ? ~b : (b | kSign);
+}
+
+// The median of the rows' norms, by key and sort (SignGuard's M, weak DP's adaptive clip).  norm_key: the key of sqrt(q) for a
+// squared norm q; a row whose q is not finite gets all ones (kNoNormKey, the padding's key as well) and sorts behind every norm.
+// median_of_norm_keys: np.median over the `finite` first keys of the ascending sort -- the middle value, or the mean of the two
+// middle values (finite >= 1).
+constexpr uint64_t kNoNormKey = ~uint64_t{0};
+BYZ_KEY_FN uint64_t norm_key(double q) { return __builtin_isfinite(q) ? ordered_bits_total(sqrt(q)) : kNoNormKey; }
+BYZ_KEY_FN double norm_of_key(uint64_t key) {           // ordered_bits_total's inverse on values >= +0.0
+    return __builtin_bit_cast(double, key & ~(uint64_t{1} << 63));
+}
+template <typename Key>                                 // (Key: uint64_t or the device's unsigned long long)
+BYZ_KEY_FN double median_of_norm_keys(const Key* sorted_keys, int64_t finite) {
+    return (norm_of_key(sorted_keys[(finite - 1) / 2]) + norm_of_key(sorted_keys[finite / 2])) / 2.0;
 }
 
 // the exponent is not all ones

@@ -167,9 +167,6 @@ __device__ __forceinline__ double sqdist3(const double* a, double b0, double b1,
     const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
     return (d0 * d0 + d1 * d1) + d2 * d2;
 }
-__device__ __forceinline__ double norm_of_key(unsigned long long key) {      // ordered_bits_total's inverse on values >= +0.0
-    return __builtin_bit_cast(double, key & ~(1ull << 63));
-}
 
 // keys[i] = the norm's order-preserving key (a row whose q is not finite, and the padding: all ones, behind every norm); the
 // largest counts and the number of finite rows into the state
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(256) void sg_norm_keys_kernel(const double* __restr
     }
     const double q = pznq[3 * n + i];
     const bool finite = __builtin_isfinite(q);
-    keys[i] = finite ? ordered_bits_total(sqrt(q)) : kNoKey;
+    keys[i] = norm_key(q);                       // order_keys.hpp: a row whose q is not finite sorts with the padding
     atomicMax(&state->max_pos, static_cast<unsigned long long>(pznq[i]));        // (integer maxima and counts commute)
     atomicMax(&state->max_zero, static_cast<unsigned long long>(pznq[n + i]));
     atomicMax(&state->max_neg, static_cast<unsigned long long>(pznq[2 * n + i]));
@@ -200,7 +197,7 @@ __global__ __launch_bounds__(256) void sg_features_kernel(const double* __restri
     const int32_t finite_rows = state->finite_rows;
     double M = __builtin_nan("");
     if (finite_rows > 0)      // np.median: the middle value, or the mean of the two middle values
-        M = (norm_of_key(sorted_keys[(finite_rows - 1) / 2]) + norm_of_key(sorted_keys[finite_rows / 2])) / 2.0;
+        M = median_of_norm_keys(sorted_keys, finite_rows);
     if (i == 0) *f64_word(words, kSgMedian) = M;
     const double q = pznq[3 * n + i];
     const double norm = sqrt(q);

@@ -235,6 +235,47 @@ def sparsefed(users_grads, users_count, corrupted_count, k=None, clip=10.0, resi
     return (out, res) if return_residual else out
 
 
+def gaussian_noise(vector, sigma, seed=0, round=0, column_offset=0):
+    """vector + sigma * z: z the standard normals of the library's Philox4x32-10 stream (include/byzagg.h), drawn on the GPU and
+    addressed by GLOBAL column -- column c of `vector` takes z[column_offset + c], so a slice of a longer vector with its
+    offset gets exactly the noise the whole vector would.  One fp64 addition, rounded once to float32.  `round` is the
+    caller's round counter: one seed, fresh noise every round.  numpy in -> numpy out; device-resident in ->
+    device-resident out."""
+    return get_engine().gaussian_noise(vector, sigma, seed=seed, round=round, column_offset=column_offset)
+
+
+def weak_dp(users_grads, users_count, corrupted_count, clip=10.0, sigma=0.01, adaptive=False, seed=0, round=0, then=None,
+            return_info=False, **then_kwargs):
+    """Norm clipping plus Gaussian noise, "weak DP" (Sun, Kairouz, Suresh and McMahan 2019; not in the reference): the
+    baseline the backdoor defences (robust_lr, sparsefed) measure themselves against, FLAME's last stage (Nguyen et al.
+    2022) and DP-FedAvg's server step.  then=None runs as ONE library call: every client clipped to norm `clip`, the mean
+    (centered_clip from zero with one iteration; a client with a non-finite entry is excluded and still counted), then
+    gaussian_noise with standard deviation sigma.  adaptive=True is FLAME's: clip = the median of the clients' finite
+    norms and the noise's standard deviation sigma * clip (sigma is then FLAME's lambda), nothing read by the host.  With a
+    callable the noise goes on then(users_grads, users_count, corrupted_count, **then_kwargs) -- `coordinate_median`,
+    `trimmed_mean`, ... -- on the device-resident matrix (a host matrix is uploaded once); `clip` is then unused and
+    adaptive is refused.  clip = 10.0 and sigma = 0.01 are this package's choice: the papers tune both.  (seed, round)
+    name the noise vector: the same pair gives the same vector, DeviceServer.defend_weak_dp counts the rounds.
+    return_info=True returns (vector, {clipped_rows, excluded_rows, clip}) (then=None only).  Not one of the `defend` keys:
+    the reference's main.py offers only those four."""
+    engine = get_engine()
+    if then is None:
+        return engine.weak_dp(users_grads, clip=clip, sigma=sigma, adaptive=adaptive, seed=seed, round=round,
+                              return_info=return_info)
+    if not callable(then):
+        raise TypeError('weak_dp: `then` is the rule that supplies the aggregate, e.g. defences.coordinate_median, or None')
+    if adaptive or return_info:
+        raise ValueError('weak_dp: adaptive and return_info describe the clipping, which a rule `then` replaces')
+    host = engine._device_matrix(users_grads) is None
+    if host:
+        users_grads = engine.to_device(engine._host_matrix(users_grads))
+    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
+    out = engine.gaussian_noise(agg, sigma, seed=seed, round=round)
+    if host:
+        out = out.numpy() if isinstance(out, DeviceBuffer) else out
+    return out
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -1482,6 +1482,114 @@ class Engine:
         info['clipped_rows'], info['excluded_rows'] = self.centered_clip_info()
         return out, res, info
 
+    # ---- clip and noise, "weak DP" (Sun et al. 2019; FLAME's last stage; not in the reference) ----
+    @staticmethod
+    def _noise_params(sigma, seed, round, column_offset):
+        """byz_noise_params; sigma must be finite and >= 0, seed and round are taken modulo 2^64, column_offset >= 0."""
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma >= 0.0):
+            raise ValueError('sigma = %r must be finite and >= 0' % (sigma,))
+        if int(column_offset) < 0:
+            raise ValueError('column_offset = %r must be >= 0' % (column_offset,))
+        mask = (1 << 64) - 1
+        return _native.NoiseParams(sigma, int(seed) & mask, int(round) & mask, int(column_offset))
+
+    def noise_words(self, n, seed=0, round=0, column_offset=0, like=None):
+        """The n raw 32-bit words of the Philox4x32-10 stream at the global columns column_offset .. column_offset + n - 1
+        (key = seed, counter = (column >> 2, round), word column & 3 of the block), as a uint32 numpy array; `like`: a torch
+        CUDA tensor, for a device-resident int32 tensor with the same bits on its stream instead."""
+        params = self._noise_params(0.0, seed, round, column_offset)
+        n = int(n)
+        if like is not None:
+            import torch
+            out = torch.empty(max(n, 0), dtype=torch.int32, device=like.device)
+            stream = torch.cuda.current_stream(like.device).cuda_stream
+            _check(self.lib.byz_noise_words_dev(self.ctx, ctypes.byref(params), n, _vp(out.data_ptr()), _vp(stream)))
+            return out
+        buf = DeviceBuffer(self, (max(n, 1),), np.uint32)
+        _check(self.lib.byz_noise_words_dev(self.ctx, ctypes.byref(params), n, _vp(buf.ptr), None))
+        return buf.numpy()
+
+    def gaussian_noise(self, x, sigma, seed=0, round=0, column_offset=0, scale=None, out=None):
+        """out[c] = fl32((double)x[c] + sigma_eff * z[column_offset + c]): z the fp64 Box-Muller normals of the Philox stream
+        addressed by GLOBAL column (include/byzagg.h), so a slice with its offset gets the whole vector's noise.  sigma_eff =
+        sigma, or sigma * scale[0] with `scale` a device-resident fp64 scalar read by the kernel (no synchronisation).
+        numpy in -> numpy out; device-resident x -> device-resident out.  out: a device vector to write, which may be x
+        itself (in place).  sigma = 0 with no scale returns x's bits."""
+        params = self._noise_params(sigma, seed, round, column_offset)
+        if not self._on_device(x):
+            if scale is not None or out is not None:
+                raise ValueError('a host vector takes neither a device scale nor an output vector')
+            xh = self._host_f32(x)
+            oh = np.empty(xh.size, dtype=np.float32)
+            _check(self.lib.byz_gaussian_noise_host(self.ctx, xh.ctypes.data_as(ctypes.c_void_p), xh.size, ctypes.byref(params),
+                                                    oh.ctypes.data_as(ctypes.c_void_p)))
+            return oh
+        (xptr,), n, stream, keep, example = self._vectors(x)
+        sptr, skeep = self._f64_vector(scale, 1) if scale is not None else (None, None)
+        if out is None:
+            out, optr = self._out_like(example, n)
+        else:
+            optr = self._device_out(out, n, 'out')
+        _check(self.lib.byz_gaussian_noise_dev(self.ctx, _vp(xptr), n, ctypes.byref(params), _vp(sptr), _vp(optr), _vp(stream)))
+        if isinstance(skeep, DeviceBuffer) and skeep is not scale:
+            self.synchronize(stream)                 # an uploaded scale must outlive the kernel
+        return out
+
+    def weak_dp_info(self):
+        """{clipped_rows, excluded_rows, clip} of the last clip_scales or weak_dp on this engine (synchronises)."""
+        clipped, excluded, clip = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        _check(self.lib.byz_weak_dp_info(self.ctx, ctypes.byref(clipped), ctypes.byref(excluded), ctypes.byref(clip)))
+        return {'clipped_rows': int(clipped.value), 'excluded_rows': int(excluded.value), 'clip': float(clip.value)}
+
+    def clip_scales(self, sq, clip=10.0, adaptive=False, return_clip=False):
+        """The clipping scales from the rows' fp64 squared norms (row_sqdist with a zero centre): d = sqrt(sq), s = 1 (d <=
+        clip), clip / d (clip < d < inf), 0 (sq not finite: excluded, still counted in n).  adaptive=True takes clip =
+        np.median of the finite norms (0 when there is none, and then every scale is 0).  fp64 out where sq lives: a torch
+        tensor, a DeviceBuffer, or numpy for a host sq.  return_clip=True returns (scales, clip), the clip a one-element
+        array of the same kind (device-resident: what gaussian_noise takes as `scale`)."""
+        if self._on_device(sq):
+            n = sq.numel() if _is_torch(sq) else int(np.prod(sq.shape))
+            host = False
+        else:
+            sq = np.ascontiguousarray(sq, dtype=np.float64).reshape(-1)
+            n, host = sq.size, True
+        qptr, qkeep = self._f64_vector(sq, n)
+        example = qkeep if _is_torch(qkeep) else None
+        stream = None
+        if example is not None:
+            import torch
+            stream = torch.cuda.current_stream(example.device).cuda_stream
+        params = _native.WeakDpParams(float(clip), 0.0, 1 if adaptive else 0, 0, 0, 0)
+        scales, sptr = self._out_like(example, n, np.float64)
+        used, cptr = self._out_like(example, 1, np.float64)
+        _check(self.lib.byz_clip_scales_dev(self.ctx, _vp(qptr), n, ctypes.byref(params), _vp(sptr), _vp(cptr), _vp(stream)))
+        if host:
+            self.synchronize(stream)                 # the uploaded norms must outlive the kernels
+            scales, used = scales.numpy(), used.numpy()
+        return (scales, used) if return_clip else scales
+
+    def weak_dp(self, g, clip=10.0, sigma=0.01, adaptive=False, seed=0, round=0, column_offset=0, return_info=False):
+        """Clip and noise: every row scaled to norm `clip` at most, the mean (centered_clip from zero with one iteration: its
+        bits before the noise; rows with a non-finite entry excluded and still counted in the divisor), then gaussian_noise
+        in place with standard deviation sigma.  adaptive=True is FLAME's: clip = the median of the finite rows' norms and
+        the noise's standard deviation sigma * clip, read on the device.  One library call, nothing synchronises.
+        return_info=True also returns weak_dp_info()."""
+        noise = self._noise_params(sigma, seed, round, column_offset)
+        params = _native.WeakDpParams(float(clip), noise.sigma, 1 if adaptive else 0, noise.seed, noise.round, noise.column_offset)
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            out = np.empty(d, dtype=np.float32)
+            _check(self.lib.byz_weak_dp_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                             out.ctypes.data_as(ctypes.c_void_p)))
+        else:
+            out, optr = self._out_like(dm, dm.cols)
+            _check(self.lib.byz_weak_dp_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params), _vp(optr),
+                                            _vp(dm.stream)))
+        return (out, self.weak_dp_info()) if return_info else out
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

@@ -16,6 +16,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_robust_lr(theta, then)     the same step with the robust learning rate round the mean or the rule `then`
     defend_bucketing(then, s)         the same step with s-bucketing, reshuffled every round, in front of the rule `then`
     defend_sparsefed(k, clip, then)   the same step with SparseFed: only the k heaviest coordinates of an error-feedback memory
+    defend_weak_dp(clip, sigma, then) the same step with norm clipping and Gaussian noise drawn on the GPU, fresh every round
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -46,6 +47,8 @@ class DeviceServer:
         self.signguard_round = 0
         # SparseFed's history: the error-feedback memory W (zeros before the first round)
         self.sparse_residual = torch.zeros_like(self.current_weights)
+        # weak DP's history: the calls of defend_weak_dp so far (the `round` of the next noise vector)
+        self.weak_dp_round = 0
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -174,6 +177,23 @@ class DeviceServer:
             raise TypeError('defend_sparsefed: `then` is the rule that supplies the aggregate, or None for the clipped mean')
         current_grads = defences.sparsefed(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), k=k, clip=clip,
                                            residual=self.sparse_residual, then=then, **then_kwargs)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with norm clipping and Gaussian noise ("weak DP") ----------------------------------------
+    def defend_weak_dp(self, clip=10.0, sigma=0.01, adaptive=False, seed=0, then=None, **then_kwargs):
+        """Clip and noise on this round's gradients (defences.weak_dp): every client clipped to norm `clip` (adaptive=True:
+        to the median norm, the noise scaled by it) and averaged, or the rule `then(grads, n_users, n_malicious,
+        **then_kwargs)`, then Gaussian noise of standard deviation sigma drawn on the GPU, and server.py:89-90's momentum
+        step on the noisy vector, as `defend` takes it.  `weak_dp_round`, the calls so far, is passed as the stream's
+        `round` and then incremented: one seed draws fresh noise every round, and a replayed round its own noise again."""
+        if then is not None and not callable(then):
+            raise TypeError('defend_weak_dp: `then` is the rule that supplies the aggregate, or None for the clipped mean')
+        current_grads = defences.weak_dp(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), clip=clip,
+                                         sigma=sigma, adaptive=adaptive, seed=seed, round=self.weak_dp_round, then=then,
+                                         **then_kwargs)
+        self.weak_dp_round += 1
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -147,6 +147,15 @@ class HipKernels:
         return self.engine.topk_sparsify_sharded(x_local, k, n_total, rank, world, add=add, all_reduce=all_reduce,
                                                  residual=residual)
 
+    def clip_scales(self, sq, clip=10.0, adaptive=False):
+        # (scales, clip) from the all-reduced squared norms: the same on every rank; the clip stays on the device
+        return self.engine.clip_scales(sq, clip=clip, adaptive=adaptive, return_clip=True)
+
+    def gaussian_noise(self, x_local, sigma, seed=0, round=0, column_offset=0, scale=None):
+        # this rank's columns of the noisy vector, in place: column_offset is the global index of its first column
+        return self.engine.gaussian_noise(x_local, sigma, seed=seed, round=round, column_offset=column_offset, scale=scale,
+                                          out=x_local)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -366,6 +375,33 @@ class ShardedAggregator:
         out, res = self.kernels.topk_sparsify_sharded(residual_local, k, total, self.rank, self.world, add=agg, all_reduce=reduce,
                                                       residual=residual_local)
         return self._maybe_gather(out, gather, total_columns), res
+
+    def weak_dp(self, g_local, users_count, corrupted_count, column_offset, clip=10.0, sigma=0.01, adaptive=False, seed=0,
+                round=0, gather=False, total_columns=None, return_info=False):
+        """Clip and noise (defences.weak_dp's contract with then=None), columns layout, both modes.  There is no sharded
+        library call to make: a rank's squared norms cover its columns -- ONE all-reduce of N doubles makes them whole, the
+        one centered_clip(iters=1) makes --, kernels.clip_scales then gives the same scales and clip on every rank, the
+        clipped mean is local to the columns (kernels.clip_update from zero) and so is the noise, given column_offset, the
+        global index of this rank's first column: the Philox stream is addressed by global column, so the ranks' slices
+        concatenate to the single-GPU vector.  adaptive=True: the clip is the median norm and the noise sigma * clip, read
+        on the device.  Returns this rank's columns (gather=True: the whole vector)."""
+        import torch
+        n, d_local = g_local.shape
+        zero = torch.zeros(d_local, dtype=torch.float32, device=g_local.device)
+        sq = self.kernels.row_sqdist(g_local, zero)
+        self._all_reduce('allreduce_weak_dp_norms', sq)
+        scales, used = self.kernels.clip_scales(sq, clip=clip, adaptive=adaptive)
+        v = self.kernels.clip_update(g_local, zero, scales)
+        if float(sigma) != 0.0:
+            v = self.kernels.gaussian_noise(v, sigma, seed=seed, round=round, column_offset=column_offset,
+                                            scale=used if adaptive else None)
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        d = torch.sqrt(sq)
+        finite = torch.isfinite(d)
+        return out, {'clipped_rows': int((finite & (d > used)).sum().item()), 'excluded_rows': int((~finite).sum().item()),
+                     'clip': float(used.item())}
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

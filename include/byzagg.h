@@ -579,6 +579,75 @@ int byz_sparsefed_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t 
 int byz_sparsefed_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_sparsefed_params* params,
                        float* residual_host, float* out_host);
 
+/* ---- Clip and noise, "weak DP" (Sun, Kairouz, Suresh & McMahan, "Can You Really Backdoor Federated Learning?", 2019;      */
+/* FLAME's last stage, Nguyen et al., USENIX Security 2022; DP-FedAvg's server step; not in the reference) ----              */
+/* The baseline the backdoor defences measure themselves against: every client clipped to a norm bound, the clipped updates  */
+/* averaged, Gaussian noise added to the average.  The clipped mean is byz_centered_clip_dev from zero with one iteration;   */
+/* the new piece is the noise, drawn ON THE DEVICE from a counter-based Philox4x32-10 stream (Salmon et al., SC'11) that is  */
+/* addressed by GLOBAL COLUMN:                                                                                               */
+/*   key = (low, high word of seed);  counter = (low word of b, high word of b, low word of round, high word of round),      */
+/*   b = global_column >> 2;  word i (0..3) of block b belongs to global column 4 b + i                                      */
+/*   normals, all in fp64, one Box-Muller pair p in {0, 1} per two words x:                                                  */
+/*     u1 = (x[2p] + 0.5) * 2^-32,  u2 = (x[2p+1] + 0.5) * 2^-32,  r = sqrt(-2 log(u1)),  t = fl64(6.283185307179586 * u2),  */
+/*     z[4b + 2p] = r cos(t),  z[4b + 2p + 1] = r sin(t)                                                                     */
+/*   out[c] = fl32((double)x[c] + sigma_eff * z[column_offset + c]),  sigma_eff = sigma * (scale_dev ? *scale_dev : 1.0)     */
+/* The integers are the same bit for bit for one call, a misaligned caller and any split of the columns over ranks (each     */
+/* rank passes the global index of its first column as column_offset); the normals are those integers through the device's   */
+/* fp64 log, sin and cos, which agree with another math library's to a few fp64 ulp, far below the one fp32 rounding.        */
+/* `round` is the caller's round counter: one seed, fresh noise every round.  scale_dev_or_null is ONE device double read by  */
+/* the kernel (the adaptive clip), so no call here synchronises with the host.                                               */
+/* n >= 1, column_offset >= 0, column_offset + n <= 2^62, sigma finite and >= 0: BYZ_E_INVALID otherwise, nothing written.    */
+/* out_dev may be x_dev (in place); any other overlap: BYZ_E_INVALID.  sigma == 0 with no scale writes x's bits verbatim.     */
+/* A NaN or an infinity in x stays where it is: nothing is sanitised.  No doubles by value, as elsewhere.                     */
+typedef struct byz_noise_params {
+    double sigma;           /* the standard deviation: finite, >= 0 (times *scale_dev when given)  */
+    uint64_t seed;          /* the stream's key                                                     */
+    uint64_t round;         /* the caller's round counter: counter words 2 and 3                    */
+    int64_t column_offset;  /* the global column of x[0]: >= 0                                      */
+} byz_noise_params;
+int byz_gaussian_noise_dev(byz_ctx* ctx, const float* x_dev, int64_t n, const byz_noise_params* params,
+                           const double* scale_dev_or_null, float* out_dev, void* stream);
+/* The raw stream: words_dev[c] = the 32-bit word of global column column_offset + c (n of them; sigma is not read).          */
+int byz_noise_words_dev(byz_ctx* ctx, const byz_noise_params* params, int64_t n, uint32_t* words_dev, void* stream);
+/* The same on host vectors (out_host may be x_host).  Synchronous.                                                          */
+int byz_gaussian_noise_host(byz_ctx* ctx, const float* x_host, int64_t n, const byz_noise_params* params, float* out_host);
+
+typedef struct byz_weak_dp_params {
+    double clip;            /* fixed mode: the clients' norm bound, > 0 (+inf allowed); adaptive mode: not read        */
+    double sigma;           /* fixed mode: the noise's standard deviation; adaptive mode: FLAME's lambda, the noise's   */
+                            /* standard deviation is sigma * clip; finite, >= 0                                         */
+    int64_t adaptive;       /* 0: clip as given; otherwise clip = the median of the finite rows' norms                  */
+    uint64_t seed;
+    uint64_t round;
+    int64_t column_offset;  /* the global column of column 0 of G: >= 0                                                 */
+} byz_weak_dp_params;
+/* The clipping piece.  sq_dev: the n_rows fp64 squared norms q of byz_row_sqdist_dev with a zero centre.  d_i = sqrt(q_i).   */
+/* Fixed mode: clip = params->clip.  Adaptive mode: clip = np.median of d_i over the rows with finite q_i (the middle value,  */
+/* or the mean of the two middle values: SignGuard's definition and its key-and-sort route); no finite row: clip = 0.         */
+/* scales_dev[i] = 1 (d_i <= clip), clip / d_i (clip < d_i < inf), 0 (q_i not finite: the row is excluded and still counted   */
+/* in n, centered clipping's convention); clip = 0: every scale 0.  clip_dev_or_null receives the one fp64 clip.  In the      */
+/* fixed mode the scales are those byz_centered_clip_dev (iters = 1, start = NULL) reports, bit for bit.  Only clip (fixed   */
+/* mode) and adaptive are read.  n_rows up to 2^20.                                                                          */
+int byz_clip_scales_dev(byz_ctx* ctx, const double* sq_dev, int64_t n_rows, const byz_weak_dp_params* params,
+                        double* scales_dev, double* clip_dev_or_null, void* stream);
+/* The last byz_clip_scales_dev or byz_weak_dp_dev on this context: the rows clipped (clip < d < inf), the rows excluded,     */
+/* the clip used.  Synchronises that call's stream.                                                                          */
+int byz_weak_dp_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows, double* clip);
+/* The whole defence: byz_row_sqdist_dev's norms (zero centre), byz_clip_scales_dev, byz_clip_update_dev from the zero        */
+/* vector, then the noise in place on out_dev with sigma_eff = sigma (fixed) or sigma * clip (adaptive, read on the device). */
+/* In the fixed mode the result before the noise has byz_centered_clip_dev(iters = 1)'s bits, and sigma = 0 returns them.    */
+/* Every launch is enqueued up front; nothing synchronises with the host.  out_dev must not overlap G (BYZ_E_INVALID).       */
+/* There is NO SHARDED ENTRY POINT: the noise is local to a column given column_offset, and the norms are the one all-reduce */
+/* of n_rows doubles that byz_centered_clip_sharded_dev already makes.  A host of the columns layout calls                   */
+/* byz_centered_clip_sharded_dev (iters = 1, no start) and byz_gaussian_noise_dev with its slice's column_offset in the      */
+/* fixed mode; in the adaptive mode byz_row_sqdist_dev, its all-reduce, byz_clip_scales_dev, byz_clip_update_dev and         */
+/* byz_gaussian_noise_dev with scale_dev = the clip.                                                                         */
+int byz_weak_dp_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                    const byz_weak_dp_params* params, float* out_dev, void* stream);
+/* The same on a host matrix (out_host: n_cols floats).  Synchronous.                                                        */
+int byz_weak_dp_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_weak_dp_params* params,
+                     float* out_host);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
