@@ -51,6 +51,12 @@ class WeakDpParams(ctypes.Structure):
                 ('round', ctypes.c_uint64), ('column_offset', c_i64)]
 
 
+class FlameParams(ctypes.Structure):
+    """byz_flame_params: FLAME's noise level, HDBSCAN's two parameters (min_cluster_size 0: n / 2 + 1) and the noise's place."""
+    _fields_ = [('lam', ctypes.c_double), ('min_samples', c_i64), ('min_cluster_size', c_i64), ('seed', ctypes.c_uint64),
+                ('round', ctypes.c_uint64), ('column_offset', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -169,6 +175,14 @@ _PROTOTYPES = {
     'byz_weak_dp_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double)],
     'byz_weak_dp_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(WeakDpParams), c_vp, c_vp],
     'byz_weak_dp_host': [c_vp, c_vp, c_i64, c_i64, _P(WeakDpParams), c_vp],
+    'byz_cosine_distances_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_cosine_from_gram_dev': [c_vp, c_vp, c_i64, c_vp, c_vp],
+    'byz_flame_core_distances_dev': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp],
+    'byz_flame_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_flame_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FlameParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_flame_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
+    'byz_flame_host': [c_vp, c_vp, c_i64, c_i64, _P(FlameParams), c_vp, c_vp, c_vp],
+    'byz_flame_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FlameParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

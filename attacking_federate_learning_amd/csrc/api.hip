@@ -1520,6 +1520,169 @@ int byz_weak_dp_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols
                                  adaptive ? weak_dp_clip_word(ctx) : nullptr, out, s);
 }
 
+// ---- FLAME (Nguyen et al., USENIX Security 2022; beyond the reference) -------------------------------------------------------
+namespace {
+
+int check_flame_rows(const char* who, int64_t n) {
+    if (n > kFlameMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kFlameMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+int check_flame_select(const char* who, int64_t n, int64_t m, int64_t ms) {
+    BYZ_TRY(check_flame_rows(who, n));
+    if (n < 2 || m < 2 || m > n || 2 * m <= n) {
+        set_error("%s: min_cluster_size = %lld must lie in 2..n and exceed n / 2 (n = %lld): one majority cluster", who, (long long)m,
+                  (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (ms > kFlameMaxSamples) {
+        set_error("%s: min_samples = %lld beyond %lld", who, (long long)ms, (long long)kFlameMaxSamples);
+        return BYZ_E_UNSUPPORTED;
+    }
+    if (ms < 0 || ms > n - 1) {
+        set_error("%s: min_samples = %lld outside 0..n - 1 (n = %lld)", who, (long long)ms, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+int64_t flame_cluster_size(const byz_flame_params* params, int64_t n) {
+    return params->min_cluster_size == 0 ? n / 2 + 1 : params->min_cluster_size;
+}
+
+int check_flame(const char* who, const byz_flame_params* params, int64_t n_rows, int64_t n_cols) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_flame_rows(who, n_rows));
+    BYZ_TRY(check_noise(who, params->lambda, params->column_offset, n_cols));
+    return check_flame_select(who, n_rows, flame_cluster_size(params, n_rows), params->min_samples);
+}
+
+// the cosine distances of G's rows into dist, the Gram in ctx->gram; with an all-reduce the Gram of the ranks' column slices
+int cosine_distances(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, byz_allreduce_f64_fn allreduce, void* user,
+                     float* dist, void* stream) {
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n) * n * sizeof(double)));
+    double* gram = ctx->gram.as<double>();
+    BYZ_TRY(launch_gram(ctx, G, n, n_cols, ld, gram, s));
+    if (allreduce != nullptr) {
+        ctx->row_map_rows = 0;      // (what the duplicate search proved holds for the local columns only)
+        BYZ_TRY(reduce_over_ranks(allreduce, user, gram, n * n, stream, "flame (Gram)"));
+    }
+    return launch_cosine_from_gram(ctx, gram, n, dist, s);
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Every launch of the stages added here is enqueued up
+// front; the one wait is the Gram's own duplicate search (dedup.hip: find_unique_rows reads a count back to size its launch),
+// the same wait byz_gram_dev and byz_pairwise_distances_dev make.  A caller's dist_in skips the Gram and with it that wait.
+int flame(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_flame_params* params,
+          byz_allreduce_f64_fn allreduce, void* user, const float* dist_in, float* out, int32_t* admitted_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    FlameScratch f;
+    BYZ_TRY(flame_workspace(ctx, n, &f));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
+    double *sq = t.a, *scale = t.b;
+    ctx->flame_stream = s;
+    ctx->flame_selected = true;
+    ctx->weak_dp_stream = s;
+    const float* dist = dist_in;
+    if (dist == nullptr) {
+        BYZ_TRY(ctx->dist.ensure(static_cast<size_t>(n) * n * sizeof(float)));
+        BYZ_TRY(cosine_distances(ctx, G, n, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+        dist = ctx->dist.as<float>();
+    }
+    BYZ_TRY(launch_flame_select(ctx, f, dist, n, flame_cluster_size(params, n), params->min_samples, admitted_out, s));
+    BYZ_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(n_cols) * sizeof(float), s));
+    BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, sq, nullptr, nullptr, s));
+    if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, sq, n, stream, "flame (norms)"));
+    BYZ_TRY(launch_clip_scales(ctx, sq, n, 0.0, true, scale, &f.info->clip, s));     // the paper's median: over all n rows
+    BYZ_TRY(launch_flame_weights(ctx, f, scale, n, s));
+    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, f.w, &f.info->admitted_f64, out, s));
+    if (params->lambda == 0.0) return BYZ_OK;              // the clipped mean's bits
+    return launch_gaussian_noise(ctx, out, n_cols, params->lambda, params->seed, params->round, params->column_offset,
+                                 weak_dp_clip_word(ctx), out, s);
+}
+
+}  // namespace
+
+int byz_cosine_distances_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float* dist, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "cosine_distances"));
+    BYZ_REQUIRE(dist, "cosine_distances: null output");
+    BYZ_TRY(check_flame_rows("cosine_distances", n_rows));
+    return cosine_distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, dist, stream);
+}
+
+int byz_cosine_from_gram_dev(byz_ctx* ctx, const double* gram, int64_t n_rows, float* dist, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(gram && dist && n_rows > 0, "cosine_from_gram: null Gram or output, or no rows (%lld)", (long long)n_rows);
+    BYZ_TRY(check_flame_rows("cosine_from_gram", n_rows));
+    return launch_cosine_from_gram(ctx, gram, n_rows, dist, as_stream(stream));
+}
+
+int byz_flame_core_distances_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t min_samples, float* core, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && core, "flame_core_distances: null distances or output");
+    BYZ_TRY(check_flame_select("flame_core_distances", n_rows, n_rows, min_samples));
+    FlameScratch f;
+    BYZ_TRY(flame_workspace(ctx, n_rows, &f));
+    return launch_flame_core(ctx, dist, n_rows, min_samples, core, f.isolated, as_stream(stream));
+}
+
+int byz_flame_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t min_cluster_size, int64_t min_samples,
+                         int32_t* admitted, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && admitted, "flame_select: null distances or output");
+    BYZ_TRY(check_flame_select("flame_select", n_rows, min_cluster_size, min_samples));
+    FlameScratch f;
+    BYZ_TRY(flame_workspace(ctx, n_rows, &f));
+    ctx->flame_stream = as_stream(stream);
+    ctx->flame_selected = true;
+    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), ctx->flame_stream));
+    return launch_flame_select(ctx, f, dist, n_rows, min_cluster_size, min_samples, admitted, ctx->flame_stream);
+}
+
+int byz_flame_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_flame_params* params,
+                  const float* dist, float* out, int32_t* admitted, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "flame"));
+    BYZ_REQUIRE(out, "flame: null output");
+    BYZ_TRY(check_flame("flame", params, n_rows, n_cols));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "flame"));
+    return flame(ctx, G, n_rows, n_cols, ld, params, nullptr, nullptr, dist, out, admitted, stream);
+}
+
+int byz_flame_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_flame_params* params,
+                          byz_allreduce_f64_fn allreduce, void* user, const float* dist, float* out, int32_t* admitted,
+                          void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "flame_sharded"));
+    BYZ_REQUIRE(out && allreduce, "flame_sharded: null output or null all-reduce");
+    BYZ_TRY(check_flame("flame_sharded", params, n_rows, n_cols));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "flame_sharded"));
+    return flame(ctx, G, n_rows, n_cols, ld, params, allreduce, user, dist, out, admitted, stream);
+}
+
+int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, double* w_star, double* clip) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->flame_selected, "flame_info: no FLAME selection on this context yet");
+    BYZ_TRY(check_small(ctx, ctx->flame_stream));            // synchronises the last call's stream
+    FlameInfo info;
+    static_assert(sizeof(FlameInfo) == kFlameInfoWords * sizeof(int32_t), "whole words");
+    BYZ_TRY(read_i32(ctx, ctx->flame_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kFlameInfoWords, ctx->flame_stream));
+    if (admitted_rows) *admitted_rows = info.admitted;
+    if (broken_rows) *broken_rows = info.broken_rows;
+    if (w_star) *w_star = static_cast<double>(info.w_star);
+    if (clip) *clip = info.clip;
+    return BYZ_OK;
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -2074,6 +2237,23 @@ int byz_weak_dp_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t 
     st.out(&out, out_host, n_cols);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_weak_dp_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, out, st.stream()));
+    return st.finish();
+}
+
+int byz_flame_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_flame_params* params,
+                   const float* dist_host, float* out_host, int32_t* admitted_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "flame"));
+    BYZ_REQUIRE(out_host, "flame: null output");
+    BYZ_TRY(check_flame("flame", params, n_rows, n_cols));
+    HostStage st(ctx);
+    float *out, *dist;
+    int32_t* admitted;
+    st.out(&out, out_host, n_cols);
+    st.in(&dist, dist_host, n_rows * n_rows);
+    st.out(&admitted, admitted_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_flame_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, dist, out, admitted, st.stream()));
     return st.finish();
 }
 

@@ -163,6 +163,12 @@ struct byz_ctx {
     hipStream_t topk_stream = nullptr;     // stream of the last top-k (byz_topk_info syncs it)
     byz::Buffer weak_dp;         // weak DP's adaptive clip, carved (cclip.hip: launch_clip_scales): the sort keys of the rows' norms
     hipStream_t weak_dp_stream = nullptr;  // stream of the last clip scales or weak DP (byz_weak_dp_info syncs it)
+    byz::Buffer flame;           // FLAME, carved into FlameScratch's arrays (flame.hip: flame_workspace): the core distances, the
+                                 // tree's edges and their sort keys, the admitted flags, the weights
+    byz::Buffer flame_info;      // the last selection's scalars (FlameInfo), in a buffer of their own: the workspace may be carved
+                                 // again, and move, between a selection and byz_flame_info
+    hipStream_t flame_stream = nullptr;    // stream of the last FLAME selection (byz_flame_info syncs it)
+    bool flame_selected = false;           // a selection has written ctx->flame_info
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -435,6 +441,35 @@ int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, b
 int launch_gaussian_noise(byz_ctx* ctx, const float* x, int64_t n, double sigma, uint64_t seed, uint64_t round, int64_t offset,
                           const double* scale_dev, float* out, hipStream_t stream);
 int launch_noise_words(byz_ctx* ctx, uint64_t seed, uint64_t round, int64_t offset, int64_t n, uint32_t* words, hipStream_t stream);
+// flame.hip: FLAME's clustering stage.  The scalars of a call live in ctx->flame_info, not in ctx->small (which is full):
+struct FlameInfo {
+    int32_t admitted, broken_rows;   // the rows admitted; the rows without a finite off-diagonal distance
+    float w_star;                    // the threshold (+inf: nobody admitted)
+    int32_t pad;
+    double admitted_f64;             // the divisor of the sum
+    double clip;                     // byz_flame_dev: the median norm
+};
+constexpr int kFlameInfoWords = static_cast<int>(sizeof(FlameInfo) / sizeof(int32_t));
+constexpr int64_t kFlameMaxRows = 16384;     // Prim's one workgroup owns 1024 x 16 vertices; the union-find fills the LDS
+constexpr int64_t kFlameMaxSamples = 32;     // rounds of the core distance's selection at most
+struct FlameScratch {
+    FlameInfo* info;
+    float* core;                     // n: the core distances
+    int32_t *isolated, *eab, *admitted;      // n flags; the tree's edges (a, b) by slot (2 n); n flags
+    unsigned long long* ekeys;       // n_pad: weight key << 32 | slot, all ones behind the n - 1 edges
+    double* w;                       // n: the sum's weights
+    int64_t n_pad;
+};
+int flame_workspace(byz_ctx* ctx, int64_t n, FlameScratch* out);
+// dist = the cosine distances of the rows behind an fp64 Gram (diagonal and broken rows +inf)
+int launch_cosine_from_gram(byz_ctx* ctx, const double* gram, int64_t n, float* dist, hipStream_t stream);
+// core[i] = the ms-th smallest off-diagonal entry of row i in the key order (ms = 0: 0); isolated[i]: no finite entry
+int launch_flame_core(byz_ctx* ctx, const float* dist, int64_t n, int64_t ms, float* core, int32_t* isolated, hipStream_t stream);
+// core distances, Prim, the edge sort, the admission: t.admitted (and admitted_out, optional), the scalars into t.info
+int launch_flame_select(byz_ctx* ctx, const FlameScratch& t, const float* dist, int64_t n, int64_t m, int64_t ms,
+                        int32_t* admitted_out, hipStream_t stream);
+// t.w[i] = t.admitted[i] ? scales[i] : 0
+int launch_flame_weights(byz_ctx* ctx, const FlameScratch& t, const double* scales, int64_t n, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

@@ -276,6 +276,33 @@ def weak_dp(users_grads, users_count, corrupted_count, clip=10.0, sigma=0.01, ad
     return out
 
 
+def cosine_distances(users_grads):
+    """The pairwise cosine distances of the clients' rows, 1 - cos, as a `Distances` handle resident on the GPU (diagonal
+    +inf, a zero or non-finite client's row and column +inf): what `flame` clusters on, and what its `distances=` takes."""
+    return get_engine().cosine_distances(users_grads)
+
+
+def flame(users_grads, users_count, corrupted_count, lam=0.001, min_samples=1, min_cluster_size=None, seed=0, round=0,
+          distances=None, return_info=False):
+    """FLAME (Nguyen et al., USENIX Security 2022; not in the reference): the backdoor defence `robust_lr`, `sparsefed` and
+    `weak_dp` are measured against.  Pairwise cosine distances between the clients; HDBSCAN with min_cluster_size =
+    n // 2 + 1 and everything outside the one majority cluster rejected; the admitted clients clipped to the median norm of
+    all clients and averaged; Gaussian noise of standard deviation lam * (that median) drawn on the GPU.  One library call,
+    nothing read by the host.  By construction roughly half of the clients, the densest majority, are admitted; identical
+    rows sit together at distance 0 and are admitted as a block, so this is a backdoor defence, not an answer to the drift
+    attack.  Nobody admitted (too many zero or non-finite clients): the zero vector plus the noise.
+    min_samples follows the `hdbscan` package's convention; scikit-learn's min_samples is one more.  lam = 0.001 is this
+    package's default: the paper tunes it per task.  The paper compares the clients' local MODELS; this compares the rows
+    it is given, and a caller who wants the models' angles passes them as `distances=` (a `Distances` handle, e.g.
+    cosine_distances(models), or a dense matrix with an infinite diagonal), which replaces the cosine stage.  (seed, round)
+    name the noise vector; DeviceServer.defend_flame counts the rounds.  The reference's leading signature; users_count
+    and corrupted_count are accepted and unused.  numpy in -> numpy out, device-resident in -> device-resident out.
+    return_info=True returns (vector, {admitted_rows, admitted, broken_rows, w_star, clip}).  Not one of the `defend` keys:
+    the reference's main.py offers only those four."""
+    return get_engine().flame(users_grads, lam=lam, min_samples=min_samples, min_cluster_size=min_cluster_size, seed=seed,
+                              round=round, distances=distances, return_info=return_info)
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -1590,6 +1590,126 @@ class Engine:
                                             _vp(dm.stream)))
         return (out, self.weak_dp_info()) if return_info else out
 
+    # ---- FLAME (Nguyen et al., USENIX Security 2022; not in the reference) ----
+    def cosine_distances(self, g):
+        """The pairwise COSINE distances of g's rows as a `Distances` handle, resident on the GPU: c_ij = max(0, 1 - g_ij /
+        (sqrt(g_ii) sqrt(g_jj))) from the fp64 Gram, rounded once to float32; the diagonal is +inf (pairwise_distances'
+        convention), a zero or non-finite row's whole row and column are +inf; symmetric bit for bit.  Up to 16,384 rows."""
+        m, stage, _ = self._staged(g)
+        dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
+        _check(self.lib.byz_cosine_distances_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(dist.ptr), _vp(m.stream)))
+        self.check(m.stream)
+        return Distances(dist, m.rows)
+
+    def cosine_from_gram(self, gram, n=None, stream=None):
+        """cosine_distances' second half on an (all-reduced) fp64 Gram, n x n, on the device -> `Distances`."""
+        ptr = gram.data_ptr() if _is_torch(gram) else gram.ptr
+        n = int(gram.shape[0]) if n is None else int(n)
+        if _is_torch(gram):
+            import torch
+            if gram.dtype != torch.float64 or not gram.is_contiguous() or not gram.is_cuda:
+                raise ValueError('the Gram must be a contiguous float64 CUDA tensor')
+            stream = torch.cuda.current_stream(gram.device).cuda_stream
+        dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
+        _check(self.lib.byz_cosine_from_gram_dev(self.ctx, _vp(ptr), n, _vp(dist.ptr), _vp(stream)))
+        self.synchronize(stream)
+        return dist
+
+    @staticmethod
+    def _flame_sizes(n, min_samples, min_cluster_size):
+        """(ms, m) checked as the library checks them (the refusals that need no GPU)."""
+        n, ms = int(n), int(min_samples)
+        m = n // 2 + 1 if min_cluster_size is None else int(min_cluster_size)
+        if n > 16384:
+            raise NotImplementedError('flame: at most 16384 rows, got %d' % n)
+        if n < 2 or m < 2 or m > n or 2 * m <= n:
+            raise ValueError('flame: min_cluster_size = %d must lie in 2..n and exceed n / 2 (n = %d)' % (m, n))
+        if ms > 32:
+            raise NotImplementedError('flame: min_samples = %d beyond 32' % ms)
+        if ms < 0 or ms > n - 1:
+            raise ValueError('flame: min_samples = %d outside 0..n - 1 (n = %d)' % (ms, n))
+        return ms, m
+
+    def flame_info(self):
+        """{admitted, broken_rows, w_star, clip} of the last flame_select or flame on this engine (synchronises): the rows
+        admitted, the rows without a finite off-diagonal distance, the threshold (+inf: nobody) and the median norm."""
+        admitted, broken = ctypes.c_int64(0), ctypes.c_int64(0)
+        w_star, clip = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self.lib.byz_flame_info(self.ctx, ctypes.byref(admitted), ctypes.byref(broken), ctypes.byref(w_star),
+                                       ctypes.byref(clip)))
+        return {'admitted': int(admitted.value), 'broken_rows': int(broken.value), 'w_star': float(w_star.value),
+                'clip': float(clip.value)}
+
+    def flame_core_distances(self, distances, min_samples=1):
+        """flame_select's first step alone: the min_samples-th smallest off-diagonal entry of every row (order: the distance,
+        -0.0 as +0.0 and a NaN behind +inf, then the column; min_samples = 0: zeros), as a float32 numpy array."""
+        if isinstance(distances, dict):
+            raise ValueError('flame_core_distances() takes a Distances handle or a dense matrix')
+        d, _ = self._as_distances(distances)
+        ms, _ = self._flame_sizes(d.n, min_samples, d.n)
+        core = DeviceBuffer(self, (d.n,), np.float32)
+        _check(self.lib.byz_flame_core_distances_dev(self.ctx, _vp(d.ptr), d.n, ms, _vp(core.ptr), None))
+        return core.numpy()
+
+    def flame_select(self, distances, min_samples=1, min_cluster_size=None, on_device=False, like=None):
+        """FLAME's clustering on a distance matrix (a `Distances` handle or a dense symmetric matrix, diagonal +inf; cosine
+        or any other): HDBSCAN with min_cluster_size m > n / 2 (default n // 2 + 1), which is one threshold on a minimum
+        spanning tree of the mutual reachability graph (include/byzagg.h).  min_samples is the `hdbscan` package's;
+        scikit-learn's is one more.  Returns (rows, info): the admitted rows ascending (on_device=True: the 0 / 1 int32
+        flags instead, as a DeviceBuffer, or as a torch tensor beside `like`, a torch CUDA tensor) and {admitted, broken_rows,
+        w_star}."""
+        if isinstance(distances, dict):
+            raise ValueError('flame_select() takes a Distances handle or a dense matrix')
+        d, _ = self._as_distances(distances)
+        ms, m = self._flame_sizes(d.n, min_samples, min_cluster_size)
+        flags, fptr = self._out_like(like if on_device else None, d.n, np.int32)
+        _check(self.lib.byz_flame_select_dev(self.ctx, _vp(d.ptr), d.n, m, ms, _vp(fptr), None))
+        info = self.flame_info()
+        info.pop('clip')
+        return (flags if on_device else np.flatnonzero(flags.numpy()).astype(np.int64)), info
+
+    def flame(self, g, lam=0.001, min_samples=1, min_cluster_size=None, seed=0, round=0, column_offset=0, distances=None,
+              return_info=False):
+        """FLAME in one library call: cosine_distances (or `distances`, which replaces that stage), flame_select, every
+        admitted row clipped to the median norm of ALL rows, their mean over the admitted count, then gaussian_noise in
+        place with standard deviation lam * clip, everything read on the device.  Nobody admitted: the zero vector plus the
+        noise.  lam = 0: the clipped mean's bits.  return_info=True also returns {admitted_rows (ascending), admitted,
+        broken_rows, w_star, clip}."""
+        noise = self._noise_params(lam, seed, round, column_offset)
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        ms, m = self._flame_sizes(n, min_samples, min_cluster_size)
+        params = _native.FlameParams(noise.sigma, ms, m, noise.seed, noise.round, noise.column_offset)
+        dist = None
+        if distances is not None:
+            if isinstance(distances, dict):
+                raise ValueError('flame() takes a Distances handle or a dense matrix as `distances`')
+            dist, _ = self._as_distances(distances)
+            if dist.n != n:
+                raise ValueError('the distance matrix has %d rows, the gradients %d' % (dist.n, n))
+        if dm is None:
+            h = self._host_matrix(g)
+            d = h.shape[1]
+            out = np.empty(d, dtype=np.float32)
+            flags = np.zeros(n, dtype=np.int32)
+            dist_host = np.ascontiguousarray(dist.numpy(), dtype=np.float32) if dist is not None else None
+            _check(self.lib.byz_flame_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
+                                           dist_host.ctypes.data_as(ctypes.c_void_p) if dist is not None else None,
+                                           out.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p)))
+        else:
+            out, optr = self._out_like(dm, dm.cols)
+            flags_dev, fptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
+            _check(self.lib.byz_flame_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                          _vp(dist.ptr) if dist is not None else None, _vp(optr), _vp(fptr), _vp(dm.stream)))
+            self.check(dm.stream)      # (a kernel of the Gram can only flag a failure; `dist` must outlive the kernels)
+            if return_info:
+                flags = flags_dev.cpu().numpy() if _is_torch(flags_dev) else flags_dev.numpy()
+        if not return_info:
+            return out
+        info = self.flame_info()
+        info['admitted_rows'] = np.flatnonzero(flags).astype(np.int64)
+        return out, info
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration

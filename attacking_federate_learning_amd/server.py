@@ -17,6 +17,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_bucketing(then, s)         the same step with s-bucketing, reshuffled every round, in front of the rule `then`
     defend_sparsefed(k, clip, then)   the same step with SparseFed: only the k heaviest coordinates of an error-feedback memory
     defend_weak_dp(clip, sigma, then) the same step with norm clipping and Gaussian noise drawn on the GPU, fresh every round
+    defend_flame(lam, min_samples)    the same step with FLAME: the majority cluster by cosine distance, clipped, averaged, noised
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -49,6 +50,8 @@ class DeviceServer:
         self.sparse_residual = torch.zeros_like(self.current_weights)
         # weak DP's history: the calls of defend_weak_dp so far (the `round` of the next noise vector)
         self.weak_dp_round = 0
+        # FLAME's history: the calls of defend_flame so far (the `round` of the next noise vector)
+        self.flame_round = 0
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -194,6 +197,19 @@ class DeviceServer:
                                          sigma=sigma, adaptive=adaptive, seed=seed, round=self.weak_dp_round, then=then,
                                          **then_kwargs)
         self.weak_dp_round += 1
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with FLAME ----------------------------------------------------------------------------------
+    def defend_flame(self, lam=0.001, min_samples=1, seed=0):
+        """FLAME on this round's gradients (defences.flame): the majority cluster by cosine distance, clipped to the median
+        norm and averaged, Gaussian noise of standard deviation lam * (that median) drawn on the GPU, and server.py:89-90's
+        momentum step on the result, as `defend` takes it.  `flame_round`, the calls so far, is passed as the stream's
+        `round` and then incremented, as defend_weak_dp counts its own."""
+        current_grads = defences.flame(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), lam=lam,
+                                       min_samples=min_samples, seed=seed, round=self.flame_round)
+        self.flame_round += 1
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -156,6 +156,13 @@ class HipKernels:
         return self.engine.gaussian_noise(x_local, sigma, seed=seed, round=round, column_offset=column_offset, scale=scale,
                                           out=x_local)
 
+    def cosine_from_gram(self, gram):
+        return self.engine.cosine_from_gram(gram)             # Distances handle from the all-reduced Gram: the same on every rank
+
+    def flame_select(self, dist, like, min_samples=1, min_cluster_size=None):
+        # (0 / 1 flags of the admitted rows: an int32 tensor beside `like`; info): the same on every rank
+        return self.engine.flame_select(dist, min_samples=min_samples, min_cluster_size=min_cluster_size, on_device=True, like=like)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -402,6 +409,35 @@ class ShardedAggregator:
         finite = torch.isfinite(d)
         return out, {'clipped_rows': int((finite & (d > used)).sum().item()), 'excluded_rows': int((~finite).sum().item()),
                      'clip': float(used.item())}
+
+    def flame(self, g_local, users_count, corrupted_count, column_offset, lam=0.001, min_samples=1, min_cluster_size=None,
+              seed=0, round=0, gather=False, total_columns=None, return_info=False):
+        """FLAME (defences.flame's contract), columns layout.  TWO all-reduces: the N x N fp64 Gram of the ranks' slices and
+        the N squared norms.  Everything after them is replicated -- kernels.cosine_from_gram, kernels.flame_select and
+        kernels.clip_scales (adaptive) give the same flags, scales and clip on every rank -- or local to the columns: the
+        sum of the admitted rows over their count, and the noise, given column_offset, the global index of this rank's first
+        column (the Philox stream is addressed by global column).  Returns this rank's columns (gather=True: the whole
+        vector)."""
+        import torch
+        n, d_local = g_local.shape
+        gram = self.kernels.gram(g_local)
+        self._all_reduce('allreduce_flame_gram', gram)
+        dist = self.kernels.cosine_from_gram(gram)
+        admitted, info = self.kernels.flame_select(dist, g_local, min_samples=min_samples, min_cluster_size=min_cluster_size)
+        zero = torch.zeros(d_local, dtype=torch.float32, device=g_local.device)
+        sq = self.kernels.row_sqdist(g_local, zero)
+        self._all_reduce('allreduce_flame_norms', sq)
+        scales, used = self.kernels.clip_scales(sq, adaptive=True)
+        weights = torch.where(admitted != 0, scales, torch.zeros_like(scales))
+        count = (admitted != 0).sum().to(torch.float64).reshape(1)
+        v = self.kernels.scaled_rows_sum(g_local, weights, count)
+        if float(lam) != 0.0:
+            v = self.kernels.gaussian_noise(v, lam, seed=seed, round=round, column_offset=column_offset, scale=used)
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        info = dict(info, clip=float(used.item()), admitted_rows=torch.nonzero(admitted).reshape(-1).cpu().numpy())
+        return out, info
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

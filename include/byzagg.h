@@ -648,6 +648,72 @@ int byz_weak_dp_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_
 int byz_weak_dp_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_weak_dp_params* params,
                      float* out_host);
 
+/* ---- FLAME (Nguyen et al., "FLAME: Taming Backdoors in Federated Learning", USENIX Security 2022; not in the reference) ---- */
+/* The backdoor defence that robust_lr, sparsefed and weak_dp are measured against: (1) pairwise COSINE distances between the    */
+/* clients, (2) HDBSCAN (Campello, Moulavi & Sander 2013) with min_cluster_size = n / 2 + 1, everything outside the one majority  */
+/* cluster rejected, (3) the admitted clients clipped to the median norm of ALL clients and averaged, (4) Gaussian noise of       */
+/* standard deviation lambda * clip.  Stages 3 and 4 are byz_clip_scales_dev (adaptive) and byz_gaussian_noise_dev.               */
+/* Cosine distances, from the fp64 Gram g as byz_gram_dev writes it (n x n, both triangles):                                      */
+/*   c_ij = fl32(max(0, 1 - g_ij / (sqrt(g_ii) * sqrt(g_jj)))), in fp64 in this order of operations, rounded once.  The diagonal  */
+/*   is +inf, byz_pairwise_distances_dev's convention.  A row with g_ii not finite or <= 0 (a zero or non-finite client) is       */
+/*   BROKEN: its whole row and column are +inf; a non-finite g_ij gives +inf as well.  Entry (i, j) is computed from the lower    */
+/*   triangle's g at (max(i, j), min(i, j)), so the matrix is symmetric bit for bit.  n up to 16,384 (BYZ_E_UNSUPPORTED beyond).  */
+int byz_cosine_distances_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, float* dist_dev,
+                             void* stream);
+/* The second half alone: what a host of the columns layout calls after its all-reduce of the ranks' Grams.                       */
+int byz_cosine_from_gram_dev(byz_ctx* ctx, const double* gram_dev, int64_t n_rows, float* dist_dev, void* stream);
+/* The clustering, on ANY symmetric matrix in byz_pairwise_distances_dev's form (n x n fp32, diagonal +inf), Euclidean included.  */
+/* With m = min_cluster_size, 2 m > n, two clusters cannot coexist and HDBSCAN (metric precomputed, allow_single_cluster) is      */
+/* exactly this rule, with ms = min_samples in the `hdbscan` package's sense (scikit-learn's min_samples is ms + 1):              */
+/*   core_i = the ms-th smallest off-diagonal entry of row i (ms = 0: 0); order: the distance (-0.0 as +0.0, every NaN behind     */
+/*            +inf, -inf taken for +inf), then the column                                                                         */
+/*   R_ij   = max(C_ij, core_i, core_j), the mutual reachability                                                                  */
+/*   w*     = the smallest threshold at which the graph {R_ij <= w*} has a connected component of at least m vertices             */
+/*   admitted_dev[i] = 1 for the rows of that component (edges tied at w* count), 0 for every other row; no finite threshold      */
+/*            gives such a component: nobody is admitted and w* = +inf.                                                          */
+/* The components of a threshold graph are those of any minimum spanning tree cut at the same threshold: the call builds ONE MST  */
+/* (Prim, one workgroup, exactly n - 1 steps, no atomics and no loop whose length depends on the data), sorts its edges and walks */
+/* them with a union-find.  By construction roughly m rows are admitted: the densest majority.  Identical rows sit together at   */
+/* distance 0 and are admitted or rejected as a block: FLAME is a backdoor defence, not an answer to the drift attack.            */
+/* 2 <= n <= 16,384 (BYZ_E_UNSUPPORTED beyond, decided on the argument alone); 2 <= m <= n < 2 m and 0 <= ms <= n - 1             */
+/* (BYZ_E_INVALID otherwise); ms > 32: BYZ_E_UNSUPPORTED.  Nothing is written when a call is refused.  Asynchronous on `stream`.  */
+int byz_flame_select_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int64_t min_cluster_size, int64_t min_samples,
+                         int32_t* admitted_dev, void* stream);
+/* Its first step alone: core_dev[i] = core_i above (n_rows floats), the same limits on n_rows and min_samples.  Exported so     */
+/* that the core distances can be tested on their own; it leaves what byz_flame_info reports untouched.                           */
+int byz_flame_core_distances_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int64_t min_samples, float* core_dev,
+                                 void* stream);
+typedef struct byz_flame_params {
+    double lambda;             /* the noise's standard deviation is lambda * clip: finite, >= 0                        */
+    int64_t min_samples;       /* ms above: 0..32, at most n_rows - 1                                                  */
+    int64_t min_cluster_size;  /* m above; 0: n_rows / 2 + 1, the paper's                                              */
+    uint64_t seed;             /* the noise's Philox key                                                               */
+    uint64_t round;            /* the caller's round counter                                                           */
+    int64_t column_offset;     /* the global column of column 0 of G: >= 0                                             */
+} byz_flame_params;
+/* The whole defence: byz_cosine_distances_dev (dist_dev_or_null == NULL; otherwise that n x n matrix REPLACES the cosine stage,  */
+/* e.g. the angles between the clients' MODELS, which the paper compares), byz_flame_select_dev, byz_row_sqdist_dev with a zero   */
+/* centre, byz_clip_scales_dev (adaptive: clip = the median norm of all the finite rows) giving s_i, w_i = admitted_i ? s_i : 0,  */
+/* byz_scaled_rows_sum_dev with the divisor L = the admitted rows (L = 0: the zero vector, never NaN), then                       */
+/* byz_gaussian_noise_dev in place with sigma = lambda and scale_dev = the clip.  The noise is added whoever is admitted;         */
+/* lambda == 0 returns the clipped mean's bits.  admitted_dev_or_null: n_rows int32 of 0 / 1.  Every launch of the stages added   */
+/* here is enqueued up front and byz_flame_info is the call that reads anything back.  ONE EXCEPTION, inherited: the Gram         */
+/* (byz_gram_dev's path) waits once for its duplicate-row search, as byz_pairwise_distances_dev does; with dist_dev_or_null given  */
+/* there is no Gram and no wait at all.  out_dev must not overlap G (BYZ_E_INVALID).  No doubles by value.                         */
+/* Timers: BYZ_K_COUNT is part of the ABI that version 1 promises, so the new kernels report into existing slots --               */
+/* BYZ_K_DISTANCES: the cosine conversion; BYZ_K_ROW_SORT: the core distances, the edge sort and the admission; BYZ_K_MISC:        */
+/* Prim (alone in a byz_flame_select_dev call; byz_flame_dev's clip scales and weights kernels report there too).                 */
+int byz_flame_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_flame_params* params,
+                  const float* dist_dev_or_null, float* out_dev, int32_t* admitted_dev_or_null, void* stream);
+/* The last byz_flame_select_dev or byz_flame_dev on this context: the rows admitted, the rows of the distance matrix without a   */
+/* finite off-diagonal entry (the cosine stage's broken rows), w* (+inf: nobody admitted) and the clip (byz_flame_dev; 0 after a  */
+/* selection alone).  Synchronises that call's stream.  BYZ_E_INVALID before the first such call.                                 */
+int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, double* w_star, double* clip);
+/* The same on a host matrix (dist_host_or_null: n_rows x n_rows floats; out_host: n_cols floats; admitted_host_or_null).         */
+/* Synchronous.                                                                                                                   */
+int byz_flame_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_flame_params* params,
+                   const float* dist_host_or_null, float* out_host, int32_t* admitted_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -814,6 +880,13 @@ int byz_dnc_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, 
 int byz_topk_sparsify_sharded_dev(byz_ctx* ctx, const float* x_local_dev, const float* add_local_dev_or_null, int64_t n_local,
                                   int64_t n_total, int64_t k, int rank_index, int rank_count, byz_allreduce_f64_fn allreduce,
                                   void* user, float* out_local_dev, float* residual_local_dev_or_null, void* stream);
+/* FLAME over the ranks' column slices: TWO all-reduces, the n x n Gram and the n squared norms (the Gram alone is skipped when   */
+/* dist_dev_or_null is given); everything after them is replicated (the selection, the scales) or local to the columns (the sum, */
+/* and the noise, which is addressed by global column: params->column_offset is the global index of this rank's first column).   */
+/* The ranks' outputs concatenate to byz_flame_dev's vector up to the fp64 rounding of the all-reduced sums.                     */
+int byz_flame_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                          const byz_flame_params* params, byz_allreduce_f64_fn allreduce, void* user,
+                          const float* dist_dev_or_null, float* out_local_dev, int32_t* admitted_dev_or_null, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
