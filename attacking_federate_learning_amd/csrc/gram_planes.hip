@@ -822,7 +822,8 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
             for (int n = 0; n < 2; ++n) b.v[p][n] = frag_at(sp, b_slot + half, n, p);
         (void)MASK;
     };
-    // the 24 MFMAs of one 32-column half: m h' + h m' + h h' per 16 x 16 block, term-major
+    // the 24 MFMAs of one 32-column half: m h' + h m' + h h' per 16 x 16 block, term-major as written; this generic and masked
+    // path (ragged and diagonal waves) leaves their order to the compiler
     auto multiply_half = [&](const AFrags& a, const BFrags& b, auto half_c, auto mask_c) __attribute__((always_inline)) {
         constexpr unsigned MASK = decltype(mask_c)::value;
         constexpr int HALF = decltype(half_c)::value;
@@ -896,59 +897,68 @@ __global__ __launch_bounds__(512, 1) void gram_planes16_kernel(const u32x4* __re
             }
         };
         // The steady state of a FULL wave (all sixteen blocks live, both stages of super-stage sp + 3 still to be requested) with its
-        // instructions in a PINNED order: behind the barrier six groups of {one DMA piece, two fragment reads of super-stage
-        // sp + 1, four MFMAs of this super-stage's second half}.  Left to itself hipcc issues the six DMA pieces and the twelve
-        // reads first -- both waves of every SIMD at once, right behind the barrier, with the matrix pipe idle -- and the 24
-        // MFMAs behind them (45.6 -> 42.3 ms per launch at N = 4000, bitwise: EXPERIMENTS.md G7).
-        // (Three other pinned orders -- the four MFMAs in front of the DMA piece, twelve groups of {two MFMAs, a DMA piece every
-        // other group, one read}, the first half pinned as well -- were alternated on one box: 41.3 .. 41.8 ms, all four:
-        // profiles/r06o_gram_pin_orders_ab.txt.  What pays is that the DMA pieces and the reads are spread AT ALL.)
+        // instructions in a PINNED order.  Left to itself hipcc issues the six DMA pieces and the twelve reads first -- both
+        // waves of every SIMD at once, right behind the barrier, with the matrix pipe idle -- and the 24 MFMAs behind them
+        // (45.6 -> 42.3 ms per launch at N = 4000, bitwise: EXPERIMENTS.md G7; four pinned orders of the memory instructions
+        // tied at 41.3 .. 41.8 ms, profiles/r06o_gram_pin_orders_ab.txt: what pays is that they are spread AT ALL).
+        // The MFMAs of a half are issued BLOCK-MAJOR and CHAINED: the three products m h', h m', h h' of one 16 x 16 block back to
+        // back into its accumulator (SrcC = the vDst just written; the second and third share A = h), the eight blocks in a
+        // serpentine walk m0n0 m0n1 m1n1 m1n0 m2n0 ... so that a change of row keeps B.  Every accumulator receives the same
+        // products in the same order as in a term-major walk -- the Gram's bits do not move -- but the accumulator and operand
+        // registers toggle less, and at the socket's power cap energy is time: +4.7 % MFMA throughput on random data in
+        // scripts/ubench/mfma_orders.hip, a tie on zeros (EXPERIMENTS.md G10).  A sched_barrier behind every MFMA keeps the
+        // order; the memory instructions sit BETWEEN blocks, never inside a chain:
+        //   * first half: one read of the second half's B in front of every other block;
+        //   * second half, behind the barrier: {one DMA piece, two fragment reads of super-stage sp + 1} in front of each of the
+        //     first six blocks.  They write `an`, b0 and LDS, none of which this half's MFMAs read.
         // The steady state runs in TRIPS OF EIGHT super-stages = one 256-column MFMA chain, every position of the chain its own
         // straight-line code:
-        //   * position 0 starts every block's chain from C = 0 (an inline constant of the MFMA), so the flush at position 7
-        //     does not have to zero the accumulators: 64 of its 128 vector instructions gone;
-        //   * position 7 adds the first half's eight blocks to the level-1 sums INSIDE the six pinned groups behind the barrier
-        //     (their last MFMAs were issued before it) and only the second half's eight behind them;
-        //   * the first half is pinned too: one read of the second half's B per six MFMAs.
+        //   * position 0 starts every block's chain from C = 0 (an inline constant of the block's first product), so the flush at
+        //     position 7 does not have to zero the accumulators: 64 of its 128 vector instructions gone;
+        //   * position 7 adds the first half's eight blocks to the level-1 sums one per block of the second half (their last
+        //     MFMAs were issued before the barrier) and only the second half's eight behind them.  (Adding a block of the second
+        //     half two blocks after its third product as well takes the kernel to 256 registers and the in-kernel form to a spill.)
         auto super8 = [&](int sp, AFrags& a, AFrags& an, auto pos_c) __attribute__((always_inline)) {
             constexpr int POS = decltype(pos_c)::value;
             constexpr bool FRESH = POS == 0, FLUSHING = POS == 7;
             constexpr int pa[3] = {1, 0, 0};
             constexpr int pb[3] = {0, 1, 0};
             const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+            // block k = 0 .. 7 of a half in the serpentine walk: row k / 2, column walk_n(k)
+            auto walk_n = [](int k) __attribute__((always_inline)) { return ((k / 2) & 1) ? 1 - k % 2 : k % 2; };
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                b1.v[g / 2][g % 2] = frag_at(sp, b_slot + 1, g % 2, g / 2);
+            for (int k = 0; k < 8; ++k) {
+                const int m = k / 2, n = walk_n(k);
+                if (k % 2 == 0) b1.v[k / 4][m % 2] = frag_at(sp, b_slot + 1, m % 2, k / 4);
 #pragma unroll
-                for (int q = 6 * g; q < 6 * g + 6; ++q) {
-                    const int t = q / 8, m = (q % 8) / 2, n = q % 2;
+                for (int t = 0; t < 3; ++t) {
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.v[pa[t]][m], b0.v[pb[t]][n], (FRESH && t == 0) ? zero4 : acc[m][n], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
             }
             wait_vmcnt<2 * kPerWave>();
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
-            for (int g = 0; g < 6; ++g) {
-                dma_piece(2 * sp + NBUF + g / 3, g % 3);
+            for (int k = 0; k < 8; ++k) {
+                const int m = k / 2, n = walk_n(k);
+                if (k < 6) {
+                    dma_piece(2 * sp + NBUF + k / 3, k % 3);
 #pragma unroll
-                for (int r = 2 * g; r < 2 * g + 2; ++r) {
-                    if (r < 8) an.v[r / 4][r % 4] = frag_at(sp + 1, a_slot + (r % 4) / 2, (r % 4) % 2, r / 4);
-                    else b0.v[(r - 8) / 2][(r - 8) % 2] = frag_at(sp + 1, b_slot, (r - 8) % 2, (r - 8) / 2);
+                    for (int r = 2 * k; r < 2 * k + 2; ++r) {
+                        if (r < 8) an.v[r / 4][r % 4] = frag_at(sp + 1, a_slot + (r % 4) / 2, (r % 4) % 2, r / 4);
+                        else b0.v[(r - 8) / 2][(r - 8) % 2] = frag_at(sp + 1, b_slot, (r - 8) % 2, (r - 8) / 2);
+                    }
                 }
 #pragma unroll
-                for (int q = 4 * g; q < 4 * g + 4; ++q) {
-                    const int t = q / 8, m = (q % 8) / 2, n = q % 2;
+                for (int t = 0; t < 3; ++t) {
                     acc[m][2 + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.v[pa[t]][m], b1.v[pb[t]][n], (FRESH && t == 0) ? zero4 : acc[m][2 + n], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
                 if constexpr (FLUSHING) {
-                    // blocks (m, n < 2) of the first half: b = 2 m + n, eight of them over the six groups
+                    // block k of the first half: all of its products were issued in front of the barrier
 #pragma unroll
-                    for (int b = (8 * g) / 6; b < (8 * (g + 1)) / 6; ++b)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc2[b / 2][b % 2][e] += acc[b / 2][b % 2][e];
+                    for (int e = 0; e < 4; ++e) acc2[m][k % 2][e] += acc[m][k % 2][e];
                 }
-                __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (FLUSHING) {
 #pragma unroll
