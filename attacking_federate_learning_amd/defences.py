@@ -28,6 +28,13 @@ class DefenseTypes:
         return self.value
 
 
+def _upload_once(users_grads, stage=True):
+    """(matrix, back): a host matrix uploaded once for the calls that follow (stage=False: left where it is), and what brings
+    a result of theirs back -- back(v) is v.numpy() for a DeviceBuffer when the matrix came from the host, else v."""
+    matrix, host = get_engine().stage(users_grads) if stage else (users_grads, False)
+    return matrix, (lambda v: v.numpy() if host and isinstance(v, DeviceBuffer) else v)
+
+
 def no_defense(users_grads, users_count, corrupted_count):
     """Column mean of the gradient matrix (reference defences.py:13-14)."""
     return get_engine().no_defense(users_grads, users_count, corrupted_count)
@@ -128,15 +135,9 @@ def nnm(users_grads, users_count, corrupted_count, then=None, distances=None, **
     `trimmed_mean`, `coordinate_median`, `geometric_median`, ... -- and the mixed matrix stays on the device in between.
     `distances` (optional): a `Distances` handle of users_grads.  Not one of the `defend` keys: the reference's main.py offers
     only those four, and this is no rule by itself."""
-    engine = get_engine()
-    host = engine._device_matrix(users_grads) is None
-    if host and then is not None:
-        users_grads = engine.to_device(engine._host_matrix(users_grads))
-    mixed = engine.nnm(users_grads, users_count, corrupted_count, distances=distances)
-    if then is None:
-        return mixed
-    out = then(mixed, users_count, corrupted_count, **then_kwargs)
-    return out.numpy() if host and isinstance(out, DeviceBuffer) else out
+    matrix, back = _upload_once(users_grads, stage=then is not None)
+    mixed = get_engine().nnm(matrix, users_count, corrupted_count, distances=distances)
+    return mixed if then is None else back(then(mixed, users_count, corrupted_count, **then_kwargs))
 
 
 def bucketing(users_grads, users_count, corrupted_count, s=2, then=None, perm=None, seed=0, **then_kwargs):
@@ -153,18 +154,12 @@ def bucketing(users_grads, users_count, corrupted_count, s=2, then=None, perm=No
     bucketing_permutation(rows, seed), drawn on the host; the paper reshuffles every round, so pass a new seed per round.
     Pre-aggregations chain: bucketing(..., then=functools.partial(nnm, then=rule)).  Not one of the `defend` keys: the
     reference's main.py offers only those four, and this is no rule by itself."""
-    engine = get_engine()
     rows = int(users_grads.shape[0])
     if perm is None:
         perm = bucketing_permutation(rows, seed)
-    host = engine._device_matrix(users_grads) is None
-    if host and then is not None:
-        users_grads = engine.to_device(engine._host_matrix(users_grads))
-    bucketed = engine.bucket_means(users_grads, s, perm)
-    if then is None:
-        return bucketed
-    out = then(bucketed, -(-rows // int(s)), corrupted_count, **then_kwargs)
-    return out.numpy() if host and isinstance(out, DeviceBuffer) else out
+    matrix, back = _upload_once(users_grads, stage=then is not None)
+    bucketed = get_engine().bucket_means(matrix, s, perm)
+    return bucketed if then is None else back(then(bucketed, -(-rows // int(s)), corrupted_count, **then_kwargs))
 
 
 def robust_lr(users_grads, users_count, corrupted_count, theta=None, then=None, return_votes=False, **then_kwargs):
@@ -185,15 +180,10 @@ def robust_lr(users_grads, users_count, corrupted_count, theta=None, then=None, 
     theta = engine._theta(theta, int(users_grads.shape[0]))
     if then is None:
         return engine.robust_lr(users_grads, theta, return_votes=return_votes)
-    host = engine._device_matrix(users_grads) is None
-    if host:
-        users_grads = engine.to_device(engine._host_matrix(users_grads))
-    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
-    votes = engine.sign_votes(users_grads)
-    out = engine.sign_flip(agg, votes, theta)
-    if host:
-        out = out.numpy() if isinstance(out, DeviceBuffer) else out
-        votes = votes.numpy() if isinstance(votes, DeviceBuffer) else votes
+    matrix, back = _upload_once(users_grads)
+    agg = then(matrix, users_count, corrupted_count, **then_kwargs)
+    votes = engine.sign_votes(matrix)
+    out, votes = back(engine.sign_flip(agg, votes, theta)), back(votes)
     return (out, votes) if return_votes else out
 
 
@@ -221,18 +211,13 @@ def sparsefed(users_grads, users_count, corrupted_count, k=None, clip=10.0, resi
         return (out, res) if return_residual else out
     if not callable(then):
         raise TypeError('sparsefed: `then` is the rule that supplies the aggregate, e.g. defences.coordinate_median, or None')
-    host = engine._device_matrix(users_grads) is None
-    if host:
-        users_grads = engine.to_device(engine._host_matrix(users_grads))
-    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
+    matrix, back = _upload_once(users_grads)
+    agg = then(matrix, users_count, corrupted_count, **then_kwargs)
     if residual is None:
         out, res = engine.topk_sparsify(agg, k)              # a zero memory: W is the aggregate
     else:
         out, res = engine.topk_sparsify(residual, k, add=agg, residual=residual)
-    if host:
-        out = out.numpy() if isinstance(out, DeviceBuffer) else out
-        res = res.numpy() if isinstance(res, DeviceBuffer) else res
-    return (out, res) if return_residual else out
+    return (back(out), back(res)) if return_residual else back(out)
 
 
 def gaussian_noise(vector, sigma, seed=0, round=0, column_offset=0):
@@ -266,14 +251,8 @@ def weak_dp(users_grads, users_count, corrupted_count, clip=10.0, sigma=0.01, ad
         raise TypeError('weak_dp: `then` is the rule that supplies the aggregate, e.g. defences.coordinate_median, or None')
     if adaptive or return_info:
         raise ValueError('weak_dp: adaptive and return_info describe the clipping, which a rule `then` replaces')
-    host = engine._device_matrix(users_grads) is None
-    if host:
-        users_grads = engine.to_device(engine._host_matrix(users_grads))
-    agg = then(users_grads, users_count, corrupted_count, **then_kwargs)
-    out = engine.gaussian_noise(agg, sigma, seed=seed, round=round)
-    if host:
-        out = out.numpy() if isinstance(out, DeviceBuffer) else out
-    return out
+    matrix, back = _upload_once(users_grads)
+    return back(engine.gaussian_noise(then(matrix, users_count, corrupted_count, **then_kwargs), sigma, seed=seed, round=round))
 
 
 def cosine_distances(users_grads):

@@ -94,12 +94,38 @@ def _check(rc):
     raise EngineError('libbyzagg error %d: %s' % (rc, msg))
 
 
+def _torch():
+    """The one lazy import: the engine loads and runs on a host without torch."""
+    import torch
+    return torch
+
+
 def _is_torch(x):
     return type(x).__module__.split('.')[0] == 'torch'
 
 
 def _vp(x):
+    """A void* for tests and scripts that call the library themselves; the engine passes its ints as they are."""
     return ctypes.c_void_p(int(x)) if x else None
+
+
+def _is_device(x):
+    return isinstance(x, DeviceBuffer) or (_is_torch(x) and x.is_cuda)
+
+
+def _stream_of(t):
+    return _torch().cuda.current_stream(t.device).cuda_stream
+
+
+def _to_host(v):
+    """numpy from a torch tensor (wherever it lives) or from anything numpy takes."""
+    return v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
+
+
+def _hp(a):
+    """The address of a host array, None for None.  (Device addresses, streams and these are Python ints: the prototypes
+    of _native.load() turn an int or None into a void*.)"""
+    return None if a is None else a.ctypes.data
 
 
 class DeviceBuffer:
@@ -117,20 +143,19 @@ class DeviceBuffer:
     def upload(self, array):
         array = np.ascontiguousarray(array, dtype=self.dtype)
         assert array.nbytes == self.nbytes
-        _check(self.engine.lib.byz_upload(self.engine.ctx, _vp(self.ptr), array.ctypes.data_as(ctypes.c_void_p),
-                                          self.nbytes, None))
-        _check(self.engine.lib.byz_stream_sync(self.engine.ctx, None))
+        _check(self.engine.lib.byz_upload(self.engine.ctx, self.ptr, _hp(array), self.nbytes, None))
+        self.engine.synchronize()
         return self
 
     def numpy(self):
         out = np.empty(self.shape, dtype=self.dtype)
-        _check(self.engine.lib.byz_download(self.engine.ctx, out.ctypes.data_as(ctypes.c_void_p), _vp(self.ptr),
-                                            self.nbytes, None))
+        _check(self.engine.lib.byz_download(self.engine.ctx, _hp(out), self.ptr, self.nbytes, None))
+        self.engine._synced(None)
         return out
 
     def free(self):
         if self.ptr and self.engine.ctx:
-            self.engine.lib.byz_free(self.engine.ctx, _vp(self.ptr))
+            self.engine.lib.byz_free(self.engine.ctx, self.ptr)
         self.ptr = None
 
     def __del__(self):
@@ -167,12 +192,212 @@ class Distances:
         return out
 
 
-class _Matrix:
-    """Uniform view of a caller's matrix: device pointer, shape, leading dimension, stream."""
+class _Operand:
+    """Anything handed to a kernel: device pointer, shape, for a matrix the leading dimension, and `keep`, what holds the
+    memory -- the caller's torch tensor or DeviceBuffer, or a temporary of this call (an upload, or the copy torch made to
+    convert).  `torch_like` is the tensor when it is one; `stream` is then torch's current stream on its device."""
 
-    def __init__(self, ptr, rows, cols, ld, stream, keepalive, torch_like=None):
-        self.ptr, self.rows, self.cols, self.ld, self.stream = ptr, rows, cols, ld, stream
-        self.keepalive, self.torch_like = keepalive, torch_like
+    def __init__(self, ptr, shape, keep, torch_like=None, ld=None):
+        self.ptr, self.shape, self.keep, self.torch_like, self.ld = ptr, tuple(int(s) for s in shape), keep, torch_like, ld
+        self.size = int(np.prod(self.shape))
+
+    rows = property(lambda self: self.shape[0])
+    cols = property(lambda self: self.shape[1])
+    stream = property(lambda self: None if self.torch_like is None else _stream_of(self.torch_like))
+
+
+# The refusal texts of the operand kinds (_Call.operand): %(n)d is the expected count, %(got)d the count found.
+_F64 = {'buffer': 'a DeviceBuffer here must hold %(n)d float64 values',
+        'device': 'the vector lives on %(device)s, this engine drives cuda:%(engine)d', 'length': 'expected %(n)d values, got %(got)d'}
+_ROWS = {'buffer': 'a DeviceBuffer row_index must hold int32', 'kind': 'row_index must hold integers, got %(dtype)s',
+         'range': 'row_index out of range: [%(lo)d, %(hi)d] for %(n)d rows'}
+
+
+def _f32(length):
+    """float32 vectors used where they are; `length` is the caller's text for a wrong length."""
+    return {'layout': 'device vectors must be contiguous float32', 'length': length}
+
+
+_DIFFER = _f32('vector lengths differ: %(n)d and %(got)d')
+
+
+def _i32(what):
+    return {'buffer': 'a DeviceBuffer of %s must hold %%(n)d int32 values' % what, 'kind': what + ' must be integers, got %(dtype)s',
+            'device': 'the %s live on %%(device)s, this engine drives cuda:%%(engine)d' % what,
+            'length': 'expected %%(n)d %s, got %%(got)d' % what}
+
+
+def _lists(what):
+    return {'buffer': 'a DeviceBuffer of neighbour lists must hold int32', 'kind': 'neighbour lists must hold integers, got %(dtype)s',
+            'device': 'the neighbour lists live on %(device)s, this engine drives cuda:%(engine)d',
+            'shape': 'expected %%(n)d %s, got shape %%(shape)r' % what}
+
+
+class _Call:
+    """One engine call that launches work: it collects the operands, and from them fixes the stream (torch's current one
+    when any operand is a torch tensor, else `stream`: None is the library's default), where the outputs go (beside the
+    operand that leads: torch for torch, a DeviceBuffer otherwise) and the kind of the result (numpy when what leads came
+    from the host).
+
+    The lifetime rule, in one place: a device temporary this call made (`upload`, `temporary`) must outlive the kernels that
+    read it, so on exit this call's stream is synchronised if there is such a temporary and work was launched on the stream
+    (`run`) with nothing synchronising it since -- synchronize(), check(), an *_info read and a library call that fills a
+    host out-parameter do, and a download does for the default stream.  The caller's own tensors and DeviceBuffers never
+    cause a synchronisation, nor do the copies torch makes: its allocator orders their reuse on the stream of the launch."""
+
+    def __init__(self, engine, stream=None):
+        self.engine, self.stream, self.like, self.resident, self.temps, self._torch_stream = engine, stream, None, False, [], False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None and self.temps:
+            self.settle()
+
+    def settle(self):
+        if self.engine._in_flight(self.stream):
+            self.engine.synchronize(self.stream)
+
+    @property
+    def host(self):
+        return self.like is None and not self.resident
+
+    def temporary(self, buf):
+        self.temps.append(buf)
+        return buf
+
+    def upload(self, array):
+        return self.temporary(self.engine.to_device(array))
+
+    def beside(self, tensor, on_its_stream=True):
+        """The outputs go beside `tensor`, a torch CUDA tensor that is no operand (on_its_stream: and the work to its stream)."""
+        self.like = tensor
+        if on_its_stream:
+            self.stream, self._torch_stream = _stream_of(tensor), True
+
+    def _adopt(self, op, leads):
+        if op.torch_like is not None:
+            if not self._torch_stream:          # (every torch operand is on this engine's GPU: one lookup serves them all)
+                self.stream, self._torch_stream = op.stream, True
+            if leads:
+                self.like = op.torch_like
+        elif leads and not any(op.keep is t for t in self.temps):
+            self.resident = True
+        return op
+
+    def matrix(self, g, needs=None):
+        """The gradient matrix (or its _Operand): used where it is when device-resident; a host matrix is staged, or refused
+        under the name `needs` of a method that takes device-resident matrices only."""
+        m = g if isinstance(g, _Operand) else self.engine._device_matrix(g)
+        if m is None:
+            if needs:
+                raise ValueError('%s() takes a device-resident matrix' % needs)
+            m = self.engine._device_matrix(self.upload(self.engine._host_matrix(g)))
+        return self._adopt(m, True)
+
+    def distances(self, distances):
+        """_as_distances, with the dense matrix it may have uploaded as this call's temporary."""
+        d, keys = self.engine._as_distances(distances)
+        if d is not distances:
+            self.temporary(d)
+        return d, keys
+
+    def as_it_lies(self, v, leads=False):
+        """A device-resident operand on the caller's word: the address of a torch tensor or a DeviceBuffer, nothing checked."""
+        op = _Operand(v.data_ptr(), v.shape, v, torch_like=v) if _is_torch(v) else _Operand(v.ptr, v.shape, v)
+        return self._adopt(op, leads)
+
+    def operand(self, v, dtype, says, shape=None, convert=True, rows=None, leads=False):
+        """A vector, index list or second matrix of `dtype` -> _Operand.  A DeviceBuffer or a torch CUDA tensor is used where
+        it is, anything else (numpy, a torch CPU tensor, a list) is uploaded.
+        says: the refusal texts of this kind of operand (_F64, _ROWS, _f32(), _i32(), _lists()); it is what keeps every
+        caller's wording.  A kind without a 'buffer' text asserts a DeviceBuffer's dtype, as it always has.
+        shape: an int is the expected number of entries (the operand is flattened), a tuple the expected shape (None: any
+        extent), None is any flat length.
+        convert: a torch CUDA tensor of another dtype or layout is converted (it must be on this engine's GPU), else refused.
+        rows: every entry must lie in [0, rows) -- for a torch tensor one reduction and a host synchronisation, a
+        DeviceBuffer is the caller's word.  leads: the outputs go beside this operand (see _Call)."""
+        dtype, flat = np.dtype(dtype), not isinstance(shape, tuple)
+        fields = {'n': shape if flat else shape[0], 'engine': self.engine.device}
+        if isinstance(v, DeviceBuffer):
+            size = int(np.prod(v.shape))
+            fields['n'] = size if fields['n'] is None else fields['n']
+            if 'buffer' not in says:
+                assert v.dtype == dtype
+            elif v.dtype != dtype or ('%(n)d' in says['buffer'] and shape is not None and size != shape):   # (one text for both)
+                raise ValueError(says['buffer'] % fields)
+            op = _Operand(v.ptr, (size,) if flat else v.shape, v)
+        elif _is_torch(v) and v.is_cuda:
+            torch = _torch()
+            want = getattr(torch, dtype.name)
+            if convert:
+                if v.device.index != self.engine.device:
+                    raise ValueError(says['device'] % dict(fields, device=v.device))
+                v = v.to(want).contiguous()
+            elif v.dtype != want or not v.is_contiguous():
+                raise ValueError(says['layout'])
+            if flat:
+                v = v.reshape(-1)
+            if rows is not None and v.numel():
+                self._in_range(says, int(v.min().item()), int(v.max().item()), rows)
+            op = _Operand(v.data_ptr(), v.shape, v, torch_like=v)
+        else:
+            host = _to_host(v)
+            if dtype.kind == 'i' and host.dtype.kind not in 'iu':
+                raise ValueError(says['kind'] % {'dtype': host.dtype})
+            host = host.reshape(-1) if flat else host
+            if rows is not None and host.size:
+                self._in_range(says, host.min(), host.max(), rows)        # (before the cast: it could wrap a wide index)
+            buf = self.upload(np.ascontiguousarray(host, dtype=dtype))
+            op = _Operand(buf.ptr, buf.shape, buf)
+        if flat and shape is not None and op.size != shape:
+            raise ValueError(says['length'] % dict(fields, got=op.size))
+        if not flat and (len(op.shape) != len(shape) or any(s is not None and s != n for s, n in zip(shape, op.shape))):
+            raise ValueError(says['shape'] % dict(fields, shape=op.shape))
+        return self._adopt(op, leads)
+
+    @staticmethod
+    def _in_range(says, lo, hi, rows):
+        if lo < 0 or hi >= rows:
+            raise ValueError(says['range'] % {'lo': lo, 'hi': hi, 'n': rows})
+
+    def written(self, v, n, what):
+        """A float32 vector of n entries the call writes: it must already be on the device."""
+        if not _is_device(v):
+            raise ValueError('%s must be a device-resident float32 vector of %d entries' % (what, n))
+        return self.operand(v, np.float32, _f32(what + ' has %(got)d entries, expected %(n)d'), n, convert=False)
+
+    def out(self, shape, dtype=np.float32, want=True):
+        """An output array (a length or a shape) -> (array, device pointer): a torch tensor beside a torch operand, a
+        DeviceBuffer otherwise; (None, None) when it is not wanted -- the library takes a null pointer then."""
+        if not want:
+            return None, None
+        shape = tuple(int(n) for n in shape) if isinstance(shape, tuple) else (int(shape),)
+        if self.like is not None:
+            torch = _torch()
+            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=self.like.device)   # float32, int32, float64
+            return t, t.data_ptr()
+        b = DeviceBuffer(self.engine, shape, dtype)
+        return b, b.ptr
+
+    def run(self, rc, reads_back=False):
+        """The return code of the library call that launched this call's work; reads_back: it filled a host out-parameter,
+        so the library waited for the kernels."""
+        _check(rc)
+        self.engine._launched(self.stream, waited=reads_back)
+
+    def numpy(self, buf):
+        """A DeviceBuffer of this call's results, downloaded.  The download waits for the default stream only."""
+        if self.stream:
+            self.settle()
+        return buf.numpy()
+
+    def result(self, x):
+        """The result in the caller's kind: numpy where the inputs came from the host, else as allocated."""
+        if isinstance(x, tuple):
+            return tuple(self.result(v) for v in x)
+        return self.numpy(x) if self.host and isinstance(x, DeviceBuffer) else x
 
 
 class Engine:
@@ -185,6 +410,7 @@ class Engine:
         self.ctx = ctx
         self.device = int(device)
         self._assemble_key = None     # what the context's device-side pointer table holds (assemble_rows)
+        self._unsynced, self._last = set(), 0    # streams with work launched and not synchronised since; the last launch's
 
     def close(self):
         if getattr(self, 'ctx', None):
@@ -205,59 +431,77 @@ class Engine:
         array = np.ascontiguousarray(array)
         return DeviceBuffer(self, array.shape, array.dtype).upload(array)
 
+    def stage(self, g):
+        """(matrix, was_host): `g` itself when it is device-resident, else a DeviceBuffer holding the host matrix -- for a
+        caller that runs several calls on one upload and brings the last result back itself."""
+        if self._device_matrix(g) is not None:
+            return g, False
+        return self.to_device(self._host_matrix(g)), True
+
     def reserve(self, n_rows, n_cols):
         _check(self.lib.byz_ctx_reserve(self.ctx, int(n_rows), int(n_cols)))
 
     def synchronize(self, stream=None):
-        _check(self.lib.byz_stream_sync(self.ctx, _vp(stream)))
+        _check(self.lib.byz_stream_sync(self.ctx, stream))
+        self._synced(stream)
 
     def check(self, stream=None):
         """Synchronise and raise if a kernel of an asynchronous call flagged a failure on the device."""
-        _check(self.lib.byz_ctx_check(self.ctx, _vp(stream)))
+        _check(self.lib.byz_ctx_check(self.ctx, stream))
+        self._synced(stream)
+
+    def _launched(self, stream, waited=False):
+        self._last = int(stream or 0)
+        (self._unsynced.discard if waited else self._unsynced.add)(self._last)
+
+    def _synced(self, stream):
+        self._unsynced.discard(int(stream or 0))
+
+    def _in_flight(self, stream):
+        return int(stream or 0) in self._unsynced
+
+    def _read(self, fn, types, *tail):
+        """The host out-parameters of an *_info or counter function, as Python values (the library synchronises)."""
+        outs = [t() for t in types]
+        _check(fn(self.ctx, *[ctypes.byref(o) for o in outs], *tail))
+        self._unsynced.discard(self._last)      # (the library synchronises the stream of the rule's last call)
+        return [o.value for o in outs]
 
     def _device_matrix(self, g):
-        """torch CUDA tensor / DeviceBuffer -> _Matrix; None for host arrays."""
+        """torch CUDA tensor / DeviceBuffer -> _Operand; None for host arrays."""
         if isinstance(g, DeviceBuffer):
             assert g.dtype == np.float32 and len(g.shape) == 2
-            return _Matrix(g.ptr, g.shape[0], g.shape[1], g.shape[1], None, g)
+            return _Operand(g.ptr, g.shape, g, ld=g.shape[1])
         if _is_torch(g):
-            import torch
             if not g.is_cuda:
                 return None
-            if g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1:
+            if g.dtype != _torch().float32 or g.dim() != 2 or g.stride(1) != 1:
                 raise ValueError('device matrices must be 2-D float32 with unit column stride')
             if g.device.index != self.device:
                 raise ValueError('the matrix lives on %s, this engine drives cuda:%d' % (g.device, self.device))
-            stream = torch.cuda.current_stream(g.device).cuda_stream
-            return _Matrix(g.data_ptr(), g.shape[0], g.shape[1], g.stride(0), stream, g, torch_like=g)
+            return _Operand(g.data_ptr(), g.shape, g, torch_like=g, ld=g.stride(0))
         return None
 
     @staticmethod
     def _host_matrix(g):
-        if _is_torch(g):
-            g = g.detach().cpu().numpy()
-        g = np.asarray(g)
+        g = _to_host(g)
         if g.ndim != 2:
             raise ValueError('expected a 2-D gradient matrix, got shape %r' % (g.shape,))
         return np.ascontiguousarray(g, dtype=np.float32)
 
-    def _out_like(self, like, shape, dtype=np.float32):
-        """Output array (a length or a shape) for a device-resident input -> (array, device pointer): a torch tensor where the
-        input (`like`: its _Matrix, or a torch tensor or None) was torch, a DeviceBuffer otherwise."""
-        example = like.torch_like if isinstance(like, _Matrix) else like
-        shape = tuple(int(n) for n in shape) if isinstance(shape, tuple) else (int(shape),)
-        if example is not None:
-            import torch
-            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=example.device)   # float32, int32, float64
-            return t, t.data_ptr()
-        b = DeviceBuffer(self, shape, dtype)
-        return b, b.ptr
+    def _allreduce_callback(self, all_reduce):
+        """all_reduce(tensor) as the library's byz_allreduce_f64_fn; the caller holds the returned object until the library
+        call has returned."""
+        device = self.device
 
-    def _sync_if_ours(self, keep, stream):
-        """`keep` is the index / staging buffer a call handed to its kernel: a DeviceBuffer we made is freed when the call
-        returns, so the temporary must outlive the kernel (torch orders its own tensors' memory)."""
-        if keep is not None and not _is_torch(keep):
-            self.synchronize(stream)
+        def reduce_on_ranks(user, buf, count, stream):
+            try:
+                if all_reduce is not None:
+                    all_reduce(_torch().as_tensor(_DeviceF64(buf, count), device='cuda:%d' % device))
+                return 0
+            except Exception:      # noqa: BLE001  (a Python exception must not unwind through the C frames)
+                return 1
+        return _native.ALLREDUCE_F64_FN(reduce_on_ranks)
 
     # ---- defences.py -------------------------------------------------------------------------
     def defend_host(self, name, g, users_count, corrupted_count, check_assert=True, want_aux=False):
@@ -267,116 +511,108 @@ class Engine:
         out = np.empty(d, dtype=np.float32)
         theta = max(int(users_count) - 2 * int(corrupted_count), 1)
         aux = np.full(max(theta, 1), -1, dtype=np.int32) if want_aux else None
-        _check(self.lib.byz_defend_host(self.ctx, NAME_TO_ID[name], g.ctypes.data_as(ctypes.c_void_p), n, d,
-                                        int(users_count), int(corrupted_count), int(bool(check_assert)),
-                                        out.ctypes.data_as(ctypes.c_void_p),
-                                        aux.ctypes.data_as(ctypes.c_void_p) if want_aux else None))
+        _check(self.lib.byz_defend_host(self.ctx, NAME_TO_ID[name], _hp(g), n, d, int(users_count), int(corrupted_count),
+                                        int(bool(check_assert)), _hp(out), _hp(aux)))
         return (out, aux) if want_aux else out
 
     def no_defense(self, g, users_count=None, corrupted_count=None):
-        m = self._device_matrix(g)
-        if m is None:
+        dm = self._device_matrix(g)
+        if dm is None:
             return self.defend_host('NoDefense', g, 0, 0)
-        out, ptr = self._out_like(m, m.cols)
-        _check(self.lib.byz_no_defense_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(ptr), _vp(m.stream)))
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            out, ptr = c.out(m.cols)
+            c.run(self.lib.byz_no_defense_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, ptr, c.stream))
         return out
 
     def pairwise_distances(self, g):
-        m = self._device_matrix(g)
-        stage = None
-        if m is None:
-            stage = self.to_device(self._host_matrix(g))
-            m = self._device_matrix(stage)
-        dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
-        _check(self.lib.byz_pairwise_distances_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(dist.ptr),
-                                                   _vp(m.stream)))
-        self.check(m.stream)
+        with _Call(self) as c:
+            m = c.matrix(g)
+            dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
+            c.run(self.lib.byz_pairwise_distances_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, dist.ptr, c.stream))
+            self.check(c.stream)
         return Distances(dist, m.rows)
 
     def gram(self, g):
         """fp64 Gram matrix of a device-resident slice (the D-sharded multi-GPU path all-reduces these)."""
-        m = self._device_matrix(g)
-        if m is None:
-            raise ValueError('gram() takes a device-resident matrix')
-        out, ptr = self._out_like(m, (m.rows, m.rows), np.float64)
-        _check(self.lib.byz_gram_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(ptr), _vp(m.stream)))
+        with _Call(self) as c:
+            m = c.matrix(g, needs='gram')
+            out, ptr = c.out((m.rows, m.rows), np.float64)
+            c.run(self.lib.byz_gram_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, ptr, c.stream))
         return out
+
+    def _row_index(self, c, row_index, m, validate):
+        """row_index (None: every row) -> (device pointer, count).  The kernel reads int32 indices straight from device
+        memory: anything else is converted, and (unless the caller vouches for a torch tensor) checked against the matrix
+        height, because an out-of-range index is an out-of-bounds read on the GPU.  A torch tensor must be on the matrix's GPU."""
+        if row_index is None:
+            return None, m.rows
+        if _is_torch(row_index):
+            if not row_index.is_cuda or (m.torch_like is not None and row_index.device != m.torch_like.device) \
+                    or row_index.device.index != self.device:
+                raise ValueError('row_index must live on the GPU of the matrix (cuda:%d), got %s'
+                                 % (self.device, row_index.device))
+            torch = _torch()
+            if row_index.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+                raise ValueError('row_index must hold integers, got %s' % row_index.dtype)
+        idx = c.operand(row_index, np.int32, _ROWS, rows=m.rows if validate or not _is_torch(row_index) else None)
+        return idx.ptr, idx.size
 
     def gram_share_add(self, panel, row_index, share_count, share_index, gram):
         """`gram` (the caller's N x N fp64 device buffer, zeroed before the first panel) += this rank's share of the Gram
         tiles of `panel`: the per-panel N x N addition pass of the clients layout folded into the reduction kernel."""
-        m = self._device_matrix(panel)
-        if m is None:
-            raise ValueError('gram_share_add() takes a device-resident matrix')
-        n_rows, idx_ptr, keep = m.rows, None, None
-        if row_index is not None:
-            idx_ptr, n_rows, keep = self._row_index(row_index, m, validate=False)
-        if tuple(gram.shape) != (n_rows, n_rows):
-            raise ValueError('the accumulator must be %d x %d' % (n_rows, n_rows))
-        # the kernel read-modify-writes N * N doubles at this address: anything else than a contiguous fp64 buffer on the
-        # panel's device would corrupt memory silently (ADVICE r4)
-        if _is_torch(gram):
-            import torch
-            if gram.dtype != torch.float64 or not gram.is_contiguous() or not gram.is_cuda:
-                raise ValueError('the accumulator must be a contiguous float64 CUDA tensor')
-            if m.torch_like is not None and gram.device != m.torch_like.device:
-                raise ValueError('the accumulator lives on %s, the panel on %s' % (gram.device, m.torch_like.device))
-            ptr = gram.data_ptr()
-        elif isinstance(gram, DeviceBuffer):
-            if gram.dtype != np.float64:
+        with _Call(self) as c:
+            m = c.matrix(panel, needs='gram_share_add')
+            idx_ptr, n_rows = self._row_index(c, row_index, m, validate=False)
+            if tuple(gram.shape) != (n_rows, n_rows):
+                raise ValueError('the accumulator must be %d x %d' % (n_rows, n_rows))
+            # the kernel read-modify-writes N * N doubles at this address: anything else than a contiguous fp64 buffer on the
+            # panel's device would corrupt memory silently (ADVICE r4)
+            if _is_torch(gram):
+                if gram.dtype != _torch().float64 or not gram.is_contiguous() or not gram.is_cuda:
+                    raise ValueError('the accumulator must be a contiguous float64 CUDA tensor')
+                if m.torch_like is not None and gram.device != m.torch_like.device:
+                    raise ValueError('the accumulator lives on %s, the panel on %s' % (gram.device, m.torch_like.device))
+            elif not isinstance(gram, DeviceBuffer):
+                raise ValueError('the accumulator must be a torch CUDA tensor or a DeviceBuffer')
+            elif gram.dtype != np.float64:
                 raise ValueError('the accumulator must be float64')
-            ptr = gram.ptr
-        else:
-            raise ValueError('the accumulator must be a torch CUDA tensor or a DeviceBuffer')
-        _check(self.lib.byz_gram_share_add_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
-                                               int(share_count), int(share_index), _vp(ptr), _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+            acc = c.as_it_lies(gram)
+            c.run(self.lib.byz_gram_share_add_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, int(share_count),
+                                                  int(share_index), acc.ptr, c.stream))
         return gram
 
     def gram_share(self, panel, row_index, share_count, share_index):
         """This rank's share of the Gram tiles of `panel` (a device matrix every rank holds, e.g. an all-gathered column
         panel): zeros outside the share, so the ranks' outputs SUM to the Gram.  `row_index` (int32, on the device, or
         None): logical row r is panel[row_index[r]] -- skips the padding rows of an unevenly sharded gather."""
-        m = self._device_matrix(panel)
-        if m is None:
-            raise ValueError('gram_share() takes a device-resident matrix')
-        n_rows, idx_ptr, keep = m.rows, None, None
-        if row_index is not None:
-            idx_ptr, n_rows, keep = self._row_index(row_index, m, validate=False)
-        out, ptr = self._out_like(m, (n_rows, n_rows), np.float64)
-        _check(self.lib.byz_gram_share_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
-                                           int(share_count), int(share_index), _vp(ptr), _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+        with _Call(self) as c:
+            m = c.matrix(panel, needs='gram_share')
+            idx_ptr, n_rows = self._row_index(c, row_index, m, validate=False)
+            out, ptr = c.out((n_rows, n_rows), np.float64)
+            c.run(self.lib.byz_gram_share_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, int(share_count),
+                                              int(share_index), ptr, c.stream))
         return out
 
     def near_pairs_count(self, stream=None):
         """Pairs the last distance kernel could not resolve through the Gram identity (synchronises)."""
-        count = ctypes.c_int64(0)
-        _check(self.lib.byz_near_pairs_count(self.ctx, ctypes.byref(count), _vp(stream)))
-        return int(count.value)
+        return self._read(self.lib.byz_near_pairs_count, [ctypes.c_int64], stream)[0]
 
     def near_pairs_sqdist(self, g, count, row_index=None):
         """Per listed pair, the sum over g's columns of the squared fp32 difference (fp64): this rank's part."""
-        m = self._device_matrix(g)
-        if m is None:
-            raise ValueError('near_pairs_sqdist() takes a device-resident matrix')
-        idx_ptr, keep = None, None
-        if row_index is not None:
-            idx_ptr, _, keep = self._row_index(row_index, m, validate=False)
-        sq, sq_ptr = self._out_like(m, count, np.float64)
-        _check(self.lib.byz_near_pairs_sqdist_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(idx_ptr), _vp(sq_ptr),
-                                                  _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+        with _Call(self) as c:
+            m = c.matrix(g, needs='near_pairs_sqdist')
+            idx_ptr, _ = self._row_index(c, row_index, m, validate=False)
+            sq, sq_ptr = c.out(count, np.float64)
+            c.run(self.lib.byz_near_pairs_sqdist_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, idx_ptr, sq_ptr, c.stream))
         return sq
 
     def near_pairs_apply(self, sq, distances, stream=None):
         """distances[i, j] = sqrt(sq[p]) for every listed pair, then identical rows are made to tie exactly again."""
-        ptr = sq.data_ptr() if _is_torch(sq) else sq.ptr
-        if _is_torch(sq):
-            import torch
-            stream = torch.cuda.current_stream(sq.device).cuda_stream
-        _check(self.lib.byz_near_pairs_apply_dev(self.ctx, _vp(ptr), int(distances.n), _vp(distances.ptr), _vp(stream)))
-        self.check(stream)
+        with _Call(self, stream) as c:
+            sq = c.as_it_lies(sq)
+            c.run(self.lib.byz_near_pairs_apply_dev(self.ctx, sq.ptr, int(distances.n), distances.ptr, c.stream))
+            self.check(c.stream)
 
     def distances_from_gram(self, gram, n, stream=None, local_columns=None, all_reduce=None):
         """Distances from an (all-reduced) fp64 Gram.  The Gram identity cannot resolve nearly coincident rows, so the
@@ -384,21 +620,19 @@ class Engine:
         difference itself: per-rank sums of squared differences, `all_reduce(tensor)` over the ranks when given, then
         applied -- the same result as the single-GPU path, which does all of it inside byz_pairwise_distances_dev.
         Without `local_columns` the list is left for the caller (near_pairs_count / _sqdist / _apply)."""
-        ptr = gram.data_ptr() if _is_torch(gram) else gram.ptr
-        if _is_torch(gram):
-            import torch
-            stream = torch.cuda.current_stream(gram.device).cuda_stream
-        dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
-        _check(self.lib.byz_distances_from_gram_dev(self.ctx, _vp(ptr), int(n), _vp(dist.ptr), _vp(stream)))
-        if local_columns is None:
-            self.check(stream)
-            return dist
-        count = self.near_pairs_count(stream)
-        if count:
-            sq = self.near_pairs_sqdist(local_columns, count)
-            if all_reduce is not None:
-                all_reduce(sq)
-            self.near_pairs_apply(sq, dist, stream)
+        with _Call(self, stream) as c:
+            gram = c.as_it_lies(gram)
+            dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
+            c.run(self.lib.byz_distances_from_gram_dev(self.ctx, gram.ptr, int(n), dist.ptr, c.stream))
+            if local_columns is None:
+                self.check(c.stream)
+                return dist
+            count = self.near_pairs_count(c.stream)
+            if count:
+                sq = self.near_pairs_sqdist(local_columns, count)
+                if all_reduce is not None:
+                    all_reduce(sq)
+                self.near_pairs_apply(sq, dist, c.stream)
         return dist
 
     def _as_distances(self, distances):
@@ -435,10 +669,11 @@ class Engine:
 
     def krum_select(self, distances, users_count, corrupted_count):
         """The selection loop of defences.py:27-37 on a distance matrix; returns the index (or -1)."""
-        d, keys = self._as_distances(distances)
-        idx = ctypes.c_int32(-2)
-        _check(self.lib.byz_krum_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count),
-                                            ctypes.byref(idx), None, None))
+        with _Call(self) as c:
+            d, keys = c.distances(distances)
+            idx = ctypes.c_int32(-2)
+            c.run(self.lib.byz_krum_select_dev(self.ctx, d.ptr, d.n, int(users_count), int(corrupted_count),
+                                               ctypes.byref(idx), None, None), reads_back=True)
         idx = int(idx.value)
         return idx if (keys is None or idx < 0) else keys[idx]
 
@@ -458,8 +693,8 @@ class Engine:
             if return_index:
                 return idx
             return self._row(g, idx)
-        m = self._device_matrix(g)
-        if m is None:
+        dm = self._device_matrix(g)
+        if dm is None:
             out, aux = self.defend_host('Krum', g, users_count, corrupted_count, check_assert=False, want_aux=True)
             if return_index:
                 return int(aux[0])
@@ -468,16 +703,17 @@ class Engine:
                 # row when no score beat 1e20 -- and since round 6 so does the host path (missing 6)
                 return g[int(aux[0])]
             return out
-        idx = ctypes.c_int32(-2)
-        out, ptr = (None, None) if return_index else self._out_like(m, m.cols)
-        # the winning row is copied on the device; the index crosses to the host (one sync) only when asked for
-        _check(self.lib.byz_krum_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(users_count),
-                                     int(corrupted_count), 0, _vp(ptr), ctypes.byref(idx) if return_index else None,
-                                     _vp(m.stream)))
-        if return_index:
-            return int(idx.value)      # (the library read the status word together with the index)
-        if check:
-            self.check(m.stream)
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            idx = ctypes.c_int32(-2)
+            out, ptr = c.out(m.cols, want=not return_index)
+            # the winning row is copied on the device; the index crosses to the host (one sync) only when asked for
+            c.run(self.lib.byz_krum_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(users_count), int(corrupted_count), 0, ptr,
+                                        ctypes.byref(idx) if return_index else None, c.stream), reads_back=return_index)
+            if return_index:
+                return int(idx.value)      # (the library read the status word together with the index)
+            if check:
+                self.check(c.stream)
         return out
 
     def _row(self, g, idx):
@@ -486,58 +722,26 @@ class Engine:
             return g.numpy()[idx]
         return g[idx]
 
-    def _row_index(self, row_index, m, validate):
-        """row_index -> (device pointer, count, keepalive).  The kernel reads int32 indices straight from device
-        memory: anything else is converted here, and (unless the caller vouches for it) checked against the
-        matrix height, because an out-of-range index is an out-of-bounds read on the GPU."""
-        if isinstance(row_index, DeviceBuffer):
-            if row_index.dtype != np.int32:
-                raise ValueError('a DeviceBuffer row_index must hold int32')
-            return row_index.ptr, int(np.prod(row_index.shape)), row_index
-        if _is_torch(row_index):
-            import torch
-            if not row_index.is_cuda or (m.torch_like is not None and row_index.device != m.torch_like.device) \
-                    or row_index.device.index != self.device:
-                raise ValueError('row_index must live on the GPU of the matrix (cuda:%d), got %s'
-                                 % (self.device, row_index.device))
-            if row_index.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
-                raise ValueError('row_index must hold integers, got %s' % row_index.dtype)
-            idx = row_index.reshape(-1).to(torch.int32).contiguous()
-            if validate and idx.numel():
-                lo, hi = int(idx.min().item()), int(idx.max().item())
-                if lo < 0 or hi >= m.rows:
-                    raise ValueError('row_index out of range: [%d, %d] for %d rows' % (lo, hi, m.rows))
-            return idx.data_ptr(), idx.numel(), idx
-        host = np.asarray(row_index)
-        if host.dtype.kind not in 'iu':
-            raise ValueError('row_index must hold integers, got %s' % host.dtype)
-        host = host.reshape(-1)
-        if host.size and (host.min() < 0 or host.max() >= m.rows):
-            raise ValueError('row_index out of range: [%d, %d] for %d rows' % (host.min(), host.max(), m.rows))
-        keep = self.to_device(host.astype(np.int32))
-        return keep.ptr, keep.shape[0], keep
-
     def trimmed_mean(self, g, users_count=None, corrupted_count=0, row_index=None, validate_index=True):
-        m = self._device_matrix(g)
-        if m is None:
+        dm = self._device_matrix(g)
+        if dm is None:
             if row_index is not None:
                 g = self._host_matrix(g)[np.asarray(row_index)]
             return self.defend_host('TrimmedMean', g, 0, corrupted_count)
-        n_rows, idx_ptr, keep = m.rows, None, None
-        if row_index is not None:
-            idx_ptr, n_rows, keep = self._row_index(row_index, m, validate_index)
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            idx_ptr, n_rows = self._row_index(c, row_index, m, validate_index)
             if n_rows == 0:
                 raise ValueError('row_index selects no rows')
-        out, ptr = self._out_like(m, m.cols)
-        _check(self.lib.byz_trimmed_mean_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
-                                             int(corrupted_count), _vp(ptr), _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+            out, ptr = c.out(m.cols)
+            c.run(self.lib.byz_trimmed_mean_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, int(corrupted_count), ptr,
+                                                c.stream))
         return out
 
     def _rank_rule(self, g, trim_count, row_index, validate_index):
         """The two coordinate-wise rank rules share their plumbing: trim_count None is the median."""
-        m = self._device_matrix(g)
-        if m is None:
+        dm = self._device_matrix(g)
+        if dm is None:
             g = self._host_matrix(g)
             if row_index is not None:
                 g = np.ascontiguousarray(g[np.asarray(row_index)])
@@ -546,25 +750,21 @@ class Engine:
                 raise ValueError('row_index selects no rows')
             out = np.empty(d, dtype=np.float32)
             if trim_count is None:
-                _check(self.lib.byz_coordinate_median_host(self.ctx, g.ctypes.data_as(ctypes.c_void_p), n, d,
-                                                           out.ctypes.data_as(ctypes.c_void_p)))
+                _check(self.lib.byz_coordinate_median_host(self.ctx, _hp(g), n, d, _hp(out)))
             else:
-                _check(self.lib.byz_rank_trimmed_mean_host(self.ctx, g.ctypes.data_as(ctypes.c_void_p), n, d, int(trim_count),
-                                                           out.ctypes.data_as(ctypes.c_void_p)))
+                _check(self.lib.byz_rank_trimmed_mean_host(self.ctx, _hp(g), n, d, int(trim_count), _hp(out)))
             return out
-        n_rows, idx_ptr, keep = m.rows, None, None
-        if row_index is not None:
-            idx_ptr, n_rows, keep = self._row_index(row_index, m, validate_index)
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            idx_ptr, n_rows = self._row_index(c, row_index, m, validate_index)
             if n_rows == 0:
                 raise ValueError('row_index selects no rows')
-        out, ptr = self._out_like(m, m.cols)
-        if trim_count is None:
-            _check(self.lib.byz_coordinate_median_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr), _vp(ptr),
-                                                      _vp(m.stream)))
-        else:
-            _check(self.lib.byz_rank_trimmed_mean_dev(self.ctx, _vp(m.ptr), int(n_rows), m.cols, m.ld, _vp(idx_ptr),
-                                                      int(trim_count), _vp(ptr), _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+            out, ptr = c.out(m.cols)
+            if trim_count is None:
+                c.run(self.lib.byz_coordinate_median_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, ptr, c.stream))
+            else:
+                c.run(self.lib.byz_rank_trimmed_mean_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, int(trim_count), ptr,
+                                                         c.stream))
         return out
 
     def coordinate_median(self, g, row_index=None, validate_index=True):
@@ -581,19 +781,17 @@ class Engine:
 
     def trimmed_mean_redone(self, stream=None):
         """16-column tiles of the last trimmed mean that the ring selection handed to the general kernel."""
-        tiles = ctypes.c_int64(0)
-        _check(self.lib.byz_trimmed_mean_redone(self.ctx, ctypes.byref(tiles), _vp(stream)))
-        return int(tiles.value)
+        return self._read(self.lib.byz_trimmed_mean_redone, [ctypes.c_int64], stream)[0]
 
     def bulyan_select(self, distances, users_count, corrupted_count, on_device=False):
         """The pick-and-remove loop of defences.py:59-68: theta indices in selection order.  `on_device=True` leaves
         them in a DeviceBuffer (int32) for `trimmed_mean(row_index=...)` -- no host round trip between the stages."""
-        d, keys = self._as_distances(distances)
         theta = int(users_count) - 2 * int(corrupted_count)
-        sel = DeviceBuffer(self, (max(theta, 1),), np.int32)
-        _check(self.lib.byz_bulyan_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count),
-                                              _vp(sel.ptr), None))
-        return self._selection(sel, theta, keys, on_device)
+        with _Call(self) as c:
+            d, keys = c.distances(distances)
+            sel = DeviceBuffer(self, (max(theta, 1),), np.int32)
+            c.run(self.lib.byz_bulyan_select_dev(self.ctx, d.ptr, d.n, int(users_count), int(corrupted_count), sel.ptr, None))
+            return self._selection(sel, theta, keys, on_device)
 
     def _selection(self, sel, count, keys, on_device):
         """The first `count` rows a selection kernel wrote to `sel`, for the caller: under the caller's keys (_as_distances), or
@@ -608,35 +806,36 @@ class Engine:
     def krum_bulyan_select(self, distances, users_count, corrupted_count, on_device=False):
         """(Krum index, Bulyan selection) from ONE distance matrix with one sort of its rows -- what a round that runs both
         defences on the same distances needs (BASELINE configs[4]); the same values `krum_select` and `bulyan_select` return."""
-        d, keys = self._as_distances(distances)
         theta = int(users_count) - 2 * int(corrupted_count)
-        sel = DeviceBuffer(self, (max(theta, 1),), np.int32)
-        idx = ctypes.c_int32(-2)
-        _check(self.lib.byz_krum_bulyan_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count),
-                                                   ctypes.byref(idx), _vp(sel.ptr), None))
-        index = int(idx.value)
-        index = index if (keys is None or index < 0) else keys[index]
-        return index, self._selection(sel, theta, keys, on_device)
+        with _Call(self) as c:
+            d, keys = c.distances(distances)
+            sel = DeviceBuffer(self, (max(theta, 1),), np.int32)
+            idx = ctypes.c_int32(-2)
+            c.run(self.lib.byz_krum_bulyan_select_dev(self.ctx, d.ptr, d.n, int(users_count), int(corrupted_count),
+                                                      ctypes.byref(idx), sel.ptr, None), reads_back=True)
+            index = int(idx.value)
+            index = index if (keys is None or index < 0) else keys[index]
+            return index, self._selection(sel, theta, keys, on_device)
 
     def bulyan_rescored(self):
         """Rows the last Bulyan loop re-scored with the reference's sequential fp32 sums (0: every pick was clear)."""
-        rows = ctypes.c_int64(0)
-        _check(self.lib.byz_bulyan_rescored(self.ctx, ctypes.byref(rows)))
-        return int(rows.value)
+        return self._read(self.lib.byz_bulyan_rescored, [ctypes.c_int64])[0]
 
     def bulyan(self, g, users_count, corrupted_count, return_selection=False):
         assert users_count >= 4 * corrupted_count + 3  # defences.py:56
-        m = self._device_matrix(g)
-        if m is None:
+        dm = self._device_matrix(g)
+        if dm is None:
             if return_selection:
                 out, aux = self.defend_host('Bulyan', g, users_count, corrupted_count, want_aux=True)
                 return out, aux[:int(users_count) - 2 * int(corrupted_count)]
             return self.defend_host('Bulyan', g, users_count, corrupted_count)
         theta = int(users_count) - 2 * int(corrupted_count)
-        out, ptr = self._out_like(m, m.cols)
-        sel, sel_ptr = self._out_like(m, max(theta, 1), np.int32) if return_selection else (None, None)
-        _check(self.lib.byz_bulyan_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(users_count),
-                                       int(corrupted_count), _vp(ptr), _vp(sel_ptr), _vp(m.stream)))
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            out, ptr = c.out(m.cols)
+            sel, sel_ptr = c.out(max(theta, 1), np.int32, want=return_selection)
+            c.run(self.lib.byz_bulyan_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(users_count), int(corrupted_count), ptr,
+                                          sel_ptr, c.stream))
         return (out, sel) if return_selection else out
 
     # ---- Multi-Krum (Blanchard et al. 2017, section 4; not in the reference) -------------------
@@ -649,26 +848,24 @@ class Engine:
         """The m best Krum-scored rows of a distance matrix (a `Distances` handle, the reference's dict, or a dense matrix),
         in ranking order: ascending score (defences.py:33-34's, as `krum` forms it), a tie broken by the visit order 1, 0, 2,
         ..., every NaN last.  `on_device=True` leaves them in a DeviceBuffer (int32)."""
-        d, keys = self._as_distances(distances)
         m = self._multi_krum_m(users_count, corrupted_count, m)
-        sel = DeviceBuffer(self, (max(m, 1),), np.int32)
-        _check(self.lib.byz_multi_krum_select_dev(self.ctx, _vp(d.ptr), d.n, int(users_count), int(corrupted_count), m,
-                                                  _vp(sel.ptr), None))
-        return self._selection(sel, m, keys, on_device)
+        with _Call(self) as c:
+            d, keys = c.distances(distances)
+            sel = DeviceBuffer(self, (max(m, 1),), np.int32)
+            c.run(self.lib.byz_multi_krum_select_dev(self.ctx, d.ptr, d.n, int(users_count), int(corrupted_count), m, sel.ptr,
+                                                     None))
+            return self._selection(sel, m, keys, on_device)
 
     def mean_rows(self, g, row_index, validate_index=True):
         """Column mean of the rows `row_index` names, in that order, with no_defense's arithmetic (sequential fp32 from
         +0.0, then / count).  `g` is device-resident; indices are checked against its height unless the caller vouches."""
-        m = self._device_matrix(g)
-        if m is None:
-            raise ValueError('mean_rows() takes a device-resident matrix')
-        idx_ptr, count, keep = self._row_index(row_index, m, validate_index)
-        if count == 0:
-            raise ValueError('row_index selects no rows')
-        out, ptr = self._out_like(m, m.cols)
-        _check(self.lib.byz_mean_rows_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(idx_ptr), int(count), _vp(ptr),
-                                          _vp(m.stream)))
-        self._sync_if_ours(keep, m.stream)
+        with _Call(self) as c:
+            m = c.matrix(g, needs='mean_rows')
+            idx_ptr, count = self._row_index(c, row_index, m, validate_index)
+            if count == 0:
+                raise ValueError('row_index selects no rows')
+            out, ptr = c.out(m.cols)
+            c.run(self.lib.byz_mean_rows_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, idx_ptr, count, ptr, c.stream))
         return out
 
     def multi_krum(self, g, users_count, corrupted_count, m=None, distances=None, return_selection=False):
@@ -683,94 +880,60 @@ class Engine:
             selection = self.multi_krum_select(distances, users_count, corrupted_count, mm)
             rows = np.sort(selection)
             if dm is None:
-                stage = self.to_device(self._host_matrix(g))
-                out = self.mean_rows(stage, rows).numpy()
+                out = self.mean_rows(self.to_device(self._host_matrix(g)), rows).numpy()
             else:
                 out = self.mean_rows(g, rows)
                 if dm.torch_like is not None:
-                    import torch
-                    selection = torch.from_numpy(selection).to(dm.torch_like.device)
+                    selection = _torch().from_numpy(selection).to(dm.torch_like.device)
             return (out, selection) if return_selection else out
         if dm is None:
             h = self._host_matrix(g)
             n, d = h.shape
             out = np.empty(d, dtype=np.float32)
             sel = np.full(max(mm, 1), -1, dtype=np.int32)
-            _check(self.lib.byz_multi_krum_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, int(users_count),
-                                                int(corrupted_count), mm, out.ctypes.data_as(ctypes.c_void_p),
-                                                sel.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_multi_krum_host(self.ctx, _hp(h), n, d, int(users_count), int(corrupted_count), mm, _hp(out),
+                                                _hp(sel)))
             return (out, sel[:mm]) if return_selection else out
-        out, ptr = self._out_like(dm, dm.cols)
-        sel, sel_ptr = self._out_like(dm, max(mm, 1), np.int32) if return_selection else (None, None)
-        _check(self.lib.byz_multi_krum_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, int(users_count),
-                                           int(corrupted_count), mm, 0, _vp(ptr), _vp(sel_ptr), _vp(dm.stream)))
-        self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            out, ptr = c.out(dm.cols)
+            sel, sel_ptr = c.out(max(mm, 1), np.int32, want=return_selection)
+            c.run(self.lib.byz_multi_krum_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, int(users_count), int(corrupted_count),
+                                              mm, 0, ptr, sel_ptr, c.stream))
+            self.check(c.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
         return (out, sel) if return_selection else out
 
     # ---- geometric median (smoothed Weiszfeld; RFA, Pillutla et al.; not in the reference) ----
-    def _f64_vector(self, v, n):
-        """A length-n fp64 vector for a kernel: (device pointer, keepalive).  torch CUDA tensors are used in place (made
-        contiguous fp64 on the matrix's device); anything else is uploaded."""
-        if _is_torch(v) and v.is_cuda:
-            import torch
-            t = v.reshape(-1).to(dtype=torch.float64).contiguous()
-            if t.device.index != self.device:
-                raise ValueError('the vector lives on %s, this engine drives cuda:%d' % (t.device, self.device))
-            if t.numel() != n:
-                raise ValueError('expected %d values, got %d' % (n, t.numel()))
-            return t.data_ptr(), t
-        if isinstance(v, DeviceBuffer):
-            if v.dtype != np.float64 or int(np.prod(v.shape)) != n:
-                raise ValueError('a DeviceBuffer here must hold %d float64 values' % n)
-            return v.ptr, v
-        host = np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1))
-        if host.size != n:
-            raise ValueError('expected %d values, got %d' % (n, host.size))
-        buf = self.to_device(host)
-        return buf.ptr, buf
-
-    def _staged(self, g):
-        """(_Matrix, keepalive, host?) for a device-resident matrix or a host one staged to the device."""
-        m = self._device_matrix(g)
-        if m is not None:
-            return m, None, False
-        stage = self.to_device(self._host_matrix(g))
-        return self._device_matrix(stage), stage, True
-
     def row_sqdist(self, g, z):
         """sq[i] = sum_c ((double)g[i, c] - (double)z[c])^2 in fp64 (fixed order; on the difference, not through the
         Gram identity).  fp64 out: a torch tensor for a torch input, numpy for a host input, a DeviceBuffer otherwise."""
-        m, stage, host = self._staged(g)
-        (zp,), n, _, keep, _ = self._vectors(z)
-        if n != m.cols:
-            raise ValueError('z has %d entries, the matrix %d columns' % (n, m.cols))
-        out, optr = self._out_like(m, m.rows, np.float64)
-        _check(self.lib.byz_row_sqdist_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(zp), _vp(optr), _vp(m.stream)))
-        if host or any(isinstance(k, DeviceBuffer) for k in keep):
-            self.synchronize(m.stream)   # staged copies must outlive the kernel
-        return out.numpy() if host else out
+        with _Call(self) as c:
+            m = c.matrix(g)
+            z = c.operand(z, np.float32, _f32('z has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False)
+            out, optr = c.out(m.rows, np.float64)
+            c.run(self.lib.byz_row_sqdist_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, z.ptr, optr, c.stream))
+            return c.result(out)
 
     def weighted_mean(self, g, weights, validate=True):
         """out[c] = fl32(S_c / W): S_c the sequential fp64 sum, in row order, of w_i * g[i, c] over the rows with w_i != 0,
         W = sum w_i.  The weights must be finite and >= 0; all zero gives NaN.  validate=True checks them here: for
         device-resident weights that is one reduction and a host synchronisation.  validate=False is for a caller that
         vouches for them (the kernel would carry a NaN or a negative weight into the mean)."""
-        m, stage, host = self._staged(g)
-        wp, wkeep = self._f64_vector(weights, m.rows)
-        if validate:
-            if _is_torch(wkeep):
-                import torch
-                bad = bool((~torch.isfinite(wkeep) | (wkeep < 0)).any().item())
-            else:
-                w_host = np.asarray(weights.numpy() if isinstance(weights, DeviceBuffer) else weights, dtype=np.float64)
-                bad = bool((~np.isfinite(w_host) | (w_host < 0)).any())
-            if bad:
-                raise ValueError('weights must be finite and >= 0')
-        out, optr = self._out_like(m, m.cols)
-        _check(self.lib.byz_weighted_mean_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(wp), _vp(optr), _vp(m.stream)))
-        if host or isinstance(wkeep, DeviceBuffer):
-            self.synchronize(m.stream)
-        return out.numpy() if host else out
+        with _Call(self) as c:
+            m = c.matrix(g)
+            w = c.operand(weights, np.float64, _F64, m.rows)
+            if validate:
+                if w.torch_like is not None:
+                    torch = _torch()
+                    bad = bool((~torch.isfinite(w.torch_like) | (w.torch_like < 0)).any().item())
+                else:
+                    w_host = np.asarray(weights.numpy() if isinstance(weights, DeviceBuffer) else _to_host(weights), dtype=np.float64)
+                    bad = bool((~np.isfinite(w_host) | (w_host < 0)).any())
+                if bad:
+                    raise ValueError('weights must be finite and >= 0')
+            out, optr = c.out(m.cols)
+            c.run(self.lib.byz_weighted_mean_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, w.ptr, optr, c.stream))
+            return c.result(out)
 
     @staticmethod
     def _geomed_params(nu, max_iter, ftol):
@@ -778,9 +941,7 @@ class Engine:
 
     def geometric_median_info(self):
         """(iterations, excluded_rows, objective) of the last geometric median on this engine (synchronises)."""
-        it, ex, obj = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-        _check(self.lib.byz_geometric_median_info(self.ctx, ctypes.byref(it), ctypes.byref(ex), ctypes.byref(obj)))
-        return int(it.value), int(ex.value), float(obj.value)
+        return tuple(self._read(self.lib.byz_geometric_median_info, [ctypes.c_int64, ctypes.c_int64, ctypes.c_double]))
 
     def geometric_median(self, g, nu=1e-6, max_iter=10, ftol=1e-6, return_info=False):
         """The geometric median of the rows by smoothed Weiszfeld iterations (RFA), started at no_defense's mean; rows with
@@ -794,14 +955,14 @@ class Engine:
             n, d = h.shape
             out = np.empty(d, dtype=np.float32)
             weights = np.empty(n, dtype=np.float64) if return_info else None
-            _check(self.lib.byz_geometric_median_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                                      out.ctypes.data_as(ctypes.c_void_p),
-                                                      weights.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+            _check(self.lib.byz_geometric_median_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(out), _hp(weights)))
         else:
-            out, ptr = self._out_like(dm, dm.cols)
-            weights, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
-            _check(self.lib.byz_geometric_median_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
-                                                     _vp(ptr), _vp(wptr), _vp(dm.stream)))
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                out, ptr = c.out(dm.cols)
+                weights, wptr = c.out(dm.rows, np.float64, want=return_info)
+                c.run(self.lib.byz_geometric_median_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), ptr,
+                                                        wptr, c.stream))
         if not return_info:
             return out
         iterations, excluded, objective = self.geometric_median_info()
@@ -812,23 +973,17 @@ class Engine:
         """out[c] = fl32(v[c] + S_c / n): S_c the sequential fp64 sum, in row order, of scales[i] * (g[i, c] - v[c]) over the
         rows with scales[i] != 0 (a row of scale 0 is not read).  One iteration of centered clipping is row_sqdist, the
         scales min(1, tau / d), then this.  The caller vouches that the scales are finite."""
-        m, stage, host = self._staged(g)
-        (vp,), n, _, keep, _ = self._vectors(v)
-        if n != m.cols:
-            raise ValueError('v has %d entries, the matrix %d columns' % (n, m.cols))
-        sp, skeep = self._f64_vector(scales, m.rows)
-        out, optr = self._out_like(m, m.cols)
-        _check(self.lib.byz_clip_update_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(vp), _vp(sp), _vp(optr),
-                                            _vp(m.stream)))
-        if host or isinstance(skeep, DeviceBuffer) or any(isinstance(k, DeviceBuffer) for k in keep):
-            self.synchronize(m.stream)   # staged copies must outlive the kernel
-        return out.numpy() if host else out
+        with _Call(self) as c:
+            m = c.matrix(g)
+            v = c.operand(v, np.float32, _f32('v has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False)
+            s = c.operand(scales, np.float64, _F64, m.rows)
+            out, optr = c.out(m.cols)
+            c.run(self.lib.byz_clip_update_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, v.ptr, s.ptr, optr, c.stream))
+            return c.result(out)
 
     def centered_clip_info(self):
         """(clipped_rows, excluded_rows) of the last iteration of the last centered clipping on this engine (synchronises)."""
-        clipped, excluded = ctypes.c_int64(0), ctypes.c_int64(0)
-        _check(self.lib.byz_centered_clip_info(self.ctx, ctypes.byref(clipped), ctypes.byref(excluded)))
-        return int(clipped.value), int(excluded.value)
+        return tuple(self._read(self.lib.byz_centered_clip_info, [ctypes.c_int64, ctypes.c_int64]))
 
     def centered_clip(self, g, tau=10.0, iters=3, start=None, return_info=False):
         """Centered clipping: from v = start (None: the zero vector; the previous round's aggregate is the paper's choice),
@@ -845,25 +1000,19 @@ class Engine:
             scales = np.empty(n, dtype=np.float64) if return_info else None
             s_host = None
             if start is not None:
-                s_host = np.ascontiguousarray(start.detach().cpu().numpy() if _is_torch(start) else start, dtype=np.float32).ravel()
+                s_host = np.ascontiguousarray(_to_host(start), dtype=np.float32).ravel()
                 if s_host.size != d:
                     raise ValueError('start has %d entries, the matrix %d columns' % (s_host.size, d))
-            _check(self.lib.byz_centered_clip_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                                   s_host.ctypes.data_as(ctypes.c_void_p) if s_host is not None else None,
-                                                   out.ctypes.data_as(ctypes.c_void_p),
-                                                   scales.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+            _check(self.lib.byz_centered_clip_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(s_host), _hp(out),
+                                                   _hp(scales)))
         else:
-            sptr, keep = None, []
-            if start is not None:
-                (sptr,), n, _, keep, _ = self._vectors(start)
-                if n != dm.cols:
-                    raise ValueError('start has %d entries, the matrix %d columns' % (n, dm.cols))
-            out, ptr = self._out_like(dm, dm.cols)
-            scales, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
-            _check(self.lib.byz_centered_clip_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
-                                                  _vp(sptr), _vp(ptr), _vp(wptr), _vp(dm.stream)))
-            if any(isinstance(k, DeviceBuffer) for k in keep):
-                self.synchronize(dm.stream)   # an uploaded start must outlive the kernels
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                sptr = None if start is None else c.operand(start, np.float32, _f32('start has %(got)d entries, the matrix %(n)d columns'), dm.cols, convert=False).ptr
+                out, ptr = c.out(dm.cols)
+                scales, wptr = c.out(dm.rows, np.float64, want=return_info)
+                c.run(self.lib.byz_centered_clip_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), sptr, ptr,
+                                                     wptr, c.stream))
         if not return_info:
             return out
         clipped, excluded = self.centered_clip_info()
@@ -874,38 +1023,31 @@ class Engine:
         """(dot, sq): dot[i] = sum_c (double)g[i, c] * (double)r[c] and sq[i] = sum_c (double)g[i, c]^2, both fp64 in a fixed
         order, in ONE read of g (FLTrust's first pass; on one rank of the columns layout, its part over its columns).  fp64
         out: torch tensors for a torch input, numpy for a host input, DeviceBuffers otherwise."""
-        m, stage, host = self._staged(g)
-        (rp,), n, _, keep, _ = self._vectors(r)
-        if n != m.cols:
-            raise ValueError('r has %d entries, the matrix %d columns' % (n, m.cols))
-        dot, dptr = self._out_like(m, m.rows, np.float64)
-        sq, sptr = self._out_like(m, m.rows, np.float64)
-        _check(self.lib.byz_row_dots_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(rp), _vp(dptr), _vp(sptr),
-                                         _vp(m.stream)))
-        if host or any(isinstance(k, DeviceBuffer) for k in keep):
-            self.synchronize(m.stream)   # staged copies must outlive the kernel
-        return (dot.numpy(), sq.numpy()) if host else (dot, sq)
+        with _Call(self) as c:
+            m = c.matrix(g)
+            r = c.operand(r, np.float32, _f32('r has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False)
+            dot, dptr = c.out(m.rows, np.float64)
+            sq, sptr = c.out(m.rows, np.float64)
+            c.run(self.lib.byz_row_dots_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, r.ptr, dptr, sptr, c.stream))
+            return c.result((dot, sq))
 
     def scaled_rows_sum(self, g, weights, divisor):
         """out[c] = fl32(S_c / T) where T = divisor > 0, zeros otherwise: S_c the sequential fp64 sum, in row order, of
         weights[i] * g[i, c] over the rows with weights[i] != 0 (a row of weight 0 is not read).  FLTrust's second pass; the
         divisor is one fp64 value, on the host or the device.  The caller vouches that the weights are finite."""
-        m, stage, host = self._staged(g)
-        wp, wkeep = self._f64_vector(weights, m.rows)
-        tp, tkeep = self._f64_vector(divisor, 1)
-        out, optr = self._out_like(m, m.cols)
-        _check(self.lib.byz_scaled_rows_sum_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(wp), _vp(tp), _vp(optr),
-                                                _vp(m.stream)))
-        if host or isinstance(wkeep, DeviceBuffer) or isinstance(tkeep, DeviceBuffer):
-            self.synchronize(m.stream)   # staged copies must outlive the kernel
-        return out.numpy() if host else out
+        with _Call(self) as c:
+            m = c.matrix(g)
+            w = c.operand(weights, np.float64, _F64, m.rows)
+            t = c.operand(divisor, np.float64, _F64, 1)
+            out, optr = c.out(m.cols)
+            c.run(self.lib.byz_scaled_rows_sum_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, w.ptr, t.ptr, optr, c.stream))
+            return c.result(out)
 
     def fltrust_info(self):
         """(trusted_rows, excluded_rows, root_ok, trust_sum) of the last FLTrust call on this engine (synchronises)."""
-        trusted, excluded, ok, total = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0.0)
-        _check(self.lib.byz_fltrust_info(self.ctx, ctypes.byref(trusted), ctypes.byref(excluded), ctypes.byref(ok),
-                                         ctypes.byref(total)))
-        return int(trusted.value), int(excluded.value), bool(ok.value), float(total.value)
+        trusted, excluded, ok, total = self._read(self.lib.byz_fltrust_info,
+                                                  [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double])
+        return trusted, excluded, bool(ok), total
 
     def fltrust(self, g, root, return_info=False):
         """FLTrust: every row's trust score is the ReLU of its cosine with `root`, the gradient the server computed on its own
@@ -917,28 +1059,21 @@ class Engine:
         if dm is None:
             h = self._host_matrix(g)
             n, d = h.shape
-            r_host = np.ascontiguousarray(root.detach().cpu().numpy() if _is_torch(root) else
-                                          (root.numpy() if isinstance(root, DeviceBuffer) else root), dtype=np.float32).ravel()
+            r_host = np.ascontiguousarray(root.numpy() if isinstance(root, DeviceBuffer) else _to_host(root), dtype=np.float32).ravel()
             if r_host.size != d:
                 raise ValueError('root has %d entries, the matrix %d columns' % (r_host.size, d))
             out = np.empty(d, dtype=np.float32)
             trust = np.empty(n, dtype=np.float64) if return_info else None
             weights = np.empty(n, dtype=np.float64) if return_info else None
-            _check(self.lib.byz_fltrust_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d,
-                                             r_host.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
-                                             trust.ctypes.data_as(ctypes.c_void_p) if return_info else None,
-                                             weights.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+            _check(self.lib.byz_fltrust_host(self.ctx, _hp(h), n, d, _hp(r_host), _hp(out), _hp(trust), _hp(weights)))
         else:
-            (rptr,), n, _, keep, _ = self._vectors(root)
-            if n != dm.cols:
-                raise ValueError('root has %d entries, the matrix %d columns' % (n, dm.cols))
-            out, ptr = self._out_like(dm, dm.cols)
-            trust, tptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
-            weights, wptr = self._out_like(dm, dm.rows, np.float64) if return_info else (None, None)
-            _check(self.lib.byz_fltrust_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, _vp(rptr), _vp(ptr), _vp(tptr),
-                                            _vp(wptr), _vp(dm.stream)))
-            if any(isinstance(k, DeviceBuffer) for k in keep):
-                self.synchronize(dm.stream)   # an uploaded root must outlive the kernels
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                root = c.operand(root, np.float32, _f32('root has %(got)d entries, the matrix %(n)d columns'), dm.cols, convert=False)
+                out, ptr = c.out(dm.cols)
+                trust, tptr = c.out(dm.rows, np.float64, want=return_info)
+                weights, wptr = c.out(dm.rows, np.float64, want=return_info)
+                c.run(self.lib.byz_fltrust_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, root.ptr, ptr, tptr, wptr, c.stream))
         if not return_info:
             return out
         trusted, excluded, ok, total = self.fltrust_info()
@@ -952,17 +1087,15 @@ class Engine:
         bit), in ONE read of g.  A value is counted on its bits: +0.0 and -0.0 are zeros, denormals and infinities count by
         their sign, a NaN counts nowhere.  window_len = 0 is allowed.  torch tensors for a torch input, numpy for a host input;
         for a DeviceBuffer the counts come back as numpy and q as a DeviceBuffer."""
-        m, stage, host = self._staged(g)
-        counts, cptr = self._out_like(m, (3, m.rows), np.int64)
-        q, qptr = self._out_like(m, m.rows, np.float64)
-        _check(self.lib.byz_row_signs_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(window_start), int(window_len),
-                                          _vp(cptr), _vp(qptr), _vp(m.stream)))
-        if host:
-            self.synchronize(m.stream)   # the staged copy must outlive the kernel
-            counts, q = counts.numpy(), q.numpy()
-        elif m.torch_like is None:
-            counts = counts.numpy()      # (a DeviceBuffer has no row views: the three count vectors come back on the host)
-        return counts[0], counts[1], counts[2], q
+        with _Call(self) as c:
+            m = c.matrix(g)
+            counts, cptr = c.out((3, m.rows), np.int64)
+            q, qptr = c.out(m.rows, np.float64)
+            c.run(self.lib.byz_row_signs_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(window_start), int(window_len), cptr,
+                                             qptr, c.stream))
+            if isinstance(counts, DeviceBuffer):
+                counts = c.numpy(counts)     # (a DeviceBuffer has no row views: the three count vectors come back on the host)
+            return counts[0], counts[1], counts[2], c.result(q)
 
     @staticmethod
     def _signguard_params(window_start, window_len, lower, upper, bandwidth, n_sample):
@@ -979,7 +1112,7 @@ class Engine:
             return None
         if sample is None:
             sample = signguard_sample(n_rows, min(int(n_samples), _native.SIGNGUARD_MAX_SAMPLES), seed)
-        sample = np.ascontiguousarray(np.asarray(sample.cpu().numpy() if _is_torch(sample) else sample).reshape(-1))
+        sample = np.ascontiguousarray(_to_host(sample).reshape(-1))
         if sample.dtype.kind not in 'iu' or sample.size < 1 or sample.size > min(n_rows, _native.SIGNGUARD_MAX_SAMPLES) or \
                 sample.min() < 0 or sample.max() >= n_rows or np.unique(sample).size != sample.size:
             raise ValueError('signguard: the sample must be 1..min(n, %d) distinct row numbers in [0, %d)'
@@ -989,13 +1122,8 @@ class Engine:
     def signguard_info(self):
         """The last SignGuard selection on this engine (synchronises): {kept_rows, norm_failed_rows, outside_rows, clusters,
         seeds, bandwidth, median_norm}."""
-        vals = [ctypes.c_int64(0) for _ in range(5)]
-        h, med = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self.lib.byz_signguard_info(self.ctx, *[ctypes.byref(v) for v in vals], ctypes.byref(h), ctypes.byref(med)))
-        names = ('kept_rows', 'norm_failed_rows', 'outside_rows', 'clusters', 'seeds')
-        info = {k: int(v.value) for k, v in zip(names, vals)}
-        info.update(bandwidth=float(h.value), median_norm=float(med.value))
-        return info
+        names = ('kept_rows', 'norm_failed_rows', 'outside_rows', 'clusters', 'seeds', 'bandwidth', 'median_norm')
+        return dict(zip(names, self._read(self.lib.byz_signguard_info, [ctypes.c_int64] * 5 + [ctypes.c_double] * 2)))
 
     def signguard_select(self, pos, zero, neg, q, window_len, lower=0.1, upper=3.0, bandwidth=None, sample=None, n_samples=50,
                          seed=0):
@@ -1003,35 +1131,27 @@ class Engine:
         {keep (int32 0 / 1), weights (fp64: min(1, M / norm) for a kept row, 0 otherwise), labels (int32, -1: no cluster),
         median_norm, kept} as device-resident fp64 / int32 vectors and two device doubles `mk` = (M, K); include/byzagg.h has
         the contract.  window_len is the m the shares are divided by.  Nothing synchronises; signguard_info() does."""
-        def host_of(v):
-            return v.detach().cpu().numpy() if _is_torch(v) else (v.numpy() if isinstance(v, DeviceBuffer) else np.asarray(v))
         n = int(q.numel()) if _is_torch(q) else int(np.prod(q.shape)) if isinstance(q, DeviceBuffer) else int(np.asarray(q).size)
         if _is_torch(q) and q.is_cuda:
-            import torch
-            counts = torch.stack([torch.as_tensor(v, device=q.device).reshape(-1).to(torch.int64) for v in (pos, zero, neg)]).contiguous()
-            if counts.shape != (3, n):
-                raise ValueError('expected three count vectors of %d entries' % n)
-            cptr, ckeep = counts.data_ptr(), counts
-            stream, like = torch.cuda.current_stream(q.device).cuda_stream, q
+            torch = _torch()
+            counts = torch.stack([torch.as_tensor(v, device=q.device).reshape(-1).to(torch.int64) for v in (pos, zero, neg)])
         else:
-            counts = np.stack([host_of(v).reshape(-1).astype(np.int64) for v in (pos, zero, neg)])
-            if counts.shape != (3, n):
-                raise ValueError('expected three count vectors of %d entries' % n)
-            ckeep = self.to_device(counts)
-            cptr, stream, like = ckeep.ptr, None, None
-        qptr, qkeep = self._f64_vector(q, n)
-        sample = self._signguard_sample(sample, n, n_samples, seed, bandwidth)
-        params = self._signguard_params(0, window_len, lower, upper, bandwidth, 0 if sample is None else sample.size)
-        skeep = self.to_device(sample) if sample is not None else None
-        keep, kptr = self._out_like(like, n, np.int32)
-        weights, wptr = self._out_like(like, n, np.float64)
-        labels, lptr = self._out_like(like, n, np.int32)
-        mk, mptr = self._out_like(like, 2, np.float64)
-        _check(self.lib.byz_signguard_select_dev(self.ctx, _vp(cptr), _vp(qptr), n, ctypes.byref(params),
-                                                 _vp(skeep.ptr if skeep is not None else None), _vp(kptr), _vp(wptr), _vp(lptr),
-                                                 _vp(mptr), _vp(stream)))
-        if skeep is not None or isinstance(ckeep, DeviceBuffer) or isinstance(qkeep, DeviceBuffer):
-            self.synchronize(stream)     # uploaded inputs must outlive the kernels
+            counts = np.stack([(v.numpy() if isinstance(v, DeviceBuffer) else _to_host(v)).reshape(-1).astype(np.int64)
+                               for v in (pos, zero, neg)])
+        if tuple(counts.shape) != (3, n):
+            raise ValueError('expected three count vectors of %d entries' % n)
+        with _Call(self) as c:
+            counts = c.operand(counts, np.int64, {}, (3, n))
+            q = c.operand(q, np.float64, _F64, n, leads=True)
+            sample = self._signguard_sample(sample, n, n_samples, seed, bandwidth)
+            params = self._signguard_params(0, window_len, lower, upper, bandwidth, 0 if sample is None else sample.size)
+            sptr = None if sample is None else c.upload(sample).ptr
+            keep, kptr = c.out(n, np.int32)
+            weights, wptr = c.out(n, np.float64)
+            labels, lptr = c.out(n, np.int32)
+            mk, mptr = c.out(2, np.float64)
+            c.run(self.lib.byz_signguard_select_dev(self.ctx, counts.ptr, q.ptr, n, ctypes.byref(params), sptr, kptr, wptr, lptr,
+                                                    mptr, c.stream))
         return {'keep': keep, 'weights': weights, 'labels': labels, 'mk': mk}
 
     def signguard(self, g, frac=0.1, lower=0.1, upper=3.0, bandwidth=None, n_samples=50, seed=0, window=None, sample=None,
@@ -1043,7 +1163,7 @@ class Engine:
         signguard_window(D, frac, seed); the sampled rows are `sample` or signguard_sample(n, n_samples, seed).
         return_info=True also returns signguard_info()'s dict with keep, weights and labels (one per row) and the window."""
         dm = self._device_matrix(g)
-        n, d = (dm.rows, dm.cols) if dm is not None else self._host_matrix(g).shape
+        n, d = dm.shape if dm is not None else self._host_matrix(g).shape
         c0, m = window if window is not None else signguard_window(d, frac, seed)
         if int(c0) < 0 or int(m) < 1 or int(c0) + int(m) > d:
             raise ValueError('signguard: the window (%r, %r) is outside the %d columns' % (c0, m, d))
@@ -1055,23 +1175,18 @@ class Engine:
             keep = np.empty(n, dtype=np.int32) if return_info else None
             weights = np.empty(n, dtype=np.float64) if return_info else None
             labels = np.empty(n, dtype=np.int32) if return_info else None
-            _check(self.lib.byz_signguard_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                               sample.ctypes.data_as(ctypes.c_void_p) if sample is not None else None,
-                                               out.ctypes.data_as(ctypes.c_void_p),
-                                               keep.ctypes.data_as(ctypes.c_void_p) if return_info else None,
-                                               weights.ctypes.data_as(ctypes.c_void_p) if return_info else None,
-                                               labels.ctypes.data_as(ctypes.c_void_p) if return_info else None))
+            _check(self.lib.byz_signguard_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(sample), _hp(out), _hp(keep),
+                                               _hp(weights), _hp(labels)))
         else:
-            skeep = self.to_device(sample) if sample is not None else None
-            out, ptr = self._out_like(dm, dm.cols)
-            keep, kptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
-            weights, wptr = self._out_like(dm, n, np.float64) if return_info else (None, None)
-            labels, lptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
-            _check(self.lib.byz_signguard_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
-                                              _vp(skeep.ptr if skeep is not None else None), _vp(ptr), _vp(kptr), _vp(wptr),
-                                              _vp(lptr), _vp(dm.stream)))
-            if skeep is not None:
-                self.synchronize(dm.stream)   # the uploaded sample must outlive the kernels
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                sptr = None if sample is None else c.upload(sample).ptr
+                out, ptr = c.out(d)
+                keep, kptr = c.out(n, np.int32, want=return_info)
+                weights, wptr = c.out(n, np.float64, want=return_info)
+                labels, lptr = c.out(n, np.int32, want=return_info)
+                c.run(self.lib.byz_signguard_dev(self.ctx, dm.ptr, n, d, dm.ld, ctypes.byref(params), sptr, ptr, kptr, wptr,
+                                                 lptr, c.stream))
         if not return_info:
             return out
         info = self.signguard_info()
@@ -1079,29 +1194,6 @@ class Engine:
         return out, info
 
     # ---- nearest-neighbour mixing (Allouah et al., AISTATS 2023; not in the reference) ----
-    def _nnm_lists(self, lists, rows, cols=None):
-        """Neighbour lists or their lengths -> (device pointer of int32 data, shape, keepalive, ours): a DeviceBuffer or a
-        torch CUDA tensor is used where it is (torch: converted to contiguous int32), anything else is uploaded (ours)."""
-        if isinstance(lists, DeviceBuffer):
-            if lists.dtype != np.int32:
-                raise ValueError('a DeviceBuffer of neighbour lists must hold int32')
-            ptr, shape, keep, ours = lists.ptr, lists.shape, lists, False
-        elif _is_torch(lists) and lists.is_cuda:
-            import torch
-            if lists.device.index != self.device:
-                raise ValueError('the neighbour lists live on %s, this engine drives cuda:%d' % (lists.device, self.device))
-            keep = lists.to(torch.int32).contiguous()
-            ptr, shape, ours = keep.data_ptr(), tuple(keep.shape), False
-        else:
-            host = np.asarray(lists.cpu().numpy() if _is_torch(lists) else lists)
-            if host.dtype.kind not in 'iu':
-                raise ValueError('neighbour lists must hold integers, got %s' % host.dtype)
-            keep = self.to_device(host.astype(np.int32))
-            ptr, shape, ours = keep.ptr, keep.shape, True
-        if len(shape) != (1 if cols is None else 2) or shape[0] != rows:
-            raise ValueError('expected %d %s, got shape %r' % (rows, 'lengths' if cols is None else 'lists', tuple(shape)))
-        return ptr, shape, keep, ours
-
     def nnm_neighbours(self, distances, k):
         """(neighbours, counts) for a distance matrix (a `Distances` handle or a dense matrix, diagonal +inf): row i of
         `neighbours` (n x k int32) is i and its k - 1 nearest rows at a finite distance, ASCENDING, then -1; counts[i] their
@@ -1110,14 +1202,13 @@ class Engine:
         on_device = isinstance(distances, Distances)
         if isinstance(distances, dict):
             raise ValueError('nnm_neighbours() takes a Distances handle or a dense matrix')
-        d, _ = self._as_distances(distances)
         k = int(k)
-        nbr = DeviceBuffer(self, (d.n, max(k, 1)), np.int32)
-        counts = DeviceBuffer(self, (d.n,), np.int32)
-        _check(self.lib.byz_nnm_neighbours_dev(self.ctx, _vp(d.ptr), d.n, k, _vp(nbr.ptr), _vp(counts.ptr), None))
-        if on_device:
-            return nbr, counts
-        return nbr.numpy(), counts.numpy()      # (a download synchronises: the temporaries outlive the kernels)
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            nbr = DeviceBuffer(self, (d.n, max(k, 1)), np.int32)
+            counts = DeviceBuffer(self, (d.n,), np.int32)
+            c.run(self.lib.byz_nnm_neighbours_dev(self.ctx, d.ptr, d.n, k, nbr.ptr, counts.ptr, None))
+            return (nbr, counts) if on_device else (nbr.numpy(), counts.numpy())
 
     def nnm_mix(self, g, neighbours, counts=None, out=None):
         """Y[i] = np.mean(g[list_i], axis=0) bit for bit (the listed rows added in ascending row order, sequential fp32 from
@@ -1125,31 +1216,25 @@ class Engine:
         list ascending with -1 behind it (nnm_neighbours' form; `counts` optional).  `g` may be a column panel of a larger
         matrix (a strided view), `out` (optional, device-resident, n x columns, may be strided too) receives the result: that
         is how a matrix too large to hold twice is mixed.  The result stays on the device when `g` was there."""
-        m, stage, host = self._staged(g)
-        nptr, nshape, nkeep, nours = self._nnm_lists(neighbours, m.rows, cols=True)
-        cptr, ckeep, cours = None, None, False
-        if counts is not None:
-            cptr, _, ckeep, cours = self._nnm_lists(counts, m.rows)
-        if out is None:
-            y, yptr = self._out_like(m, (m.rows, m.cols))
-            ldy = m.cols
-        else:
-            om = self._device_matrix(out)
-            if om is None or (om.rows, om.cols) != (m.rows, m.cols):
-                raise ValueError('out must be a device-resident %d x %d float32 matrix' % (m.rows, m.cols))
-            y, yptr, ldy = out, om.ptr, om.ld
-        _check(self.lib.byz_nnm_mix_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(nptr), _vp(cptr), int(nshape[1]),
-                                        _vp(yptr), ldy, _vp(m.stream)))
-        if host or nours or cours:
-            self.synchronize(m.stream)   # staged copies must outlive the kernels
-        return y.numpy() if host and out is None else y
+        with _Call(self) as c:
+            m = c.matrix(g)
+            nbr = c.operand(neighbours, np.int32, _lists('lists'), (m.rows, None))
+            cptr = None if counts is None else c.operand(counts, np.int32, _lists('lengths'), (m.rows,)).ptr
+            if out is None:
+                y, yptr = c.out((m.rows, m.cols))
+                ldy = m.cols
+            else:
+                om = self._device_matrix(out)
+                if om is None or om.shape != m.shape:
+                    raise ValueError('out must be a device-resident %d x %d float32 matrix' % (m.rows, m.cols))
+                y, yptr, ldy = out, om.ptr, om.ld
+            c.run(self.lib.byz_nnm_mix_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, nbr.ptr, cptr, nbr.cols, yptr, ldy, c.stream))
+            return c.result(y) if out is None else y
 
     def nnm_info(self):
         """(solo_rows, short_rows) of the last neighbour search on this engine: the rows whose list is themselves alone
         although k > 1, and the rows whose list is shorter than k (synchronises)."""
-        solo, short = ctypes.c_int64(0), ctypes.c_int64(0)
-        _check(self.lib.byz_nnm_info(self.ctx, ctypes.byref(solo), ctypes.byref(short)))
-        return int(solo.value), int(short.value)
+        return tuple(self._read(self.lib.byz_nnm_info, [ctypes.c_int64, ctypes.c_int64]))
 
     def nnm(self, g, users_count, corrupted_count, distances=None, return_neighbours=False):
         """Nearest-neighbour mixing: every row replaced by the mean of its users_count - corrupted_count nearest rows, itself
@@ -1159,58 +1244,36 @@ class Engine:
         k = int(users_count) - int(corrupted_count)
         dm = self._device_matrix(g)
         if distances is not None:
-            d, _ = self._as_distances(distances)
-            nbr, counts = self.nnm_neighbours(d, k)
-            y = self.nnm_mix(g, nbr, counts)
-            self.synchronize(dm.stream if dm is not None else None)   # the lists are ours: they must outlive the mix
+            with _Call(self) as c:
+                if dm is not None:
+                    c.matrix(dm)
+                d, _ = c.distances(distances)
+                nbr, counts = (c.temporary(b) for b in self.nnm_neighbours(d, k))   # the lists are ours: they must outlive the mix
+                y = self.nnm_mix(g, nbr, counts)
             if not return_neighbours:
                 return y
             if dm is None:
                 nbr = nbr.numpy()
             elif dm.torch_like is not None:
-                import torch
-                nbr = torch.from_numpy(nbr.numpy()).to(dm.torch_like.device)
+                nbr = _torch().from_numpy(nbr.numpy()).to(dm.torch_like.device)
             return y, nbr
         if dm is None:
             h = self._host_matrix(g)
             n, d = h.shape
             y = np.empty((n, d), dtype=np.float32)
             nbr = np.full((n, max(k, 1)), -1, dtype=np.int32) if return_neighbours else None
-            _check(self.lib.byz_nnm_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, int(users_count),
-                                         int(corrupted_count), y.ctypes.data_as(ctypes.c_void_p),
-                                         nbr.ctypes.data_as(ctypes.c_void_p) if return_neighbours else None))
+            _check(self.lib.byz_nnm_host(self.ctx, _hp(h), n, d, int(users_count), int(corrupted_count), _hp(y), _hp(nbr)))
             return (y, nbr) if return_neighbours else y
-        y, yptr = self._out_like(dm, (dm.rows, dm.cols))
-        nbr, nptr = self._out_like(dm, (dm.rows, max(k, 1)), np.int32) if return_neighbours else (None, None)
-        _check(self.lib.byz_nnm_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, int(users_count), int(corrupted_count),
-                                    _vp(yptr), dm.cols, _vp(nptr), _vp(dm.stream)))
-        self.check(dm.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            y, yptr = c.out(dm.shape)
+            nbr, nptr = c.out((dm.rows, max(k, 1)), np.int32, want=return_neighbours)
+            c.run(self.lib.byz_nnm_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, int(users_count), int(corrupted_count), yptr,
+                                       dm.cols, nptr, c.stream))
+            self.check(c.stream)      # (a kernel of the distances can only flag a failure: the sticky status word)
         return (y, nbr) if return_neighbours else y
 
     # ---- the robust learning rate (Ozdayi, Kantarcioglu and Gel, AAAI 2021; not in the reference) ----
-    def _i32_vector(self, v, n, what='votes'):
-        """A length-n int32 vector for a kernel -> (device pointer, keepalive, ours): a DeviceBuffer or a torch CUDA tensor
-        is used where it is (torch: made contiguous int32), anything else is uploaded (ours)."""
-        if isinstance(v, DeviceBuffer):
-            if v.dtype != np.int32 or int(np.prod(v.shape)) != n:
-                raise ValueError('a DeviceBuffer of %s must hold %d int32 values' % (what, n))
-            return v.ptr, v, False
-        if _is_torch(v) and v.is_cuda:
-            import torch
-            if v.device.index != self.device:
-                raise ValueError('the %s live on %s, this engine drives cuda:%d' % (what, v.device, self.device))
-            t = v.reshape(-1).to(torch.int32).contiguous()
-            if t.numel() != n:
-                raise ValueError('expected %d %s, got %d' % (n, what, t.numel()))
-            return t.data_ptr(), t, False
-        host = np.asarray(v.cpu().numpy() if _is_torch(v) else v).reshape(-1)
-        if host.dtype.kind not in 'iu':
-            raise ValueError('%s must be integers, got %s' % (what, host.dtype))
-        if host.size != n:
-            raise ValueError('expected %d %s, got %d' % (n, what, host.size))
-        buf = self.to_device(host.astype(np.int32))
-        return buf.ptr, buf, True
-
     @staticmethod
     def _theta(theta, n_rows=None):
         if isinstance(theta, bool) or int(theta) != theta:
@@ -1224,38 +1287,33 @@ class Engine:
         """votes[c] = #{r : g[r, c] > 0} - #{r : g[r, c] < 0}, int32 of length D, in one read of g: +0.0, -0.0 and NaN cast
         no vote, +-inf and denormals vote by their sign.  np.sign(votes) is signSGD's majority vote.  A torch tensor for a
         torch input, numpy for a host input, a DeviceBuffer otherwise."""
-        m, stage, host = self._staged(g)
-        votes, vptr = self._out_like(m, m.cols, np.int32)
-        _check(self.lib.byz_sign_votes_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(vptr), _vp(m.stream)))
-        return votes.numpy() if host else votes      # (a download synchronises: the staged copy outlives the kernel)
+        with _Call(self) as c:
+            m = c.matrix(g)
+            votes, vptr = c.out(m.cols, np.int32)
+            c.run(self.lib.byz_sign_votes_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, vptr, c.stream))
+            return c.result(votes)
 
     def sign_flip(self, agg, votes, theta, out=None):
         """out[c] = agg[c] with its sign bit inverted where abs(votes[c]) < theta, agg[c] verbatim elsewhere: the robust
         learning rate applied to ANY aggregate.  out=agg (device-resident) flips in place.  numpy in -> numpy out;
         device-resident in -> device-resident out."""
         theta = self._theta(theta)
-        (aptr,), n, stream, keep, example = self._vectors(agg)
-        host = not (isinstance(agg, DeviceBuffer) or (_is_torch(agg) and agg.is_cuda))
-        vptr, vkeep, vours = self._i32_vector(votes, n)
-        if out is None:
-            res, optr = self._out_like(example, n)
-        else:
-            (optr,), n_out, _, _, _ = self._vectors(out)
-            if host or n_out != n or not (isinstance(out, DeviceBuffer) or (_is_torch(out) and out.is_cuda)):
-                raise ValueError('out must be a device-resident float32 vector of %d entries' % n)
-            res = out
-        _check(self.lib.byz_sign_flip_dev(self.ctx, _vp(aptr), _vp(vptr), n, theta, _vp(optr), _vp(stream)))
-        if host:
-            return res.numpy()                       # (a download synchronises)
-        if vours:
-            self.synchronize(stream)                 # uploaded votes must outlive the kernel
-        return res
+        with _Call(self) as c:
+            a = c.operand(agg, np.float32, _f32(None), convert=False, leads=True)
+            v = c.operand(votes, np.int32, _i32('votes'), a.size)
+            if out is None:
+                res, optr = c.out(a.size)
+            else:
+                refusal = 'out must be a device-resident float32 vector of %(n)d entries'
+                if c.host or not _is_device(out):
+                    raise ValueError(refusal % {'n': a.size})
+                res, optr = out, c.operand(out, np.float32, _f32(refusal), a.size, convert=False).ptr
+            c.run(self.lib.byz_sign_flip_dev(self.ctx, a.ptr, v.ptr, a.size, theta, optr, c.stream))
+            return c.result(res)
 
     def robust_lr_info(self):
         """The number of columns the last sign_flip or robust_lr on this engine flipped (synchronises)."""
-        flipped = ctypes.c_int64(0)
-        _check(self.lib.byz_robust_lr_info(self.ctx, ctypes.byref(flipped)))
-        return int(flipped.value)
+        return self._read(self.lib.byz_robust_lr_info, [ctypes.c_int64])[0]
 
     def robust_lr(self, g, theta, return_votes=False):
         """The robust learning rate around the plain mean, fused: no_defense's vector (bit for bit) with the sign bit
@@ -1268,15 +1326,14 @@ class Engine:
             theta = self._theta(theta, n)
             out = np.empty(d, dtype=np.float32)
             votes = np.empty(d, dtype=np.int32) if return_votes else None
-            _check(self.lib.byz_robust_lr_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, theta,
-                                               out.ctypes.data_as(ctypes.c_void_p),
-                                               votes.ctypes.data_as(ctypes.c_void_p) if return_votes else None))
+            _check(self.lib.byz_robust_lr_host(self.ctx, _hp(h), n, d, theta, _hp(out), _hp(votes)))
             return (out, votes) if return_votes else out
         theta = self._theta(theta, dm.rows)
-        out, optr = self._out_like(dm, dm.cols)
-        votes, vptr = self._out_like(dm, dm.cols, np.int32) if return_votes else (None, None)
-        _check(self.lib.byz_robust_lr_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, theta, _vp(optr), _vp(vptr),
-                                          _vp(dm.stream)))
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            out, optr = c.out(dm.cols)
+            votes, vptr = c.out(dm.cols, np.int32, want=return_votes)
+            c.run(self.lib.byz_robust_lr_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, theta, optr, vptr, c.stream))
         return (out, votes) if return_votes else out
 
     # ---- s-bucketing (Karimireddy, He and Jaggi, ICLR 2022; not in the reference) ----
@@ -1293,30 +1350,27 @@ class Engine:
         s = int(s)
         dm = self._device_matrix(g)
         h = self._host_matrix(g) if dm is None else None
-        n, d = (dm.rows, dm.cols) if dm is not None else h.shape
+        n, d = dm.shape if dm is not None else h.shape
         if s < 1 or s > n:
             raise ValueError('s = %d outside 1..%d (the row count)' % (s, n))
         buckets = -(-n // s)
-        on_device = isinstance(perm, DeviceBuffer) or (_is_torch(perm) and perm.is_cuda)
-        if perm is not None and not on_device:
+        if perm is not None and not _is_device(perm):
             perm = np.asarray(perm.numpy() if _is_torch(perm) else perm).reshape(-1)
             if perm.dtype.kind not in 'iu' or perm.size != n or not np.array_equal(np.sort(perm), np.arange(n)):
                 raise ValueError('perm must be a permutation of range(%d)' % n)
             perm = np.ascontiguousarray(perm, dtype=np.int32)
         if dm is None:
-            if on_device:
-                perm = perm.numpy() if isinstance(perm, DeviceBuffer) else perm.cpu().numpy()
-                perm = np.ascontiguousarray(perm.reshape(-1), dtype=np.int32)
+            if _is_device(perm):
+                perm = np.ascontiguousarray((perm.numpy() if isinstance(perm, DeviceBuffer) else _to_host(perm)).reshape(-1),
+                                            dtype=np.int32)
             y = np.empty((buckets, d), dtype=np.float32)
-            _check(self.lib.byz_bucket_means_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d,
-                                                  perm.ctypes.data_as(ctypes.c_void_p) if perm is not None else None, s,
-                                                  y.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_bucket_means_host(self.ctx, _hp(h), n, d, _hp(perm), s, _hp(y)))
             return y
-        pptr, keep, ours = (None, None, False) if perm is None else self._i32_vector(perm, n, what='perm entries')
-        y, yptr = self._out_like(dm, (buckets, d))
-        _check(self.lib.byz_bucket_means_dev(self.ctx, _vp(dm.ptr), n, d, dm.ld, _vp(pptr), s, _vp(yptr), d, _vp(dm.stream)))
-        if ours:
-            self.synchronize(dm.stream)      # the uploaded permutation must outlive the kernel
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            pptr = None if perm is None else c.operand(perm, np.int32, _i32('perm entries'), n).ptr
+            y, yptr = c.out((buckets, d))
+            c.run(self.lib.byz_bucket_means_dev(self.ctx, dm.ptr, n, d, dm.ld, pptr, s, yptr, d, c.stream))
         return y
 
     # ---- SparseFed: global top-k with error feedback (Panda et al., AISTATS 2022; not in the reference) ----
@@ -1330,10 +1384,6 @@ class Engine:
         return k
 
     @staticmethod
-    def _on_device(v):
-        return isinstance(v, DeviceBuffer) or (_is_torch(v) and v.is_cuda)
-
-    @staticmethod
     def _host_f32(v, n=None, writable=False):
         """A flat C-contiguous float32 host vector: `v` itself where it already is one (required when the call writes it)."""
         if writable:
@@ -1341,29 +1391,26 @@ class Engine:
                 raise ValueError('a host vector that is written must be a writable C-contiguous float32 numpy array')
             host = v.reshape(-1)
         else:
-            if isinstance(v, DeviceBuffer):
-                v = v.numpy()
-            host = np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float32).reshape(-1)
+            host = np.ascontiguousarray(v.numpy() if isinstance(v, DeviceBuffer) else _to_host(v), dtype=np.float32).reshape(-1)
         if n is not None and host.size != n:
             raise ValueError('expected %d values, got %d' % (n, host.size))
         return host
-
-    def _device_out(self, v, n, what):
-        if not self._on_device(v):
-            raise ValueError('%s must be a device-resident float32 vector of %d entries' % (what, n))
-        (ptr,), size, _, _, _ = self._vectors(v)
-        if size != n:
-            raise ValueError('%s has %d entries, expected %d' % (what, size, n))
-        return ptr
 
     def topk_info(self):
         """{selected, threshold_key, ties, ties_taken} of the last top-k on this engine (synchronises): selected == k, the
         threshold key T = the k-th largest of bits & 0x7fffffff (0xffffffff for k = 0), the columns whose key is T and how
         many of them were taken (the first in index order)."""
-        sel, ties, taken, key = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_uint32(0)
-        _check(self.lib.byz_topk_info(self.ctx, ctypes.byref(sel), ctypes.byref(key), ctypes.byref(ties), ctypes.byref(taken)))
-        return {'selected': int(sel.value), 'threshold_key': int(key.value), 'ties': int(ties.value),
-                'ties_taken': int(taken.value)}
+        names = ('selected', 'threshold_key', 'ties', 'ties_taken')
+        return dict(zip(names, self._read(self.lib.byz_topk_info, [ctypes.c_int64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64])))
+
+    def _topk_operands(self, c, x, add, out, residual):
+        """(x, add pointer, out, out pointer, residual, residual pointer) of a device-resident top-k: `out` and `residual` are
+        the caller's vectors to write, or allocated beside x and add."""
+        x = c.operand(x, np.float32, _f32(None), convert=False, leads=True)
+        aptr = None if add is None else c.operand(add, np.float32, _DIFFER, x.size, convert=False, leads=True).ptr
+        out, optr = c.out(x.size) if out is None else (out, c.written(out, x.size, 'out').ptr)
+        residual, rptr = c.out(x.size) if residual is None else (residual, c.written(residual, x.size, 'residual').ptr)
+        return x, aptr, out, optr, residual, rptr
 
     def topk_sparsify(self, x, k, add=None, out=None, residual=None, return_info=False):
         """(out, residual) of the global top-k of w = x (add=None) or fl32(x + add): the k columns first in the order (key =
@@ -1372,33 +1419,20 @@ class Engine:
         them; nothing is sanitised.  k: an integer in [0, n].  numpy in -> numpy out; device-resident x -> device-resident
         out.  out / residual: vectors to write (device-resident for a device x); residual=x and out=add are the in-place
         round.  return_info=True also returns topk_info()."""
-        if not self._on_device(x):
+        if not _is_device(x):
             xh = self._host_f32(x)
             n = xh.size
             k = self._topk_k(k, n)
             ah = self._host_f32(add, n) if add is not None else None
             oh = self._host_f32(out, n, writable=True) if out is not None else np.empty(n, dtype=np.float32)
             rh = self._host_f32(residual, n, writable=True) if residual is not None else np.empty(n, dtype=np.float32)
-            _check(self.lib.byz_topk_sparsify_host(self.ctx, xh.ctypes.data_as(ctypes.c_void_p),
-                                                   ah.ctypes.data_as(ctypes.c_void_p) if ah is not None else None, n, k,
-                                                   oh.ctypes.data_as(ctypes.c_void_p), rh.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_topk_sparsify_host(self.ctx, _hp(xh), _hp(ah), n, k, _hp(oh), _hp(rh)))
             oh, rh = (out if out is not None else oh), (residual if residual is not None else rh)     # the caller's own arrays
             return (oh, rh, self.topk_info()) if return_info else (oh, rh)
-        vectors = (x,) if add is None else (x, add)
-        ptrs, n, stream, keep, example = self._vectors(*vectors)
-        k = self._topk_k(k, n)
-        xptr, aptr = ptrs[0], (ptrs[1] if add is not None else None)
-        if out is None:
-            out, optr = self._out_like(example, n)
-        else:
-            optr = self._device_out(out, n, 'out')
-        if residual is None:
-            residual, rptr = self._out_like(example, n)
-        else:
-            rptr = self._device_out(residual, n, 'residual')
-        _check(self.lib.byz_topk_sparsify_dev(self.ctx, _vp(xptr), _vp(aptr), n, k, _vp(optr), _vp(rptr), _vp(stream)))
-        if add is not None and not self._on_device(add):
-            self.synchronize(stream)                 # an uploaded add must outlive the kernels
+        with _Call(self) as c:
+            x, aptr, out, optr, residual, rptr = self._topk_operands(c, x, add, out, residual)
+            k = self._topk_k(k, x.size)
+            c.run(self.lib.byz_topk_sparsify_dev(self.ctx, x.ptr, aptr, x.size, k, optr, rptr, c.stream))
         return (out, residual, self.topk_info()) if return_info else (out, residual)
 
     def topk_sparsify_sharded(self, x_local, k, n_total, rank, world, add=None, all_reduce=None, out=None, residual=None,
@@ -1408,36 +1442,17 @@ class Engine:
         all_reduce(tensor) sums a CUDA fp64 tensor in place over the ranks on the current stream (None: one rank).  Four
         all-reduces whatever the data: 2048, 1024, 1024 and `world` doubles.  Returns this rank's (out, residual); the
         selected set is topk_sparsify's on the concatenated vector, bit for bit."""
-        if not self._on_device(x_local) or (add is not None and not self._on_device(add)):
+        if not _is_device(x_local) or (add is not None and not _is_device(add)):
             raise ValueError('topk_sparsify_sharded() takes device-resident vectors')
-        vectors = (x_local,) if add is None else (x_local, add)
-        ptrs, n, stream, keep, example = self._vectors(*vectors)
-        n_total, rank, world = int(n_total), int(rank), int(world)
-        if world < 1 or not 0 <= rank < world or n > n_total:
-            raise ValueError('rank %d of %d with %d of %d columns' % (rank, world, n, n_total))
-        k = self._topk_k(k, n_total)
-        device = self.device
-
-        def reduce_on_ranks(user, buf, count, stream_):
-            try:
-                if all_reduce is not None:
-                    import torch
-                    all_reduce(torch.as_tensor(_DeviceF64(buf, count), device='cuda:%d' % device))
-                return 0
-            except Exception:      # noqa: BLE001  (a Python exception must not unwind through the C frames)
-                return 1
-        callback = _native.ALLREDUCE_F64_FN(reduce_on_ranks)
-        if out is None:
-            out, optr = self._out_like(example, n)
-        else:
-            optr = self._device_out(out, n, 'out')
-        if residual is None:
-            residual, rptr = self._out_like(example, n)
-        else:
-            rptr = self._device_out(residual, n, 'residual')
-        _check(self.lib.byz_topk_sparsify_sharded_dev(self.ctx, _vp(ptrs[0]), _vp(ptrs[1] if add is not None else None), n,
-                                                      n_total, k, rank, world, ctypes.cast(callback, ctypes.c_void_p), None,
-                                                      _vp(optr), _vp(rptr), _vp(stream)))
+        with _Call(self) as c:
+            x, aptr, out, optr, residual, rptr = self._topk_operands(c, x_local, add, out, residual)
+            n, n_total, rank, world = x.size, int(n_total), int(rank), int(world)
+            if world < 1 or not 0 <= rank < world or n > n_total:
+                raise ValueError('rank %d of %d with %d of %d columns' % (rank, world, n, n_total))
+            k = self._topk_k(k, n_total)
+            callback = self._allreduce_callback(all_reduce)
+            c.run(self.lib.byz_topk_sparsify_sharded_dev(self.ctx, x.ptr, aptr, n, n_total, k, rank, world,
+                                                         ctypes.cast(callback, ctypes.c_void_p), None, optr, rptr, c.stream))
         return (out, residual, self.topk_info()) if return_info else (out, residual)
 
     def sparsefed(self, g, k, clip=10.0, residual=None, return_info=False):
@@ -1453,29 +1468,27 @@ class Engine:
             h = self._host_matrix(g)
             n, d = h.shape
             params.k = self._topk_k(k, d)
-            if residual is not None and self._on_device(residual):
+            if residual is not None and _is_device(residual):
                 raise ValueError('a host matrix takes a host memory (a float32 numpy vector)')
             res = self._host_f32(residual, d, writable=True) if residual is not None else np.zeros(d, dtype=np.float32)
             out = np.empty(d, dtype=np.float32)
-            _check(self.lib.byz_sparsefed_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                               res.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_sparsefed_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(res), _hp(out)))
             res = residual if residual is not None else res       # the caller's own array
         else:
-            d = dm.cols
-            params.k = self._topk_k(k, d)
-            if residual is None:
-                if dm.torch_like is not None:
-                    import torch
-                    res = torch.zeros(d, dtype=torch.float32, device=dm.torch_like.device)
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                d = dm.cols
+                params.k = self._topk_k(k, d)
+                if residual is not None:
+                    res, rptr = residual, c.written(residual, d, 'residual').ptr
+                elif dm.torch_like is not None:
+                    res = _torch().zeros(d, dtype=_torch().float32, device=dm.torch_like.device)
                     rptr = res.data_ptr()
                 else:
-                    res = self.to_device(np.zeros(d, dtype=np.float32))
+                    res = self.to_device(np.zeros(d, dtype=np.float32))      # (the caller's from here on: no temporary)
                     rptr = res.ptr
-            else:
-                res, rptr = residual, self._device_out(residual, d, 'residual')
-            out, optr = self._out_like(dm, d)
-            _check(self.lib.byz_sparsefed_dev(self.ctx, _vp(dm.ptr), dm.rows, d, dm.ld, ctypes.byref(params), _vp(rptr),
-                                              _vp(optr), _vp(dm.stream)))
+                out, optr = c.out(d)
+                c.run(self.lib.byz_sparsefed_dev(self.ctx, dm.ptr, dm.rows, d, dm.ld, ctypes.byref(params), rptr, optr, c.stream))
         if not return_info:
             return out, res
         info = self.topk_info()
@@ -1500,15 +1513,12 @@ class Engine:
         CUDA tensor, for a device-resident int32 tensor with the same bits on its stream instead."""
         params = self._noise_params(0.0, seed, round, column_offset)
         n = int(n)
-        if like is not None:
-            import torch
-            out = torch.empty(max(n, 0), dtype=torch.int32, device=like.device)
-            stream = torch.cuda.current_stream(like.device).cuda_stream
-            _check(self.lib.byz_noise_words_dev(self.ctx, ctypes.byref(params), n, _vp(out.data_ptr()), _vp(stream)))
-            return out
-        buf = DeviceBuffer(self, (max(n, 1),), np.uint32)
-        _check(self.lib.byz_noise_words_dev(self.ctx, ctypes.byref(params), n, _vp(buf.ptr), None))
-        return buf.numpy()
+        with _Call(self) as c:
+            if like is not None:
+                c.beside(like)
+            out, ptr = c.out(max(n, 0), np.int32) if like is not None else c.out(max(n, 1), np.uint32)
+            c.run(self.lib.byz_noise_words_dev(self.ctx, ctypes.byref(params), n, ptr, c.stream))
+            return out if like is not None else c.numpy(out)
 
     def gaussian_noise(self, x, sigma, seed=0, round=0, column_offset=0, scale=None, out=None):
         """out[c] = fl32((double)x[c] + sigma_eff * z[column_offset + c]): z the fp64 Box-Muller normals of the Philox stream
@@ -1517,30 +1527,24 @@ class Engine:
         numpy in -> numpy out; device-resident x -> device-resident out.  out: a device vector to write, which may be x
         itself (in place).  sigma = 0 with no scale returns x's bits."""
         params = self._noise_params(sigma, seed, round, column_offset)
-        if not self._on_device(x):
+        if not _is_device(x):
             if scale is not None or out is not None:
                 raise ValueError('a host vector takes neither a device scale nor an output vector')
             xh = self._host_f32(x)
             oh = np.empty(xh.size, dtype=np.float32)
-            _check(self.lib.byz_gaussian_noise_host(self.ctx, xh.ctypes.data_as(ctypes.c_void_p), xh.size, ctypes.byref(params),
-                                                    oh.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_gaussian_noise_host(self.ctx, _hp(xh), xh.size, ctypes.byref(params), _hp(oh)))
             return oh
-        (xptr,), n, stream, keep, example = self._vectors(x)
-        sptr, skeep = self._f64_vector(scale, 1) if scale is not None else (None, None)
-        if out is None:
-            out, optr = self._out_like(example, n)
-        else:
-            optr = self._device_out(out, n, 'out')
-        _check(self.lib.byz_gaussian_noise_dev(self.ctx, _vp(xptr), n, ctypes.byref(params), _vp(sptr), _vp(optr), _vp(stream)))
-        if isinstance(skeep, DeviceBuffer) and skeep is not scale:
-            self.synchronize(stream)                 # an uploaded scale must outlive the kernel
+        with _Call(self) as c:
+            x = c.operand(x, np.float32, _f32(None), convert=False, leads=True)
+            sptr = None if scale is None else c.operand(scale, np.float64, _F64, 1).ptr
+            out, optr = c.out(x.size) if out is None else (out, c.written(out, x.size, 'out').ptr)
+            c.run(self.lib.byz_gaussian_noise_dev(self.ctx, x.ptr, x.size, ctypes.byref(params), sptr, optr, c.stream))
         return out
 
     def weak_dp_info(self):
         """{clipped_rows, excluded_rows, clip} of the last clip_scales or weak_dp on this engine (synchronises)."""
-        clipped, excluded, clip = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-        _check(self.lib.byz_weak_dp_info(self.ctx, ctypes.byref(clipped), ctypes.byref(excluded), ctypes.byref(clip)))
-        return {'clipped_rows': int(clipped.value), 'excluded_rows': int(excluded.value), 'clip': float(clip.value)}
+        return dict(zip(('clipped_rows', 'excluded_rows', 'clip'),
+                        self._read(self.lib.byz_weak_dp_info, [ctypes.c_int64, ctypes.c_int64, ctypes.c_double])))
 
     def clip_scales(self, sq, clip=10.0, adaptive=False, return_clip=False):
         """The clipping scales from the rows' fp64 squared norms (row_sqdist with a zero centre): d = sqrt(sq), s = 1 (d <=
@@ -1548,26 +1552,15 @@ class Engine:
         np.median of the finite norms (0 when there is none, and then every scale is 0).  fp64 out where sq lives: a torch
         tensor, a DeviceBuffer, or numpy for a host sq.  return_clip=True returns (scales, clip), the clip a one-element
         array of the same kind (device-resident: what gaussian_noise takes as `scale`)."""
-        if self._on_device(sq):
-            n = sq.numel() if _is_torch(sq) else int(np.prod(sq.shape))
-            host = False
-        else:
-            sq = np.ascontiguousarray(sq, dtype=np.float64).reshape(-1)
-            n, host = sq.size, True
-        qptr, qkeep = self._f64_vector(sq, n)
-        example = qkeep if _is_torch(qkeep) else None
-        stream = None
-        if example is not None:
-            import torch
-            stream = torch.cuda.current_stream(example.device).cuda_stream
+        if not _is_device(sq):
+            sq = np.ascontiguousarray(sq, dtype=np.float64)
         params = _native.WeakDpParams(float(clip), 0.0, 1 if adaptive else 0, 0, 0, 0)
-        scales, sptr = self._out_like(example, n, np.float64)
-        used, cptr = self._out_like(example, 1, np.float64)
-        _check(self.lib.byz_clip_scales_dev(self.ctx, _vp(qptr), n, ctypes.byref(params), _vp(sptr), _vp(cptr), _vp(stream)))
-        if host:
-            self.synchronize(stream)                 # the uploaded norms must outlive the kernels
-            scales, used = scales.numpy(), used.numpy()
-        return (scales, used) if return_clip else scales
+        with _Call(self) as c:
+            q = c.operand(sq, np.float64, _F64, leads=True)
+            scales, sptr = c.out(q.size, np.float64)
+            used, cptr = c.out(1, np.float64)
+            c.run(self.lib.byz_clip_scales_dev(self.ctx, q.ptr, q.size, ctypes.byref(params), sptr, cptr, c.stream))
+            return c.result((scales, used)) if return_clip else c.result(scales)
 
     def weak_dp(self, g, clip=10.0, sigma=0.01, adaptive=False, seed=0, round=0, column_offset=0, return_info=False):
         """Clip and noise: every row scaled to norm `clip` at most, the mean (centered_clip from zero with one iteration: its
@@ -1582,12 +1575,12 @@ class Engine:
             h = self._host_matrix(g)
             n, d = h.shape
             out = np.empty(d, dtype=np.float32)
-            _check(self.lib.byz_weak_dp_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                             out.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_weak_dp_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(out)))
         else:
-            out, optr = self._out_like(dm, dm.cols)
-            _check(self.lib.byz_weak_dp_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params), _vp(optr),
-                                            _vp(dm.stream)))
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                out, optr = c.out(dm.cols)
+                c.run(self.lib.byz_weak_dp_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), optr, c.stream))
         return (out, self.weak_dp_info()) if return_info else out
 
     # ---- FLAME (Nguyen et al., USENIX Security 2022; not in the reference) ----
@@ -1595,24 +1588,23 @@ class Engine:
         """The pairwise COSINE distances of g's rows as a `Distances` handle, resident on the GPU: c_ij = max(0, 1 - g_ij /
         (sqrt(g_ii) sqrt(g_jj))) from the fp64 Gram, rounded once to float32; the diagonal is +inf (pairwise_distances'
         convention), a zero or non-finite row's whole row and column are +inf; symmetric bit for bit.  Up to 16,384 rows."""
-        m, stage, _ = self._staged(g)
-        dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
-        _check(self.lib.byz_cosine_distances_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(dist.ptr), _vp(m.stream)))
-        self.check(m.stream)
+        with _Call(self) as c:
+            m = c.matrix(g)
+            dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
+            c.run(self.lib.byz_cosine_distances_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, dist.ptr, c.stream))
+            self.check(c.stream)
         return Distances(dist, m.rows)
 
     def cosine_from_gram(self, gram, n=None, stream=None):
         """cosine_distances' second half on an (all-reduced) fp64 Gram, n x n, on the device -> `Distances`."""
-        ptr = gram.data_ptr() if _is_torch(gram) else gram.ptr
         n = int(gram.shape[0]) if n is None else int(n)
-        if _is_torch(gram):
-            import torch
-            if gram.dtype != torch.float64 or not gram.is_contiguous() or not gram.is_cuda:
-                raise ValueError('the Gram must be a contiguous float64 CUDA tensor')
-            stream = torch.cuda.current_stream(gram.device).cuda_stream
-        dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
-        _check(self.lib.byz_cosine_from_gram_dev(self.ctx, _vp(ptr), n, _vp(dist.ptr), _vp(stream)))
-        self.synchronize(stream)
+        if _is_torch(gram) and (gram.dtype != _torch().float64 or not gram.is_contiguous() or not gram.is_cuda):
+            raise ValueError('the Gram must be a contiguous float64 CUDA tensor')
+        with _Call(self, stream) as c:
+            gram = c.as_it_lies(gram)
+            dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
+            c.run(self.lib.byz_cosine_from_gram_dev(self.ctx, gram.ptr, n, dist.ptr, c.stream))
+            self.synchronize(c.stream)
         return dist
 
     @staticmethod
@@ -1633,23 +1625,20 @@ class Engine:
     def flame_info(self):
         """{admitted, broken_rows, w_star, clip} of the last flame_select or flame on this engine (synchronises): the rows
         admitted, the rows without a finite off-diagonal distance, the threshold (+inf: nobody) and the median norm."""
-        admitted, broken = ctypes.c_int64(0), ctypes.c_int64(0)
-        w_star, clip = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self.lib.byz_flame_info(self.ctx, ctypes.byref(admitted), ctypes.byref(broken), ctypes.byref(w_star),
-                                       ctypes.byref(clip)))
-        return {'admitted': int(admitted.value), 'broken_rows': int(broken.value), 'w_star': float(w_star.value),
-                'clip': float(clip.value)}
+        return dict(zip(('admitted', 'broken_rows', 'w_star', 'clip'),
+                        self._read(self.lib.byz_flame_info, [ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double])))
 
     def flame_core_distances(self, distances, min_samples=1):
         """flame_select's first step alone: the min_samples-th smallest off-diagonal entry of every row (order: the distance,
         -0.0 as +0.0 and a NaN behind +inf, then the column; min_samples = 0: zeros), as a float32 numpy array."""
         if isinstance(distances, dict):
             raise ValueError('flame_core_distances() takes a Distances handle or a dense matrix')
-        d, _ = self._as_distances(distances)
-        ms, _ = self._flame_sizes(d.n, min_samples, d.n)
-        core = DeviceBuffer(self, (d.n,), np.float32)
-        _check(self.lib.byz_flame_core_distances_dev(self.ctx, _vp(d.ptr), d.n, ms, _vp(core.ptr), None))
-        return core.numpy()
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            ms, _ = self._flame_sizes(d.n, min_samples, d.n)
+            core = DeviceBuffer(self, (d.n,), np.float32)
+            c.run(self.lib.byz_flame_core_distances_dev(self.ctx, d.ptr, d.n, ms, core.ptr, None))
+            return core.numpy()
 
     def flame_select(self, distances, min_samples=1, min_cluster_size=None, on_device=False, like=None):
         """FLAME's clustering on a distance matrix (a `Distances` handle or a dense symmetric matrix, diagonal +inf; cosine
@@ -1660,11 +1649,14 @@ class Engine:
         w_star}."""
         if isinstance(distances, dict):
             raise ValueError('flame_select() takes a Distances handle or a dense matrix')
-        d, _ = self._as_distances(distances)
-        ms, m = self._flame_sizes(d.n, min_samples, min_cluster_size)
-        flags, fptr = self._out_like(like if on_device else None, d.n, np.int32)
-        _check(self.lib.byz_flame_select_dev(self.ctx, _vp(d.ptr), d.n, m, ms, _vp(fptr), None))
-        info = self.flame_info()
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            ms, m = self._flame_sizes(d.n, min_samples, min_cluster_size)
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            flags, fptr = c.out(d.n, np.int32)
+            c.run(self.lib.byz_flame_select_dev(self.ctx, d.ptr, d.n, m, ms, fptr, None))
+            info = self.flame_info()
         info.pop('clip')
         return (flags if on_device else np.flatnonzero(flags.numpy()).astype(np.int64)), info
 
@@ -1680,30 +1672,30 @@ class Engine:
         n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
         ms, m = self._flame_sizes(n, min_samples, min_cluster_size)
         params = _native.FlameParams(noise.sigma, ms, m, noise.seed, noise.round, noise.column_offset)
-        dist = None
-        if distances is not None:
-            if isinstance(distances, dict):
-                raise ValueError('flame() takes a Distances handle or a dense matrix as `distances`')
-            dist, _ = self._as_distances(distances)
-            if dist.n != n:
-                raise ValueError('the distance matrix has %d rows, the gradients %d' % (dist.n, n))
-        if dm is None:
-            h = self._host_matrix(g)
-            d = h.shape[1]
-            out = np.empty(d, dtype=np.float32)
-            flags = np.zeros(n, dtype=np.int32)
-            dist_host = np.ascontiguousarray(dist.numpy(), dtype=np.float32) if dist is not None else None
-            _check(self.lib.byz_flame_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                           dist_host.ctypes.data_as(ctypes.c_void_p) if dist is not None else None,
-                                           out.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p)))
-        else:
-            out, optr = self._out_like(dm, dm.cols)
-            flags_dev, fptr = self._out_like(dm, n, np.int32) if return_info else (None, None)
-            _check(self.lib.byz_flame_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
-                                          _vp(dist.ptr) if dist is not None else None, _vp(optr), _vp(fptr), _vp(dm.stream)))
-            self.check(dm.stream)      # (a kernel of the Gram can only flag a failure; `dist` must outlive the kernels)
-            if return_info:
-                flags = flags_dev.cpu().numpy() if _is_torch(flags_dev) else flags_dev.numpy()
+        if isinstance(distances, dict):
+            raise ValueError('flame() takes a Distances handle or a dense matrix as `distances`')
+        with _Call(self) as c:
+            dist = None
+            if distances is not None:
+                dist, _ = c.distances(distances)
+                if dist.n != n:
+                    raise ValueError('the distance matrix has %d rows, the gradients %d' % (dist.n, n))
+            if dm is None:
+                h = self._host_matrix(g)
+                d = h.shape[1]
+                out = np.empty(d, dtype=np.float32)
+                flags = np.zeros(n, dtype=np.int32)
+                dist_host = np.ascontiguousarray(dist.numpy(), dtype=np.float32) if dist is not None else None
+                _check(self.lib.byz_flame_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(dist_host), _hp(out), _hp(flags)))
+            else:
+                dm = c.matrix(dm)
+                out, optr = c.out(dm.cols)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                c.run(self.lib.byz_flame_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                             dist.ptr if dist is not None else None, optr, fptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    flags = _to_host(flags) if _is_torch(flags) else flags.numpy()
         if not return_info:
             return out
         info = self.flame_info()
@@ -1712,69 +1704,63 @@ class Engine:
 
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
-        """columns -> ((n_iters, b) host int64 array or None, torch tensor or None).  One list (1-D) or one per iteration
-        (2-D); host lists are checked here (range, strictly ascending) unless the caller vouches; a torch CUDA tensor is used
-        in place and checked with one reduction and a host synchronisation."""
+        """columns -> an (n_iters, b) int64 array of column lists: a torch CUDA tensor where it was one, else numpy.  One list
+        (1-D) or one per iteration (2-D).  DnC's own contract is checked here unless the caller vouches: every list in range
+        and strictly ascending (for a torch CUDA tensor one reduction and a host synchronisation)."""
         if _is_torch(columns) and columns.is_cuda:
-            import torch
             t = columns.reshape(1, -1) if columns.dim() == 1 else columns
-            if t.dim() != 2 or t.dtype != torch.int64 or t.device.index != self.device or t.numel() == 0:
+            if t.dim() != 2 or t.dtype != _torch().int64 or t.device.index != self.device or t.numel() == 0:
                 raise ValueError('device column lists must be a non-empty 1-D or 2-D int64 tensor on cuda:%d' % self.device)
             t = t.contiguous()
-            if validate:
-                bad = bool(((t < 0) | (t >= n_cols)).any().item()) or bool((t[:, 1:] <= t[:, :-1]).any().item())
-                if bad:
-                    raise ValueError('column lists must be in [0, %d) and strictly ascending' % n_cols)
-            return None, t
-        host = np.asarray(columns.detach().cpu().numpy() if _is_torch(columns) else columns)
-        if host.dtype.kind not in 'iu' or host.ndim not in (1, 2) or host.size == 0:
-            raise ValueError('column lists must be a non-empty 1-D or 2-D integer array')
-        host = np.ascontiguousarray(host.reshape(1, -1) if host.ndim == 1 else host, dtype=np.int64)
-        if validate and (host.min() < 0 or host.max() >= n_cols or (np.diff(host, axis=1) <= 0).any()):
+            bad = validate and (bool(((t < 0) | (t >= n_cols)).any().item()) or bool((t[:, 1:] <= t[:, :-1]).any().item()))
+        else:
+            t = _to_host(columns)
+            if t.dtype.kind not in 'iu' or t.ndim not in (1, 2) or t.size == 0:
+                raise ValueError('column lists must be a non-empty 1-D or 2-D integer array')
+            t = np.ascontiguousarray(t.reshape(1, -1) if t.ndim == 1 else t, dtype=np.int64)
+            bad = validate and (t.min() < 0 or t.max() >= n_cols or (np.diff(t, axis=1) <= 0).any())
+        if bad:
             raise ValueError('column lists must be in [0, %d) and strictly ascending' % n_cols)
-        return host, None
+        return t
 
-    def _dnc_device_lists(self, columns, n_cols, validate):
-        """(device pointer, n_iters, sub_dim, keepalive)"""
-        host, t = self._dnc_lists(columns, n_cols, validate)
-        if t is not None:
-            return t.data_ptr(), int(t.shape[0]), int(t.shape[1]), t
-        keep = self.to_device(host)
-        return keep.ptr, int(host.shape[0]), int(host.shape[1]), keep
+    def _dnc_operand(self, c, columns, n_cols, validate):
+        return c.operand(self._dnc_lists(columns, n_cols, validate), np.int64, {}, (None, None), convert=False)
 
     def dnc_info(self):
         """(kept_rows, inactive_rows) of the last DnC call on this engine (synchronises)."""
-        kept, inactive = ctypes.c_int64(0), ctypes.c_int64(0)
-        _check(self.lib.byz_dnc_info(self.ctx, ctypes.byref(kept), ctypes.byref(inactive)))
-        return int(kept.value), int(inactive.value)
+        return tuple(self._read(self.lib.byz_dnc_info, [ctypes.c_int64, ctypes.c_int64]))
 
     def dnc_scores(self, g, columns, power_iters=32, validate_columns=True):
         """One DnC iteration's scores for one list of sampled columns: the squared projection of every centred row on the
         top right singular vector of the sampled, centred matrix (power iteration from the row of largest norm), +inf for a
         row with a non-finite sampled value.  fp64: a torch tensor for a torch input, numpy for a host input."""
-        m, stage, host = self._staged(g)
-        ptr, n_iters, b, keep = self._dnc_device_lists(columns, m.cols, validate_columns)
-        if n_iters != 1:
-            raise ValueError('dnc_scores() takes one list of columns')
-        out, optr = self._out_like(m, m.rows, np.float64)
-        _check(self.lib.byz_dnc_scores_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, _vp(ptr), b, int(power_iters), _vp(optr),
-                                           _vp(m.stream)))
-        if host or isinstance(keep, DeviceBuffer):
-            self.synchronize(m.stream)   # staged copies must outlive the kernels
-        return out.numpy() if host else out
+        with _Call(self) as c:
+            m = c.matrix(g)
+            cols = self._dnc_operand(c, columns, m.cols, validate_columns)
+            if cols.rows != 1:
+                raise ValueError('dnc_scores() takes one list of columns')
+            out, optr = c.out(m.rows, np.float64)
+            c.run(self.lib.byz_dnc_scores_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, cols.ptr, cols.cols, int(power_iters), optr,
+                                              c.stream))
+            return c.result(out)
+
+    def _dnc_kept(self, good):
+        """The rows DnC kept, read back: numpy unless they are a torch tensor."""
+        kept, _ = self.dnc_info()
+        return good.numpy()[:kept] if isinstance(good, DeviceBuffer) else good[:kept]
 
     def dnc_select(self, g, remove_count, columns, power_iters=32, validate_columns=True):
         """The rows DnC keeps, ascending: every iteration (one per list of `columns`) ranks the rows by (score, index) and
         removes the `remove_count` highest; the kept sets are intersected.  int32: a torch tensor for a torch input, numpy
         otherwise.  Synchronises (the count is read back)."""
-        m, stage, host = self._staged(g)
-        ptr, n_iters, b, keep = self._dnc_device_lists(columns, m.cols, validate_columns)
-        params = _native.DncParams(n_iters, b, int(power_iters), int(remove_count))
-        good, gptr = self._out_like(m, m.rows, np.int32)
-        _check(self.lib.byz_dnc_select_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, ctypes.byref(params), _vp(ptr), _vp(gptr),
-                                           None, _vp(m.stream)))
-        kept, _ = self.dnc_info()
-        return good.numpy()[:kept] if host or isinstance(good, DeviceBuffer) else good[:kept]
+        with _Call(self) as c:
+            m = c.matrix(g)
+            cols = self._dnc_operand(c, columns, m.cols, validate_columns)
+            params = _native.DncParams(cols.rows, cols.cols, int(power_iters), int(remove_count))
+            good, gptr = c.out(m.rows, np.int32)
+            c.run(self.lib.byz_dnc_select_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, ctypes.byref(params), cols.ptr, gptr, None,
+                                              c.stream))
+            return self._dnc_kept(good)
 
     def dnc(self, g, remove_count, columns, power_iters=32, return_selection=False, validate_columns=True):
         """DnC: np.mean(g[good], axis=0) over the rows every iteration kept (`dnc_select`'s).  `columns`: one ascending list
@@ -1784,28 +1770,23 @@ class Engine:
         if dm is None:
             h = self._host_matrix(g)
             n, d = h.shape
-            cols, t = self._dnc_lists(columns, d, validate_columns)
-            if cols is None:
-                cols = t.cpu().numpy()
+            cols = _to_host(self._dnc_lists(columns, d, validate_columns))
             params = _native.DncParams(cols.shape[0], cols.shape[1], int(power_iters), int(remove_count))
             out = np.empty(d, dtype=np.float32)
             good = np.empty(n, dtype=np.int32)
             kept = ctypes.c_int64(0)
-            _check(self.lib.byz_dnc_host(self.ctx, h.ctypes.data_as(ctypes.c_void_p), n, d, ctypes.byref(params),
-                                         cols.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
-                                         good.ctypes.data_as(ctypes.c_void_p), ctypes.byref(kept)))
+            _check(self.lib.byz_dnc_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(cols), _hp(out), _hp(good),
+                                         ctypes.byref(kept)))
             return (out, good[:kept.value]) if return_selection else out
-        ptr, n_iters, b, keep = self._dnc_device_lists(columns, dm.cols, validate_columns)
-        params = _native.DncParams(n_iters, b, int(power_iters), int(remove_count))
-        out, optr = self._out_like(dm, dm.cols)
-        good, gptr = self._out_like(dm, dm.rows, np.int32) if return_selection else (None, None)
-        _check(self.lib.byz_dnc_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params), _vp(ptr), _vp(optr),
-                                    _vp(gptr), _vp(dm.stream)))
-        self._sync_if_ours(keep, dm.stream)
-        if not return_selection:
-            return out
-        kept, _ = self.dnc_info()
-        return out, (good.numpy()[:kept] if isinstance(good, DeviceBuffer) else good[:kept])
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            cols = self._dnc_operand(c, columns, dm.cols, validate_columns)
+            params = _native.DncParams(cols.rows, cols.cols, int(power_iters), int(remove_count))
+            out, optr = c.out(dm.cols)
+            good, gptr = c.out(dm.rows, np.int32, want=return_selection)
+            c.run(self.lib.byz_dnc_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), cols.ptr, optr, gptr,
+                                       c.stream))
+            return (out, self._dnc_kept(good)) if return_selection else out
 
     def dnc_sharded(self, g_local, remove_count, local_columns, sub_dim, power_iters=32, all_reduce=None,
                     return_selection=False):
@@ -1813,57 +1794,39 @@ class Engine:
         iteration of the sampled columns this rank owns, as indices into its slice (a list may be empty); sub_dim the global
         sample size; all_reduce(tensor) sums a CUDA fp64 tensor in place over the ranks on the current stream (None: one
         rank).  Returns this rank's columns of the mean (and the kept rows, the same on every rank)."""
-        dm = self._device_matrix(g_local)
-        if dm is None:
-            raise ValueError('dnc_sharded() takes a device-resident matrix')
-        lists = [np.ascontiguousarray(np.asarray(c, dtype=np.int64).reshape(-1)) for c in local_columns]
-        for c in lists:
-            if c.size and (c.min() < 0 or c.max() >= dm.cols or (np.diff(c) <= 0).any()):
-                raise ValueError('local column lists must be in [0, %d) and strictly ascending' % dm.cols)
-        counts = (ctypes.c_int64 * len(lists))(*[int(c.size) for c in lists])
-        flat = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
-        keep = self.to_device(flat) if flat.size else None
-        device = self.device
-
-        def reduce_on_ranks(user, buf, count, stream):
-            try:
-                if all_reduce is not None:
-                    import torch
-                    all_reduce(torch.as_tensor(_DeviceF64(buf, count), device='cuda:%d' % device))
-                return 0
-            except Exception:      # noqa: BLE001  (a Python exception must not unwind through the C frames)
-                return 1
-        callback = _native.ALLREDUCE_F64_FN(reduce_on_ranks)
-        params = _native.DncParams(len(lists), int(sub_dim), int(power_iters), int(remove_count))
-        out, optr = self._out_like(dm, dm.cols)
-        good, gptr = self._out_like(dm, dm.rows, np.int32) if return_selection else (None, None)
-        _check(self.lib.byz_dnc_sharded_dev(self.ctx, _vp(dm.ptr), dm.rows, dm.cols, dm.ld, ctypes.byref(params),
-                                            _vp(keep.ptr) if keep is not None else None, counts,
-                                            ctypes.cast(callback, ctypes.c_void_p), None, _vp(optr), _vp(gptr), _vp(dm.stream)))
-        self._sync_if_ours(keep, dm.stream)
-        if not return_selection:
-            return out
-        kept, _ = self.dnc_info()
-        return out, (good.numpy()[:kept] if isinstance(good, DeviceBuffer) else good[:kept])
+        with _Call(self) as c:
+            dm = c.matrix(g_local, needs='dnc_sharded')
+            lists = [np.ascontiguousarray(np.asarray(cl, dtype=np.int64).reshape(-1)) for cl in local_columns]
+            for cl in lists:
+                if cl.size and (cl.min() < 0 or cl.max() >= dm.cols or (np.diff(cl) <= 0).any()):
+                    raise ValueError('local column lists must be in [0, %d) and strictly ascending' % dm.cols)
+            counts = (ctypes.c_int64 * len(lists))(*[int(cl.size) for cl in lists])
+            flat = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+            fptr = c.upload(flat).ptr if flat.size else None
+            callback = self._allreduce_callback(all_reduce)
+            params = _native.DncParams(len(lists), int(sub_dim), int(power_iters), int(remove_count))
+            out, optr = c.out(dm.cols)
+            good, gptr = c.out(dm.rows, np.int32, want=return_selection)
+            c.run(self.lib.byz_dnc_sharded_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), fptr, counts,
+                                               ctypes.cast(callback, ctypes.c_void_p), None, optr, gptr, c.stream))
+            return (out, self._dnc_kept(good)) if return_selection else out
 
     # ---- malicious.py ------------------------------------------------------------------------
     def drift_attack(self, rows, num_std, write_back=False):
         """(drift, mean, std) over the rows; device inputs may be overwritten in place (write_back)."""
-        m = self._device_matrix(rows)
-        if m is None:
+        dm = self._device_matrix(rows)
+        if dm is None:
             g = self._host_matrix(rows)
             n, d = g.shape
             drift, mean, std = (np.empty(d, dtype=np.float32) for _ in range(3))
-            _check(self.lib.byz_drift_attack_host(self.ctx, g.ctypes.data_as(ctypes.c_void_p), n, d, float(num_std),
-                                                  drift.ctypes.data_as(ctypes.c_void_p),
-                                                  mean.ctypes.data_as(ctypes.c_void_p),
-                                                  std.ctypes.data_as(ctypes.c_void_p)))
+            _check(self.lib.byz_drift_attack_host(self.ctx, _hp(g), n, d, float(num_std), _hp(drift), _hp(mean), _hp(std)))
             return drift, mean, std
-        outs = [self._out_like(m, m.cols) for _ in range(3)]
-        _check(self.lib.byz_drift_attack_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, float(num_std),
-                                             _vp(outs[0][1]), _vp(outs[1][1]), _vp(outs[2][1]),
-                                             int(bool(write_back)), _vp(m.stream)))
-        return outs[0][0], outs[1][0], outs[2][0]
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            (drift, dptr), (mean, mptr), (std, sptr) = (c.out(m.cols) for _ in range(3))
+            c.run(self.lib.byz_drift_attack_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, float(num_std), dptr, mptr, sptr,
+                                                int(bool(write_back)), c.stream))
+        return drift, mean, std
 
     def column_chain(self, rows, carry=None, mean=None):
         """One link of the attack's statistics over rows that several owners hold (sharded.py, clients layout): the running
@@ -1872,21 +1835,22 @@ class Engine:
         m = self._device_matrix(rows)
         if m is None or m.torch_like is None:
             raise ValueError('column_chain() takes a torch CUDA matrix')
-        import torch
         for v in (carry, mean):
-            if v is not None and (not _is_torch(v) or v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != m.cols
+            if v is not None and (not _is_torch(v) or v.dtype != _torch().float32 or not v.is_contiguous() or v.numel() != m.cols
                                   or v.device != m.torch_like.device):
                 raise ValueError('carry / mean must be contiguous float32 vectors of %d columns on the matrix\'s device' % m.cols)
-        out = torch.empty(m.cols, dtype=torch.float32, device=m.torch_like.device)
-        _check(self.lib.byz_column_chain_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld,
-                                             _vp(carry.data_ptr() if carry is not None else None),
-                                             _vp(mean.data_ptr() if mean is not None else None), _vp(out.data_ptr()), _vp(m.stream)))
+        with _Call(self) as c:
+            m = c.matrix(m)
+            out, optr = c.out(m.cols)
+            c.run(self.lib.byz_column_chain_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld,
+                                                carry.data_ptr() if carry is not None else None,
+                                                mean.data_ptr() if mean is not None else None, optr, c.stream))
         return out
 
     def column_finish(self, total_rows, num_std, sum=None, sumsq=None, mean=None):
         """The end of a chain.  sum given: returns mean = sum / total_rows.  sumsq (and mean) given: returns (std, drift) =
         (sqrt(sumsq / total_rows), mean - num_std * std)."""
-        import torch
+        torch = _torch()
         if (sum is None) == (sumsq is None):
             raise ValueError('column_finish: give the sum (returns the mean) or the sum of squared deviations (returns std, drift)')
         if sum is None and mean is None:
@@ -1900,86 +1864,54 @@ class Engine:
             if t.numel() != ref.numel() or t.device != ref.device:
                 raise ValueError('column_finish: %s has %d values on %s, expected %d on %s' % (name, t.numel(), t.device, ref.numel(), ref.device))
         n = ref.numel()
-        stream = torch.cuda.current_stream(ref.device).cuda_stream
+        stream = _stream_of(ref)
         if sum is not None:
             mean = torch.empty_like(sum)
-            _check(self.lib.byz_column_finish_dev(self.ctx, _vp(sum.data_ptr()), None, int(total_rows), float(num_std), n,
-                                                  _vp(mean.data_ptr()), None, None, _vp(stream)))
+            _check(self.lib.byz_column_finish_dev(self.ctx, sum.data_ptr(), None, int(total_rows), float(num_std), n,
+                                                  mean.data_ptr(), None, None, stream))
             return mean
         std, drift = torch.empty_like(sumsq), torch.empty_like(sumsq)
-        _check(self.lib.byz_column_finish_dev(self.ctx, None, _vp(sumsq.data_ptr()), int(total_rows), float(num_std), n,
-                                              _vp(mean.data_ptr()), _vp(std.data_ptr()), _vp(drift.data_ptr()), _vp(stream)))
+        _check(self.lib.byz_column_finish_dev(self.ctx, None, sumsq.data_ptr(), int(total_rows), float(num_std), n,
+                                              mean.data_ptr(), std.data_ptr(), drift.data_ptr(), stream))
         return std, drift
 
     def drift_axpy_host(self, mean, std, num_std):
         """DriftAttack._attack_grads on host vectors (malicious.py:34-36), computed on the device."""
         mean_c = np.ascontiguousarray(mean, dtype=np.float32)
         a, b = self.to_device(mean_c), self.to_device(np.ascontiguousarray(std, dtype=np.float32))
-        _check(self.lib.byz_drift_axpy_dev(self.ctx, _vp(a.ptr), _vp(b.ptr), mean_c.size, float(num_std), None))
+        _check(self.lib.byz_drift_axpy_dev(self.ctx, a.ptr, b.ptr, mean_c.size, float(num_std), None))
         return a.numpy()
 
     # ---- server.py:89-90 ---------------------------------------------------------------------
     def server_update(self, weights, velocity, agg, momentum, learning_rate):
         """In-place fused momentum update on device-resident vectors (torch tensors or DeviceBuffers)."""
-        def ptr_of(x):
-            return x.data_ptr() if _is_torch(x) else x.ptr
-        n = weights.numel() if _is_torch(weights) else int(np.prod(weights.shape))
-        stream = None
-        if _is_torch(weights):
-            import torch
-            stream = torch.cuda.current_stream(weights.device).cuda_stream
-        _check(self.lib.byz_server_update_dev(self.ctx, _vp(ptr_of(weights)), _vp(ptr_of(velocity)), _vp(ptr_of(agg)),
-                                              int(n), float(momentum), float(learning_rate), _vp(stream)))
+        with _Call(self) as c:
+            w, v, a = c.as_it_lies(weights), c.as_it_lies(velocity), c.as_it_lies(agg)
+            c.run(self.lib.byz_server_update_dev(self.ctx, w.ptr, v.ptr, a.ptr, w.size, float(momentum), float(learning_rate),
+                                                 c.stream))
 
     # ---- backdoor.py:52-65 (the hook's arithmetic; the training loop stays with the caller) ----
-    def _vectors(self, *vectors):
-        """Same-length fp32 vectors -> (device pointers, n, stream, keepalives, torch example or None).
-        Host vectors (numpy) are uploaded; torch CUDA tensors and DeviceBuffers are used in place."""
-        ptrs, keep, stream, example = [], [], None, None
-        n = None
-        for v in vectors:
-            if isinstance(v, DeviceBuffer):
-                assert v.dtype == np.float32
-                size, ptr = int(np.prod(v.shape)), v.ptr
-            elif _is_torch(v) and v.is_cuda:
-                import torch
-                if v.dtype != torch.float32 or not v.is_contiguous():
-                    raise ValueError('device vectors must be contiguous float32')
-                size, ptr, example = v.numel(), v.data_ptr(), v
-                stream = torch.cuda.current_stream(v.device).cuda_stream
-            else:
-                host = v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v)
-                buf = self.to_device(np.ascontiguousarray(host, dtype=np.float32).ravel())
-                keep.append(buf)
-                size, ptr = int(np.prod(buf.shape)), buf.ptr
-            if n is None:
-                n = size
-            elif size != n:
-                raise ValueError('vector lengths differ: %d and %d' % (n, size))
-            ptrs.append(ptr)
-            keep.append(v)
-        return ptrs, n, stream, keep, example
+    def _vector_rule(self, launch, *vectors):
+        """A rule on same-length float32 vectors: host vectors are uploaded, torch CUDA tensors and DeviceBuffers used in place;
+        numpy out when every vector came from the host, else device-resident."""
+        with _Call(self) as c:
+            ops = [c.operand(vectors[0], np.float32, _f32(None), convert=False, leads=True)]
+            ops += [c.operand(v, np.float32, _DIFFER, ops[0].size, convert=False, leads=True) for v in vectors[1:]]
+            out, optr = c.out(ops[0].size)
+            c.run(launch([op.ptr for op in ops], ops[0].size, optr, c.stream))
+            return c.result(out)
 
     def backdoor_initial_params(self, original_params, grads_mean, learning_rate):
         """original_params - learning_rate * grads_mean (backdoor.py:54).  numpy in -> numpy out;
         device-resident in -> device-resident out."""
-        (p, m), n, stream, keep, example = self._vectors(original_params, grads_mean)
-        out, optr = self._out_like(example, n)
-        _check(self.lib.byz_backdoor_initial_params_dev(self.ctx, _vp(p), _vp(m), n, float(np.float32(learning_rate)),
-                                                        _vp(optr), _vp(stream)))
-        host = example is None and not any(isinstance(v, DeviceBuffer) for v in (original_params, grads_mean))
-        return out.numpy() if host else out
+        return self._vector_rule(lambda p, n, optr, stream: self.lib.byz_backdoor_initial_params_dev(
+            self.ctx, p[0], p[1], n, float(np.float32(learning_rate)), optr, stream), original_params, grads_mean)
 
     def backdoor_clip(self, grads_mean, grads_stdev, original_params, mal_net_params, learning_rate, num_std):
         """The gradient that leads to `mal_net_params`, clipped to mean +- num_std * std (backdoor.py:57-63)."""
-        args = (grads_mean, grads_stdev, original_params, mal_net_params)
-        (m, s, p, q), n, stream, keep, example = self._vectors(*args)
-        out, optr = self._out_like(example, n)
-        _check(self.lib.byz_backdoor_clip_dev(self.ctx, _vp(m), _vp(s), _vp(p), _vp(q), n,
-                                              float(np.float32(learning_rate)), float(np.float32(num_std)),
-                                              _vp(optr), _vp(stream)))
-        host = example is None and not any(isinstance(v, DeviceBuffer) for v in args)
-        return out.numpy() if host else out
+        return self._vector_rule(lambda p, n, optr, stream: self.lib.byz_backdoor_clip_dev(
+            self.ctx, p[0], p[1], p[2], p[3], n, float(np.float32(learning_rate)), float(np.float32(num_std)), optr, stream),
+            grads_mean, grads_stdev, original_params, mal_net_params)
 
     # ---- user.py:92 + server.py:81-83 --------------------------------------------------------------
     def assemble_row(self, g, row, grads):
@@ -1998,8 +1930,8 @@ class Engine:
             sync_after = self._order_after_torch(m, keep)
             table = (ctypes.c_void_p * len(ptrs))(*ptrs)
             lengths = (ctypes.c_int64 * len(lens))(*lens)
-            _check(self.lib.byz_assemble_row_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(row), len(ptrs),
-                                                 table, lengths, _vp(m.stream)))
+            _check(self.lib.byz_assemble_row_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(row), len(ptrs),
+                                                 table, lengths, m.stream))
             if sync_after:
                 self.synchronize(m.stream)
             return
@@ -2007,8 +1939,8 @@ class Engine:
         host = np.ascontiguousarray(host, dtype=np.float32).ravel()
         if host.size != m.cols:
             raise ValueError('the row holds %d values, the gradient %d' % (m.cols, host.size))
-        _check(self.lib.byz_assemble_row_host(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(row),
-                                              host.ctypes.data_as(ctypes.c_void_p), _vp(m.stream)))
+        _check(self.lib.byz_assemble_row_host(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(row),
+                                              _hp(host), m.stream))
         self.synchronize(m.stream)   # `host` may be a temporary
 
     @staticmethod
@@ -2022,7 +1954,7 @@ class Engine:
                 assert t.dtype == np.float32 and (rows is None or t.shape[0] == rows)
                 ptr, size = t.ptr, int(np.prod(t.shape))
             elif _is_torch(t) and t.is_cuda:
-                import torch
+                torch = _torch()
                 if t.dtype != torch.float32 or (rows is not None and t.shape[0] != rows):
                     raise ValueError(not_float32)
                 t = t if t.is_contiguous() else t.contiguous()
@@ -2041,7 +1973,7 @@ class Engine:
         Returns whether the caller must synchronise m.stream after the launch."""
         for t in tensors:
             if _is_torch(t):
-                import torch
+                torch = _torch()
                 current = torch.cuda.current_stream(t.device)
                 if int(current.cuda_stream) != int(m.stream or 0):
                     current.synchronize()
@@ -2067,7 +1999,7 @@ class Engine:
         n_seg = len(clients_grads[0])
         key = None
         if n_seg and _is_torch(clients_grads[0][0]):
-            import torch
+            torch = _torch()
             try:     # C-level chain + map: no Python frame per tensor, no intermediate list
                 first = clients_grads[0]
                 # The table on the device is only valid for THESE tensors: the addresses of all of them, and -- because the
@@ -2084,8 +2016,8 @@ class Engine:
             except (TypeError, AttributeError):
                 key = None      # DeviceBuffers among them: the general path below
         if key is not None and key == self._assemble_key:      # (equal keys: equal tensor counts too)
-            _check(self.lib.byz_assemble_rows_again_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(first_row), n_clients,
-                                                        n_seg, _vp(m.stream)))
+            _check(self.lib.byz_assemble_rows_again_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(first_row), n_clients,
+                                                        n_seg, m.stream))
             return
         self._assemble_key = None
         flat = list(itertools.chain.from_iterable(clients_grads))
@@ -2104,8 +2036,8 @@ class Engine:
         sync_after = self._order_after_torch(m, keep)
         table = (ctypes.c_void_p * len(ptrs))(*ptrs)
         lengths = (ctypes.c_int64 * n_seg)(*lens)
-        _check(self.lib.byz_assemble_rows_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, int(first_row), n_clients, n_seg,
-                                              table, lengths, _vp(m.stream)))
+        _check(self.lib.byz_assemble_rows_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(first_row), n_clients, n_seg,
+                                              table, lengths, m.stream))
         if sync_after:
             self.synchronize(m.stream)
         if key is not None and all(k is t for k, t in zip(keep, flat)):      # (no contiguous temporaries among them)
@@ -2122,8 +2054,8 @@ class Engine:
         sync_after = self._order_after_torch(m, keep)
         table = (ctypes.c_void_p * len(ptrs))(*ptrs)
         lengths = (ctypes.c_int64 * len(lens))(*lens)
-        _check(self.lib.byz_assemble_columns_dev(self.ctx, _vp(m.ptr), m.rows, m.cols, m.ld, len(ptrs), table, lengths,
-                                                 _vp(m.stream)))
+        _check(self.lib.byz_assemble_columns_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, len(ptrs), table, lengths,
+                                                 m.stream))
         if sync_after:
             self.synchronize(m.stream)
 
@@ -2144,7 +2076,7 @@ class Engine:
     def lane_exchange_selftest(self):
         buf = DeviceBuffer(self, (16 * 64,), np.int32)
         n = ctypes.c_int32(0)
-        _check(self.lib.byz_selftest_lane_exchange_dev(self.ctx, _vp(buf.ptr), ctypes.byref(n), None))
+        _check(self.lib.byz_selftest_lane_exchange_dev(self.ctx, buf.ptr, ctypes.byref(n), None))
         self.synchronize()
         return buf.numpy()[: n.value * 64].reshape(n.value, 64)
 
