@@ -57,6 +57,9 @@ class FlameParams(ctypes.Structure):
                 ('round', ctypes.c_uint64), ('column_offset', c_i64)]
 
 
+MANHATTAN_CHAIN = 128             # BYZ_MANHATTAN_CHAIN: the Manhattan matrix's relative error is at most (this + 2) * 2^-24
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -183,6 +186,15 @@ _PROTOTYPES = {
     'byz_flame_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
     'byz_flame_host': [c_vp, c_vp, c_i64, c_i64, _P(FlameParams), c_vp, c_vp, c_vp],
     'byz_flame_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FlameParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_manhattan_distances_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_manhattan_sums_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_manhattan_from_sums_dev': [c_vp, c_vp, c_i64, c_vp, c_vp],
+    'byz_multi_metrics_features_dev': [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
+    'byz_multi_metrics_select_dev': [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_multi_metrics_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
+    'byz_multi_metrics_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_int32), _P(ctypes.c_double)],
+    'byz_multi_metrics_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     'byz_dnc_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp],

@@ -1683,6 +1683,155 @@ int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, d
     return BYZ_OK;
 }
 
+// ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
+namespace {
+
+int check_mm_rows(const char* who, int64_t n) {
+    if (n > kMmMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kMmMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    return BYZ_OK;
+}
+
+int check_mm_keep(const char* who, int64_t n, int64_t keep) {
+    BYZ_TRY(check_mm_rows(who, n));
+    if (n < 1 || keep < 1 || keep > n) {
+        set_error("%s: keep = %lld outside 1..%lld (the row count)", who, (long long)keep, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// the L1 sums of G's rows into the workspace's n x n doubles (with an all-reduce: of the ranks' column slices), then dist
+int manhattan_distances(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, byz_allreduce_f64_fn allreduce, void* user,
+                        float* dist, void* stream) {
+    hipStream_t s = as_stream(stream);
+    double *partial, *sums;
+    BYZ_TRY(manhattan_workspace(ctx, n, n_cols, &partial, &sums));
+    BYZ_TRY(launch_manhattan_sums(ctx, G, n, n_cols, ld, partial, sums, s));
+    if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, sums, n * n, stream, "multi_metrics (L1 sums)"));
+    return launch_manhattan_from_sums(ctx, sums, n, dist, s);
+}
+
+void mm_selected(byz_ctx* ctx, hipStream_t s) {
+    ctx->multi_metrics_stream = s;
+    ctx->multi_metrics_selected = true;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  ONE Gram serves the Euclidean and the cosine matrix: the
+// distances' own path leaves it in ctx->gram untouched (launch_distances_from_gram reads it), and cosine_from_gram reads the
+// same doubles byz_cosine_distances_dev would have computed, launch_gram being deterministic.  Where the Euclidean matrix
+// comes from the small-N kernel, which forms no Gram, the Gram is computed here for the cosine matrix alone -- once, either way.
+// Sharded: the Gram's all-reduce (and the near pairs', when there are any) inside the distances, then the L1 sums'.
+int multi_metrics(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, int64_t keep, byz_allreduce_f64_fn allreduce,
+                  void* user, float* out, int32_t* flags_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    MmScratch t;
+    BYZ_TRY(multi_metrics_workspace(ctx, n, true, &t));
+    BYZ_TRY(ensure_distance_workspaces(ctx, n));
+    mm_selected(ctx, s);
+    float* euc = ctx->dist.as<float>();
+    double* gram = ctx->gram.as<double>();
+    BYZ_TRY(distances(ctx, G, n, n_cols, ld, allreduce, user, euc, stream));
+    if (allreduce == nullptr && krum_small_applies(n, n_cols)) BYZ_TRY(launch_gram(ctx, G, n, n_cols, ld, gram, s));
+    BYZ_TRY(launch_cosine_from_gram(ctx, gram, n, t.cos, s));
+    BYZ_TRY(launch_mm_usable_from_gram(ctx, gram, n, t.usable, s));
+    BYZ_TRY(manhattan_distances(ctx, G, n, n_cols, ld, allreduce, user, t.man, stream));
+    BYZ_TRY(launch_mm_features(ctx, t.man, euc, t.cos, t.usable, n, t.feat, s));
+    BYZ_TRY(launch_mm_select(ctx, t, t.feat, n, keep, flags_out, nullptr, s));
+    // sharded: the selection is the same on every rank; each rank averages its own columns of the chosen rows
+    BYZ_TRY(launch_column_mean_rows_counted(ctx, G, t.rows, t.count, n_cols, ld, out, s));
+    return launch_mm_zero_if_empty(ctx, t.count, n_cols, out, s);
+}
+
+int check_multi_metrics(const char* who, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t keep, const float* out) {
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, who));
+    BYZ_REQUIRE(out, "%s: null output", who);
+    BYZ_TRY(check_mm_keep(who, n_rows, keep));
+    return check_cclip_output(G, n_rows, n_cols, ld, out, who);
+}
+
+}  // namespace
+
+int byz_manhattan_distances_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float* dist, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "manhattan_distances"));
+    BYZ_REQUIRE(dist, "manhattan_distances: null output");
+    BYZ_TRY(check_mm_rows("manhattan_distances", n_rows));
+    return manhattan_distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, dist, stream);
+}
+
+int byz_manhattan_sums_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, double* sums, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "manhattan_sums"));
+    BYZ_REQUIRE(sums, "manhattan_sums: null output");
+    BYZ_TRY(check_mm_rows("manhattan_sums", n_rows));
+    double *partial, *unused;
+    BYZ_TRY(manhattan_workspace(ctx, n_rows, n_cols, &partial, &unused));
+    return launch_manhattan_sums(ctx, G, n_rows, n_cols, ld, partial, sums, as_stream(stream));
+}
+
+int byz_manhattan_from_sums_dev(byz_ctx* ctx, const double* sums, int64_t n_rows, float* dist, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(sums && dist && n_rows > 0, "manhattan_from_sums: null sums or output, or no rows (%lld)", (long long)n_rows);
+    BYZ_TRY(check_mm_rows("manhattan_from_sums", n_rows));
+    return launch_manhattan_from_sums(ctx, sums, n_rows, dist, as_stream(stream));
+}
+
+int byz_multi_metrics_features_dev(byz_ctx* ctx, const float* man, const float* euc, const float* cos, int64_t n_rows, double* features,
+                                   void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(man && euc && cos && features && n_rows > 0, "multi_metrics_features: a null matrix or output, or no rows (%lld)",
+                (long long)n_rows);
+    BYZ_TRY(check_mm_rows("multi_metrics_features", n_rows));
+    MmScratch t;
+    BYZ_TRY(multi_metrics_workspace(ctx, n_rows, false, &t));
+    BYZ_TRY(launch_mm_usable_from_cos(ctx, cos, n_rows, t.usable, as_stream(stream)));
+    return launch_mm_features(ctx, man, euc, cos, t.usable, n_rows, features, as_stream(stream));
+}
+
+int byz_multi_metrics_select_dev(byz_ctx* ctx, const double* features, int64_t n_rows, int64_t keep, int32_t* flags, double* scores,
+                                 void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(features && flags, "multi_metrics_select: null features or output");
+    BYZ_TRY(check_mm_keep("multi_metrics_select", n_rows, keep));
+    MmScratch t;
+    BYZ_TRY(multi_metrics_workspace(ctx, n_rows, false, &t));
+    mm_selected(ctx, as_stream(stream));
+    return launch_mm_select(ctx, t, features, n_rows, keep, flags, scores, as_stream(stream));
+}
+
+int byz_multi_metrics_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t keep, float* out,
+                          int32_t* flags, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_multi_metrics("multi_metrics", G, n_rows, n_cols, ld, keep, out));
+    return multi_metrics(ctx, G, n_rows, n_cols, ld, keep, nullptr, nullptr, out, flags, stream);
+}
+
+int byz_multi_metrics_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t keep,
+                                  byz_allreduce_f64_fn allreduce, void* user, float* out, int32_t* flags, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_multi_metrics("multi_metrics_sharded", G, n_rows, n_cols, ld, keep, out));
+    BYZ_REQUIRE(allreduce, "multi_metrics_sharded: null all-reduce");
+    return multi_metrics(ctx, G, n_rows, n_cols, ld, keep, allreduce, user, out, flags, stream);
+}
+
+int byz_multi_metrics_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* usable_rows, int32_t* degenerate, double* det) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->multi_metrics_selected, "multi_metrics_info: no Multi-Metrics selection on this context yet");
+    BYZ_TRY(check_small(ctx, ctx->multi_metrics_stream));      // synchronises the last call's stream
+    MmInfo info;
+    static_assert(sizeof(MmInfo) == kMmInfoWords * sizeof(int32_t), "whole words");
+    BYZ_TRY(read_i32(ctx, ctx->multi_metrics_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kMmInfoWords,
+                     ctx->multi_metrics_stream));
+    if (kept_rows) *kept_rows = info.kept;
+    if (usable_rows) *usable_rows = info.usable;
+    if (degenerate) *degenerate = info.degenerate;
+    if (det) *det = info.det;
+    return BYZ_OK;
+}
+
 // ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; beyond the reference) ----------------------------
 namespace {
 
@@ -2254,6 +2403,22 @@ int byz_flame_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_
     st.out(&admitted, admitted_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_flame_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, dist, out, admitted, st.stream()));
+    return st.finish();
+}
+
+int byz_multi_metrics_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t keep, float* out_host,
+                           int32_t* flags_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "multi_metrics"));
+    BYZ_REQUIRE(out_host, "multi_metrics: null output");
+    BYZ_TRY(check_mm_keep("multi_metrics", n_rows, keep));
+    HostStage st(ctx);
+    float* out;
+    int32_t* flags;
+    st.out(&out, out_host, n_cols);
+    st.out(&flags, flags_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_multi_metrics_dev(ctx, st.G(), n_rows, n_cols, n_cols, keep, out, flags, st.stream()));
     return st.finish();
 }
 

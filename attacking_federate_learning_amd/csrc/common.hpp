@@ -169,6 +169,12 @@ struct byz_ctx {
                                  // again, and move, between a selection and byz_flame_info
     hipStream_t flame_stream = nullptr;    // stream of the last FLAME selection (byz_flame_info syncs it)
     bool flame_selected = false;           // a selection has written ctx->flame_info
+    byz::Buffer manhattan;       // the Manhattan distances, carved (manhattan.hip: manhattan_workspace): the tile kernel's fp64
+                                 // partials (chunks x n x n), then the n x n sums
+    byz::Buffer multi_metrics;   // Multi-Metrics, carved into MmScratch's arrays (multi_metrics.hip: multi_metrics_workspace)
+    byz::Buffer multi_metrics_info;        // the last selection's scalars (MmInfo), in a buffer of their own, as FLAME's are
+    hipStream_t multi_metrics_stream = nullptr;   // stream of the last Multi-Metrics selection (byz_multi_metrics_info syncs it)
+    bool multi_metrics_selected = false;   // a selection has written ctx->multi_metrics_info
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -470,6 +476,41 @@ int launch_flame_select(byz_ctx* ctx, const FlameScratch& t, const float* dist, 
                         int32_t* admitted_out, hipStream_t stream);
 // t.w[i] = t.admitted[i] ? scales[i] : 0
 int launch_flame_weights(byz_ctx* ctx, const FlameScratch& t, const double* scales, int64_t n, hipStream_t stream);
+// manhattan.hip: the pairwise L1 distances.  sums (n x n fp64, both triangles) = sum_c |g_ic - g_jc| over the columns given,
+// additive over column shards; dist = the sums of the lower triangle rounded once to fp32, the diagonal and every pair whose sum
+// is not finite +inf.  partial: the tile kernel's per-chunk sums (manhattan_workspace carves both).
+constexpr int64_t kManhattanMaxRows = 16384;                      // the `Distances` limit FLAME has
+constexpr int64_t kManhattanPartialBytes = int64_t{512} << 20;    // the column split stops where its partials would pass this
+int manhattan_workspace(byz_ctx* ctx, int64_t n, int64_t d, double** partial, double** sums);
+int launch_manhattan_sums(byz_ctx* ctx, const float* G, int64_t n, int64_t d, int64_t ld, double* partial, double* sums,
+                          hipStream_t stream);
+int launch_manhattan_from_sums(byz_ctx* ctx, const double* sums, int64_t n, float* dist, hipStream_t stream);
+// multi_metrics.hip: Multi-Metrics' features, scores and selection.  The scalars of a call live in ctx->multi_metrics_info:
+struct MmInfo {
+    int32_t kept, usable, degenerate, pad;   // rows chosen = min(usable, keep); rows with three finite features; the fallback ran
+    double det;                              // det R of the features' correlation matrix (0 when fewer than 4 rows are usable)
+};
+constexpr int kMmInfoWords = static_cast<int>(sizeof(MmInfo) / sizeof(int32_t));
+constexpr int64_t kMmMaxRows = 16384;        // the selection's one workgroup owns 1024 x 16 rows
+struct MmScratch {
+    MmInfo* info;
+    float *man, *cos;                        // n x n each: the whole call's Manhattan and cosine matrices
+    double *feat, *scores;                   // n x 3; n
+    int32_t *usable, *flags, *rows, *count;  // n each; the chosen rows ascending; their number (what the mean reads)
+};
+int multi_metrics_workspace(byz_ctx* ctx, int64_t n, bool matrices, MmScratch* out);
+// usable[i] = the Gram's g_ii is finite and > 0 (cosine_distances' notion), or: row i of cos has a finite off-diagonal entry
+int launch_mm_usable_from_gram(byz_ctx* ctx, const double* gram, int64_t n, int32_t* usable, hipStream_t stream);
+int launch_mm_usable_from_cos(byz_ctx* ctx, const float* cos, int64_t n, int32_t* usable, hipStream_t stream);
+// feat[i] = (sum man_ij, sum euc_ij, sum cos_ij) over the usable j != i, in fp64; (inf, inf, inf) for a row that is not usable
+int launch_mm_features(byz_ctx* ctx, const float* man, const float* euc, const float* cos, const int32_t* usable, int64_t n,
+                       double* feat, hipStream_t stream);
+// scores, the min(usable, keep) lowest (score, row) as 0 / 1 flags (t.flags and flags_out, optional), ascending in t.rows, their
+// number in t.count, the scalars into t.info; scores_out optional
+int launch_mm_select(byz_ctx* ctx, const MmScratch& t, const double* feat, int64_t n, int64_t keep, int32_t* flags_out,
+                     double* scores_out, hipStream_t stream);
+// out[c] = 0 for every column when *count_dev == 0 (the counted mean of no rows is 0 / 0)
+int launch_mm_zero_if_empty(byz_ctx* ctx, const int32_t* count_dev, int64_t n_cols, float* out, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

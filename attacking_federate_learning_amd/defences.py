@@ -282,6 +282,28 @@ def flame(users_grads, users_count, corrupted_count, lam=0.001, min_samples=1, m
                               round=round, distances=distances, return_info=return_info)
 
 
+def manhattan_distances(users_grads):
+    """The pairwise Manhattan (L1) distances of the clients' rows as a `Distances` handle resident on the GPU (diagonal
+    +inf, a pair whose sum is not finite +inf): what `multi_metrics` adds to the Euclidean and cosine matrices, and what
+    `krum`, `multi_krum`, `nnm` and `flame` take as `distances=` to run on L1 geometry."""
+    return get_engine().manhattan_distances(users_grads)
+
+
+def multi_metrics(users_grads, users_count, corrupted_count, p=0.3, return_info=False):
+    """Multi-Metrics (Huang et al., ICCV 2023; not in the reference): the backdoor defence beside `flame`, `robust_lr` and
+    `sparsefed`.  Every client is described by its summed Manhattan, Euclidean and cosine distance to the other usable
+    clients (a zero or non-finite client is not usable); the three features are divided by their standard deviations and
+    scored by the squared Mahalanobis norm under their correlation matrix, uncentred, as in the paper; the int(p * n)
+    clients of smallest score (ties to the lower row) are averaged: np.mean(users_grads[chosen], axis=0), bit for bit.
+    Fewer than four usable clients, a constant feature or a singular correlation matrix: the Manhattan feature alone
+    scores.  Nobody usable: the zero vector.  One library call, nothing read by the host.  p = 0.3 is the paper's; p > 1
+    and int(p * n) < 1 are refused.  The reference's leading signature; users_count and corrupted_count are accepted and
+    unused.  numpy in -> numpy out, device-resident in -> device-resident out.  return_info=True returns (vector,
+    {chosen_rows, kept, usable, degenerate, det}).  Not one of the `defend` keys: the reference's main.py offers only those
+    four."""
+    return get_engine().multi_metrics(users_grads, p=p, return_info=return_info)
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

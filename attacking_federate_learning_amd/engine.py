@@ -1702,6 +1702,137 @@ class Engine:
         info['admitted_rows'] = np.flatnonzero(flags).astype(np.int64)
         return out, info
 
+    # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----
+    def manhattan_distances(self, g):
+        """The pairwise MANHATTAN (L1) distances of g's rows as a `Distances` handle, resident on the GPU: m_ij = sum_c
+        |g_ic - g_jc|, fp32 chains of 128 terms folded into fp64 and rounded once to float32 (relative error at most
+        130 * 2^-24); the diagonal is +inf (pairwise_distances' convention), a pair whose sum is not finite is +inf, a zero
+        row is an ordinary row; symmetric bit for bit.  Up to 16,384 rows.  Whatever takes `distances=` takes it."""
+        with _Call(self) as c:
+            m = c.matrix(g)
+            if m.rows > 16384:
+                raise NotImplementedError('manhattan_distances: at most 16384 rows, got %d' % m.rows)
+            dist = DeviceBuffer(self, (m.rows, m.rows), np.float32)
+            c.run(self.lib.byz_manhattan_distances_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, dist.ptr, c.stream))
+            self.check(c.stream)
+        return Distances(dist, m.rows)
+
+    def manhattan_sums(self, g):
+        """manhattan_distances' first half: the n x n fp64 sums over the columns of a device-resident slice (additive over
+        column slices: the columns layout all-reduces them)."""
+        with _Call(self) as c:
+            m = c.matrix(g, needs='manhattan_sums')
+            out, ptr = c.out((m.rows, m.rows), np.float64)
+            c.run(self.lib.byz_manhattan_sums_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, ptr, c.stream))
+        return out
+
+    def manhattan_from_sums(self, sums, n=None, stream=None):
+        """manhattan_distances' second half on (all-reduced) fp64 sums, n x n, on the device -> `Distances`."""
+        n = int(sums.shape[0]) if n is None else int(n)
+        if _is_torch(sums) and (sums.dtype != _torch().float64 or not sums.is_contiguous() or not sums.is_cuda):
+            raise ValueError('the sums must be a contiguous float64 CUDA tensor')
+        with _Call(self, stream) as c:
+            sums = c.as_it_lies(sums)
+            dist = Distances(DeviceBuffer(self, (n, n), np.float32), n)
+            c.run(self.lib.byz_manhattan_from_sums_dev(self.ctx, sums.ptr, n, dist.ptr, c.stream))
+            self.synchronize(c.stream)
+        return dist
+
+    @staticmethod
+    def _multi_metrics_keep(n, p=None, keep=None):
+        """keep = int(p * n), checked as the library checks it (the refusals that need no GPU)."""
+        n = int(n)
+        if n > 16384:
+            raise NotImplementedError('multi_metrics: at most 16384 rows, got %d' % n)
+        if keep is None:
+            p = float(p)
+            if not p <= 1.0:
+                raise ValueError('multi_metrics: p = %r must be at most 1' % p)
+            keep = int(p * n)
+            if keep < 1:
+                raise ValueError('multi_metrics: int(p * n) = %d: p = %r keeps nobody of %d rows' % (keep, p, n))
+        keep = int(keep)
+        if keep < 1 or keep > n:
+            raise ValueError('multi_metrics: keep = %d outside 1..%d (the row count)' % (keep, n))
+        return keep
+
+    def multi_metrics_info(self):
+        """{kept, usable, degenerate, det} of the last multi_metrics_select or multi_metrics on this engine (synchronises): the
+        rows chosen, the rows with three finite features, whether the degenerate rule (the Manhattan feature alone) scored
+        them, and the determinant of the features' correlation matrix."""
+        return dict(zip(('kept', 'usable', 'degenerate', 'det'),
+                        self._read(self.lib.byz_multi_metrics_info, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double])))
+
+    def multi_metrics_features(self, man, euc, cos):
+        """Multi-Metrics' features from three distance matrices (`Distances` handles or dense matrices with an infinite
+        diagonal: Manhattan, Euclidean, cosine -- or any three): an (n, 3) float64 numpy array, row i = the sums of row i of
+        each matrix over the usable j != i, (inf, inf, inf) for a row that is not usable (no finite off-diagonal cosine)."""
+        if any(isinstance(d, dict) for d in (man, euc, cos)):
+            raise ValueError('multi_metrics_features() takes Distances handles or dense matrices')
+        with _Call(self) as c:
+            ds = [c.distances(d)[0] for d in (man, euc, cos)]
+            n = ds[0].n
+            if any(d.n != n for d in ds):
+                raise ValueError('the three distance matrices have %s rows' % ', '.join(str(d.n) for d in ds))
+            self._multi_metrics_keep(n, keep=1)
+            feat = DeviceBuffer(self, (n, 3), np.float64)
+            c.run(self.lib.byz_multi_metrics_features_dev(self.ctx, ds[0].ptr, ds[1].ptr, ds[2].ptr, n, feat.ptr, None))
+            return feat.numpy()
+
+    def multi_metrics_select(self, features, keep, on_device=False, return_scores=False, like=None):
+        """Multi-Metrics' scores and selection on an (n, 3) feature matrix (float64; multi_metrics_features' or the caller's
+        own): the squared Mahalanobis norm of x / s under the features' correlation matrix, uncentred, and the min(usable,
+        keep) rows of smallest (score, row) (include/byzagg.h).  Returns (rows, info) or (rows, scores, info): the chosen
+        rows ascending (on_device=True: the 0 / 1 int32 flags instead, as a DeviceBuffer, or a torch tensor beside `like`),
+        the float64 scores (+inf for a row that is not usable) and {kept, usable, degenerate, det}."""
+        with _Call(self) as c:
+            host = None if _is_device(features) else np.ascontiguousarray(_to_host(features), dtype=np.float64)
+            shape = tuple(features.shape) if host is None else host.shape
+            if len(shape) != 2 or shape[1] != 3:
+                raise ValueError('multi_metrics_select: the features must be (n, 3), got %r' % (shape,))
+            n = int(shape[0])
+            keep = self._multi_metrics_keep(n, keep=keep)
+            f = c.operand(features if host is None else host.reshape(-1), np.float64, _F64, 3 * n)
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            flags, fptr = c.out(n, np.int32)
+            scores, sptr = c.out(n, np.float64, want=return_scores)
+            c.run(self.lib.byz_multi_metrics_select_dev(self.ctx, f.ptr, n, keep, fptr, sptr, None))
+            info = self.multi_metrics_info()
+            rows = flags if on_device else np.flatnonzero(_to_host(flags) if _is_torch(flags) else flags.numpy()).astype(np.int64)
+            if return_scores:
+                scores = _to_host(scores) if _is_torch(scores) else scores.numpy()
+        return (rows, scores, info) if return_scores else (rows, info)
+
+    def multi_metrics(self, g, p=0.3, return_info=False):
+        """Multi-Metrics in one library call: the Manhattan, Euclidean and cosine matrices (one Gram for the last two), the
+        features over the usable rows (Gram diagonal finite and > 0), multi_metrics_select with keep = int(p * n), and
+        np.mean(g[chosen], axis=0) bit for bit.  Nobody usable: the zero vector.  return_info=True also returns {chosen_rows
+        (ascending), kept, usable, degenerate, det}."""
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        keep = self._multi_metrics_keep(n, p=p)
+        with _Call(self) as c:
+            if dm is None:
+                h = self._host_matrix(g)
+                d = h.shape[1]
+                out = np.empty(d, dtype=np.float32)
+                flags = np.zeros(n, dtype=np.int32)
+                _check(self.lib.byz_multi_metrics_host(self.ctx, _hp(h), n, d, keep, _hp(out), _hp(flags)))
+            else:
+                dm = c.matrix(dm)
+                out, optr = c.out(dm.cols)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                c.run(self.lib.byz_multi_metrics_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, keep, optr, fptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    flags = _to_host(flags) if _is_torch(flags) else flags.numpy()
+        if not return_info:
+            return out
+        info = self.multi_metrics_info()
+        info['chosen_rows'] = np.flatnonzero(flags).astype(np.int64)
+        return out, info
+
     # ---- DnC, the spectral defence (Shejwalkar & Houmansadr 2021, Algorithm 2; not in the reference) ----
     def _dnc_lists(self, columns, n_cols, validate=True):
         """columns -> an (n_iters, b) int64 array of column lists: a torch CUDA tensor where it was one, else numpy.  One list

@@ -18,6 +18,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_sparsefed(k, clip, then)   the same step with SparseFed: only the k heaviest coordinates of an error-feedback memory
     defend_weak_dp(clip, sigma, then) the same step with norm clipping and Gaussian noise drawn on the GPU, fresh every round
     defend_flame(lam, min_samples)    the same step with FLAME: the majority cluster by cosine distance, clipped, averaged, noised
+    defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
 reference's own code.
@@ -210,6 +211,16 @@ class DeviceServer:
         current_grads = defences.flame(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), lam=lam,
                                        min_samples=min_samples, seed=seed, round=self.flame_round)
         self.flame_round += 1
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with Multi-Metrics ---------------------------------------------------------------------------
+    def defend_multi_metrics(self, p=0.3):
+        """Multi-Metrics on this round's gradients (defences.multi_metrics): the int(p * n) clients of smallest Mahalanobis
+        score over their summed Manhattan, Euclidean and cosine distances, averaged, and server.py:89-90's momentum step on
+        the result, as `defend` takes it.  Stateless: nothing is carried from round to round."""
+        current_grads = defences.multi_metrics(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), p=p)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

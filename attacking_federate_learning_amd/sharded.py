@@ -163,6 +163,17 @@ class HipKernels:
         # (0 / 1 flags of the admitted rows: an int32 tensor beside `like`; info): the same on every rank
         return self.engine.flame_select(dist, min_samples=min_samples, min_cluster_size=min_cluster_size, on_device=True, like=like)
 
+    def manhattan_sums(self, g_local):
+        return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
+
+    def manhattan_from_sums(self, sums):
+        return self.engine.manhattan_from_sums(sums)           # Distances handle from the all-reduced sums: the same on every rank
+
+    def multi_metrics_select(self, man, euc, cos, keep, like):
+        # (0 / 1 flags of the chosen rows: an int32 tensor beside `like`; info): the same on every rank
+        features = self.engine.multi_metrics_features(man, euc, cos)
+        return self.engine.multi_metrics_select(features, keep, on_device=True, like=like)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -438,6 +449,35 @@ class ShardedAggregator:
             return out
         info = dict(info, clip=float(used.item()), admitted_rows=torch.nonzero(admitted).reshape(-1).cpu().numpy())
         return out, info
+
+    def multi_metrics(self, g_local, users_count, corrupted_count, p=0.3, gather=False, total_columns=None, return_info=False):
+        """Multi-Metrics (defences.multi_metrics' contract), columns layout.  The Gram's all-reduce (shared by the Euclidean
+        and the cosine matrix) and ONE more of n x n doubles: the L1 sums, which are additive over the column slices.
+        Everything after them is replicated -- kernels.manhattan_from_sums, kernels.cosine_from_gram and
+        kernels.multi_metrics_select give the same flags on every rank -- or local to the columns: the mean of the chosen
+        rows.  Returns this rank's columns (gather=True: the whole vector)."""
+        import torch
+        from .engine import Engine
+        n = g_local.shape[0]
+        keep = Engine._multi_metrics_keep(n, p=p)             # (a rank-local argument error: before any collective)
+        gram = self.kernels.gram(g_local)
+        self._all_reduce('allreduce_multi_metrics_gram', gram)
+        reduce_pairs = (lambda t: self._all_reduce('allreduce_near_pairs', t)) if self._collective() else None
+        euc = self.kernels.distances_from_gram(gram, local_columns=g_local, all_reduce=reduce_pairs)
+        cos = self.kernels.cosine_from_gram(gram)
+        sums = self.kernels.manhattan_sums(g_local)
+        self._all_reduce('allreduce_multi_metrics_l1', sums)
+        man = self.kernels.manhattan_from_sums(sums)
+        flags, info = self.kernels.multi_metrics_select(man, euc, cos, keep, g_local)
+        chosen = torch.nonzero(flags).reshape(-1).to(torch.int32)
+        if chosen.numel() == 0:
+            v = torch.zeros(g_local.shape[1], dtype=torch.float32, device=g_local.device)
+        else:
+            v = self.kernels.mean_rows(g_local, chosen)
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, dict(info, chosen_rows=chosen.cpu().numpy().astype(np.int64))
 
     def krum(self, g_local, users_count, corrupted_count, return_index=False, gather=False, total_columns=None):
         if not return_index:

@@ -714,6 +714,61 @@ int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, d
 int byz_flame_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_flame_params* params,
                    const float* dist_host_or_null, float* out_host, int32_t* admitted_host_or_null);
 
+/* ---- Multi-Metrics (Huang, Li, Wang, Chen, Zhang & Li, "Multi-metrics adaptively identifies backdoors in Federated Learning",  */
+/* ICCV 2023; not in the reference) ----                                                                                           */
+/* The fourth backdoor defence beside FLAME, robust_lr and sparsefed: L2 and cosine distances lose contrast in high dimensions,   */
+/* the L1 distance keeps it.  Every client is described by its summed Manhattan, Euclidean and cosine distance to the others; the */
+/* three features are whitened by their own covariance; the keep clients of smallest squared Mahalanobis norm are averaged.       */
+/* The Manhattan matrix, which no Gram gives: m_ij = sum_c |g_ic - g_jc|, computed on the vector pipe in fp32 chains of at most   */
+/* BYZ_MANHATTAN_CHAIN terms folded into fp64, rounded once to fp32.  Worst-case relative error (BYZ_MANHATTAN_CHAIN + 2) * 2^-24 */
+/* = 7.75e-6.  The diagonal is +inf (byz_pairwise_distances_dev's convention); a pair whose sum is not finite -- a NaN or an      */
+/* infinity in either row, or overflow -- is +inf; a zero row is an ordinary row.  Symmetric bit for bit.  Chains are assigned by  */
+/* column index: the same matrix behind another ld or a moved base pointer, or a second run, gives the same bits.  n up to 16,384  */
+/* (BYZ_E_UNSUPPORTED beyond, nothing written).  Any entry that takes a distance matrix (byz_krum_select_dev,                      */
+/* byz_multi_krum_select_dev, byz_nnm_neighbours_dev, byz_flame_select_dev) takes this one.                                        */
+#define BYZ_MANHATTAN_CHAIN 128
+int byz_manhattan_distances_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, float* dist_dev,
+                                void* stream);
+/* The two halves, for a host of the columns layout: the L1 sums of a column slice (n x n fp64, both triangles) are ADDITIVE over  */
+/* the slices; after the all-reduce the second half rounds the lower triangle's sums once and mirrors them.                        */
+int byz_manhattan_sums_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, double* sums_dev,
+                           void* stream);
+int byz_manhattan_from_sums_dev(byz_ctx* ctx, const double* sums_dev, int64_t n_rows, float* dist_dev, void* stream);
+/* The features, in fp64, from three n x n matrices in byz_pairwise_distances_dev's form (Manhattan, Euclidean, cosine; a caller   */
+/* may pass any three): row i is USABLE when row i of cos_dev has a finite off-diagonal entry -- with byz_cosine_distances_dev's  */
+/* matrix: g_ii finite and > 0, as long as two rows are usable.  features_dev[3 i ..] = (sum m_ij, sum e_ij, sum c_ij) over the   */
+/* usable j != i, added in ascending j in 256 interleaved chains that meet in a fixed tree; (inf, inf, inf) for a row that is not  */
+/* usable.                                                                                                                         */
+int byz_multi_metrics_features_dev(byz_ctx* ctx, const float* man_dev, const float* euc_dev, const float* cos_dev, int64_t n_rows,
+                                   double* features_dev, void* stream);
+/* The selection on ANY n x 3 feature matrix (fp64): U = the rows whose three features are finite, u = |U|.  With y = x - x_first  */
+/* (the first usable row's features: the variance does not see the shift, and a constant feature's deviation is exactly 0):       */
+/*   s_k = the sample standard deviation (ddof = 1) of feature k, R = the features' correlation matrix (the covariance of x / s),  */
+/*   score_i = z_i^T R^-1 z_i with z_i = x_i / s -- the paper's squared Mahalanobis norm, uncentred, computed through the         */
+/*   correlation matrix so that the features' scales do not enter the conditioning; R^-1 = adj R / det R in closed form.           */
+/* DEGENERATE -- u < 4, an s_k that is zero or not finite, det R <= 1e-12 -- score_i = x_i0, the Manhattan feature.  A row outside */
+/* U scores +inf and is never chosen.  Chosen: the min(u, keep) smallest by (score ascending, row ascending; a NaN last).          */
+/* flags_dev: n_rows int32 of 0 / 1; scores_dev_or_null: n_rows doubles.  1 <= keep <= n_rows (BYZ_E_INVALID otherwise), n_rows    */
+/* up to 16,384 (BYZ_E_UNSUPPORTED beyond); nothing is written when a call is refused.  Asynchronous on `stream`.                  */
+int byz_multi_metrics_select_dev(byz_ctx* ctx, const double* features_dev, int64_t n_rows, int64_t keep, int32_t* flags_dev,
+                                 double* scores_dev_or_null, void* stream);
+/* The whole defence: byz_pairwise_distances_dev, byz_cosine_distances_dev and byz_manhattan_distances_dev's matrices (ONE Gram    */
+/* serves the first two, their bits unchanged), the features with U = the rows whose g_ii is finite and > 0, the selection, then   */
+/* out_dev = byz_mean_rows_dev over the chosen rows ascending: np.mean(G[chosen], axis = 0) bit for bit.  Nobody usable: the zero  */
+/* vector.  flags_dev_or_null: n_rows int32 of 0 / 1.  Nothing here synchronises with the host and byz_multi_metrics_info is the   */
+/* call that reads anything back; the one wait is the Gram's own duplicate-row search, as in byz_flame_dev.  out_dev must not      */
+/* overlap G (BYZ_E_INVALID).  Timers: BYZ_K_DISTANCES: the L1 tile kernel, its reduction and the two conversions;                 */
+/* BYZ_K_ROW_SORT: the ranking and the compaction; BYZ_K_MISC: the usable flags, the features and the scores.                      */
+int byz_multi_metrics_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t keep, float* out_dev,
+                          int32_t* flags_dev_or_null, void* stream);
+/* The last byz_multi_metrics_select_dev or byz_multi_metrics_dev on this context: the rows chosen (min(u, keep)), the usable      */
+/* rows u, whether the degenerate rule scored them, and det R (0 when it was never formed).  Synchronises that call's stream.      */
+/* BYZ_E_INVALID before the first such call.                                                                                       */
+int byz_multi_metrics_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* usable_rows, int32_t* degenerate, double* det);
+/* The same on a host matrix (out_host: n_cols floats; flags_host_or_null: n_rows int32).  Synchronous.                            */
+int byz_multi_metrics_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t keep, float* out_host,
+                           int32_t* flags_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -887,6 +942,14 @@ int byz_topk_sparsify_sharded_dev(byz_ctx* ctx, const float* x_local_dev, const 
 int byz_flame_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
                           const byz_flame_params* params, byz_allreduce_f64_fn allreduce, void* user,
                           const float* dist_dev_or_null, float* out_local_dev, int32_t* admitted_dev_or_null, void* stream);
+/* Multi-Metrics over the ranks' column slices: the L1 sums are additive over the slices, so beside the Gram's all-reduce (and the  */
+/* near-duplicate pairs', when there are any) there is ONE more of n x n doubles, issued after it.  The features, the scores and   */
+/* the selection are replicated; the final mean is local to the columns.  The ranks' outputs concatenate to                        */
+/* byz_multi_metrics_dev's vector up to the fp64 rounding of the all-reduced sums.  A rank-local argument error returns before any */
+/* collective.                                                                                                                     */
+int byz_multi_metrics_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                                  int64_t keep, byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
+                                  int32_t* flags_dev_or_null, void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
