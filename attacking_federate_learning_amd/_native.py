@@ -60,6 +60,11 @@ class FlameParams(ctypes.Structure):
 MANHATTAN_CHAIN = 128             # BYZ_MANHATTAN_CHAIN: the Manhattan matrix's relative error is at most (this + 2) * 2^-24
 
 
+class ClippedClusteringParams(ctypes.Structure):
+    """byz_clipped_clustering_params: the fixed clip, the adaptive switch (the median norm), the linkage and its fill."""
+    _fields_ = [('clip', ctypes.c_double), ('adaptive', ctypes.c_int32), ('method', ctypes.c_int32), ('fill', ctypes.c_double)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -194,6 +199,15 @@ _PROTOTYPES = {
     'byz_multi_metrics_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_multi_metrics_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_int32), _P(ctypes.c_double)],
     'byz_multi_metrics_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
+    'byz_linkage_dev': [c_vp, c_vp, c_i64, c_int, _P(ctypes.c_double), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_linkage_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64)],
+    'byz_linkage_cut_dev': [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'byz_clipped_clustering_select_dev': [c_vp, c_vp, c_i64, c_int, _P(ctypes.c_double), c_vp, c_vp],
+    'byz_clipped_clustering_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(ClippedClusteringParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_clipped_clustering_info': [c_vp, _P(c_i64), _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)],
+    'byz_clipped_clustering_host': [c_vp, c_vp, c_i64, c_i64, _P(ClippedClusteringParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_clipped_clustering_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(ClippedClusteringParams), c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp],
     'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],

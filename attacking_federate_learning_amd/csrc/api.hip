@@ -2,6 +2,7 @@
 // workspace management, and the composition of the kernels into the reference's functions.
 #include "common.hpp"
 
+#include <cmath>
 #include <cstring>
 
 namespace byz {
@@ -1683,6 +1684,163 @@ int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, d
     return BYZ_OK;
 }
 
+// ---- Agglomerative clustering and ClippedClustering (Li, Ngai & Voigt 2023; beyond the reference) ---------------------------------
+namespace {
+
+int check_linkage(const char* who, int64_t n, int method, const double* fill) {
+    BYZ_TRY(check_flame_rows(who, n));
+    if (n < 2) {
+        set_error("%s: at least 2 rows, got %lld", who, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (method != BYZ_LINKAGE_AVERAGE && method != BYZ_LINKAGE_COMPLETE && method != BYZ_LINKAGE_SINGLE) {
+        set_error("%s: method = %d is none of average (0), complete (1), single (2)", who, method);
+        return BYZ_E_INVALID;
+    }
+    if (!fill || !std::isfinite(*fill) || !(*fill >= 0.0)) {
+        set_error("%s: fill = %g must be finite and >= 0", who, fill ? *fill : 0.0);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+int check_clipped_clustering(const char* who, const byz_clipped_clustering_params* params, int64_t n_rows) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!params->adaptive && !(params->clip > 0.0)) {      // (a NaN fails; +inf passes, as weak DP's clip)
+        set_error("%s: clip = %g must be > 0 in the fixed mode", who, params->clip);
+        return BYZ_E_INVALID;
+    }
+    return check_linkage(who, n_rows, params->method, &params->fill);
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  It waits where flame() waits: inside the Gram's duplicate
+// search, and nowhere when the caller passes the distances.
+int clipped_clustering(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, const byz_clipped_clustering_params* params,
+                       byz_allreduce_f64_fn allreduce, void* user, const float* dist_in, const double* sq_in, float* out,
+                       int32_t* admitted_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    LinkageScratch f;
+    BYZ_TRY(linkage_workspace(ctx, n, &f));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
+    double* scale = t.b;
+    ctx->linkage_stream = s;
+    ctx->linkage_ran = true;
+    ctx->clipped_clustering_selected = true;
+    ctx->weak_dp_stream = s;
+    const float* dist = dist_in;
+    if (dist == nullptr) {
+        BYZ_TRY(ctx->dist.ensure(static_cast<size_t>(n) * n * sizeof(float)));
+        BYZ_TRY(cosine_distances(ctx, G, n, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
+        dist = ctx->dist.as<float>();
+    }
+    BYZ_TRY(launch_clipped_clustering_select(ctx, f, dist, n, params->method, params->fill, admitted_out, s));
+    BYZ_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(n_cols) * sizeof(float), s));
+    const double* sq = sq_in;
+    if (sq == nullptr) {
+        BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, t.a, nullptr, nullptr, s));
+        if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.a, n, stream, "clipped_clustering (norms)"));
+        sq = t.a;
+    }
+    BYZ_TRY(launch_clip_scales(ctx, sq, n, params->clip, params->adaptive != 0, scale, &f.info->clip, s));
+    FlameScratch weights{};                                   // (flame_weights_kernel reads the flags and writes the weights)
+    weights.admitted = f.admitted;
+    weights.w = f.w;
+    BYZ_TRY(launch_flame_weights(ctx, weights, scale, n, s));
+    return launch_scaled_rows_sum(ctx, G, n, n_cols, ld, f.w, &f.info->admitted_f64, out, s);
+}
+
+}  // namespace
+
+int byz_linkage_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int method, const double* fill, int32_t* pair, double* height,
+                    int32_t* size, int32_t* usable_rows, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && pair && height && size, "linkage: null distances or output");
+    BYZ_TRY(check_linkage("linkage", n_rows, method, fill));
+    LinkageScratch f;
+    BYZ_TRY(linkage_workspace(ctx, n_rows, &f));
+    ctx->linkage_stream = as_stream(stream);
+    ctx->linkage_ran = true;
+    return launch_linkage(ctx, f, dist, n_rows, method, *fill, pair, height, size, usable_rows, ctx->linkage_stream);
+}
+
+int byz_linkage_info(byz_ctx* ctx, int64_t* merges, int64_t* rescans, int64_t* max_rescans) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->linkage_ran, "linkage_info: no linkage on this context yet");
+    BYZ_TRY(check_small(ctx, ctx->linkage_stream));          // synchronises the last call's stream
+    LinkageInfo info;
+    static_assert(sizeof(LinkageInfo) == kLinkageInfoWords * sizeof(int32_t), "whole words");
+    BYZ_TRY(read_i32(ctx, ctx->linkage_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kLinkageInfoWords, ctx->linkage_stream));
+    if (merges) *merges = info.steps;
+    if (rescans) *rescans = info.rescans;
+    if (max_rescans) *max_rescans = info.max_rescans;
+    return BYZ_OK;
+}
+
+int byz_linkage_cut_dev(byz_ctx* ctx, const int32_t* pair, int64_t n_rows, const int32_t* usable_rows, int64_t n_clusters,
+                        int32_t* labels, int32_t* cluster_sizes, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(pair && usable_rows && labels && cluster_sizes, "linkage_cut: null merges, flags or output");
+    BYZ_TRY(check_flame_rows("linkage_cut", n_rows));
+    BYZ_REQUIRE(n_rows >= 2 && n_clusters >= 1 && n_clusters <= n_rows, "linkage_cut: %lld clusters of %lld rows (at least 2 rows, 1..n clusters)",
+                (long long)n_clusters, (long long)n_rows);
+    return launch_linkage_cut(ctx, pair, n_rows, usable_rows, n_clusters, labels, cluster_sizes, as_stream(stream));
+}
+
+int byz_clipped_clustering_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int method, const double* fill,
+                                      int32_t* admitted, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && admitted, "clipped_clustering_select: null distances or output");
+    BYZ_TRY(check_linkage("clipped_clustering_select", n_rows, method, fill));
+    LinkageScratch f;
+    BYZ_TRY(linkage_workspace(ctx, n_rows, &f));
+    ctx->linkage_stream = as_stream(stream);
+    ctx->linkage_ran = true;
+    ctx->clipped_clustering_selected = true;
+    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), ctx->linkage_stream));
+    return launch_clipped_clustering_select(ctx, f, dist, n_rows, method, *fill, admitted, ctx->linkage_stream);
+}
+
+int byz_clipped_clustering_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                               const byz_clipped_clustering_params* params, const float* dist, const double* sq, float* out,
+                               int32_t* admitted, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "clipped_clustering"));
+    BYZ_REQUIRE(out, "clipped_clustering: null output");
+    BYZ_TRY(check_clipped_clustering("clipped_clustering", params, n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "clipped_clustering"));
+    return clipped_clustering(ctx, G, n_rows, n_cols, ld, params, nullptr, nullptr, dist, sq, out, admitted, stream);
+}
+
+int byz_clipped_clustering_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                       const byz_clipped_clustering_params* params, byz_allreduce_f64_fn allreduce, void* user,
+                                       const float* dist, float* out, int32_t* admitted, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "clipped_clustering_sharded"));
+    BYZ_REQUIRE(out && allreduce, "clipped_clustering_sharded: null output or null all-reduce");
+    BYZ_TRY(check_clipped_clustering("clipped_clustering_sharded", params, n_rows));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "clipped_clustering_sharded"));
+    return clipped_clustering(ctx, G, n_rows, n_cols, ld, params, allreduce, user, dist, nullptr, out, admitted, stream);
+}
+
+int byz_clipped_clustering_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* usable_rows, double* top_height, double* second_height,
+                                double* clip) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->clipped_clustering_selected, "clipped_clustering_info: no ClippedClustering selection on this context yet");
+    BYZ_TRY(check_small(ctx, ctx->linkage_stream));          // synchronises the last call's stream
+    LinkageInfo info;
+    BYZ_TRY(read_i32(ctx, ctx->linkage_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kLinkageInfoWords, ctx->linkage_stream));
+    if (admitted_rows) *admitted_rows = info.admitted;
+    if (usable_rows) *usable_rows = info.usable;
+    if (top_height) *top_height = info.top_height;
+    if (second_height) *second_height = info.second_height;
+    if (clip) *clip = info.clip;
+    return BYZ_OK;
+}
+
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
@@ -2403,6 +2561,26 @@ int byz_flame_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_
     st.out(&admitted, admitted_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_flame_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, dist, out, admitted, st.stream()));
+    return st.finish();
+}
+
+int byz_clipped_clustering_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                                const byz_clipped_clustering_params* params, const float* dist_host, const double* sq_host,
+                                float* out_host, int32_t* admitted_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "clipped_clustering"));
+    BYZ_REQUIRE(out_host, "clipped_clustering: null output");
+    BYZ_TRY(check_clipped_clustering("clipped_clustering", params, n_rows));
+    HostStage st(ctx);
+    float *out, *dist;
+    double* sq;
+    int32_t* admitted;
+    st.out(&out, out_host, n_cols);
+    st.in(&dist, dist_host, n_rows * n_rows);
+    st.in(&sq, sq_host, n_rows);
+    st.out(&admitted, admitted_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_clipped_clustering_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, dist, sq, out, admitted, st.stream()));
     return st.finish();
 }
 

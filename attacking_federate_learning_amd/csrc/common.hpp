@@ -175,6 +175,12 @@ struct byz_ctx {
     byz::Buffer multi_metrics_info;        // the last selection's scalars (MmInfo), in a buffer of their own, as FLAME's are
     hipStream_t multi_metrics_stream = nullptr;   // stream of the last Multi-Metrics selection (byz_multi_metrics_info syncs it)
     bool multi_metrics_selected = false;   // a selection has written ctx->multi_metrics_info
+    byz::Buffer linkage;         // agglomerative clustering, carved into LinkageScratch's arrays (linkage.hip: linkage_workspace): the fp64
+                                 // working matrix (n x n), the first nearest partners, the merges, the labels, the flags, the weights
+    byz::Buffer linkage_info;    // the last linkage's and selection's scalars (LinkageInfo), in a buffer of their own, as FLAME's are
+    hipStream_t linkage_stream = nullptr;  // stream of the last linkage or ClippedClustering call (the two info calls sync it)
+    bool linkage_ran = false;              // a linkage has written ctx->linkage_info
+    bool clipped_clustering_selected = false;   // a ClippedClustering selection has written it as well
     // large_rows.hip: more than 16,384 rows
     byz::Buffer large_keys;      // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
@@ -511,6 +517,35 @@ int launch_mm_select(byz_ctx* ctx, const MmScratch& t, const double* feat, int64
                      double* scores_out, hipStream_t stream);
 // out[c] = 0 for every column when *count_dev == 0 (the counted mean of no rows is 0 / 0)
 int launch_mm_zero_if_empty(byz_ctx* ctx, const int32_t* count_dev, int64_t n_cols, float* out, hipStream_t stream);
+// linkage.hip: agglomerative clustering and ClippedClustering's selection.  The scalars of a call live in ctx->linkage_info:
+struct LinkageInfo {
+    int32_t admitted, usable;        // ClippedClustering: the rows admitted; the rows with a finite off-diagonal distance
+    int32_t steps, rescans;          // the last linkage: its merges; the nearest-partner caches it rebuilt from a row of W
+    int32_t max_rescans, pad;        // the most of them in one step
+    double top_height, second_height;        // the last merge's height and the one before (0 where there is none)
+    double admitted_f64;             // the divisor of the sum
+    double clip;                     // byz_clipped_clustering_dev: the clip used
+};
+constexpr int kLinkageInfoWords = static_cast<int>(sizeof(LinkageInfo) / sizeof(int32_t));
+struct LinkageScratch {
+    LinkageInfo* info;
+    double* W;                       // n x n: the working matrix
+    unsigned long long* near_d;      // n: the bits of every row's smallest distance before the first merge
+    int32_t *near_p, *usable, *pair, *size, *labels, *cluster_sizes, *admitted;   // its column; n flags; the merges (2 n; n); the
+                                     // 2-cut's labels (n) and sizes (2); n flags
+    double *height, *w;              // n: the merges' heights; the sum's weights
+};
+int linkage_workspace(byz_ctx* ctx, int64_t n, LinkageScratch* out);
+// the u - 1 merges of the usable rows into pair (2 (n - 1)), height and size (n - 1 each; -1, +inf and 0 behind the merges);
+// t.usable (and usable_out, optional): the n flags; the step and rescan counts into t.info
+int launch_linkage(byz_ctx* ctx, const LinkageScratch& t, const float* dist, int64_t n, int method, double fill, int32_t* pair,
+                   double* height, int32_t* size, int32_t* usable_out, hipStream_t stream);
+// the first u - n_clusters merges replayed: labels (n; -1: not usable) numbered by lowest row, cluster_sizes (n_clusters)
+int launch_linkage_cut(byz_ctx* ctx, const int32_t* pair, int64_t n, const int32_t* usable, int64_t n_clusters, int32_t* labels,
+                       int32_t* cluster_sizes, hipStream_t stream);
+// linkage, 2-cut, the larger cluster: t.admitted (and admitted_out, optional), the scalars into t.info
+int launch_clipped_clustering_select(byz_ctx* ctx, const LinkageScratch& t, const float* dist, int64_t n, int method, double fill,
+                                     int32_t* admitted_out, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

@@ -14,6 +14,8 @@ Differences a caller can observe, all documented in DESIGN.md:
   * `_krum_create_distances` returns a `Distances` handle (GPU-resident N x N matrix) instead of a dict
     of dicts; `krum(..., distances=handle)` accepts it, `handle.to_dict()` rebuilds the reference's form.
 """
+import numpy as np
+
 from .engine import (DeviceBuffer, Distances, bucketing_permutation, dnc_columns, get_engine,  # noqa: F401
                      signguard_sample, signguard_window)
 
@@ -302,6 +304,56 @@ def multi_metrics(users_grads, users_count, corrupted_count, p=0.3, return_info=
     {chosen_rows, kept, usable, degenerate, det}).  Not one of the `defend` keys: the reference's main.py offers only those
     four."""
     return get_engine().multi_metrics(users_grads, p=p, return_info=return_info)
+
+
+def linkage_labels(distances, n_clusters=2, method='average', fill=2.0):
+    """Agglomerative clustering of a distance matrix (a `Distances` handle -- cosine_distances, _krum_create_distances,
+    manhattan_distances -- or a dense symmetric matrix, the diagonal ignored) cut into `n_clusters`, on the GPU: int32 labels,
+    the clusters numbered by their lowest row in ascending order, -1 for a row without a finite off-diagonal distance, which
+    takes no part.  method: 'average', 'complete' or 'single'; an entry that is not finite or is negative counts as `fill`.
+    Engine.linkage returns the whole dendrogram in scipy's format."""
+    engine = get_engine()
+    pair, _, _, usable = engine.linkage_merges(distances, method=method, fill=fill)
+    return engine.linkage_cut(pair, usable, n_clusters)[0]
+
+
+def clipped_clustering(users_grads, users_count, corrupted_count, clip=None, method='average', distances=None, norm_history=None,
+                       max_tau=1e5, return_info=False):
+    """ClippedClustering (Li, Ngai and Voigt, IEEE Trans. Big Data 2023; Blades' `Clippedclustering`; not in the reference):
+    every client clipped to the median norm, pairwise cosine distances, agglomerative clustering with average linkage cut
+    into two clusters, the mean of the larger one.  Scaling a row by a positive number does not change its cosines, so the
+    cosine stage runs on the UNCLIPPED rows (Blades clips first: the same distances).  Distances that are not finite count
+    as 2.0, the largest cosine distance, as in Blades; a zero or non-finite client takes no part.  Equal cluster sizes: the
+    cluster of the lowest usable row is admitted (Blades' tie goes to scikit-learn's label 0, which is not a property of
+    the data).  With two or more usable clients the two-way cut ALWAYS rejects somebody: the rule never returns the plain
+    clipped mean.  One usable client: it alone; none: the zero vector.
+    clip=None is the adaptive mode, the median of this round's finite norms: one library call, nothing read by the host.
+    clip > 0 is a fixed threshold.  norm_history, a Python list, is the paper's running threshold (Blades' `l2norm_his`):
+    the call appends this round's n norms to it IN PLACE and clips to min(np.median of its finite entries, max_tau); the
+    norms are read back for that, which is ONE synchronisation, and are handed to the library so that it does not compute
+    them again.  method: 'average' (the paper's), 'complete' or 'single'.  `distances=` (a `Distances` handle or a dense
+    matrix) replaces the cosine stage.  The reference's leading signature; users_count and corrupted_count are accepted and
+    unused.  numpy in -> numpy out, device-resident in -> device-resident out.  return_info=True returns (vector,
+    {admitted_rows, admitted, usable, top_height, second_height, clip}).  Not one of the `defend` keys: the reference's
+    main.py offers only those four."""
+    engine = get_engine()
+    if norm_history is None:
+        return engine.clipped_clustering(users_grads, clip=clip, method=method, distances=distances, return_info=return_info)
+    if clip is not None:
+        raise ValueError('clipped_clustering: norm_history sets the clip; pass clip=None with it')
+    matrix, was_host = engine.stage(users_grads)
+    sq = engine.row_sqdist(matrix, np.zeros(matrix.shape[1], dtype=np.float32))
+    norms = np.sqrt(sq.numpy() if isinstance(sq, DeviceBuffer) else sq.detach().cpu().numpy())
+    norm_history.extend(float(v) for v in norms)
+    history = np.asarray(norm_history, dtype=np.float64)
+    history = history[np.isfinite(history)]
+    threshold = min(float(np.median(history)), float(max_tau)) if history.size else 0.0
+    if not threshold > 0.0:
+        threshold = float(np.finfo(np.float64).tiny)        # (every norm 0 so far: nothing to clip to, every scale next to 0)
+    got = engine.clipped_clustering(matrix, clip=threshold, method=method, distances=distances, sq=sq, return_info=return_info)
+    if not was_host:
+        return got
+    return (got[0].numpy(), got[1]) if return_info else got.numpy()
 
 
 def coordinate_median(users_grads, users_count, corrupted_count):

@@ -1702,6 +1702,164 @@ class Engine:
         info['admitted_rows'] = np.flatnonzero(flags).astype(np.int64)
         return out, info
 
+    # ---- agglomerative clustering and ClippedClustering (Li, Ngai & Voigt 2023; not in the reference) ----
+    _LINKAGE_METHODS = {'average': 0, 'complete': 1, 'single': 2}
+
+    @classmethod
+    def _linkage_args(cls, n, method, fill):
+        """(method code, fill) checked as the library checks them (the refusals that need no GPU)."""
+        n, fill = int(n), float(fill)
+        if n > 16384:
+            raise NotImplementedError('linkage: at most 16384 rows, got %d' % n)
+        if n < 2:
+            raise ValueError('linkage: at least 2 rows, got %d' % n)
+        if method not in cls._LINKAGE_METHODS:
+            raise ValueError('linkage: method = %r is none of %s' % (method, ', '.join(sorted(cls._LINKAGE_METHODS))))
+        if not (np.isfinite(fill) and fill >= 0.0):
+            raise ValueError('linkage: fill = %r must be finite and >= 0' % fill)
+        return cls._LINKAGE_METHODS[method], fill
+
+    def linkage_info(self):
+        """{merges, rescans, max_rescans} of the last linkage on this engine, ClippedClustering's included (synchronises): the
+        steps, the nearest-partner caches rebuilt from a row of the working matrix, and the most of them in one step."""
+        return dict(zip(('merges', 'rescans', 'max_rescans'),
+                        self._read(self.lib.byz_linkage_info, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64])))
+
+    def linkage_merges(self, distances, method='average', fill=2.0):
+        """The device's merges as they are (include/byzagg.h): (pair (u - 1, 2) int32 slots a < b, height (u - 1) float64,
+        size (u - 1) int32, usable (n) bool) for the u usable rows of a `Distances` handle or a dense symmetric matrix."""
+        if isinstance(distances, dict):
+            raise ValueError('linkage() takes a Distances handle or a dense matrix')
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            code, fill = self._linkage_args(d.n, method, fill)
+            pair = DeviceBuffer(self, (d.n - 1, 2), np.int32)
+            height = DeviceBuffer(self, (d.n - 1,), np.float64)
+            size = DeviceBuffer(self, (d.n - 1,), np.int32)
+            usable = DeviceBuffer(self, (d.n,), np.int32)
+            c.run(self.lib.byz_linkage_dev(self.ctx, d.ptr, d.n, code, ctypes.byref(ctypes.c_double(fill)), pair.ptr, height.ptr,
+                                           size.ptr, usable.ptr, None))
+            usable = usable.numpy() != 0
+            merges = max(int(usable.sum()) - 1, 0)
+            return pair.numpy()[:merges], height.numpy()[:merges], size.numpy()[:merges], usable
+
+    def linkage(self, distances, method='average', fill=2.0):
+        """Agglomerative clustering of a distance matrix (a `Distances` handle or a dense symmetric matrix, the diagonal
+        ignored; cosine, Euclidean, Manhattan or any other) with 'average', 'complete' or 'single' linkage, on the GPU.
+        Returns (Z, usable): Z is scipy's (u - 1) x 4 float64 linkage matrix over the u usable rows -- the rows with a finite
+        off-diagonal distance, `usable` their mask; observation i of Z is the i-th usable row -- built on the host from the
+        device's merges, so scipy.cluster.hierarchy.fcluster and dendrogram take it.  An entry between usable rows that is
+        not finite or is negative counts as `fill`.  Merges are made in the order (distance, lower row, higher row), which
+        fixes every tie; the heights are scipy's up to the rounding of a different merge order."""
+        pair, height, size, usable = self.linkage_merges(distances, method=method, fill=fill)
+        u = int(usable.sum())
+        ident = np.full(usable.size, -1, dtype=np.int64)      # the scipy id of the cluster a slot holds
+        ident[usable] = np.arange(u)
+        z = np.zeros((max(u - 1, 0), 4), dtype=np.float64)
+        for t in range(z.shape[0]):
+            a, b = int(pair[t, 0]), int(pair[t, 1])
+            lo, hi = sorted((ident[a], ident[b]))
+            z[t] = (lo, hi, height[t], size[t])
+            ident[a] = u + t
+        return z, usable
+
+    def linkage_cut(self, pair, usable, n_clusters):
+        """The cut of linkage_merges' `pair` into n_clusters: (labels (n) int32, the clusters numbered by their lowest row in
+        ascending order and -1 for a row that is not usable, sizes (n_clusters) int32)."""
+        usable = np.ascontiguousarray(np.asarray(usable) != 0, dtype=np.int32)
+        n, c_count = int(usable.size), int(n_clusters)
+        if n > 16384:
+            raise NotImplementedError('linkage_cut: at most 16384 rows, got %d' % n)
+        if n < 2 or c_count < 1 or c_count > n:
+            raise ValueError('linkage_cut: %d clusters of %d rows (at least 2 rows, 1..n clusters)' % (c_count, n))
+        merges = np.full((n - 1, 2), -1, dtype=np.int32)
+        pair = np.asarray(pair, dtype=np.int32).reshape(-1, 2)
+        if pair.shape[0] > n - 1:
+            raise ValueError('linkage_cut: %d merges of %d rows' % (pair.shape[0], n))
+        merges[:pair.shape[0]] = pair
+        with _Call(self) as c:
+            p, f = c.upload(merges), c.upload(usable)
+            labels = DeviceBuffer(self, (n,), np.int32)
+            sizes = DeviceBuffer(self, (c_count,), np.int32)
+            c.run(self.lib.byz_linkage_cut_dev(self.ctx, p.ptr, n, f.ptr, c_count, labels.ptr, sizes.ptr, None))
+            return labels.numpy(), sizes.numpy()
+
+    def clipped_clustering_info(self):
+        """{admitted, usable, top_height, second_height, clip} of the last clipped_clustering_select or clipped_clustering on
+        this engine (synchronises): the rows admitted, the rows with a finite off-diagonal distance, the heights of the
+        last merge and of the one before (0 where there is none) and the clip used (0 after a selection alone)."""
+        return dict(zip(('admitted', 'usable', 'top_height', 'second_height', 'clip'),
+                        self._read(self.lib.byz_clipped_clustering_info,
+                                   [ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double])))
+
+    def clipped_clustering_select(self, distances, method='average', fill=2.0, on_device=False, like=None):
+        """ClippedClustering's selection on a distance matrix: the linkage, the cut into two clusters and the LARGER one
+        (equal sizes: the cluster of the lowest usable row).  Returns (rows, info): the admitted rows ascending
+        (on_device=True: the 0 / 1 int32 flags instead, as a DeviceBuffer, or a torch tensor beside `like`) and {admitted,
+        usable, top_height, second_height}."""
+        if isinstance(distances, dict):
+            raise ValueError('clipped_clustering_select() takes a Distances handle or a dense matrix')
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            code, fill = self._linkage_args(d.n, method, fill)
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            flags, fptr = c.out(d.n, np.int32)
+            c.run(self.lib.byz_clipped_clustering_select_dev(self.ctx, d.ptr, d.n, code, ctypes.byref(ctypes.c_double(fill)), fptr,
+                                                             None))
+            info = self.clipped_clustering_info()
+        info.pop('clip')
+        return (flags if on_device else np.flatnonzero(flags.numpy()).astype(np.int64)), info
+
+    def clipped_clustering(self, g, clip=None, method='average', fill=2.0, distances=None, sq=None, return_info=False):
+        """ClippedClustering in one library call: cosine_distances (or `distances`, which replaces that stage),
+        clipped_clustering_select, every admitted row clipped to `clip` (None: the median norm of this round's finite rows,
+        read on the device), their mean over the admitted count.  `sq`: the rows' fp64 squared norms where the caller has
+        them (device-resident for a device matrix), which spares the pass that computes them.  Nobody admitted: the zero
+        vector.  return_info=True also returns {admitted_rows (ascending), admitted, usable, top_height, second_height,
+        clip}."""
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        code, fill = self._linkage_args(n, method, fill)
+        if clip is not None and not float(clip) > 0.0:
+            raise ValueError('clipped_clustering: clip = %r must be > 0 (None: the median norm)' % clip)
+        params = _native.ClippedClusteringParams(0.0 if clip is None else float(clip), 1 if clip is None else 0, code, fill)
+        if isinstance(distances, dict):
+            raise ValueError('clipped_clustering() takes a Distances handle or a dense matrix as `distances`')
+        with _Call(self) as c:
+            dist = None
+            if distances is not None:
+                dist, _ = c.distances(distances)
+                if dist.n != n:
+                    raise ValueError('the distance matrix has %d rows, the gradients %d' % (dist.n, n))
+            if dm is None:
+                h = self._host_matrix(g)
+                d = h.shape[1]
+                out = np.empty(d, dtype=np.float32)
+                flags = np.zeros(n, dtype=np.int32)
+                dist_host = np.ascontiguousarray(dist.numpy(), dtype=np.float32) if dist is not None else None
+                sq_host = None if sq is None else np.ascontiguousarray(_to_host(sq), dtype=np.float64).reshape(-1)
+                if sq_host is not None and sq_host.size != n:
+                    raise ValueError('expected %d squared norms, got %d' % (n, sq_host.size))
+                _check(self.lib.byz_clipped_clustering_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(dist_host),
+                                                            _hp(sq_host), _hp(out), _hp(flags)))
+            else:
+                dm = c.matrix(dm)
+                q = None if sq is None else c.operand(sq, np.float64, _F64, n)
+                out, optr = c.out(dm.cols)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                c.run(self.lib.byz_clipped_clustering_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params),
+                                                          dist.ptr if dist is not None else None,
+                                                          q.ptr if q is not None else None, optr, fptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    flags = _to_host(flags) if _is_torch(flags) else flags.numpy()
+        if not return_info:
+            return out
+        info = self.clipped_clustering_info()
+        info['admitted_rows'] = np.flatnonzero(flags).astype(np.int64)
+        return out, info
+
     # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----
     def manhattan_distances(self, g):
         """The pairwise MANHATTAN (L1) distances of g's rows as a `Distances` handle, resident on the GPU: m_ij = sum_c

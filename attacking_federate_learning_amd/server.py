@@ -18,6 +18,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_sparsefed(k, clip, then)   the same step with SparseFed: only the k heaviest coordinates of an error-feedback memory
     defend_weak_dp(clip, sigma, then) the same step with norm clipping and Gaussian noise drawn on the GPU, fresh every round
     defend_flame(lam, min_samples)    the same step with FLAME: the majority cluster by cosine distance, clipped, averaged, noised
+    defend_clipped_clustering(method) the same step with ClippedClustering: the larger of two average-linkage clusters, clipped
     defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
@@ -53,6 +54,8 @@ class DeviceServer:
         self.weak_dp_round = 0
         # FLAME's history: the calls of defend_flame so far (the `round` of the next noise vector)
         self.flame_round = 0
+        # ClippedClustering's history: the norms of every client of every round so far (the clip is their median)
+        self.clipped_clustering_norms = []
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -221,6 +224,18 @@ class DeviceServer:
         score over their summed Manhattan, Euclidean and cosine distances, averaged, and server.py:89-90's momentum step on
         the result, as `defend` takes it.  Stateless: nothing is carried from round to round."""
         current_grads = defences.multi_metrics(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), p=p)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with ClippedClustering ----------------------------------------------------------------------
+    def defend_clipped_clustering(self, method='average', max_tau=1e5):
+        """ClippedClustering on this round's gradients (defences.clipped_clustering): the larger of the two average-linkage
+        clusters by cosine distance, clipped to min(median of `clipped_clustering_norms`, max_tau) and averaged, and
+        server.py:89-90's momentum step on the result, as `defend` takes it.  `clipped_clustering_norms` is the paper's
+        running history: every call appends this round's norms to it (one read-back a round) before it takes the median."""
+        current_grads = defences.clipped_clustering(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop),
+                                                    method=method, norm_history=self.clipped_clustering_norms, max_tau=max_tau)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

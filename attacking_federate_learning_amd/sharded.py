@@ -163,6 +163,10 @@ class HipKernels:
         # (0 / 1 flags of the admitted rows: an int32 tensor beside `like`; info): the same on every rank
         return self.engine.flame_select(dist, min_samples=min_samples, min_cluster_size=min_cluster_size, on_device=True, like=like)
 
+    def clipped_clustering_select(self, dist, like, method='average', fill=2.0):
+        # (0 / 1 flags of the admitted rows: an int32 tensor beside `like`; info): the same on every rank
+        return self.engine.clipped_clustering_select(dist, method=method, fill=fill, on_device=True, like=like)
+
     def manhattan_sums(self, g_local):
         return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
 
@@ -444,6 +448,32 @@ class ShardedAggregator:
         v = self.kernels.scaled_rows_sum(g_local, weights, count)
         if float(lam) != 0.0:
             v = self.kernels.gaussian_noise(v, lam, seed=seed, round=round, column_offset=column_offset, scale=used)
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        info = dict(info, clip=float(used.item()), admitted_rows=torch.nonzero(admitted).reshape(-1).cpu().numpy())
+        return out, info
+
+    def clipped_clustering(self, g_local, users_count, corrupted_count, clip=None, method='average', fill=2.0, gather=False,
+                           total_columns=None, return_info=False):
+        """ClippedClustering (defences.clipped_clustering's contract), columns layout.  TWO all-reduces: the N x N fp64 Gram of
+        the ranks' slices and the N squared norms.  Everything after them is replicated -- kernels.cosine_from_gram,
+        kernels.clipped_clustering_select and kernels.clip_scales (clip=None: the median norm) give the same flags, scales
+        and clip on every rank -- or local to the columns: the sum of the admitted rows over their count.  Returns this
+        rank's columns (gather=True: the whole vector)."""
+        import torch
+        n, d_local = g_local.shape
+        gram = self.kernels.gram(g_local)
+        self._all_reduce('allreduce_clipped_clustering_gram', gram)
+        dist = self.kernels.cosine_from_gram(gram)
+        admitted, info = self.kernels.clipped_clustering_select(dist, g_local, method=method, fill=fill)
+        zero = torch.zeros(d_local, dtype=torch.float32, device=g_local.device)
+        sq = self.kernels.row_sqdist(g_local, zero)
+        self._all_reduce('allreduce_clipped_clustering_norms', sq)
+        scales, used = self.kernels.clip_scales(sq, clip=1.0 if clip is None else clip, adaptive=clip is None)
+        weights = torch.where(admitted != 0, scales, torch.zeros_like(scales))
+        count = (admitted != 0).sum().to(torch.float64).reshape(1)
+        v = self.kernels.scaled_rows_sum(g_local, weights, count)
         out = self._maybe_gather(v, gather, total_columns)
         if not return_info:
             return out

@@ -769,6 +769,80 @@ int byz_multi_metrics_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* usable_row
 int byz_multi_metrics_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t keep, float* out_host,
                            int32_t* flags_host_or_null);
 
+/* ---- Agglomerative clustering and ClippedClustering (Li, Ngai & Voigt, "An Experimental Study of Byzantine-Robust Aggregation     */
+/* Schemes in Federated Learning", IEEE Trans. Big Data 2023; the `Clippedclustering` aggregator of Blades; not in the reference) ---- */
+/* The rule's four stages: (1) every client clipped to the median norm, (2) pairwise COSINE distances, (3) agglomerative clustering  */
+/* with AVERAGE linkage cut into two clusters, (4) the mean of the larger cluster.  Stages 1, 2 and 4 are byz_clip_scales_dev,       */
+/* byz_cosine_distances_dev and byz_scaled_rows_sum_dev; stage 3 is the linkage below, a primitive over ANY symmetric matrix in      */
+/* byz_pairwise_distances_dev's form (n x n fp32, the diagonal ignored): cosine, Euclidean or Manhattan.                             */
+/* The linkage, exactly:                                                                                                             */
+/*   entry (i, j), i != j, is READ from the lower triangle, at (max(i, j), min(i, j)): the matrix is symmetric by construction.      */
+/*   Row i is USABLE when it has a finite off-diagonal entry (the cosine stage's notion of a row that is not broken).  A row that is */
+/*   not usable takes no part: it is never merged and its label is -1.                                                               */
+/*   W, the working copy, is fp64: an entry that is not finite, or is negative, becomes `fill` (finite, >= 0; ClippedClustering      */
+/*   passes 2.0, the largest cosine distance, as Blades does); -0.0 counts as +0.0.                                                  */
+/*   Every step merges the active pair smallest in (W[a][b], a, b), a < b: the distance, then the lower slot, then the higher one.   */
+/*   The merged cluster keeps slot a (so a cluster's slot is its lowest row), slot b retires, and for every other active k, in fp64  */
+/*   in exactly this order of operations, with the sizes s_a and s_b held as doubles:                                                */
+/*     BYZ_LINKAGE_AVERAGE   W[a][k] = (s_a * W[a][k] + s_b * W[b][k]) / (s_a + s_b)   (two products, a sum, a quotient: scipy's)     */
+/*     BYZ_LINKAGE_COMPLETE  W[a][k] = max(W[a][k], W[b][k])                                                                         */
+/*     BYZ_LINKAGE_SINGLE    W[a][k] = min(W[a][k], W[b][k])                                                                         */
+/*   u usable rows give u - 1 merges: pair_dev[2 t], pair_dev[2 t + 1] = the slots a < b of merge t, height_dev[t] = W[a][b],        */
+/*   size_dev[t] = the merged size.  pair_dev holds 2 (n_rows - 1) int32, height_dev n_rows - 1 doubles, size_dev n_rows - 1 int32;  */
+/*   behind the u - 1 merges they hold -1, +inf and 0.  usable_rows_dev (optional): n_rows int32 of 0 / 1.                           */
+/* One workgroup runs the u - 1 steps with a nearest-partner cache per slot (Muellner 2011): no floating-point atomics, no grid or   */
+/* host synchronisation; the caches a merge invalidates are rebuilt from a row of W each, at most n_rows a step, the one loop whose  */
+/* length depends on the data.  method: 0 average, 1 complete, 2 single (BYZ_E_INVALID otherwise); *fill (a HOST double, read        */
+/* before the call returns: the ABI takes no doubles by value) finite and >= 0 (BYZ_E_INVALID otherwise); 2 <= n_rows <= 16,384      */
+/* (below: BYZ_E_INVALID; beyond: BYZ_E_UNSUPPORTED, decided on the argument alone).  Nothing is written when a call is refused.     */
+/* Asynchronous on `stream`.  Timers: BYZ_K_ROW_SORT: the working copy, the first caches and the cut; BYZ_K_MISC: the linkage.       */
+#define BYZ_LINKAGE_AVERAGE 0
+#define BYZ_LINKAGE_COMPLETE 1
+#define BYZ_LINKAGE_SINGLE 2
+int byz_linkage_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int method, const double* fill, int32_t* pair_dev,
+                    double* height_dev, int32_t* size_dev, int32_t* usable_rows_dev, void* stream);
+/* The last byz_linkage_dev or ClippedClustering call on this context: its merges, the nearest-partner caches it rebuilt from a row  */
+/* of W, and the most of them in one step.  Synchronises that call's stream.  BYZ_E_INVALID before the first such call.              */
+int byz_linkage_info(byz_ctx* ctx, int64_t* merges, int64_t* rescans, int64_t* max_rescans);
+/* The cut into n_clusters = c clusters, 1 <= c <= n_rows (BYZ_E_INVALID otherwise; with u < c usable rows every usable row is its    */
+/* own cluster): the first u - c merges of pair_dev (2 (n_rows - 1) int32, byz_linkage_dev's) replayed; labels_dev[i] in 0..c-1,   */
+/* the clusters numbered by their lowest row in ascending order, -1 for a row that is not usable; cluster_sizes_dev: c int32.  One   */
+/* workgroup; a pair outside 0 <= a < b < n_rows is skipped.  2 <= n_rows <= 16,384.  Asynchronous on `stream`.                     */
+int byz_linkage_cut_dev(byz_ctx* ctx, const int32_t* pair_dev, int64_t n_rows, const int32_t* usable_rows_dev, int64_t n_clusters,
+                        int32_t* labels_dev, int32_t* cluster_sizes_dev, void* stream);
+/* ClippedClustering's selection: the linkage, the cut into two, admitted_dev[i] = 1 for the rows of the LARGER cluster and 0 for     */
+/* every other row.  Equal sizes: the cluster of the lowest usable row (this library's rule: Blades' tie goes to scikit-learn's      */
+/* label 0, which is not a property of the data).  One usable row: it alone is admitted; none: nobody.  With two or more usable      */
+/* rows somebody is always rejected.  The limits and refusals of byz_linkage_dev.                                                    */
+int byz_clipped_clustering_select_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int method, const double* fill,
+                                      int32_t* admitted_dev, void* stream);
+typedef struct byz_clipped_clustering_params {
+    double clip;       /* the fixed mode's clip: > 0 (+inf: nobody is clipped)                                  */
+    int32_t adaptive;  /* != 0: clip = the median of this round's finite norms instead (FLAME's mode)            */
+    int32_t method;    /* BYZ_LINKAGE_*: the paper's is average                                                 */
+    double fill;       /* the distance taken for an entry that is not finite or is negative: finite, >= 0 (2.0) */
+} byz_clipped_clustering_params;
+/* The whole rule: byz_cosine_distances_dev (dist_dev_or_null == NULL; otherwise that n x n matrix REPLACES the cosine stage, as in   */
+/* byz_flame_dev), byz_clipped_clustering_select_dev, byz_row_sqdist_dev with a zero centre (sq_dev_or_null == NULL; otherwise the   */
+/* caller's n_rows squared norms, which spares that pass), byz_clip_scales_dev giving s_i, w_i = admitted_i ? s_i : 0, and           */
+/* byz_scaled_rows_sum_dev with the divisor L = the admitted rows (L = 0: the zero vector, never NaN).  Scaling a row by a positive  */
+/* number does not change its cosines, so the cosine stage runs on the UNCLIPPED rows (Blades clips first).                          */
+/* admitted_dev_or_null: n_rows int32 of 0 / 1.  It waits as byz_flame_dev does: once, inside the Gram's duplicate-row search, and   */
+/* not at all when dist_dev_or_null is given.  out_dev must not overlap G (BYZ_E_INVALID).  The limits of byz_linkage_dev.           */
+int byz_clipped_clustering_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                               const byz_clipped_clustering_params* params, const float* dist_dev_or_null,
+                               const double* sq_dev_or_null, float* out_dev, int32_t* admitted_dev_or_null, void* stream);
+/* The last byz_clipped_clustering_select_dev or byz_clipped_clustering_dev on this context: the rows admitted, the usable rows, the  */
+/* heights of the last merge and of the one before (0 where there is none) and the clip (0 after a selection alone).  Synchronises  */
+/* that call's stream.  BYZ_E_INVALID before the first such call.                                                                    */
+int byz_clipped_clustering_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* usable_rows, double* top_height, double* second_height,
+                                double* clip);
+/* The same on a host matrix (dist_host_or_null: n_rows x n_rows floats; sq_host_or_null: n_rows doubles; out_host: n_cols floats;   */
+/* admitted_host_or_null).  Synchronous.                                                                                             */
+int byz_clipped_clustering_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                                const byz_clipped_clustering_params* params, const float* dist_host_or_null,
+                                const double* sq_host_or_null, float* out_host, int32_t* admitted_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
@@ -950,6 +1024,14 @@ int byz_flame_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows
 int byz_multi_metrics_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
                                   int64_t keep, byz_allreduce_f64_fn allreduce, void* user, float* out_local_dev,
                                   int32_t* flags_dev_or_null, void* stream);
+
+/* ClippedClustering over the ranks' column slices: TWO all-reduces, the n x n Gram and the n squared norms (the Gram's is skipped    */
+/* when dist_dev_or_null is given); the selection and the scales are replicated on every rank, the sum is local to the columns.      */
+/* The ranks' outputs concatenate to byz_clipped_clustering_dev's vector up to the fp64 rounding of the all-reduced sums.            */
+int byz_clipped_clustering_sharded_dev(byz_ctx* ctx, const float* G_local_dev, int64_t n_rows, int64_t n_cols_local, int64_t ld,
+                                       const byz_clipped_clustering_params* params, byz_allreduce_f64_fn allreduce, void* user,
+                                       const float* dist_dev_or_null, float* out_local_dev, int32_t* admitted_dev_or_null,
+                                       void* stream);
 
 /* ---- malicious.Attack.attack / DriftAttack._attack_grads (malicious.py:10-36) ---------- */
 /* Column mean and population std over the n_rows rows of G (the malicious clients' honest  */
