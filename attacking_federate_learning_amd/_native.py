@@ -57,7 +57,13 @@ class FlameParams(ctypes.Structure):
                 ('round', ctypes.c_uint64), ('column_offset', c_i64)]
 
 
-MANHATTAN_CHAIN = 128             # BYZ_MANHATTAN_CHAIN: the Manhattan matrix's relative error is at most (this + 2) * 2^-24
+class FangParams(ctypes.Structure):
+    """byz_fang_params: the full-knowledge factor b, the partial-knowledge multiples of sigma, the mode and the draw's place."""
+    _fields_ = [('b', ctypes.c_double), ('k_lo', ctypes.c_double), ('k_hi', ctypes.c_double), ('partial', ctypes.c_int),
+                ('seed', ctypes.c_uint64), ('round', ctypes.c_uint64), ('column_offset', ctypes.c_uint64)]
+
+
+MANHATTAN_CHAIN = 128            # BYZ_MANHATTAN_CHAIN: the Manhattan matrix's relative error is at most (this + 2) * 2^-24
 
 
 class ClippedClusteringParams(ctypes.Structure):
@@ -216,6 +222,12 @@ _PROTOTYPES = {
     'byz_dnc_info': [c_vp, _P(c_i64), _P(c_i64)],
     'byz_dnc_host': [c_vp, c_vp, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, _P(c_i64)],
     'byz_dnc_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(DncParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_column_extremes_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_fang_fill_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FangParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_fang_trmean_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(FangParams), c_vp],
+    'byz_fang_trmean_attack_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FangParams), c_vp],
+    'byz_fang_krum_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(ctypes.c_double), c_vp, c_vp, c_vp, c_vp],
+    'byz_fang_krum_info': [c_vp, _P(ctypes.c_double), _P(ctypes.c_double), _P(c_i64), _P(c_i64), _P(c_i32)],
     'byz_timing_enable': [c_vp, c_int],
     'byz_timing_reset': [c_vp],
     'byz_timing_read': [c_vp, c_int, _P(ctypes.c_double), _P(c_i64)],

@@ -2127,6 +2127,201 @@ int byz_drift_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols,
     return BYZ_OK;
 }
 
+// ---- the attacks of Fang, Cao, Jia and Gong (USENIX Security 2020; beyond the reference) -----------------------------------------
+namespace {
+
+// What the attacks keep in ctx->fang.  m = 0 (the trimmed-mean attack): the column vectors alone.
+struct FangScratch {
+    float *a, *b, *c, *vec;          // n_cols each: mean or mu; lo or sigma; hi; the direction s, then the attack vector
+    double *t, *q;                   // m each: g_i . s and |g_i|^2 of the benign rows
+    float* block;                    // m x m: the benign rows' distances
+    unsigned long long* bounds;      // 2: the bits of min_i S_i and of max_i q_i
+};
+
+int fang_workspace(byz_ctx* ctx, int64_t n_cols, int64_t m, FangScratch* out) {
+    Carve c;
+    c.take(&out->a, n_cols);
+    c.take(&out->b, n_cols);
+    c.take(&out->c, n_cols);
+    c.take(&out->vec, n_cols);
+    c.take(&out->t, m);
+    c.take(&out->q, m);
+    c.take(&out->block, m * m);
+    c.take(&out->bounds, 2);
+    return c.commit(ctx->fang);
+}
+
+// (written so that a NaN fails every test)
+int check_fang(const char* who, const byz_fang_params* params, int64_t n_cols) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!params->partial && !(params->b > 1.0 && __builtin_isfinite(params->b))) {
+        set_error("%s: b = %g must be finite and > 1", who, params->b);
+        return BYZ_E_INVALID;
+    }
+    if (params->partial && !(params->k_lo >= 0.0 && params->k_hi >= params->k_lo && __builtin_isfinite(params->k_hi))) {
+        set_error("%s: 0 <= k_lo = %g <= k_hi = %g, both finite, violated", who, params->k_lo, params->k_hi);
+        return BYZ_E_INVALID;
+    }
+    if (params->round >> 32 != 0) {
+        set_error("%s: round = %llu must be below 2^32 (the attacker row takes the counter's top word)", who,
+                  (unsigned long long)params->round);
+        return BYZ_E_INVALID;
+    }
+    if (n_cols < 1 || params->column_offset > static_cast<uint64_t>(kNoiseMaxColumn) ||
+        static_cast<uint64_t>(n_cols) > static_cast<uint64_t>(kNoiseMaxColumn) - params->column_offset) {
+        set_error("%s: %lld columns from global column %llu (at least one, up to 2^62)", who, (long long)n_cols,
+                  (unsigned long long)params->column_offset);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+FangDraw fang_draw(const byz_fang_params* params) {
+    return {params->b, params->k_lo, params->k_hi, params->seed, params->round, static_cast<int64_t>(params->column_offset)};
+}
+
+int check_attackers(const char* who, int64_t n_rows, int64_t n_attackers) {
+    if (n_attackers < 0 || n_attackers > n_rows) {
+        set_error("%s: %lld attacker rows of %lld rows", who, (long long)n_attackers, (long long)n_rows);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_column_extremes_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers, float* mean,
+                            float* lo, float* hi, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "column_extremes"));
+    BYZ_TRY(check_attackers("column_extremes", n_rows, n_attackers));
+    BYZ_REQUIRE(mean || lo || hi, "column_extremes: no output asked for");
+    return launch_column_extremes(ctx, G, n_rows, n_cols, ld, n_attackers, mean, lo, hi, as_stream(stream));
+}
+
+int byz_fang_fill_dev(byz_ctx* ctx, float* G, int64_t n_attackers, int64_t n_cols, int64_t ld, const byz_fang_params* params,
+                      const float* a, const float* b, const float* c, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_attackers, n_cols, ld, "fang_fill"));
+    BYZ_TRY(check_fang("fang_fill", params, n_cols));
+    BYZ_REQUIRE(a && b && (params->partial || c), "fang_fill: null column vector");
+    return launch_fang_fill(ctx, G, n_attackers, n_cols, ld, fang_draw(params), params->partial != 0, a, b, c, as_stream(stream));
+}
+
+// full knowledge: column_extremes over all the rows, then the fill; partial: the drift attack's statistics of the attacker rows
+// (write_back = 0, no drifted vector), then the fill.  Nothing synchronises.
+int byz_fang_trmean_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                               const byz_fang_params* params, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "fang_trmean_attack"));
+    BYZ_TRY(check_attackers("fang_trmean_attack", n_rows, n_attackers));
+    BYZ_TRY(check_fang("fang_trmean_attack", params, n_cols));
+    BYZ_REQUIRE(params->partial || n_attackers < n_rows, "fang_trmean_attack: full knowledge needs a benign row (%lld rows, all the attacker's)",
+                (long long)n_rows);
+    if (n_attackers == 0) return BYZ_OK;
+    hipStream_t s = as_stream(stream);
+    FangScratch w;
+    BYZ_TRY(fang_workspace(ctx, n_cols, 0, &w));
+    if (params->partial) BYZ_TRY(launch_column_drift(ctx, G, n_attackers, n_cols, ld, 0.0f, nullptr, w.a, w.b, s));
+    else BYZ_TRY(launch_column_extremes(ctx, G, n_rows, n_cols, ld, n_attackers, w.a, w.b, w.c, s));
+    return launch_fang_fill(ctx, G, n_attackers, n_cols, ld, fang_draw(params), params->partial != 0, w.a, w.b, w.c, s);
+}
+
+int byz_fang_trmean_attack_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t n_attackers,
+                                const byz_fang_params* params, float* rows_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "fang_trmean_attack"));
+    BYZ_TRY(check_attackers("fang_trmean_attack", n_rows, n_attackers));
+    BYZ_TRY(check_fang("fang_trmean_attack", params, n_cols));
+    BYZ_REQUIRE(rows_host || n_attackers == 0, "fang_trmean_attack: null output");
+    HostStage st(ctx);   // (the matrix alone: the result is its first rows)
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_fang_trmean_attack_dev(ctx, st.G(), n_rows, n_cols, n_cols, n_attackers, params, st.stream()));
+    if (n_attackers > 0)
+        BYZ_HIP(hipMemcpyAsync(rows_host, st.G(), static_cast<size_t>(n_attackers) * n_cols * sizeof(float), hipMemcpyDeviceToHost,
+                               st.stream()));
+    return st.finish();
+}
+
+// The Krum attack.  The benign block's distances, t and q once; then one step = the attacker's rows and columns of the matrix
+// for lambda (no Gram) + the library's own Krum selection, whose index the host reads: that read per step, and the one of the
+// two bounds before the first, are the call's synchronisations (and the one the Gram's duplicate search makes, as everywhere).
+int byz_fang_krum_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                             const double* threshold, float* dist_out, double* t_out, double* q_out, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "fang_krum_attack"));
+    BYZ_REQUIRE(threshold && *threshold > 0.0 && __builtin_isfinite(*threshold), "fang_krum_attack: the threshold must be finite and > 0");
+    BYZ_REQUIRE(n_attackers >= 1 && n_rows > 2 * n_attackers + 1, "fang_krum_attack: n = %lld rows must exceed 2 c + 1 with c = %lld >= 1 attackers",
+                (long long)n_rows, (long long)n_attackers);
+    BYZ_TRY(check_row_ceiling("fang_krum_attack", n_rows));
+    hipStream_t s = as_stream(stream);
+    const int64_t n = n_rows, c = n_attackers, m = n - c;
+    FangScratch w;
+    BYZ_TRY(fang_workspace(ctx, n_cols, m, &w));
+    BYZ_TRY(ensure_distance_workspaces(ctx, n));
+    float* dist = dist_out ? dist_out : ctx->dist.as<float>();
+    const float* benign = G + c * ld;
+    // s from the mean of ALL rows (no_defense's bits), t and q of the benign rows, their distances, the two bounds
+    BYZ_TRY(launch_column_mean(ctx, G, n, n_cols, ld, w.a, s));
+    BYZ_TRY(launch_sign_vector(ctx, w.a, n_cols, 1.0f, -1.0f, w.vec, s));
+    RowScratch rows;
+    BYZ_TRY(row_scratch(ctx, m, n_cols, &rows, 2));
+    BYZ_TRY(launch_row_dots(ctx, benign, m, n_cols, ld, w.vec, rows.partials, w.t, w.q, s));
+    BYZ_TRY(distances(ctx, benign, m, n_cols, ld, nullptr, nullptr, w.block, stream));
+    BYZ_TRY(launch_fang_krum_bound(ctx, w.block, w.q, m, w.bounds, s));
+    int32_t raw[4];
+    BYZ_TRY(read_i32(ctx, reinterpret_cast<const int32_t*>(w.bounds), raw, 4, s));
+    double s_min, q_max;
+    std::memcpy(&s_min, raw, sizeof(double));
+    std::memcpy(&q_max, raw + 2, sizeof(double));
+    const double lambda0 = fang_lambda0(s_min, q_max, n, c, n_cols);
+    BYZ_REQUIRE(__builtin_isfinite(lambda0), "fang_krum_attack: the bound lambda_0 = %g is not finite (a benign row holds a value that is not)", lambda0);
+    BYZ_HIP(hipMemcpy2DAsync(dist + c * n + c, static_cast<size_t>(n) * sizeof(float), w.block, static_cast<size_t>(m) * sizeof(float),
+                             static_cast<size_t>(m) * sizeof(float), static_cast<size_t>(m), hipMemcpyDeviceToDevice, s));
+    double lambda = lambda0;
+    int64_t steps = 0;
+    int32_t chosen = -1;
+    bool succeeded = false;
+    for (;;) {
+        BYZ_TRY(launch_fang_krum_fill(ctx, dist, n, c, n_cols, w.q, w.t, lambda, s));
+        BYZ_TRY(krum_select(ctx, dist, n, n, c, krum_winner_word(ctx), s));
+        BYZ_TRY(read_winner(ctx, &chosen, s));
+        ++steps;
+        succeeded = chosen >= 0 && chosen < c;
+        if (succeeded || lambda < *threshold || steps >= 4096) break;
+        lambda = lambda / 2.0;
+    }
+    // every attacker row = -lambda s
+    BYZ_TRY(launch_sign_vector(ctx, w.a, n_cols, static_cast<float>(-lambda), static_cast<float>(lambda), w.vec, s));
+    BYZ_TRY(launch_broadcast_rows(ctx, G, c, n_cols, ld, w.vec, s));
+    const size_t row_bytes = static_cast<size_t>(m) * sizeof(double);
+    if (t_out) BYZ_HIP(hipMemcpyAsync(t_out, w.t, row_bytes, hipMemcpyDeviceToDevice, s));
+    if (q_out) BYZ_HIP(hipMemcpyAsync(q_out, w.q, row_bytes, hipMemcpyDeviceToDevice, s));
+    ctx->fang_krum_ran = true;
+    ctx->fang_stream = s;
+    ctx->fang_lambda0 = lambda0;
+    ctx->fang_lambda = lambda;
+    ctx->fang_steps = steps;
+    ctx->fang_chosen = chosen;
+    ctx->fang_succeeded = succeeded ? 1 : 0;
+    return BYZ_OK;
+}
+
+int byz_fang_krum_info(byz_ctx* ctx, double* lambda0, double* lambda, int64_t* steps, int64_t* chosen, int32_t* succeeded) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->fang_krum_ran, "fang_krum_info: no Krum attack on this context yet");
+    BYZ_TRY(check_small(ctx, ctx->fang_stream));             // synchronises the last call's stream: the rows' overwrite is behind it
+    if (lambda0) *lambda0 = ctx->fang_lambda0;
+    if (lambda) *lambda = ctx->fang_lambda;
+    if (steps) *steps = ctx->fang_steps;
+    if (chosen) *chosen = ctx->fang_chosen;
+    if (succeeded) *succeeded = ctx->fang_succeeded;
+    return BYZ_OK;
+}
+
 int byz_column_chain_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* carry_in,
                          const float* mean, float* out_sum, void* stream) {
     BYZ_TRY(enter(ctx));

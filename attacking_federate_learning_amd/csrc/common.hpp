@@ -181,8 +181,15 @@ struct byz_ctx {
     hipStream_t linkage_stream = nullptr;  // stream of the last linkage or ClippedClustering call (the two info calls sync it)
     bool linkage_ran = false;              // a linkage has written ctx->linkage_info
     bool clipped_clustering_selected = false;   // a ClippedClustering selection has written it as well
+    byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
+                                 // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
+    hipStream_t fang_stream = nullptr;     // stream of the last Krum attack (byz_fang_krum_info syncs it)
+    bool fang_krum_ran = false;            // a Krum attack has filled the five values below (byz_fang_krum_info reports them)
+    double fang_lambda0 = 0.0, fang_lambda = 0.0;
+    int64_t fang_steps = 0, fang_chosen = -1;
+    int32_t fang_succeeded = 0;
     // large_rows.hip: more than 16,384 rows
-    byz::Buffer large_keys;      // sort keys of one batch of rows
+    byz::Buffer large_keys;     // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
     byz::Buffer large_rank;      // n x n uint32: rank of column w in row u, [u][w]
     byz::Buffer large_rank_t;    // n x n uint32: the same transposed, [w][u]: a pick reads the winner's row of it
@@ -453,6 +460,30 @@ int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, b
 int launch_gaussian_noise(byz_ctx* ctx, const float* x, int64_t n, double sigma, uint64_t seed, uint64_t round, int64_t offset,
                           const double* scale_dev, float* out, hipStream_t stream);
 int launch_noise_words(byz_ctx* ctx, uint64_t seed, uint64_t round, int64_t offset, int64_t n, uint32_t* words, hipStream_t stream);
+// fang.hip: the Fang et al. attacks on the trimmed mean / median and on Krum.
+// mean[j] = no_defense's mean over ALL n_rows rows, lo[j] / hi[j] = np.fmin.reduce / np.fmax.reduce over the rows >= first_benign,
+// one read of G (any of the three may be null)
+int launch_column_extremes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t first_benign, float* mean,
+                           float* lo, float* hi, hipStream_t stream);
+struct FangDraw {
+    double b, k_lo, k_hi;
+    uint64_t seed, round;
+    int64_t offset;       // the global column of the caller's column 0
+};
+// the n_attackers first rows of G drawn from the columns' intervals; partial: a = mu, b = sigma (c unused), else a = mean, b = lo, c = hi
+int launch_fang_fill(byz_ctx* ctx, float* G, int64_t n_attackers, int64_t n_cols, int64_t ld, const FangDraw& draw, bool partial,
+                     const float* a, const float* b, const float* c, hipStream_t stream);
+// out[j] = mean[j] > 0 ? positive : otherwise
+int launch_sign_vector(byz_ctx* ctx, const float* mean, int64_t n_cols, float positive, float otherwise, float* out, hipStream_t stream);
+// bounds[0] = the bits of min_i S_i, S_i = the fp64 sum in column order of row i of the m x m benign block without its diagonal and
+// without the first of its largest entries; bounds[1] = the bits of max_i q_i.  Non-negative doubles order as their bits do.
+int launch_fang_krum_bound(byz_ctx* ctx, const float* block, const double* q, int64_t m, unsigned long long* bounds, hipStream_t stream);
+// Theorem 1's bound from the two values above
+double fang_lambda0(double s_min, double q_max, int64_t n, int64_t c, int64_t n_cols);
+// the c attacker rows and columns of dist (n x n): fl32(sqrt(max(q_i + (2 lambda) t_i + (lambda lambda) d, 0))) against benign i,
+// 0 between attackers, +inf on their diagonal
+int launch_fang_krum_fill(byz_ctx* ctx, float* dist, int64_t n, int64_t c, int64_t n_cols, const double* q, const double* t,
+                          double lambda, hipStream_t stream);
 // flame.hip: FLAME's clustering stage.  The scalars of a call live in ctx->flame_info, not in ctx->small (which is full):
 struct FlameInfo {
     int32_t admitted, broken_rows;   // the rows admitted; the rows without a finite off-diagonal distance

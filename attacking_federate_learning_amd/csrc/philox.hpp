@@ -74,6 +74,19 @@ BYZ_PHILOX_FN void philox_normals(const uint32_t (&x)[4], double (&z)[4]) {
     }
 }
 
+// One uniform draw from the interval [A, B] (A <= B, both fp64 formed from fp32 numbers) out of one word:
+//     u = (word + 0.5) * 2^-32                 exact, inside (0, 1)
+//     value = fl32(A + u * (B - A))            every operation rounded; rounding is monotone, so fl32(A) <= value <= fl32(B)
+// An end that is not finite gives `otherwise` (the caller's extreme) and no arithmetic: no inf - inf, never a new NaN.
+BYZ_PHILOX_FN float philox_uniform(uint32_t word, double A, double B, float otherwise) {
+    constexpr double kUnit = 1.0 / 4294967296.0;       // 2^-32
+    if (!(__builtin_isfinite(A) && __builtin_isfinite(B))) return otherwise;
+    const double u = (static_cast<double>(word) + 0.5) * kUnit;
+    const double w = B - A;
+    const double step = u * w;
+    return static_cast<float>(A + step);
+}
+
 }  // namespace byz
 
 #undef BYZ_PHILOX_FN

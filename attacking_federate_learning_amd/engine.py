@@ -2117,6 +2117,95 @@ class Engine:
                                                 int(bool(write_back)), c.stream))
         return drift, mean, std
 
+    # ---- the attacks of Fang et al. (USENIX Security 2020; not in the reference) ----
+    def column_extremes(self, g, n_malicious):
+        """(mean, lo, hi) per column in ONE read of g: no_defense's mean over ALL rows, np.fmin.reduce and np.fmax.reduce over
+        the benign rows g[n_malicious:] (a NaN is skipped; no benign number: NaN).  numpy for a host matrix, else device
+        vectors beside g."""
+        with _Call(self) as c:
+            m = c.matrix(g)
+            (mean, mptr), (lo, lptr), (hi, hptr) = (c.out(m.cols) for _ in range(3))
+            c.run(self.lib.byz_column_extremes_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, int(n_malicious), mptr, lptr, hptr,
+                                                   c.stream))
+            return c.result((mean, lo, hi))
+
+    @staticmethod
+    def _fang_params(b, partial, seed, round, column_offset, k_lo=3.0, k_hi=4.0):
+        """byz_fang_params; b finite and > 1, 0 <= k_lo <= k_hi finite, 0 <= round < 2^32, column_offset >= 0; the seed is
+        taken modulo 2^64."""
+        b, k_lo, k_hi = float(b), float(k_lo), float(k_hi)
+        if not partial and not (np.isfinite(b) and b > 1.0):
+            raise ValueError('b = %r must be finite and > 1' % (b,))
+        if partial and not (0.0 <= k_lo <= k_hi and np.isfinite(k_hi)):
+            raise ValueError('0 <= k_lo <= k_hi, both finite, violated: %r, %r' % (k_lo, k_hi))
+        if not 0 <= int(round) < (1 << 32):
+            raise ValueError('round = %r must lie in [0, 2^32): the attacker row takes the counter\'s top word' % (round,))
+        if int(column_offset) < 0:
+            raise ValueError('column_offset = %r must be >= 0' % (column_offset,))
+        return _native.FangParams(b, k_lo, k_hi, 1 if partial else 0, int(seed) & ((1 << 64) - 1), int(round), int(column_offset))
+
+    def fang_trmean_attack(self, g, n_malicious, b=2.0, partial=False, seed=0, round=0, column_offset=0, k_lo=3.0, k_hi=4.0):
+        """Fang et al.'s attack on the trimmed mean and the median (include/byzagg.h, rules A and B).  Rows 0 .. n_malicious - 1
+        of g hold the attackers' honest gradients, the others are benign.  Full knowledge: per column the mean of all rows
+        decides the side, every attacker value is drawn beyond the benign extreme of that side, from [lo / b, lo] or [b lo, lo]
+        (mean > 0), [hi, b hi] or [hi, hi / b] (otherwise). partial=True: from the attacker rows' own mean and std, [mu - k_hi
+        sigma, mu - k_lo sigma] or [mu + k_lo sigma, mu + k_hi sigma].  The draws come from the Philox stream of (seed, round,
+        attacker row, global column): every attacker row its own numbers, a column slice with its column_offset the whole
+        matrix's.  A device-resident g is attacked IN PLACE and its first n_malicious rows are returned as a view (torch) or
+        None (DeviceBuffer); a host matrix is left alone and the attacked rows come back as numpy.  Nothing synchronises."""
+        params = self._fang_params(b, partial, seed, round, column_offset, k_lo, k_hi)
+        c_rows = int(n_malicious)
+        dm = self._device_matrix(g)
+        if dm is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            if not 0 <= c_rows <= n:
+                raise ValueError('%d attacker rows of %d rows' % (c_rows, n))
+            rows = np.empty((c_rows, d), dtype=np.float32)
+            _check(self.lib.byz_fang_trmean_attack_host(self.ctx, _hp(h), n, d, c_rows, ctypes.byref(params), _hp(rows)))
+            return rows
+        with _Call(self) as c:
+            dm = c.matrix(dm)
+            c.run(self.lib.byz_fang_trmean_attack_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, c_rows, ctypes.byref(params),
+                                                      c.stream))
+        return g[:c_rows] if dm.torch_like is not None else None
+
+    def fang_krum_info(self):
+        """{lambda0, lambda, steps, chosen, succeeded} of the last fang_krum_attack on this engine (synchronises)."""
+        lambda0, lam, steps, chosen, succeeded = self._read(
+            self.lib.byz_fang_krum_info, [ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32])
+        return {'lambda0': lambda0, 'lambda': lam, 'steps': steps, 'chosen': chosen, 'succeeded': bool(succeeded)}
+
+    def fang_krum_attack(self, g, n_malicious, threshold=1e-5, return_info=False, return_working=False):
+        """Fang et al.'s attack on Krum (include/byzagg.h, rule C): every attacker row becomes -lambda s, s the sign of the
+        column means, lambda halved from Theorem 1's bound until the library's own Krum picks an attacker row or lambda falls
+        below `threshold`.  The benign rows' distances are computed once; a step rewrites the attackers' rows and columns of
+        the distance matrix from t = g . s and q = |g|^2 and runs krum_select: the host reads one index per step.  A
+        device-resident g is attacked IN PLACE (returns its first rows as a view, or None for a DeviceBuffer); a host matrix is
+        left alone and the attacked rows come back as numpy.  return_info=True adds fang_krum_info(); return_working=True adds
+        to that dict the last step's `distances` (a Distances handle) and the benign rows' `t` and `q` (fp64)."""
+        c_rows = int(n_malicious)
+        threshold = ctypes.c_double(float(threshold))
+        with _Call(self) as c:
+            m = c.matrix(g)
+            dist = DeviceBuffer(self, (m.rows, m.rows), np.float32) if return_working else None
+            dptr = dist.ptr if return_working else None
+            t, tptr = c.out(max(m.rows - c_rows, 1), np.float64, want=return_working)
+            q, qptr = c.out(max(m.rows - c_rows, 1), np.float64, want=return_working)
+            c.run(self.lib.byz_fang_krum_attack_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, c_rows, ctypes.byref(threshold), dptr,
+                                                    tptr, qptr, c.stream))
+            if c.host:
+                rows = c.numpy(m.keep)[:c_rows]
+            else:
+                rows = g[:c_rows] if m.torch_like is not None else None
+            if not (return_info or return_working):
+                return rows
+            info = self.fang_krum_info()
+            if return_working:
+                info['distances'] = Distances(dist, m.rows)
+                info['t'], info['q'] = c.result((t, q))
+            return rows, info
+
     def column_chain(self, rows, carry=None, mean=None):
         """One link of the attack's statistics over rows that several owners hold (sharded.py, clients layout): the running
         column sums after THESE rows, continuing `carry` (the previous owner's result; None: the chain starts here) -- of the

@@ -6,6 +6,9 @@ overridable hook `_attack_grads(grads_mean, grads_stdev, original_params, learni
 and rebinds every `usr.grads` to the ONE array the hook returned (reference malicious.py:26-27).
 `backdoor.BackdoorAttack` subclasses `Attack` and overrides only the hook, which keeps working.
 
+Beyond the reference: `FangTrimmedMeanAttack` and `FangKrumAttack`, the adaptive attacks of Fang et al. (USENIX Security 2020)
+on the trimmed mean / median and on Krum; they need the benign gradients too and give every malicious user its own row.
+
 The column statistics run in libbyzagg's column kernel; for `DriftAttack` the drift itself is fused into
 that kernel, so the m x D matrix is read once.
 """
@@ -66,3 +69,78 @@ class DriftAttack(Attack):
         else:  # called directly with arbitrary vectors
             grads_mean[:] = get_engine().drift_axpy_host(grads_mean, grads_stdev, self.num_std)
         return grads_mean
+
+
+class _FangAttack(Attack):
+    """What the two attacks of Fang, Cao, Jia and Gong (USENIX Security 2020) share: they need the BENIGN gradients as well
+    (full knowledge), passed as `attack(users, benign_users=...)` or bound beforehand with `bind(matrix)`; `num_std` is not
+    read (it is None).  `grads_mean` / `grads_stdev` are kept as `Attack.attack` keeps them."""
+
+    def __init__(self):
+        super(_FangAttack, self).__init__(None)
+        self.benign = None
+
+    def bind(self, benign):
+        """The benign clients' gradients for the calls that follow: a 2-D float32 array, one row a client (None: unbind)."""
+        self.benign = None if benign is None else np.ascontiguousarray(benign, dtype=np.float32)
+        return self
+
+    def _matrix(self, users, benign_users, needs_benign):
+        rows = np.stack([np.asarray(usr.grads, dtype=np.float32) for usr in users])
+        if benign_users is not None:
+            benign = np.stack([np.asarray(usr.grads, dtype=np.float32) for usr in benign_users])
+        else:
+            benign = self.benign
+        if benign is None:
+            if needs_benign:
+                raise ValueError('%s needs the benign gradients: attack(users, benign_users=...) or bind(matrix)'
+                                 % type(self).__name__)
+            return rows
+        return np.concatenate([rows, benign.reshape(-1, rows.shape[1])])
+
+    def _hand_out(self, users, attacked):
+        for usr, row in zip(users, attacked):
+            usr.grads = row
+
+
+class FangTrimmedMeanAttack(_FangAttack):
+    """The trimmed-mean / median attack (section 4.3): per coordinate every malicious value is drawn beyond the benign extreme
+    on the side that turns the aggregate round -- from [lo / b, lo] or [b lo, lo] where the column mean is above 0, from
+    [hi, b hi] or [hi, hi / b] otherwise.  partial=True is the paper's partial-knowledge variant, from the malicious clients' own
+    mean and std alone: [mu - 4 sigma, mu - 3 sigma] or [mu + 3 sigma, mu + 4 sigma]; it needs no benign gradients.
+    UNLIKE DriftAttack, which rebinds every malicious `usr.grads` to ONE shared array (reference malicious.py:26-27), every
+    malicious user gets ITS OWN row here: the paper samples c numbers per coordinate.  The draws are a function of (seed, the
+    number of earlier calls, the user's position, the coordinate): `round` counts the calls."""
+
+    def __init__(self, b=2.0, partial=False, seed=0):
+        super(FangTrimmedMeanAttack, self).__init__()
+        self.b, self.partial, self.seed, self.round = b, bool(partial), seed, 0
+
+    def attack(self, users, benign_users=None):
+        if len(users) == 0:
+            return
+        _, self.grads_mean, self.grads_stdev = self._statistics(users, 0.0)
+        g = self._matrix(users, None if self.partial else benign_users, needs_benign=not self.partial)
+        attacked = get_engine().fang_trmean_attack(g, len(users), b=self.b, partial=self.partial, seed=self.seed, round=self.round)
+        self.round += 1
+        self._hand_out(users, attacked)
+
+
+class FangKrumAttack(_FangAttack):
+    """The Krum attack (section 4.2): every malicious gradient becomes -lambda s, s the sign of the column means, with the
+    largest lambda = lambda_0 / 2^k for which Krum over all the clients picks a malicious one (lambda_0: the paper's Theorem 1);
+    below `threshold` the search gives up and keeps its last lambda.  The paper's other malicious vectors "within epsilon of
+    the first" are copies of it, as in every public implementation; each user still gets its own row.  `info` holds the last
+    call's {lambda0, lambda, steps, chosen, succeeded}."""
+
+    def __init__(self, threshold=1e-5):
+        super(FangKrumAttack, self).__init__()
+        self.threshold, self.info = threshold, None
+
+    def attack(self, users, benign_users=None):
+        if len(users) == 0:
+            return
+        _, self.grads_mean, self.grads_stdev = self._statistics(users, 0.0)
+        g = self._matrix(users, benign_users, needs_benign=True)
+        attacked, self.info = get_engine().fang_krum_attack(g, len(users), threshold=self.threshold, return_info=True)
+        self._hand_out(users, attacked)

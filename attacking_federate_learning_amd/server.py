@@ -8,7 +8,9 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     collect_gradients(users)        server.py:81-83   rows written by libbyzagg (host vectors or device tensors)
     collect_batched(net, x, y)      server.py:54-56 + user.py:76-92 for every client at once (clients.py)
     attack(attacker_rows, num_std)  main.py:68 -> malicious.py:10-36 on the first rows, in place
-    defend(defence_method)          server.py:86-90   defences.defend[...] on the device matrix + fused momentum step
+    attack_fang_trimmed_mean(rows)  Fang et al.'s attack on the trimmed mean / median on the same rows, fresh draws every round
+    attack_fang_krum(rows)          Fang et al.'s attack on Krum on the same rows
+    defend(defence_method)          server.py:86-90  defences.defend[...] on the device matrix + fused momentum step
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
     defend_signguard(frac, ...)       the same step with SignGuard, a new census window every round
@@ -54,6 +56,8 @@ class DeviceServer:
         self.weak_dp_round = 0
         # FLAME's history: the calls of defend_flame so far (the `round` of the next noise vector)
         self.flame_round = 0
+        # the Fang trimmed-mean attack's history: the calls of attack_fang_trimmed_mean so far (the `round` of the next draws)
+        self.fang_round = 0
         # ClippedClustering's history: the norms of every client of every round so far (the clip is their median)
         self.clipped_clustering_norms = []
 
@@ -74,6 +78,28 @@ class DeviceServer:
         rows = self.users_grads.data[:n_malicious]
         _, mean, std = self.engine.drift_attack(rows, num_std, write_back=(num_std != 0))
         return mean, std
+
+    # ---- the adaptive attacks of Fang et al. on the same rows -------------------------------------------
+    def attack_fang_trimmed_mean(self, n_malicious, b=2.0, partial=False, seed=0):
+        """Fang et al.'s trimmed-mean / median attack on rows 0 .. n_malicious-1, in place (engine.fang_trmean_attack): every
+        malicious row its own draws beyond the benign extremes (partial=True: from the malicious rows' own mean and std).
+        `fang_round`, the calls so far, is passed as the stream's `round` and then incremented, as defend_weak_dp counts its
+        own: one seed draws fresh numbers every round.  Nothing leaves the GPU; nothing synchronises."""
+        if n_malicious <= 0:
+            return None
+        rows = self.engine.fang_trmean_attack(self.users_grads.data, n_malicious, b=b, partial=partial, seed=seed,
+                                              round=self.fang_round)
+        self.fang_round += 1
+        return rows
+
+    def attack_fang_krum(self, n_malicious, threshold=1e-5):
+        """Fang et al.'s Krum attack on rows 0 .. n_malicious-1, in place (engine.fang_krum_attack): all of them become
+        -lambda s.  Returns {lambda0, lambda, steps, chosen, succeeded}.  The gradients stay on the GPU; the host reads one
+        index per halving of lambda."""
+        if n_malicious <= 0:
+            return None
+        _, info = self.engine.fang_krum_attack(self.users_grads.data, n_malicious, threshold=threshold, return_info=True)
+        return info
 
     # ---- server.py:86-90 ---------------------------------------------------------------------------
     def defend(self, defence_method, cur_epoch=None):

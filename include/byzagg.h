@@ -1058,6 +1058,81 @@ int byz_column_finish_dev(byz_ctx* ctx, const float* sum_dev, const float* sumsq
 int byz_drift_axpy_dev(byz_ctx* ctx, float* mean_dev, const float* std_dev, int64_t n,
                        float num_std, void* stream);
 
+/* ---- The attacks of Fang, Cao, Jia & Gong, "Local Model Poisoning Attacks to Byzantine-Robust Federated Learning" (USENIX    */
+/* Security 2020, sections 4.2 and 4.3; not in the reference) ----                                                                */
+/* The adaptive baseline beside A Little Is Enough: one attack tailored to the trimmed mean and the median, one to Krum.  G is    */
+/* n_rows x n_cols; rows 0 .. c - 1 (c = n_attackers) are the attacker's and hold their honest gradients on entry, rows c ..      */
+/* n_rows - 1 are benign.  The paper works on local MODELS; a gradient g moves the model by -lr g, so its "changing direction"    */
+/* s = -1 is a column mean above 0 here and its "above the largest benign model" is "below the smallest benign gradient".         */
+/*                                                                                                                                */
+/* A. Trimmed-mean / median attack, full knowledge (section 4.3).  Per column j:                                                  */
+/*   mean_j = np.mean(G[:, j]) over ALL rows: byz_no_defense_dev's bits.                                                          */
+/*   lo_j = np.fmin.reduce(G[c:, j]), hi_j = np.fmax.reduce(G[c:, j]) over the BENIGN rows: a NaN is skipped, a column with no     */
+/*   benign number gives NaN (of zeros of both signs the first one met stays).                                                    */
+/*   mean_j > 0: every attacker value is drawn from [lo / b, lo] when lo > 0, else from [b lo, lo];                                */
+/*   otherwise (mean_j <= 0, -0.0, NaN): from [hi, b hi] when hi > 0, else from [hi, hi / b].                                       */
+/*   The ends A <= B are fp64: one product or quotient of b and the fp32 extreme.                                                 */
+/* B. The same attack, partial knowledge: mu_j, sigma_j = the attacker rows' np.mean and np.var ** 0.5 (byz_drift_attack_dev's     */
+/*   bits, write_back = 0).  mu_j > 0: drawn from [mu - k_hi sigma, mu - k_lo sigma], otherwise from [mu + k_lo sigma, mu + k_hi   */
+/*   sigma]; the ends are (double)mu -+ fl64(k * (double)sigma).  One attacker has sigma = 0: the value is the end itself.        */
+/* The draw: u = (word + 0.5) * 2^-32 in fp64 (exact, inside (0, 1)); value = fl32(A + fl64(u * fl64(B - A))).  Rounding is         */
+/*   monotone, so fl32(A) <= value <= fl32(B).  An end that is not finite gives the extreme itself (lo_j, hi_j, or the k_lo end): */
+/*   no inf - inf, never a new NaN.  The word of (attacker row i, global column j) is word j & 3 of the Philox4x32-10 block        */
+/*   (key = seed, counter = (low, high word of j >> 2, round, i)): byz_noise_words_dev's stream with `round | i << 32` as its     */
+/*   round.  `round` therefore has 32 bits (BYZ_E_INVALID beyond).  Every attacker row draws independently, the paper's "sample c */
+/*   numbers"; one call, a misaligned caller and any split of the columns over ranks draw the same bits.                          */
+/* There is NO SHARDED ENTRY POINT for A and B: given column_offset they are local to a column, a rank of the columns layout      */
+/*   calls byz_fang_trmean_attack_dev on its slice with the global index of its first column.                                     */
+typedef struct byz_fang_params {
+    double b;               /* full knowledge: the interval's factor, finite and > 1 (the paper's 2)            */
+    double k_lo, k_hi;      /* partial knowledge: 0 <= k_lo <= k_hi, finite (the paper's 3 and 4)                */
+    int partial;            /* 0: full knowledge (A); otherwise partial knowledge (B)                            */
+    uint64_t seed, round, column_offset;   /* the Philox key; the round counter, < 2^32; the global column of     */
+                            /* column 0 of G, column_offset + n_cols <= 2^62                                      */
+} byz_fang_params;
+/* mean_dev, lo_dev, hi_dev (n_cols floats each, any of them NULL, not all) of rule A in ONE read of G; 0 <= n_attackers <=       */
+/* n_rows (n_attackers = n_rows: no benign row, lo = hi = NaN).                                                                   */
+int byz_column_extremes_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                            float* mean_dev, float* lo_dev, float* hi_dev, void* stream);
+/* The draw alone, into the n_attackers >= 1 rows of G_dev.  Full knowledge: a = mean, b = lo, c = hi; partial: a = mu, b =       */
+/* sigma, c is not read.                                                                                                          */
+int byz_fang_fill_dev(byz_ctx* ctx, float* G_dev, int64_t n_attackers, int64_t n_cols, int64_t ld, const byz_fang_params* params,
+                      const float* a_dev, const float* b_dev, const float* c_dev_or_null, void* stream);
+/* The attack, in place on rows 0 .. n_attackers - 1: byz_column_extremes_dev (full) or the attacker rows' statistics (partial)   */
+/* into a context workspace, then byz_fang_fill_dev.  n_attackers = 0 does nothing; full knowledge needs n_attackers < n_rows.    */
+/* Every launch is enqueued up front; nothing synchronises with the host.                                                        */
+int byz_fang_trmean_attack_dev(byz_ctx* ctx, float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                               const byz_fang_params* params, void* stream);
+/* The same on a host matrix, which is left as it is: rows_host receives the n_attackers x n_cols attacked rows.  Synchronous.    */
+int byz_fang_trmean_attack_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t n_attackers,
+                                const byz_fang_params* params, float* rows_host);
+/* C. Krum attack, full knowledge (section 4.2).  s_j = +1 where mean_j > 0 (rule A's mean), else -1; every attacker row becomes  */
+/* the ONE vector -lambda s.  The paper's other c - 1 rows "within epsilon of the first" are copies of it here, as in every       */
+/* public implementation.  Upper bound (Theorem 1, with w_Re the zero gradient), all in fp64:                                     */
+/*   lambda_0 = min_i S_i / ((n - 2c - 1) sqrt(d)) + sqrt(max_i q_i) / sqrt(d),  q_i = |g_i|^2 of benign row i (byz_row_dots_dev), */
+/*   S_i = the sum, in column order, of benign i's n - c - 2 smallest distances to the other benign rows: its row of              */
+/*   byz_pairwise_distances_dev of the benign block without the first of its largest entries.                                     */
+/* lambda = lambda_0, lambda_0 / 2, ...: a step writes the attacker's c rows and columns of the n x n fp32 distance matrix from   */
+/*   d(benign i, -lambda s)^2 = q_i + fl(fl(2 lambda) t_i) + fl(fl(lambda lambda) d),  t_i = g_i . s (byz_row_dots_dev),           */
+/*   summed left to right in fp64, then fl32(sqrt(max(., 0))); attacker-attacker entries are 0, the diagonal +inf as              */
+/*   byz_pairwise_distances_dev writes it; the benign block is computed ONCE, no step costs a Gram.  Then the library's own        */
+/*   byz_krum_select_dev(dist, n, n, c).  The loop stops at the first lambda for which Krum returns an index < c (succeeded = 1),  */
+/*   or after the first lambda tried that lies below *threshold (succeeded = 0); the last lambda tried is used either way, and    */
+/*   rows 0 .. c - 1 of G are overwritten with -lambda s (fl32(lambda) with the sign).                                            */
+/* n_rows > 2 n_attackers + 1 and n_attackers >= 1, *threshold finite and > 0 (the paper's 1e-5): BYZ_E_INVALID otherwise, and    */
+/* when lambda_0 is not finite (a benign row holds a value that is not); nothing is written then.  No doubles by value.           */
+/* SYNCHRONISES: the host reads the two bounds once and one int32, Krum's index, per step (and the Gram of the benign block       */
+/* waits once for its duplicate-row search, as byz_pairwise_distances_dev does).  The last launches, the rows' overwrite, are      */
+/* asynchronous on `stream`.  dist_dev_or_null: n x n floats, receives the last step's matrix; t_dev_or_null, q_dev_or_null:      */
+/* n_rows - n_attackers doubles each.  Under the columns layout t and q need an all-reduce: not offered here.                     */
+int byz_fang_krum_attack_dev(byz_ctx* ctx, float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                             const double* threshold, float* dist_dev_or_null, double* t_dev_or_null, double* q_dev_or_null,
+                             void* stream);
+/* The last byz_fang_krum_attack_dev on this context: lambda_0, the lambda used, the steps taken (lambda = lambda_0 / 2^(steps-1)), */
+/* the index Krum chose at the last step (-1: none) and whether that was an attacker row.  Synchronises that call's stream, as     */
+/* byz_flame_info does: the rows' overwrite is complete when it returns.  BYZ_E_INVALID before the first such call.               */
+int byz_fang_krum_info(byz_ctx* ctx, double* lambda0, double* lambda, int64_t* steps, int64_t* chosen, int32_t* succeeded);
+
 /* ---- next row after the path: Server.defend's update (server.py:89-90) ----------------- */
 /* velocity = momentum*velocity - lr*agg ; weights += velocity, fused, in place.            */
 int byz_server_update_dev(byz_ctx* ctx, float* weights_dev, float* velocity_dev,
