@@ -107,6 +107,8 @@ _PROTOTYPES = {
     'byz_trimmed_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
     'byz_coordinate_median_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_rank_trimmed_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
+    'byz_window_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'byz_phocas_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_trimmed_mean_redone': [c_vp, _P(c_i64), c_vp],
     'byz_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_krum_bulyan_select_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(c_i32), c_vp, c_vp],
@@ -139,6 +141,8 @@ _PROTOTYPES = {
     'byz_multi_krum_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp],
     'byz_coordinate_median_host': [c_vp, c_vp, c_i64, c_i64, c_vp],
     'byz_rank_trimmed_mean_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp],
+    'byz_window_mean_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
+    'byz_phocas_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_row_sqdist_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_weighted_mean_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     'byz_geometric_median_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(GeomedParams), c_vp, c_vp, c_vp],

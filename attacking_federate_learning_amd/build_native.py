@@ -21,7 +21,7 @@ SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_wind
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip',
            'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip', 'nnm.hip', 'robust_lr.hip', 'topk.hip',
            'bucketing.hip', 'signguard.hip', 'noise.hip', 'flame.hip', 'manhattan.hip', 'multi_metrics.hip', 'linkage.hip',
-           'fang.hip']
+           'fang.hip', 'centre_window.hip']
 # median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
 # dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
 # LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a
@@ -63,7 +63,9 @@ EXTRA_FLAGS = {'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000
                # SignGuard: q has row_dots' bits; the selection's stated order of operations
                'signguard.hip': ['-ffp-contract=off'],
                # the resident tile of keys lives in registers (full unroll of every loop over it); fixed-order fp64 sums
-               'rank_select.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off']}
+               'rank_select.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off'],
+               # the resident tile of values likewise; d = fl32(x - c) is one stated subtraction, the fp64 sums run in a fixed order
+               'centre_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off']}
 COMMON_FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function',
                 '-Wno-nan-infinity-disabled']
 

@@ -637,6 +637,33 @@ int byz_rank_trimmed_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int6
     return launch_rank_select(ctx, G, n_rows, n_cols, ld, row_index, trim_count, false, out, as_stream(stream));
 }
 
+int byz_window_mean_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                        const float* centre, int64_t keep, float* out, float* radius, void* stream) {
+    BYZ_TRY(enter(ctx));
+    return launch_centre_window(ctx, G, n_rows, n_cols, ld, row_index, centre, keep, out, radius, as_stream(stream));
+}
+
+// Phocas: the window of n - b values around the bits byz_rank_trimmed_mean_dev returns.  Everything is checked before the first
+// launch; the centre goes to the caller's vector when there is one, else to the workspace.
+int byz_phocas_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                   int64_t trim_count, float* out, float* centre_out, float* radius, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "phocas"));
+    BYZ_REQUIRE(out, "phocas: null output");
+    BYZ_TRY(check_row_ceiling("phocas", n_rows));
+    BYZ_REQUIRE(trim_count >= 0 && 2 * trim_count < n_rows, "phocas: trim_count %lld must satisfy 0 <= 2 b < %lld rows",
+                (long long)trim_count, (long long)n_rows);
+    float* centre = centre_out;
+    if (centre == nullptr) {
+        Carve c;
+        c.take(&centre, n_cols);
+        BYZ_TRY(c.commit(ctx->phocas));
+    }
+    hipStream_t s = as_stream(stream);
+    BYZ_TRY(launch_rank_select(ctx, G, n_rows, n_cols, ld, row_index, trim_count, false, centre, s));
+    return launch_centre_window(ctx, G, n_rows, n_cols, ld, row_index, centre, n_rows - trim_count, out, radius, s);
+}
+
 int byz_trimmed_mean_redone(byz_ctx* ctx, int64_t* tiles_host, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(tiles_host, "trimmed_mean_redone: null output");
@@ -2539,6 +2566,40 @@ int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows
 int byz_rank_trimmed_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t trim_count,
                                float* out_host) {
     return rank_select_host(ctx, G_host, n_rows, n_cols, trim_count, false, out_host);
+}
+
+int byz_window_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const float* centre_host, int64_t keep,
+                         float* out_host, float* radius_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "window_mean"));
+    BYZ_REQUIRE(centre_host && out_host, "window_mean: null centre or output");
+    BYZ_TRY(check_centre_window("window_mean", n_rows, keep));      // refused before anything is staged
+    HostStage st(ctx);
+    float *centre, *out, *radius;
+    st.in<float>(&centre, centre_host, n_cols);
+    st.out(&out, out_host, n_cols);
+    st.out(&radius, radius_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(launch_centre_window(ctx, st.G(), n_rows, n_cols, n_cols, nullptr, centre, keep, out, radius, st.stream()));
+    return st.finish_sync();
+}
+
+int byz_phocas_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t trim_count, float* out_host,
+                    float* centre_out_host, float* radius_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "phocas"));
+    BYZ_REQUIRE(out_host, "phocas: null output");
+    BYZ_TRY(check_row_ceiling("phocas", n_rows));
+    BYZ_REQUIRE(trim_count >= 0 && 2 * trim_count < n_rows, "phocas: trim_count %lld must satisfy 0 <= 2 b < %lld rows",
+                (long long)trim_count, (long long)n_rows);
+    HostStage st(ctx);
+    float *out, *centre, *radius;
+    st.out(&out, out_host, n_cols);
+    st.inout<float>(&centre, nullptr, centre_out_host, n_cols);      // (always carved: the window is taken around it)
+    st.out(&radius, radius_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_phocas_dev(ctx, st.G(), n_rows, n_cols, n_cols, nullptr, trim_count, out, centre, radius, st.stream()));
+    return st.finish_sync();
 }
 
 int byz_geometric_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_geomed_params* params,

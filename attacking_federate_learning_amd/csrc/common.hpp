@@ -188,8 +188,10 @@ struct byz_ctx {
     double fang_lambda0 = 0.0, fang_lambda = 0.0;
     int64_t fang_steps = 0, fang_chosen = -1;
     int32_t fang_succeeded = 0;
+    byz::Buffer phocas;          // Phocas, carved (api.hip: byz_phocas_dev): the rank-trimmed mean the window is taken around, when the
+                                 // caller does not ask for it
     // large_rows.hip: more than 16,384 rows
-    byz::Buffer large_keys;     // sort keys of one batch of rows
+    byz::Buffer large_keys;    // sort keys of one batch of rows
     byz::Buffer large_idx;       // n x n uint32: column index at every ascending rank
     byz::Buffer large_rank;      // n x n uint32: rank of column w in row u, [u][w]
     byz::Buffer large_rank_t;    // n x n uint32: the same transposed, [w][u]: a pick reads the winner's row of it
@@ -648,6 +650,12 @@ int launch_trimmed_mean_tall(byz_ctx* ctx, const float* G, int64_t n_rows, int64
 int64_t rank_select_resident_max_rows();
 int launch_rank_select(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        int64_t trim_count, bool median, float* out, hipStream_t stream);
+// centre_window.hip: per column the mean of the `keep` values nearest a GIVEN centre (ties in row order), optionally the radius
+// |x - c| of the last one kept: one order statistic by the same radix select and in the same two geometries.
+// check_centre_window: the row ceiling (BYZ_E_UNSUPPORTED) and 1 <= keep <= n_rows (BYZ_E_INVALID), as the launcher applies them
+int check_centre_window(const char* who, int64_t n_rows, int64_t keep);
+int launch_centre_window(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
+                         const float* centre, int64_t keep, float* out, float* radius, hipStream_t stream);
 // window_lean.hip: the row-split ring selection, first stage of the trimmed mean (round 3)
 int launch_window_lean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        int64_t keep, float* out, int32_t* redo, hipStream_t stream);

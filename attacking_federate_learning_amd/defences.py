@@ -372,6 +372,44 @@ def rank_trimmed_mean(users_grads, users_count, corrupted_count):
     return get_engine().rank_trimmed_mean(users_grads, corrupted_count)
 
 
+def phocas(users_grads, users_count, corrupted_count):
+    """Phocas (Xie, Koyejo and Gupta 2018; not in the reference): per column the corrupted_count-trimmed mean of Yin et al.
+    (`rank_trimmed_mean`'s bits), then the mean of the rows - corrupted_count values nearest to it (in fp64, rounded once;
+    ties in the distance go to the earlier row).  One library call, nothing read by the host.  The reference's signature;
+    users_count is accepted and unused (the rows are counted).  numpy in -> numpy out, device-resident in -> device-resident
+    out.  Not one of the `defend` keys: the reference's main.py offers only those four."""
+    assert users_grads.shape[0] >= 2 * corrupted_count + 1, (
+        'rows>=2*corrupted_count + 1', users_grads.shape[0], corrupted_count)
+    return get_engine().phocas(users_grads, corrupted_count)
+
+
+def mean_around(users_grads, users_count, corrupted_count, centre='median', keep=None):
+    """Per column the mean of the `keep` values nearest to a centre (default keep: rows - corrupted_count), in fp64 and
+    rounded once, ties in the distance going to the earlier row (Engine.window_mean).  centre='median': the coordinate-wise
+    median, `coordinate_median`'s bits -- with the default keep this is "MeaMed", the mean around the median of Xie, Koyejo
+    and Gupta 2018; the reference's `trimmed_mean` is the same rule with keep fixed at rows - corrupted_count - 1 and an
+    fp32 finish.  centre='trimmed': the corrupted_count-trimmed mean, which with the default keep is `phocas`.  Or a vector
+    of one float32 per column, on the device or the host.  A host matrix is uploaded once.  users_count is accepted and
+    unused.  Not one of the `defend` keys."""
+    rows = users_grads.shape[0]
+    if keep is None:
+        keep = rows - int(corrupted_count)
+    if isinstance(centre, str) and centre not in ('median', 'trimmed'):
+        raise ValueError("mean_around: centre is 'median', 'trimmed' or a vector, got %r" % (centre,))
+    if not 1 <= int(keep) <= rows:
+        raise ValueError('mean_around: keep %d outside 1..%d (the row count)' % (int(keep), rows))
+    engine = get_engine()
+    if not isinstance(centre, str):
+        return engine.window_mean(users_grads, centre, keep)
+    matrix, back = _upload_once(users_grads)
+    if centre == 'median':
+        around = engine.coordinate_median(matrix)
+    else:
+        assert rows >= 2 * corrupted_count + 1, ('rows>=2*corrupted_count + 1', rows, corrupted_count)
+        around = engine.rank_trimmed_mean(matrix, corrupted_count)
+    return back(engine.window_mean(matrix, around, keep))
+
+
 def dnc(users_grads, users_count, corrupted_count, niters=1, filter_frac=1.0, sub_dim=10000, power_iters=32, seed=0,
         columns=None, return_index=False):
     """DnC, the spectral defence (Shejwalkar and Houmansadr, NDSS 2021, Algorithm 2; not in the reference): in each of

@@ -779,6 +779,68 @@ class Engine:
             raise ValueError('rank_trimmed_mean needs a trim count')
         return self._rank_rule(g, trim_count, row_index, validate_index)
 
+    def _window_rule(self, g, centre, count, row_index, validate_index, want_radius):
+        """window_mean (a centre given, count = keep) and phocas (centre None, count = trim_count) share their plumbing:
+        (out, radius or None), device tensors, strided views and host matrices as `_rank_rule` takes them."""
+        dm = self._device_matrix(g)
+        if dm is None:
+            g = self._host_matrix(g)
+            if row_index is not None:
+                if np.size(row_index) == 0:
+                    raise ValueError('row_index selects no rows')
+                g = np.ascontiguousarray(g[np.asarray(row_index)])
+            n, d = g.shape
+            # a host matrix's extent is known here: refused before the library is touched (the device path leaves it to the library)
+            if centre is None and not 0 <= 2 * int(count) < n:
+                raise ValueError('phocas: trim_count %d must satisfy 0 <= 2 b < %d rows' % (int(count), n))
+            if centre is not None and not 1 <= int(count) <= n:
+                raise ValueError('window_mean: keep %d outside 1..%d (the row count)' % (int(count), n))
+            out = np.empty(d, dtype=np.float32)
+            radius = np.empty(d, dtype=np.float32) if want_radius else None
+            if centre is None:
+                _check(self.lib.byz_phocas_host(self.ctx, _hp(g), n, d, int(count), _hp(out), None, _hp(radius)))
+                return out, radius
+            c_host = np.ascontiguousarray(centre.numpy() if isinstance(centre, DeviceBuffer) else _to_host(centre),
+                                          dtype=np.float32).ravel()
+            if c_host.size != d:
+                raise ValueError('centre has %d entries, the matrix %d columns' % (c_host.size, d))
+            _check(self.lib.byz_window_mean_host(self.ctx, _hp(g), n, d, _hp(c_host), int(count), _hp(out), _hp(radius)))
+            return out, radius
+        with _Call(self) as c:
+            m = c.matrix(dm)
+            idx_ptr, n_rows = self._row_index(c, row_index, m, validate_index)
+            if n_rows == 0:
+                raise ValueError('row_index selects no rows')
+            if centre is not None:
+                centre = c.operand(centre, np.float32, _f32('centre has %(got)d entries, the matrix %(n)d columns'), m.cols,
+                                   convert=False)
+            out, ptr = c.out(m.cols)
+            radius, rptr = c.out(m.cols, want=want_radius)
+            if centre is None:
+                c.run(self.lib.byz_phocas_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, int(count), ptr, None, rptr,
+                                              c.stream))
+                return out, radius
+            c.run(self.lib.byz_window_mean_dev(self.ctx, m.ptr, n_rows, m.cols, m.ld, idx_ptr, centre.ptr, int(count), ptr, rptr,
+                                               c.stream))
+        return out, radius
+
+    def window_mean(self, g, centre, keep, row_index=None, validate_index=True, return_radius=False):
+        """Per column the mean of the `keep` values nearest to centre[column] (1 <= keep <= n), summed in fp64 and rounded to
+        float32 once: the rows are ranked by |fl32(x - c)|, ties in the order of the rows (of g[row_index] when given), every
+        NaN difference behind +inf.  `centre`: a device tensor or an array of `cols` float32 values.  return_radius=True
+        returns (out, radius): |x - c| of the last value kept, per column."""
+        if keep is None or centre is None:
+            raise ValueError('window_mean needs a centre and a keep count')
+        out, radius = self._window_rule(g, centre, keep, row_index, validate_index, return_radius)
+        return (out, radius) if return_radius else out
+
+    def phocas(self, g, trim_count, row_index=None, validate_index=True):
+        """Phocas (Xie, Koyejo and Gupta 2018): per column the mean of the n - b values nearest to the b-trimmed mean,
+        b = trim_count (0 <= b, 2 b < n) -- window_mean(g, rank_trimmed_mean(g, b), n - b), bit for bit, in one call."""
+        if trim_count is None:
+            raise ValueError('phocas needs a trim count')
+        return self._window_rule(g, None, trim_count, row_index, validate_index, False)[0]
+
     def trimmed_mean_redone(self, stream=None):
         """16-column tiles of the last trimmed mean that the ring selection handed to the general kernel."""
         return self._read(self.lib.byz_trimmed_mean_redone, [ctypes.c_int64], stream)[0]

@@ -103,8 +103,9 @@ class DeviceServer:
 
     # ---- server.py:86-90 ---------------------------------------------------------------------------
     def defend(self, defence_method, cur_epoch=None):
-        current_grads = defences.defend[defence_method](self.users_grads.data, self.n_users,
-                                                        int(self.n_users * self.mal_prop))
+        # one of the reference's four keys, or a rule of the reference's signature itself (defences.phocas, coordinate_median, ...)
+        rule = defence_method if callable(defence_method) else defences.defend[defence_method]
+        current_grads = rule(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop))
         # velocity = momentum * velocity - learning_rate * current_grads ; current_weights += velocity
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)

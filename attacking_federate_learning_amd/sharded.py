@@ -133,6 +133,14 @@ class HipKernels:
     def rank_trimmed_mean(self, g_local, trim_count, row_index=None):
         return self.engine.rank_trimmed_mean(g_local, trim_count, row_index=row_index, validate_index=False)
 
+    def window_mean(self, g_local, centre_local, keep, row_index=None, return_radius=False):
+        # column-local: this rank's slice of the matrix around this rank's slice of the centre
+        return self.engine.window_mean(g_local, centre_local, keep, row_index=row_index, validate_index=False,
+                                       return_radius=return_radius)
+
+    def phocas(self, g_local, trim_count, row_index=None):
+        return self.engine.phocas(g_local, trim_count, row_index=row_index, validate_index=False)
+
     def no_defense(self, g_local):
         return self.engine.no_defense(g_local)
 
@@ -369,6 +377,18 @@ class ShardedAggregator:
         assert g_local.shape[0] >= 2 * corrupted_count + 1, (
             'rows>=2*corrupted_count + 1', g_local.shape[0], corrupted_count)
         return self._maybe_gather(self.kernels.rank_trimmed_mean(g_local, corrupted_count), gather, total_columns)
+
+    def window_mean(self, g_local, centre_local, keep, gather=False, total_columns=None):
+        """columns layout: per column of the rank's own slice the mean of the `keep` values nearest to the rank's slice of the
+        centre (Engine.window_mean); no collective."""
+        return self._maybe_gather(self.kernels.window_mean(g_local, centre_local, keep), gather, total_columns)
+
+    def phocas(self, g_local, users_count, corrupted_count, gather=False, total_columns=None):
+        """columns layout: Phocas per column of the rank's own slice -- the corrupted_count-trimmed mean, then the mean of the
+        rows - corrupted_count values nearest to it; no collective."""
+        assert g_local.shape[0] >= 2 * corrupted_count + 1, (
+            'rows>=2*corrupted_count + 1', g_local.shape[0], corrupted_count)
+        return self._maybe_gather(self.kernels.phocas(g_local, corrupted_count), gather, total_columns)
 
     def robust_lr(self, g_local, users_count, corrupted_count, theta=None, gather=False, total_columns=None):
         """The robust learning rate round the mean, columns layout: the sign vote and the mean are local to a column, so

@@ -171,6 +171,35 @@ int byz_rank_trimmed_mean_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, 
                               int64_t ld, const int32_t* row_index_dev, int64_t trim_count,
                               float* out_dev, void* stream);
 
+/* ---- the mean of the values nearest a centre; Phocas (Xie, Koyejo and Gupta 2018; not in the reference) */
+/* Per column of the logical matrix (row r is G[row_index[r]] when row_index_dev is given), n = n_rows,   */
+/* c = centre_dev[column] (given, not found) and 1 <= keep <= n (else BYZ_E_INVALID):                     */
+/*   d      = fl32(col - c)                     one fp32 subtraction, never an FMA                        */
+/*   a      = |d|                                                                                         */
+/*   order  = np.argsort(a, kind='stable')      ties in |d| by LOGICAL row order; every NaN difference    */
+/*                                              behind +inf, in row order                                 */
+/*   kept   = order[:keep]                                                                                */
+/*   radius = a[order[keep - 1]]                radius_dev (optional, n_cols floats): exact bits; when it */
+/*                                              is NaN, which NaN is unspecified                          */
+/*   out    = fl32(sum of col[kept] in fp64 / keep)                                                       */
+/* The sum runs in a fixed order and is rounded to fp32 once after the division: the same bits on every   */
+/* run and for every ld, base alignment and matrix width.  With ref the exactly rounded mean of col[kept] */
+/* and mabs the mean of |col[kept]|: |out - ref| <= 2^-23 |ref| + 2^-30 mabs + 2^-149.  A kept NaN makes  */
+/* the column NaN, +inf and -inf both kept give NaN, one of them kept gives that infinity.  A non-finite  */
+/* centre is no special case (a NaN centre keeps the first `keep` rows).  A column whose kept values are  */
+/* all equal returns that value exactly.  More than 2^20 rows: BYZ_E_UNSUPPORTED.  Asynchronous on        */
+/* `stream`; nothing is launched when an argument is refused.                                             */
+int byz_window_mean_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                        const int32_t* row_index_dev, const float* centre_dev, int64_t keep,
+                        float* out_dev, float* radius_dev, void* stream);
+/* Phocas: the window of keep = n_rows - trim_count values around the bits byz_rank_trimmed_mean_dev      */
+/* returns for b = trim_count (0 <= b and 2 b < n, else BYZ_E_INVALID) -- by definition, so this call and */
+/* the two calls made by hand agree bit for bit.  centre_out_dev (optional, n_cols floats): that trimmed  */
+/* mean; radius_dev (optional) as above.  Must not alias each other or out_dev.                           */
+int byz_phocas_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld,
+                   const int32_t* row_index_dev, int64_t trim_count, float* out_dev,
+                   float* centre_out_dev, float* radius_dev, void* stream);
+
 /* ---- defences.bulyan (reference defences.py:55-70) ------------------------------------- */
 /* Selection loop on a distance matrix: theta = users_count - 2*corrupted_count picks, each */
 /* the Krum winner among the rows still present.  Exact fp64 running scores pick the winner  */
@@ -1212,6 +1241,13 @@ int byz_coordinate_median_host(byz_ctx* ctx, const float* G_host, int64_t n_rows
                                float* out_host);
 int byz_rank_trimmed_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
                                int64_t trim_count, float* out_host);
+
+/* byz_window_mean_dev and byz_phocas_dev on a host matrix (C-contiguous fp32): centre_host and out_host  */
+/* n_cols floats; radius_host and centre_out_host optional, n_cols floats each.  Synchronous.             */
+int byz_window_mean_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols,
+                         const float* centre_host, int64_t keep, float* out_host, float* radius_host);
+int byz_phocas_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t trim_count,
+                    float* out_host, float* centre_out_host, float* radius_host);
 
 /* DnC on a host matrix: columns_host (n_iters * sub_dim int64, as byz_dnc_dev's list; checked here: each in  */
 /* [0, n_cols), strictly ascending within an iteration, BYZ_E_INVALID otherwise), out_host (n_cols floats),    */
