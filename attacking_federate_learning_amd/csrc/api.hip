@@ -43,11 +43,13 @@ int read_i32(byz_ctx* ctx, const int32_t* dev, int32_t* host, int64_t count, hip
     return BYZ_OK;
 }
 
-// The device-side scalars (common.hpp: layout of ctx->small) in one read-back; the sticky status word is checked and
-// cleared here, so that every entry point that synchronises anyway also reports what a kernel could only flag.
-int read_small(byz_ctx* ctx, int32_t (&words)[kSmallWords], hipStream_t stream) {
-    BYZ_TRY(read_i32(ctx, ctx->small.as<int32_t>(), words, kSmallWords, stream));
-    const int32_t sticky = words[kWordStatus];
+// The first `bytes` of the device scalars (device_scalars.hpp: `host` is a CoreScalars or the whole DeviceScalars, which begins
+// with one) in one read-back; the sticky status word is checked and cleared here, so that every entry point that synchronises
+// anyway also reports what a kernel could only flag.
+int read_scalars(byz_ctx* ctx, void* host, size_t bytes, hipStream_t stream) {
+    BYZ_TRY(read_i32(ctx, ctx->scalars.as<int32_t>(), static_cast<int32_t*>(host), static_cast<int64_t>(bytes / sizeof(int32_t)), stream));
+    const CoreScalars& core = *static_cast<const CoreScalars*>(host);
+    const int32_t sticky = core.status;
     if (sticky != 0) {
         BYZ_HIP(hipMemsetAsync(device_status_word(ctx), 0, sizeof(int32_t), stream));
         if (sticky & kStatusLostTicket) {
@@ -71,32 +73,44 @@ int read_small(byz_ctx* ctx, int32_t (&words)[kSmallWords], hipStream_t stream) 
             return BYZ_E_UNSUPPORTED;
         }
         set_error("distances: %d near-duplicate pairs exceed the list capacity (BYZ_NEAR_PAIR_CAPACITY); their distances "
-                  "were not re-evaluated", words[kWordNearPairs]);
+                  "were not re-evaluated", core.near_pairs);
         return BYZ_E_UNSUPPORTED;
     }
     return BYZ_OK;
 }
 
-// read_small where nothing but the flagged failures is of interest: synchronises; a kernel that flagged one makes the call fail
-int check_small(byz_ctx* ctx, hipStream_t stream) {
-    int32_t words[kSmallWords];
-    return read_small(ctx, words, stream);
+// what a hot path reads: the core alone
+int read_core(byz_ctx* ctx, CoreScalars* core, hipStream_t stream) { return read_scalars(ctx, core, sizeof *core, stream); }
+
+// read_core where nothing but the flagged failures is of interest: synchronises; a kernel that flagged one makes the call fail
+int check_core(byz_ctx* ctx, hipStream_t stream) {
+    CoreScalars core;
+    return read_core(ctx, &core, stream);
+}
+
+// What every byz_*_info call does before it copies its fields out: the whole block in one read-back on the stream of the last
+// call that wrote the report (which synchronises it), the sticky status with it.  refusal (optional): the error of a report
+// that is refused before a first call; the others report the zeroed block.
+int read_report(byz_ctx* ctx, ReportKind kind, const char* refusal, DeviceScalars* all) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(refusal == nullptr || ctx->last[kind].ran, "%s", refusal);
+    return read_scalars(ctx, all, sizeof *all, ctx->last[kind].stream);
 }
 
 // the Krum winner's index to the host, when the caller asked for it (one synchronisation, the status word with it)
 int read_winner(byz_ctx* ctx, int32_t* index_host, hipStream_t stream) {
     if (!index_host) return BYZ_OK;
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, stream));
-    *index_host = words[kWordKrumWinner];
+    CoreScalars core;
+    BYZ_TRY(read_core(ctx, &core, stream));
+    *index_host = core.krum_winner;
     return BYZ_OK;
 }
 
 // the near-duplicate pairs the last distance kernel listed, refused when the list could not hold them
 int near_pair_count(byz_ctx* ctx, int64_t* count, hipStream_t stream) {
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, stream));
-    *count = words[kWordNearPairs];
+    CoreScalars core;
+    BYZ_TRY(read_core(ctx, &core, stream));
+    *count = core.near_pairs;
     if (*count > ctx->near_pair_capacity) {
         set_error("distances: %lld near-duplicate pairs exceed the list capacity %lld (BYZ_NEAR_PAIR_CAPACITY)", (long long)*count,
                   (long long)ctx->near_pair_capacity);
@@ -186,15 +200,11 @@ class HostStage {
     }
     float* G() const { return ctx_->stage_in.as<float>(); }
     hipStream_t stream() const { return nullptr; }
-    // the two endings.  finish: the downloads queued, then the device scalars read back and the status word checked (`words`: for
-    // a wrapper that reports one of them)
-    int finish(int32_t (&words)[kSmallWords]) {
+    // the two endings.  finish: the downloads queued, then the device scalars read back and the status word checked (`all`: the
+    // whole block, for a wrapper that reports a field of it; the core alone otherwise)
+    int finish(DeviceScalars* all = nullptr) {
         BYZ_TRY(download());
-        return read_small(ctx_, words, stream());
-    }
-    int finish() {
-        int32_t words[kSmallWords];
-        return finish(words);
+        return all != nullptr ? read_scalars(ctx_, all, sizeof *all, stream()) : check_core(ctx_, stream());
     }
     // finish_sync: the downloads queued, then the stream synchronised and nothing else
     int finish_sync() {
@@ -246,12 +256,11 @@ int bulyan_select(byz_ctx* ctx, const float* dist, int64_t n, int64_t users_coun
     const int64_t krum_prefix = krum_winner_dev != nullptr ? python_prefix_len(n - 1, users_count - corrupted) : 0;
     BYZ_TRY(launch_row_sort(ctx, dist, n, krum_prefix, drop, true, stream));
     if (krum_winner_dev != nullptr) BYZ_TRY(launch_krum_argmin(ctx, n, krum_winner_dev, stream));
-    int32_t* status_dev = ctx->small.as<int32_t>() + kWordBulyanStatus;   // (the re-scored rows' count is the word behind it)
-    BYZ_TRY(launch_bulyan_loop(ctx, dist, n, theta, drop, users_count, corrupted, selection_dev, status_dev, stream));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, stream));
-    const int32_t status = words[kWordBulyanStatus];
-    ctx->bulyan_rescored = words[kWordBulyanRescored];
+    BYZ_TRY(launch_bulyan_loop(ctx, dist, n, theta, drop, users_count, corrupted, selection_dev, &device_scalars(ctx)->core.bulyan, stream));
+    CoreScalars core;
+    BYZ_TRY(read_core(ctx, &core, stream));
+    const int32_t status = core.bulyan.status;
+    ctx->bulyan_rescored = core.bulyan.rescored;
     if (status == 2) {
         set_error("bulyan: the selection loop's workgroups lost contact with each other (exchange timed out)");
         return BYZ_E_HIP;
@@ -433,7 +442,7 @@ int byz_ctx_create(int device, byz_ctx** out) {
     byz_ctx* ctx = new byz_ctx();
     ctx->device = device;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (ctx->small.ensure(256) != BYZ_OK || hipMemset(ctx->small.ptr, 0, 256) != hipSuccess) {
+    if (ctx->scalars.ensure(sizeof(DeviceScalars)) != BYZ_OK || hipMemset(ctx->scalars.ptr, 0, sizeof(DeviceScalars)) != hipSuccess) {
         delete ctx;   // (frees what was allocated)
         set_error("byz_ctx_create: cannot allocate the device scalars");
         return BYZ_E_HIP;
@@ -576,7 +585,7 @@ int byz_near_pairs_apply_dev(byz_ctx* ctx, const double* sq_dev, int64_t n_rows,
 
 int byz_ctx_check(byz_ctx* ctx, void* stream) {
     BYZ_TRY(enter(ctx));
-    return check_small(ctx, as_stream(stream));
+    return check_core(ctx, as_stream(stream));
 }
 
 int byz_bulyan_rescored(const byz_ctx* ctx, int64_t* rows_host) {
@@ -819,11 +828,11 @@ int geometric_median(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, in
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
     double *sq = t.a, *w = t.b;
-    int32_t* words = geomed_words(ctx);
-    const int32_t* done = words + kGeomedDone;
-    const int32_t* fallback = words + kGeomedFallback;
-    BYZ_HIP(hipMemsetAsync(words + kGeomedDone, 0, 6 * sizeof(int32_t), s));     // [20, 26): done .. objective
-    ctx->geomed_stream = s;
+    GeomedReport* report = &device_scalars(ctx)->geomed;
+    const int32_t* done = &report->done;
+    const int32_t* fallback = &report->fallback;
+    BYZ_HIP(hipMemsetAsync(report, 0, sizeof *report, s));
+    mark(ctx, kReportGeomed, s);
     // mean0: no_defense's kernel, then its finiteness; the fallback's launches return at once when it is finite
     BYZ_TRY(launch_column_mean(ctx, G, n, n_cols, ld, out, s));
     if (allreduce == nullptr) {
@@ -893,12 +902,11 @@ int byz_geometric_median_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_row
 }
 
 int byz_geometric_median_info(byz_ctx* ctx, int64_t* iterations, int64_t* excluded_rows, double* objective) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->geomed_stream));   // synchronises the last call's stream
-    if (iterations) *iterations = words[kGeomedIterations];
-    if (excluded_rows) *excluded_rows = words[kGeomedExcluded];
-    if (objective) std::memcpy(objective, words + kGeomedObjective, sizeof(double));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportGeomed, nullptr, &all));
+    if (iterations) *iterations = all.geomed.iterations;
+    if (excluded_rows) *excluded_rows = all.geomed.excluded;
+    if (objective) *objective = all.geomed.objective;
     return BYZ_OK;
 }
 
@@ -943,7 +951,7 @@ int centered_clip(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
     double *sq = t.a, *scale = t.b;
-    ctx->cclip_stream = s;
+    mark(ctx, kReportCclip, s);
     const size_t vec_bytes = static_cast<size_t>(n_cols) * sizeof(float);
     if (start == nullptr) BYZ_HIP(hipMemsetAsync(out, 0, vec_bytes, s));
     else if (start != out) BYZ_HIP(hipMemcpyAsync(out, start, vec_bytes, hipMemcpyDeviceToDevice, s));
@@ -993,11 +1001,10 @@ int byz_centered_clip_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, 
 }
 
 int byz_centered_clip_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->cclip_stream));   // synchronises the last call's stream
-    if (clipped_rows) *clipped_rows = words[kCclipClipped];
-    if (excluded_rows) *excluded_rows = words[kCclipExcluded];
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportCclip, nullptr, &all));
+    if (clipped_rows) *clipped_rows = all.cclip.clipped;
+    if (excluded_rows) *excluded_rows = all.cclip.excluded;
     return BYZ_OK;
 }
 
@@ -1012,13 +1019,12 @@ int fltrust(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld,
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n, n_cols, &t, 2));
     double *pq = t.a, *ts = t.b, *w = t.b + n;
-    ctx->fltrust_stream = s;
+    mark(ctx, kReportFltrust, s);
     BYZ_TRY(launch_row_sqdist(ctx, root, 1, n_cols, n_cols, nullptr, t.root, pq + 2 * n, nullptr, nullptr, s));
     BYZ_TRY(launch_row_dots(ctx, G, n, n_cols, ld, root, t.partials, pq, pq + n, s));
     if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, pq, 2 * n + 1, stream, "fltrust (dots and norms)"));
     BYZ_TRY(launch_fltrust_trust(ctx, pq, n, ts, w, s));
-    const double* T = reinterpret_cast<const double*>(geomed_words(ctx) + kFltrustTrustSum);
-    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, w, T, out, s));      // (out may be root: its last reader is behind)
+    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, w, &device_scalars(ctx)->fltrust.trust_sum, out, s));      // (out may be root: its last reader is behind)
     const size_t row_bytes = static_cast<size_t>(n) * sizeof(double);
     if (trust != nullptr) BYZ_HIP(hipMemcpyAsync(trust, ts, row_bytes, hipMemcpyDeviceToDevice, s));
     if (weights != nullptr) BYZ_HIP(hipMemcpyAsync(weights, w, row_bytes, hipMemcpyDeviceToDevice, s));
@@ -1070,13 +1076,12 @@ int byz_fltrust_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_
 }
 
 int byz_fltrust_info(byz_ctx* ctx, int64_t* trusted_rows, int64_t* excluded_rows, int32_t* root_ok, double* trust_sum) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->fltrust_stream));   // synchronises the last call's stream
-    if (trusted_rows) *trusted_rows = words[kFltrustTrusted];
-    if (excluded_rows) *excluded_rows = words[kFltrustExcluded];
-    if (root_ok) *root_ok = words[kFltrustRootOk];
-    if (trust_sum) std::memcpy(trust_sum, words + kFltrustTrustSum, sizeof(double));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportFltrust, nullptr, &all));
+    if (trusted_rows) *trusted_rows = all.fltrust.trusted;
+    if (excluded_rows) *excluded_rows = all.fltrust.excluded;
+    if (root_ok) *root_ok = all.fltrust.root_ok;
+    if (trust_sum) *trust_sum = all.fltrust.trust_sum;
     return BYZ_OK;
 }
 
@@ -1110,13 +1115,12 @@ int signguard(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t l
     hipStream_t s = as_stream(stream);
     SgScratch t;
     BYZ_TRY(signguard_workspace(ctx, n, n_cols, &t));
-    ctx->signguard_stream = s;
+    mark(ctx, kReportSignguard, s);
     BYZ_TRY(launch_row_signs(ctx, t, G, n, n_cols, ld, win_start, win_len, nullptr, nullptr, t.pznq, s));
     if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, t.pznq, 4 * n, stream, "signguard (counts and norms)"));
     BYZ_TRY(launch_signguard_select(ctx, t, t.pznq, n, p->window_len, p->lower, p->upper, p->bandwidth, sample, p->n_sample,
                                     keep ? keep : t.keep, t.w, labels ? labels : t.labels, nullptr, s));
-    const double* K = reinterpret_cast<const double*>(geomed_words(ctx) + kSgKeptF64);
-    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, t.w, K, out, s));
+    BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, t.w, &device_scalars(ctx)->sg.kept_f64, out, s));
     if (weights != nullptr)
         BYZ_HIP(hipMemcpyAsync(weights, t.w, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToDevice, s));
     return BYZ_OK;
@@ -1144,7 +1148,7 @@ int byz_signguard_select_dev(byz_ctx* ctx, const int64_t* counts, const double* 
     hipStream_t s = as_stream(stream);
     SgScratch t;
     BYZ_TRY(signguard_workspace(ctx, n_rows, 0, &t));
-    ctx->signguard_stream = s;
+    mark(ctx, kReportSignguard, s);
     BYZ_TRY(launch_signguard_counts_f64(ctx, reinterpret_cast<const long long*>(counts), q, n_rows, t.pznq, s));
     return launch_signguard_select(ctx, t, t.pznq, n_rows, params->window_len, params->lower, params->upper, params->bandwidth, sample,
                                    params->n_sample, keep ? keep : t.keep, weights ? weights : t.w, labels ? labels : t.labels, mk, s);
@@ -1184,16 +1188,15 @@ int byz_signguard_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int6
 
 int byz_signguard_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* norm_failed_rows, int64_t* outside_rows, int64_t* clusters,
                        int64_t* seeds, double* bandwidth, double* median_norm) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->signguard_stream));   // synchronises the last call's stream
-    if (kept_rows) *kept_rows = words[kSgKept];
-    if (norm_failed_rows) *norm_failed_rows = words[kSgNormFailed];
-    if (outside_rows) *outside_rows = words[kSgOutside];
-    if (clusters) *clusters = words[kSgClusters];
-    if (seeds) *seeds = words[kSgSeeds];
-    if (bandwidth) std::memcpy(bandwidth, words + kSgBandwidth, sizeof(double));
-    if (median_norm) std::memcpy(median_norm, words + kSgMedian, sizeof(double));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportSignguard, nullptr, &all));
+    if (kept_rows) *kept_rows = all.sg.kept;
+    if (norm_failed_rows) *norm_failed_rows = all.sg.norm_failed;
+    if (outside_rows) *outside_rows = all.sg.outside;
+    if (clusters) *clusters = all.sg.clusters;
+    if (seeds) *seeds = all.sg.seeds;
+    if (bandwidth) *bandwidth = all.sg.bandwidth;
+    if (median_norm) *median_norm = all.sg.median;
     return BYZ_OK;
 }
 
@@ -1243,7 +1246,7 @@ int nnm(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, int
     BYZ_TRY(ctx->nnm_lists.ensure(list_bytes + static_cast<size_t>(n) * sizeof(int32_t)));
     int32_t* nbr = ctx->nnm_lists.as<int32_t>();
     int32_t* counts = nbr + n * k;
-    ctx->nnm_stream = s;
+    mark(ctx, kReportNnm, s);
     BYZ_TRY(distances(ctx, G, n, n_cols, ld, allreduce, user, ctx->dist.as<float>(), stream));
     BYZ_TRY(launch_nnm_neighbours(ctx, ctx->dist.as<float>(), n, k, nbr, counts, s));
     BYZ_TRY(launch_nnm_mix(ctx, G, n, n_cols, ld, nbr, counts, k, Y, ldy, s));
@@ -1257,7 +1260,7 @@ int byz_nnm_neighbours_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int6
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_nnm("nnm_neighbours", n_rows, k));
     BYZ_REQUIRE(dist && nbr, "nnm_neighbours: null distances or output");
-    ctx->nnm_stream = as_stream(stream);
+    mark(ctx, kReportNnm, as_stream(stream));
     return launch_nnm_neighbours(ctx, dist, n_rows, k, nbr, counts, as_stream(stream));
 }
 
@@ -1292,11 +1295,10 @@ int byz_nnm_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_
 }
 
 int byz_nnm_info(byz_ctx* ctx, int64_t* solo_rows, int64_t* short_rows) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->nnm_stream));   // synchronises the last call's stream
-    if (solo_rows) *solo_rows = words[kNnmSolo];
-    if (short_rows) *short_rows = words[kNnmShort];
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportNnm, nullptr, &all));
+    if (solo_rows) *solo_rows = all.nnm.solo;
+    if (short_rows) *short_rows = all.nnm.short_rows;
     return BYZ_OK;
 }
 
@@ -1319,7 +1321,7 @@ int byz_sign_votes_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "sign_votes"));
     BYZ_REQUIRE(votes, "sign_votes: null output");
     BYZ_TRY(check_row_ceiling("sign_votes", n_rows));
-    ctx->rlr_stream = as_stream(stream);
+    mark(ctx, kReportRlr, as_stream(stream));
     return launch_sign_votes(ctx, G, n_rows, n_cols, ld, 0, nullptr, votes, as_stream(stream));
 }
 
@@ -1327,7 +1329,7 @@ int byz_sign_flip_dev(byz_ctx* ctx, const float* agg, const int32_t* votes, int6
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(agg && votes && out && n_cols > 0, "sign_flip: null vector or no columns (%lld)", (long long)n_cols);
     BYZ_TRY(check_rlr_theta("sign_flip", theta, kLargeMaxRows));
-    ctx->rlr_stream = as_stream(stream);
+    mark(ctx, kReportRlr, as_stream(stream));
     return launch_sign_flip(ctx, agg, votes, n_cols, theta, out, as_stream(stream));
 }
 
@@ -1339,15 +1341,14 @@ int byz_robust_lr_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     BYZ_TRY(check_row_ceiling("robust_lr", n_rows));
     BYZ_TRY(check_rlr_theta("robust_lr", theta, n_rows));
     BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "robust_lr"));
-    ctx->rlr_stream = as_stream(stream);
+    mark(ctx, kReportRlr, as_stream(stream));
     return launch_sign_votes(ctx, G, n_rows, n_cols, ld, theta, out, votes, as_stream(stream));
 }
 
 int byz_robust_lr_info(byz_ctx* ctx, int64_t* flipped_cols) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->rlr_stream));   // synchronises the last call's stream
-    if (flipped_cols) std::memcpy(flipped_cols, words + kRlrFlipped, sizeof(int64_t));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportRlr, nullptr, &all));
+    if (flipped_cols) *flipped_cols = static_cast<int64_t>(all.rlr.flipped);
     return BYZ_OK;
 }
 
@@ -1403,7 +1404,7 @@ int byz_topk_sparsify_dev(byz_ctx* ctx, const float* x, const float* add, int64_
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(x && out && n > 0, "topk_sparsify: null vector or no columns (%lld)", (long long)n);
     BYZ_TRY(check_topk("topk_sparsify", x, add, n, n, k, out, residual));
-    ctx->topk_stream = as_stream(stream);
+    mark(ctx, kReportTopk, as_stream(stream));
     return launch_topk_sparsify(ctx, x, add, n, k, 0, 1, nullptr, nullptr, out, residual, 0, stream);
 }
 
@@ -1418,18 +1419,17 @@ int byz_topk_sparsify_sharded_dev(byz_ctx* ctx, const float* x, const float* add
                 "topk_sparsify_sharded: rank %d of %d", rank_index, rank_count);
     BYZ_REQUIRE(n_local == 0 || (x && out), "topk_sparsify_sharded: null vector");
     BYZ_TRY(check_topk("topk_sparsify_sharded", x, add, n_local, n_total, k, out, residual));
-    ctx->topk_stream = as_stream(stream);
+    mark(ctx, kReportTopk, as_stream(stream));
     return launch_topk_sparsify(ctx, x, add, n_local, k, rank_index, rank_count, allreduce, user, out, residual, 0, stream);
 }
 
 int byz_topk_info(byz_ctx* ctx, int64_t* selected, uint32_t* threshold_key, int64_t* ties, int64_t* ties_taken) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->topk_stream));   // synchronises the last call's stream
-    if (selected) std::memcpy(selected, words + kTopkSelected, sizeof(int64_t));
-    if (ties) std::memcpy(ties, words + kTopkTies, sizeof(int64_t));
-    if (ties_taken) std::memcpy(ties_taken, words + kTopkTaken, sizeof(int64_t));
-    if (threshold_key) std::memcpy(threshold_key, words + kTopkKey, sizeof(uint32_t));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportTopk, nullptr, &all));
+    if (selected) *selected = static_cast<int64_t>(all.topk.selected);
+    if (ties) *ties = static_cast<int64_t>(all.topk.ties);
+    if (ties_taken) *ties_taken = static_cast<int64_t>(all.topk.taken);
+    if (threshold_key) *threshold_key = static_cast<uint32_t>(all.topk.key);
     return BYZ_OK;
 }
 
@@ -1446,7 +1446,7 @@ int byz_sparsefed_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     float* agg = topk_aggregate_workspace(ctx, n_cols);
     if (agg == nullptr) return BYZ_E_HIP;
     BYZ_TRY(centered_clip(ctx, G, n_rows, n_cols, ld, &clip, nullptr, nullptr, nullptr, agg, nullptr, stream));
-    ctx->topk_stream = as_stream(stream);
+    mark(ctx, kReportTopk, as_stream(stream));
     return launch_topk_sparsify(ctx, residual, agg, n_cols, params->k, 0, 1, nullptr, nullptr, out, residual, n_cols, stream);
 }
 
@@ -1511,17 +1511,16 @@ int byz_clip_scales_dev(byz_ctx* ctx, const double* sq, int64_t n_rows, const by
     BYZ_REQUIRE(sq && scales && n_rows > 0, "clip_scales: null norms or scales, or no rows (%lld)", (long long)n_rows);
     BYZ_REQUIRE(params && (params->adaptive || params->clip > 0.0), "clip_scales: null parameters, or clip not > 0 in the fixed mode");
     BYZ_TRY(check_row_ceiling("clip_scales", n_rows));
-    ctx->weak_dp_stream = as_stream(stream);
+    mark(ctx, kReportWeakDp, as_stream(stream));
     return launch_clip_scales(ctx, sq, n_rows, params->clip, params->adaptive != 0, scales, clip_dev, as_stream(stream));
 }
 
 int byz_weak_dp_info(byz_ctx* ctx, int64_t* clipped_rows, int64_t* excluded_rows, double* clip) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->weak_dp_stream));   // synchronises the last call's stream
-    if (clipped_rows) *clipped_rows = words[kWeakDpClipped];
-    if (excluded_rows) *excluded_rows = words[kWeakDpExcluded];
-    if (clip) std::memcpy(clip, words + kWeakDpClip, sizeof(double));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportWeakDp, nullptr, &all));
+    if (clipped_rows) *clipped_rows = all.weak_dp.clipped;
+    if (excluded_rows) *excluded_rows = all.weak_dp.excluded;
+    if (clip) *clip = all.weak_dp.clip;
     return BYZ_OK;
 }
 
@@ -1538,14 +1537,14 @@ int byz_weak_dp_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n_rows, n_cols, &t));
     double *sq = t.a, *scale = t.b;
-    ctx->weak_dp_stream = s;
+    mark(ctx, kReportWeakDp, s);
     BYZ_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(n_cols) * sizeof(float), s));
     BYZ_TRY(launch_row_sqdist(ctx, G, n_rows, n_cols, ld, out, t.partials, sq, nullptr, nullptr, s));
     BYZ_TRY(launch_clip_scales(ctx, sq, n_rows, params->clip, adaptive, scale, nullptr, s));
     BYZ_TRY(launch_clip_update(ctx, G, n_rows, n_cols, ld, out, scale, out, s));
     if (params->sigma == 0.0) return BYZ_OK;               // the clipped mean's bits
     return launch_gaussian_noise(ctx, out, n_cols, params->sigma, params->seed, params->round, params->column_offset,
-                                 adaptive ? weak_dp_clip_word(ctx) : nullptr, out, s);
+                                 adaptive ? &device_scalars(ctx)->weak_dp.clip : nullptr, out, s);
 }
 
 // ---- FLAME (Nguyen et al., USENIX Security 2022; beyond the reference) -------------------------------------------------------
@@ -1616,9 +1615,8 @@ int flame(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, c
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
     double *sq = t.a, *scale = t.b;
-    ctx->flame_stream = s;
-    ctx->flame_selected = true;
-    ctx->weak_dp_stream = s;
+    mark(ctx, kReportFlame, s);
+    mark(ctx, kReportWeakDp, s);
     const float* dist = dist_in;
     if (dist == nullptr) {
         BYZ_TRY(ctx->dist.ensure(static_cast<size_t>(n) * n * sizeof(float)));
@@ -1634,7 +1632,7 @@ int flame(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, c
     BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, f.w, &f.info->admitted_f64, out, s));
     if (params->lambda == 0.0) return BYZ_OK;              // the clipped mean's bits
     return launch_gaussian_noise(ctx, out, n_cols, params->lambda, params->seed, params->round, params->column_offset,
-                                 weak_dp_clip_word(ctx), out, s);
+                                 &device_scalars(ctx)->weak_dp.clip, out, s);
 }
 
 }  // namespace
@@ -1670,10 +1668,9 @@ int byz_flame_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_
     BYZ_TRY(check_flame_select("flame_select", n_rows, min_cluster_size, min_samples));
     FlameScratch f;
     BYZ_TRY(flame_workspace(ctx, n_rows, &f));
-    ctx->flame_stream = as_stream(stream);
-    ctx->flame_selected = true;
-    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), ctx->flame_stream));
-    return launch_flame_select(ctx, f, dist, n_rows, min_cluster_size, min_samples, admitted, ctx->flame_stream);
+    mark(ctx, kReportFlame, as_stream(stream));
+    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), as_stream(stream)));
+    return launch_flame_select(ctx, f, dist, n_rows, min_cluster_size, min_samples, admitted, as_stream(stream));
 }
 
 int byz_flame_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_flame_params* params,
@@ -1698,12 +1695,9 @@ int byz_flame_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t 
 }
 
 int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, double* w_star, double* clip) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(ctx->flame_selected, "flame_info: no FLAME selection on this context yet");
-    BYZ_TRY(check_small(ctx, ctx->flame_stream));            // synchronises the last call's stream
-    FlameInfo info;
-    static_assert(sizeof(FlameInfo) == kFlameInfoWords * sizeof(int32_t), "whole words");
-    BYZ_TRY(read_i32(ctx, ctx->flame_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kFlameInfoWords, ctx->flame_stream));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportFlame, "flame_info: no FLAME selection on this context yet", &all));
+    const FlameInfo& info = all.flame;
     if (admitted_rows) *admitted_rows = info.admitted;
     if (broken_rows) *broken_rows = info.broken_rows;
     if (w_star) *w_star = static_cast<double>(info.w_star);
@@ -1754,10 +1748,9 @@ int clipped_clustering(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, 
     RowScratch t;
     BYZ_TRY(row_scratch(ctx, n, n_cols, &t));
     double* scale = t.b;
-    ctx->linkage_stream = s;
-    ctx->linkage_ran = true;
-    ctx->clipped_clustering_selected = true;
-    ctx->weak_dp_stream = s;
+    mark(ctx, kReportLinkage, s);
+    mark(ctx, kReportClippedClustering, s);
+    mark(ctx, kReportWeakDp, s);
     const float* dist = dist_in;
     if (dist == nullptr) {
         BYZ_TRY(ctx->dist.ensure(static_cast<size_t>(n) * n * sizeof(float)));
@@ -1789,18 +1782,15 @@ int byz_linkage_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int method,
     BYZ_TRY(check_linkage("linkage", n_rows, method, fill));
     LinkageScratch f;
     BYZ_TRY(linkage_workspace(ctx, n_rows, &f));
-    ctx->linkage_stream = as_stream(stream);
-    ctx->linkage_ran = true;
-    return launch_linkage(ctx, f, dist, n_rows, method, *fill, pair, height, size, usable_rows, ctx->linkage_stream);
+    mark(ctx, kReportLinkage, as_stream(stream));
+    ctx->last[kReportClippedClustering].stream = as_stream(stream);   // (one LinkageInfo: its other info call follows the last writer too)
+    return launch_linkage(ctx, f, dist, n_rows, method, *fill, pair, height, size, usable_rows, as_stream(stream));
 }
 
 int byz_linkage_info(byz_ctx* ctx, int64_t* merges, int64_t* rescans, int64_t* max_rescans) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(ctx->linkage_ran, "linkage_info: no linkage on this context yet");
-    BYZ_TRY(check_small(ctx, ctx->linkage_stream));          // synchronises the last call's stream
-    LinkageInfo info;
-    static_assert(sizeof(LinkageInfo) == kLinkageInfoWords * sizeof(int32_t), "whole words");
-    BYZ_TRY(read_i32(ctx, ctx->linkage_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kLinkageInfoWords, ctx->linkage_stream));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportLinkage, "linkage_info: no linkage on this context yet", &all));
+    const LinkageInfo& info = all.linkage;
     if (merges) *merges = info.steps;
     if (rescans) *rescans = info.rescans;
     if (max_rescans) *max_rescans = info.max_rescans;
@@ -1824,11 +1814,10 @@ int byz_clipped_clustering_select_dev(byz_ctx* ctx, const float* dist, int64_t n
     BYZ_TRY(check_linkage("clipped_clustering_select", n_rows, method, fill));
     LinkageScratch f;
     BYZ_TRY(linkage_workspace(ctx, n_rows, &f));
-    ctx->linkage_stream = as_stream(stream);
-    ctx->linkage_ran = true;
-    ctx->clipped_clustering_selected = true;
-    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), ctx->linkage_stream));
-    return launch_clipped_clustering_select(ctx, f, dist, n_rows, method, *fill, admitted, ctx->linkage_stream);
+    mark(ctx, kReportLinkage, as_stream(stream));
+    mark(ctx, kReportClippedClustering, as_stream(stream));
+    BYZ_HIP(hipMemsetAsync(&f.info->clip, 0, sizeof(double), as_stream(stream)));
+    return launch_clipped_clustering_select(ctx, f, dist, n_rows, method, *fill, admitted, as_stream(stream));
 }
 
 int byz_clipped_clustering_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,
@@ -1855,11 +1844,9 @@ int byz_clipped_clustering_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_r
 
 int byz_clipped_clustering_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* usable_rows, double* top_height, double* second_height,
                                 double* clip) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(ctx->clipped_clustering_selected, "clipped_clustering_info: no ClippedClustering selection on this context yet");
-    BYZ_TRY(check_small(ctx, ctx->linkage_stream));          // synchronises the last call's stream
-    LinkageInfo info;
-    BYZ_TRY(read_i32(ctx, ctx->linkage_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kLinkageInfoWords, ctx->linkage_stream));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportClippedClustering, "clipped_clustering_info: no ClippedClustering selection on this context yet", &all));
+    const LinkageInfo& info = all.linkage;
     if (admitted_rows) *admitted_rows = info.admitted;
     if (usable_rows) *usable_rows = info.usable;
     if (top_height) *top_height = info.top_height;
@@ -1899,11 +1886,6 @@ int manhattan_distances(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols,
     return launch_manhattan_from_sums(ctx, sums, n, dist, s);
 }
 
-void mm_selected(byz_ctx* ctx, hipStream_t s) {
-    ctx->multi_metrics_stream = s;
-    ctx->multi_metrics_selected = true;
-}
-
 // The whole call; allreduce == nullptr: one GPU holds every column.  ONE Gram serves the Euclidean and the cosine matrix: the
 // distances' own path leaves it in ctx->gram untouched (launch_distances_from_gram reads it), and cosine_from_gram reads the
 // same doubles byz_cosine_distances_dev would have computed, launch_gram being deterministic.  Where the Euclidean matrix
@@ -1915,7 +1897,7 @@ int multi_metrics(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64
     MmScratch t;
     BYZ_TRY(multi_metrics_workspace(ctx, n, true, &t));
     BYZ_TRY(ensure_distance_workspaces(ctx, n));
-    mm_selected(ctx, s);
+    mark(ctx, kReportMultiMetrics, s);
     float* euc = ctx->dist.as<float>();
     double* gram = ctx->gram.as<double>();
     BYZ_TRY(distances(ctx, G, n, n_cols, ld, allreduce, user, euc, stream));
@@ -1983,7 +1965,7 @@ int byz_multi_metrics_select_dev(byz_ctx* ctx, const double* features, int64_t n
     BYZ_TRY(check_mm_keep("multi_metrics_select", n_rows, keep));
     MmScratch t;
     BYZ_TRY(multi_metrics_workspace(ctx, n_rows, false, &t));
-    mm_selected(ctx, as_stream(stream));
+    mark(ctx, kReportMultiMetrics, as_stream(stream));
     return launch_mm_select(ctx, t, features, n_rows, keep, flags, scores, as_stream(stream));
 }
 
@@ -2003,13 +1985,9 @@ int byz_multi_metrics_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, 
 }
 
 int byz_multi_metrics_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* usable_rows, int32_t* degenerate, double* det) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(ctx->multi_metrics_selected, "multi_metrics_info: no Multi-Metrics selection on this context yet");
-    BYZ_TRY(check_small(ctx, ctx->multi_metrics_stream));      // synchronises the last call's stream
-    MmInfo info;
-    static_assert(sizeof(MmInfo) == kMmInfoWords * sizeof(int32_t), "whole words");
-    BYZ_TRY(read_i32(ctx, ctx->multi_metrics_info.as<int32_t>(), reinterpret_cast<int32_t*>(&info), kMmInfoWords,
-                     ctx->multi_metrics_stream));
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportMultiMetrics, "multi_metrics_info: no Multi-Metrics selection on this context yet", &all));
+    const MmInfo& info = all.mm;
     if (kept_rows) *kept_rows = info.kept;
     if (usable_rows) *usable_rows = info.usable;
     if (degenerate) *degenerate = info.degenerate;
@@ -2062,7 +2040,7 @@ int dnc_select(byz_ctx* ctx, const float* G, int64_t n, int64_t ld, const byz_dn
         }
     BYZ_REQUIRE(columns || widest == 0, "dnc: null column list");
     BYZ_TRY(dnc_workspace(ctx, n, widest, t));
-    ctx->dnc_stream = s;
+    mark(ctx, kReportDnc, s);
     const int64_t n_keep = n - params->remove_count;
     const int64_t* cols = columns;
     for (int64_t k = 0; k < params->n_iters; ++k) {
@@ -2079,7 +2057,7 @@ int dnc(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, con
     DncScratch t;
     BYZ_TRY(dnc_select(ctx, G, n, ld, params, columns, local_counts, allreduce, user, good_out, nullptr, &t, stream));
     // the kept rows are known on the device alone: the row-list mean reads their count there
-    return launch_column_mean_rows_counted(ctx, G, t.good, ctx->small.as<int32_t>() + kDncKept, n_cols, ld, out, as_stream(stream));
+    return launch_column_mean_rows_counted(ctx, G, t.good, &device_scalars(ctx)->dnc.kept, n_cols, ld, out, as_stream(stream));
 }
 
 }  // namespace
@@ -2131,11 +2109,10 @@ int byz_dnc_sharded_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_
 }
 
 int byz_dnc_info(byz_ctx* ctx, int64_t* kept_rows, int64_t* inactive_rows) {
-    BYZ_TRY(enter(ctx));
-    int32_t words[kSmallWords];
-    BYZ_TRY(read_small(ctx, words, ctx->dnc_stream));   // synchronises the last call's stream
-    if (kept_rows) *kept_rows = words[kDncKept];
-    if (inactive_rows) *inactive_rows = words[kDncInactive];
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportDnc, nullptr, &all));
+    if (kept_rows) *kept_rows = all.dnc.kept;
+    if (inactive_rows) *inactive_rows = all.dnc.inactive;
     return BYZ_OK;
 }
 
@@ -2327,8 +2304,7 @@ int byz_fang_krum_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_c
     const size_t row_bytes = static_cast<size_t>(m) * sizeof(double);
     if (t_out) BYZ_HIP(hipMemcpyAsync(t_out, w.t, row_bytes, hipMemcpyDeviceToDevice, s));
     if (q_out) BYZ_HIP(hipMemcpyAsync(q_out, w.q, row_bytes, hipMemcpyDeviceToDevice, s));
-    ctx->fang_krum_ran = true;
-    ctx->fang_stream = s;
+    mark(ctx, kReportFangKrum, s);
     ctx->fang_lambda0 = lambda0;
     ctx->fang_lambda = lambda;
     ctx->fang_steps = steps;
@@ -2338,9 +2314,8 @@ int byz_fang_krum_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_c
 }
 
 int byz_fang_krum_info(byz_ctx* ctx, double* lambda0, double* lambda, int64_t* steps, int64_t* chosen, int32_t* succeeded) {
-    BYZ_TRY(enter(ctx));
-    BYZ_REQUIRE(ctx->fang_krum_ran, "fang_krum_info: no Krum attack on this context yet");
-    BYZ_TRY(check_small(ctx, ctx->fang_stream));             // synchronises the last call's stream: the rows' overwrite is behind it
+    DeviceScalars all;      // (the five values are the host's; the read synchronises the last call's stream: the rows' overwrite is behind it)
+    BYZ_TRY(read_report(ctx, kReportFangKrum, "fang_krum_info: no Krum attack on this context yet", &all));
     if (lambda0) *lambda0 = ctx->fang_lambda0;
     if (lambda) *lambda = ctx->fang_lambda;
     if (steps) *steps = ctx->fang_steps;
@@ -2878,9 +2853,9 @@ int byz_dnc_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
     st.out(&good, good_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_dnc_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, columns, out, good, st.stream()));
-    int32_t words[kSmallWords];
-    BYZ_TRY(st.finish(words));
-    if (kept_host) *kept_host = words[kDncKept];
+    DeviceScalars all;
+    BYZ_TRY(st.finish(&all));
+    if (kept_host) *kept_host = all.dnc.kept;
     return BYZ_OK;
 }
 

@@ -2,7 +2,7 @@
 // Algorithm 2): v <- v + (1/n) sum_i (x_i - v) min(1, tau / |x_i - v|).  Streaming passes over G, nothing of order N^2.
 //
 //   scales  one workgroup: d_i = sqrt(sq_i), s_i = 1 (d_i <= tau), tau / d_i (tau < d_i < inf), 0 (d_i not finite: the row is
-//           excluded); the clipped and excluded counts go to the context's small area (common.hpp).
+//           excluded); the clipped and excluded counts go to the context's report (device_scalars.hpp).
 //   update  out[c] = fl32((double)v[c] + S_c / n), S_c = sum over the rows with s_i != 0 of s_i * ((double)x_ic - (double)v[c]),
 //           sequential in row order, no fused multiply-add; a row of scale 0 is neither loaded nor multiplied.  It is the
 //           weighted mean's kernel template with another product (weighted_rows_kernel<VEC, kRowsCentred>, geomed.hip, where
@@ -27,12 +27,12 @@ __global__ __launch_bounds__(256) void clip_norm_keys_kernel(const double* __res
 }
 
 // sq == nullptr: no iteration ran, every scale is 1 and both counts 0.  sorted_keys != nullptr (n_pad of them): tau is the
-// median of the finite norms instead (0 when no row is finite; a clip of 0 leaves every scale 0).  words[0], words[1]: the
-// clipped and the excluded rows; clip_word, clip_out (optional): the clip used.
+// median of the finite norms instead (0 when no row is finite; a clip of 0 leaves every scale 0).  clipped_out, excluded_out:
+// the report's counts; clip_word, clip_out (optional): the clip used.
 __global__ __launch_bounds__(kStepThreads) void cclip_scales_kernel(const double* __restrict__ sq, int64_t n, double tau,
                                                                     const unsigned long long* __restrict__ sorted_keys,
-                                                                    int64_t n_pad, double* __restrict__ s, int32_t* words,
-                                                                    double* clip_word, double* clip_out) {
+                                                                    int64_t n_pad, double* __restrict__ s, int32_t* clipped_out,
+                                                                    int32_t* excluded_out, double* clip_word, double* clip_out) {
     __shared__ int lds[kStepThreads];
     if (sorted_keys != nullptr) {
         int finite = 0;
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(kStepThreads) void cclip_scales_kernel(const double
     const int c = block_sum<int, kStepThreads>(clipped, lds);
     const int e = block_sum<int, kStepThreads>(excluded, lds);
     if (threadIdx.x == 0) {
-        words[0] = c;
-        words[1] = e;
+        *clipped_out = c;
+        *excluded_out = e;
         if (clip_word != nullptr) *clip_word = tau;
         if (clip_out != nullptr) *clip_out = tau;
     }
@@ -71,17 +71,16 @@ __global__ __launch_bounds__(kStepThreads) void cclip_scales_kernel(const double
 
 int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, double* s, hipStream_t stream) {
     BYZ_REQUIRE(s && n > 0 && n <= kLargeMaxRows, "clip scales: bad arguments");
-    static_assert(kCclipExcluded == kCclipClipped + 1, "the two counts are adjacent words");
-    cclip_scales_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, tau, nullptr, 0, s, geomed_words(ctx) + kCclipClipped, nullptr, nullptr);
+    CclipReport* r = &device_scalars(ctx)->cclip;
+    cclip_scales_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, tau, nullptr, 0, s, &r->clipped, &r->excluded, nullptr, nullptr);
     return check_launch("cclip_scales_kernel");
 }
 
 // weak DP's scales: adaptive = false: the clip is `clip` and s has launch_cclip_scales' bits; adaptive = true: the median of the
-// finite norms.  The counts and the clip go to the context's weak-DP words (common.hpp), the clip to clip_out as well (optional).
+// finite norms.  The counts and the clip go to the context's weak-DP report, the clip to clip_out as well (optional).
 int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, bool adaptive, double* s, double* clip_out,
                        hipStream_t stream) {
     BYZ_REQUIRE(sq && s && n > 0 && n <= kLargeMaxRows, "clip scales: bad arguments");
-    static_assert(kWeakDpExcluded == kWeakDpClipped + 1, "the two counts are adjacent words");
     unsigned long long* keys = nullptr;
     const int64_t n_pad = n < 2 ? 2 : next_pow2(n);            // segment_sort_u64 takes two keys at least
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
@@ -93,9 +92,8 @@ int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, b
         BYZ_TRY(check_launch("clip_norm_keys_kernel"));
         BYZ_TRY(segment_sort_u64(ctx, keys, 1, n_pad, stream));
     }
-    int32_t* words = geomed_words(ctx);
-    cclip_scales_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, clip, keys, n_pad, s, words + kWeakDpClipped, weak_dp_clip_word(ctx),
-                                                        clip_out);
+    WeakDpReport* r = &device_scalars(ctx)->weak_dp;
+    cclip_scales_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, clip, keys, n_pad, s, &r->clipped, &r->excluded, &r->clip, clip_out);
     return check_launch("cclip_scales_kernel");
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/byzagg.h"
 #include "carve.hpp"
+#include "device_scalars.hpp"
 
 namespace byz {
 
@@ -145,46 +146,25 @@ struct byz_ctx {
                                  // four arrays (api.hip: row_scratch): rowsq's (chunk, row) fp64 partials (at most 64 per row, FLTrust:
                                  // twice that); sq (n + 1; FLTrust: p, q, q0); the weights or scales (n; FLTrust: ts and w); FLTrust's
                                  // root partials
-    hipStream_t geomed_stream = nullptr;   // stream of the last geometric median (byz_geometric_median_info syncs it)
     byz::Buffer dnc;             // DnC, carved into DncScratch's arrays (dnc_workspace): the centred sample (n x sub_dim fp64), the
                                  // column partials, the n-vectors, the state, keep and good (int32, an array each)
-    hipStream_t dnc_stream = nullptr;      // stream of the last DnC call (byz_dnc_info syncs it)
-    hipStream_t cclip_stream = nullptr;    // stream of the last centered clipping (byz_centered_clip_info syncs it)
-    hipStream_t fltrust_stream = nullptr;  // stream of the last FLTrust call (byz_fltrust_info syncs it)
     byz::Buffer nnm_keys;        // nearest-neighbour mixing: n segments of next_pow2(n) sort keys
     byz::Buffer nnm_mask;        // carved: its 0/1 fp32 mask, transposed ([j][i], padded to the mix kernel's tiles); the n list lengths
     byz::Buffer nnm_lists;       // its neighbour lists (n x k int32) and their lengths (n) when the caller passes no buffer
-    hipStream_t nnm_stream = nullptr;      // stream of the last neighbour search (byz_nnm_info syncs it)
-    hipStream_t rlr_stream = nullptr;      // stream of the last sign vote or flip (byz_robust_lr_info syncs it)
     byz::Buffer signguard;       // SignGuard, carved into SgScratch's arrays (signguard_workspace): the census partials, then the selection's
-    hipStream_t signguard_stream = nullptr;   // stream of the last SignGuard selection (byz_signguard_info syncs it)
     byz::Buffer topk;            // top-k along a vector, carved (topk.hip: TopkScratch): the three histograms and the state, the chunk
                                  // arrays, the doubles of the columns layout, SparseFed's aggregate
-    hipStream_t topk_stream = nullptr;     // stream of the last top-k (byz_topk_info syncs it)
     byz::Buffer weak_dp;         // weak DP's adaptive clip, carved (cclip.hip: launch_clip_scales): the sort keys of the rows' norms
-    hipStream_t weak_dp_stream = nullptr;  // stream of the last clip scales or weak DP (byz_weak_dp_info syncs it)
     byz::Buffer flame;           // FLAME, carved into FlameScratch's arrays (flame.hip: flame_workspace): the core distances, the
                                  // tree's edges and their sort keys, the admitted flags, the weights
-    byz::Buffer flame_info;      // the last selection's scalars (FlameInfo), in a buffer of their own: the workspace may be carved
-                                 // again, and move, between a selection and byz_flame_info
-    hipStream_t flame_stream = nullptr;    // stream of the last FLAME selection (byz_flame_info syncs it)
-    bool flame_selected = false;           // a selection has written ctx->flame_info
     byz::Buffer manhattan;       // the Manhattan distances, carved (manhattan.hip: manhattan_workspace): the tile kernel's fp64
                                  // partials (chunks x n x n), then the n x n sums
     byz::Buffer multi_metrics;   // Multi-Metrics, carved into MmScratch's arrays (multi_metrics.hip: multi_metrics_workspace)
-    byz::Buffer multi_metrics_info;        // the last selection's scalars (MmInfo), in a buffer of their own, as FLAME's are
-    hipStream_t multi_metrics_stream = nullptr;   // stream of the last Multi-Metrics selection (byz_multi_metrics_info syncs it)
-    bool multi_metrics_selected = false;   // a selection has written ctx->multi_metrics_info
     byz::Buffer linkage;         // agglomerative clustering, carved into LinkageScratch's arrays (linkage.hip: linkage_workspace): the fp64
                                  // working matrix (n x n), the first nearest partners, the merges, the labels, the flags, the weights
-    byz::Buffer linkage_info;    // the last linkage's and selection's scalars (LinkageInfo), in a buffer of their own, as FLAME's are
-    hipStream_t linkage_stream = nullptr;  // stream of the last linkage or ClippedClustering call (the two info calls sync it)
-    bool linkage_ran = false;              // a linkage has written ctx->linkage_info
-    bool clipped_clustering_selected = false;   // a ClippedClustering selection has written it as well
     byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
                                  // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
-    hipStream_t fang_stream = nullptr;     // stream of the last Krum attack (byz_fang_krum_info syncs it)
-    bool fang_krum_ran = false;            // a Krum attack has filled the five values below (byz_fang_krum_info reports them)
+    // the last Krum attack's values (byz_fang_krum_info reports them; last[kReportFangKrum] says whether there was one)
     double fang_lambda0 = 0.0, fang_lambda = 0.0;
     int64_t fang_steps = 0, fang_chosen = -1;
     int32_t fang_succeeded = 0;
@@ -204,7 +184,8 @@ struct byz_ctx {
     byz::Buffer xchg;            // Bulyan grid loop: tagged 8-byte granules the workgroups exchange
     int64_t bulyan_rescored = 0; // rows the last Bulyan loop re-scored in the reference's fp32 arithmetic
     byz::Buffer selection;       // theta int32
-    byz::Buffer small;           // misc device scalars (winner index, status words)
+    byz::Buffer scalars;         // one DeviceScalars (device_scalars.hpp): the winner, the status words, every info call's report
+    byz::LastCall last[byz::kReportCount];   // per report: the last call that wrote it (its info call syncs that stream)
     bool small_configured = false;   // krum_small.hip: dynamic-LDS attributes set for this context's device
     // kernels whose hipFuncAttributeMaxDynamicSharedMemorySize has been raised for this context's device, and to what: the
     // attribute belongs to the (function, device) pair and setting it is a runtime call per launch otherwise (round 6)
@@ -234,60 +215,13 @@ inline hipError_t allow_dynamic_lds(byz_ctx* ctx, const void* kernel, int bytes)
     return e;
 }
 
-// ctx->small (256 bytes, allocated and zeroed with the context) holds the device-side scalars, by int32 word:
-constexpr int kSmallWords = 64;          // words one read-back fetches (read_small): every word below
-constexpr int kWordKrumWinner = 0;       // Krum winner
-constexpr int kWordBulyanStatus = 8;     // Bulyan loop status
-constexpr int kWordBulyanRescored = 9;   // rows the Bulyan loop re-scored
-constexpr int kWordStatus = 16;          // sticky device status: the kStatus* bits
-constexpr int kWordNearPairs = 17;       // number of near-duplicate pairs listed by the last distance kernel
-// non-zero: the register-resident column statistics of the CURRENT call gave up a turn; the two-pass kernel queued behind them
-// recomputes the call's columns (zeroed before every such launch; kStatusNoTurn is no longer set)
-constexpr int kWordAttackRedo = 18;
-// geometric median: done (the launches still queued return at once), its iterations, its excluded rows, mean0 was not finite (the
-// fallback ran), its objective (fp64: two words)
-constexpr int kGeomedDone = 20, kGeomedIterations = 21, kGeomedExcluded = 22, kGeomedFallback = 23, kGeomedObjective = 24;
-// DnC: the rows the last call kept, the rows its last iteration found inactive
-constexpr int kDncKept = 26, kDncInactive = 27;
-// centered clipping: the rows its last iteration clipped (tau < d < inf) and excluded (d not finite)
-constexpr int kCclipClipped = 28, kCclipExcluded = 29;
-// FLTrust: the rows with a positive trust score, the rows with a non-finite dot product or norm, T = the sum of the trust scores
-// (fp64: two words, 8-byte aligned), the root's squared norm was finite and positive
-constexpr int kFltrustTrusted = 30, kFltrustExcluded = 31, kFltrustTrustSum = 32, kFltrustRootOk = 34;
-// nearest-neighbour mixing: the rows whose list is themselves alone although k > 1, the rows whose list is shorter than k (adjacent:
-// one memset clears both)
-constexpr int kNnmSolo = 36, kNnmShort = 37;
-// robust learning rate: the columns the last call flipped (one 64-bit counter: two words, 8-byte aligned)
-constexpr int kRlrFlipped = 38;
-// SignGuard: the rows kept, failing the norm filter, outside the benign cluster; the clusters and the seeds; flat: the bandwidth was
-// 0, not finite or below kSgMinBandwidth and every row got label 0; then three fp64 (two words each, 8-byte aligned): the
-// bandwidth h, the median norm M, and K = the kept rows as the divisor of the sum
-constexpr int kSgKept = 40, kSgNormFailed = 41, kSgOutside = 42, kSgClusters = 43, kSgSeeds = 44, kSgFlat = 45;
-constexpr int kSgBandwidth = 46, kSgMedian = 48, kSgKeptF64 = 50;
-// top-k along a vector: four 64-bit words (8-byte aligned): selected, the ties at the threshold, the ties taken, the threshold key
-constexpr int kTopkSelected = 52, kTopkTies = 54, kTopkTaken = 56, kTopkKey = 58;
-// weak DP (byz_clip_scales_dev, byz_weak_dp_dev): the rows clipped and excluded, the clip used (fp64: two words, 8-byte aligned).
-// The last words of the 256 bytes: the next scalar needs a larger ctx->small.
-constexpr int kWeakDpClipped = 60, kWeakDpExcluded = 61, kWeakDpClip = 62;
-constexpr int kStatusLostTicket = 1;     // a Gram chunk lost its ticket
-constexpr int kStatusPairOverflow = 2;   // the near-duplicate pair list overflowed
-constexpr int kStatusFalseTwin = 4;      // two rows with bitwise equal Gram entries turned out to differ
-constexpr int kStatusSmallTimeout = 8;   // the row workgroups of the small-N path did not all report their scores in time
-constexpr int kStatusNoTurn = 16;        // a wave of the register-resident column statistics never got its turn
-inline int32_t* device_status_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordStatus; }
-inline int32_t* attack_redo_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordAttackRedo; }
-inline int32_t* near_pair_count_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordNearPairs; }
-inline int32_t* krum_winner_word(byz_ctx* ctx) { return ctx->small.as<int32_t>() + kWordKrumWinner; }
-inline int32_t* geomed_words(byz_ctx* ctx) { return ctx->small.as<int32_t>(); }
-inline unsigned long long* rlr_flip_counter(byz_ctx* ctx) {
-    return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kRlrFlipped);
-}
-
-inline unsigned long long* topk_info_words(byz_ctx* ctx) {
-    return reinterpret_cast<unsigned long long*>(ctx->small.as<int32_t>() + kTopkSelected);
-}
-
-inline double* weak_dp_clip_word(byz_ctx* ctx) { return reinterpret_cast<double*>(ctx->small.as<int32_t>() + kWeakDpClip); }
+inline DeviceScalars* device_scalars(byz_ctx* ctx) { return ctx->scalars.as<DeviceScalars>(); }
+inline int32_t* device_status_word(byz_ctx* ctx) { return &device_scalars(ctx)->core.status; }
+inline int32_t* attack_redo_word(byz_ctx* ctx) { return &device_scalars(ctx)->core.attack_redo; }
+inline int32_t* near_pair_count_word(byz_ctx* ctx) { return &device_scalars(ctx)->core.near_pairs; }
+inline int32_t* krum_winner_word(byz_ctx* ctx) { return &device_scalars(ctx)->core.krum_winner; }
+// a call that writes the report `kind` on `stream`: what the report's info call synchronises
+inline void mark(byz_ctx* ctx, ReportKind kind, hipStream_t stream) { ctx->last[kind] = {stream, true}; }
 
 // Brackets one kernel launch with events when timing is on (bench.py's roofline leg).
 struct KernelTimer {
@@ -409,7 +343,7 @@ int launch_row_sort(byz_ctx* ctx, const float* dist, int64_t n, int64_t prefix_l
                     bool want_tables, hipStream_t stream);
 int launch_krum_argmin(byz_ctx* ctx, int64_t n, int32_t* winner_dev, hipStream_t stream);
 int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count,
-                       int64_t users_count, int64_t corrupted, int32_t* selection_dev, int32_t* status_dev,
+                       int64_t users_count, int64_t corrupted, int32_t* selection_dev, BulyanStatus* status_dev,
                        hipStream_t stream);
 
 // large_rows.hip: beyond the LDS-resident kernels' 16,384 rows (BYZ_SELECT_LARGE=1 takes these paths at any size)
@@ -435,7 +369,7 @@ int dnc_workspace(byz_ctx* ctx, int64_t n, int64_t b, DncScratch* out);
 int launch_dnc_scores(byz_ctx* ctx, const DncScratch& t, const float* G, int64_t n, int64_t ld, const int64_t* columns, int64_t b,
                       int64_t power_iters, byz_allreduce_f64_fn allreduce, void* user, void* stream);
 // t.keep (&)= the n_keep lowest (score, row); then the kept rows ascending into t.good (and good_out), their count into the
-// context's word (and count_out)
+// context's DnC report (and count_out)
 int launch_dnc_rank(byz_ctx* ctx, const DncScratch& t, int64_t n, int64_t n_keep, bool first, hipStream_t stream);
 int launch_dnc_compact(byz_ctx* ctx, const DncScratch& t, int64_t n, int32_t* good_out, int32_t* count_out, hipStream_t stream);
 // geomed.hip: the geometric median's passes (row distances to a vector, weighted row mean) and its small loop kernels.
@@ -451,10 +385,10 @@ int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w
 int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
                        hipStream_t stream);
 int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream);
-// cclip.hip: centered clipping's scales: s from sq (sq == nullptr: all 1), the counts into the context's words
+// cclip.hip: centered clipping's scales: s from sq (sq == nullptr: all 1), the counts into the context's report
 int launch_cclip_scales(byz_ctx* ctx, const double* sq, int64_t n, double tau, double* s, hipStream_t stream);
 // weak DP's scales from sq: the clip is `clip`, or (adaptive) the np.median of the finite rows' norms; s has launch_cclip_scales'
-// bits in the fixed mode; the counts and the clip into the context's weak-DP words, the clip into clip_out (optional) as well
+// bits in the fixed mode; the counts and the clip into the context's weak-DP report, the clip into clip_out (optional) as well
 int launch_clip_scales(byz_ctx* ctx, const double* sq, int64_t n, double clip, bool adaptive, double* s, double* clip_out,
                        hipStream_t stream);
 // noise.hip: out[c] = fl32((double)x[c] + sigma * (scale_dev ? *scale_dev : 1) * z[offset + c]), z the Philox normals of the
@@ -486,15 +420,7 @@ double fang_lambda0(double s_min, double q_max, int64_t n, int64_t c, int64_t n_
 // 0 between attackers, +inf on their diagonal
 int launch_fang_krum_fill(byz_ctx* ctx, float* dist, int64_t n, int64_t c, int64_t n_cols, const double* q, const double* t,
                           double lambda, hipStream_t stream);
-// flame.hip: FLAME's clustering stage.  The scalars of a call live in ctx->flame_info, not in ctx->small (which is full):
-struct FlameInfo {
-    int32_t admitted, broken_rows;   // the rows admitted; the rows without a finite off-diagonal distance
-    float w_star;                    // the threshold (+inf: nobody admitted)
-    int32_t pad;
-    double admitted_f64;             // the divisor of the sum
-    double clip;                     // byz_flame_dev: the median norm
-};
-constexpr int kFlameInfoWords = static_cast<int>(sizeof(FlameInfo) / sizeof(int32_t));
+// flame.hip: FLAME's clustering stage.  The scalars of a call: DeviceScalars::flame.
 constexpr int64_t kFlameMaxRows = 16384;     // Prim's one workgroup owns 1024 x 16 vertices; the union-find fills the LDS
 constexpr int64_t kFlameMaxSamples = 32;     // rounds of the core distance's selection at most
 struct FlameScratch {
@@ -524,12 +450,7 @@ int manhattan_workspace(byz_ctx* ctx, int64_t n, int64_t d, double** partial, do
 int launch_manhattan_sums(byz_ctx* ctx, const float* G, int64_t n, int64_t d, int64_t ld, double* partial, double* sums,
                           hipStream_t stream);
 int launch_manhattan_from_sums(byz_ctx* ctx, const double* sums, int64_t n, float* dist, hipStream_t stream);
-// multi_metrics.hip: Multi-Metrics' features, scores and selection.  The scalars of a call live in ctx->multi_metrics_info:
-struct MmInfo {
-    int32_t kept, usable, degenerate, pad;   // rows chosen = min(usable, keep); rows with three finite features; the fallback ran
-    double det;                              // det R of the features' correlation matrix (0 when fewer than 4 rows are usable)
-};
-constexpr int kMmInfoWords = static_cast<int>(sizeof(MmInfo) / sizeof(int32_t));
+// multi_metrics.hip: Multi-Metrics' features, scores and selection.  The scalars of a call: DeviceScalars::mm.
 constexpr int64_t kMmMaxRows = 16384;        // the selection's one workgroup owns 1024 x 16 rows
 struct MmScratch {
     MmInfo* info;
@@ -550,16 +471,7 @@ int launch_mm_select(byz_ctx* ctx, const MmScratch& t, const double* feat, int64
                      double* scores_out, hipStream_t stream);
 // out[c] = 0 for every column when *count_dev == 0 (the counted mean of no rows is 0 / 0)
 int launch_mm_zero_if_empty(byz_ctx* ctx, const int32_t* count_dev, int64_t n_cols, float* out, hipStream_t stream);
-// linkage.hip: agglomerative clustering and ClippedClustering's selection.  The scalars of a call live in ctx->linkage_info:
-struct LinkageInfo {
-    int32_t admitted, usable;        // ClippedClustering: the rows admitted; the rows with a finite off-diagonal distance
-    int32_t steps, rescans;          // the last linkage: its merges; the nearest-partner caches it rebuilt from a row of W
-    int32_t max_rescans, pad;        // the most of them in one step
-    double top_height, second_height;        // the last merge's height and the one before (0 where there is none)
-    double admitted_f64;             // the divisor of the sum
-    double clip;                     // byz_clipped_clustering_dev: the clip used
-};
-constexpr int kLinkageInfoWords = static_cast<int>(sizeof(LinkageInfo) / sizeof(int32_t));
+// linkage.hip: agglomerative clustering and ClippedClustering's selection.  The scalars of a call: DeviceScalars::linkage.
 struct LinkageScratch {
     LinkageInfo* info;
     double* W;                       // n x n: the working matrix
@@ -588,7 +500,7 @@ int launch_row_dots(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols
 // geomed.hip, the weighted mean's kernel template: out = *divisor > 0 ? sum_i w_i x_i / *divisor : 0
 int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* w,
                            const double* divisor, float* out, hipStream_t stream);
-// fltrust.hip: FLTrust's trust scores ts and weights w from pq = p (n), q (n), q0 (1); T and the counts into the context's words
+// fltrust.hip: FLTrust's trust scores ts and weights w from pq = p (n), q (n), q0 (1); T and the counts into the context's report
 int launch_fltrust_trust(byz_ctx* ctx, const double* pq, int64_t n, double* ts, double* w, hipStream_t stream);
 // signguard.hip: SignGuard's census and selection.  The workspace for n rows (ctx->signguard):
 constexpr int kSgMaxSamples = BYZ_SIGNGUARD_MAX_SAMPLES;   // rows the bandwidth is estimated from at most
@@ -618,7 +530,7 @@ int launch_nnm_mix(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int6
                    int64_t k, float* Y, int64_t ldy, hipStream_t stream);
 // robust_lr.hip: the robust learning rate's sign vote (votes[c] = #positive - #negative, decided on the bits) and the flip of an
 // aggregate's sign bit where |votes[c]| < theta.  out == nullptr: the votes alone; otherwise out = no_defense's vector with the
-// flips applied, in the same walk (votes optional).  Both count the flipped columns into the context's counter.
+// flips applied, in the same walk (votes optional).  Both count the flipped columns into the context's report.
 int launch_sign_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t theta, float* out,
                       int32_t* votes, hipStream_t stream);
 int launch_sign_flip(byz_ctx* ctx, const float* agg, const int32_t* votes, int64_t n_cols, int64_t theta, float* out,
@@ -636,7 +548,7 @@ int launch_topk_sparsify(byz_ctx* ctx, const float* x, const float* add, int64_t
 // n_cols floats of the top-k workspace for SparseFed's aggregate (nullptr: the allocation failed, the error text is set)
 float* topk_aggregate_workspace(byz_ctx* ctx, int64_t n_cols);
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
-                             int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
+                             int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, BulyanStatus* status_dev,
                              hipStream_t stream);
 
 int launch_trimmed_mean(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld,

@@ -18,7 +18,7 @@
 //            +inf, -0.0 as +0.0), n^2 comparisons through LDS tiles; ANDed into the running intersection
 //   compact  the kept rows in ascending order and their count (block_exclusive_scan, order_keys.hpp)
 // Every sum has a fixed order: two calls give the same bits.  Nothing synchronises with the host; the kept count stays in the
-// context's small area (common.hpp) until byz_dnc_info reads it.
+// context's DncReport (device_scalars.hpp) until byz_dnc_info reads it.
 #include "order_keys.hpp"
 #include "row_walk.hpp"
 
@@ -228,12 +228,11 @@ __global__ __launch_bounds__(kThreads) void dnc_rank_kernel(const double* __rest
     }
 }
 
-// good: n int32, the kept rows ascending, -1 behind them; the count to the context's word and to count_out (optional);
-// inactive_word: the rows the last iteration found inactive
+// good: n int32, the kept rows ascending, -1 behind them; the count to the context's report and to count_out (optional);
+// report->inactive: the rows the last iteration found inactive
 __global__ __launch_bounds__(kOneThreads) void dnc_compact_kernel(const int32_t* __restrict__ keep, const double* __restrict__ bad,
                                                                   int64_t n, int32_t* __restrict__ good,
-                                                                  int32_t* __restrict__ count_word, int32_t* __restrict__ inactive_word,
-                                                                  int32_t* __restrict__ count_out) {
+                                                                  DncReport* __restrict__ report, int32_t* __restrict__ count_out) {
     __shared__ int lds[kOneThreads];
     const int tid = threadIdx.x;
     const int64_t chunk = (n + kOneThreads - 1) / kOneThreads;
@@ -251,8 +250,8 @@ __global__ __launch_bounds__(kOneThreads) void dnc_compact_kernel(const int32_t*
         if (keep[r] != 0) good[slot++] = static_cast<int32_t>(r);
     for (int64_t r = total + tid; r < n; r += kOneThreads) good[r] = -1;
     if (tid == 0) {
-        *count_word = total;
-        *inactive_word = inactive;
+        report->kept = total;
+        report->inactive = inactive;
         if (count_out != nullptr) *count_out = total;
     }
 }
@@ -356,8 +355,7 @@ int launch_dnc_rank(byz_ctx* ctx, const DncScratch& t, int64_t n, int64_t n_keep
 
 int launch_dnc_compact(byz_ctx* ctx, const DncScratch& t, int64_t n, int32_t* good_out, int32_t* count_out, hipStream_t stream) {
     KernelTimer timer(ctx, BYZ_K_KRUM_ARGMIN, stream);
-    int32_t* words = ctx->small.as<int32_t>();
-    dnc_compact_kernel<<<1, kOneThreads, 0, stream>>>(t.keep, t.bad, n, t.good, words + kDncKept, words + kDncInactive, count_out);
+    dnc_compact_kernel<<<1, kOneThreads, 0, stream>>>(t.keep, t.bad, n, t.good, &device_scalars(ctx)->dnc, count_out);
     BYZ_TRY(check_launch("dnc_compact_kernel"));
     if (good_out != nullptr) {
         dnc_copy_i32_kernel<<<static_cast<unsigned>(ceil_div(n, kThreads)), kThreads, 0, stream>>>(t.good, n, good_out);

@@ -251,8 +251,7 @@ __global__ __launch_bounds__(256) void flame_weights_kernel(const int32_t* __res
 
 int flame_workspace(byz_ctx* ctx, int64_t n, FlameScratch* out) {
     out->n_pad = next_pow2(n - 1 < 2 ? 2 : n - 1);
-    BYZ_TRY(ctx->flame_info.ensure(sizeof(FlameInfo)));      // (allocated once: the size never changes)
-    out->info = ctx->flame_info.as<FlameInfo>();
+    out->info = &device_scalars(ctx)->flame;
     Carve c;
     c.take(&out->core, n);
     c.take(&out->isolated, n);

@@ -7,7 +7,7 @@
 //           (rowsq_partial_kernel<VEC4, true>, geomed.hip, where launch_row_dots lives beside launch_row_sqdist);
 //           q0 = |r|^2 is launch_row_sqdist on the 1 x n_cols matrix r.
 //   trust   one workgroup, here: c_i = p_i / (sqrt(q_i) * sqrt(q0)), ts_i = max(c_i, 0), w_i = ts_i * (sqrt(q0) / sqrt(q_i)),
-//           T = sum ts_i in a fixed order; T and the counts go to the context's small area (common.hpp).
+//           T = sum ts_i in a fixed order; T and the counts go to the context's report (device_scalars.hpp).
 //   sum     out[c] = T > 0 ? fl32(S_c / T) : 0, S_c = sum over the rows with w_i != 0 of w_i * (double)x_ic, sequential in row
 //           order, no fused multiply-add; a row of weight 0 is neither loaded nor multiplied.  The weighted mean's kernel
 //           template with another last line (weighted_rows_kernel<VEC, kRowsScaled>, geomed.hip: launch_scaled_rows_sum).
@@ -21,7 +21,7 @@ constexpr int kStepThreads = 1024;
 // pq: p (n), q (n), q0 (1).  A thread takes a run of consecutive rows; T is the threads' sums through block_sum's tree.
 __global__ __launch_bounds__(kStepThreads) void fltrust_trust_kernel(const double* __restrict__ pq, int64_t n,
                                                                      double* __restrict__ ts, double* __restrict__ w,
-                                                                     int32_t* words) {
+                                                                     FltrustReport* r) {
     __shared__ double lds[kStepThreads];
     __shared__ int lds_i[kStepThreads];
     const double q0 = pq[2 * n];
@@ -49,10 +49,10 @@ __global__ __launch_bounds__(kStepThreads) void fltrust_trust_kernel(const doubl
     const int n_trusted = block_sum<int, kStepThreads>(trusted, lds_i);
     const int n_excluded = block_sum<int, kStepThreads>(excluded, lds_i);
     if (threadIdx.x == 0) {
-        words[kFltrustTrusted] = n_trusted;
-        words[kFltrustExcluded] = n_excluded;
-        words[kFltrustRootOk] = root_ok ? 1 : 0;
-        *reinterpret_cast<double*>(words + kFltrustTrustSum) = T;
+        r->trusted = n_trusted;
+        r->excluded = n_excluded;
+        r->root_ok = root_ok ? 1 : 0;
+        r->trust_sum = T;
     }
 }
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kStepThreads) void fltrust_trust_kernel(const doubl
 
 int launch_fltrust_trust(byz_ctx* ctx, const double* pq, int64_t n, double* ts, double* w, hipStream_t stream) {
     BYZ_REQUIRE(pq && ts && w && n > 0 && n <= kLargeMaxRows, "trust scores: bad arguments");
-    fltrust_trust_kernel<<<1, kStepThreads, 0, stream>>>(pq, n, ts, w, geomed_words(ctx));
+    fltrust_trust_kernel<<<1, kStepThreads, 0, stream>>>(pq, n, ts, w, &device_scalars(ctx)->fltrust);
     return check_launch("fltrust_trust_kernel");
 }
 

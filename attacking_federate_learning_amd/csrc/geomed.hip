@@ -22,7 +22,7 @@
 //   step    one workgroup: d_i = sqrt(sq_i), F = sum of d over the active rows (fixed order), the stop test
 //           |F_old - F| <= ftol * F, beta_i = 1 / max(nu, d_i).
 // Every launch of the loop is enqueued up front; after the stop the remaining launches read the done word and return at once
-// (the redo_gate idiom of column_sequential_kernel).  The state lives in the context's small area (common.hpp).
+// (the redo_gate idiom of column_sequential_kernel).  The state lives in the context's GeomedReport (device_scalars.hpp).
 #include "row_walk.hpp"
 
 #include <algorithm>
@@ -178,28 +178,26 @@ __global__ __launch_bounds__(kThreads) void weighted_rows_kernel(const float* __
     }
 }
 
-// ---- the loop's small kernels (state in ctx->small, common.hpp) ----------------------------------------------------------
-__device__ __forceinline__ double* objective_of(int32_t* words) { return reinterpret_cast<double*>(words + kGeomedObjective); }
-
-__global__ __launch_bounds__(256) void finite_check_kernel(const float* __restrict__ v, int64_t n, int32_t* words,
+// ---- the loop's small kernels (state: GeomedReport, device_scalars.hpp) ------------------------------------------------------
+__global__ __launch_bounds__(256) void finite_check_kernel(const float* __restrict__ v, int64_t n, GeomedReport* r,
                                                            double* flag_f64) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n) return;
     const float x = v[i];
     if (!__builtin_isfinite(x)) {
-        __hip_atomic_store(words + kGeomedFallback, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&r->fallback, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (flag_f64 != nullptr) *flag_f64 = 1.0;
     }
 }
 
 // mean0 was not finite: the active rows are those with a finite sq0 (the fp64 squared norm), their weights 1, the others 0
 __global__ __launch_bounds__(kStepThreads) void geomed_fallback_kernel(const double* __restrict__ sq0, int64_t n, double* w,
-                                                                       int32_t* words, const double* global_flag) {
+                                                                       GeomedReport* r, const double* global_flag) {
     __shared__ double lds[kStepThreads];
     const bool fallback = global_flag != nullptr ? *global_flag > 0.0
-                                                 : __hip_atomic_load(words + kGeomedFallback, __ATOMIC_RELAXED,
+                                                 : __hip_atomic_load(&r->fallback, __ATOMIC_RELAXED,
                                                                      __HIP_MEMORY_SCOPE_AGENT) != 0;
-    if (global_flag != nullptr && threadIdx.x == 0) words[kGeomedFallback] = fallback ? 1 : 0;
+    if (global_flag != nullptr && threadIdx.x == 0) r->fallback = fallback ? 1 : 0;
     if (!fallback) return;
     double excluded = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kStepThreads) {
@@ -210,8 +208,8 @@ __global__ __launch_bounds__(kStepThreads) void geomed_fallback_kernel(const dou
     const double total = block_sum<double, kStepThreads>(excluded, lds);
     if (threadIdx.x == 0) {
         const int64_t ex = static_cast<int64_t>(total);
-        words[kGeomedExcluded] = static_cast<int32_t>(ex);
-        if (ex == n) words[kGeomedDone] = 1;          // no row left: the output is wmean's NaN, iterations 0
+        r->excluded = static_cast<int32_t>(ex);
+        if (ex == n) r->done = 1;          // no row left: the output is wmean's NaN, iterations 0
     }
 }
 
@@ -219,11 +217,11 @@ __global__ __launch_bounds__(kStepThreads) void geomed_fallback_kernel(const dou
 // flag is set, then those with a non-zero weight (a beta of an active row is never 0).  k < max_iter and no stop: the weights
 // of update k + 1.
 __global__ __launch_bounds__(kStepThreads) void geomed_step_kernel(const double* __restrict__ sq, int64_t n, double* w,
-                                                                   int32_t* words, double nu, double ftol, int64_t k,
+                                                                   GeomedReport* r, double nu, double ftol, int64_t k,
                                                                    int64_t max_iter) {
     __shared__ double lds[kStepThreads];
-    if (__hip_atomic_load(words + kGeomedDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
-    const bool fallback = words[kGeomedFallback] != 0;
+    if (__hip_atomic_load(&r->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+    const bool fallback = r->fallback != 0;
     const int64_t per = (n + kStepThreads - 1) / kStepThreads;
     const int64_t lo = threadIdx.x * per < n ? threadIdx.x * per : n;
     const int64_t hi = lo + per < n ? lo + per : n;
@@ -231,13 +229,13 @@ __global__ __launch_bounds__(kStepThreads) void geomed_step_kernel(const double*
     for (int64_t i = lo; i < hi; ++i)
         if (!fallback || w[i] != 0.0) f = f + sqrt(sq[i]);
     const double F = block_sum<double, kStepThreads>(f, lds);
-    const double F_old = *objective_of(words);
+    const double F_old = r->objective;
     const bool stop = k > 0 && fabs(F_old - F) <= ftol * F;
     __syncthreads();                                  // every thread has read F_old
     if (threadIdx.x == 0) {
-        *objective_of(words) = F;
-        words[kGeomedIterations] = static_cast<int32_t>(k);
-        if (stop) words[kGeomedDone] = 1;
+        r->objective = F;
+        r->iterations = static_cast<int32_t>(k);
+        if (stop) r->done = 1;
     }
     if (stop || k >= max_iter) return;
     for (int64_t i = lo; i < hi; ++i) {
@@ -249,10 +247,10 @@ __global__ __launch_bounds__(kStepThreads) void geomed_step_kernel(const double*
 
 // weights_out = beta / sum(beta) of the last update, or uniform over the active rows when there was none
 __global__ __launch_bounds__(kStepThreads) void geomed_weights_kernel(const double* __restrict__ w, int64_t n,
-                                                                      const int32_t* words, double* __restrict__ out) {
+                                                                      const GeomedReport* r, double* __restrict__ out) {
     __shared__ double lds[kStepThreads];
-    const bool fallback = words[kGeomedFallback] != 0;
-    const bool updated = words[kGeomedIterations] > 0;
+    const bool fallback = r->fallback != 0;
+    const bool updated = r->iterations > 0;
     const int64_t per = (n + kStepThreads - 1) / kStepThreads;
     const int64_t lo = threadIdx.x * per < n ? threadIdx.x * per : n;
     const int64_t hi = lo + per < n ? lo + per : n;
@@ -359,23 +357,23 @@ int launch_scaled_rows_sum(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
 }
 
 int launch_geomed_finite_check(byz_ctx* ctx, const float* v, int64_t n, double* flag_f64, hipStream_t stream) {
-    finite_check_kernel<<<static_cast<unsigned>(ceil_div(n, 256)), 256, 0, stream>>>(v, n, geomed_words(ctx), flag_f64);
+    finite_check_kernel<<<static_cast<unsigned>(ceil_div(n, 256)), 256, 0, stream>>>(v, n, &device_scalars(ctx)->geomed, flag_f64);
     return check_launch("finite_check_kernel");
 }
 
 int launch_geomed_fallback(byz_ctx* ctx, const double* sq0, int64_t n, double* w, const double* global_flag, hipStream_t stream) {
-    geomed_fallback_kernel<<<1, kStepThreads, 0, stream>>>(sq0, n, w, geomed_words(ctx), global_flag);
+    geomed_fallback_kernel<<<1, kStepThreads, 0, stream>>>(sq0, n, w, &device_scalars(ctx)->geomed, global_flag);
     return check_launch("geomed_fallback_kernel");
 }
 
 int launch_geomed_step(byz_ctx* ctx, const double* sq, int64_t n, double* w, double nu, double ftol, int64_t k, int64_t max_iter,
                        hipStream_t stream) {
-    geomed_step_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, w, geomed_words(ctx), nu, ftol, k, max_iter);
+    geomed_step_kernel<<<1, kStepThreads, 0, stream>>>(sq, n, w, &device_scalars(ctx)->geomed, nu, ftol, k, max_iter);
     return check_launch("geomed_step_kernel");
 }
 
 int launch_geomed_weights(byz_ctx* ctx, const double* w, int64_t n, double* out, hipStream_t stream) {
-    geomed_weights_kernel<<<1, kStepThreads, 0, stream>>>(w, n, geomed_words(ctx), out);
+    geomed_weights_kernel<<<1, kStepThreads, 0, stream>>>(w, n, &device_scalars(ctx)->geomed, out);
     return check_launch("geomed_weights_kernel");
 }
 

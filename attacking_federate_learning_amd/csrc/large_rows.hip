@@ -912,7 +912,7 @@ int launch_row_sort_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t pr
 }
 
 int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count, int64_t users_count,
-                             int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, int32_t* status_dev,
+                             int64_t corrupted, const int32_t* twin_class, int32_t* selection_dev, BulyanStatus* status_dev,
                              hipStream_t stream) {
     BYZ_REQUIRE(dist && selection_dev && status_dev && n > 0 && theta >= 0 && theta <= n,
                 "bulyan loop (large): bad arguments (n=%lld theta=%lld)", (long long)n, (long long)theta);
@@ -926,7 +926,7 @@ int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t
     int batch = 16;
     if (const char* e = std::getenv("BYZ_LARGE_BATCH")) batch = std::atoi(e);
     batch = batch < 1 ? 1 : (batch > kBatchMax ? kBatchMax : batch);
-    BYZ_HIP(hipMemsetAsync(status_dev, 0, 3 * sizeof(int32_t), stream));   // status, rows re-scored, (unused)
+    BYZ_HIP(hipMemsetAsync(status_dev, 0, sizeof *status_dev, stream));
     BYZ_HIP(hipMemsetAsync(st.words, 0, 4 * sizeof(int32_t), stream));
     // The deciding kernel on many workgroups (a cooperative launch) where the device offers it; BYZ_LARGE_COOP=0: on one workgroup
     // (the comparison, and the form for a device that cannot hold the grid at once).  The same selection.
@@ -963,8 +963,8 @@ int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t
                 const uint32_t* rank_p = ctx->large_rank_t.as<uint32_t>();
                 const float* dist_p = ctx->large_dist_t.as<float>();
                 LargeState st_arg = st;
-                const int32_t* status_p = status_dev;
-                int32_t* rescored_p = status_dev + 1;
+                const int32_t* status_p = &status_dev->status;
+                int32_t* rescored_p = &status_dev->rescored;
                 void* args[] = {&n_i, &theta_i, &drop_i, &users_i, &corrupted_i, &batch, &val_p, &idx_p, &rank_p, &dist_p, &st_arg,
                                 &status_p, &rescored_p, &wg_best, &n_listed_dev};
                 BYZ_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&large_decide_grid_kernel), dim3(grid_blocks),
@@ -972,19 +972,19 @@ int launch_bulyan_loop_large(byz_ctx* ctx, const float* dist, int64_t n, int64_t
             } else {
                 large_decide_kernel<<<1, 1024, 0, stream>>>((int)n, (int)theta, (int)drop_count, (int)users_count, (int)corrupted, batch,
                                                             ctx->sorted_val.as<float>(), ctx->large_idx.as<uint32_t>(),
-                                                            ctx->large_rank_t.as<uint32_t>(), ctx->large_dist_t.as<float>(), st, status_dev,
-                                                            status_dev + 1);
+                                                            ctx->large_rank_t.as<uint32_t>(), ctx->large_dist_t.as<float>(), st, &status_dev->status,
+                                                            &status_dev->rescored);
             }
             large_rescore_kernel<<<rescore_grid, 256, 0, stream>>>((int)n, (int)users_count, (int)corrupted, ctx->sorted_val.as<float>(),
-                                                                   ctx->large_idx.as<uint32_t>(), st, status_dev);
+                                                                   ctx->large_idx.as<uint32_t>(), st, &status_dev->status);
             large_settle_kernel<<<1, 1024, 0, stream>>>((int)n, (int)theta, (int)drop_count, ctx->sorted_val.as<float>(),
                                                         ctx->large_idx.as<uint32_t>(), ctx->large_rank_t.as<uint32_t>(),
-                                                        ctx->large_dist_t.as<float>(), st, selection_dev, status_dev);
+                                                        ctx->large_dist_t.as<float>(), st, selection_dev, &status_dev->status);
         }
         BYZ_TRY(check_launch("large_decide_kernel / large_rescore_kernel / large_settle_kernel"));
         int32_t* host = static_cast<int32_t*>(ctx->pinned.ptr);
         BYZ_HIP(hipMemcpyAsync(host, st.words, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        BYZ_HIP(hipMemcpyAsync(host + 1, status_dev, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        BYZ_HIP(hipMemcpyAsync(host + 1, &status_dev->status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         BYZ_HIP(hipStreamSynchronize(stream));
         if (host[1] != 0) break;                 // the reference's KeyError: the caller reads the status word
         BYZ_REQUIRE(host[0] > next || host[0] >= theta, "bulyan loop (large): no pick settled in %lld batches", (long long)queued);

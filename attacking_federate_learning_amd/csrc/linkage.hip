@@ -412,8 +412,7 @@ int launch_linkage_slots(const LinkageScratch& t, int n, int method, int32_t* pa
 }  // namespace
 
 int linkage_workspace(byz_ctx* ctx, int64_t n, LinkageScratch* out) {
-    BYZ_TRY(ctx->linkage_info.ensure(sizeof(LinkageInfo)));      // (allocated once: the size never changes)
-    out->info = ctx->linkage_info.as<LinkageInfo>();
+    out->info = &device_scalars(ctx)->linkage;
     Carve c;
     c.take(&out->W, n * n);
     c.take(&out->near_d, n);

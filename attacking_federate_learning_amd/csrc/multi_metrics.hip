@@ -228,8 +228,7 @@ __global__ __launch_bounds__(256) void mm_zero_if_empty_kernel(const int32_t* __
 }  // namespace
 
 int multi_metrics_workspace(byz_ctx* ctx, int64_t n, bool matrices, MmScratch* out) {
-    BYZ_TRY(ctx->multi_metrics_info.ensure(sizeof(MmInfo)));      // (allocated once: the size never changes)
-    out->info = ctx->multi_metrics_info.as<MmInfo>();
+    out->info = &device_scalars(ctx)->mm;
     Carve c;
     c.take(&out->man, matrices ? n * n : 0);
     c.take(&out->cos, matrices ? n * n : 0);

@@ -50,10 +50,10 @@ __global__ __launch_bounds__(kKeyThreads) void nnm_keys_kernel(const float* __re
     keys[static_cast<int64_t>(i) * n_pad + r] = key;
 }
 
-// one workgroup a row.  nbr: n x k int32 (ascending, then -1); counts (optional): n; words: the context's small area
+// one workgroup a row.  nbr: n x k int32 (ascending, then -1); counts (optional): n; report: the context's, zeroed before
 __global__ __launch_bounds__(kTakeThreads) void nnm_take_kernel(const unsigned long long* __restrict__ keys, int n, int64_t n_pad,
                                                                 int k, int32_t* __restrict__ nbr, int32_t* __restrict__ counts,
-                                                                int32_t* __restrict__ words) {
+                                                                NnmReport* __restrict__ report) {
     __shared__ uint32_t bitmap[kBitmapWords];
     __shared__ int offsets[kTakeThreads];
     const int tid = threadIdx.x;
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(kTakeThreads) void nnm_take_kernel(const unsigned l
     for (int t = k_i + tid; t < k; t += kTakeThreads) list[t] = -1;
     if (tid == 0) {
         if (counts != nullptr) counts[i] = k_i;
-        if (k_i < k) atomicAdd(words + kNnmShort, 1);
-        if (k_i == 1 && k > 1) atomicAdd(words + kNnmSolo, 1);
+        if (k_i < k) atomicAdd(&report->short_rows, 1);
+        if (k_i == 1 && k > 1) atomicAdd(&report->solo, 1);
     }
 }
 
@@ -257,12 +257,13 @@ int launch_nnm_neighbours(byz_ctx* ctx, const float* dist, int64_t n, int64_t k,
     BYZ_TRY(ctx->nnm_keys.ensure(static_cast<size_t>(n) * n_pad * 8));
     unsigned long long* keys = ctx->nnm_keys.as<unsigned long long>();
     KernelTimer t(ctx, BYZ_K_ROW_SORT, stream);
-    BYZ_HIP(hipMemsetAsync(geomed_words(ctx) + kNnmSolo, 0, 2 * sizeof(int32_t), stream));
+    NnmReport* report = &device_scalars(ctx)->nnm;
+    BYZ_HIP(hipMemsetAsync(report, 0, sizeof *report, stream));
     nnm_keys_kernel<<<dim3(static_cast<unsigned>(ceil_div(n_pad, kKeyThreads)), static_cast<unsigned>(n)), kKeyThreads, 0, stream>>>(
         dist, (int)n, n_pad, keys);
     BYZ_TRY(check_launch("nnm_keys_kernel"));
     if (k > 1) BYZ_TRY(segment_sort_u64(ctx, keys, n, n_pad, stream));     // (k == 1 takes no candidate)
-    nnm_take_kernel<<<static_cast<unsigned>(n), kTakeThreads, 0, stream>>>(keys, (int)n, n_pad, (int)k, nbr, counts, geomed_words(ctx));
+    nnm_take_kernel<<<static_cast<unsigned>(n), kTakeThreads, 0, stream>>>(keys, (int)n, n_pad, (int)k, nbr, counts, report);
     return check_launch("nnm_take_kernel");
 }
 

@@ -113,7 +113,7 @@ int launch_sign_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
                 (long long)n_rows);
     WalkShape shape;
     BYZ_TRY(walk_shape(ctx, G, ld, n_cols, "sign votes", &shape));
-    unsigned long long* counter = rlr_flip_counter(ctx);
+    unsigned long long* counter = &device_scalars(ctx)->rlr.flipped;
     BYZ_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), stream));
     const dim3 grid(static_cast<unsigned>(shape.blocks));
     const int32_t th = static_cast<int32_t>(theta);
@@ -137,7 +137,7 @@ int launch_sign_flip(byz_ctx* ctx, const float* agg, const int32_t* votes, int64
         set_error("sign flip: %lld columns is beyond one launch", (long long)n_cols);
         return BYZ_E_UNSUPPORTED;
     }
-    unsigned long long* counter = rlr_flip_counter(ctx);
+    unsigned long long* counter = &device_scalars(ctx)->rlr.flipped;
     BYZ_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), stream));
     KernelTimer t(ctx, BYZ_K_MISC, stream);
     sign_flip_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, stream>>>(agg, votes, n_cols, static_cast<int32_t>(theta), out, counter);

@@ -1815,7 +1815,7 @@ int launch_krum_argmin(byz_ctx* ctx, int64_t n, int32_t* winner_dev, hipStream_t
 }
 
 int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta, int64_t drop_count,
-                       int64_t users_count, int64_t corrupted, int32_t* selection_dev, int32_t* status_dev,
+                       int64_t users_count, int64_t corrupted, int32_t* selection_dev, BulyanStatus* status_dev,
                        hipStream_t stream) {
     BYZ_REQUIRE(dist && selection_dev && status_dev && n > 0 && theta >= 0 && theta <= n,
                 "bulyan loop: bad arguments (n=%lld theta=%lld)", (long long)n, (long long)theta);
@@ -1826,7 +1826,7 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
     int32_t* cls_tmp = ctx->twin_class.as<int32_t>();
     int32_t* cls = cls_tmp + n;
     BYZ_HIP(hipMemsetAsync(ctx->xchg.ptr, 0, kGranules * sizeof(unsigned long long), stream));
-    BYZ_HIP(hipMemsetAsync(status_dev, 0, 3 * sizeof(int32_t), stream));   // status, rows re-scored, (unused)
+    BYZ_HIP(hipMemsetAsync(status_dev, 0, sizeof *status_dev, stream));
     KernelTimer t(ctx, BYZ_K_BULYAN_LOOP, stream);
     twin_class_kernel<<<static_cast<unsigned>(ceil_div(n, 4)), 256, 0, stream>>>(dist, (int)n, cls_tmp);
     BYZ_TRY(check_launch("twin_class_kernel"));
@@ -1857,13 +1857,13 @@ int launch_bulyan_loop(byz_ctx* ctx, const float* dist, int64_t n, int64_t theta
         spec<<<n_wgs, n >= 6000 ? 512 : 256, 0, stream>>>(
             dist, (int)n, (int)theta, (int)drop_count, (int)users_count, (int)corrupted, ctx->sorted_idx.as<uint16_t>(),
             ctx->rank_t.as<uint16_t>(), ctx->sorted_val.as<float>(), ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls,
-            ctx->xchg.as<unsigned long long>(), selection_dev, status_dev, status_dev + 1, batch, owner);
+            ctx->xchg.as<unsigned long long>(), selection_dev, &status_dev->status, &status_dev->rescored, batch, owner);
         return check_launch("bulyan_spec_kernel");
     }
     bulyan_grid_kernel<<<n_wgs, kGridThreads, 0, stream>>>(
         dist, (int)n, (int)theta, (int)drop_count, (int)users_count, (int)corrupted, ctx->sorted_idx.as<uint16_t>(),
         ctx->rank_t.as<uint16_t>(), ctx->sorted_val.as<float>(), ctx->row_total.as<double>(), ctx->row_top.as<double>(), cls,
-        ctx->xchg.as<unsigned long long>(), selection_dev, status_dev, status_dev + 1);
+        ctx->xchg.as<unsigned long long>(), selection_dev, &status_dev->status, &status_dev->rescored);
     return check_launch("bulyan_grid_kernel");
 }
 

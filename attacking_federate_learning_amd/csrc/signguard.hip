@@ -162,7 +162,6 @@ struct SgState {
     int32_t finite_rows, seeds, centres, clusters;
 };
 
-__device__ __forceinline__ double* f64_word(int32_t* words, int at) { return reinterpret_cast<double*>(words + at); }
 __device__ __forceinline__ double sqdist3(const double* a, double b0, double b1, double b2) {
     const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
     return (d0 * d0 + d1 * d1) + d2 * d2;
@@ -191,14 +190,14 @@ __global__ __launch_bounds__(256) void sg_norm_keys_kernel(const double* __restr
 __global__ __launch_bounds__(256) void sg_features_kernel(const double* __restrict__ pznq, int64_t n,
                                                           const unsigned long long* __restrict__ sorted_keys, const SgState* state,
                                                           double window_len, double lower, double upper, double* __restrict__ feat,
-                                                          int32_t* __restrict__ norm_ok, int32_t* words) {
+                                                          int32_t* __restrict__ norm_ok, SgReport* report) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n) return;
     const int32_t finite_rows = state->finite_rows;
     double M = __builtin_nan("");
     if (finite_rows > 0)      // np.median: the middle value, or the mean of the two middle values
         M = median_of_norm_keys(sorted_keys, finite_rows);
-    if (i == 0) *f64_word(words, kSgMedian) = M;
+    if (i == 0) report->median = M;
     const double q = pznq[3 * n + i];
     const double norm = sqrt(q);
     norm_ok[i] = __builtin_isfinite(q) && lower * M < norm && norm < upper * M ? 1 : 0;
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(256) void sg_kth_distance_kernel(const double* __re
 }
 
 // h = the caller's, or the mean of kth in sample order; flat: h is 0, not finite, or too small for the bins to pack
-__global__ void sg_bandwidth_kernel(const double* __restrict__ kth, int s, double given, int32_t* words) {
+__global__ void sg_bandwidth_kernel(const double* __restrict__ kth, int s, double given, SgReport* report) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double h = given;
     if (!(given > 0.0)) {
@@ -242,20 +241,20 @@ __global__ void sg_bandwidth_kernel(const double* __restrict__ kth, int s, doubl
         for (int j = 0; j < s; ++j) sum = sum + kth[j];
         h = sum / static_cast<double>(s);
     }
-    *f64_word(words, kSgBandwidth) = h;
-    words[kSgFlat] = __builtin_isfinite(h) && h >= kSgMinBandwidth ? 0 : 1;
+    report->bandwidth = h;
+    report->flat = __builtin_isfinite(h) && h >= kSgMinBandwidth ? 0 : 1;
 }
 
 // the packed bin of every row: rint(x / h), ties to even, 21 bits a coordinate (x < 1 and h >= 2^-20)
 __global__ __launch_bounds__(256) void sg_bins_kernel(const double* __restrict__ feat, int64_t n, int64_t n_pad,
-                                                      const int32_t* words, unsigned long long* __restrict__ keys) {
+                                                      const SgReport* report, unsigned long long* __restrict__ keys) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n_pad) return;
-    if (i >= n || words[kSgFlat] != 0) {
+    if (i >= n || report->flat != 0) {
         keys[i] = kNoKey;
         return;
     }
-    const double h = *reinterpret_cast<const double*>(words + kSgBandwidth);
+    const double h = report->bandwidth;
     unsigned long long key = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) key = key << kBinBits | static_cast<unsigned long long>(rint(feat[3 * i + k] / h));
@@ -305,12 +304,12 @@ __device__ __forceinline__ void shift_totals(double (&s)[3], int& count, double 
 // with squared distance <= h^2, the new centre their mean; the stop: a move <= 1e-3 h, or kSgMaxShifts updates.
 __global__ __launch_bounds__(kShiftThreads) void sg_mean_shift_kernel(const double* __restrict__ feat, int64_t n,
                                                                       const unsigned long long* __restrict__ seeds,
-                                                                      const SgState* state, const int32_t* words,
+                                                                      const SgState* state, const SgReport* report,
                                                                       double* __restrict__ centres, int32_t* __restrict__ members) {
     __shared__ double lds[kShiftThreads / 64][4];
     const int sid = blockIdx.x;
     if (sid >= state->seeds) return;
-    const double h = *reinterpret_cast<const double*>(words + kSgBandwidth);
+    const double h = report->bandwidth;
     const double h2 = h * h, stop = 1e-3 * h;
     const unsigned long long key = seeds[sid];
     constexpr unsigned long long kMask = (1ull << kBinBits) - 1;
@@ -369,11 +368,11 @@ __global__ __launch_bounds__(256) void sg_rank_kernel(const double* __restrict__
 // One workgroup.  Through the ranked centres: one still standing removes every later one within <= h.  Then the standing ones,
 // in rank order, are the clusters (final: 3 doubles each); their row counts are zeroed for the labelling.
 __global__ __launch_bounds__(kStepThreads) void sg_suppress_kernel(const double* __restrict__ centres, const int32_t* __restrict__ order,
-                                                                   SgState* state, const int32_t* words, int32_t* standing,
+                                                                   SgState* state, const SgReport* report, int32_t* standing,
                                                                    double* __restrict__ final_centres, int32_t* __restrict__ label_rows) {
     __shared__ int lds[kStepThreads];
     const int live = state->centres;
-    const double h = *reinterpret_cast<const double*>(words + kSgBandwidth);
+    const double h = report->bandwidth;
     const double h2 = h * h;
     for (int r = threadIdx.x; r < live; r += kStepThreads) standing[r] = 1;
     for (int r = 0; r < live; ++r) {
@@ -405,15 +404,15 @@ __global__ __launch_bounds__(kStepThreads) void sg_suppress_kernel(const double*
 
 // the nearest cluster's number, the first on ties; -1 when it is farther than h; flat: 0
 __global__ __launch_bounds__(256) void sg_labels_kernel(const double* __restrict__ feat, int64_t n, const double* __restrict__ final_centres,
-                                                        const SgState* state, const int32_t* words, int32_t* __restrict__ labels,
+                                                        const SgState* state, const SgReport* report, int32_t* __restrict__ labels,
                                                         int32_t* label_rows) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n) return;
-    if (words[kSgFlat] != 0) {
+    if (report->flat != 0) {
         labels[i] = 0;
         return;
     }
-    const double h = *reinterpret_cast<const double*>(words + kSgBandwidth);
+    const double h = report->bandwidth;
     const int clusters = state->clusters;
     int best = -1;
     double best_d2 = 0.0;
@@ -429,14 +428,14 @@ __global__ __launch_bounds__(256) void sg_labels_kernel(const double* __restrict
     if (best >= 0) atomicAdd(label_rows + best, 1);
 }
 
-// One workgroup: the benign cluster (the most rows, the lowest number on ties), keep, w, K and the counts into the words
+// One workgroup: the benign cluster (the most rows, the lowest number on ties), keep, w, K and the counts into the report
 __global__ __launch_bounds__(kStepThreads) void sg_result_kernel(const double* __restrict__ pznq, int64_t n, const int32_t* __restrict__ norm_ok,
                                                                  const int32_t* __restrict__ labels, const int32_t* __restrict__ label_rows,
-                                                                 const SgState* state, int32_t* words, int32_t* __restrict__ keep,
+                                                                 const SgState* state, SgReport* report, int32_t* __restrict__ keep,
                                                                  double* __restrict__ w, double* mk_out) {
     __shared__ int lds[kStepThreads];
     __shared__ int lds_at[kStepThreads];
-    const bool flat = words[kSgFlat] != 0;
+    const bool flat = report->flat != 0;
     const int clusters = flat ? 1 : state->clusters;
     int benign = flat ? 0 : -1;
     if (!flat) {
@@ -462,7 +461,7 @@ __global__ __launch_bounds__(kStepThreads) void sg_result_kernel(const double* _
         benign = lds_at[0];
         __syncthreads();
     }
-    const double M = *f64_word(words, kSgMedian);
+    const double M = report->median;
     const int64_t per = (n + kStepThreads - 1) / kStepThreads;
     const int64_t lo = threadIdx.x * per < n ? threadIdx.x * per : n;
     const int64_t hi = lo + per < n ? lo + per : n;
@@ -481,12 +480,12 @@ __global__ __launch_bounds__(kStepThreads) void sg_result_kernel(const double* _
     const int n_failed = block_sum<int, kStepThreads>(failed, lds);
     const int n_outside = block_sum<int, kStepThreads>(outside, lds);
     if (threadIdx.x == 0) {
-        words[kSgKept] = n_kept;
-        words[kSgNormFailed] = n_failed;
-        words[kSgOutside] = n_outside;
-        words[kSgClusters] = clusters;
-        words[kSgSeeds] = flat ? 0 : state->seeds;
-        *f64_word(words, kSgKeptF64) = static_cast<double>(n_kept);
+        report->kept = n_kept;
+        report->norm_failed = n_failed;
+        report->outside = n_outside;
+        report->clusters = clusters;
+        report->seeds = flat ? 0 : state->seeds;
+        report->kept_f64 = static_cast<double>(n_kept);
         if (mk_out != nullptr) {
             mk_out[0] = M;
             mk_out[1] = static_cast<double>(n_kept);
@@ -545,7 +544,7 @@ int launch_signguard_counts_f64(byz_ctx* ctx, const long long* counts, const dou
     return check_launch("counts_to_f64_kernel");
 }
 
-// pznq (4n fp64: pos, zero, neg, q) -> keep, w, labels (n each; never null), M and K into the context's words (and mk_out,
+// pznq (4n fp64: pos, zero, neg, q) -> keep, w, labels (n each; never null), M and K into the context's report (and mk_out,
 // optional: two device doubles).  sample: n_sample device int32 row numbers, read only when bandwidth is not > 0.
 int launch_signguard_select(byz_ctx* ctx, const SgScratch& t, const double* pznq, int64_t n, int64_t window_len, double lower,
                             double upper, double bandwidth, const int32_t* sample, int64_t n_sample, int32_t* keep, double* w,
@@ -555,7 +554,7 @@ int launch_signguard_select(byz_ctx* ctx, const SgScratch& t, const double* pznq
     BYZ_REQUIRE(!estimate || (sample && n_sample >= 1 && n_sample <= kSgMaxSamples), "signguard select: bad sample");
     static_assert(sizeof(SgState) <= 64, "the state's slot");
     SgState* state = reinterpret_cast<SgState*>(t.state);
-    int32_t* words = geomed_words(ctx);
+    SgReport* report = &device_scalars(ctx)->sg;
     const int64_t n_pad = padded_rows(n);
     const unsigned row_blocks = static_cast<unsigned>(ceil_div(n, 256)), pad_blocks = static_cast<unsigned>(ceil_div(n_pad, 256));
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
@@ -564,29 +563,29 @@ int launch_signguard_select(byz_ctx* ctx, const SgScratch& t, const double* pznq
     BYZ_TRY(check_launch("sg_norm_keys_kernel"));
     BYZ_TRY(segment_sort_u64(ctx, t.keys, 1, n_pad, stream));
     sg_features_kernel<<<row_blocks, 256, 0, stream>>>(pznq, n, t.keys, state, static_cast<double>(window_len), lower, upper, t.feat,
-                                                       t.norm_ok, words);
+                                                       t.norm_ok, report);
     BYZ_TRY(check_launch("sg_features_kernel"));
     if (estimate) {
         const int s = static_cast<int>(n_sample);
         sg_kth_distance_kernel<<<static_cast<unsigned>(s), 256, 0, stream>>>(t.feat, n, sample, s, std::max(1, s / 2), t.kth);
         BYZ_TRY(check_launch("sg_kth_distance_kernel"));
     }
-    sg_bandwidth_kernel<<<1, 64, 0, stream>>>(t.kth, static_cast<int>(n_sample), estimate ? 0.0 : bandwidth, words);
+    sg_bandwidth_kernel<<<1, 64, 0, stream>>>(t.kth, static_cast<int>(n_sample), estimate ? 0.0 : bandwidth, report);
     BYZ_TRY(check_launch("sg_bandwidth_kernel"));
-    sg_bins_kernel<<<pad_blocks, 256, 0, stream>>>(t.feat, n, n_pad, words, t.keys);
+    sg_bins_kernel<<<pad_blocks, 256, 0, stream>>>(t.feat, n, n_pad, report, t.keys);
     BYZ_TRY(check_launch("sg_bins_kernel"));
     BYZ_TRY(segment_sort_u64(ctx, t.keys, 1, n_pad, stream));
     sg_seeds_kernel<<<1, kStepThreads, 0, stream>>>(t.keys, n, t.seeds, state);
     BYZ_TRY(check_launch("sg_seeds_kernel"));
-    sg_mean_shift_kernel<<<static_cast<unsigned>(n), kShiftThreads, 0, stream>>>(t.feat, n, t.seeds, state, words, t.centres, t.members);
+    sg_mean_shift_kernel<<<static_cast<unsigned>(n), kShiftThreads, 0, stream>>>(t.feat, n, t.seeds, state, report, t.centres, t.members);
     BYZ_TRY(check_launch("sg_mean_shift_kernel"));
     sg_rank_kernel<<<row_blocks, 256, 0, stream>>>(t.centres, t.members, state, t.order);
     BYZ_TRY(check_launch("sg_rank_kernel"));
-    sg_suppress_kernel<<<1, kStepThreads, 0, stream>>>(t.centres, t.order, state, words, t.standing, t.final_centres, t.label_rows);
+    sg_suppress_kernel<<<1, kStepThreads, 0, stream>>>(t.centres, t.order, state, report, t.standing, t.final_centres, t.label_rows);
     BYZ_TRY(check_launch("sg_suppress_kernel"));
-    sg_labels_kernel<<<row_blocks, 256, 0, stream>>>(t.feat, n, t.final_centres, state, words, labels, t.label_rows);
+    sg_labels_kernel<<<row_blocks, 256, 0, stream>>>(t.feat, n, t.final_centres, state, report, labels, t.label_rows);
     BYZ_TRY(check_launch("sg_labels_kernel"));
-    sg_result_kernel<<<1, kStepThreads, 0, stream>>>(pznq, n, t.norm_ok, labels, t.label_rows, state, words, keep, w, mk_out);
+    sg_result_kernel<<<1, kStepThreads, 0, stream>>>(pznq, n, t.norm_ok, labels, t.label_rows, state, report, keep, w, mk_out);
     return check_launch("sg_result_kernel");
 }
 

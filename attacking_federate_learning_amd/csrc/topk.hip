@@ -131,12 +131,11 @@ __global__ __launch_bounds__(kThreads) void topk_bins_f64_kernel(const unsigned 
 
 // ---- one workgroup: the bins walked from the top ------------------------------------------------------------------------------
 // hist_f64 != nullptr: the all-reduced bins of every rank (then hist is this rank's own, read for its ties after the last pass
-// and written as a double into gather[rank_index]).  info: the four values byz_topk_info reports (selected, ties, taken as
-// 64-bit, then the key), written after the last pass.
+// and written as a double into gather[rank_index]).  info: the four values byz_topk_info reports, written after the last pass.
 __global__ __launch_bounds__(kThreads) void topk_find_kernel(const unsigned long long* __restrict__ hist, const double* __restrict__ hist_f64,
                                                              int pass, unsigned long long k, TopkState* __restrict__ state,
                                                              double* __restrict__ gather, int rank_index,
-                                                             unsigned long long* __restrict__ info) {
+                                                             TopkReport* __restrict__ info) {
     __shared__ unsigned long long scan[kThreads];
     const int bits = pass_bits(pass), n_bins = 1 << bits, per = n_bins / kThreads;   // 8 or 4 bins a thread
     const int tid = threadIdx.x;
@@ -175,10 +174,10 @@ __global__ __launch_bounds__(kThreads) void topk_find_kernel(const unsigned long
                 if (last) {
                     state->ties = h[j];
                     state->quota = quota;
-                    info[0] = k;
-                    info[1] = h[j];
-                    info[2] = quota;
-                    info[3] = found;
+                    info->selected = k;
+                    info->ties = h[j];
+                    info->taken = quota;
+                    info->key = found;
                     if (gather != nullptr) gather[rank_index] = static_cast<double>(hist[top - j]);
                 }
             }
@@ -191,10 +190,10 @@ __global__ __launch_bounds__(kThreads) void topk_find_kernel(const unsigned long
         if (last) {
             state->ties = 0;
             state->quota = 0;
-            info[0] = 0;
-            info[1] = 0;
-            info[2] = 0;
-            info[3] = kNoKey;
+            info->selected = 0;
+            info->ties = 0;
+            info->taken = 0;
+            info->key = kNoKey;
         }
     }
 }
@@ -396,7 +395,7 @@ int topk_pass(byz_ctx* ctx, const TopkScratch& t, const float* x, const float* a
     }
     KernelTimer timer(ctx, BYZ_K_MISC, s);
     topk_find_kernel<<<1, kThreads, 0, s>>>(hist, allreduce != nullptr ? t.f64 : nullptr, PASS, static_cast<unsigned long long>(k),
-                                            state, allreduce != nullptr ? gather : nullptr, rank_index, topk_info_words(ctx));
+                                            state, allreduce != nullptr ? gather : nullptr, rank_index, &device_scalars(ctx)->topk);
     return check_launch("topk_find_kernel");
 }
 
