@@ -218,6 +218,10 @@ _PROTOTYPES = {
     'byz_clipped_clustering_host': [c_vp, c_vp, c_i64, c_i64, _P(ClippedClusteringParams), c_vp, c_vp, c_vp, c_vp],
     'byz_clipped_clustering_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(ClippedClusteringParams), c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp],
+    'byz_faba_select_dev': [c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
+    'byz_faba_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_faba_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
+    'byz_faba_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],

@@ -1855,6 +1855,76 @@ int byz_clipped_clustering_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* u
     return BYZ_OK;
 }
 
+// ---- FABA (Xia, Chen, Yu & Ma, IJCAI 2019; beyond the reference) ------------------------------------------------------------------
+namespace {
+
+int check_faba(const char* who, int64_t n, int64_t remove_count, int power) {
+    if (n > kFabaMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kFabaMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    if (n < 2) {
+        set_error("%s: at least 2 rows, got %lld", who, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (remove_count < 0 || remove_count > n - 1) {
+        set_error("%s: remove_count = %lld outside 0..n - 1 (n = %lld)", who, (long long)remove_count, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (power != 1 && power != 2) {
+        set_error("%s: power = %d is neither 1 (the distances) nor 2 (their squares)", who, power);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_faba_select_dev(byz_ctx* ctx, const float* dist, int64_t n_rows, int64_t remove_count, int power, int32_t* kept,
+                        int32_t* order, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(dist && kept, "faba_select: null distances or output");
+    BYZ_TRY(check_faba("faba_select", n_rows, remove_count, power));
+    FabaScratch f;
+    BYZ_TRY(faba_workspace(ctx, n_rows, &f));
+    mark(ctx, kReportFaba, as_stream(stream));
+    return launch_faba_select(ctx, f, dist, n_rows, remove_count, power, kept, order, as_stream(stream));
+}
+
+// It waits where byz_pairwise_distances_dev waits (the Gram's duplicate search), and nowhere when the caller passes the distances.
+int byz_faba_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t remove_count, const float* dist_in,
+                 float* out, int32_t* kept, int32_t* order, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "faba"));
+    BYZ_REQUIRE(out, "faba: null output");
+    BYZ_TRY(check_faba("faba", n_rows, remove_count, 2));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "faba"));
+    hipStream_t s = as_stream(stream);
+    FabaScratch f;
+    BYZ_TRY(faba_workspace(ctx, n_rows, &f));
+    mark(ctx, kReportFaba, s);
+    const float* dist = dist_in;
+    if (dist == nullptr) {
+        BYZ_TRY(ensure_distance_workspaces(ctx, n_rows));
+        BYZ_TRY(distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, ctx->dist.as<float>(), stream));
+        dist = ctx->dist.as<float>();
+    }
+    BYZ_TRY(launch_faba_select(ctx, f, dist, n_rows, remove_count, 2, kept, order, s));
+    return launch_scaled_rows_sum(ctx, G, n_rows, n_cols, ld, f.w, &f.info->kept_f64, out, s);
+}
+
+int byz_faba_info(byz_ctx* ctx, int64_t* removed_rows, int64_t* kept_rows, int64_t* forced_rows, double* last_score, double* divisor) {
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportFaba, "faba_info: no FABA selection on this context yet", &all));
+    const FabaReport& info = all.faba;
+    if (removed_rows) *removed_rows = info.removed;
+    if (kept_rows) *kept_rows = info.kept;
+    if (forced_rows) *forced_rows = info.forced;
+    if (last_score) *last_score = info.last_score;
+    if (divisor) *divisor = info.kept_f64;
+    return BYZ_OK;
+}
+
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
@@ -2812,6 +2882,24 @@ int byz_clipped_clustering_host(byz_ctx* ctx, const float* G_host, int64_t n_row
     st.out(&admitted, admitted_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_clipped_clustering_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, dist, sq, out, admitted, st.stream()));
+    return st.finish();
+}
+
+int byz_faba_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t remove_count, const float* dist_host,
+                  float* out_host, int32_t* kept_host, int32_t* order_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "faba"));
+    BYZ_REQUIRE(out_host, "faba: null output");
+    BYZ_TRY(check_faba("faba", n_rows, remove_count, 2));
+    HostStage st(ctx);
+    float *out, *dist;
+    int32_t *kept, *order;
+    st.out(&out, out_host, n_cols);
+    st.in(&dist, dist_host, n_rows * n_rows);
+    st.out(&kept, kept_host, n_rows);
+    st.out(&order, order_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_faba_dev(ctx, st.G(), n_rows, n_cols, n_cols, remove_count, dist, out, kept, order, st.stream()));
     return st.finish();
 }
 

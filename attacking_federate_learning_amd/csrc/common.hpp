@@ -162,6 +162,8 @@ struct byz_ctx {
     byz::Buffer multi_metrics;   // Multi-Metrics, carved into MmScratch's arrays (multi_metrics.hip: multi_metrics_workspace)
     byz::Buffer linkage;         // agglomerative clustering, carved into LinkageScratch's arrays (linkage.hip: linkage_workspace): the fp64
                                  // working matrix (n x n), the first nearest partners, the merges, the labels, the flags, the weights
+    byz::Buffer faba;            // FABA, carved into FabaScratch's arrays (faba.hip: faba_workspace): the rows' sums and bad counts, the
+                                 // removal order, the kept flags, the weights
     byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
                                  // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
     // the last Krum attack's values (byz_fang_krum_info reports them; last[kReportFangKrum] says whether there was one)
@@ -491,6 +493,18 @@ int launch_linkage_cut(byz_ctx* ctx, const int32_t* pair, int64_t n, const int32
 // linkage, 2-cut, the larger cluster: t.admitted (and admitted_out, optional), the scalars into t.info
 int launch_clipped_clustering_select(byz_ctx* ctx, const LinkageScratch& t, const float* dist, int64_t n, int method, double fill,
                                      int32_t* admitted_out, hipStream_t stream);
+// faba.hip: FABA's selection on a distance matrix.  The scalars of a call: DeviceScalars::faba.
+constexpr int64_t kFabaMaxRows = 16384;      // the loop's one workgroup owns 1024 x 16 rows
+struct FabaScratch {
+    FabaReport* info;
+    double *s, *w;                   // n: every row's initial sum; the aggregate's 0 / 1 weights
+    int32_t *bad, *order, *kept;     // n: every row's initial bad count; the removal order (-1 behind it); the 0 / 1 flags
+};
+int faba_workspace(byz_ctx* ctx, int64_t n, FabaScratch* out);
+// the initial sums, the removal loop: t.kept and t.w (kept_out optional), the order into order_out (or t.order), the scalars into
+// t.info
+int launch_faba_select(byz_ctx* ctx, const FabaScratch& t, const float* dist, int64_t n, int64_t r, int power, int32_t* kept_out,
+                       int32_t* order_out, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

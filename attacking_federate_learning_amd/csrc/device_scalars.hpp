@@ -80,6 +80,12 @@ struct LinkageInfo {
     double admitted_f64;             // the divisor of the sum
     double clip;                     // byz_clipped_clustering_dev: the clip used
 };
+struct FabaReport {
+    int32_t removed, kept;           // the rows removed; the rows kept (they add up to n)
+    int32_t forced, pad;             // the rows removed beyond the caller's count because a bad count forced it
+    double last_score;               // s of the last removed row (0 when nobody was removed)
+    double kept_f64;                 // the divisor of the sum
+};
 
 struct DeviceScalars {
     CoreScalars core;
@@ -95,6 +101,7 @@ struct DeviceScalars {
     FlameInfo flame;
     MmInfo mm;
     LinkageInfo linkage;
+    FabaReport faba;
 };
 
 // What a read-back as bytes, and a 64-bit store or atomic of a kernel, rely on.  No member is padded by the compiler: the sizes
@@ -104,13 +111,13 @@ static_assert(sizeof(CoreScalars) % sizeof(int32_t) == 0 && sizeof(DeviceScalars
 static_assert(sizeof(DeviceScalars) == sizeof(CoreScalars) + sizeof(GeomedReport) + sizeof(DncReport) + sizeof(CclipReport) +
                                            sizeof(FltrustReport) + sizeof(NnmReport) + sizeof(RlrReport) + sizeof(SgReport) +
                                            sizeof(TopkReport) + sizeof(WeakDpReport) + sizeof(FlameInfo) + sizeof(MmInfo) +
-                                           sizeof(LinkageInfo), "no padding between the reports");
+                                           sizeof(LinkageInfo) + sizeof(FabaReport), "no padding between the reports");
 #define BYZ_AT(member) offsetof(DeviceScalars, member)
 constexpr size_t kEightByteFields[] = {
     BYZ_AT(geomed.objective), BYZ_AT(fltrust.trust_sum), BYZ_AT(rlr.flipped), BYZ_AT(sg.bandwidth), BYZ_AT(sg.median),
     BYZ_AT(sg.kept_f64), BYZ_AT(topk.selected), BYZ_AT(topk.ties), BYZ_AT(topk.taken), BYZ_AT(topk.key), BYZ_AT(weak_dp.clip),
     BYZ_AT(flame.admitted_f64), BYZ_AT(flame.clip), BYZ_AT(mm.det), BYZ_AT(linkage.top_height), BYZ_AT(linkage.second_height),
-    BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip)};
+    BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64)};
 #undef BYZ_AT
 constexpr bool eight_byte_fields_aligned() {
     for (size_t at : kEightByteFields)
@@ -122,7 +129,7 @@ static_assert(eight_byte_fields_aligned(), "every double and 64-bit counter sits
 // the reports an info call reads; byz_ctx::last[kind]: the stream of the last call that wrote it, and whether there was one
 enum ReportKind {
     kReportGeomed, kReportDnc, kReportCclip, kReportFltrust, kReportNnm, kReportRlr, kReportSignguard, kReportTopk, kReportWeakDp,
-    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportCount
+    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportFaba, kReportCount
 };
 struct LastCall { hipStream_t stream = nullptr; bool ran = false; };
 

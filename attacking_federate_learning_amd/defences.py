@@ -356,6 +356,23 @@ def clipped_clustering(users_grads, users_count, corrupted_count, clip=None, met
     return (got[0].numpy(), got[1]) if return_info else got.numpy()
 
 
+def faba(users_grads, users_count, corrupted_count, distances=None, return_info=False):
+    """FABA (Xia, Chen, Yu and Ma, IJCAI 2019; not in the reference): the mean of the clients is taken, the client farthest
+    from it dropped, corrupted_count times over; the rest are averaged.  The oldest family of rules, iterative outlier
+    removal, and the baseline the clustering defences here are compared with.  It runs on ONE pairwise distance matrix:
+    the client farthest from the mean of a set is the client with the largest sum of squared distances to the set, and a
+    removal takes one entry off every other client's sum, so the gradients are read for the distances and for the final
+    mean and never in between.  A client with a NaN or infinite entry goes first and counts towards corrupted_count;
+    identical clients tie and go lowest row first.  FABA removes what is FAR from the crowd: the drift attack's rows,
+    which sit inside it, pass, as they pass `krum`.  `distances=` (a `Distances` handle or a dense matrix of Euclidean
+    distances) replaces the distance stage.  Asserts users_count >= 2*corrupted_count + 1, as `multi_krum` does.  numpy
+    in -> numpy out, device-resident in -> device-resident out.  return_info=True returns (vector, {kept_rows, order,
+    removed, kept, forced, last_score, divisor}).  Not one of the `defend` keys: the reference's main.py offers only
+    those four."""
+    assert users_count >= 2 * corrupted_count + 1, ('users_count>=2*corrupted_count + 1', users_count, corrupted_count)
+    return get_engine().faba(users_grads, users_count, corrupted_count, distances=distances, return_info=return_info)
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -1922,6 +1922,98 @@ class Engine:
         info['admitted_rows'] = np.flatnonzero(flags).astype(np.int64)
         return out, info
 
+    # ---- FABA (Xia, Chen, Yu & Ma, IJCAI 2019; not in the reference) ----
+    @staticmethod
+    def _faba_args(n, remove_count, power=2):
+        """(remove_count, power) checked as the library checks them (the refusals that need no GPU)."""
+        n, r = int(n), int(remove_count)
+        if n > 16384:
+            raise NotImplementedError('faba: at most 16384 rows, got %d' % n)
+        if n < 2:
+            raise ValueError('faba: at least 2 rows, got %d' % n)
+        if r < 0 or r > n - 1:
+            raise ValueError('faba: remove_count = %d outside 0..n - 1 (n = %d)' % (r, n))
+        if power not in (1, 2):
+            raise ValueError('faba: power = %r is neither 1 (the distances) nor 2 (their squares)' % (power,))
+        return r, int(power)
+
+    def faba_info(self):
+        """{removed, kept, forced, last_score, divisor} of the last faba_select or faba on this engine (synchronises): the rows
+        removed and kept, the rows removed beyond remove_count because a row had an unusable distance to a kept row, the
+        summed (squared) distance of the last removed row at its removal (0: nobody was removed) and the sum's divisor."""
+        return dict(zip(('removed', 'kept', 'forced', 'last_score', 'divisor'),
+                        self._read(self.lib.byz_faba_info,
+                                   [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double])))
+
+    def faba_select(self, distances, remove_count, power=2, on_device=False, like=None, return_order=False):
+        """FABA's selection on a distance matrix (a `Distances` handle or a dense symmetric matrix, the diagonal ignored):
+        remove_count times, the kept row with the largest sum of (power 2: squared) distances to the kept rows is removed,
+        which for Euclidean distances is the row farthest from the kept rows' mean (include/byzagg.h states the rule).  A
+        row with an entry that is not finite or is negative against a kept row goes first and is never kept.  power=1 sums
+        the distances themselves (cosine, Manhattan).  Returns (rows, info): the kept rows ascending (on_device=True: the
+        0 / 1 int32 flags instead, as a DeviceBuffer, or a torch tensor beside `like`) and {removed, kept, forced,
+        last_score, divisor}; return_order=True: (rows, order, info), order the removed rows in removal order (on_device:
+        n int32, -1 behind them)."""
+        if isinstance(distances, dict):
+            raise ValueError('faba_select() takes a Distances handle or a dense matrix')
+        with _Call(self) as c:
+            d, _ = c.distances(distances)
+            r, power = self._faba_args(d.n, remove_count, power)
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            flags, fptr = c.out(d.n, np.int32)
+            order, optr = c.out(d.n, np.int32, want=return_order)
+            c.run(self.lib.byz_faba_select_dev(self.ctx, d.ptr, d.n, r, power, fptr, optr, None))
+            info = self.faba_info()
+        if not on_device:
+            flags = np.flatnonzero(flags.numpy()).astype(np.int64)
+            if return_order:
+                order = order.numpy()[:info['removed']].astype(np.int64)
+        return (flags, order, info) if return_order else (flags, info)
+
+    def faba(self, g, users_count, corrupted_count, distances=None, return_info=False):
+        """FABA in one library call: pairwise_distances (or `distances`, which replaces that stage), faba_select with
+        remove_count = corrupted_count on the squared distances, and the mean of the kept rows: scaled_rows_sum's bits with
+        the 0 / 1 flags as weights and the kept count, read on the device, as the divisor.  Nobody kept: the zero vector.
+        return_info=True also returns {kept_rows (ascending), order (the removed rows in removal order), removed, kept,
+        forced, last_score, divisor}."""
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        r, _ = self._faba_args(n, corrupted_count)
+        if isinstance(distances, dict):
+            raise ValueError('faba() takes a Distances handle or a dense matrix as `distances`')
+        with _Call(self) as c:
+            dist = None
+            if distances is not None:
+                dist, _ = c.distances(distances)
+                if dist.n != n:
+                    raise ValueError('the distance matrix has %d rows, the gradients %d' % (dist.n, n))
+            if dm is None:
+                h = self._host_matrix(g)
+                d = h.shape[1]
+                out = np.empty(d, dtype=np.float32)
+                flags = np.zeros(n, dtype=np.int32)
+                order = np.full(n, -1, dtype=np.int32)
+                dist_host = np.ascontiguousarray(dist.numpy(), dtype=np.float32) if dist is not None else None
+                _check(self.lib.byz_faba_host(self.ctx, _hp(h), n, d, r, _hp(dist_host), _hp(out), _hp(flags), _hp(order)))
+            else:
+                dm = c.matrix(dm)
+                out, optr = c.out(dm.cols)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                order, rptr = c.out(n, np.int32, want=return_info)
+                c.run(self.lib.byz_faba_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, r, dist.ptr if dist is not None else None,
+                                            optr, fptr, rptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    flags = _to_host(flags) if _is_torch(flags) else flags.numpy()
+                    order = _to_host(order) if _is_torch(order) else order.numpy()
+        if not return_info:
+            return out
+        info = self.faba_info()
+        info['kept_rows'] = np.flatnonzero(flags).astype(np.int64)
+        info['order'] = np.asarray(order)[:info['removed']].astype(np.int64)
+        return out, info
+
     # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----
     def manhattan_distances(self, g):
         """The pairwise MANHATTAN (L1) distances of g's rows as a `Distances` handle, resident on the GPU: m_ij = sum_c

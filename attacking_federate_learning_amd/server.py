@@ -21,6 +21,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_weak_dp(clip, sigma, then) the same step with norm clipping and Gaussian noise drawn on the GPU, fresh every round
     defend_flame(lam, min_samples)    the same step with FLAME: the majority cluster by cosine distance, clipped, averaged, noised
     defend_clipped_clustering(method) the same step with ClippedClustering: the larger of two average-linkage clusters, clipped
+    defend_faba()                     the same step with FABA: the clients farthest from the running mean dropped one by one
     defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
@@ -251,6 +252,16 @@ class DeviceServer:
         score over their summed Manhattan, Euclidean and cosine distances, averaged, and server.py:89-90's momentum step on
         the result, as `defend` takes it.  Stateless: nothing is carried from round to round."""
         current_grads = defences.multi_metrics(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), p=p)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with FABA -----------------------------------------------------------------------------------
+    def defend_faba(self):
+        """FABA on this round's gradients (defences.faba): int(n_users * mal_prop) times the client farthest from the mean of
+        those still kept is dropped, the rest averaged, and server.py:89-90's momentum step on the result, as `defend` takes
+        it.  Stateless: nothing is carried from round to round."""
+        current_grads = defences.faba(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop))
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

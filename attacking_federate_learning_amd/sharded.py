@@ -175,6 +175,10 @@ class HipKernels:
         # (0 / 1 flags of the admitted rows: an int32 tensor beside `like`; info): the same on every rank
         return self.engine.clipped_clustering_select(dist, method=method, fill=fill, on_device=True, like=like)
 
+    def faba_select(self, dist, remove_count, like, power=2):
+        # (0 / 1 flags of the kept rows: an int32 tensor beside `like`; info): the same on every rank
+        return self.engine.faba_select(dist, remove_count, power=power, on_device=True, like=like)
+
     def manhattan_sums(self, g_local):
         return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
 
@@ -562,6 +566,22 @@ class ShardedAggregator:
         out = self.kernels.mean_rows(g_local, np.sort(selection))
         out = self._maybe_gather(out, gather, total_columns)
         return (out, selection) if return_selection else out
+
+    def faba(self, g_local, users_count, corrupted_count, gather=False, total_columns=None, return_info=False):
+        """FABA (defences.faba's contract), columns layout.  No collective of its own: the distances' all-reduce of the N x N
+        fp64 Gram (global_distances) is the only bulk exchange.  Everything after it is replicated -- kernels.faba_select
+        gives the same flags on every rank -- or local to the columns: the sum of the kept rows over their count.  Returns
+        this rank's columns (gather=True: the whole vector)."""
+        import torch
+        assert users_count >= 2 * corrupted_count + 1, ('users_count>=2*corrupted_count + 1', users_count, corrupted_count)
+        dist_m = self.global_distances(g_local)
+        kept, info = self.kernels.faba_select(dist_m, corrupted_count, g_local)
+        weights = (kept != 0).to(torch.float64)
+        v = self.kernels.scaled_rows_sum(g_local, weights, weights.sum().reshape(1))
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, dict(info, kept_rows=torch.nonzero(kept).reshape(-1).cpu().numpy())
 
     def nnm(self, g_local, users_count, corrupted_count, return_neighbours=False):
         """Nearest-neighbour mixing, columns layout: the distances' one all-reduce and nothing more; the neighbour lists are

@@ -872,6 +872,50 @@ int byz_clipped_clustering_host(byz_ctx* ctx, const float* G_host, int64_t n_row
                                 const byz_clipped_clustering_params* params, const float* dist_host_or_null,
                                 const double* sq_host_or_null, float* out_host, int32_t* admitted_host_or_null);
 
+/* ---- FABA (Xia, Chen, Yu & Ma, "FABA: An Algorithm for Fast Aggregation against Byzantine Attacks in Distributed Neural Networks", */
+/* IJCAI 2019; not in the reference) ----                                                                                            */
+/* The rule: take the mean of the rows still kept, drop the row farthest from it, r times; average the rest.  For a set S of m rows  */
+/* and a row i of S, |g_i - mean(S)|^2 = (1/m) sum_{j in S} |g_i - g_j|^2 - (1/(2 m^2)) sum_{j,k in S} |g_j - g_k|^2, and the second */
+/* term is the same for every i: the farthest row is the row with the largest SUM of squared distances to the kept rows, and the      */
+/* rule runs on an n x n matrix in byz_pairwise_distances_dev's form (fp32, the diagonal ignored, taken as symmetric) without reading */
+/* the gradients again.  The selection, exactly (C: the matrix, r: remove_count, power 1 or 2):                                      */
+/*   An off-diagonal entry c is USABLE when it is finite and >= 0 (-0.0 is, and counts as +0.0).  Its term is e = (double)c for       */
+/*   power 1 and (double)c * (double)c for power 2 (exact in fp64).                                                                  */
+/*   Row i starts with bad_i = the entries C[i][j], j != i, that are not usable, and s_i = the fp64 sum of the terms of those that    */
+/*   are, in this order: 64 chains, chain l the sum, from +0.0, of the terms of the columns j = l, l + 64, l + 128, ... ascending     */
+/*   (the diagonal and entries that are not usable skipped); then chain[l] += chain[l + h] for every l < h, for h = 32, 16, 8, 4, 2,  */
+/*   1 in turn; s_i = chain[0].                                                                                                      */
+/*   A step removes the kept row q that is first in the order (bad descending, s descending by value, row ascending) and then, for    */
+/*   every other row i, reads c = C[q][i]: bad_i -= 1 where c is not usable, s_i = s_i - e(c) (one fp64 subtraction) where it is.     */
+/*   The loop makes r steps and goes on while the largest bad of the kept rows is positive, so that no row with an unusable entry    */
+/*   against a kept row is averaged.  A matrix WITHOUT ANY usable off-diagonal entry judges nobody: every row is removed.            */
+/*   Rows removed = max(r, what the bad counts force) <= n_rows.                                                                     */
+/* Consequences: with power 2 on Euclidean distances this is FABA; rows whose entries are all NaN or +inf (broken gradients) go       */
+/* first, lowest row first, and count towards r; identical rows tie and go lowest row first; power 1 is "largest summed distance",   */
+/* for the cosine and Manhattan matrices.  FABA removes what is far from the crowd: rows that sit inside it (the drift attack's)      */
+/* pass, as they pass Krum.                                                                                                          */
+/* kept_dev: n_rows int32 of 0 / 1.  order_dev_or_null: n_rows int32, the removed rows in removal order, then -1.                    */
+/* One workgroup runs the steps (an argmax, one row read and one subtraction a row): no floating-point atomics, no grid or host      */
+/* synchronisation, at most n_rows steps.  2 <= n_rows <= 16,384 (below: BYZ_E_INVALID; beyond: BYZ_E_UNSUPPORTED, decided on the      */
+/* argument alone); 0 <= remove_count <= n_rows - 1 and power in {1, 2} (BYZ_E_INVALID otherwise).  Nothing is written when a call   */
+/* is refused.  Asynchronous on `stream`.  Timers: BYZ_K_ROW_SORT: the initial sums; BYZ_K_MISC: the loop.                           */
+int byz_faba_select_dev(byz_ctx* ctx, const float* dist_dev, int64_t n_rows, int64_t remove_count, int power, int32_t* kept_dev,
+                        int32_t* order_dev_or_null, void* stream);
+/* The whole rule: byz_pairwise_distances_dev (dist_dev_or_null == NULL; otherwise that n x n matrix REPLACES the stage), the         */
+/* selection above with power 2, and byz_scaled_rows_sum_dev with the 0 / 1 flags as fp64 weights and the kept count, an fp64 read   */
+/* on the device, as the divisor: its bits.  Nobody kept: the zero vector, never NaN.  It waits as byz_pairwise_distances_dev does,  */
+/* and not at all when dist_dev_or_null is given.  out_dev (n_cols floats) must not overlap G (BYZ_E_INVALID).                       */
+int byz_faba_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t remove_count,
+                 const float* dist_dev_or_null, float* out_dev, int32_t* kept_dev_or_null, int32_t* order_dev_or_null, void* stream);
+/* The last byz_faba_select_dev or byz_faba_dev on this context: the rows removed, the rows kept, the rows removed beyond             */
+/* remove_count because a bad count forced it, s of the last removed row (0: nobody was removed) and the divisor of the sum.          */
+/* Synchronises that call's stream.  BYZ_E_INVALID before the first such call.                                                       */
+int byz_faba_info(byz_ctx* ctx, int64_t* removed_rows, int64_t* kept_rows, int64_t* forced_rows, double* last_score, double* divisor);
+/* The same on a host matrix (dist_host_or_null: n_rows x n_rows floats; out_host: n_cols floats; kept_host_or_null and               */
+/* order_host_or_null: n_rows int32).  Synchronous.                                                                                  */
+int byz_faba_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t remove_count,
+                  const float* dist_host_or_null, float* out_host, int32_t* kept_host_or_null, int32_t* order_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
