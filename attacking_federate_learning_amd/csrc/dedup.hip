@@ -13,6 +13,7 @@
 // With configs[4]'s duplicates: the verification reads the 2,400 duplicate rows once (+1.5% of the matrix) and the
 // Gram shrinks from 79^2/2 to 60^2/2 tiles (-42%).
 #include "common.hpp"
+#include "lane_exchange.hpp"
 
 namespace byz {
 namespace {
@@ -43,8 +44,7 @@ __global__ __launch_bounds__(256) void row_signature_kernel(const float* __restr
         if (col < n_cols && (s == 0 || span > 0))
             h += mix64((static_cast<uint64_t>(bits[col]) << 24) ^ static_cast<uint64_t>(col) * 0x9e3779b97f4a7c15ull);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
+    h = lanes::wave_sum_shfl(h);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = h;
     __syncthreads();
     if (threadIdx.x == 0) signature[row] = (part[0] + part[1]) + (part[2] + part[3]);

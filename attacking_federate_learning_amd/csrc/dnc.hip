@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void dnc_rowdot_kernel(const double* __re
     double acc = 0.0;
 #pragma unroll 4
     for (int64_t j = lane; j < b; j += 64) acc = acc + row[j] * w[j];
-    const double s = wave_sum(acc);
+    const double s = wave_sum_shfl(acc);
     if (lane == 0) y[i] = s;
 }
 

@@ -111,10 +111,10 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
     }
 #pragma unroll
     for (int r = 0; r < kRowsPerWave; ++r) {
-        const double s = wave_sum(acc[r]);
+        const double s = wave_sum_shfl(acc[r]);
         if (lane == 0 && row0 + r < n_rows) partials[static_cast<int64_t>(blockIdx.y) * n_rows + row0 + r] = s;
         if constexpr (DOTS) {
-            const double s_q = wave_sum(acc_q[r]);
+            const double s_q = wave_sum_shfl(acc_q[r]);
             if (lane == 0 && row0 + r < n_rows)
                 partials[(static_cast<int64_t>(gridDim.y) + blockIdx.y) * n_rows + row0 + r] = s_q;
         }

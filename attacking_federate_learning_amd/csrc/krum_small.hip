@@ -639,35 +639,24 @@ __global__ __launch_bounds__(256) void small_pick_kernel(const float* __restrict
     __shared__ int chosen;
     const int tid = threadIdx.x;
     if (tid < 64) {
-        float best = kKrumInit;
-        int pos = 0x7fffffff, row = -1;
+        // (a lane that admitted nothing keeps kKrumInit at position INT_MAX: it is better than nobody, and every admitted score,
+        // being below kKrumInit, is better than it)
+        lanes::Scored<float> mine{kKrumInit, 0x7fffffff, -1};
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int u = tid + 64 * r;
             if (u < n) {
                 const float s = scores[u];
-                const int vp = visit_position(u);
-                if (s < kKrumInit && (s < best || (s == best && vp < pos))) {   // false for NaN, as in the reference
-                    best = s;
-                    pos = vp;
-                    row = u;
+                if (s < kKrumInit) {   // false for NaN, as in the reference
+                    const lanes::Scored<float> o{s, visit_position(u), u};
+                    if (better(o, mine)) mine = o;
                 }
             }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const float ob = __shfl_xor(best, m, 64);
-            const int op = __shfl_xor(pos, m, 64);
-            const int orow = __shfl_xor(row, m, 64);
-            if (op != 0x7fffffff && (pos == 0x7fffffff || ob < best || (ob == best && op < pos))) {
-                best = ob;
-                pos = op;
-                row = orow;
-            }
-        }
+        mine = lanes::wave_best_shfl(mine);
         if (tid == 0) {
             // a single row has an empty distance dict in the reference: nothing is visited, the index stays -1
-            chosen = n < 2 ? -1 : row;
+            chosen = n < 2 ? -1 : mine.row;
             if (blockIdx.x == 0) *winner = chosen;
         }
     }

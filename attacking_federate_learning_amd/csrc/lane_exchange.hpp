@@ -1,4 +1,5 @@
-// Cross-lane exchange primitives and the in-register bitonic network shared by the median-window kernels.
+// Cross-lane exchange primitives, the in-register bitonic network shared by the median-window kernels, the wave-wide
+// reductions (sum, min, max) and the Krum / Bulyan ordering with its wave and block argmin.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -144,6 +145,148 @@ __device__ __forceinline__ void wave_bitonic_merge(float (&x)[C][R], int lane) {
         }
     });
 }
+
+// ---- wave-wide reductions -----------------------------------------------------------------------
+// Two exchange kinds, one reduction each, generic over the value (int, uint32_t, float, double, long long: 64-bit values
+// travel as two 32-bit halves) and the operator:
+//   _dpp   four DPP steps inside every 16-lane row (xor 1, xor 2, half mirror, mirror: each an involution, so every lane ends
+//          up with its row's result), then the four rows' results through v_readlane, combined (r0 . r1) . (r2 . r3).  No LDS
+//          pipe: a DPP move costs ~8 cycles of dependent latency where a ds_bpermute shuffle costs ~100.  Wave-uniform result.
+//   _shfl  the __shfl_xor butterfly, masks 32, 16, ..., 1.  Every lane gets the result.
+// Both orders are fixed; kernels whose outputs are compared bit for bit depend on them.
+template <int CTRL, typename T>
+__device__ __forceinline__ T dpp(T v) {
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+    } else {
+        const long long b = __builtin_bit_cast(long long, v);
+        const int lo = dpp<CTRL>(static_cast<int>(b)), hi = dpp<CTRL>(static_cast<int>(b >> 32));
+        return __builtin_bit_cast(T, (static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
+    }
+}
+template <typename T>
+__device__ __forceinline__ T readlane(T v, int l) {   // l is wave-uniform
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+    } else {
+        const long long b = __builtin_bit_cast(long long, v);
+        const int lo = readlane(static_cast<int>(b), l), hi = readlane(static_cast<int>(b >> 32), l);
+        return __builtin_bit_cast(T, (static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
+    }
+}
+
+struct Sum {
+    template <typename T>
+    __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+    __device__ __forceinline__ float operator()(float a, float b) const { return __fadd_rn(a, b); }   // never contracted
+};
+struct Min {   // NaN-free inputs
+    template <typename T>
+    __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
+    __device__ __forceinline__ float operator()(float a, float b) const { return __builtin_fminf(a, b); }
+    __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); }
+};
+struct Max {   // NaN-free inputs
+    template <typename T>
+    __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; }
+    __device__ __forceinline__ float operator()(float a, float b) const { return __builtin_fmaxf(a, b); }
+};
+
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce_dpp(T v, Op op) {
+    v = op(v, dpp<0xB1>(v));    // quad_perm [1,0,3,2]
+    v = op(v, dpp<0x4E>(v));    // quad_perm [2,3,0,1]
+    v = op(v, dpp<0x141>(v));   // row_half_mirror
+    v = op(v, dpp<0x140>(v));   // row_mirror
+    return op(op(readlane(v, 0), readlane(v, 16)), op(readlane(v, 32), readlane(v, 48)));
+}
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce_shfl(T v, Op op) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v = op(v, __shfl_xor(v, m, 64));
+    return v;
+}
+template <typename T> __device__ __forceinline__ T wave_sum_dpp(T v) { return wave_reduce_dpp(v, Sum{}); }
+template <typename T> __device__ __forceinline__ T wave_min_dpp(T v) { return wave_reduce_dpp(v, Min{}); }
+template <typename T> __device__ __forceinline__ T wave_max_dpp(T v) { return wave_reduce_dpp(v, Max{}); }
+template <typename T> __device__ __forceinline__ T wave_sum_shfl(T v) { return wave_reduce_shfl(v, Sum{}); }
+template <typename T> __device__ __forceinline__ T wave_min_shfl(T v) { return wave_reduce_shfl(v, Min{}); }
+template <typename T> __device__ __forceinline__ T wave_max_shfl(T v) { return wave_reduce_shfl(v, Max{}); }
+
+// ---- the Krum / Bulyan ordering and its argmin --------------------------------------------------
+// A candidate is a score, its position in the reference's visit order (INT_MAX = none) and its row.
+template <typename S>
+struct Scored {
+    S score;
+    int pos;
+    int row;
+};
+struct Candidate {
+    double score;
+    int pos;
+    int row;
+    int cls;   // the row's twin class where the caller needs it (the Bulyan loop), else 0: travels with the winner
+};
+
+// strict '<' on the score; an equal score keeps the earlier visitor
+template <typename C>
+__device__ __forceinline__ bool better(const C& a, const C& b) {
+    return a.score < b.score || (a.score == b.score && a.pos < b.pos);
+}
+
+// the candidate whose every field went through the exchange x
+template <typename S, typename X>
+__device__ __forceinline__ Scored<S> each_field(const Scored<S>& c, X x) { return {x(c.score), x(c.pos), x(c.row)}; }
+template <typename X>
+__device__ __forceinline__ Candidate each_field(const Candidate& c, X x) { return {x(c.score), x(c.pos), x(c.row), x(c.cls)}; }
+
+template <typename C>
+__device__ __forceinline__ C wave_best_dpp(C c) {   // wave-uniform result
+    const auto step = [&c](auto x) {
+        const C o = each_field(c, x);
+        if (better(o, c)) c = o;
+    };
+    step([](auto v) { return dpp<0xB1>(v); });
+    step([](auto v) { return dpp<0x4E>(v); });
+    step([](auto v) { return dpp<0x141>(v); });
+    step([](auto v) { return dpp<0x140>(v); });
+    C best = each_field(c, [](auto v) { return readlane(v, 0); });
+#pragma unroll
+    for (int l = 16; l < 64; l += 16) {
+        const C o = each_field(c, [l](auto v) { return readlane(v, l); });
+        if (better(o, best)) best = o;
+    }
+    return best;
+}
+template <typename C>
+__device__ __forceinline__ C wave_best_shfl(C c) {   // every lane gets the result
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const C o = each_field(c, [m](auto v) { return __shfl_xor(v, m, 64); });
+        if (better(o, c)) c = o;
+    }
+    return c;
+}
+
+// Block-wide best of the waves' bests, broadcast to every thread.  `slots` holds one candidate per wave: WAVES of them where
+// the kernel fixes its workgroup size, blockDim.x / 64 otherwise.
+template <int WAVES = 0, typename C>
+__device__ __forceinline__ C block_best_of_waves(C c, C* slots) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = WAVES > 0 ? WAVES : blockDim.x >> 6;
+    __syncthreads();  // slots may still be read from the previous call
+    if (lane == 0) slots[wave] = c;
+    __syncthreads();
+    C best = slots[0];
+    for (int w = 1; w < n_waves; ++w) {
+        const C o = slots[w];
+        if (better(o, best)) best = o;
+    }
+    return best;
+}
+template <int WAVES = 0, typename C>
+__device__ __forceinline__ C block_best_dpp(C c, C* slots) { return block_best_of_waves<WAVES>(wave_best_dpp(c), slots); }
+template <int WAVES = 0, typename C>
+__device__ __forceinline__ C block_best_shfl(C c, C* slots) { return block_best_of_waves<WAVES>(wave_best_shfl(c), slots); }
 
 }  // namespace lanes
 }  // namespace byz

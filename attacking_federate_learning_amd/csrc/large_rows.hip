@@ -19,6 +19,7 @@
 //                               outside the band cannot win or tie, so the selection is the reference's, pick for pick.  Rows
 //                               with a negative or non-finite entry (an arbitrary caller-supplied matrix) always contend.
 #include "common.hpp"
+#include "lane_exchange.hpp"
 #include "order_keys.hpp"
 
 #include <hip/hip_cooperative_groups.h>
@@ -284,20 +285,9 @@ __global__ __launch_bounds__(256) void transpose32_kernel(const uint32_t* __rest
 //                         its winner is not the guess, the batch is cut there: the sums go back to what they were when the batch
 //                         began, the picks that stood and the true winner are replayed, and the next batch starts behind it.
 // The same selection pick for pick whatever the batch length (BYZ_LARGE_BATCH, 1 .. 32).
-struct Pick {
-    float score;
-    int pos;
-    int row;
-};
-__device__ __forceinline__ bool better(const Pick& a, const Pick& b) {
-    return a.score < b.score || (a.score == b.score && a.pos < b.pos);   // strict '<'; an equal score keeps the earlier visitor
-}
-struct Guess {
-    double score;
-    int pos;
-    int row;
-};
-__device__ __forceinline__ bool better(const Guess& a, const Guess& b) { return a.score < b.score || (a.score == b.score && a.pos < b.pos); }
+// (the ordering, better(), and the wave and block argmin over __shfl_xor: lane_exchange.hpp)
+using Pick = lanes::Scored<float>;      // the reference's fp32 score
+using Guess = lanes::Scored<double>;    // the running fp64 sums' score
 
 // how many live values pick t adds per row: users_count - len(selection_set) - corrupted_count of the n - t - 1 that are left
 // (defences.py:26, 34, 61)
@@ -359,11 +349,7 @@ __global__ __launch_bounds__(1024) void large_decide_kernel(int n, int theta, in
     if (t0 == 0) {
         double big = 0.0;
         for (int u = tid; u < n; u += 1024) big = st.irregular[u] ? big : (st.total[u] > big ? st.total[u] : big);
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const double o = __shfl_xor(big, m, 64);
-            big = o > big ? o : big;
-        }
+        big = lanes::wave_max_shfl(big);
         if (lane == 0) best[wave].score = big;
         __syncthreads();
         if (tid == 0) {
@@ -434,17 +420,7 @@ __global__ __launch_bounds__(1024) void large_decide_kernel(int n, int theta, in
                 if (better(o, mine)) mine = o;
             }
         }
-#pragma unroll
-        for (int x = 32; x > 0; x >>= 1) {
-            const Guess o{__shfl_xor(mine.score, x, 64), __shfl_xor(mine.pos, x, 64), __shfl_xor(mine.row, x, 64)};
-            if (better(o, mine)) mine = o;
-        }
-        __syncthreads();      // (best[] may still be read from the pick before)
-        if (lane == 0) best[wave] = mine;
-        __syncthreads();
-        mine = best[0];
-        for (int w = 1; w < 16; ++w)
-            if (better(best[w], mine)) mine = best[w];
+        mine = lanes::block_best_shfl<16>(mine, best);
         const double low = mine.score;
         // fl(sum) of m non-negative terms added one by one lies in [s (1 - u)^(m-1), s (1 + u)^(m-1)], u = 2^-24: a row can reach
         // the smallest sum only from below s_min ((1 + u) / (1 - u))^(m-1) <= s_min (1 + 2.1 m u) for m u <= 2^-6 (scripts/proto/
@@ -521,11 +497,7 @@ __global__ __launch_bounds__(1024) void large_scale_kernel(int n, LargeState st)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double big = 0.0;
     for (int u = tid; u < n; u += 1024) big = st.irregular[u] ? big : (st.total[u] > big ? st.total[u] : big);
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const double o = __shfl_xor(big, m, 64);
-        big = o > big ? o : big;
-    }
+    big = lanes::wave_max_shfl(big);
     if (lane == 0) part[wave] = big;
     __syncthreads();
     if (tid == 0) {
@@ -603,11 +575,7 @@ __global__ __launch_bounds__(kGridBlock) void large_decide_grid_kernel(int n, in
             st.exact[u] = o.score;
             if (better(o, mine)) mine = o;
         }
-#pragma unroll
-        for (int x = 32; x > 0; x >>= 1) {
-            const Guess o{__shfl_xor(mine.score, x, 64), __shfl_xor(mine.pos, x, 64), __shfl_xor(mine.row, x, 64)};
-            if (better(o, mine)) mine = o;
-        }
+        mine = lanes::wave_best_shfl(mine);
         if (lane == 0) best[wave] = mine;
         if (tid == 0) lds_count = 0;
         __syncthreads();
@@ -623,11 +591,7 @@ __global__ __launch_bounds__(kGridBlock) void large_decide_grid_kernel(int n, in
             const Guess o = wg_best[b];
             if (better(o, mine)) mine = o;
         }
-#pragma unroll
-        for (int x = 32; x > 0; x >>= 1) {
-            const Guess o{__shfl_xor(mine.score, x, 64), __shfl_xor(mine.pos, x, 64), __shfl_xor(mine.row, x, 64)};
-            if (better(o, mine)) mine = o;
-        }
+        mine = lanes::wave_best_shfl(mine);
         const double low = mine.score;
         double bound = low * (1.0 + 2.1 * static_cast<double>(m) * 5.9604644775390625e-08 + 1e-9) + slack;      // (large_decide_kernel)
         if (!(low < 9e19) || m > (1 << 18)) bound = __builtin_inf();
@@ -742,7 +706,7 @@ __global__ __launch_bounds__(1024) void large_settle_kernel(int n, int theta, in
                                                             const float* __restrict__ dist_t, LargeState st,
                                                             int32_t* __restrict__ selection, int32_t* __restrict__ status) {
     __shared__ Pick picks_sh[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int picks = st.words[1];
     if (*status != 0 || picks == 0) return;
     const int t0 = st.words[0];
@@ -757,17 +721,7 @@ __global__ __launch_bounds__(1024) void large_settle_kernel(int n, int theta, in
                 if (better(o, mine)) mine = o;
             }
         }
-#pragma unroll
-        for (int x = 32; x > 0; x >>= 1) {
-            const Pick o{__shfl_xor(mine.score, x, 64), __shfl_xor(mine.pos, x, 64), __shfl_xor(mine.row, x, 64)};
-            if (better(o, mine)) mine = o;
-        }
-        __syncthreads();
-        if (lane == 0) picks_sh[wave] = mine;
-        __syncthreads();
-        mine = picks_sh[0];
-        for (int w = 1; w < 16; ++w)
-            if (better(picks_sh[w], mine)) mine = picks_sh[w];
+        mine = lanes::block_best_shfl<16>(mine, picks_sh);
         const int winner = mine.row;
         if (winner == st.guess[k] && winner >= 0) {
             if (tid == 0) selection[t0 + k] = winner;

@@ -74,32 +74,6 @@ __device__ __forceinline__ float uniform(float v) {
 }
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, m, 64));
-    return uniform(v);
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = __builtin_fminf(v, __shfl_xor(v, m, 64));
-    return uniform(v);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return uniform(v);
-}
-// integer wave sum: four DPP butterfly steps inside each 16-lane row, then four v_readlane
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    int x = static_cast<int>(v);
-    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true);   // row_mirror
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) +
-                                 __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48));
-}
-
 // ascending sort inside every 16-lane segment (10 compare-exchange stages; lane masks <= 15)
 __device__ __forceinline__ float segment16_sort(float v, int lane) {
     const float pinf = __builtin_inff();
@@ -225,8 +199,8 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
             }
         }
         // per-lane counts are at most 40: two columns share one register through the reduction
-        const uint32_t s01 = wave_sum_u32(neg[0] | (neg[1] << 16));
-        const uint32_t s23 = wave_sum_u32(neg[2] | (neg[3] << 16));
+        const uint32_t s01 = wave_sum_dpp(neg[0] | (neg[1] << 16));
+        const uint32_t s23 = wave_sum_dpp(neg[2] | (neg[3] << 16));
         // ---- absorb the counts
         {
             const uint32_t packed = (lane & 2) ? s23 : s01;
@@ -263,7 +237,7 @@ __device__ __forceinline__ void select4(const float (&x)[NC][RPL], int groups, i
                     }
                 }
             }
-            const float wa = wave_max(below), wb = wave_min(above);
+            const float wa = uniform(wave_max_shfl(below)), wb = uniform(wave_min_shfl(above));
             if (col == c) {
                 res_a = wa;
                 res_b = wb;
@@ -556,7 +530,7 @@ __device__ __forceinline__ float tied_window_sum(const float (&v)[RPL], int grou
             }
         }
     }
-    float sum = wave_sum(acc);
+    float sum = uniform(wave_sum_shfl(acc));
     const int need = keep - n_closer;
     if (t == 0.0f) {
         // ties are zeros of either sign: they add nothing
@@ -624,8 +598,8 @@ __device__ __forceinline__ void finish_tile(float (&x)[NC][RPL], const float (&m
     float med[NC], lo_x[NC], hi_x[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        lo_x[c] = wave_min(mn[c]);
-        hi_x[c] = wave_max(mx[c]);
+        lo_x[c] = uniform(wave_min_shfl(mn[c]));
+        hi_x[c] = uniform(wave_max_shfl(mx[c]));
         q[c].hi = hi_x[c];
         q[c].c_hi = n_rows;
         q[c].c_lo = 0;
@@ -754,7 +728,7 @@ __device__ __forceinline__ void finish_tile(float (&x)[NC][RPL], const float (&m
                 }
             }
         }
-        float sum = wave_sum(acc);
+        float sum = uniform(wave_sum_shfl(acc));
         if (!dead[c] && n_in != keep) sum = tied_window_sum<RPL>(x[c], chunks, keep, t);
         // defences.py:51: np.mean(good) + med
         result[c] = dead[c] ? qnan : __fadd_rn(__fdiv_rn(sum, static_cast<float>(keep)), med[c]);
@@ -924,20 +898,83 @@ int launch_ring(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, in
 }
 
 // every lane_xor pattern over the lane ids (tests/test_gpu_parity.py checks the exchange against lane ^ mask)
-__global__ void lane_selftest_kernel(int32_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
+// Two waves; both compute every row, wave 0 writes it (only the block stage's rows differ between them).
+constexpr int kSelftestThreads = 128;
+__global__ __launch_bounds__(kSelftestThreads) void lane_selftest_kernel(int32_t* __restrict__ out) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool writer = tid < 64;
     const int masks[11] = {1, 2, 3, 4, 7, 8, 15, 16, 31, 32, 63};
     const float me = static_cast<float>(lane);
 #pragma unroll
-    for (int p = 0; p < 11; ++p) out[p * 64 + lane] = static_cast<int32_t>(lane_xor(me, masks[p], lane));
+    for (int p = 0; p < 11; ++p) {
+        const int32_t from = static_cast<int32_t>(lane_xor(me, masks[p], lane));
+        if (writer) out[p * 64 + lane] = from;
+    }
+
+    // Rows 11 ..: what every lane holds after one shared reduction (a 64-bit result takes two rows: low word, high word).
+    int row = 11;
+    const auto put = [&](auto v) {
+        if constexpr (sizeof(v) == 4) {
+            if (writer) out[row * 64 + lane] = __builtin_bit_cast(int32_t, v);
+            row += 1;
+        } else {
+            const long long b = __builtin_bit_cast(long long, v);
+            if (writer) out[row * 64 + lane] = static_cast<int32_t>(b);
+            if (writer) out[(row + 1) * 64 + lane] = static_cast<int32_t>(b >> 32);
+            row += 2;
+        }
+    };
+    const int x = (37 * lane + 11) % 64 - 20;     // a permutation of -20 .. 43
+    put(wave_sum_dpp(x));
+    put(wave_min_dpp(x));
+    put(wave_max_dpp(x));
+    put(wave_sum_shfl(x));
+    put(wave_min_shfl(x));
+    put(wave_max_shfl(x));
+    put(wave_min_dpp(static_cast<float>(x)));
+    put(wave_min_shfl(static_cast<float>(x)));
+    put(wave_min_dpp(static_cast<double>(x)));
+    put(wave_min_shfl(static_cast<double>(x)));
+    put(wave_sum_dpp(static_cast<long long>(x)));
+    put(wave_sum_shfl(static_cast<long long>(x)));
+    const double third = 1.0 + static_cast<double>(lane) / 3.0;     // the additions round
+    put(wave_sum_dpp(static_cast<float>(third)));
+    put(wave_sum_shfl(third));
+    put(wave_sum_dpp(static_cast<uint32_t>(lane)));
+    // the argmin: eight-way ties on the score, the earlier visitor is the HIGHER lane; then nobody admitted
+    const int score = (37 * lane + 11) % 8, pos = 63 - lane;
+    const Scored<float> pick{static_cast<float>(score), pos, lane}, no_pick{1e20f, 0x7fffffff, -1};
+    const Scored<double> guess{static_cast<double>(score), pos, lane};
+    const Candidate cand{static_cast<double>(score), pos, lane, lane % 5};
+    put(wave_best_dpp(pick).row);
+    put(wave_best_shfl(pick).row);
+    put(wave_best_dpp(guess).row);
+    put(wave_best_shfl(guess).row);
+    put(wave_best_dpp(no_pick).row);
+    put(wave_best_shfl(no_pick).row);
+    put(wave_best_dpp(cand).row);
+    put(wave_best_dpp(cand).cls);
+    put(wave_best_shfl(cand).row);
+    put(wave_best_shfl(cand).cls);
+    // the block stage over both waves: the same scores, and the second wave holds the earlier visitors, so the winner is
+    // decided by the tie-break between the waves' slots
+    __shared__ Candidate cand_slot[kSelftestThreads / 64];
+    __shared__ Scored<float> pick_slot[kSelftestThreads / 64];
+    const int block_pos = kSelftestThreads - 1 - tid;
+    const Candidate block_cand = block_best_dpp(Candidate{static_cast<double>(score), block_pos, tid, tid % 5}, cand_slot);
+    put(block_cand.row);
+    put(block_cand.cls);
+    put(block_best_shfl<kSelftestThreads / 64>(Scored<float>{static_cast<float>(score), block_pos, tid}, pick_slot).row);
 }
+constexpr int kSelftestRows = 11 + 6 + 2 + 4 + 4 + 1 + 2 + 1 + 10 + 3;
+static_assert(kSelftestRows <= 64, "byzagg.h promises the caller at most 64 rows");
 
 }  // namespace
 
 int launch_lane_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_patterns, hipStream_t stream) {
     KernelTimer t(ctx, BYZ_K_MISC, stream);
-    lane_selftest_kernel<<<1, 64, 0, stream>>>(out);
-    *n_patterns = 11;
+    lane_selftest_kernel<<<1, kSelftestThreads, 0, stream>>>(out);
+    *n_patterns = kSelftestRows;
     return check_launch("lane_selftest_kernel");
 }
 

@@ -23,6 +23,7 @@
 // block's global loads are issued before the current block's MFMAs.  Workgroups are numbered so that the row tiles of one
 // column panel run next to each other on ONE XCD: the panel is read from HBM once and then served by that XCD's L2.
 #include "common.hpp"
+#include "lane_exchange.hpp"
 #include "order_keys.hpp"
 
 namespace byz {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(64) void nnm_mask_kernel(const int32_t* __restrict_
         }
         if (counts == nullptr && negative != 0ull) open = false;
     }
-    for (int x = 32; x >= 1; x >>= 1) mine += __shfl_xor(mine, x, 64);
+    mine = lanes::wave_sum_shfl(mine);
     if (lane == 0) row_count[i] = mine;
 }
 

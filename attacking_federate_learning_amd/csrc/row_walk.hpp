@@ -8,6 +8,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "lane_exchange.hpp"
 
 namespace byz {
 
@@ -100,12 +101,8 @@ __device__ __forceinline__ bool gated_out(const int32_t* skip_if_set, const int3
     return false;
 }
 
-// fixed butterfly over a wave: every lane gets the total
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+// the column kernels' wave sum is lane_exchange.hpp's fixed butterfly (every lane gets the total), under its own name
+using lanes::wave_sum_shfl;
 
 // fixed-order tree over one workgroup of THREADS threads (lds: THREADS values); every thread gets the total
 template <typename T, int THREADS>

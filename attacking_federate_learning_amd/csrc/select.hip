@@ -24,6 +24,7 @@
 // sum, the contenders are re-scored in exactly that arithmetic (reference_score), so that given the same distance
 // matrix the selection is the reference's, pick for pick -- not a more accurate one.
 #include "common.hpp"
+#include "lane_exchange.hpp"
 #include "order_keys.hpp"
 
 #include <cstdlib>
@@ -31,6 +32,8 @@
 
 namespace byz {
 namespace {
+
+using namespace lanes;
 
 constexpr int kMaxSelectRows = 16384;  // 128 KiB of 64-bit keys in LDS
 constexpr float kKrumInit = 1e20f;     // defences.py:27
@@ -377,96 +380,8 @@ __global__ __launch_bounds__(256) void rank_transpose_kernel(const uint16_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------
-struct Candidate {
-    double score;
-    int pos;   // position in the reference's visit order; INT_MAX = none
-    int row;
-    int cls;   // the row's twin class where the caller needs it (the Bulyan loop), else 0: travels with the winner
-};
-
-__device__ __forceinline__ bool better(const Candidate& a, const Candidate& b) {
-    // strict '<' on the score; an equal score keeps the earlier visitor
-    return a.score < b.score || (a.score == b.score && a.pos < b.pos);
-}
-
-// Wave-wide reductions without the LDS pipe: four DPP steps inside every 16-lane row (xor 1, xor 2, half mirror, mirror: each
-// an involution, so every lane ends up with its row's result), then the four rows' results through v_readlane.  A
-// ds_bpermute shuffle costs ~100 cycles of dependent latency and the loop makes ~30 of them per pick; a DPP move ~8.
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = dpp_i<CTRL>(static_cast<int>(b)), hi = dpp_i<CTRL>(static_cast<int>(b >> 32));
-    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
-}
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane(static_cast<int>(b), l), hi = __builtin_amdgcn_readlane(static_cast<int>(b >> 32), l);
-    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
-}
-
-__device__ __forceinline__ Candidate wave_best(Candidate c) {   // wave-uniform result
-#define BYZ_STEP(CTRL)                                                                              \
-    {                                                                                               \
-        Candidate o;                                                                                \
-        o.score = dpp_d<CTRL>(c.score);                                                             \
-        o.pos = dpp_i<CTRL>(c.pos);                                                                 \
-        o.row = dpp_i<CTRL>(c.row);                                                                 \
-        o.cls = dpp_i<CTRL>(c.cls);                                                                 \
-        if (better(o, c)) c = o;                                                                    \
-    }
-    BYZ_STEP(0xB1) BYZ_STEP(0x4E) BYZ_STEP(0x141) BYZ_STEP(0x140)
-#undef BYZ_STEP
-    Candidate best{readlane_d(c.score, 0), __builtin_amdgcn_readlane(c.pos, 0), __builtin_amdgcn_readlane(c.row, 0),
-                   __builtin_amdgcn_readlane(c.cls, 0)};
-#pragma unroll
-    for (int l = 16; l < 64; l += 16) {
-        const Candidate o{readlane_d(c.score, l), __builtin_amdgcn_readlane(c.pos, l), __builtin_amdgcn_readlane(c.row, l),
-                          __builtin_amdgcn_readlane(c.cls, l)};
-        if (better(o, best)) best = o;
-    }
-    return best;
-}
-__device__ __forceinline__ double wave_min_d(double v) {   // wave-uniform; NaN-free inputs
-    v = fmin(v, dpp_d<0xB1>(v));
-    v = fmin(v, dpp_d<0x4E>(v));
-    v = fmin(v, dpp_d<0x141>(v));
-    v = fmin(v, dpp_d<0x140>(v));
-    return fmin(fmin(readlane_d(v, 0), readlane_d(v, 16)), fmin(readlane_d(v, 32), readlane_d(v, 48)));
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-    v = __builtin_fminf(v, __int_as_float(dpp_i<0xB1>(__float_as_int(v))));
-    v = __builtin_fminf(v, __int_as_float(dpp_i<0x4E>(__float_as_int(v))));
-    v = __builtin_fminf(v, __int_as_float(dpp_i<0x141>(__float_as_int(v))));
-    v = __builtin_fminf(v, __int_as_float(dpp_i<0x140>(__float_as_int(v))));
-    const int b = __float_as_int(v);
-    return __builtin_fminf(__builtin_fminf(__int_as_float(__builtin_amdgcn_readlane(b, 0)), __int_as_float(__builtin_amdgcn_readlane(b, 16))),
-                           __builtin_fminf(__int_as_float(__builtin_amdgcn_readlane(b, 32)), __int_as_float(__builtin_amdgcn_readlane(b, 48))));
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-    v = min(v, dpp_i<0xB1>(v));
-    v = min(v, dpp_i<0x4E>(v));
-    v = min(v, dpp_i<0x141>(v));
-    v = min(v, dpp_i<0x140>(v));
-    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-// Block-wide best candidate, broadcast to every thread.  `slots` holds blockDim.x/64 candidates.
-__device__ __forceinline__ Candidate block_best(Candidate c, Candidate* slots) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    c = wave_best(c);
-    __syncthreads();  // slots may still be read from the previous call
-    if (lane == 0) slots[wave] = c;
-    __syncthreads();
-    Candidate best = slots[0];
-    for (int w = 1; w < n_waves; ++w) {
-        const Candidate o = slots[w];
-        if (better(o, best)) best = o;
-    }
-    return best;
-}
+// Candidate, better(), the wave and block argmin and the wave-wide reductions: lane_exchange.hpp.  The picks below reduce over
+// row-DPP (the _dpp forms): the loop makes ~30 wave reductions per pick and a ds_bpermute shuffle costs ~100 cycles each.
 
 __global__ __launch_bounds__(1024) void krum_argmin_kernel(const float* __restrict__ scores, int n,
                                                            int32_t* __restrict__ winner) {
@@ -480,7 +395,7 @@ __global__ __launch_bounds__(1024) void krum_argmin_kernel(const float* __restri
         }
     }
     // a single row has an empty distance dict in the reference: nothing is visited, index stays -1
-    const Candidate best = block_best(c, slots);
+    const Candidate best = block_best_dpp(c, slots);
     if (threadIdx.x == 0) *winner = (n < 2) ? -1 : best.row;
 }
 
@@ -598,24 +513,6 @@ __device__ __forceinline__ bool gather_granules(const unsigned long long* slots,
     }
     mine = v;
     return true;
-}
-
-__device__ __forceinline__ int wave_max_int(int v) {   // wave-uniform result
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-__device__ __forceinline__ int wave_sum_int(int x) {   // wave-uniform result
-    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true);   // row_mirror
-    return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
-           __builtin_amdgcn_readlane(x, 48);
 }
 
 // both granules of a pick in one polling loop: one exchange latency instead of two
@@ -1145,10 +1042,10 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
         const bool candidate = alive && bad <= drop && score < static_cast<double>(kKrumInit);   // false for NaN
         Candidate c{static_cast<double>(kKrumInit), 0x7fffffff, -1, -1};
         if (candidate) c = Candidate{score, my_pos, u, my_class};
-        const Candidate best = block_best(c, slots);
+        const Candidate best = block_best_dpp(c, slots);
         const int best_class = best.cls;      // (travels with the winner: a load of cls[best.row] here cost every pick a round trip)
         double second = (candidate && my_class != best_class) ? score : __builtin_inf();
-        second = wave_min_d(second);
+        second = wave_min_dpp(second);
         if (lane == 0) second_slots[wave] = second;
         __syncthreads();
         if (wave == 0) {
@@ -1182,7 +1079,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
             const float b = __uint_as_float(static_cast<uint32_t>(gb >> 32));
             const int a_row = static_cast<int>((ga >> 18) & 0x3fffu);
             const int a_cls = static_cast<int>((ga >> 4) & 0x3fffu);
-            const float m1 = wave_min_f(a);
+            const float m1 = wave_min_dpp(a);
             GridDecision d{0, -1, 0.0};
             if (!ok) {
                 d.mode = 3;
@@ -1198,7 +1095,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
                 const int lead_cls = __builtin_amdgcn_readlane(a_cls, __builtin_ctzll(first));
                 const bool one_class = __ballot(in_b) == 0ull && __ballot(in_a && a_cls != lead_cls) == 0ull;
                 if (one_class) {
-                    const int pos = wave_min_i(in_a ? visit_position(a_row) : 0x7fffffff);
+                    const int pos = wave_min_dpp(in_a ? visit_position(a_row) : 0x7fffffff);
                     d.winner = row_of_visit(pos);
                 } else {
                     d.mode = 1;
@@ -1245,7 +1142,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
         if (d.mode == 1) {
             const int n_lead = n_leaders;
             if (wave == 0 && lane == 0) n_rescored += n_lead;
-            const Candidate local = block_best(r, slots);   // every lane of a wave holds the same r
+            const Candidate local = block_best_dpp(r, slots);   // every lane of a wave holds the same r
             if (wave == 0) {
                 unsigned long long gr = local.row >= 0
                     ? (static_cast<unsigned long long>(__float_as_uint(static_cast<float>(local.score))) << 32) |
@@ -1264,7 +1161,7 @@ __global__ __launch_bounds__(kGridThreads) void bulyan_grid_kernel(
                 Candidate g{static_cast<double>(kKrumInit), 0x7fffffff, -1};
                 if (r_row != static_cast<int>(kNoRow))
                     g = Candidate{static_cast<double>(__uint_as_float(static_cast<uint32_t>(gr >> 32))), visit_position(r_row), r_row};
-                g = wave_best(g);
+                g = wave_best_dpp(g);
                 if (lane == 0) {
                     decision.mode = !ok ? 3 : (g.row < 0 ? 2 : 0);
                     decision.winner = g.row;
@@ -1492,10 +1389,10 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
             const bool candidate = row.alive && row.bad <= drop && score < static_cast<double>(kKrumInit);   // false for NaN
             Candidate c{static_cast<double>(kKrumInit), 0x7fffffff, -1, -1};
             if (candidate) c = Candidate{score, my_pos, u, my_class};
-            const Candidate best = block_best(c, slots);
+            const Candidate best = block_best_dpp(c, slots);
             const int best_class = best.cls;
             double second = (candidate && my_class != best_class) ? score : __builtin_inf();
-            second = wave_min_d(second);
+            second = wave_min_dpp(second);
             if (lane == 0) second_slots[wave] = second;
             __syncthreads();
             if (wave == 0) {
@@ -1528,7 +1425,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                 const float b = __uint_as_float(static_cast<uint32_t>(gb >> 32));
                 const int a_row = static_cast<int>((ga >> 18) & 0x3fffu);
                 const int a_cls = static_cast<int>((ga >> 4) & 0x3fffu);
-                const float m1 = wave_min_f(a);
+                const float m1 = wave_min_dpp(a);
                 GridDecision d{0, -1, 0.0};
                 int is_contested = 0;
                 if (!ok) {
@@ -1545,7 +1442,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                     const bool one_class = __ballot(in_b) == 0ull && __ballot(in_a && a_cls != lead_cls) == 0ull;
                     // one class in the band: its earliest member, proven.  Otherwise, OPTIMISTICALLY, the smallest exact score
                     // (the earliest of the workgroups whose best rounds down to the same float): verified behind the batch
-                    const int pos = wave_min_i((one_class ? in_a : a == m1) ? visit_position(a_row) : 0x7fffffff);
+                    const int pos = wave_min_dpp((one_class ? in_a : a == m1) ? visit_position(a_row) : 0x7fffffff);
                     d.winner = row_of_visit(pos);
                     is_contested = one_class ? 0 : 1;
                 }
@@ -1683,7 +1580,7 @@ __global__ __launch_bounds__(kSpecThreads) void bulyan_spec_kernel(
                         Candidate g{static_cast<double>(kKrumInit), 0x7fffffff, -1, -1};
                         if (r_row != static_cast<int>(kNoRow))
                             g = Candidate{static_cast<double>(__uint_as_float(static_cast<uint32_t>(mine >> 32))), visit_position(r_row), r_row, 0};
-                        g = wave_best(g);
+                        g = wave_best_dpp(g);
                         if (lane == 0) true_row[k] = ok ? g.row : -2;
                     }
                 }

@@ -51,12 +51,6 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int64_t c, in
     }
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // q_part[chunk * n_rows + row]; cnt_part[(plane * chunks + chunk) * n_rows + row], plane = pos, zero, neg.
 // [win_lo, win_hi): the window's columns (empty when win_hi <= win_lo).
 template <bool VEC4>
@@ -116,8 +110,9 @@ __global__ __launch_bounds__(kThreads) void row_signs_partial_kernel(const float
     const int64_t chunks = gridDim.y;
 #pragma unroll
     for (int r = 0; r < kRowsPerWave; ++r) {
-        const double s_q = wave_sum(acc_q[r]);
-        const long long pos = wave_sum_i64(n_pos[r]), zero = wave_sum_i64(n_zero[r]), neg = wave_sum_i64(n_neg[r]);
+        const double s_q = wave_sum_shfl(acc_q[r]);
+        const long long pos = wave_sum_shfl<long long>(n_pos[r]), zero = wave_sum_shfl<long long>(n_zero[r]),
+                        neg = wave_sum_shfl<long long>(n_neg[r]);
         if (lane == 0 && row0 + r < n_rows) {
             const int64_t at = static_cast<int64_t>(blockIdx.y) * n_rows + row0 + r;
             q_part[at] = s_q;
@@ -283,8 +278,8 @@ __device__ __forceinline__ void shift_totals(double (&s)[3], int& count, double 
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     double c = static_cast<double>(count);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] = wave_sum(s[k]);
-    c = wave_sum(c);
+    for (int k = 0; k < 3; ++k) s[k] = wave_sum_shfl(s[k]);
+    c = wave_sum_shfl(c);
     __syncthreads();                                  // (the previous round's readers are done)
     if (lane == 0) {
         lds[wave][0] = s[0]; lds[wave][1] = s[1]; lds[wave][2] = s[2]; lds[wave][3] = c;

@@ -106,28 +106,6 @@ __device__ __forceinline__ uint32_t group_scan(uint32_t v) {
     return static_cast<uint32_t>(x);
 }
 
-// sum over the 64 lanes in a fixed order, no LDS trip: four DPP steps inside each 16-lane row, then the row totals in order
-__device__ __forceinline__ float wave_sum_f(float v, int lane) {
-    (void)lane;
-    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));    // quad_perm [1,0,3,2]
-    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));    // quad_perm [2,3,0,1]
-    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)));   // row_half_mirror
-    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true)));   // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return __fadd_rn(__fadd_rn(r0, r1), __fadd_rn(r2, r3));
-}
-__device__ __forceinline__ int wave_sum_i(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true);   // row_mirror
-    return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
-           __builtin_amdgcn_readlane(x, 48);
-}
-
 // Register rows are loaded (and then swept) in this order: the three sampled ones first, so that the range phase can start
 // while the rest of the tile is still on its way (memory returns loads in order).
 template <int RPW>
@@ -643,8 +621,8 @@ __global__ __launch_bounds__(64 * W, 4) void window_lean_kernel(const float* __r
                     within += und ? 1 : 0;
                     part = __fadd_rn(part, (und || (skip && i < total[k])) ? __fsub_rn(sx[k][r], pivot) : 0.0f);
                 }
-                const int n_within = wave_sum_i(within);
-                float sum = wave_sum_f(part, lane);
+                const int n_within = wave_sum_dpp(within);
+                float sum = wave_sum_dpp(part);   // (fixed order, every addition __fadd_rn: the result is compared bit for bit)
                 // ... plus the decided-in rings, summed by sweep B: the partials in a fixed order
                 for (int p = 0; p < W; ++p) sum = __fadd_rn(sum, part_sum[p * kTileCols + c]);
                 if (lane == 0) {

@@ -2605,12 +2605,15 @@ class Engine:
                 out[name] = {'total_ms': ms.value, 'launches': calls.value}
         return out
 
-    def lane_exchange_selftest(self):
-        buf = DeviceBuffer(self, (16 * 64,), np.int32)
+    def lane_exchange_selftest(self, reductions=False):
+        """The self-test kernel's rows of 64 lanes: the 11 lane_xor patterns, or with `reductions` the rows behind them
+        (every lane's result of one of lane_exchange.hpp's wave reductions each)."""
+        buf = DeviceBuffer(self, (64 * 64,), np.int32)
         n = ctypes.c_int32(0)
         _check(self.lib.byz_selftest_lane_exchange_dev(self.ctx, buf.ptr, ctypes.byref(n), None))
         self.synchronize()
-        return buf.numpy()[: n.value * 64].reshape(n.value, 64)
+        rows = buf.numpy()[: n.value * 64].reshape(n.value, 64)
+        return rows[11:] if reductions else rows[:11]
 
 
 _default = None

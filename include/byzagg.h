@@ -1312,7 +1312,9 @@ int byz_timing_read(byz_ctx* ctx, int kernel, double* total_ms, int64_t* launche
 const char* byz_kernel_name(int kernel);
 
 /* ---- self-test of the cross-lane exchange primitives (tests only) ----------------------- */
-/* out_dev: 64 * n_patterns int32; entry [p*64 + lane] = source lane observed by `lane`.     */
+/* out_dev: room for 64 rows of 64 int32; n_patterns (<= 64) rows are written.  Rows 0..10:  */
+/* entry [p*64 + lane] = source lane observed by `lane`; rows 11..: what every lane holds    */
+/* after one of lane_exchange.hpp's wave reductions (tests/test_gpu_parity.py has the list). */
 int byz_selftest_lane_exchange_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_patterns_host,
                                    void* stream);
 

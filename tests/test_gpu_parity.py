@@ -43,6 +43,66 @@ def test_lane_exchange_patterns(eng):
     for row, m in zip(got, masks):
         assert row.tolist() == [lane ^ m for lane in range(64)], 'lane_xor(%d)' % m
 
+    # the rows behind them: every lane's result of one shared wave reduction (lane_exchange.hpp), against numpy restatements
+    got = eng.lane_exchange_selftest(reductions=True)
+    assert got.shape == (33, 64)
+    rows = iter(got)
+    lanes = np.arange(64)
+
+    def word(what, want):                    # a 32-bit result: all 64 lanes hold it
+        assert next(rows).tolist() == [int(np.asarray(want).view(np.int32))] * 64, what
+
+    def dword(what, want):                   # a 64-bit result: the row of low words, then the row of high words
+        lo, hi = next(rows), next(rows)
+        have = (hi.astype(np.int64) << 32) | lo.view(np.uint32).astype(np.int64)
+        assert have.tolist() == np.broadcast_to(np.asarray(want).view(np.int64), 64).tolist(), what
+
+    x = (37 * lanes + 11) % 64 - 20
+    assert sorted(x.tolist()) == list(range(-20, 44))           # one owner each for the minimum and the maximum
+    for form in ('row-DPP', 'butterfly'):
+        word('int sum, ' + form, np.int32(x.sum()))
+        word('int min, ' + form, np.int32(-20))
+        word('int max, ' + form, np.int32(43))
+    word('float min, row-DPP', np.float32(-20))
+    word('float min, butterfly', np.float32(-20))
+    dword('double min, row-DPP', np.float64(-20))
+    dword('double min, butterfly', np.float64(-20))
+    dword('long long sum, row-DPP', np.int64(x.sum()))
+    dword('long long sum, butterfly', np.int64(x.sum()))
+
+    # float sum, row-DPP: inside a 16-lane row xor 1, xor 2, xor 7 (half mirror), xor 15 (mirror), every addition rounded to
+    # fp32; the four rows' lane 0 combined as (r0 + r1) + (r2 + r3)
+    third = 1 + lanes / 3                                        # fp64
+    v = third.astype(np.float32).reshape(4, 16)
+    for s in (1, 2, 7, 15):
+        v = v + v[:, np.arange(16) ^ s]
+    assert v.dtype == np.float32
+    r = v[:, 0]
+    word('float sum, row-DPP', (r[0] + r[1]) + (r[2] + r[3]))
+    # double sum, butterfly: masks 32, 16, ..., 1, per lane
+    v = third.copy()
+    for m in (32, 16, 8, 4, 2, 1):
+        v = v + v[lanes ^ m]
+    dword('double sum, butterfly', v)
+    word('uint32 sum, row-DPP', np.int32(lanes.sum()))
+
+    # the argmin under the Krum / Bulyan ordering: least score, then least pos; eight-way ties on the score
+    score, pos = (37 * lanes + 11) % 8, 63 - lanes
+    winner = min(range(64), key=lambda l: (score[l], pos[l]))
+    assert (score == score[winner]).sum() == 8
+    for what in ('float score, row-DPP', 'float score, butterfly', 'double score, row-DPP', 'double score, butterfly'):
+        word('argmin, ' + what, np.int32(winner))
+    word('argmin, nobody admitted, row-DPP', np.int32(-1))
+    word('argmin, nobody admitted, butterfly', np.int32(-1))
+    for form in ('row-DPP', 'butterfly'):
+        word('argmin with cls, row, ' + form, np.int32(winner))
+        word('argmin with cls, cls, ' + form, np.int32(winner % 5))
+    # the block stage over two waves, rows 0 .. 127: the same scores, pos = 127 - row, so the second wave holds the winner
+    word('block argmin with cls, row, row-DPP', np.int32(64 + winner))
+    word('block argmin with cls, cls, row-DPP', np.int32((64 + winner) % 5))
+    word('block argmin, butterfly', np.int32(64 + winner))
+    assert next(rows, None) is None
+
 
 # ---- golden vectors minted from the reference -------------------------------------------------------
 def test_golden_no_defense(defences, golden):
