@@ -7,7 +7,7 @@
 //   radius = a[order[keep - 1]]
 //   out    = fl32(sum of col[kept] in fp64 / keep)
 //
-// ONE order statistic of the keys bits(a) -- a >= 0, so its bits order as unsigned integers as they are -- found by rank_select.hip's
+// ONE order statistic of the keys bits(a) -- a >= 0, so its bits order as unsigned integers as they are -- found by column_select.hpp's
 // radix select, 8 bits per pass, with one 32-bit counter per (digit, column): a single rank needs no second half of the word, so
 // the same histogram serves every height up to 2^20.  |d| does not invert to x: the resident tile holds the VALUES and forms the
 // key again in every pass (a subtract, a mask, a min).  With T the key of rank keep - 1, `run` the keys equal to T and
@@ -21,10 +21,13 @@
 // +inf's or the NaNs').  Nothing but the column's own rows, its centre and the height-picked geometry enters a result: the same
 // bits for every ld, base alignment, grid and column split.
 //
-// Two shapes of one kernel template, rank_select.hip's (the dispatcher picks by height alone):
+// Two shapes of one kernel template, picked by height alone from column_select.hpp's table:
 //   streamed   RPT == 0: 64 columns per workgroup, sixteen waves split the rows, eight loads in flight per thread; the four select
 //              passes and the sums: FIVE passes over HBM;
 //   resident   RPT  > 0: the workgroup's COLS x n tile is loaded ONCE into registers (thread (tx, ty) holds rows ty, ty + RG, ...).
+// The header also has the walk to the rank's digit, the tile and its grid, the row loader, the streamed loop, the fixed-order total
+// and the launch.  This file's own: the tile held as values, `fresh`, where the scheduling barriers stand, and the ties.
+#include "column_select.hpp"
 #include "common.hpp"
 #include "order_keys.hpp"
 
@@ -34,13 +37,12 @@ namespace {
 constexpr uint32_t kInfKey = 0x7f800000u;      // bits(+inf): the largest key of a number
 constexpr uint32_t kNanKey = 0x7f800001u;      // every NaN difference: one key above +inf's
 constexpr uint32_t kPadKey = 0x7f800002u;      // the streamed sums' rows beyond the height: above every threshold
-constexpr int kStreamUnroll = 8;
 constexpr int kResidentBatch = 4;
 // keys formed at a time: the scheduler does not gather more of a tile's keys first (89 VGPRs at 64 rows a thread; 109 without the
 // barriers, no spill either way)
 constexpr int kResidentGroup = 4;
 constexpr int kWalkUnroll = 8;
-constexpr int kSegments = 16;                  // the walk to the rank's digit: sixteen 16-digit segment sums, then 16 + 16 steps
+using colsel::kSegments;
 
 __device__ __forceinline__ uint32_t window_key(float x, float c) {
     const uint32_t a = __float_as_uint(__fsub_rn(x, c)) & 0x7fffffffu;
@@ -68,27 +70,12 @@ __global__ __launch_bounds__(COLS * RG) void centre_window_kernel(const float* _
     uint32_t* const tie_min = run + COLS;                            // [COLS]: ordered bits of the smallest tied value
     uint32_t* const tie_max = tie_min + COLS;                        // [COLS]: of the largest
     const int tid = threadIdx.x;
-    const int tx = tid % COLS, ty = tid / COLS;
-
-    int64_t tile = blockIdx.x;
-    if constexpr (COLS < 64) {
-        // a row segment of a narrow tile is a part of a 128-byte line: workgroups b and b + 8 (one XCD, dispatched together) take
-        // neighbouring tiles so that the parts of a line meet in one L2
-        const int64_t per = (tiles + 7) / 8;
-        tile = static_cast<int64_t>(blockIdx.x % 8) * per + blockIdx.x / 8;
-        if (tile >= tiles) return;
-    }
-    const int64_t col_raw = tile * COLS + tx;
-    const bool real = col_raw < n_cols;
-    const int64_t col = real ? col_raw : n_cols - 1;
-    const int last_row = n_rows - 1;
-    auto load = [&](int r) -> float {
-        const int rr = r < last_row ? r : last_row;
-        int64_t src = rr;
-        if constexpr (INDEXED) src = row_index[rr];
-        return G[src * ld + col];
-    };
-    const float c = centre[col];
+    const colsel::ColumnTile tile = colsel::column_tile<COLS>(tiles, n_cols);
+    if (tile.none) return;
+    const int tx = tile.tx, ty = tile.ty;
+    const colsel::ColumnRows rows{G, ld, row_index, tile.col, n_rows - 1};
+    auto load = [&](int r) -> float { return rows.at<INDEXED>(r); };
+    const float c = centre[tile.col];
 
     // ---- the resident tile: kept as values.  A row beyond the height holds a NaN: its key is the NaNs', and behind every real
     // row IN ROW ORDER is exactly where the restatement would put a NaN appended to the column -- no rank asked for reaches it,
@@ -140,46 +127,17 @@ __global__ __launch_bounds__(COLS * RG) void centre_window_kernel(const float* _
                 if (j % kResidentGroup == kResidentGroup - 1) __builtin_amdgcn_sched_barrier(0);
             }
         } else {
-            for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
-                float v[kStreamUnroll];
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) count(window_key(v[j], c), r0 + j * RG < n_rows);
-            }
+            colsel::stream_rows<RG>(ty, n_rows, load, [&](float v, int, bool valid) { count(window_key(v, c), valid); });
         }
         __syncthreads();
-        if (ty < kSegments) {
-            uint32_t s = 0u;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) s += hist[(16 * ty + b) * COLS + tx];
-            seg[ty * COLS + tx] = s;
-        }
+        auto counter = [hist](int slot) { return hist[slot]; };
+        if (ty < kSegments) seg[ty * COLS + tx] = colsel::segment_sum<COLS>(ty, tx, counter);
         __syncthreads();
-        if (ty == 0) {      // one thread per column walks 16 + 16 counters to the digit that holds the rank
-            int want = left[tx];
-            int s16 = kSegments - 1;
-            for (int g = 0; g < kSegments; ++g) {
-                const int cnt = static_cast<int>(seg[g * COLS + tx]);
-                if (want < cnt) {
-                    s16 = g;
-                    break;
-                }
-                want -= cnt;
-            }
-            int digit = 16 * s16 + 15;
-            uint32_t cnt = 0u;
-            for (int b = 16 * s16; b < 16 * s16 + 16; ++b) {
-                cnt = hist[b * COLS + tx];
-                if (want < static_cast<int>(cnt)) {
-                    digit = b;
-                    break;
-                }
-                want -= static_cast<int>(cnt);
-            }
-            found[tx] = (prefix << 8) | static_cast<uint32_t>(digit);
-            left[tx] = want;
-            run[tx] = cnt;
+        if (ty == 0) {      // one thread per column
+            const colsel::DigitRank at = colsel::walk_to_digit<COLS>(left[tx], seg, tx, counter);
+            found[tx] = (prefix << 8) | static_cast<uint32_t>(at.digit);
+            left[tx] = at.left;
+            run[tx] = at.run;
         }
         __syncthreads();
     }
@@ -207,13 +165,7 @@ __global__ __launch_bounds__(COLS * RG) void centre_window_kernel(const float* _
             if (j % kResidentGroup == kResidentGroup - 1) __builtin_amdgcn_sched_barrier(0);
         }
     } else {
-        for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
-            float v[kStreamUnroll];
-#pragma unroll
-            for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
-#pragma unroll
-            for (int j = 0; j < kStreamUnroll; ++j) fold(v[j], r0 + j * RG < n_rows ? window_key(v[j], c) : kPadKey);
-        }
+        colsel::stream_rows<RG>(ty, n_rows, load, [&](float v, int, bool valid) { fold(v, valid ? window_key(v, c) : kPadKey); });
     }
     if (lo <= hi) {
         atomicMin(&tie_min[tx], lo);
@@ -222,9 +174,8 @@ __global__ __launch_bounds__(COLS * RG) void centre_window_kernel(const float* _
     double* const part = reinterpret_cast<double*>(hist);      // [RG][COLS], over the dead histogram
     part[ty * COLS + tx] = sum;
     __syncthreads();
-    if (ty != 0 || !real) return;
-    double total = 0.0;
-    for (int w = 0; w < RG; ++w) total += part[w * COLS + tx];      // a fixed order: the same bits every run
+    if (ty != 0 || !tile.real) return;
+    double total = colsel::fixed_order_total<COLS, RG>(part, tx);
     if (!all) {
         const uint32_t t_lo = tie_min[tx], t_hi = tie_max[tx];
         if (t_lo == t_hi) {
@@ -246,22 +197,8 @@ __global__ __launch_bounds__(COLS * RG) void centre_window_kernel(const float* _
             }
         }
     }
-    out[col] = static_cast<float>(total / static_cast<double>(keep));
-    if (radius != nullptr) radius[col] = __uint_as_float(T);      // (kNanKey's bits are a NaN's)
-}
-
-template <int COLS, int RG, int RPT>
-int launch_shape(byz_ctx* ctx, const float* G, int n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index, const float* centre,
-                 int keep, float* out, float* radius, hipStream_t stream) {
-    const int64_t tiles = ceil_div(n_cols, COLS);
-    const int64_t grid = COLS < 64 ? ceil_div(tiles, 8) * 8 : tiles;
-    BYZ_REQUIRE(grid <= 0x7fffffff, "window mean: too many columns");
-    constexpr int lds_bytes = lds_words(COLS) * 4;
-    auto* kernel = row_index != nullptr ? &centre_window_kernel<COLS, RG, RPT, true> : &centre_window_kernel<COLS, RG, RPT, false>;
-    BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), lds_bytes));
-    kernel<<<static_cast<unsigned>(grid), COLS * RG, lds_bytes, stream>>>(G, n_rows, n_cols, ld, row_index, centre, keep, tiles, out,
-                                                                         radius);
-    return check_launch("centre_window_kernel");
+    out[tile.col] = static_cast<float>(total / static_cast<double>(keep));
+    if (radius != nullptr) radius[tile.col] = __uint_as_float(T);      // (kNanKey's bits are a NaN's)
 }
 
 }  // namespace
@@ -282,13 +219,14 @@ int launch_centre_window(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n
     BYZ_TRY(check_centre_window("window_mean", n_rows, keep));
     const int n = static_cast<int>(n_rows), k = static_cast<int>(keep);
     KernelTimer t(ctx, BYZ_K_TRIMMED_MEAN, stream);
-    // rank_select.hip's geometries and its edges, by height alone
-    if (n <= 256) return launch_shape<64, 16, 16>(ctx, G, n, n_cols, ld, row_index, centre, k, out, radius, stream);
-    if (n <= 1024) return launch_shape<16, 32, 32>(ctx, G, n, n_cols, ld, row_index, centre, k, out, radius, stream);
-    if (n <= 2304) return launch_shape<16, 64, 36>(ctx, G, n, n_cols, ld, row_index, centre, k, out, radius, stream);
-    if (n <= rank_select_resident_max_rows())
-        return launch_shape<16, 64, 64>(ctx, G, n, n_cols, ld, row_index, centre, k, out, radius, stream);
-    return launch_shape<64, 16, 0>(ctx, G, n, n_cols, ld, row_index, centre, k, out, radius, stream);
+    return colsel::for_height(n, [&](auto geometry) {
+        using Geo = decltype(geometry);
+        const colsel::TileGrid t = colsel::tile_grid<Geo::COLS>(n_cols);
+        auto* kernel = row_index != nullptr ? &centre_window_kernel<Geo::COLS, Geo::RG, Geo::RPT, true>
+                                            : &centre_window_kernel<Geo::COLS, Geo::RG, Geo::RPT, false>;
+        return colsel::launch_column_tiles(ctx, kernel, "centre_window_kernel", "window mean", t, Geo::COLS * Geo::RG,
+                                           lds_words(Geo::COLS) * 4, stream, G, n, n_cols, ld, row_index, centre, k, t.tiles, out, radius);
+    });
 }
 
 }  // namespace byz

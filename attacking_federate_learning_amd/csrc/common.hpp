@@ -572,8 +572,7 @@ int64_t trimmed_mean_max_rows();
 int launch_trimmed_mean_tall(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                              int64_t keep, float* out, hipStream_t stream);
 // rank_select.hip: the coordinate-wise median (median = true; trim_count ignored) and the rank-trimmed mean: two order statistics by one
-// radix select, the column tile resident in registers up to rank_select_resident_max_rows() rows, streamed from HBM beyond
-int64_t rank_select_resident_max_rows();
+// radix select (column_select.hpp), the column tile resident in registers up to 4,096 rows, streamed from HBM beyond
 int launch_rank_select(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        int64_t trim_count, bool median, float* out, hipStream_t stream);
 // centre_window.hip: per column the mean of the `keep` values nearest a GIVEN centre (ties in row order), optionally the radius

@@ -18,7 +18,12 @@
 //              select passes and the sums, FIVE passes (the median: four, its values are read off the keys);
 //   resident   RPT  > 0: the workgroup's COLS x n tile is loaded ONCE into registers as keys (thread (tx, ty) holds rows ty,
 //              ty + RG, ...), the four passes and the sums run over the registers: 4 n D + 4 D bytes of traffic.
-// The dispatcher picks by height alone (pick_shape).
+// The geometry comes by height alone from column_select.hpp's table, and with it the select's common parts: the walk to a rank's
+// digit, the tile and its grid, the row loader, the streamed loop, the fixed-order total and the launch.  This file's own: the two
+// ranks counted together, the counters' width (wide beyond 65,535 rows), kNanKey / kPadKey, and the sums.
+#include <type_traits>
+
+#include "column_select.hpp"
 #include "common.hpp"
 #include "order_keys.hpp"
 
@@ -29,9 +34,8 @@ namespace {
 // they sit behind every rank asked for and need no predicate.  (Both are bit patterns of NaNs: no other float maps onto them.)
 constexpr uint32_t kNanKey = 0xfffffffeu;
 constexpr uint32_t kPadKey = 0xffffffffu;
-constexpr int kStreamUnroll = 8;
 constexpr int kResidentBatch = 4;
-constexpr int kSegments = 16;                  // the walk to a rank's digit: sixteen 16-digit segment sums, then 16 + 16 steps
+using colsel::kSegments;
 
 __device__ __forceinline__ uint32_t rank_key(float v) {
     if ((__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u) return kNanKey;
@@ -59,25 +63,11 @@ __global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __r
     uint32_t* const run = reinterpret_cast<uint32_t*>(left + 2 * COLS);   // [2][COLS]: keys equal to the answer
     uint32_t* const nan_seen = run + 2 * COLS;                       // [COLS]
     const int tid = threadIdx.x;
-    const int tx = tid % COLS, ty = tid / COLS;
-
-    int64_t tile = blockIdx.x;
-    if constexpr (COLS < 64) {
-        // a row segment of a narrow tile is a part of a 128-byte line: workgroups b and b + 8 (one XCD, dispatched together) take
-        // neighbouring tiles so that the parts of a line meet in one L2
-        const int64_t per = (tiles + 7) / 8;
-        tile = static_cast<int64_t>(blockIdx.x % 8) * per + blockIdx.x / 8;
-        if (tile >= tiles) return;
-    }
-    const int64_t col_raw = tile * COLS + tx;
-    const bool real = col_raw < n_cols;
-    const int64_t col = real ? col_raw : n_cols - 1;
-    const int last_row = n_rows - 1;
-    auto load = [&](int r) -> float {
-        const int rr = r < last_row ? r : last_row;
-        const int64_t src = row_index ? row_index[rr] : rr;
-        return G[src * ld + col];
-    };
+    const colsel::ColumnTile tile = colsel::column_tile<COLS>(tiles, n_cols);
+    if (tile.none) return;
+    const int tx = tile.tx, ty = tile.ty;
+    const colsel::ColumnRows rows{G, ld, row_index, tile.col, n_rows - 1};
+    auto load = [&](int r) -> float { return rows.at(r); };
 
     // ---- the resident tile: kept as keys
     uint32_t keys[RPT > 0 ? RPT : 1];
@@ -126,13 +116,7 @@ __global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __r
 #pragma unroll
             for (int j = 0; j < RPT; ++j) count(keys[j], true);      // (the padding is counted: behind every rank)
         } else {
-            for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
-                float v[kStreamUnroll];
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) count(rank_key(v[j]), r0 + j * RG < n_rows);
-            }
+            colsel::stream_rows<RG>(ty, n_rows, load, [&](float v, int, bool valid) { count(rank_key(v), valid); });
         }
         if (MEDIAN && pass == 0 && nan != 0u) atomicOr(&nan_seen[tx], 1u);
         __syncthreads();
@@ -142,52 +126,29 @@ __global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __r
             else return which != 0 ? hist[slot] >> 16 : hist[slot] & 0xffffu;
         };
         if (ty < kSegments) {
-            uint32_t s_lo = 0u, s_hi = 0u;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-                s_lo += counter(0, (16 * ty + b) * COLS + tx);
-                s_hi += counter(1, (16 * ty + b) * COLS + tx);
-            }
-            seg[ty * COLS + tx] = s_lo;
-            seg[(kSegments + ty) * COLS + tx] = s_hi;
+            const uint2 s = colsel::segment_sum<COLS>(ty, tx, [&](int slot) { return make_uint2(counter(0, slot), counter(1, slot)); });
+            seg[ty * COLS + tx] = s.x;
+            seg[(kSegments + ty) * COLS + tx] = s.y;
         }
         __syncthreads();
-        if (ty < 2) {      // one thread per column and rank walks 16 + 16 counters to the digit that holds the rank
+        if (ty < 2) {      // one thread per column and rank
             const int which = ty;
-            int want = left[which * COLS + tx];
-            int s16 = kSegments - 1;
-            for (int g = 0; g < kSegments; ++g) {
-                const int cnt = static_cast<int>(seg[(which * kSegments + g) * COLS + tx]);
-                if (want < cnt) {
-                    s16 = g;
-                    break;
-                }
-                want -= cnt;
-            }
-            int digit = 16 * s16 + 15;
-            uint32_t cnt = 0u;
-            for (int b = 16 * s16; b < 16 * s16 + 16; ++b) {
-                cnt = counter(which, b * COLS + tx);
-                if (want < static_cast<int>(cnt)) {
-                    digit = b;
-                    break;
-                }
-                want -= static_cast<int>(cnt);
-            }
-            found[which * COLS + tx] = ((which ? prefix_hi : prefix_lo) << 8) | static_cast<uint32_t>(digit);
-            left[which * COLS + tx] = want;
-            run[which * COLS + tx] = cnt;
+            const colsel::DigitRank at = colsel::walk_to_digit<COLS>(left[which * COLS + tx], seg + which * kSegments * COLS, tx,
+                                                                     [&](int slot) { return counter(which, slot); });
+            found[which * COLS + tx] = ((which ? prefix_hi : prefix_lo) << 8) | static_cast<uint32_t>(at.digit);
+            left[which * COLS + tx] = at.left;
+            run[which * COLS + tx] = at.run;
         }
         __syncthreads();
     }
 
     const uint32_t key_lo = found[tx], key_hi = found[COLS + tx];
     if constexpr (MEDIAN) {
-        if (ty != 0 || !real) return;
+        if (ty != 0 || !tile.real) return;
         const float lo = key_value(key_lo), hi = key_value(key_hi);
         float med = rank_lo == rank_hi ? lo : __fmul_rn(__fadd_rn(lo, hi), 0.5f);
         if (nan_seen[tx] != 0u) med = __uint_as_float(0x7fc00000u);
-        out[col] = med;
+        out[tile.col] = med;
     } else {
         // ---- the sums: everything strictly between the two order statistics
         double sum = 0.0;
@@ -198,27 +159,20 @@ __global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __r
                 if (in) sum += static_cast<double>(key_value(keys[j]));
             }
         } else {
-            for (int r0 = ty; r0 < n_rows; r0 += RG * kStreamUnroll) {
-                float v[kStreamUnroll];
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) v[j] = load(r0 + j * RG);
-#pragma unroll
-                for (int j = 0; j < kStreamUnroll; ++j) {
-                    const uint32_t key = rank_key(v[j]);
-                    const bool in = r0 + j * RG < n_rows && key > key_lo && key < key_hi;
-                    if (in) sum += static_cast<double>(v[j]);
-                }
-            }
+            colsel::stream_rows<RG>(ty, n_rows, load, [&](float v, int, bool valid) {
+                const uint32_t key = rank_key(v);
+                const bool in = valid && key > key_lo && key < key_hi;
+                if (in) sum += static_cast<double>(v);
+            });
         }
         double* const part = reinterpret_cast<double*>(hist);      // [RG][COLS], over the dead histogram
         part[ty * COLS + tx] = sum;
         __syncthreads();
-        if (ty != 0 || !real) return;
+        if (ty != 0 || !tile.real) return;
         const float lo = key_value(key_lo), hi = key_value(key_hi);
         float result = lo;                     // every kept value equal (a NaN key: NaN)
         if (key_lo != key_hi) {
-            double total = 0.0;
-            for (int w = 0; w < RG; ++w) total += part[w * COLS + tx];      // a fixed order: the same bits every run
+            double total = colsel::fixed_order_total<COLS, RG>(part, tx);
             // kept copies of lo: from its rank to the end of its run; of hi: from the start of its run to its rank
             const double c_lo = static_cast<double>(static_cast<int>(run[tx]) - left[tx]);
             const double c_hi = static_cast<double>(left[COLS + tx] + 1);
@@ -226,51 +180,31 @@ __global__ __launch_bounds__(COLS * RG) void rank_select_kernel(const float* __r
             total += c_hi * static_cast<double>(hi);
             result = static_cast<float>(total / static_cast<double>(rank_hi - rank_lo + 1));
         }
-        out[col] = result;
+        out[tile.col] = result;
     }
 }
 
-template <int COLS, int RG, int RPT, bool WIDE, bool MEDIAN>
-int launch_shape(byz_ctx* ctx, const float* G, int n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index, int rank_lo,
-                 int rank_hi, float* out, hipStream_t stream) {
-    const int64_t tiles = ceil_div(n_cols, COLS);
-    const int64_t grid = COLS < 64 ? ceil_div(tiles, 8) * 8 : tiles;
-    BYZ_REQUIRE(grid <= 0x7fffffff, "rank select: too many columns");
-    constexpr int lds_bytes = lds_words(COLS, WIDE) * 4;
-    auto* kernel = &rank_select_kernel<COLS, RG, RPT, WIDE, MEDIAN>;
-    BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), lds_bytes));
-    kernel<<<static_cast<unsigned>(grid), COLS * RG, lds_bytes, stream>>>(G, n_rows, n_cols, ld, row_index, rank_lo, rank_hi, tiles, out);
-    return check_launch("rank_select_kernel");
-}
-
-// Which shape takes a column height: by height alone, never by data (DESIGN.md 3.3b has the timings behind the edges).
-enum Shape { kResident256, kResident1024, kResident2304, kResident4096, kStreamed, kStreamedWide };
-constexpr int kResidentMaxRows = 4096;
-Shape pick_shape(int64_t n_rows) {
-    if (n_rows <= 256) return kResident256;
-    if (n_rows <= 1024) return kResident1024;
-    if (n_rows <= 2304) return kResident2304;
-    if (n_rows <= kResidentMaxRows) return kResident4096;
-    return n_rows <= 65535 ? kStreamed : kStreamedWide;
-}
-
+// Heights up to 65,535 keep both ranks' counts in one word; a streamed column beyond that takes the wide counters.
 template <bool MEDIAN>
 int launch_picked(byz_ctx* ctx, const float* G, int n, int64_t n_cols, int64_t ld, const int32_t* row_index, int rank_lo, int rank_hi,
                   float* out, hipStream_t stream) {
-    switch (pick_shape(n)) {
-        case kResident256: return launch_shape<64, 16, 16, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
-        case kResident1024: return launch_shape<16, 32, 32, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
-        case kResident2304: return launch_shape<16, 64, 36, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
-        case kResident4096: return launch_shape<16, 64, 64, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
-        case kStreamed: return launch_shape<64, 16, 0, false, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
-        case kStreamedWide: break;
-    }
-    return launch_shape<64, 16, 0, true, MEDIAN>(ctx, G, n, n_cols, ld, row_index, rank_lo, rank_hi, out, stream);
+    auto launch = [&](auto geometry, auto wide) {
+        using Geo = decltype(geometry);
+        constexpr bool WIDE = decltype(wide)::value;
+        const colsel::TileGrid t = colsel::tile_grid<Geo::COLS>(n_cols);
+        return colsel::launch_column_tiles(ctx, &rank_select_kernel<Geo::COLS, Geo::RG, Geo::RPT, WIDE, MEDIAN>, "rank_select_kernel",
+                                           "rank select", t, Geo::COLS * Geo::RG, lds_words(Geo::COLS, WIDE) * 4, stream, G, n, n_cols,
+                                           ld, row_index, rank_lo, rank_hi, t.tiles, out);
+    };
+    return colsel::for_height(n, [&](auto geometry) {
+        if constexpr (decltype(geometry)::RPT == 0) {
+            if (n > 65535) return launch(geometry, std::true_type{});
+        }
+        return launch(geometry, std::false_type{});
+    });
 }
 
 }  // namespace
-
-int64_t rank_select_resident_max_rows() { return kResidentMaxRows; }
 
 int launch_rank_select(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const int32_t* row_index,
                        int64_t trim_count, bool median, float* out, hipStream_t stream) {

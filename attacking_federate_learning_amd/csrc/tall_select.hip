@@ -9,39 +9,29 @@
 // t in row order.  Until round 6's last session every height beyond 5,632 rows was SORTED (an LDS bitonic network up to 16,384 rows,
 // a global-memory one beyond: 13.7 ms for 10,000 x 32,768 = 96 GB/s, six times the register kernels' cost per value).  Here an order
 // statistic is a RADIX SELECT over the 32-bit keys, 8 bits per pass, the column streamed from HBM once per pass:
-//   * a workgroup owns 64 consecutive columns; its four waves split the rows (wave w: rows w, w + 4, ...), a wave reads 256
-//     contiguous bytes per row;
+//   * a workgroup owns 64 consecutive columns; its sixteen waves split the rows (wave w: rows w, w + 16, ...), a wave reads 256
+//     contiguous bytes per row: column_select.hpp's streamed geometry, and its tile, row loader and streamed loop;
 //   * a pass counts the keys that match the digits found so far into hist[digit][column] (LDS, one bank per column: no
-//     conflicts whatever the data), then one thread per column walks its 256 counters to the digit that holds the rank;
+//     conflicts whatever the data), then one thread per column walks to the digit that holds the rank (the header's walk);
 //   * 4 passes give the lower median (and, on the way, the next larger value for an even count and whether a NaN is there), 4 the
 //     window's edge, the last one the sums: 9 passes, 36 bytes per value -- bound by HBM like the sort never was.
 // Ties at the edge with both signs present (+t and -t: the only place where row order matters) are settled by one thread per
-// column walking the rows in order; a NaN anywhere in the column makes the result NaN, like np.median.
+// column walking the rows in order; a NaN anywhere in the column makes the result NaN, like np.median.  This file's own: the two
+// stages, what stage 1 leaves in extra[] (NaN seen, the smallest key beyond, the next key) and the signed ties.
+#include "column_select.hpp"
 #include "common.hpp"
 #include "order_keys.hpp"
 
 namespace byz {
 namespace {
 
-constexpr int kTileCols = 64;
-constexpr int kWaves = 16;     // sixteen waves split the rows: what covers HBM's latency is loads in flight (four waves: 1.2 TB/s)
-constexpr int kUnroll = 8;
+// sixteen waves split the rows: what covers HBM's latency is loads in flight (four waves: 1.2 TB/s)
+constexpr int kTileCols = colsel::Streamed::COLS;
+constexpr int kWaves = colsel::Streamed::RG;
 // hist[256][64] (the waves' partial sums and counts live in it once the selects are done), then per column: the digits found so
 // far, the rank left, and the sixteen 16-digit segment sums of the walk to the rank's digit
 constexpr int kHistWords = 256 * kTileCols;
 constexpr int kLdsWords = kHistWords + kTileCols * (2 + kWaves + 3);
-
-struct Column {
-    const float* G;
-    int64_t ld;
-    const int32_t* row_index;
-    int n_rows;
-    int64_t col;      // this thread's column (clamped into the matrix; `real` says whether it exists)
-    __device__ __forceinline__ float at(int r) const {
-        const int64_t src = row_index ? row_index[r] : r;
-        return G[src * ld + col];
-    }
-};
 
 // STAGE 1: the value's order-preserving bits; STAGE 2: the bits of |fl(x - med)| (non-negative floats order like their bits)
 template <int STAGE>
@@ -51,11 +41,12 @@ __device__ __forceinline__ uint32_t key_of(float x, float med) {
 }
 
 // The key of rank `rank` (0-based, ascending) among the column's keys.  Every thread of the workgroup calls it; the result is
-// the same in the four threads of a column.  `left_out` / `equal_out`: the rank inside the run of equal keys, and its length.
+// the same in the sixteen threads of a column.  `left_out` / `equal_out`: the rank inside the run of equal keys, and its length.
 template <int STAGE>
-__device__ __forceinline__ uint32_t radix_select(const Column& c, float med, int rank, uint32_t* hist, uint32_t* found, int* left,
-                                                 uint32_t* seg, uint32_t* extra, int tx, int ty, int& left_out, int& equal_out) {
-    static_assert(kWaves == 16, "the walk to the rank's digit takes sixteen 16-digit segments, one per wave");
+__device__ __forceinline__ uint32_t radix_select(const colsel::ColumnRows& c, int n_rows, float med, int rank, uint32_t* hist,
+                                                 uint32_t* found, int* left, uint32_t* seg, uint32_t* extra, int tx, int ty,
+                                                 int& left_out, int& equal_out) {
+    static_assert(kWaves == colsel::kSegments, "the walk to the rank's digit takes sixteen 16-digit segments, one per wave");
     // STAGE 1 also leaves (for the median of an even count, and np.median's NaN) in extra[0..63] whether the column holds a NaN and in
     // extra[128..191] the smallest key above the answer: the first pass sees every value; the last pass knows the answer's upper 24 bits,
     // so a larger key either shares them (the next occupied digit of the last histogram) or lies beyond them (a running minimum)
@@ -74,62 +65,31 @@ __device__ __forceinline__ uint32_t radix_select(const Column& c, float med, int
         const uint32_t prefix = found[tx];
         uint32_t beyond = 0xffffffffu;
         int nan = 0;
-        for (int r0 = ty; r0 < c.n_rows; r0 += kWaves * kUnroll) {
-            float v[kUnroll];
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j) {
-                const int r = r0 + j * kWaves;
-                v[j] = c.at(r < c.n_rows ? r : c.n_rows - 1);
+        colsel::stream_rows<kWaves>(ty, n_rows, [&](int r) { return c.at(r); }, [&](float v, int, bool valid) {
+            const uint32_t key = key_of<STAGE>(v, med);
+            const bool match = shift == 24 || (key >> (shift + 8)) == prefix;
+            if (valid && match) atomicAdd(&hist[((key >> shift) & 255u) * kTileCols + tx], 1u);
+            if constexpr (STAGE == 1) {      // (a clamped row repeats a real value: harmless for both)
+                if (shift == 24) nan |= (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u ? 1 : 0;
+                if (shift == 0) beyond = (key >> 8) > prefix && key < beyond ? key : beyond;
             }
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j) {
-                const int r = r0 + j * kWaves;
-                const uint32_t key = key_of<STAGE>(v[j], med);
-                const bool match = shift == 24 || (key >> (shift + 8)) == prefix;
-                if (r < c.n_rows && match) atomicAdd(&hist[((key >> shift) & 255u) * kTileCols + tx], 1u);
-                if constexpr (STAGE == 1) {      // (a clamped row repeats a real value: harmless for both)
-                    if (shift == 24) nan |= (__float_as_uint(v[j]) & 0x7fffffffu) > 0x7f800000u ? 1 : 0;
-                    if (shift == 0) beyond = (key >> 8) > prefix && key < beyond ? key : beyond;
-                }
-            }
-        }
+        });
         if constexpr (STAGE == 1) {
             if (shift == 24 && nan != 0) atomicOr(&extra[tx], 1u);
             if (shift == 0 && beyond != 0xffffffffu) atomicMin(&extra[kTileCols + tx], beyond);
         }
         __syncthreads();
-        {   // the digit that holds the rank: sixteen segment sums per column first, then one thread walks 16 + 16 counters
-            uint32_t seg_sum = 0u;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) seg_sum += hist[(16 * ty + b) * kTileCols + tx];
-            seg[ty * kTileCols + tx] = seg_sum;
-        }
+        // the digit that holds the rank: every wave sums one segment per column, then one thread per column walks
+        auto counter = [hist](int slot) { return hist[slot]; };
+        seg[ty * kTileCols + tx] = colsel::segment_sum<kTileCols>(ty, tx, counter);
         __syncthreads();
         if (ty == 0) {
-            int want = left[tx];
-            int s16 = 15;
-            for (int g = 0; g < 16; ++g) {
-                const int cnt = static_cast<int>(seg[g * kTileCols + tx]);
-                if (want < cnt) {
-                    s16 = g;
-                    break;
-                }
-                want -= cnt;
-            }
-            int digit = 16 * s16 + 15;
-            uint32_t count = 0u;
-            for (int b = 16 * s16; b < 16 * s16 + 16; ++b) {
-                count = hist[b * kTileCols + tx];
-                if (want < static_cast<int>(count)) {
-                    digit = b;
-                    break;
-                }
-                want -= static_cast<int>(count);
-            }
+            const colsel::DigitRank at = colsel::walk_to_digit<kTileCols>(left[tx], seg, tx, counter);
+            const int digit = at.digit;
             found[tx] = (prefix << 8) | static_cast<uint32_t>(digit);
-            left[tx] = want;
+            left[tx] = at.left;
             if (shift == 0) {
-                seg[tx] = count;      // (the run of keys equal to the answer)
+                seg[tx] = at.run;      // (the run of keys equal to the answer)
                 if constexpr (STAGE == 1) {
                     uint32_t next = extra[kTileCols + tx];
                     for (int b = digit + 1; b < 256; ++b) {
@@ -164,21 +124,20 @@ __global__ __launch_bounds__(kTileCols * kWaves) void tall_select_kernel(const f
     int* const part_less = reinterpret_cast<int*>(part_sum + kWaves * kTileCols);       // [kWaves][64]
     int* const part_pos = part_less + kWaves * kTileCols;
     int* const part_neg = part_pos + kWaves * kTileCols;
-    const int tx = threadIdx.x & (kTileCols - 1), ty = threadIdx.x / kTileCols;
-    const int64_t col = static_cast<int64_t>(blockIdx.x) * kTileCols + tx;
-    const bool real = col < n_cols;
-    const Column c{G, ld, row_index, n_rows, real ? col : n_cols - 1};
+    const colsel::ColumnTile tile = colsel::column_tile<kTileCols>(gridDim.x, n_cols);      // (64 columns: one tile per workgroup)
+    const int tx = tile.tx, ty = tile.ty;
+    const colsel::ColumnRows c{G, ld, row_index, tile.col, n_rows - 1};
 
     // ---- the median: rank (n - 1) / 2, and for an even count the next value above it
     const int mid = (n_rows - 1) >> 1;
     int run_left, run_len;
-    const uint32_t lower_key = radix_select<1>(c, 0.0f, mid, hist, found, left, seg, extra, tx, ty, run_left, run_len);
+    const uint32_t lower_key = radix_select<1>(c, n_rows, 0.0f, mid, hist, found, left, seg, extra, tx, ty, run_left, run_len);
     float med = from_ordered_bits(lower_key);
     {
         const uint32_t above = extra[2 * kTileCols + tx];      // the smallest key above the lower median
         const int any_nan = static_cast<int>(extra[tx]);        // a NaN anywhere: np.median is NaN then
         if (any_nan) {
-            if (ty == 0 && real) out[col] = __uint_as_float(0x7fc00000u);
+            if (ty == 0 && tile.real) out[tile.col] = __uint_as_float(0x7fc00000u);
             // (the column goes on through the passes with the others of its tile -- the barriers are the workgroup's -- and its
             //  result is not written again)
         }
@@ -188,42 +147,31 @@ __global__ __launch_bounds__(kTileCols * kWaves) void tall_select_kernel(const f
             med = __fmul_rn(__fadd_rn(med, upper), 0.5f);
         }
         if (keep <= 0) {      // np.mean([]) -> nan
-            if (ty == 0 && real) out[col] = __uint_as_float(0x7fc00000u);
+            if (ty == 0 && tile.real) out[tile.col] = __uint_as_float(0x7fc00000u);
             return;
         }
         // ---- the window's edge: the keep-th smallest |fl(x - med)|
         int edge_left, edge_len;
-        const uint32_t t_bits = radix_select<2>(c, med, keep - 1, hist, found, left, seg, extra, tx, ty, edge_left, edge_len);
+        const uint32_t t_bits = radix_select<2>(c, n_rows, med, keep - 1, hist, found, left, seg, extra, tx, ty, edge_left, edge_len);
         // ---- the sums: everything closer than the edge, and the tied values at it by sign
         double sum = 0.0;      // (np.mean sums pairwise: close to exact; a lane's share of a 2^20-row column is 262,144 values)
         int n_less = 0, n_pos = 0, n_neg = 0;
-        for (int r0 = ty; r0 < n_rows; r0 += kWaves * kUnroll) {
-            float v[kUnroll];
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j) {
-                const int r = r0 + j * kWaves;
-                v[j] = c.at(r < n_rows ? r : n_rows - 1);
+        colsel::stream_rows<kWaves>(ty, n_rows, [&](int r) { return c.at(r); }, [&](float v, int, bool in) {
+            const float d = __fsub_rn(v, med);
+            const uint32_t a = __float_as_uint(__builtin_fabsf(d));
+            if (in && a < t_bits) {
+                sum += static_cast<double>(d);
+                ++n_less;
             }
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j) {
-                const int r = r0 + j * kWaves;
-                const float d = __fsub_rn(v[j], med);
-                const uint32_t a = __float_as_uint(__builtin_fabsf(d));
-                const bool in = r < n_rows;
-                if (in && a < t_bits) {
-                    sum += static_cast<double>(d);
-                    ++n_less;
-                }
-                n_pos += in && a == t_bits && d > 0.0f ? 1 : 0;
-                n_neg += in && a == t_bits && d < 0.0f ? 1 : 0;
-            }
-        }
+            n_pos += in && a == t_bits && d > 0.0f ? 1 : 0;
+            n_neg += in && a == t_bits && d < 0.0f ? 1 : 0;
+        });
         part_sum[ty * kTileCols + tx] = sum;
         part_less[ty * kTileCols + tx] = n_less;
         part_pos[ty * kTileCols + tx] = n_pos;
         part_neg[ty * kTileCols + tx] = n_neg;
         __syncthreads();
-        if (ty != 0 || !real || any_nan) return;
+        if (ty != 0 || !tile.real || any_nan) return;
         double total = 0.0;
         int less = 0, pos = 0, neg = 0;
         for (int w = 0; w < kWaves; ++w) {      // a fixed order: the same bits every run
@@ -251,7 +199,7 @@ __global__ __launch_bounds__(kTileCols * kWaves) void tall_select_kernel(const f
             }
             total += static_cast<double>(tp - tn) * static_cast<double>(edge);
         }
-        out[col] = __fadd_rn(static_cast<float>(total / static_cast<double>(keep)), med);
+        out[tile.col] = __fadd_rn(static_cast<float>(total / static_cast<double>(keep)), med);
     }
 }
 
@@ -265,13 +213,8 @@ int launch_trimmed_mean_tall(byz_ctx* ctx, const float* G, int64_t n_rows, int64
         set_error("trimmed_mean supports at most %lld rows, got %lld", (long long)kLargeMaxRows, (long long)n_rows);
         return BYZ_E_UNSUPPORTED;
     }
-    const int64_t tiles = ceil_div(n_cols, kTileCols);
-    BYZ_REQUIRE(tiles <= 0x7fffffff, "trimmed_mean: too many columns");
-    const int lds_bytes = kLdsWords * 4;
-    BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&tall_select_kernel), lds_bytes));
-    tall_select_kernel<<<static_cast<unsigned>(tiles), kTileCols * kWaves, lds_bytes, stream>>>(G, (int)n_rows, n_cols, ld, row_index,
-                                                                                             (int)keep, out);
-    return check_launch("tall_select_kernel");
+    return colsel::launch_column_tiles(ctx, &tall_select_kernel, "tall_select_kernel", "trimmed_mean", colsel::tile_grid<kTileCols>(n_cols),
+                                       kTileCols * kWaves, kLdsWords * 4, stream, G, (int)n_rows, n_cols, ld, row_index, (int)keep, out);
 }
 
 }  // namespace byz

@@ -89,6 +89,27 @@ def test_column_counts_that_are_not_multiples_of_the_tile(eng, torch, n, d):
     check_window(eng, torch, g, c, [int(0.76 * n)])
 
 
+@pytest.mark.parametrize('d', [1, 17, 2051])
+@pytest.mark.parametrize('n', [300, 2305])
+def test_sixteen_column_tiles_whose_count_is_no_multiple_of_eight(eng, torch, n, d):
+    """Both heights take 16-column tiles, whose workgroups are regrouped by eights (column_select.hpp: column_tile): 1, 2 and
+    129 tiles leave workgroups beyond the last tile and a last tile that is not full.  Without row_index and with one."""
+    rng = np.random.default_rng(n + d)
+    full, c = make('normal', n + 7, d, seed=n + d)
+    full[:, ::2], c[::2] = tie_case(n + 7, (d + 1) // 2, seed=d)
+    keep = int(0.76 * n)
+    index = rng.permutation(n + 7)[:n]
+    logical = np.ascontiguousarray(full[index])
+    want = check_window(eng, torch, logical, c, [keep])[keep]
+    ft, ct = on_device(eng, torch, full), on_device(eng, torch, c)
+    idx = torch.from_numpy(index.astype(np.int32)).to(ft.device)
+    got, radius = eng.window_mean(ft, ct, keep, row_index=idx, return_radius=True)
+    want_radius, kept = restated_window(logical, c, keep)[1:]
+    assert same_radius(radius.cpu().numpy(), want_radius)
+    assert window_within_bar(got.cpu().numpy(), logical, kept)
+    assert got.cpu().numpy().tobytes() == want.tobytes()
+
+
 # ---- special columns ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('n', [7, 1000, 2080, 4000, 6001])
 def test_constant_and_two_valued_columns_are_exact(eng, torch, n):
