@@ -71,6 +71,11 @@ class ClippedClusteringParams(ctypes.Structure):
     _fields_ = [('clip', ctypes.c_double), ('adaptive', ctypes.c_int32), ('method', ctypes.c_int32), ('fill', ctypes.c_double)]
 
 
+class AfaParams(ctypes.Structure):
+    """byz_afa_params: AFA's first xi, its growth per removing round and the cap on the rounds (0: none)."""
+    _fields_ = [('xi0', ctypes.c_double), ('delta_xi', ctypes.c_double), ('max_rounds', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -222,6 +227,10 @@ _PROTOTYPES = {
     'byz_faba_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_faba_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
     'byz_faba_host': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
+    'byz_afa_select_dev': [c_vp, c_vp, c_i64, c_vp, _P(AfaParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_afa_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, _P(AfaParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_afa_info': [c_vp, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
+    'byz_afa_host': [c_vp, c_vp, c_i64, c_i64, c_vp, _P(AfaParams), c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],

@@ -1925,6 +1925,86 @@ int byz_faba_info(byz_ctx* ctx, int64_t* removed_rows, int64_t* kept_rows, int64
     return BYZ_OK;
 }
 
+// ---- AFA (Munoz-Gonzalez, Co & Lupu, arXiv:1909.05125; beyond the reference) -----------------------------------------------------
+namespace {
+
+int check_afa(const char* who, int64_t n, const byz_afa_params* params) {
+    if (n > kAfaMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kAfaMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    if (n < 2) {
+        set_error("%s: at least 2 rows, got %lld", who, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!(std::isfinite(params->xi0) && params->xi0 >= 0.0 && std::isfinite(params->delta_xi) && params->delta_xi >= 0.0) ||
+        params->max_rounds < 0) {
+        set_error("%s: xi0 = %g and delta_xi = %g must be finite and >= 0, max_rounds = %lld >= 0", who, params->xi0, params->delta_xi,
+                  (long long)params->max_rounds);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_afa_select_dev(byz_ctx* ctx, const double* gram, int64_t n_rows, const double* weights, const byz_afa_params* params,
+                       int32_t* kept, int32_t* round_of, double* score, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(gram && kept, "afa_select: null Gram or output");
+    BYZ_TRY(check_afa("afa_select", n_rows, params));
+    AfaScratch a;
+    BYZ_TRY(afa_workspace(ctx, n_rows, &a));
+    mark(ctx, kReportAfa, as_stream(stream));
+    return launch_afa_select(ctx, a, gram, n_rows, weights, params->xi0, params->delta_xi, params->max_rounds, kept, round_of, score,
+                             as_stream(stream));
+}
+
+// It waits where byz_gram_dev waits (the Gram's duplicate search), and nowhere when the caller passes the Gram.
+int byz_afa_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const double* weights,
+                const byz_afa_params* params, const double* gram_in, float* out, int32_t* kept, int32_t* round_of, double* score,
+                void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "afa"));
+    BYZ_REQUIRE(out, "afa: null output");
+    BYZ_TRY(check_afa("afa", n_rows, params));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "afa"));
+    hipStream_t s = as_stream(stream);
+    AfaScratch a;
+    BYZ_TRY(afa_workspace(ctx, n_rows, &a));
+    mark(ctx, kReportAfa, s);
+    const double* gram = gram_in;
+    if (gram == nullptr) {
+        BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
+        BYZ_TRY(launch_gram(ctx, G, n_rows, n_cols, ld, ctx->gram.as<double>(), s));
+        gram = ctx->gram.as<double>();
+    }
+    BYZ_TRY(launch_afa_select(ctx, a, gram, n_rows, weights, params->xi0, params->delta_xi, params->max_rounds, kept, round_of, score, s));
+    return launch_scaled_rows_sum(ctx, G, n_rows, n_cols, ld, a.w, &a.info->divisor, out, s);
+}
+
+int byz_afa_info(byz_ctx* ctx, int64_t* counts6, double* stats4, double* divisor) {
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportAfa, "afa_info: no AFA selection on this context yet", &all));
+    const AfaReport& info = all.afa;
+    if (counts6) {
+        const int32_t counts[6] = {info.rounds, info.kept, info.removed, info.excluded, info.branch, info.degenerate};
+        for (int i = 0; i < 6; ++i) counts6[i] = counts[i];
+    }
+    if (stats4) {
+        stats4[0] = info.mean;
+        stats4[1] = info.med;
+        stats4[2] = info.sd;
+        stats4[3] = info.thr;
+    }
+    if (divisor) *divisor = info.divisor;
+    return BYZ_OK;
+}
+
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
@@ -2900,6 +2980,28 @@ int byz_faba_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_c
     st.out(&order, order_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_faba_dev(ctx, st.G(), n_rows, n_cols, n_cols, remove_count, dist, out, kept, order, st.stream()));
+    return st.finish();
+}
+
+int byz_afa_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const double* weights_host,
+                 const byz_afa_params* params, const double* gram_host, float* out_host, int32_t* kept_host, int32_t* round_of_host,
+                 double* score_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "afa"));
+    BYZ_REQUIRE(out_host, "afa: null output");
+    BYZ_TRY(check_afa("afa", n_rows, params));
+    HostStage st(ctx);
+    float* out;
+    double *weights, *gram, *score;
+    int32_t *kept, *round_of;
+    st.out(&out, out_host, n_cols);
+    st.in(&weights, weights_host, n_rows);
+    st.in(&gram, gram_host, n_rows * n_rows);
+    st.out(&score, score_host, n_rows);
+    st.out(&kept, kept_host, n_rows);
+    st.out(&round_of, round_of_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_afa_dev(ctx, st.G(), n_rows, n_cols, n_cols, weights, params, gram, out, kept, round_of, score, st.stream()));
     return st.finish();
 }
 

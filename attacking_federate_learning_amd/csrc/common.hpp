@@ -164,6 +164,8 @@ struct byz_ctx {
                                  // working matrix (n x n), the first nearest partners, the merges, the labels, the flags, the weights
     byz::Buffer faba;            // FABA, carved into FabaScratch's arrays (faba.hip: faba_workspace): the rows' sums and bad counts, the
                                  // removal order, the kept flags, the weights
+    byz::Buffer afa;             // AFA, carved into AfaScratch's arrays (afa.hip: afa_workspace): the rows' u, r and weights, the kept
+                                 // flags, the rounds of removal
     byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
                                  // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
     // the last Krum attack's values (byz_fang_krum_info reports them; last[kReportFangKrum] says whether there was one)
@@ -505,6 +507,19 @@ int faba_workspace(byz_ctx* ctx, int64_t n, FabaScratch* out);
 // t.info
 int launch_faba_select(byz_ctx* ctx, const FabaScratch& t, const float* dist, int64_t n, int64_t r, int power, int32_t* kept_out,
                        int32_t* order_out, hipStream_t stream);
+// afa.hip: AFA's selection on an fp64 Gram.  The scalars of a call: DeviceScalars::afa.
+constexpr int64_t kAfaMaxRows = 16384;       // the loop's one workgroup owns 1024 x 16 rows
+struct AfaScratch {
+    AfaReport* info;
+    double *u, *r, *w;               // n: every row's initial u; sqrt of its diagonal (0: excluded); its weight, 0 when not kept
+    int32_t *kept, *round_of;        // n: the 0 / 1 flags; the round of removal (0: excluded, -1: kept)
+};
+int afa_workspace(byz_ctx* ctx, int64_t n, AfaScratch* out);
+// the usable rows, the initial u, the rounds: t.kept and t.w (kept_out, round_of_out and score_out optional), the weights' sum and
+// the other scalars into t.info
+int launch_afa_select(byz_ctx* ctx, const AfaScratch& t, const double* gram, int64_t n, const double* weights, double xi0,
+                      double delta_xi, int64_t max_rounds, int32_t* kept_out, int32_t* round_of_out, double* score_out,
+                      hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

@@ -86,6 +86,13 @@ struct FabaReport {
     double last_score;               // s of the last removed row (0 when nobody was removed)
     double kept_f64;                 // the divisor of the sum
 };
+struct AfaReport {
+    int32_t rounds, kept;            // the rounds run (the last one removed nobody unless max_rounds cut it); the rows kept
+    int32_t removed, excluded;       // the rows a round removed; the rows that were never usable (the three add up to n)
+    int32_t branch, degenerate;      // the last removing round: -1 below the median, +1 above, 0 none; a round's A was not > 0
+    double mean, med, sd, thr;       // the last complete round's statistics (0 before the first)
+    double divisor;                  // the kept rows' weights summed: the divisor of the sum
+};
 
 struct DeviceScalars {
     CoreScalars core;
@@ -102,6 +109,7 @@ struct DeviceScalars {
     MmInfo mm;
     LinkageInfo linkage;
     FabaReport faba;
+    AfaReport afa;
 };
 
 // What a read-back as bytes, and a 64-bit store or atomic of a kernel, rely on.  No member is padded by the compiler: the sizes
@@ -111,13 +119,15 @@ static_assert(sizeof(CoreScalars) % sizeof(int32_t) == 0 && sizeof(DeviceScalars
 static_assert(sizeof(DeviceScalars) == sizeof(CoreScalars) + sizeof(GeomedReport) + sizeof(DncReport) + sizeof(CclipReport) +
                                            sizeof(FltrustReport) + sizeof(NnmReport) + sizeof(RlrReport) + sizeof(SgReport) +
                                            sizeof(TopkReport) + sizeof(WeakDpReport) + sizeof(FlameInfo) + sizeof(MmInfo) +
-                                           sizeof(LinkageInfo) + sizeof(FabaReport), "no padding between the reports");
+                                           sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport),
+              "no padding between the reports");
 #define BYZ_AT(member) offsetof(DeviceScalars, member)
 constexpr size_t kEightByteFields[] = {
     BYZ_AT(geomed.objective), BYZ_AT(fltrust.trust_sum), BYZ_AT(rlr.flipped), BYZ_AT(sg.bandwidth), BYZ_AT(sg.median),
     BYZ_AT(sg.kept_f64), BYZ_AT(topk.selected), BYZ_AT(topk.ties), BYZ_AT(topk.taken), BYZ_AT(topk.key), BYZ_AT(weak_dp.clip),
     BYZ_AT(flame.admitted_f64), BYZ_AT(flame.clip), BYZ_AT(mm.det), BYZ_AT(linkage.top_height), BYZ_AT(linkage.second_height),
-    BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64)};
+    BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64),
+    BYZ_AT(afa.mean), BYZ_AT(afa.med), BYZ_AT(afa.sd), BYZ_AT(afa.thr), BYZ_AT(afa.divisor)};
 #undef BYZ_AT
 constexpr bool eight_byte_fields_aligned() {
     for (size_t at : kEightByteFields)
@@ -127,9 +137,11 @@ constexpr bool eight_byte_fields_aligned() {
 static_assert(eight_byte_fields_aligned(), "every double and 64-bit counter sits at an 8-byte offset");
 
 // the reports an info call reads; byz_ctx::last[kind]: the stream of the last call that wrote it, and whether there was one
+// (kReportAfa stands in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of kReportCount; the
+// kinds index byz_ctx::last and nothing else, so their numbers are free)
 enum ReportKind {
     kReportGeomed, kReportDnc, kReportCclip, kReportFltrust, kReportNnm, kReportRlr, kReportSignguard, kReportTopk, kReportWeakDp,
-    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportFaba, kReportCount
+    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportAfa, kReportFaba, kReportCount
 };
 struct LastCall { hipStream_t stream = nullptr; bool ran = false; };
 

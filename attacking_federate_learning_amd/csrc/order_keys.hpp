@@ -49,6 +49,13 @@ BYZ_KEY_FN uint64_t ordered_bits_total(double v) {      // (no plain fp64 map to
     return (b & kSign) ? ~b : (b | kSign);
 }
 
+// the fp64 total map read back: the NaN key gives a NaN, every other key its value (the zeros' key: +0.0)
+BYZ_KEY_FN double value_of_total_key(uint64_t key) {
+    constexpr uint64_t kSign = uint64_t{1} << 63;
+    if (key == ~uint64_t{0}) return __builtin_nan("");
+    return __builtin_bit_cast(double, (key & kSign) ? (key & ~kSign) : ~key);
+}
+
 // The median of the rows' norms, by key and sort (SignGuard's M, weak DP's adaptive clip).  norm_key: the key of sqrt(q) for a
 // squared norm q; a row whose q is not finite gets all ones (kNoNormKey, the padding's key as well) and sorts behind every norm.
 // median_of_norm_keys: np.median over the `finite` first keys of the ascending sort -- the middle value, or the mean of the two

@@ -373,6 +373,79 @@ def faba(users_grads, users_count, corrupted_count, distances=None, return_info=
     return get_engine().faba(users_grads, users_count, corrupted_count, distances=distances, return_info=return_info)
 
 
+class AfaReputation:
+    """AFA's memory of who misbehaved (arXiv:1909.05125, section 3.2): client k's chance of sending a good update is
+    Beta(alpha_k, beta_k), every client starting at (alpha0, beta0).  A round in which the rule kept the client adds 1 to its
+    alpha, a round in which the rule removed it 1 to its beta, and its weight in the next round is the mean alpha / (alpha +
+    beta).  A client is BLOCKED for good once P(p_k < 0.5) = I_0.5(alpha, beta) >= delta: its weight is 0 from then on, so the
+    rule sees it as excluded.  Host-side, n small integers; for integer counts the regularised incomplete beta function is
+    the exact binomial tail sum_{j = alpha}^{alpha + beta - 1} C(alpha + beta - 1, j) / 2^(alpha + beta - 1)."""
+
+    def __init__(self, n, alpha0=3, beta0=3, delta=0.95):
+        if int(alpha0) < 1 or int(beta0) < 1:
+            raise ValueError('AfaReputation: alpha0 and beta0 are positive integers')
+        self.alpha = np.full(int(n), int(alpha0), dtype=np.int64)
+        self.beta = np.full(int(n), int(beta0), dtype=np.int64)
+        self.blocked = np.zeros(int(n), dtype=bool)
+        self.delta = float(delta)
+
+    @staticmethod
+    def bad_probability(alpha, beta):
+        """I_0.5(alpha, beta) for positive integers: P(p < 0.5) under Beta(alpha, beta)."""
+        import math
+        alpha, beta = int(alpha), int(beta)
+        trials = alpha + beta - 1
+        return sum(math.comb(trials, j) for j in range(alpha, trials + 1)) / 2 ** trials
+
+    def weights(self):
+        """alpha / (alpha + beta) as float64, 0 for a blocked client.  A caller's sample counts multiply in on the host."""
+        w = self.alpha / (self.alpha + self.beta)
+        w[self.blocked] = 0.0
+        return w
+
+    def update(self, kept, excluded=()):
+        """One round's outcome: `kept` and `excluded` are row indices.  A kept client's alpha grows by 1, a removed client's
+        beta (removed: neither kept nor excluded); an excluded or blocked client is left alone.  Returns the clients blocked
+        by this round."""
+        n = self.alpha.size
+        kept_mask, out_mask = np.zeros(n, dtype=bool), self.blocked.copy()
+        kept_mask[np.asarray(kept, dtype=np.int64)] = True
+        out_mask[np.asarray(excluded, dtype=np.int64)] = True
+        self.alpha[kept_mask & ~out_mask] += 1
+        removed = ~kept_mask & ~out_mask
+        self.beta[removed] += 1
+        fresh = [k for k in np.flatnonzero(removed) if self.bad_probability(self.alpha[k], self.beta[k]) >= self.delta]
+        self.blocked[fresh] = True
+        return np.asarray(fresh, dtype=np.int64)
+
+
+def afa(users_grads, users_count, corrupted_count, weights=None, xi=2.0, delta_xi=0.5, gram=None, reputation=None):
+    """AFA, Adaptive Federated Averaging (Munoz-Gonzalez, Co and Lupu, arXiv:1909.05125, Algorithm 1; not in the reference):
+    every client's cosine with the weighted aggregate of the clients still kept is taken, the clients whose cosine lies more
+    than xi standard deviations from the median are removed on the side the mean of the cosines points away from, xi grows by
+    delta_xi, and the round repeats until it removes nobody; the rest are averaged with their weights.  It needs NO count of
+    attackers: corrupted_count is accepted for the common signature and not used.  It runs on ONE fp64 Gram matrix (`gram=`
+    replaces that stage) and reads the gradients for the Gram and for the final sum only.  The drift attack's copies of one
+    vector have a cosine near 1 with the aggregate where an honest client's is small: the upper branch removes them, as the
+    lower branch removes sign-flipped clients.  Clients of pure noise at three times the honest scale, and sign-flipped
+    clients scaled by 3, are mostly KEPT: they drag the aggregate with them; put `weak_dp` or `centered_clip` in front for
+    those.  A client with a NaN or zero gradient, or a weight that is not positive, is excluded.  `weights`: one fp64 weight a
+    client (sample counts).  `reputation`: an `AfaReputation`; its weights multiply in, and it is updated with this round's
+    kept and excluded clients.  numpy in -> numpy out, device-resident in -> device-resident out.  Usable as `then=` of
+    `nnm`, `bucketing`, `robust_lr`, `sparsefed` and `weak_dp`.  Not one of the `defend` keys: the reference's main.py offers
+    only those four."""
+    engine = get_engine()
+    if reputation is None:
+        return engine.afa(users_grads, users_count, corrupted_count, weights=weights, xi=xi, delta_xi=delta_xi, gram=gram)
+    w = reputation.weights()
+    if weights is not None:
+        w = w * np.asarray(weights.cpu() if hasattr(weights, 'cpu') else weights, dtype=np.float64).reshape(-1)
+    out, info = engine.afa(users_grads, users_count, corrupted_count, weights=w, xi=xi, delta_xi=delta_xi, gram=gram,
+                           return_info=True)
+    reputation.update(info['kept_rows'], info['excluded_rows'])
+    return out
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

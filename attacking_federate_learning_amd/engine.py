@@ -2014,6 +2014,109 @@ class Engine:
         info['order'] = np.asarray(order)[:info['removed']].astype(np.int64)
         return out, info
 
+    # ---- AFA (Munoz-Gonzalez, Co & Lupu, arXiv:1909.05125; not in the reference) ----
+    @staticmethod
+    def _afa_params(n, xi, delta_xi, max_rounds):
+        """byz_afa_params, checked as the library checks them (the refusals that need no GPU)."""
+        n = int(n)
+        if n > 16384:
+            raise NotImplementedError('afa: at most 16384 rows, got %d' % n)
+        if n < 2:
+            raise ValueError('afa: at least 2 rows, got %d' % n)
+        xi, delta_xi, max_rounds = float(xi), float(delta_xi), int(0 if max_rounds is None else max_rounds)
+        if not (np.isfinite(xi) and xi >= 0.0 and np.isfinite(delta_xi) and delta_xi >= 0.0) or max_rounds < 0:
+            raise ValueError('afa: xi = %r and delta_xi = %r must be finite and >= 0, max_rounds = %r >= 0' % (xi, delta_xi, max_rounds))
+        return _native.AfaParams(xi, delta_xi, max_rounds)
+
+    def afa_info(self):
+        """{rounds, kept, removed, excluded, branch, degenerate, mean, med, sd, thr, divisor} of the last afa_select or afa on
+        this engine (synchronises): the rounds run, the rows kept, removed by a round and excluded before the first, the side
+        of the last removing round (-1 below the median, +1 above, 0: nobody was removed), whether a round's A was not > 0,
+        the last complete round's statistics and the kept rows' weights summed."""
+        counts, stats, divisor = (ctypes.c_int64 * 6)(), (ctypes.c_double * 4)(), ctypes.c_double()
+        _check(self.lib.byz_afa_info(self.ctx, counts, stats, ctypes.byref(divisor)))
+        self._unsynced.discard(self._last)
+        info = dict(zip(('rounds', 'kept', 'removed', 'excluded', 'branch', 'degenerate'), (int(v) for v in counts)))
+        info.update(zip(('mean', 'med', 'sd', 'thr'), (float(v) for v in stats)))
+        info['degenerate'] = bool(info['degenerate'])
+        info['divisor'] = divisor.value
+        return info
+
+    def afa_select(self, gram, weights=None, xi=2.0, delta_xi=0.5, max_rounds=None, on_device=False, like=None):
+        """AFA's selection on an fp64 Gram (n x n, as `gram` returns it; taken as symmetric): every row's cosine with the
+        weighted sum of the rows still kept, the rows more than xi standard deviations from the median removed on the side the
+        mean points away from, xi raised by delta_xi, until a round removes nobody (include/byzagg.h states the rule).  A row
+        whose diagonal entry or weight is not finite and positive is excluded before the first round.  Returns (rows, info):
+        the kept rows ascending (on_device=True: the 0 / 1 int32 flags instead, as a DeviceBuffer, or a torch tensor beside
+        `like`) and afa_info()'s fields with `round_of` (int32: the round that removed a row, 0 excluded, -1 kept) and `score`
+        (fp64: the last cosine a row had), host arrays unless on_device."""
+        with _Call(self) as c:
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            shape = tuple(gram.shape)
+            if len(shape) != 2 or shape[0] != shape[1]:
+                raise ValueError('afa_select() takes a square fp64 Gram, got shape %r' % (shape,))
+            n = shape[0]
+            params = self._afa_params(n, xi, delta_xi, max_rounds)
+            gm = c.operand(gram, np.float64, _F64, n * n)
+            w = c.operand(weights, np.float64, _F64, n) if weights is not None else None
+            flags, fptr = c.out(n, np.int32)
+            round_of, rptr = c.out(n, np.int32)
+            score, sptr = c.out(n, np.float64)
+            c.run(self.lib.byz_afa_select_dev(self.ctx, gm.ptr, n, w.ptr if w is not None else None, ctypes.byref(params), fptr, rptr,
+                                              sptr, c.stream))
+            info = self.afa_info()
+        if not on_device:
+            flags = np.flatnonzero(flags.numpy()).astype(np.int64)
+            round_of, score = round_of.numpy(), score.numpy()
+        info['round_of'], info['score'] = round_of, score
+        return flags, info
+
+    def afa(self, g, users_count=None, corrupted_count=None, weights=None, xi=2.0, delta_xi=0.5, max_rounds=None, gram=None,
+            return_info=False):
+        """AFA in one library call: gram (or `gram`, which replaces that stage), afa_select, and the weighted mean of the kept
+        rows: scaled_rows_sum's bits with the weights w_k * kept_k and their sum, read on the device, as the divisor.  Nobody
+        kept: the zero vector.  users_count and corrupted_count are accepted and unused: the rule needs no count.
+        return_info=True also returns afa_info()'s fields with kept_rows (ascending), excluded_rows, round_of and score."""
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        params = self._afa_params(n, xi, delta_xi, max_rounds)
+        if gram is not None and tuple(gram.shape) != (n, n):
+            raise ValueError('the Gram has shape %r, the gradients %d rows' % (tuple(gram.shape), n))
+        if dm is None:
+            h = self._host_matrix(g)
+            d = h.shape[1]
+            out = np.empty(d, dtype=np.float32)
+            flags, round_of, score = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64)
+            w_host = np.ascontiguousarray(_to_host(weights), dtype=np.float64).ravel() if weights is not None else None
+            if w_host is not None and w_host.size != n:
+                raise ValueError('expected %d values, got %d' % (n, w_host.size))
+            if gram is not None:
+                gram = np.ascontiguousarray(gram.numpy() if isinstance(gram, DeviceBuffer) else _to_host(gram), dtype=np.float64)
+            _check(self.lib.byz_afa_host(self.ctx, _hp(h), n, d, _hp(w_host), ctypes.byref(params), _hp(gram), _hp(out), _hp(flags),
+                                         _hp(round_of), _hp(score)))
+        else:
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                gm = c.operand(gram, np.float64, _F64, n * n) if gram is not None else None
+                w = c.operand(weights, np.float64, _F64, n) if weights is not None else None
+                out, optr = c.out(dm.cols)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                round_of, rptr = c.out(n, np.int32, want=return_info)
+                score, sptr = c.out(n, np.float64, want=return_info)
+                c.run(self.lib.byz_afa_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, w.ptr if w is not None else None,
+                                           ctypes.byref(params), gm.ptr if gm is not None else None, optr, fptr, rptr, sptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    flags, round_of, score = (_to_host(v) if _is_torch(v) else v.numpy() for v in (flags, round_of, score))
+        if not return_info:
+            return out
+        info = self.afa_info()
+        round_of = np.asarray(round_of)
+        info.update(kept_rows=np.flatnonzero(flags).astype(np.int64), excluded_rows=np.flatnonzero(round_of == 0).astype(np.int64),
+                    round_of=round_of, score=np.asarray(score))
+        return out, info
+
     # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----
     def manhattan_distances(self, g):
         """The pairwise MANHATTAN (L1) distances of g's rows as a `Distances` handle, resident on the GPU: m_ij = sum_c

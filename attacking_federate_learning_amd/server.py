@@ -22,6 +22,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_flame(lam, min_samples)    the same step with FLAME: the majority cluster by cosine distance, clipped, averaged, noised
     defend_clipped_clustering(method) the same step with ClippedClustering: the larger of two average-linkage clusters, clipped
     defend_faba()                     the same step with FABA: the clients farthest from the running mean dropped one by one
+    defend_afa(xi, delta_xi)          the same step with AFA: cosine outliers dropped round after round, reputations kept across rounds
     defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
@@ -61,6 +62,8 @@ class DeviceServer:
         self.fang_round = 0
         # ClippedClustering's history: the norms of every client of every round so far (the clip is their median)
         self.clipped_clustering_norms = []
+        # AFA's history: the clients' reputations (made by the first defend_afa that asks for them)
+        self.afa_reputation = None
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -262,6 +265,20 @@ class DeviceServer:
         those still kept is dropped, the rest averaged, and server.py:89-90's momentum step on the result, as `defend` takes
         it.  Stateless: nothing is carried from round to round."""
         current_grads = defences.faba(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop))
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with AFA --------------------------------------------------------------------------------------
+    def defend_afa(self, xi=2.0, delta_xi=0.5, reputation=True):
+        """AFA on this round's gradients (defences.afa): the clients whose cosine with the aggregate lies too far from the
+        median dropped, round after round, the rest averaged with their reputations as weights, and server.py:89-90's momentum
+        step on the result, as `defend` takes it.  reputation=True keeps ONE `defences.AfaReputation` across the calls
+        (`afa_reputation`): a client removed often enough is blocked for good.  reputation=False: stateless, unit weights."""
+        if reputation and self.afa_reputation is None:
+            self.afa_reputation = defences.AfaReputation(self.n_users)
+        current_grads = defences.afa(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), xi=xi,
+                                     delta_xi=delta_xi, reputation=self.afa_reputation if reputation else None)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

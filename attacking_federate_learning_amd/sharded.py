@@ -179,6 +179,11 @@ class HipKernels:
         # (0 / 1 flags of the kept rows: an int32 tensor beside `like`; info): the same on every rank
         return self.engine.faba_select(dist, remove_count, power=power, on_device=True, like=like)
 
+    def afa_select(self, gram, like, weights=None, xi=2.0, delta_xi=0.5, max_rounds=None):
+        # (0 / 1 flags of the kept rows: an int32 tensor beside `like`; info): the same on every rank
+        return self.engine.afa_select(gram, weights=weights, xi=xi, delta_xi=delta_xi, max_rounds=max_rounds, on_device=True,
+                                      like=like)
+
     def manhattan_sums(self, g_local):
         return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
 
@@ -578,6 +583,27 @@ class ShardedAggregator:
         kept, info = self.kernels.faba_select(dist_m, corrupted_count, g_local)
         weights = (kept != 0).to(torch.float64)
         v = self.kernels.scaled_rows_sum(g_local, weights, weights.sum().reshape(1))
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, dict(info, kept_rows=torch.nonzero(kept).reshape(-1).cpu().numpy())
+
+    def afa(self, g_local, users_count=None, corrupted_count=None, weights=None, xi=2.0, delta_xi=0.5, max_rounds=None,
+            gather=False, total_columns=None, return_info=False):
+        """AFA (defences.afa's contract), columns layout.  ONE all-reduce: the N x N fp64 Gram of the ranks' slices, the
+        exchange the distances make.  Everything after it is replicated -- kernels.afa_select gives the same flags, weights and
+        divisor on every rank -- or local to the columns: the weighted sum of the kept rows over their weights' sum.  Returns
+        this rank's columns (gather=True: the whole vector)."""
+        import torch
+        n = g_local.shape[0]
+        gram = self.kernels.gram(g_local)
+        self._all_reduce('allreduce_gram', gram)
+        kept, info = self.kernels.afa_select(gram, g_local, weights=weights, xi=xi, delta_xi=delta_xi, max_rounds=max_rounds)
+        w = torch.ones(n, dtype=torch.float64, device=g_local.device) if weights is None else \
+            torch.as_tensor(weights, dtype=torch.float64).to(g_local.device).reshape(-1)
+        w = torch.where(kept != 0, w, torch.zeros_like(w))
+        divisor = torch.tensor([info['divisor']], dtype=torch.float64, device=g_local.device)     # (the selection's own sum)
+        v = self.kernels.scaled_rows_sum(g_local, w, divisor)
         out = self._maybe_gather(v, gather, total_columns)
         if not return_info:
             return out

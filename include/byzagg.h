@@ -916,6 +916,67 @@ int byz_faba_info(byz_ctx* ctx, int64_t* removed_rows, int64_t* kept_rows, int64
 int byz_faba_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t remove_count,
                   const float* dist_host_or_null, float* out_host, int32_t* kept_host_or_null, int32_t* order_host_or_null);
 
+/* ---- AFA, Adaptive Federated Averaging (Munoz-Gonzalez, Co & Lupu, "Byzantine-Robust Federated Machine Learning through Adaptive   */
+/* Model Averaging", arXiv:1909.05125, Algorithm 1; not in the reference) ----                                                        */
+/* The rule: every row's cosine with the weighted aggregate of the rows still kept; the rows whose cosine lies more than xi standard  */
+/* deviations from the median are removed, on the side the mean of the cosines points away from; xi grows by delta_xi and the round   */
+/* repeats until it removes nobody.  It needs no count of attackers.  With the kept set S, weights w and the Gram C (C[k][j] = g_k .   */
+/* g_j), g_k . agg is proportional to u_k = sum_{j in S} w_j C[k][j] and |agg|^2 to A = sum_{k in S} w_k u_k, and removing row q takes  */
+/* w_q C[q][k] off every u_k: the rule runs on the n x n fp64 Gram in byz_gram_dev's form (row-major, taken as symmetric: a round      */
+/* reads C[q][k] of a removed row q only) and never reads the gradients.  The selection, exactly (every operation an fp64 operation   */
+/* rounded once, no contraction; w: weights_dev_or_null, NULL: all ones):                                                             */
+/*   Row k is USABLE when C[k][k] is finite and > 0 and w[k] is finite and > 0.  Every other row is EXCLUDED before the first round:  */
+/*   never kept, never averaged, never summed over, reported apart from the removed rows (a NaN or zero gradient, a weight of 0).     */
+/*   r_k = sqrt(C[k][k]).  u_k starts as the sum of w_j * C[k][j] over the usable j in this order: 64 chains, chain l the sum, from   */
+/*   +0.0, of the products of the columns j = l, l + 64, l + 128, ... ascending (excluded columns skipped); then chain[l] += chain[l   */
+/*   + h] for every l < h, for h = 32, 16, 8, 4, 2, 1 in turn; u_k = chain[0].                                                        */
+/*   A SUM OVER THE KEPT ROWS (A, sum s, sum (s - mean)^2, the divisor) has one order: 1024 chains, chain t the sum, from +0.0, of    */
+/*   the terms of the kept rows t, t + 1024, t + 2048, ... ascending; inside every aligned group of 64 chains chain[l] += chain[l +  */
+/*   h] for l < h, h = 32, 16, 8, 4, 2, 1; then the 16 groups' sums W: W[v] += W[v + h] for v < h, h = 8, 4, 2, 1; the sum is W[0].  */
+/*   Round 1, 2, ... on the kept set S of m rows, xi = xi0 in round 1:                                                                */
+/*     A = sum_{k in S} w_k * u_k.  A not finite or <= 0: the loop ends here, `degenerate` set, S as it stands.                       */
+/*     s_k = u_k / (r_k * sqrt(A));  mean = (sum s_k) / m;  sd = sqrt((sum (s_k - mean)^2) / m)  (np.std: population form, two       */
+/*     passes);  med = np.median of the s_k: the order statistic (m - 1) / 2 for odd m, (lo + hi) / 2 of the order statistics m / 2  */
+/*     - 1 and m / 2 for even m.  The order is by value: -0.0 equals +0.0 and is read back as +0.0; an s_k that is a NaN (it cannot   */
+/*     occur for usable rows and a finite A) sorts behind +inf, and a med, sd or thr that is a NaN removes nobody.                    */
+/*     mean < med: thr = med - xi * sd and R = { k in S : s_k < thr };  otherwise: thr = med + xi * sd and R = { k in S : s_k > thr }. */
+/*     Both comparisons are strict: the median row is never removed, S never empties, and sd = 0 removes nobody.                      */
+/*     The rows of R leave S.  R empty, or the round's number = max_rounds (0: no cap): the loop ends.  Otherwise, for every q in R   */
+/*     in ascending row order and every kept k: u_k = u_k - w_q * C[q][k]; then xi = xi + delta_xi and the next round starts.         */
+/*   At most n_rows rounds, n_rows - 1 of them removing.  A matrix whose rows are all unusable (all zeros, say) is not refused:       */
+/*   everybody is excluded, no round runs, the weights are all 0 and the aggregate is the zero vector.                                */
+/* kept_dev: n_rows int32 of 0 / 1.  round_of_dev_or_null: n_rows int32, the round that removed the row, 0 for an excluded row, -1   */
+/* for a kept one.  score_dev_or_null: n_rows fp64, the last s_k the row had (+0.0 where it never had one).                           */
+/* One workgroup runs the rounds: no floating-point atomics, no grid or host synchronisation.  2 <= n_rows <= 16,384 (below:          */
+/* BYZ_E_INVALID; beyond: BYZ_E_UNSUPPORTED, decided on the argument alone); xi0 and delta_xi finite and >= 0, max_rounds >= 0        */
+/* (BYZ_E_INVALID otherwise).  Nothing is written when a call is refused.  Asynchronous on `stream`.  Timers: BYZ_K_ROW_SORT: the     */
+/* usable rows and the initial u; BYZ_K_MISC: the rounds.                                                                            */
+typedef struct byz_afa_params {
+    double xi0;          /* the first round's xi (the paper: 2) */
+    double delta_xi;     /* added to xi after every removing round (the paper: 0.5) */
+    int64_t max_rounds;  /* 0: until a round removes nobody */
+} byz_afa_params;
+int byz_afa_select_dev(byz_ctx* ctx, const double* gram_dev, int64_t n_rows, const double* weights_dev_or_null,
+                       const byz_afa_params* params, int32_t* kept_dev, int32_t* round_of_dev_or_null, double* score_dev_or_null,
+                       void* stream);
+/* The whole rule: byz_gram_dev (gram_dev_or_null == NULL; otherwise that n x n fp64 matrix REPLACES the stage), the selection above, */
+/* and byz_scaled_rows_sum_dev with the weights w_k * kept_k and their sum (the order above), an fp64 read on the device, as the      */
+/* divisor: its bits.  Nobody kept: the zero vector, never NaN.  It waits as byz_gram_dev does, and not at all when gram_dev_or_null  */
+/* is given.  out_dev (n_cols floats) must not overlap G (BYZ_E_INVALID).                                                             */
+int byz_afa_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const double* weights_dev_or_null,
+                const byz_afa_params* params, const double* gram_dev_or_null, float* out_dev, int32_t* kept_dev_or_null,
+                int32_t* round_of_dev_or_null, double* score_dev_or_null, void* stream);
+/* The last byz_afa_select_dev or byz_afa_dev on this context.  counts6: rounds run, rows kept, removed and excluded, the branch of   */
+/* the last removing round (-1: below the median, +1: above, 0: no round removed anybody), degenerate (0 / 1).  stats4: the last      */
+/* complete round's mean, med, sd and thr (0 before the first).  divisor: the kept rows' weights summed.  Any pointer may be NULL.    */
+/* Synchronises that call's stream.  BYZ_E_INVALID before the first such call.                                                        */
+int byz_afa_info(byz_ctx* ctx, int64_t* counts6, double* stats4, double* divisor);
+/* The same on a host matrix (weights_host_or_null: n_rows fp64; gram_host_or_null: n_rows x n_rows fp64; out_host: n_cols floats;    */
+/* kept_host_or_null and round_of_host_or_null: n_rows int32; score_host_or_null: n_rows fp64).  Synchronous.                         */
+int byz_afa_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const double* weights_host_or_null,
+                 const byz_afa_params* params, const double* gram_host_or_null, float* out_host, int32_t* kept_host_or_null,
+                 int32_t* round_of_host_or_null, double* score_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
