@@ -76,6 +76,11 @@ class AfaParams(ctypes.Structure):
     _fields_ = [('xi0', ctypes.c_double), ('delta_xi', ctypes.c_double), ('max_rounds', c_i64)]
 
 
+class AurorParams(ctypes.Structure):
+    """byz_auror_params: the indicative gap, the share of votes that removes a row, the sweeps' cap and the accumulate switch."""
+    _fields_ = [('alpha', ctypes.c_double), ('tau', ctypes.c_double), ('max_iter', c_i64), ('accumulate', c_i64)]
+
+
 class DncParams(ctypes.Structure):
     """byz_dnc_params: DnC's iterations, sampled columns per iteration, power iterations and rows removed per iteration."""
     _fields_ = [('n_iters', c_i64), ('sub_dim', c_i64), ('power_iters', c_i64), ('remove_count', c_i64)]
@@ -231,6 +236,11 @@ _PROTOTYPES = {
     'byz_afa_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, _P(AfaParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_afa_info': [c_vp, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)],
     'byz_afa_host': [c_vp, c_vp, c_i64, c_i64, c_vp, _P(AfaParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_auror_votes_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(AurorParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_auror_select_dev': [c_vp, c_vp, c_vp, c_vp, c_i64, _P(AurorParams), c_vp, c_vp],
+    'byz_auror_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(AurorParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_auror_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64)],
+    'byz_auror_host': [c_vp, c_vp, c_i64, c_i64, _P(AurorParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],

@@ -21,7 +21,7 @@ SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_wind
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip',
            'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip', 'nnm.hip', 'robust_lr.hip', 'topk.hip',
            'bucketing.hip', 'signguard.hip', 'noise.hip', 'flame.hip', 'manhattan.hip', 'multi_metrics.hip', 'linkage.hip',
-           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip']
+           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip', 'auror.hip']
 # median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
 # dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
 # LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a
@@ -60,6 +60,9 @@ EXTRA_FLAGS = {'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000
                'faba.hip': ['-ffp-contract=off'],
                # AFA's u, A, scores and thresholds: every product rounded before the sum or difference that takes it
                'afa.hip': ['-ffp-contract=off'],
+               # Auror: the resident tile of values lives in registers (full unroll of every loop over it); t = 0.5 * (c0 + c1) and the
+               # clusters' fp64 sums are the stated operations
+               'auror.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off'],
                # the Fang attacks: no_defense's chain, the draw A + u (B - A) and the Krum attack's distances, every product rounded
                'fang.hip': ['-ffp-contract=off'],
                # bucketing's means are no_defense's chain per bucket

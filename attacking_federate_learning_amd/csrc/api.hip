@@ -2005,6 +2005,91 @@ int byz_afa_info(byz_ctx* ctx, int64_t* counts6, double* stats4, double* divisor
     return BYZ_OK;
 }
 
+// ---- Auror (Shen, Tople & Saxena, ACSAC 2016; beyond the reference) ---------------------------------------------------------------
+namespace {
+
+int check_auror(const char* who, int64_t n, const byz_auror_params* params) {
+    if (n > kAurorMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kAurorMaxRows, (long long)n);
+        return BYZ_E_UNSUPPORTED;
+    }
+    if (n < 1) {
+        set_error("%s: at least 1 row, got %lld", who, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!(std::isfinite(params->alpha) && params->alpha >= 0.0 && params->tau >= 0.0 && params->tau <= 1.0) || params->max_iter < 1 ||
+        (params->accumulate != 0 && params->accumulate != 1)) {
+        set_error("%s: alpha = %g must be finite and >= 0, 0 <= tau = %g <= 1, max_iter = %lld >= 1, accumulate = %lld 0 or 1", who,
+                  params->alpha, params->tau, (long long)params->max_iter, (long long)params->accumulate);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+long long* as_ll(int64_t* p) { return reinterpret_cast<long long*>(p); }
+const long long* as_const_ll(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+
+}  // namespace
+
+int byz_auror_votes_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_auror_params* params,
+                        int64_t* votes, int32_t* bad, int64_t* counts, double* gap, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "auror_votes"));
+    BYZ_REQUIRE(votes && bad && counts, "auror_votes: null votes, bad flags or counts");
+    BYZ_TRY(check_auror("auror_votes", n_rows, params));
+    return launch_auror_votes(ctx, G, n_rows, n_cols, ld, params->alpha, params->max_iter, params->accumulate != 0, as_ll(votes), bad,
+                              as_ll(counts), gap, as_stream(stream));
+}
+
+int byz_auror_select_dev(byz_ctx* ctx, const int64_t* votes, const int32_t* bad, const int64_t* counts, int64_t n_rows,
+                         const byz_auror_params* params, int32_t* kept, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(votes && bad && counts && kept, "auror_select: null votes, bad flags, counts or output");
+    BYZ_TRY(check_auror("auror_select", n_rows, params));
+    AurorScratch a;
+    BYZ_TRY(auror_workspace(ctx, n_rows, &a));
+    mark(ctx, kReportAuror, as_stream(stream));
+    return launch_auror_select(ctx, a, as_const_ll(votes), bad, as_const_ll(counts), n_rows, params->tau, kept, as_stream(stream));
+}
+
+int byz_auror_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_auror_params* params,
+                  int64_t* votes, int32_t* bad, int64_t* counts, float* out, int32_t* kept, double* gap, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "auror"));
+    BYZ_REQUIRE(out, "auror: null output");
+    BYZ_TRY(check_auror("auror", n_rows, params));
+    const bool history = votes != nullptr;
+    BYZ_REQUIRE((bad != nullptr) == history && (counts != nullptr) == history, "auror: votes, bad flags and counts come together or not at all");
+    BYZ_REQUIRE(history || params->accumulate == 0, "auror: accumulate = 1 needs the caller's votes, bad flags and counts");
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "auror"));
+    hipStream_t s = as_stream(stream);
+    AurorScratch a;
+    BYZ_TRY(auror_workspace(ctx, n_rows, &a));
+    mark(ctx, kReportAuror, s);
+    long long* v = history ? as_ll(votes) : a.votes;
+    long long* c = history ? as_ll(counts) : a.counts;
+    int32_t* b = history ? bad : a.bad;
+    BYZ_TRY(launch_auror_votes(ctx, G, n_rows, n_cols, ld, params->alpha, params->max_iter, params->accumulate != 0, v, b, c, gap, s));
+    BYZ_TRY(launch_auror_select(ctx, a, v, b, c, n_rows, params->tau, kept, s));
+    return launch_scaled_rows_sum(ctx, G, n_rows, n_cols, ld, a.w, &a.info->kept_f64, out, s);
+}
+
+int byz_auror_info(byz_ctx* ctx, int64_t* indicative, int64_t* removed_rows, int64_t* kept_rows, int64_t* bad_rows, int64_t* capped_cols) {
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportAuror, "auror_info: no Auror selection on this context yet", &all));
+    const AurorReport& info = all.auror;
+    if (indicative) *indicative = info.indicative;
+    if (removed_rows) *removed_rows = info.removed;
+    if (kept_rows) *kept_rows = info.kept;
+    if (bad_rows) *bad_rows = info.bad_rows;
+    if (capped_cols) *capped_cols = info.capped;
+    return BYZ_OK;
+}
+
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
@@ -3002,6 +3087,31 @@ int byz_afa_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
     st.out(&round_of, round_of_host, n_rows);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_afa_dev(ctx, st.G(), n_rows, n_cols, n_cols, weights, params, gram, out, kept, round_of, score, st.stream()));
+    return st.finish();
+}
+
+int byz_auror_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_auror_params* params, float* out_host,
+                   int32_t* kept_host, int64_t* votes_host, int32_t* bad_host, int64_t* counts_host, double* gap_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "auror"));
+    BYZ_REQUIRE(out_host, "auror: null output");
+    BYZ_TRY(check_auror("auror", n_rows, params));
+    const bool add = params->accumulate != 0;
+    BYZ_REQUIRE(!add || (votes_host && bad_host && counts_host), "auror: accumulate = 1 needs the caller's votes, bad flags and counts");
+    HostStage st(ctx);
+    float* out;
+    double* gap;
+    int64_t *votes, *counts;
+    int32_t *kept, *bad;
+    st.out(&out, out_host, n_cols);
+    st.out(&kept, kept_host, n_rows);
+    st.out(&gap, gap_host, n_cols);
+    // the history: always on the device (the call writes all three), uploaded when it is added to
+    st.inout(&votes, add ? votes_host : nullptr, votes_host, n_rows);
+    st.inout(&bad, add ? bad_host : nullptr, bad_host, n_rows);
+    st.inout(&counts, add ? counts_host : nullptr, counts_host, 4);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_auror_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, votes, bad, counts, out, kept, gap, st.stream()));
     return st.finish();
 }
 

@@ -105,26 +105,32 @@ struct ColumnTile {
     bool real;        // the thread's column exists;
     int64_t col;      // it is clamped into the matrix otherwise, so that every thread loads and meets every barrier
 };
-// `tiles` is read by tiles narrower than 64 columns only
+// `tiles` is read by tiles narrower than 64 columns only.  block: the workgroup's place in tile_grid's grid -- blockIdx.x, or the
+// places blockIdx.x, blockIdx.x + gridDim.x, ... of a workgroup that walks several tiles (auror.hip; a grid that is a multiple of
+// eight keeps block % 8, the XCD's label, the same at every step)
 template <int COLS>
-__device__ __forceinline__ ColumnTile column_tile(int64_t tiles, int64_t n_cols) {
+__device__ __forceinline__ ColumnTile column_tile(int64_t block, int64_t tiles, int64_t n_cols) {
     const int tid = threadIdx.x;
     ColumnTile t;
     t.tx = tid % COLS;
     t.ty = tid / COLS;
-    int64_t tile = blockIdx.x;
+    int64_t tile = block;
     t.none = false;
     if constexpr (COLS < 64) {
         // a row segment of a narrow tile is a part of a 128-byte line: workgroups b and b + 8 (one XCD, dispatched together) take
         // neighbouring tiles so that the parts of a line meet in one L2
         const int64_t per = (tiles + 7) / 8;
-        tile = static_cast<int64_t>(blockIdx.x % 8) * per + blockIdx.x / 8;
+        tile = (block % 8) * per + block / 8;
         t.none = tile >= tiles;
     }
     const int64_t col_raw = tile * COLS + t.tx;
     t.real = col_raw < n_cols;
     t.col = t.real ? col_raw : n_cols - 1;
     return t;
+}
+template <int COLS>
+__device__ __forceinline__ ColumnTile column_tile(int64_t tiles, int64_t n_cols) {
+    return column_tile<COLS>(static_cast<int64_t>(blockIdx.x), tiles, n_cols);
 }
 
 // ---- the rows -------------------------------------------------------------------------------------------------------------------

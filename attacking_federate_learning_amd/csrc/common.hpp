@@ -166,6 +166,8 @@ struct byz_ctx {
                                  // removal order, the kept flags, the weights
     byz::Buffer afa;             // AFA, carved into AfaScratch's arrays (afa.hip: afa_workspace): the rows' u, r and weights, the kept
                                  // flags, the rounds of removal
+    byz::Buffer auror;           // Auror, carved into AurorScratch's arrays (auror.hip: auror_workspace): the weights, and the votes,
+                                 // bad flags and counts of a call that carries no history
     byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
                                  // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
     // the last Krum attack's values (byz_fang_krum_info reports them; last[kReportFangKrum] says whether there was one)
@@ -520,6 +522,21 @@ int afa_workspace(byz_ctx* ctx, int64_t n, AfaScratch* out);
 int launch_afa_select(byz_ctx* ctx, const AfaScratch& t, const double* gram, int64_t n, const double* weights, double xi0,
                       double delta_xi, int64_t max_rounds, int32_t* kept_out, int32_t* round_of_out, double* score_out,
                       hipStream_t stream);
+// auror.hip: Auror's per-column 2-means, its votes and the selection on them.  The scalars of a call: DeviceScalars::auror.
+constexpr int64_t kAurorMaxRows = 16384;     // a workgroup's vote counters: one int32 and one byte a row in LDS
+struct AurorScratch {
+    AurorReport* info;
+    double* w;                       // n: the aggregate's 0 / 1 weights
+    long long *votes, *counts;       // n and 4: byz_auror_dev's own when the caller carries no history
+    int32_t* bad;                    // n
+};
+int auror_workspace(byz_ctx* ctx, int64_t n, AurorScratch* out);
+// every column clustered, votes (n), bad (n) and counts (4) overwritten or (accumulate) added to, gap (n_cols, optional) written
+int launch_auror_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, double alpha, int64_t max_iter,
+                       bool accumulate, long long* votes, int32_t* bad, long long* counts, double* gap, hipStream_t stream);
+// the flags into kept_out (optional) and t.w, the counts into t.info
+int launch_auror_select(byz_ctx* ctx, const AurorScratch& t, const long long* votes, const int32_t* bad, const long long* counts,
+                        int64_t n, double tau, int32_t* kept_out, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

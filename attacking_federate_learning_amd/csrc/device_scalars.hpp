@@ -93,6 +93,13 @@ struct AfaReport {
     double mean, med, sd, thr;       // the last complete round's statistics (0 before the first)
     double divisor;                  // the kept rows' weights summed: the divisor of the sum
 };
+struct AurorReport {                 // byz_auror_select_dev and byz_auror_dev: what the selection read and decided
+    long long indicative, clustered; // counts[0] and counts[1] as the selection found them (accumulated: over the rounds)
+    long long capped;                // counts[2]: the columns max_iter stopped
+    int32_t removed, kept;           // the rows removed (bad rows included) and kept: they add up to n
+    int32_t bad_rows, pad;           // the rows with a non-finite value
+    double kept_f64;                 // the divisor of the sum
+};
 
 struct DeviceScalars {
     CoreScalars core;
@@ -110,6 +117,7 @@ struct DeviceScalars {
     LinkageInfo linkage;
     FabaReport faba;
     AfaReport afa;
+    AurorReport auror;
 };
 
 // What a read-back as bytes, and a 64-bit store or atomic of a kernel, rely on.  No member is padded by the compiler: the sizes
@@ -119,7 +127,7 @@ static_assert(sizeof(CoreScalars) % sizeof(int32_t) == 0 && sizeof(DeviceScalars
 static_assert(sizeof(DeviceScalars) == sizeof(CoreScalars) + sizeof(GeomedReport) + sizeof(DncReport) + sizeof(CclipReport) +
                                            sizeof(FltrustReport) + sizeof(NnmReport) + sizeof(RlrReport) + sizeof(SgReport) +
                                            sizeof(TopkReport) + sizeof(WeakDpReport) + sizeof(FlameInfo) + sizeof(MmInfo) +
-                                           sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport),
+                                           sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport) + sizeof(AurorReport),
               "no padding between the reports");
 #define BYZ_AT(member) offsetof(DeviceScalars, member)
 constexpr size_t kEightByteFields[] = {
@@ -127,7 +135,8 @@ constexpr size_t kEightByteFields[] = {
     BYZ_AT(sg.kept_f64), BYZ_AT(topk.selected), BYZ_AT(topk.ties), BYZ_AT(topk.taken), BYZ_AT(topk.key), BYZ_AT(weak_dp.clip),
     BYZ_AT(flame.admitted_f64), BYZ_AT(flame.clip), BYZ_AT(mm.det), BYZ_AT(linkage.top_height), BYZ_AT(linkage.second_height),
     BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64),
-    BYZ_AT(afa.mean), BYZ_AT(afa.med), BYZ_AT(afa.sd), BYZ_AT(afa.thr), BYZ_AT(afa.divisor)};
+    BYZ_AT(afa.mean), BYZ_AT(afa.med), BYZ_AT(afa.sd), BYZ_AT(afa.thr), BYZ_AT(afa.divisor),
+    BYZ_AT(auror.indicative), BYZ_AT(auror.clustered), BYZ_AT(auror.capped), BYZ_AT(auror.kept_f64)};
 #undef BYZ_AT
 constexpr bool eight_byte_fields_aligned() {
     for (size_t at : kEightByteFields)
@@ -137,11 +146,12 @@ constexpr bool eight_byte_fields_aligned() {
 static_assert(eight_byte_fields_aligned(), "every double and 64-bit counter sits at an 8-byte offset");
 
 // the reports an info call reads; byz_ctx::last[kind]: the stream of the last call that wrote it, and whether there was one
-// (kReportAfa stands in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of kReportCount; the
-// kinds index byz_ctx::last and nothing else, so their numbers are free)
+// (kReportAuror and kReportAfa stand in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of
+// kReportCount; the kinds index byz_ctx::last and nothing else, so their numbers are free)
 enum ReportKind {
     kReportGeomed, kReportDnc, kReportCclip, kReportFltrust, kReportNnm, kReportRlr, kReportSignguard, kReportTopk, kReportWeakDp,
-    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportAfa, kReportFaba, kReportCount
+    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportAuror, kReportAfa,
+    kReportFaba, kReportCount
 };
 struct LastCall { hipStream_t stream = nullptr; bool ran = false; };
 

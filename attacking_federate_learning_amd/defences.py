@@ -446,6 +446,62 @@ def afa(users_grads, users_count, corrupted_count, weights=None, xi=2.0, delta_x
     return out
 
 
+class AurorHistory:
+    """Auror's evidence carried over rounds (the paper gathers it over several): n int64 votes, n int32 bad flags and the 4
+    int64 counts {indicative, clustered, capped, 0}, on the device, which every `auror(..., history=)` call adds to in place
+    before it selects.  A client that once sent a non-finite value stays bad until `reset()`."""
+
+    def __init__(self, n):
+        engine = get_engine()
+        self.n = int(n)
+        self.votes = engine.empty((self.n,), np.int64)
+        self.bad = engine.empty((self.n,), np.int32)
+        self.counts = engine.empty((4,), np.int64)
+        self.rounds = 0
+        self.reset()
+
+    def reset(self):
+        """Forget every round: zero votes, flags and counts."""
+        self.votes.upload(np.zeros(self.n, dtype=np.int64))
+        self.bad.upload(np.zeros(self.n, dtype=np.int32))
+        self.counts.upload(np.zeros(4, dtype=np.int64))
+        self.rounds = 0
+
+    def numpy(self):
+        """(votes, bad, counts) as host arrays."""
+        return self.votes.numpy(), self.bad.numpy(), self.counts.numpy()
+
+
+def auror(users_grads, users_count, corrupted_count, alpha, tau=0.5, max_iter=32, history=None, return_info=False):
+    """Auror (Shen, Tople and Saxena, ACSAC 2016; not in the reference): every coordinate's values over the clients are split
+    into two clusters (2-means from the smallest and largest value), a coordinate whose two centres end more than `alpha`
+    apart is indicative, and a client that sits in the smaller cluster of more than `tau` of the indicative coordinates is
+    dropped; the rest are averaged.  The classic defence against TARGETED poisoning: a label flip or a backdoor moves a few
+    coordinates a lot and leaves the rest alone.  The rule is column-local and reads the matrix once (up to 4096 clients).
+    What it does not do: it is no answer to the drift attack, and `alpha` has NO default, because a unimodal coordinate of
+    spread sigma splits into centres about 1.6 sigma apart -- with alpha below that every coordinate is indicative and
+    honest clients are dropped (an "A Little Is Enough" matrix with alpha = 1.0 sigma lost 759 of 760 honest rows).  Choose
+    it from `Engine.auror_votes(..., return_gap=True)`.  It needs NO count of attackers: corrupted_count is accepted for the
+    common signature and not used.  A client with a NaN or infinite value is dropped.  `history`: an `AurorHistory`; this
+    round's votes are added to it and the selection reads the sums (device-resident matrices; a host matrix is uploaded).
+    numpy in -> numpy out, device-resident in -> device-resident out.  return_info=True returns (vector, {kept_rows, votes,
+    bad, counts, gap, indicative, removed, kept, bad_rows, capped_cols}).  Usable as `then=` of `nnm`, `bucketing`,
+    `robust_lr`, `sparsefed` and `weak_dp` (pass alpha= beside it).  Not one of the `defend` keys: the reference's main.py
+    offers only those four."""
+    engine = get_engine()
+    if history is None:
+        return engine.auror(users_grads, users_count, corrupted_count, alpha=alpha, tau=tau, max_iter=max_iter, return_info=return_info)
+    matrix, was_host = engine.stage(users_grads)
+    if matrix.shape[0] != history.n:
+        raise ValueError('auror: the history holds %d clients, the gradients %d' % (history.n, matrix.shape[0]))
+    got = engine.auror(matrix, users_count, corrupted_count, alpha=alpha, tau=tau, max_iter=max_iter, votes=history.votes,
+                       bad=history.bad, counts=history.counts, return_info=return_info)
+    history.rounds += 1
+    if not was_host:
+        return got
+    return (got[0].numpy(), got[1]) if return_info else got.numpy()
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -227,6 +227,12 @@ def _i32(what):
             'length': 'expected %%(n)d %s, got %%(got)d' % what}
 
 
+def _ints(what):
+    """int32 or int64 arrays used where they are (Auror's votes, bad flags and counts)."""
+    return dict(_i32(what), buffer='a DeviceBuffer of %s must hold %%(n)d integers of the width the call states' % what,
+                layout='device %s must be contiguous and of the width the call states' % what)
+
+
 def _lists(what):
     return {'buffer': 'a DeviceBuffer of neighbour lists must hold int32', 'kind': 'neighbour lists must hold integers, got %(dtype)s',
             'device': 'the neighbour lists live on %(device)s, this engine drives cuda:%(engine)d',
@@ -2115,6 +2121,124 @@ class Engine:
         round_of = np.asarray(round_of)
         info.update(kept_rows=np.flatnonzero(flags).astype(np.int64), excluded_rows=np.flatnonzero(round_of == 0).astype(np.int64),
                     round_of=round_of, score=np.asarray(score))
+        return out, info
+
+    # ---- Auror (Shen, Tople & Saxena, ACSAC 2016; not in the reference) ----
+    @staticmethod
+    def _auror_params(n, alpha, tau=0.5, max_iter=32, accumulate=False):
+        """byz_auror_params, checked as the library checks them (the refusals that need no GPU)."""
+        n = int(n)
+        if n > 16384:
+            raise NotImplementedError('auror: at most 16384 rows, got %d' % n)
+        if n < 1:
+            raise ValueError('auror: at least 1 row, got %d' % n)
+        alpha, tau, max_iter = float(alpha), float(tau), int(max_iter)
+        if not (np.isfinite(alpha) and alpha >= 0.0 and 0.0 <= tau <= 1.0) or max_iter < 1:
+            raise ValueError('auror: alpha = %r must be finite and >= 0, 0 <= tau = %r <= 1, max_iter = %r >= 1' % (alpha, tau, max_iter))
+        return _native.AurorParams(alpha, tau, max_iter, 1 if accumulate else 0)
+
+    def auror_info(self):
+        """{indicative, removed, kept, bad_rows, capped_cols} of the last auror_select or auror on this engine (synchronises):
+        the indicative columns the selection read (accumulated: over the rounds), the rows removed (bad rows included) and
+        kept, the rows with a non-finite value, the columns max_iter stopped."""
+        return dict(zip(('indicative', 'removed', 'kept', 'bad_rows', 'capped_cols'),
+                        self._read(self.lib.byz_auror_info, [ctypes.c_int64] * 5)))
+
+    def _auror_history(self, c, n, votes, bad, counts):
+        """The caller's votes, bad flags and counts as they lie on the device (all three or none), or fresh arrays."""
+        given = [v is not None for v in (votes, bad, counts)]
+        if any(given) and not all(given):
+            raise ValueError('auror: votes, bad and counts come together or not at all')
+        if not given[0]:
+            return c.out(n, np.int64), c.out(n, np.int32), c.out(4, np.int64), False
+        ops = []
+        for v, dtype, count, what in ((votes, np.int64, n, 'votes'), (bad, np.int32, n, 'bad flags'), (counts, np.int64, 4, 'counts')):
+            if not _is_device(v):
+                raise ValueError('auror: the %s to add to must be device-resident' % what)
+            op = c.operand(v, dtype, _ints(what), count, convert=False)
+            ops.append((v, op.ptr))
+        return ops[0], ops[1], ops[2], True
+
+    def auror_votes(self, g, alpha, max_iter=32, votes=None, bad=None, counts=None, return_gap=False):
+        """Auror's votes on a device-resident or host matrix: every column's finite values split in two by Lloyd's 2-means from
+        (min, max), a column whose centres end more than alpha apart indicative, one vote for every row in the smaller cluster
+        of an indicative column (include/byzagg.h states the rule).  Returns (votes int64[n], bad int32[n], counts int64[4] =
+        {indicative, clustered, capped columns, 0}) and, return_gap=True, gap float64[D] (the centres' final distance, 0
+        where a column was not clustered: what alpha is chosen from).  votes=, bad=, counts= (device-resident, all three): an
+        earlier call's, which this call adds to in place.  Device arrays for a device matrix, numpy for a host one."""
+        with _Call(self) as c:
+            m = c.matrix(g)
+            (v, vptr), (b, bptr), (k, kptr), add = self._auror_history(c, m.rows, votes, bad, counts)
+            params = self._auror_params(m.rows, alpha, 0.5, max_iter, accumulate=add)
+            gap, gptr = c.out(m.cols, np.float64, want=return_gap)
+            c.run(self.lib.byz_auror_votes_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, ctypes.byref(params), vptr, bptr, kptr, gptr,
+                                               c.stream))
+            return c.result((v, b, k, gap) if return_gap else (v, b, k))
+
+    def auror_select(self, votes, bad, counts, tau=0.5, on_device=False, like=None):
+        """Auror's selection: row i is removed iff it is bad, or counts[0] > 0 and votes[i] > tau * counts[0].  Returns (rows,
+        info): the kept rows ascending (on_device=True: the 0 / 1 int32 flags instead, as a DeviceBuffer, or a torch tensor
+        beside `like`) and auror_info()'s fields."""
+        with _Call(self) as c:
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            b = c.operand(bad, np.int32, _ints('bad flags'))
+            n = b.size
+            params = self._auror_params(n, 0.0, tau)
+            v = c.operand(votes, np.int64, _ints('votes'), n)
+            k = c.operand(counts, np.int64, _ints('counts'), 4)
+            flags, fptr = c.out(n, np.int32)
+            c.run(self.lib.byz_auror_select_dev(self.ctx, v.ptr, b.ptr, k.ptr, n, ctypes.byref(params), fptr, c.stream))
+            info = self.auror_info()
+        if not on_device:
+            flags = np.flatnonzero(flags.numpy()).astype(np.int64)
+        return flags, info
+
+    def auror(self, g, users_count=None, corrupted_count=None, alpha=None, tau=0.5, max_iter=32, votes=None, bad=None, counts=None,
+              return_info=False):
+        """Auror in one library call: auror_votes, auror_select and the mean of the kept rows: scaled_rows_sum's bits with the
+        0 / 1 flags as weights and the kept count, read on the device, as the divisor.  Nobody kept: the zero vector.
+        users_count and corrupted_count are accepted and unused: the rule needs no count.  alpha has no default (a value below
+        about 1.6 standard deviations of an honest column makes every column indicative).  votes=, bad=, counts=
+        (device-resident, all three): the history this call adds to in place (device matrices only).  return_info=True also
+        returns auror_info()'s fields with kept_rows (ascending), votes, bad, counts and gap as host arrays."""
+        if alpha is None:
+            raise ValueError('auror: alpha has no default; choose it from auror_votes(..., return_gap=True)')
+        dm = self._device_matrix(g)
+        n = dm.rows if dm is not None else self._host_matrix(g).shape[0]
+        history = votes is not None or bad is not None or counts is not None
+        params = self._auror_params(n, alpha, tau, max_iter, accumulate=history)
+        if dm is None:
+            if history:
+                raise ValueError('auror: a history lives on the device; pass a device-resident matrix with it')
+            h = self._host_matrix(g)
+            d = h.shape[1]
+            out = np.empty(d, dtype=np.float32)
+            flags, v, b = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+            k, gap = np.zeros(4, dtype=np.int64), np.zeros(d, dtype=np.float64)
+            _check(self.lib.byz_auror_host(self.ctx, _hp(h), n, d, ctypes.byref(params), _hp(out), _hp(flags), _hp(v), _hp(b), _hp(k),
+                                           _hp(gap)))
+        else:
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                out, optr = c.out(dm.cols)
+                if history:
+                    (v, vptr), (b, bptr), (k, kptr), _ = self._auror_history(c, n, votes, bad, counts)
+                elif return_info:
+                    (v, vptr), (b, bptr), (k, kptr) = c.out(n, np.int64), c.out(n, np.int32), c.out(4, np.int64)
+                else:
+                    (v, vptr), (b, bptr), (k, kptr) = (None, None), (None, None), (None, None)
+                flags, fptr = c.out(n, np.int32, want=return_info)
+                gap, gptr = c.out(dm.cols, np.float64, want=return_info)
+                c.run(self.lib.byz_auror_dev(self.ctx, dm.ptr, dm.rows, dm.cols, dm.ld, ctypes.byref(params), vptr, bptr, kptr, optr,
+                                             fptr, gptr, c.stream))
+                if return_info:
+                    flags, v, b, k, gap = (_to_host(x) if _is_torch(x) else x.numpy() for x in (flags, v, b, k, gap))
+        if not return_info:
+            return out
+        info = self.auror_info()
+        info.update(kept_rows=np.flatnonzero(flags).astype(np.int64), votes=np.asarray(v), bad=np.asarray(b), counts=np.asarray(k),
+                    gap=np.asarray(gap))
         return out, info
 
     # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----

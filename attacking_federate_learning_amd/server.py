@@ -23,6 +23,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_clipped_clustering(method) the same step with ClippedClustering: the larger of two average-linkage clusters, clipped
     defend_faba()                     the same step with FABA: the clients farthest from the running mean dropped one by one
     defend_afa(xi, delta_xi)          the same step with AFA: cosine outliers dropped round after round, reputations kept across rounds
+    defend_auror(alpha, tau)          the same step with Auror: per-coordinate 2-means, suspicion votes kept across rounds
     defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
@@ -64,6 +65,9 @@ class DeviceServer:
         self.clipped_clustering_norms = []
         # AFA's history: the clients' reputations (made by the first defend_afa that asks for them)
         self.afa_reputation = None
+        # Auror's history: the clients' votes and the indicative count summed over the rounds (made by the first defend_auror
+        # that asks for it)
+        self.auror_history = None
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -279,6 +283,21 @@ class DeviceServer:
             self.afa_reputation = defences.AfaReputation(self.n_users)
         current_grads = defences.afa(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), xi=xi,
                                      delta_xi=delta_xi, reputation=self.afa_reputation if reputation else None)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with Auror ------------------------------------------------------------------------------------
+    def defend_auror(self, alpha, tau=0.5, max_iter=32, history=True):
+        """Auror on this round's gradients (defences.auror): every coordinate's values split in two, the clients in the smaller
+        cluster of more than tau of the coordinates whose centres lie more than alpha apart dropped, the rest averaged, and
+        server.py:89-90's momentum step on the result, as `defend` takes it.  alpha has no default (defences.auror says why).
+        history=True keeps ONE `defences.AurorHistory` across the calls (`auror_history`), as the paper gathers its evidence
+        over several rounds; history=False: stateless."""
+        if history and self.auror_history is None:
+            self.auror_history = defences.AurorHistory(self.n_users)
+        current_grads = defences.auror(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), alpha, tau=tau,
+                                       max_iter=max_iter, history=self.auror_history if history else None)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -184,6 +184,14 @@ class HipKernels:
         return self.engine.afa_select(gram, weights=weights, xi=xi, delta_xi=delta_xi, max_rounds=max_rounds, on_device=True,
                                       like=like)
 
+    def auror_votes(self, g_local, alpha, max_iter=32):
+        # (votes int64, bad int32, counts int64[4]) of this rank's columns, on the device: additive over the column slices
+        return self.engine.auror_votes(g_local, alpha, max_iter=max_iter)
+
+    def auror_select(self, votes, bad, counts, like, tau=0.5):
+        # (0 / 1 flags of the kept rows: an int32 tensor beside `like`; info): the same on every rank
+        return self.engine.auror_select(votes, bad, counts, tau=tau, on_device=True, like=like)
+
     def manhattan_sums(self, g_local):
         return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
 
@@ -608,6 +616,29 @@ class ShardedAggregator:
         if not return_info:
             return out
         return out, dict(info, kept_rows=torch.nonzero(kept).reshape(-1).cpu().numpy())
+
+    def auror(self, g_local, users_count=None, corrupted_count=None, alpha=None, tau=0.5, max_iter=32, gather=False,
+              total_columns=None, return_info=False):
+        """Auror (defences.auror's contract), columns layout.  The vote is column-local, so every rank makes the single-GPU
+        call on its own slice; ONE all-reduce of the n votes, n bad flags and 4 counts as int64 (2 n + 4 words) makes them the
+        whole matrix's.  The selection is then replicated -- kernels.auror_select gives the same flags on every rank -- and
+        the sum of the kept rows over their count is local to the columns.  Returns this rank's columns (gather=True: the
+        whole vector)."""
+        import torch
+        if alpha is None:
+            raise ValueError('auror: alpha has no default')
+        n = g_local.shape[0]
+        votes, bad, counts = self.kernels.auror_votes(g_local, alpha, max_iter=max_iter)
+        packed = torch.cat([votes.reshape(-1), bad.reshape(-1).to(torch.int64), counts.reshape(-1)])
+        self._all_reduce('allreduce_auror_votes', packed)
+        votes, bad, counts = packed[:n], (packed[n:2 * n] != 0).to(torch.int32), packed[2 * n:]
+        kept, info = self.kernels.auror_select(votes, bad, counts, g_local, tau=tau)
+        weights = (kept != 0).to(torch.float64)
+        v = self.kernels.scaled_rows_sum(g_local, weights, weights.sum().reshape(1))
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, dict(info, kept_rows=torch.nonzero(kept).reshape(-1).cpu().numpy(), votes=votes.cpu().numpy())
 
     def nnm(self, g_local, users_count, corrupted_count, return_neighbours=False):
         """Nearest-neighbour mixing, columns layout: the distances' one all-reduce and nothing more; the neighbour lists are

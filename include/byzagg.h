@@ -977,6 +977,64 @@ int byz_afa_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_co
                  const byz_afa_params* params, const double* gram_host_or_null, float* out_host, int32_t* kept_host_or_null,
                  int32_t* round_of_host_or_null, double* score_host_or_null);
 
+/* ---- Auror (Shen, Tople & Saxena, "AUROR: Defending Against Poisoning Attacks in Collaborative Deep Learning Systems", ACSAC 2016;  */
+/* not in the reference) ----                                                                                                         */
+/* The rule is column-local: every column's n values are split into two clusters, a column whose two centres end far apart is         */
+/* INDICATIVE, and a row that sits in the smaller cluster of most indicative columns is removed.  It is the classic answer to         */
+/* targeted poisoning (a label flip, a backdoor), which moves a few coordinates a lot.  It is NO answer to the drift attack: in a     */
+/* unimodal column of spread sigma the two centres end about 1.6 sigma apart, so with alpha below that every column is indicative and  */
+/* honest rows are removed.  alpha therefore has no default: byz_auror_votes_dev's gap output is there to choose it from.             */
+/* The votes, exactly.  Per column, with x the FINITE values of the column and m their count (fp64 operations rounded once each):      */
+/*   A non-finite value abstains in its column, and its row is BAD; the row's finite values still take part in their own columns.     */
+/*   m < 2 or min == max (-0.0 == +0.0): the column is not clustered, its gap is 0, it is not indicative.                              */
+/*   Otherwise c0 = (double)min, c1 = (double)max, and sweep k = 1, 2, ..., max_iter:                                                  */
+/*     t = 0.5 * (c0 + c1).  Cluster 1 is the values with (double)x > t; a value equal to t is in cluster 0.  m1 = the count of       */
+/*     cluster 1, S1 and S0 the fp64 sums of the two clusters, c1 = S1 / m1, c0 = S0 / (m - m1).  min <= t < max throughout, so        */
+/*     neither cluster is empty.  The column stops after a sweep k >= 2 whose m1 equals the previous sweep's (an integer: the order   */
+/*     of the sums has no say in it), and after sweep max_iter in any case; stopped there WITHOUT that equality it is CAPPED.          */
+/*     The order of a sum: the rows of one row group (rows g, g + RG, g + 2 RG, ... with RG the launch geometry's row groups: 16 up   */
+/*     to 256 rows and beyond 4096, 32 up to 1024, 64 up to 4096) ascending from +0.0, then the row groups ascending from +0.0.        */
+/*   The final assignment is the last sweep's (its t, its m1), gap = c1 - c0 its centres' distance.  The column is indicative iff      */
+/*   gap > alpha.  In an indicative column the cluster with FEWER members is suspicious (equal counts: nobody), and every row in it    */
+/*   gets one vote.                                                                                                                   */
+/* votes_dev: n_rows int64.  bad_dev: n_rows int32 of 0 / 1.  counts_dev: 4 int64 = {indicative, clustered, capped columns, 0}.        */
+/* gap_dev_or_null: n_cols fp64.  accumulate = 0 overwrites votes, bad and counts; accumulate = 1 adds to the votes and counts and     */
+/* keeps a bad flag that is set (the paper gathers its evidence over several rounds): the caller's arrays then hold an earlier call's  */
+/* results for the same n_rows, or zeros.  gap is always overwritten.                                                                 */
+/* 1 <= n_rows <= 16,384 (beyond: BYZ_E_UNSUPPORTED, decided on the argument alone); alpha finite and >= 0, 0 <= tau <= 1,             */
+/* max_iter >= 1, accumulate 0 or 1 (BYZ_E_INVALID otherwise, NaN included).  Nothing is written when a call is refused.               */
+/* One read of the matrix up to 4096 rows (a workgroup's columns stay in registers over the sweeps), one read a sweep beyond.  Integer */
+/* atomics only, one 64-bit add a row and workgroup at most.  Asynchronous on `stream`.  Timer: BYZ_K_MISC.                            */
+typedef struct byz_auror_params {
+    double alpha;        /* a column is indicative when its centres end more than this apart */
+    double tau;          /* a row is removed when it has more than tau * indicative votes (the paper: 0.5) */
+    int64_t max_iter;    /* sweeps a column at most (32 covers Gaussian columns of up to 4097 rows) */
+    int64_t accumulate;  /* 1: add to votes, bad and counts */
+} byz_auror_params;
+int byz_auror_votes_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_auror_params* params,
+                        int64_t* votes_dev, int32_t* bad_dev, int64_t* counts_dev, double* gap_dev_or_null, void* stream);
+/* The selection: row i is removed iff bad[i] != 0, or counts[0] > 0 and (double)votes[i] > tau * (double)counts[0].  With no          */
+/* indicative column nobody is removed for votes.  kept_dev: n_rows int32 of 0 / 1.  One workgroup.  Asynchronous on `stream`.         */
+int byz_auror_select_dev(byz_ctx* ctx, const int64_t* votes_dev, const int32_t* bad_dev, const int64_t* counts_dev, int64_t n_rows,
+                         const byz_auror_params* params, int32_t* kept_dev, void* stream);
+/* The whole rule: the votes, the selection, and byz_scaled_rows_sum_dev with the 0 / 1 flags as fp64 weights and the kept count, an   */
+/* fp64 read on the device, as the divisor: its bits.  Nobody kept: the zero vector, never NaN.  votes_dev, bad_dev and counts_dev     */
+/* are the caller's history, all three or none (none: the context's own, and accumulate must be 0).  out_dev (n_cols floats) must not  */
+/* overlap G (BYZ_E_INVALID).  Nothing synchronises with the host.                                                                    */
+int byz_auror_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const byz_auror_params* params,
+                  int64_t* votes_dev_or_null, int32_t* bad_dev_or_null, int64_t* counts_dev_or_null, float* out_dev,
+                  int32_t* kept_dev_or_null, double* gap_dev_or_null, void* stream);
+/* The last byz_auror_select_dev or byz_auror_dev on this context: the indicative columns the selection read (accumulated: over the    */
+/* rounds), the rows removed (bad rows included) and kept, the bad rows, the capped columns.  Any pointer may be NULL.  Synchronises   */
+/* that call's stream: the only Auror call that does.  BYZ_E_INVALID before the first such call.                                       */
+int byz_auror_info(byz_ctx* ctx, int64_t* indicative, int64_t* removed_rows, int64_t* kept_rows, int64_t* bad_rows, int64_t* capped_cols);
+/* The same on a host matrix (out_host: n_cols floats; kept_host_or_null: n_rows int32; votes_host_or_null: n_rows int64;              */
+/* bad_host_or_null: n_rows int32; counts_host_or_null: 4 int64; gap_host_or_null: n_cols fp64).  With accumulate = 1 the three        */
+/* history arrays are read and written, and all three are required (BYZ_E_INVALID otherwise).  Synchronous.                           */
+int byz_auror_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, const byz_auror_params* params, float* out_host,
+                   int32_t* kept_host_or_null, int64_t* votes_host_or_null, int32_t* bad_host_or_null, int64_t* counts_host_or_null,
+                   double* gap_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
