@@ -260,6 +260,7 @@ _PROTOTYPES = {
     'byz_timing_read': [c_vp, c_int, _P(ctypes.c_double), _P(c_i64)],
     'byz_kernel_name': [c_int],
     'byz_selftest_lane_exchange_dev': [c_vp, c_vp, _P(c_i32), c_vp],
+    'byz_selftest_owner_loop_dev': [c_vp, c_vp, _P(c_i32), c_vp],
     'byz_gram_unit_table': [c_i64, _P(c_i32), c_i64, _P(c_i64)],
 }
 _RESTYPES = {'byz_last_error': ctypes.c_char_p, 'byz_kernel_name': ctypes.c_char_p, 'byz_ctx_destroy': None}

@@ -9,9 +9,9 @@
 //   afa_rows_kernel   one thread a row: the weight a row counts with (0: the row is excluded) and r_k = sqrt(C[k][k]).
 //   afa_init_kernel   one wave a row: u_k over the usable columns.  Lane l adds the products of the columns l, l + 64, ... in
 //                     ascending order (64 interleaved chains), the chains fold 32, 16, 8, 4, 2, 1.
-//   afa_loop_kernel   ONE workgroup of 1024 threads, thread t owns the rows t + 1024 s (s < 16): their u in registers (every
-//                     index static), a bit mask of those still kept, their s in LDS (128 KiB).  A round is three sums
-//                     over the workgroup in one stated order (afa_block_sum), the exact median of the s by an 8-bit radix walk
+//   afa_loop_kernel   ONE workgroup on owner_loop.hpp's scheme: the owned rows' u in registers (every index static), a bit mask
+//                     of those still kept, their s in LDS (128 KiB).  A round is three sums over the workgroup in one stated
+//                     order (afa_block_sum: a block exchange), the exact median of the s by an 8-bit radix walk
 //                     over their ordered keys (a 256-bin LDS histogram, integer LDS atomics only, one barrier a digit), the
 //                     removals, and the update: the removed rows of a block of 1024 rows are listed in LDS in ascending
 //                     order, and every thread then takes them off its u four row reads at a time: the reads of a batch are
@@ -27,13 +27,8 @@ namespace byz {
 namespace {
 
 constexpr int kAfaInitThreads = 256;          // four rows a workgroup, one wave each
-constexpr int kAfaThreads = 1024;
-constexpr int kAfaWaves = kAfaThreads / 64;
-constexpr int kAfaSlots = 16;                 // rows a thread owns: kAfaThreads * kAfaSlots = kAfaMaxRows
 constexpr int kAfaBatch = 4;                  // row reads a thread keeps in flight in the update (6 and 8 spill scalars)
 constexpr int kAfaDigits = 256;               // the radix walk's digit: 8 bits, 8 digits a key
-static_assert(kAfaThreads * kAfaSlots == kAfaMaxRows, "every row has an owner");
-static_assert(kAfaWaves == 16, "the waves' sums fold 8, 4, 2, 1");
 
 __global__ void afa_rows_kernel(const double* __restrict__ C, const double* __restrict__ w_in, int n, double* __restrict__ w,
                                 double* __restrict__ r) {
@@ -63,19 +58,13 @@ __global__ __launch_bounds__(kAfaInitThreads) void afa_init_kernel(const double*
 
 // The one order of a sum over the workgroup: thread t's chain (the caller's: its rows ascending from +0.0), the 64 chains of a
 // wave folded 32, 16, 8, 4, 2, 1, the 16 waves' sums folded 8, 4, 2, 1.  Every thread gets the same bits (an exchange adds
-// the same two numbers in both lanes).  One barrier a call: two buffers taken in turn, so that a call's reads are behind the
-// next call's barrier before the buffer is written again.
-__device__ __forceinline__ double afa_block_sum(double chain, double (*buf)[kAfaWaves], int& turn) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* slots = buf[turn & 1];
-    ++turn;
-    chain = lanes::wave_sum_shfl(chain);
-    if (lane == 0) slots[wave] = chain;
-    __syncthreads();
-    double v = slots[lane & (kAfaWaves - 1)];
+// the same two numbers in both lanes).  One barrier a call: owner_loop.hpp's block exchange.
+__device__ __forceinline__ double afa_block_sum(double chain, ExchangeBuf<double>& buf, int& turn) {
+    return block_exchange(lanes::wave_sum_shfl(chain), buf, turn, threadIdx.x & 63, threadIdx.x >> 6, [](double v) {
 #pragma unroll
-    for (int m = kAfaWaves / 2; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
+        for (int m = kOwnerWaves / 2; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
+        return v;
+    });
 }
 __device__ __forceinline__ int afa_block_count(int mine, int* slots) {     // (two barriers: not on a round's critical path twice)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -83,9 +72,9 @@ __device__ __forceinline__ int afa_block_count(int mine, int* slots) {     // (t
     __syncthreads();
     if (lane == 0) slots[wave] = mine;
     __syncthreads();
-    int v = slots[lane & (kAfaWaves - 1)];
+    int v = slots[lane & (kOwnerWaves - 1)];
 #pragma unroll
-    for (int m = kAfaWaves / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    for (int m = kOwnerWaves / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
     return __builtin_amdgcn_readfirstlane(v);
 }
 
@@ -103,13 +92,13 @@ __device__ __forceinline__ uint32_t afa_here(uint32_t mask) {
 
 struct AfaLds {
     double s[kAfaMaxRows];                    // every row's last s
-    double list_w[kAfaThreads];               // the removed rows of one block of 1024 rows, ascending: their weights
-    int list_q[kAfaThreads];                  //                                                         and their rows
+    double list_w[kOwnerThreads];               // the removed rows of one block of 1024 rows, ascending: their weights
+    int list_q[kOwnerThreads];                  //                                                         and their rows
     unsigned hist[3][kAfaDigits];             // the radix walk's histograms, taken in turn (one barrier a digit)
-    double sum[2][kAfaWaves];
-    unsigned long long key[kAfaWaves];
-    int count[kAfaWaves];                     // afa_block_count's alone: written behind its first barrier, read behind its second
-    int listed[kAfaWaves];                    // the update's alone: a block's counts, written before the block's first barrier, read
+    ExchangeBuf<double> sum;
+    unsigned long long key[kOwnerWaves];
+    int count[kOwnerWaves];                     // afa_block_count's alone: written behind its first barrier, read behind its second
+    int listed[kOwnerWaves];                    // the update's alone: a block's counts, written before the block's first barrier, read
                                               // behind it, and the block's last barrier stands before the next block's (and the next
                                               // round's) write.  Were they one array, a wave still reading a round's removed count
                                               // could meet the first block's list counts.
@@ -134,9 +123,9 @@ __device__ __forceinline__ double afa_median(AfaLds& lds, uint32_t live, int m) 
         int run_digit = -1, run = 0;                  // equal digits of a thread's rows are counted before they are added
         const uint32_t mask = afa_here(live);
 #pragma unroll
-        for (int s = 0; s < kAfaSlots; ++s) {
+        for (int s = 0; s < kOwnerSlots; ++s) {
             if ((mask >> s) & 1u) {
-                const unsigned long long key = ordered_bits_total(lds.s[t + kAfaThreads * s]);
+                const unsigned long long key = ordered_bits_total(lds.s[row_of(t, s)]);
                 if ((key & known) == prefix) {
                     const int digit = static_cast<int>((key >> shift) & 0xffu);
                     if (digit != run_digit) {
@@ -184,25 +173,25 @@ __device__ __forceinline__ double afa_median(AfaLds& lds, uint32_t live, int m) 
     unsigned long long above = ~0ull;                 // the smallest kept key above the lower statistic
     const uint32_t mask = afa_here(live);
 #pragma unroll
-    for (int s = 0; s < kAfaSlots; ++s) {
+    for (int s = 0; s < kOwnerSlots; ++s) {
         if ((mask >> s) & 1u) {
-            const unsigned long long key = ordered_bits_total(lds.s[t + kAfaThreads * s]);
+            const unsigned long long key = ordered_bits_total(lds.s[row_of(t, s)]);
             if (key > prefix && key < above) above = key;
         }
     }
     above = lanes::wave_min_shfl(above);
     if (lane == 0) lds.key[wave] = above;
     __syncthreads();
-    above = lds.key[lane & (kAfaWaves - 1)];
+    above = lds.key[lane & (kOwnerWaves - 1)];
 #pragma unroll
-    for (int d = kAfaWaves / 2; d > 0; d >>= 1) {
+    for (int d = kOwnerWaves / 2; d > 0; d >>= 1) {
         const unsigned long long other = __shfl_xor(above, d, 64);
         above = other < above ? other : above;
     }
     return (lo + value_of_total_key(above)) / 2.0;
 }
 
-__global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __restrict__ C, const double* __restrict__ u0,
+__global__ __launch_bounds__(kOwnerThreads) void afa_loop_kernel(const double* __restrict__ C, const double* __restrict__ u0,
                                                                const double* __restrict__ r0, double* __restrict__ w, int n,
                                                                double xi, double delta_xi, int max_rounds,
                                                                int32_t* __restrict__ kept, int32_t* __restrict__ kept_out,
@@ -210,12 +199,12 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
                                                                AfaReport* __restrict__ info) {
     __shared__ AfaLds lds;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int slots = (n + kAfaThreads - 1) / kAfaThreads;       // the slots that hold a row: uniform
-    double u[kAfaSlots];                              // (r is read again where a round needs it: once)
-    uint32_t live = 0;                                // bit s: row t + 1024 s is kept
+    const int slots = (n + kOwnerThreads - 1) / kOwnerThreads;       // the slots that hold a row: uniform
+    double u[kOwnerSlots];                              // (r is read again where a round needs it: once)
+    uint32_t live = 0;                                // bit s: row row_of(t, s) is kept
 #pragma unroll
-    for (int s = 0; s < kAfaSlots; ++s) {
-        const int v = t + kAfaThreads * s;
+    for (int s = 0; s < kOwnerSlots; ++s) {
+        const int v = row_of(t, s);
         const bool in = v < n;
         u[s] = in ? u0[v] : 0.0;
         if (in) {
@@ -233,8 +222,8 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
         int h = afa_here(t);
         uint32_t mask = afa_here(live);
 #pragma unroll
-        for (int s = 0; s < kAfaSlots; ++s)
-            if ((mask >> s) & 1u) chain += w[h + kAfaThreads * s] * u[s];
+        for (int s = 0; s < kOwnerSlots; ++s)
+            if ((mask >> s) & 1u) chain += w[row_of(h, s)] * u[s];
         const double A = afa_block_sum(chain, lds.sum, turn);
         if (!(__builtin_isfinite(A) && A > 0.0)) {
             degenerate = 1;
@@ -245,10 +234,10 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
         h = afa_here(t);
         mask = afa_here(live);
 #pragma unroll
-        for (int s = 0; s < kAfaSlots; ++s) {
+        for (int s = 0; s < kOwnerSlots; ++s) {
             if ((mask >> s) & 1u) {
-                const double sk = u[s] / (r0[h + kAfaThreads * s] * root);
-                lds.s[t + kAfaThreads * s] = sk;
+                const double sk = u[s] / (r0[row_of(h, s)] * root);
+                lds.s[row_of(t, s)] = sk;
                 chain += sk;
             }
         }
@@ -257,9 +246,9 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
         chain = 0.0;
         mask = afa_here(live);
 #pragma unroll
-        for (int s = 0; s < kAfaSlots; ++s) {
+        for (int s = 0; s < kOwnerSlots; ++s) {
             if ((mask >> s) & 1u) {
-                const double d = lds.s[t + kAfaThreads * s] - mean;
+                const double d = lds.s[row_of(t, s)] - mean;
                 chain += d * d;
             }
         }
@@ -267,16 +256,16 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
         med = afa_median(lds, live, m);
         const bool lower = mean < med;
         thr = lower ? med - xi * sd : med + xi * sd;
-        uint32_t gone = 0;                            // bit s: row t + 1024 s is removed in this round
+        uint32_t gone = 0;                            // bit s: row row_of(t, s) is removed in this round
         h = afa_here(t);
         mask = afa_here(live);
 #pragma unroll
-        for (int s = 0; s < kAfaSlots; ++s) {
+        for (int s = 0; s < kOwnerSlots; ++s) {
             if ((mask >> s) & 1u) {
-                const double sk = lds.s[t + kAfaThreads * s];
+                const double sk = lds.s[row_of(t, s)];
                 if (lower ? sk < thr : sk > thr) {
                     gone |= 1u << s;
-                    round_of[h + kAfaThreads * s] = round;
+                    round_of[row_of(h, s)] = round;
                 }
             }
         }
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
             __syncthreads();
             int first = 0, listed = 0;
 #pragma unroll
-            for (int v = 0; v < kAfaWaves; ++v) {
+            for (int v = 0; v < kOwnerWaves; ++v) {
                 const int c = lds.listed[v];
                 first += v < wave ? c : 0;
                 listed += c;
@@ -303,7 +292,7 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
             if (listed > 0) {
                 if (mine) {
                     const int at = first + __builtin_popcountll(votes & ((1ull << lane) - 1ull));
-                    const int q = afa_here(t) + kAfaThreads * g;
+                    const int q = row_of(afa_here(t), g);
                     lds.list_q[at] = q;
                     lds.list_w[at] = w[q];
                 }
@@ -311,8 +300,8 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
                 h = afa_here(t);
                 mask = afa_here(live);                // (the rows still kept: nobody reads a removed or excluded row's u again)
 #pragma unroll
-                for (int s = 0; s < kAfaSlots; ++s) {
-                    const int v = h + kAfaThreads * s;
+                for (int s = 0; s < kOwnerSlots; ++s) {
+                    const int v = row_of(h, s);
                     if ((mask >> s) & 1u) {
                         double acc = u[s];
                         for (int b0 = 0; b0 < listed; b0 += kAfaBatch) {
@@ -337,8 +326,8 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
     double chain = 0.0;
     const int h = afa_here(t);
 #pragma unroll
-    for (int s = 0; s < kAfaSlots; ++s) {
-        const int v = h + kAfaThreads * s;
+    for (int s = 0; s < kOwnerSlots; ++s) {
+        const int v = row_of(h, s);
         if (v < n) {
             const int flag = static_cast<int>((live >> s) & 1u);
             kept[v] = flag;
@@ -366,7 +355,57 @@ __global__ __launch_bounds__(kAfaThreads) void afa_loop_kernel(const double* __r
     }
 }
 
+// owner_loop.hpp's pieces on one workgroup (tests/test_gpu_parity.py restates every row): row r holds thread t's word at
+// out[r * 1024 + t]; a 64-bit value takes two rows (low, high), a RemovalKey three (hi's low, hi's high, lo).
+__global__ __launch_bounds__(kOwnerThreads) void owner_loop_selftest_kernel(int32_t* __restrict__ out) {
+    __shared__ ExchangeBuf<unsigned long long> keys;
+    __shared__ ExchangeBuf<double> sums;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int row = 0;
+    const auto word = [&](uint32_t w) { out[row++ * kOwnerThreads + t] = static_cast<int32_t>(w); };
+    const auto put = [&](auto v) {                    // 8 bytes: the low word, the high word
+        word(static_cast<uint32_t>(__builtin_bit_cast(unsigned long long, v)));
+        word(static_cast<uint32_t>(__builtin_bit_cast(unsigned long long, v) >> 32));
+    };
+    const auto put_key = [&](RemovalKey k) { put(k.hi), word(k.lo); };
+    const auto key_max = [](RemovalKey a, RemovalKey b) { return removal_less(a, b) ? b : a; };
+    const auto key_min = [](unsigned long long a, unsigned long long b) { return a < b ? a : b; };
+    // (a) the exchange of a 64-bit value and of a three-word struct
+    const unsigned long long wide = static_cast<unsigned long long>(t) * 0x0001000300050007ull + 0x1234ull;
+    const RemovalKey three{wide ^ 0xffffull, static_cast<uint32_t>(t) * 40503u + 7u};
+    lanes::for_pow2_up<1, 32>([&](auto mc) {
+        put(lanes::lane_xor<decltype(mc)::value>(wide, lane));
+        put_key(lanes::lane_xor<decltype(mc)::value>(three, lane));
+    });
+    // (b) the lane fold: eight-way ties on the high word, the low word decides
+    const RemovalKey tied{static_cast<unsigned long long>((37 * lane + 11 + wave) % 8), static_cast<uint32_t>(t) * 2654435761u};
+    put_key(lanes::lanes_fold<32>(tied, lane, key_max));
+    put_key(lanes::lanes_fold<8>(tied, lane, key_max));
+    // (c) two block exchanges with no barrier of the kernel's between them: the winner sits in wave 5, then in wave 11
+    int turn = 0;
+    const auto waves_min = [&](unsigned long long v) { return lanes::lanes_fold<kOwnerWaves / 2>(v, lane, key_min); };
+    const unsigned long long first = (static_cast<unsigned long long>(t ^ (5 * 64 + 17)) << 32) | static_cast<uint32_t>(t);
+    const unsigned long long second = (static_cast<unsigned long long>(t ^ (11 * 64 + 3)) << 32) | static_cast<uint32_t>(t);
+    const unsigned long long won = block_exchange(lanes::lanes_fold<32>(first, lane, key_min), keys, turn, lane, wave, waves_min);
+    const unsigned long long won_next = block_exchange(lanes::lanes_fold<32>(second, lane, key_min), keys, turn, lane, wave, waves_min);
+    put(won), put(won_next);
+    // (d) the block sum on inputs whose additions round, twice in a row
+    int sum_turn = 0;
+    const double x = (1.0 + static_cast<double>(lane) / 3.0) * static_cast<double>(1 << (wave % 5));
+    const double total = afa_block_sum(x, sums, sum_turn), total_next = afa_block_sum(x / 7.0, sums, sum_turn);
+    put(total), put(total_next);
+}
+constexpr int kOwnerSelftestRows = 6 * (2 + 3) + 3 + 3 + 2 + 2 + 2 + 2;
+static_assert(kOwnerSelftestRows <= 64, "byzagg.h promises the caller at most 64 rows");
+
 }  // namespace
+
+int launch_owner_loop_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_rows, hipStream_t stream) {
+    KernelTimer timer(ctx, BYZ_K_MISC, stream);
+    owner_loop_selftest_kernel<<<1, kOwnerThreads, 0, stream>>>(out);
+    *n_rows = kOwnerSelftestRows;
+    return check_launch("owner_loop_selftest_kernel");
+}
 
 int afa_workspace(byz_ctx* ctx, int64_t n, AfaScratch* out) {
     out->info = &device_scalars(ctx)->afa;
@@ -396,7 +435,7 @@ int launch_afa_select(byz_ctx* ctx, const AfaScratch& t, const double* gram, int
     }
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
     const int rounds = static_cast<int>(max_rounds > n ? n : max_rounds);
-    afa_loop_kernel<<<1, kAfaThreads, 0, stream>>>(gram, t.u, t.r, t.w, static_cast<int>(n), xi0, delta_xi, rounds, t.kept, kept_out,
+    afa_loop_kernel<<<1, kOwnerThreads, 0, stream>>>(gram, t.u, t.r, t.w, static_cast<int>(n), xi0, delta_xi, rounds, t.kept, kept_out,
                                                    round_of_out != nullptr ? round_of_out : t.round_of, score_out, t.info);
     return check_launch("afa_loop_kernel");
 }

@@ -1550,16 +1550,17 @@ int byz_weak_dp_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols
 // ---- FLAME (Nguyen et al., USENIX Security 2022; beyond the reference) -------------------------------------------------------
 namespace {
 
-int check_flame_rows(const char* who, int64_t n) {
-    if (n > kFlameMaxRows) {
-        set_error("%s: at most %lld rows, got %lld", who, (long long)kFlameMaxRows, (long long)n);
+// the ceiling of the kernels whose one workgroup owns every row (owner_loop.hpp): FLAME, the linkage, Multi-Metrics, FABA, AFA
+int check_owned_rows(const char* who, int64_t n) {
+    if (n > kOwnerMaxRows) {
+        set_error("%s: at most %lld rows, got %lld", who, (long long)kOwnerMaxRows, (long long)n);
         return BYZ_E_UNSUPPORTED;
     }
     return BYZ_OK;
 }
 
 int check_flame_select(const char* who, int64_t n, int64_t m, int64_t ms) {
-    BYZ_TRY(check_flame_rows(who, n));
+    BYZ_TRY(check_owned_rows(who, n));
     if (n < 2 || m < 2 || m > n || 2 * m <= n) {
         set_error("%s: min_cluster_size = %lld must lie in 2..n and exceed n / 2 (n = %lld): one majority cluster", who, (long long)m,
                   (long long)n);
@@ -1585,7 +1586,7 @@ int check_flame(const char* who, const byz_flame_params* params, int64_t n_rows,
         set_error("%s: null parameters", who);
         return BYZ_E_INVALID;
     }
-    BYZ_TRY(check_flame_rows(who, n_rows));
+    BYZ_TRY(check_owned_rows(who, n_rows));
     BYZ_TRY(check_noise(who, params->lambda, params->column_offset, n_cols));
     return check_flame_select(who, n_rows, flame_cluster_size(params, n_rows), params->min_samples);
 }
@@ -1628,7 +1629,7 @@ int flame(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, int64_t ld, c
     BYZ_TRY(launch_row_sqdist(ctx, G, n, n_cols, ld, out, t.partials, sq, nullptr, nullptr, s));
     if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, sq, n, stream, "flame (norms)"));
     BYZ_TRY(launch_clip_scales(ctx, sq, n, 0.0, true, scale, &f.info->clip, s));     // the paper's median: over all n rows
-    BYZ_TRY(launch_flame_weights(ctx, f, scale, n, s));
+    BYZ_TRY(launch_flame_weights(ctx, f.admitted, scale, n, f.w, s));
     BYZ_TRY(launch_scaled_rows_sum(ctx, G, n, n_cols, ld, f.w, &f.info->admitted_f64, out, s));
     if (params->lambda == 0.0) return BYZ_OK;              // the clipped mean's bits
     return launch_gaussian_noise(ctx, out, n_cols, params->lambda, params->seed, params->round, params->column_offset,
@@ -1641,14 +1642,14 @@ int byz_cosine_distances_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "cosine_distances"));
     BYZ_REQUIRE(dist, "cosine_distances: null output");
-    BYZ_TRY(check_flame_rows("cosine_distances", n_rows));
+    BYZ_TRY(check_owned_rows("cosine_distances", n_rows));
     return cosine_distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, dist, stream);
 }
 
 int byz_cosine_from_gram_dev(byz_ctx* ctx, const double* gram, int64_t n_rows, float* dist, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(gram && dist && n_rows > 0, "cosine_from_gram: null Gram or output, or no rows (%lld)", (long long)n_rows);
-    BYZ_TRY(check_flame_rows("cosine_from_gram", n_rows));
+    BYZ_TRY(check_owned_rows("cosine_from_gram", n_rows));
     return launch_cosine_from_gram(ctx, gram, n_rows, dist, as_stream(stream));
 }
 
@@ -1709,7 +1710,7 @@ int byz_flame_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* broken_rows, d
 namespace {
 
 int check_linkage(const char* who, int64_t n, int method, const double* fill) {
-    BYZ_TRY(check_flame_rows(who, n));
+    BYZ_TRY(check_owned_rows(who, n));
     if (n < 2) {
         set_error("%s: at least 2 rows, got %lld", who, (long long)n);
         return BYZ_E_INVALID;
@@ -1766,10 +1767,7 @@ int clipped_clustering(byz_ctx* ctx, const float* G, int64_t n, int64_t n_cols, 
         sq = t.a;
     }
     BYZ_TRY(launch_clip_scales(ctx, sq, n, params->clip, params->adaptive != 0, scale, &f.info->clip, s));
-    FlameScratch weights{};                                   // (flame_weights_kernel reads the flags and writes the weights)
-    weights.admitted = f.admitted;
-    weights.w = f.w;
-    BYZ_TRY(launch_flame_weights(ctx, weights, scale, n, s));
+    BYZ_TRY(launch_flame_weights(ctx, f.admitted, scale, n, f.w, s));
     return launch_scaled_rows_sum(ctx, G, n, n_cols, ld, f.w, &f.info->admitted_f64, out, s);
 }
 
@@ -1801,7 +1799,7 @@ int byz_linkage_cut_dev(byz_ctx* ctx, const int32_t* pair, int64_t n_rows, const
                         int32_t* labels, int32_t* cluster_sizes, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(pair && usable_rows && labels && cluster_sizes, "linkage_cut: null merges, flags or output");
-    BYZ_TRY(check_flame_rows("linkage_cut", n_rows));
+    BYZ_TRY(check_owned_rows("linkage_cut", n_rows));
     BYZ_REQUIRE(n_rows >= 2 && n_clusters >= 1 && n_clusters <= n_rows, "linkage_cut: %lld clusters of %lld rows (at least 2 rows, 1..n clusters)",
                 (long long)n_clusters, (long long)n_rows);
     return launch_linkage_cut(ctx, pair, n_rows, usable_rows, n_clusters, labels, cluster_sizes, as_stream(stream));
@@ -1859,10 +1857,7 @@ int byz_clipped_clustering_info(byz_ctx* ctx, int64_t* admitted_rows, int64_t* u
 namespace {
 
 int check_faba(const char* who, int64_t n, int64_t remove_count, int power) {
-    if (n > kFabaMaxRows) {
-        set_error("%s: at most %lld rows, got %lld", who, (long long)kFabaMaxRows, (long long)n);
-        return BYZ_E_UNSUPPORTED;
-    }
+    BYZ_TRY(check_owned_rows(who, n));
     if (n < 2) {
         set_error("%s: at least 2 rows, got %lld", who, (long long)n);
         return BYZ_E_INVALID;
@@ -1929,10 +1924,7 @@ int byz_faba_info(byz_ctx* ctx, int64_t* removed_rows, int64_t* kept_rows, int64
 namespace {
 
 int check_afa(const char* who, int64_t n, const byz_afa_params* params) {
-    if (n > kAfaMaxRows) {
-        set_error("%s: at most %lld rows, got %lld", who, (long long)kAfaMaxRows, (long long)n);
-        return BYZ_E_UNSUPPORTED;
-    }
+    BYZ_TRY(check_owned_rows(who, n));
     if (n < 2) {
         set_error("%s: at least 2 rows, got %lld", who, (long long)n);
         return BYZ_E_INVALID;
@@ -2093,16 +2085,8 @@ int byz_auror_info(byz_ctx* ctx, int64_t* indicative, int64_t* removed_rows, int
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
-int check_mm_rows(const char* who, int64_t n) {
-    if (n > kMmMaxRows) {
-        set_error("%s: at most %lld rows, got %lld", who, (long long)kMmMaxRows, (long long)n);
-        return BYZ_E_UNSUPPORTED;
-    }
-    return BYZ_OK;
-}
-
 int check_mm_keep(const char* who, int64_t n, int64_t keep) {
-    BYZ_TRY(check_mm_rows(who, n));
+    BYZ_TRY(check_owned_rows(who, n));
     if (n < 1 || keep < 1 || keep > n) {
         set_error("%s: keep = %lld outside 1..%lld (the row count)", who, (long long)keep, (long long)n);
         return BYZ_E_INVALID;
@@ -2160,7 +2144,7 @@ int byz_manhattan_distances_dev(byz_ctx* ctx, const float* G, int64_t n_rows, in
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "manhattan_distances"));
     BYZ_REQUIRE(dist, "manhattan_distances: null output");
-    BYZ_TRY(check_mm_rows("manhattan_distances", n_rows));
+    BYZ_TRY(check_owned_rows("manhattan_distances", n_rows));
     return manhattan_distances(ctx, G, n_rows, n_cols, ld, nullptr, nullptr, dist, stream);
 }
 
@@ -2168,7 +2152,7 @@ int byz_manhattan_sums_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
     BYZ_TRY(enter(ctx));
     BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "manhattan_sums"));
     BYZ_REQUIRE(sums, "manhattan_sums: null output");
-    BYZ_TRY(check_mm_rows("manhattan_sums", n_rows));
+    BYZ_TRY(check_owned_rows("manhattan_sums", n_rows));
     double *partial, *unused;
     BYZ_TRY(manhattan_workspace(ctx, n_rows, n_cols, &partial, &unused));
     return launch_manhattan_sums(ctx, G, n_rows, n_cols, ld, partial, sums, as_stream(stream));
@@ -2177,7 +2161,7 @@ int byz_manhattan_sums_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t
 int byz_manhattan_from_sums_dev(byz_ctx* ctx, const double* sums, int64_t n_rows, float* dist, void* stream) {
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(sums && dist && n_rows > 0, "manhattan_from_sums: null sums or output, or no rows (%lld)", (long long)n_rows);
-    BYZ_TRY(check_mm_rows("manhattan_from_sums", n_rows));
+    BYZ_TRY(check_owned_rows("manhattan_from_sums", n_rows));
     return launch_manhattan_from_sums(ctx, sums, n_rows, dist, as_stream(stream));
 }
 
@@ -2186,7 +2170,7 @@ int byz_multi_metrics_features_dev(byz_ctx* ctx, const float* man, const float* 
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(man && euc && cos && features && n_rows > 0, "multi_metrics_features: a null matrix or output, or no rows (%lld)",
                 (long long)n_rows);
-    BYZ_TRY(check_mm_rows("multi_metrics_features", n_rows));
+    BYZ_TRY(check_owned_rows("multi_metrics_features", n_rows));
     MmScratch t;
     BYZ_TRY(multi_metrics_workspace(ctx, n_rows, false, &t));
     BYZ_TRY(launch_mm_usable_from_cos(ctx, cos, n_rows, t.usable, as_stream(stream)));
@@ -3211,6 +3195,12 @@ int byz_selftest_lane_exchange_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_pa
     BYZ_TRY(enter(ctx));
     BYZ_REQUIRE(out_dev && n_patterns_host, "selftest: bad arguments");
     return launch_lane_selftest(ctx, out_dev, n_patterns_host, as_stream(stream));
+}
+
+int byz_selftest_owner_loop_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_rows_host, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(out_dev && n_rows_host, "selftest: bad arguments");
+    return launch_owner_loop_selftest(ctx, out_dev, n_rows_host, as_stream(stream));
 }
 
 int byz_gram_unit_table(int64_t n_rows, int32_t* units_host, int64_t capacity_units, int64_t* n_units) {

@@ -15,6 +15,7 @@
 #include "../../include/byzagg.h"
 #include "carve.hpp"
 #include "device_scalars.hpp"
+#include "owner_loop.hpp"
 
 namespace byz {
 
@@ -427,7 +428,7 @@ double fang_lambda0(double s_min, double q_max, int64_t n, int64_t c, int64_t n_
 int launch_fang_krum_fill(byz_ctx* ctx, float* dist, int64_t n, int64_t c, int64_t n_cols, const double* q, const double* t,
                           double lambda, hipStream_t stream);
 // flame.hip: FLAME's clustering stage.  The scalars of a call: DeviceScalars::flame.
-constexpr int64_t kFlameMaxRows = 16384;     // Prim's one workgroup owns 1024 x 16 vertices; the union-find fills the LDS
+constexpr int64_t kFlameMaxRows = kOwnerMaxRows;     // Prim's one workgroup owns 1024 x 16 vertices; the union-find fills the LDS
 constexpr int64_t kFlameMaxSamples = 32;     // rounds of the core distance's selection at most
 struct FlameScratch {
     FlameInfo* info;
@@ -445,8 +446,8 @@ int launch_flame_core(byz_ctx* ctx, const float* dist, int64_t n, int64_t ms, fl
 // core distances, Prim, the edge sort, the admission: t.admitted (and admitted_out, optional), the scalars into t.info
 int launch_flame_select(byz_ctx* ctx, const FlameScratch& t, const float* dist, int64_t n, int64_t m, int64_t ms,
                         int32_t* admitted_out, hipStream_t stream);
-// t.w[i] = t.admitted[i] ? scales[i] : 0
-int launch_flame_weights(byz_ctx* ctx, const FlameScratch& t, const double* scales, int64_t n, hipStream_t stream);
+// w[i] = flags[i] ? scales[i] : 0
+int launch_flame_weights(byz_ctx* ctx, const int32_t* flags, const double* scales, int64_t n, double* w, hipStream_t stream);
 // manhattan.hip: the pairwise L1 distances.  sums (n x n fp64, both triangles) = sum_c |g_ic - g_jc| over the columns given,
 // additive over column shards; dist = the sums of the lower triangle rounded once to fp32, the diagonal and every pair whose sum
 // is not finite +inf.  partial: the tile kernel's per-chunk sums (manhattan_workspace carves both).
@@ -457,7 +458,7 @@ int launch_manhattan_sums(byz_ctx* ctx, const float* G, int64_t n, int64_t d, in
                           hipStream_t stream);
 int launch_manhattan_from_sums(byz_ctx* ctx, const double* sums, int64_t n, float* dist, hipStream_t stream);
 // multi_metrics.hip: Multi-Metrics' features, scores and selection.  The scalars of a call: DeviceScalars::mm.
-constexpr int64_t kMmMaxRows = 16384;        // the selection's one workgroup owns 1024 x 16 rows
+constexpr int64_t kMmMaxRows = kOwnerMaxRows;        // the selection's one workgroup owns 1024 x 16 rows
 struct MmScratch {
     MmInfo* info;
     float *man, *cos;                        // n x n each: the whole call's Manhattan and cosine matrices
@@ -498,7 +499,7 @@ int launch_linkage_cut(byz_ctx* ctx, const int32_t* pair, int64_t n, const int32
 int launch_clipped_clustering_select(byz_ctx* ctx, const LinkageScratch& t, const float* dist, int64_t n, int method, double fill,
                                      int32_t* admitted_out, hipStream_t stream);
 // faba.hip: FABA's selection on a distance matrix.  The scalars of a call: DeviceScalars::faba.
-constexpr int64_t kFabaMaxRows = 16384;      // the loop's one workgroup owns 1024 x 16 rows
+constexpr int64_t kFabaMaxRows = kOwnerMaxRows;      // the loop's one workgroup owns 1024 x 16 rows
 struct FabaScratch {
     FabaReport* info;
     double *s, *w;                   // n: every row's initial sum; the aggregate's 0 / 1 weights
@@ -510,7 +511,7 @@ int faba_workspace(byz_ctx* ctx, int64_t n, FabaScratch* out);
 int launch_faba_select(byz_ctx* ctx, const FabaScratch& t, const float* dist, int64_t n, int64_t r, int power, int32_t* kept_out,
                        int32_t* order_out, hipStream_t stream);
 // afa.hip: AFA's selection on an fp64 Gram.  The scalars of a call: DeviceScalars::afa.
-constexpr int64_t kAfaMaxRows = 16384;       // the loop's one workgroup owns 1024 x 16 rows
+constexpr int64_t kAfaMaxRows = kOwnerMaxRows;       // the loop's one workgroup owns 1024 x 16 rows
 struct AfaScratch {
     AfaReport* info;
     double *u, *r, *w;               // n: every row's initial u; sqrt of its diagonal (0: excluded); its weight, 0 when not kept
@@ -620,6 +621,8 @@ int64_t select_max_rows();
 
 // median_window.hip: lane_exchange.hpp's exchanges over the lane ids
 int launch_lane_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_patterns, hipStream_t stream);
+// afa.hip: owner_loop.hpp's exchange, folds and block exchange on one workgroup of 1024 threads (rows of 1024 words)
+int launch_owner_loop_selftest(byz_ctx* ctx, int32_t* out, int32_t* n_rows, hipStream_t stream);
 
 // krum_small.hip: the whole of Krum for N <= 128 in five launches
 bool krum_small_applies(int64_t n_rows, int64_t n_cols);

@@ -9,24 +9,20 @@
 //   faba_init_kernel   one wave per row: s_i = the fp64 sum of the usable entries' terms of row i, bad_i = the entries that are
 //                      not usable.  Lane l adds the columns l, l + 64, ... in ascending order (64 interleaved chains), the
 //                      chains fold 32, 16, 8, 4, 2, 1 by lane_exchange.hpp's exchange: an order that no launch geometry changes.
-//   faba_loop_kernel   ONE workgroup of 1024 threads, thread t owns the rows t + 1024 s (s < 16), their s and bad in registers
-//                      (every index static) and a bit mask of those still kept.  A step is the argmax of (bad, s, lowest row)
-//                      over the owned rows, over the wave (one butterfly on the three-word key: six exchanges of three words
-//                      deep, where a reduction word by word would be eighteen deep), one LDS exchange of the 16 waves' maxima
-//                      behind one barrier (two buffers, as Prim in flame.hip), one coalesced read of the removed row and one
-//                      fp64 subtraction or one decrement a row.  At most n steps.  No atomics, no grid synchronisation.
+//   faba_loop_kernel   ONE workgroup on owner_loop.hpp's scheme: the owned rows' s and bad in registers (every index static) and
+//                      a bit mask of those still kept.  A step is the argmax of (bad, s, lowest row) over the owned rows, the
+//                      lane fold of the three-word removal key (six exchanges of three words deep, where a reduction word by
+//                      word would be eighteen deep), one block exchange and the waves' fold, one coalesced read of the removed
+//                      row and one fp64 subtraction or one decrement a row.  At most n steps.  No atomics, no grid synchronisation.
 //                      It ends by writing the flags, the removal order, the fp64 weights, the divisor and the report.
 #include "common.hpp"
 #include "lane_exchange.hpp"
+#include "order_keys.hpp"
 
 namespace byz {
 namespace {
 
 constexpr int kFabaInitThreads = 256;          // four rows a workgroup, one wave each
-constexpr int kFabaThreads = 1024;
-constexpr int kFabaSlots = 16;                 // rows a thread owns: kFabaThreads * kFabaSlots = kFabaMaxRows
-constexpr int kFabaIndexBits = 14;             // a row, and a bad count, is below 2^14
-static_assert(kFabaThreads * kFabaSlots == kFabaMaxRows && kFabaMaxRows == (1 << kFabaIndexBits), "every row has an owner");
 
 // an off-diagonal entry takes part in the sums when it is finite and >= 0 (-0.0 is: its term is a zero)
 __device__ __forceinline__ bool faba_usable(float c) { return __builtin_isfinite(c) && c >= 0.0f; }
@@ -36,46 +32,9 @@ __device__ __forceinline__ double faba_term(float c, int power) {
     return power == 2 ? d * d : d;
 }
 
-// the value of lane ^ MASK through lane_exchange.hpp's exchange (nothing but moves touches the bits)
-template <int MASK>
-__device__ __forceinline__ uint32_t u32_xor(uint32_t v, int lane) {
-    return __float_as_uint(lanes::lane_xor(__uint_as_float(v), MASK, lane));
-}
-template <int MASK>
-__device__ __forceinline__ unsigned long long u64_xor(unsigned long long v, int lane) {
-    return (static_cast<unsigned long long>(u32_xor<MASK>(static_cast<uint32_t>(v >> 32), lane)) << 32) |
-           u32_xor<MASK>(static_cast<uint32_t>(v), lane);
-}
-
-// doubles as integers of the same order (s is never a NaN and never -0.0: the sums start at +0.0 and x - x is +0.0)
-__device__ __forceinline__ unsigned long long ordered_f64(double v) {
-    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double from_ordered_f64(unsigned long long k) {
-    return __longlong_as_double(static_cast<long long>((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-
-// The step's key, larger is removed first: bad (14 bits), the ordered bits of s (64), the row counted down (14), in 96 bits:
-// hi = bad << 50 | key >> 14, lo = (key & 0x3fff) << 14 | (16383 - row).  The key of a non-negative s has its top bit set, so
-// no row's key is {0, 0}: that is "nobody".
-struct FabaKey {
-    unsigned long long hi;
-    uint32_t lo;
-};
-__device__ __forceinline__ FabaKey faba_max(FabaKey a, FabaKey b) {
-    return (a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo)) ? b : a;
-}
-// the maximum over the 2 * TOP lanes that differ in the low bits: every one of them gets it
-template <int TOP>
-__device__ __forceinline__ FabaKey faba_lanes_max(FabaKey v, int lane) {
-    lanes::for_pow2_up<1, TOP>([&](auto mc) {
-        constexpr int mask = decltype(mc)::value;
-        const FabaKey other{u64_xor<mask>(v.hi, lane), u32_xor<mask>(v.lo, lane)};
-        v = faba_max(v, other);
-    });
-    return v;
-}
+// The step's key is owner_loop.hpp's removal_key on order_keys.hpp's total key of s (s is never a NaN and never -0.0: the sums
+// start at +0.0 and x - x is +0.0, so the map is the plain sign flip and value_of_total_key gives the bits back).
+__device__ __forceinline__ RemovalKey faba_max(RemovalKey a, RemovalKey b) { return removal_less(a, b) ? b : a; }
 
 __global__ __launch_bounds__(kFabaInitThreads) void faba_init_kernel(const float* __restrict__ dist, int n, int power,
                                                                      double* __restrict__ s, int32_t* __restrict__ bad) {
@@ -93,8 +52,8 @@ __global__ __launch_bounds__(kFabaInitThreads) void faba_init_kernel(const float
     }
     lanes::for_pow2_down<32>([&](auto mc) {
         constexpr int mask = decltype(mc)::value;
-        acc += __longlong_as_double(static_cast<long long>(u64_xor<mask>(static_cast<unsigned long long>(__double_as_longlong(acc)), lane)));
-        nb += static_cast<int>(u32_xor<mask>(static_cast<uint32_t>(nb), lane));
+        acc += lanes::lane_xor<mask>(acc, lane);
+        nb += lanes::lane_xor<mask>(nb, lane);
     });
     if (lane == 0) {
         s[i] = acc;
@@ -102,22 +61,21 @@ __global__ __launch_bounds__(kFabaInitThreads) void faba_init_kernel(const float
     }
 }
 
-__global__ __launch_bounds__(kFabaThreads) void faba_loop_kernel(const float* __restrict__ dist, const double* __restrict__ s0,
+__global__ __launch_bounds__(kOwnerThreads) void faba_loop_kernel(const float* __restrict__ dist, const double* __restrict__ s0,
                                                                  const int32_t* __restrict__ bad0, int n, int r, int power,
                                                                  int32_t* __restrict__ order, int32_t* __restrict__ kept,
                                                                  int32_t* __restrict__ kept_out, double* __restrict__ w,
                                                                  FabaReport* __restrict__ info) {
-    __shared__ unsigned long long slot_hi[2][kFabaThreads / 64];
-    __shared__ uint32_t slot_lo[2][kFabaThreads / 64];
+    __shared__ ExchangeBuf<RemovalKey> slot;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int slots = (n + kFabaThreads - 1) / kFabaThreads;     // the slots that hold a row: uniform
-    double sv[kFabaSlots];
-    int bad[kFabaSlots];
-    uint32_t live = 0;                                // bit s: row t + 1024 s is kept
+    const int slots = (n + kOwnerThreads - 1) / kOwnerThreads;     // the slots that hold a row: uniform
+    double sv[kOwnerSlots];
+    int bad[kOwnerSlots];
+    uint32_t live = 0;                                // bit s: row row_of(t, s) is kept
     int any = 0;
 #pragma unroll
-    for (int s = 0; s < kFabaSlots; ++s) {
-        const int v = t + kFabaThreads * s;
+    for (int s = 0; s < kOwnerSlots; ++s) {
+        const int v = row_of(t, s);
         const bool in = v < n;
         sv[s] = in ? s0[v] : 0.0;
         bad[s] = in ? bad0[v] : 0;
@@ -128,62 +86,52 @@ __global__ __launch_bounds__(kFabaThreads) void faba_loop_kernel(const float* __
     }
     // no usable entry anywhere: no row can be judged, and the loop does not stop before it has removed them all
     const bool judged = __syncthreads_or(any) != 0;
-    int removed = 0;
+    int removed = 0, turn = 0;
     unsigned long long last = 0;                      // the ordered bits of the last removed row's s
     for (int step = 0; step < n; ++step) {
         int bb = 0, bi = 0;
         double bs = 0.0;
         bool found = false;
 #pragma unroll
-        for (int s = 0; s < kFabaSlots; ++s) {
+        for (int s = 0; s < kOwnerSlots; ++s) {
             if (s < slots) {
                 const bool mine = ((live >> s) & 1u) != 0;
                 if (mine && (!found || bad[s] > bb || (bad[s] == bb && sv[s] > bs))) {      // (ascending rows: a tie stays low)
                     found = true;
                     bb = bad[s];
                     bs = sv[s];
-                    bi = t + kFabaThreads * s;
+                    bi = row_of(t, s);
                 }
             }
         }
-        FabaKey k{0ull, 0u};
-        if (found) {
-            const unsigned long long key = ordered_f64(bs);
-            const unsigned long long b = static_cast<unsigned long long>(bb < 0 ? 0 : (bb > kFabaMaxRows - 1 ? kFabaMaxRows - 1 : bb));
-            k.hi = (b << 50) | (key >> kFabaIndexBits);
-            k.lo = (static_cast<uint32_t>(key & (kFabaMaxRows - 1)) << kFabaIndexBits) | static_cast<uint32_t>(kFabaMaxRows - 1 - bi);
-        }
-        k = faba_lanes_max<32>(k, lane);
-        if (lane == 0) {
-            slot_hi[step & 1][wave] = k.hi;
-            slot_lo[step & 1][wave] = k.lo;
-        }
-        __syncthreads();                              // (the other buffer is the next step's: one barrier a step)
-        FabaKey win{slot_hi[step & 1][lane & 15], slot_lo[step & 1][lane & 15]};
-        win = faba_lanes_max<8>(win, lane);
+        RemovalKey k{0ull, 0u};
+        __builtin_assume(bs == bs);                   // (never a NaN: the total map's NaN test and its branch fold away)
+        if (found) k = removal_key(bb, ordered_bits_total(bs), bi);
+        const auto waves_max = [lane](RemovalKey v) { return lanes::lanes_fold<kOwnerWaves / 2>(v, lane, faba_max); };
+        const RemovalKey win = block_exchange(lanes::lanes_fold<32>(k, lane, faba_max), slot, turn, lane, wave, waves_max);
         const uint32_t hi_hi = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(win.hi >> 32)));
         const uint32_t hi_lo = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(win.hi)));
         const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<int>(win.lo));
         const unsigned long long hi = (static_cast<unsigned long long>(hi_hi) << 32) | hi_lo;
         if (hi == 0 && lo == 0) break;                // (cannot happen: a kept row is left at every step below n)
-        const int wbad = static_cast<int>(hi >> 50);
+        const int wbad = removal_bad(hi);
         if (step >= r && wbad == 0 && judged) break;
-        const int q = kFabaMaxRows - 1 - static_cast<int>(lo & (kFabaMaxRows - 1));
+        const int q = removal_row(lo);
         if (q >= n) break;                            // (cannot happen: the key came from a row)
-        last = ((hi & ((1ull << 50) - 1)) << kFabaIndexBits) | (lo >> kFabaIndexBits);
+        last = removal_s_key(hi, lo);
         removed = step + 1;
         if (t == 0) order[step] = q;
-        if ((q & (kFabaThreads - 1)) == t) live &= ~(1u << (q >> 10));
+        if (owner_thread(q) == t) live &= ~(1u << slot_of(q));
         const float* __restrict__ row = dist + static_cast<int64_t>(q) * n;
-        float c[kFabaSlots];
+        float c[kOwnerSlots];
 #pragma unroll
-        for (int s = 0; s < kFabaSlots; ++s) {
-            const int v = t + kFabaThreads * s;
+        for (int s = 0; s < kOwnerSlots; ++s) {
+            const int v = row_of(t, s);
             c[s] = (s < slots && v < n) ? row[v] : 0.0f;
         }
 #pragma unroll
-        for (int s = 0; s < kFabaSlots; ++s) {
-            const int v = t + kFabaThreads * s;
+        for (int s = 0; s < kOwnerSlots; ++s) {
+            const int v = row_of(t, s);
             if (s < slots && v < n && v != q) {
                 if (faba_usable(c[s])) sv[s] -= faba_term(c[s], power);
                 else bad[s] -= 1;
@@ -191,8 +139,8 @@ __global__ __launch_bounds__(kFabaThreads) void faba_loop_kernel(const float* __
         }
     }
 #pragma unroll
-    for (int s = 0; s < kFabaSlots; ++s) {
-        const int v = t + kFabaThreads * s;
+    for (int s = 0; s < kOwnerSlots; ++s) {
+        const int v = row_of(t, s);
         if (v < n) {
             const int flag = static_cast<int>((live >> s) & 1u);
             kept[v] = flag;
@@ -200,13 +148,13 @@ __global__ __launch_bounds__(kFabaThreads) void faba_loop_kernel(const float* __
             w[v] = flag ? 1.0 : 0.0;
         }
     }
-    for (int e = removed + t; e < n; e += kFabaThreads) order[e] = -1;
+    for (int e = removed + t; e < n; e += kOwnerThreads) order[e] = -1;
     if (t == 0) {
         info->removed = removed;
         info->kept = n - removed;
         info->forced = removed > r ? removed - r : 0;
         info->pad = 0;
-        info->last_score = removed > 0 ? from_ordered_f64(last) : 0.0;
+        info->last_score = removed > 0 ? value_of_total_key(last) : 0.0;
         info->kept_f64 = static_cast<double>(n - removed);
     }
 }
@@ -236,7 +184,7 @@ int launch_faba_select(byz_ctx* ctx, const FabaScratch& t, const float* dist, in
         BYZ_TRY(check_launch("faba_init_kernel"));
     }
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
-    faba_loop_kernel<<<1, kFabaThreads, 0, stream>>>(dist, t.s, t.bad, static_cast<int>(n), static_cast<int>(r), power,
+    faba_loop_kernel<<<1, kOwnerThreads, 0, stream>>>(dist, t.s, t.bad, static_cast<int>(n), static_cast<int>(r), power,
                                                      order_out != nullptr ? order_out : t.order, t.kept, kept_out, t.w, t.info);
     return check_launch("faba_loop_kernel");
 }

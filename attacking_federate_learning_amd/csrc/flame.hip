@@ -11,11 +11,11 @@
 //                             fixed number of trips over the row; ms = 1 is one round, the row minimum; ms = 0: core = 0.
 //                             A distance of -inf counts as +inf here and in Prim (weight_key).
 //                             isolated_i = row i has no finite off-diagonal entry.
-//   mst_prim_kernel           Prim on R_ij = max(C_ij, core_i, core_j), never stored: ONE workgroup of 1024 threads, thread t
-//                             owns the vertices t + 1024 s (s < 16), their keys and parents in registers (every index static).
-//                             A step is one coalesced read of the new tree vertex's row, the update of the owned keys, the
-//                             argmin of (key << 32 | vertex) over the wave by DPP (lane_exchange.hpp), one LDS exchange of the
-//                             16 waves' minima and one barrier.  Exactly n - 1 steps.  No atomics, no grid synchronisation,
+//   mst_prim_kernel           Prim on R_ij = max(C_ij, core_i, core_j), never stored: ONE workgroup on owner_loop.hpp's scheme,
+//                             the owned vertices' keys and parents in registers (every index static).
+//                             A step is one coalesced read of the new tree vertex's row, the update of the owned keys and the
+//                             workgroup's argmin of (key << 32 | vertex): the lane fold, one block exchange, the waves' fold.
+//                             Exactly n - 1 steps.  No atomics, no grid synchronisation,
 //                             no loop whose length depends on the data.  A vertex in the tree is marked by a bit of its
 //                             owner's mask and competes with the all-ones pack, which no (key, vertex) pair equals.
 //   flame_admit_kernel        one workgroup: the ascending edges (segment_sort_u64 on (weight key << 32 | slot)) pass through
@@ -30,13 +30,10 @@
 namespace byz {
 namespace {
 
-constexpr int kPrimThreads = 1024;
-constexpr int kPrimSlots = 16;                 // vertices a thread owns: kPrimThreads * kPrimSlots = kFlameMaxRows
 constexpr int kCoreThreads = 256;
 constexpr int kAdmitThreads = 1024;
 constexpr int kAdmitChunk = 2048;              // edges staged in LDS at a time
 constexpr unsigned long long kNoPack = ~0ull;  // no (key, vertex) pair: a vertex is below 2^14
-static_assert(kPrimThreads * kPrimSlots == kFlameMaxRows, "every vertex has an owner");
 
 // the key a distance competes with: order_keys.hpp's total key, with -inf taken for +inf -- a weight that is not finite merges
 // nothing, and only while all of them sort LAST are the tree's finite edges a spanning forest of the finite graph
@@ -46,24 +43,6 @@ __device__ __forceinline__ uint32_t weight_key(float v) {
 }
 
 __device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-
-// the value of lane ^ MASK, both halves through lane_exchange.hpp's exchange (nothing but moves touches the bits)
-template <int MASK>
-__device__ __forceinline__ unsigned long long pack_xor(unsigned long long v, int lane) {
-    const float lo = lanes::lane_xor(__uint_as_float(static_cast<uint32_t>(v)), MASK, lane);
-    const float hi = lanes::lane_xor(__uint_as_float(static_cast<uint32_t>(v >> 32)), MASK, lane);
-    return (static_cast<unsigned long long>(__float_as_uint(hi)) << 32) | __float_as_uint(lo);
-}
-
-// the minimum over the 2 * TOP lanes that differ in the low bits: every one of them gets it
-template <int TOP>
-__device__ __forceinline__ unsigned long long lanes_min(unsigned long long v, int lane) {
-    lanes::for_pow2_up<1, TOP>([&](auto mc) {
-        constexpr int mask = decltype(mc)::value;
-        v = min_u64(v, pack_xor<mask>(v, lane));
-    });
-    return v;
-}
 
 __global__ __launch_bounds__(256) void cosine_from_gram_kernel(const double* __restrict__ gram, int64_t n, float* __restrict__ dist) {
     const int64_t j = static_cast<int64_t>(blockIdx.x) * 64 + (threadIdx.x & 63);
@@ -104,7 +83,7 @@ __global__ __launch_bounds__(kCoreThreads) void core_distance_kernel(const float
                 if ((r == 0 || key > prev) && key < best) best = key;
             }
         }
-        best = lanes_min<32>(best, lane);
+        best = lanes::lanes_fold<32>(best, lane, min_u64);
         if (lane == 0) part[wave] = best;
         __syncthreads();
         prev = min_u64(min_u64(part[0], part[1]), min_u64(part[2], part[3]));
@@ -116,38 +95,38 @@ __global__ __launch_bounds__(kCoreThreads) void core_distance_kernel(const float
     }
 }
 
-__global__ __launch_bounds__(kPrimThreads) void mst_prim_kernel(const float* __restrict__ dist, const float* __restrict__ core, int n,
+__global__ __launch_bounds__(kOwnerThreads) void mst_prim_kernel(const float* __restrict__ dist, const float* __restrict__ core, int n,
                                                                 int n_pad, unsigned long long* __restrict__ ekeys,
                                                                 int32_t* __restrict__ eab) {
-    __shared__ unsigned long long slot[2][kPrimThreads / 64];
+    __shared__ ExchangeBuf<unsigned long long> slot;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t key[kPrimSlots], ckey[kPrimSlots];
-    int parent[kPrimSlots];
-    uint32_t done = 0;                                // bit s: vertex t + 1024 s is in the tree, or beyond n
+    uint32_t key[kOwnerSlots], ckey[kOwnerSlots];
+    int parent[kOwnerSlots];
+    uint32_t done = 0;                                // bit s: vertex row_of(t, s) is in the tree, or beyond n
 #pragma unroll
-    for (int s = 0; s < kPrimSlots; ++s) {
-        const int v = t + kPrimThreads * s;
+    for (int s = 0; s < kOwnerSlots; ++s) {
+        const int v = row_of(t, s);
         key[s] = 0xffffffffu;
         parent[s] = 0;
         ckey[s] = v < n ? weight_key(core[v]) : 0xffffffffu;
         if (v >= n) done |= 1u << s;
     }
     if (t == 0) done |= 1u;                           // the tree starts at vertex 0
-    for (int e = n - 1 + t; e < n_pad; e += kPrimThreads) ekeys[e] = kNoPack;      // the sort's padding
-    int u = 0;
+    for (int e = n - 1 + t; e < n_pad; e += kOwnerThreads) ekeys[e] = kNoPack;      // the sort's padding
+    int u = 0, turn = 0;
     for (int step = 0; step < n - 1; ++step) {
         const float* __restrict__ row = dist + static_cast<int64_t>(u) * n;
         const uint32_t cu = weight_key(core[u]);
-        float c[kPrimSlots];
+        float c[kOwnerSlots];
 #pragma unroll
-        for (int s = 0; s < kPrimSlots; ++s) {
-            const int v = t + kPrimThreads * s;
+        for (int s = 0; s < kOwnerSlots; ++s) {
+            const int v = row_of(t, s);
             c[s] = v < n ? row[v] : __builtin_inff();
         }
         unsigned long long best = kNoPack;
 #pragma unroll
-        for (int s = 0; s < kPrimSlots; ++s) {
-            const int v = t + kPrimThreads * s;
+        for (int s = 0; s < kOwnerSlots; ++s) {
+            const int v = row_of(t, s);
             const bool live = ((done >> s) & 1u) == 0;
             uint32_t r = weight_key(c[s]);
             r = r > cu ? r : cu;
@@ -159,18 +138,16 @@ __global__ __launch_bounds__(kPrimThreads) void mst_prim_kernel(const float* __r
             const unsigned long long pack = (static_cast<unsigned long long>(key[s]) << 32) | static_cast<uint32_t>(v);
             best = min_u64(best, live ? pack : kNoPack);
         }
-        best = lanes_min<32>(best, lane);
-        if (lane == 0) slot[step & 1][wave] = best;
-        __syncthreads();                              // (the other buffer is the next step's: one barrier a step)
-        const unsigned long long win = lanes_min<8>(slot[step & 1][lane & 15], lane);
+        const auto waves_min = [lane](unsigned long long v) { return lanes::lanes_fold<kOwnerWaves / 2>(v, lane, min_u64); };
+        const unsigned long long win = block_exchange(lanes::lanes_fold<32>(best, lane, min_u64), slot, turn, lane, wave, waves_min);
         int nu = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(win)));
         const uint32_t wkey = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(win >> 32)));
         if (nu < 0 || nu >= n) nu = 0;                // (cannot happen: a live vertex is left at every step)
-        if ((nu & (kPrimThreads - 1)) == t) {
-            const int su = nu >> 10;
+        if (owner_thread(nu) == t) {
+            const int su = slot_of(nu);
             int p = 0;
 #pragma unroll
-            for (int s = 0; s < kPrimSlots; ++s) p = s == su ? parent[s] : p;
+            for (int s = 0; s < kOwnerSlots; ++s) p = s == su ? parent[s] : p;
             done |= 1u << su;
             ekeys[step] = (static_cast<unsigned long long>(wkey) << 32) | static_cast<uint32_t>(step);
             eab[2 * step] = p;
@@ -288,7 +265,7 @@ int launch_flame_select(byz_ctx* ctx, const FlameScratch& t, const float* dist, 
     BYZ_TRY(launch_flame_core(ctx, dist, n, ms, t.core, t.isolated, stream));
     {
         KernelTimer timer(ctx, BYZ_K_MISC, stream);
-        mst_prim_kernel<<<1, kPrimThreads, 0, stream>>>(dist, t.core, static_cast<int>(n), static_cast<int>(t.n_pad), t.ekeys, t.eab);
+        mst_prim_kernel<<<1, kOwnerThreads, 0, stream>>>(dist, t.core, static_cast<int>(n), static_cast<int>(t.n_pad), t.ekeys, t.eab);
         BYZ_TRY(check_launch("mst_prim_kernel"));
     }
     KernelTimer timer(ctx, BYZ_K_ROW_SORT, stream);
@@ -300,9 +277,9 @@ int launch_flame_select(byz_ctx* ctx, const FlameScratch& t, const float* dist, 
     return check_launch("flame_admit_kernel");
 }
 
-int launch_flame_weights(byz_ctx* ctx, const FlameScratch& t, const double* scales, int64_t n, hipStream_t stream) {
+int launch_flame_weights(byz_ctx* ctx, const int32_t* flags, const double* scales, int64_t n, double* w, hipStream_t stream) {
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
-    flame_weights_kernel<<<static_cast<unsigned>(ceil_div(n, 256)), 256, 0, stream>>>(t.admitted, scales, n, t.w);
+    flame_weights_kernel<<<static_cast<unsigned>(ceil_div(n, 256)), 256, 0, stream>>>(flags, scales, n, w);
     return check_launch("flame_weights_kernel");
 }
 

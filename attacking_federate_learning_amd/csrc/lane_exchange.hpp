@@ -1,5 +1,6 @@
-// Cross-lane exchange primitives, the in-register bitonic network shared by the median-window kernels, the wave-wide
-// reductions (sum, min, max) and the Krum / Bulyan ordering with its wave and block argmin.
+// Cross-lane exchange primitives (one word, and through it any 4- or 8-byte value or small struct), the fold over the lanes that
+// differ in the low bits (the one-workgroup loops' lane fold: owner_loop.hpp), the in-register bitonic network shared by the
+// median-window kernels, the wave-wide reductions (sum, min, max) and the Krum / Bulyan ordering with its wave and block argmin.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,6 +54,29 @@ __device__ __forceinline__ void for_pow2_down(F&& f) {
         f(std::integral_constant<int, J>{});
         for_pow2_down<J / 2>(f);
     }
+}
+
+// The exchange above for any value: 4 bytes as they are, 8 bytes as two words, a struct field by field through its each_field
+// (found by the struct's namespace).  Nothing but moves touches the bits.
+template <int MASK, typename T>
+__device__ __forceinline__ T lane_xor(T v, int lane) {
+    if constexpr (std::is_class_v<T>) {
+        return each_field(v, [lane](auto f) { return lane_xor<MASK>(f, lane); });
+    } else if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, lane_xor(__builtin_bit_cast(float, v), MASK, lane));
+    } else {
+        static_assert(sizeof(T) == 8 && std::is_trivially_copyable_v<T>, "words of 4 or 8 bytes");
+        const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+        const uint32_t lo = lane_xor<MASK>(static_cast<uint32_t>(b), lane), hi = lane_xor<MASK>(static_cast<uint32_t>(b >> 32), lane);
+        return __builtin_bit_cast(T, (static_cast<unsigned long long>(hi) << 32) | lo);
+    }
+}
+// v = op(v, the value of lane ^ m) for m = 1, 2, ..., TOP: the fold over the 2 * TOP lanes that differ in the low bits, and every
+// one of them gets the result (op: a minimum or maximum under a total order, or any operator that gives both partners the same)
+template <int TOP, typename T, typename Op>
+__device__ __forceinline__ T lanes_fold(T v, int lane, Op op) {
+    for_pow2_up<1, TOP>([&](auto mc) { v = op(v, lane_xor<decltype(mc)::value>(v, lane)); });
+    return v;
 }
 
 // Sorts the 64*R values {x[r] of lane l} ascending in index i = r + R*l, for C independent columns.

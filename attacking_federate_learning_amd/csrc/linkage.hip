@@ -9,9 +9,9 @@
 //                             finite off-diagonal entry (an integer OR into a zeroed flag: no floating-point atomic anywhere).
 //   linkage_nearest_kernel    grid-wide, a workgroup per row: the first nearest-partner cache, (W[i][k], k) smallest over the usable
 //                             k != i.  A nonnegative double orders as its integer bits.
-//   linkage_kernel<SLOTS, M>  ONE workgroup of 1024 threads on mst_prim_kernel's geometry: thread t owns the slots t + 1024 s
-//                             (s < SLOTS <= 16), their activity bits and cached distances in registers (every index static), the sizes and the cached partners in LDS.
-//                             A step: the workgroup's argmin of (cached distance, slot) by DPP and one LDS exchange -- the winner is
+//   linkage_kernel<SLOTS, M>  ONE workgroup on owner_loop.hpp's scheme with SLOTS <= 16 slots a thread: their activity bits and
+//                             cached distances in registers (every index static), the sizes and the cached partners in LDS.
+//                             A step: the workgroup's argmin of (cached distance, slot) (block_argmin) -- the winner is
 //                             the pair (a, b) smallest in (W[a][b], a, b), a < b, because the lowest slot holding the smallest
 //                             distance has every partner at that distance above it, and its cache names the lowest of them;
 //                             rows a and b of W read coalesced; the Lance-Williams update of the owned columns k; row a written
@@ -33,14 +33,11 @@
 namespace byz {
 namespace {
 
-constexpr int kLinkThreads = 1024;
-constexpr int kLinkMaxSlots = 16;              // slots a thread owns at most: kLinkThreads * kLinkMaxSlots = kFlameMaxRows
 constexpr int kLinkBatch = 4;                  // slots whose two row entries are in flight at once (16 registers)
 constexpr int kScanBatch = 8;                  // row entries a lane of a rescanning wave has in flight
 constexpr int kPrepTile = 64;
 constexpr int kNearThreads = 256;
 constexpr int kJumpRounds = 14;                // 2^14 = kFlameMaxRows: a chain of parents is shorter
-static_assert(kLinkThreads * kLinkMaxSlots == kFlameMaxRows, "every slot has an owner");
 static_assert((int64_t{1} << kJumpRounds) >= kFlameMaxRows && kJumpRounds % 2 == 0, "the jumps end in the first buffer");
 
 // a candidate of the argmin: the distance's bits and the slot it is cached for (or the column, in a rescan)
@@ -53,34 +50,17 @@ __device__ __forceinline__ bool cand_less(const Cand& a, const Cand& b) { return
 __device__ __forceinline__ Cand cand_min(const Cand& a, const Cand& b) { return cand_less(b, a) ? b : a; }
 __device__ __forceinline__ unsigned long long dist_bits(double v) { return __builtin_bit_cast(unsigned long long, v); }
 
-__device__ __forceinline__ uint32_t word_xor(uint32_t v, int mask, int lane) {
-    return __float_as_uint(lanes::lane_xor(__uint_as_float(v), mask, lane));
-}
-template <int MASK>
-__device__ __forceinline__ Cand cand_xor(const Cand& c, int lane) {
-    const uint32_t lo = word_xor(static_cast<uint32_t>(c.d), MASK, lane), hi = word_xor(static_cast<uint32_t>(c.d >> 32), MASK, lane);
-    return Cand{(static_cast<unsigned long long>(hi) << 32) | lo, word_xor(c.idx, MASK, lane)};
-}
+template <typename X>
+__device__ __forceinline__ Cand each_field(const Cand& c, X x) { return {x(c.d), x(c.idx)}; }
 // the minimum over the 2 * TOP lanes that differ in the low bits: every one of them gets it
 template <int TOP>
 __device__ __forceinline__ Cand lanes_argmin(Cand c, int lane) {
-    lanes::for_pow2_up<1, TOP>([&](auto mc) {
-        constexpr int mask = decltype(mc)::value;
-        c = cand_min(c, cand_xor<mask>(c, lane));
-    });
-    return c;
+    return lanes::lanes_fold<TOP>(c, lane, [](const Cand& a, const Cand& b) { return cand_min(a, b); });
 }
-// the workgroup's minimum, in every thread: one barrier (the buffers alternate; `turn` counts the calls, the same in every thread)
-template <int THREADS>
-__device__ __forceinline__ Cand block_argmin(Cand c, Cand (*xchg)[THREADS / 64], int& turn, int lane, int wave) {
-    static_assert(THREADS / 64 == 16 || THREADS / 64 == 4, "the second round's lane masks");
-    c = lanes_argmin<32>(c, lane);
-    if (lane == 0) xchg[turn & 1][wave] = c;
-    __syncthreads();
-    Cand r = xchg[turn & 1][lane & (THREADS / 64 - 1)];
-    r = lanes_argmin<THREADS / 128>(r, lane);
-    ++turn;
-    return r;
+// the workgroup's minimum, in every thread: the lane fold, one block exchange (one barrier), the waves' fold
+template <int WAVES>
+__device__ __forceinline__ Cand block_argmin(Cand c, ExchangeBuf<Cand, WAVES>& xchg, int& turn, int lane, int wave) {
+    return block_exchange(lanes_argmin<32>(c, lane), xchg, turn, lane, wave, [lane](Cand r) { return lanes_argmin<WAVES / 2>(r, lane); });
 }
 
 __global__ __launch_bounds__(256) void linkage_prepare_kernel(const float* __restrict__ dist, int64_t n, double fill,
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(256) void linkage_prepare_kernel(const float* __res
 __global__ __launch_bounds__(kNearThreads) void linkage_nearest_kernel(const double* __restrict__ W, const int32_t* __restrict__ usable,
                                                                        int n, unsigned long long* __restrict__ near_d,
                                                                        int32_t* __restrict__ near_p) {
-    __shared__ Cand xchg[2][kNearThreads / 64];
+    __shared__ ExchangeBuf<Cand, kNearThreads / 64> xchg;
     const int i = blockIdx.x, tid = threadIdx.x;
     const double* __restrict__ row = W + static_cast<int64_t>(i) * n;
     Cand best = no_cand();
@@ -136,7 +116,7 @@ __global__ __launch_bounds__(kNearThreads) void linkage_nearest_kernel(const dou
         for (int k = tid; k < n; k += kNearThreads)
             if (k != i && usable[k] != 0) best = cand_min(best, Cand{dist_bits(row[k]), static_cast<uint32_t>(k)});
     int turn = 0;
-    best = block_argmin<kNearThreads>(best, xchg, turn, tid & 63, tid >> 6);
+    best = block_argmin(best, xchg, turn, tid & 63, tid >> 6);
     if (tid == 0) {
         near_d[i] = best.d;
         near_p[i] = static_cast<int32_t>(best.idx);
@@ -151,22 +131,22 @@ __device__ __forceinline__ double lance_williams(double x, double y, double sa, 
 }
 
 template <int SLOTS, int METHOD>
-__global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const int32_t* __restrict__ usable,
+__global__ __launch_bounds__(kOwnerThreads) void linkage_kernel(double* W, const int32_t* __restrict__ usable,
                                                                const unsigned long long* __restrict__ near_d,
                                                                const int32_t* __restrict__ near_p, int n, int32_t* __restrict__ pair,
                                                                double* __restrict__ height, int32_t* __restrict__ size_out,
                                                                LinkageInfo* __restrict__ info) {
-    __shared__ Cand xchg[2][kLinkThreads / 64];
-    __shared__ int32_t sizes[SLOTS * kLinkThreads];
-    __shared__ unsigned short queue[SLOTS * kLinkThreads];
-    __shared__ unsigned short partner[SLOTS * kLinkThreads];     // the cached partner of every slot (written by the slot's owner)
-    __shared__ unsigned char alive[SLOTS * kLinkThreads];        // the slot is a cluster: what a scanning wave reads of `active`
-    __shared__ Cand found[2][kLinkThreads / 64];                  // a round of rescans: every wave's result (the buffers alternate)
+    __shared__ ExchangeBuf<Cand> xchg;
+    __shared__ int32_t sizes[SLOTS * kOwnerThreads];
+    __shared__ unsigned short queue[SLOTS * kOwnerThreads];
+    __shared__ unsigned short partner[SLOTS * kOwnerThreads];     // the cached partner of every slot (written by the slot's owner)
+    __shared__ unsigned char alive[SLOTS * kOwnerThreads];        // the slot is a cluster: what a scanning wave reads of `active`
+    __shared__ Cand found[2][kOwnerWaves];                  // a round of rescans: every wave's result (the buffers alternate)
     __shared__ int qcount[2], ucount;
-    constexpr int kBatch = SLOTS < kLinkBatch ? SLOTS : (SLOTS == kLinkMaxSlots ? kLinkBatch / 2 : kLinkBatch);
+    constexpr int kBatch = SLOTS < kLinkBatch ? SLOTS : (SLOTS == kOwnerSlots ? kLinkBatch / 2 : kLinkBatch);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned long long cd[SLOTS];
-    uint32_t active = 0;                              // bit s: slot t + 1024 s is a cluster
+    uint32_t active = 0;                              // bit s: slot row_of(t, s) is a cluster
     if (t == 0) {
         qcount[0] = 0;
         qcount[1] = 0;
@@ -174,7 +154,7 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
     }
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
-        const int k = t + kLinkThreads * s;
+        const int k = row_of(t, s);
         cd[s] = ~0ull;
         sizes[k] = 1;
         partner[k] = 0;
@@ -191,7 +171,7 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
     __syncthreads();
     const int u = ucount;
     const int steps = u > 1 ? u - 1 : 0;
-    for (int e = steps + t; e < n - 1; e += kLinkThreads) {      // behind the merges
+    for (int e = steps + t; e < n - 1; e += kOwnerThreads) {      // behind the merges
         pair[2 * e] = -1;
         pair[2 * e + 1] = -1;
         height[e] = __builtin_inf();
@@ -202,8 +182,8 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
         Cand best = no_cand();
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s)
-            if ((active >> s) & 1u) best = cand_min(best, Cand{cd[s], static_cast<uint32_t>(t + kLinkThreads * s)});
-        const Cand win = block_argmin<kLinkThreads>(best, xchg, turn, lane, wave);
+            if ((active >> s) & 1u) best = cand_min(best, Cand{cd[s], static_cast<uint32_t>(row_of(t, s))});
+        const Cand win = block_argmin(best, xchg, turn, lane, wave);
         int a = __builtin_amdgcn_readfirstlane(static_cast<int>(win.idx));
         if (a < 0 || a >= n) a = 0;                   // (cannot happen: two clusters are left at every step)
         int b = partner[a];
@@ -230,7 +210,7 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
             double x[kBatch], y[kBatch];
 #pragma unroll
             for (int q = 0; q < kBatch; ++q) {
-                const int k = tt + kLinkThreads * (s0 + q);
+                const int k = row_of(tt, s0 + q);
                 const bool live = ((active >> (s0 + q)) & 1u) != 0 && k != a && k != b;
                 x[q] = live ? row_a[k] : 0.0;
                 y[q] = live ? row_b[k] : 0.0;
@@ -238,7 +218,7 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
 #pragma unroll
             for (int q = 0; q < kBatch; ++q) {
                 const int s = s0 + q;
-                const int k = tt + kLinkThreads * s;
+                const int k = row_of(tt, s);
                 const bool live = ((active >> s) & 1u) != 0 && k != a && k != b;
                 if (live) {
                     const double nv = lance_williams<METHOD>(x[q], y[q], sa, sb);
@@ -257,13 +237,13 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
             }
             if constexpr (SLOTS > kBatch) __builtin_amdgcn_sched_barrier(0);
         }
-        if ((b & (kLinkThreads - 1)) == t) {
-            active &= ~(1u << (b >> 10));
+        if (owner_thread(b) == t) {
+            active &= ~(1u << slot_of(b));
             alive[b] = 0;
         }
-        const Cand mine = block_argmin<kLinkThreads>(self, xchg, turn, lane, wave);      // (its barrier publishes W and the queue)
-        if ((a & (kLinkThreads - 1)) == t) {
-            const int sa_slot = a >> 10;
+        const Cand mine = block_argmin(self, xchg, turn, lane, wave);      // (its barrier publishes W and the queue)
+        if (owner_thread(a) == t) {
+            const int sa_slot = slot_of(a);
 #pragma unroll
             for (int s = 0; s < SLOTS; ++s)
                 if (s == sa_slot) cd[s] = mine.d;
@@ -275,8 +255,8 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
         rescans += pending;
         max_rescans = pending > max_rescans ? pending : max_rescans;
         // the one loop whose length depends on the data: the queued slots, a wave each, 16 at a time
-        for (int base = 0; base < pending; base += kLinkThreads / 64) {
-            const int round = (base / (kLinkThreads / 64)) & 1;
+        for (int base = 0; base < pending; base += kOwnerWaves) {
+            const int round = (base / (kOwnerWaves)) & 1;
             if (base + wave < pending) {
                 int k = __builtin_amdgcn_readfirstlane(static_cast<int>(queue[base + wave]));
                 if (k >= n) k = 0;                    // (cannot happen)
@@ -298,12 +278,12 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
                 if (lane == 0) found[round][wave] = near;
             }
             __syncthreads();
-            const int count = pending - base < kLinkThreads / 64 ? pending - base : kLinkThreads / 64;
+            const int count = pending - base < kOwnerWaves ? pending - base : kOwnerWaves;
             for (int q = 0; q < count; ++q) {
                 const int k = queue[base + q];
-                if ((k & (kLinkThreads - 1)) == t) {
+                if (owner_thread(k) == t) {
                     const Cand got = found[round][q];
-                    const int sk = k >> 10;
+                    const int sk = slot_of(k);
 #pragma unroll
                     for (int s = 0; s < SLOTS; ++s)
                         if (s == sk) cd[s] = got.d;
@@ -319,7 +299,7 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_kernel(double* W, const 
     }
 }
 
-__global__ __launch_bounds__(kLinkThreads) void linkage_cut_kernel(const int32_t* __restrict__ pair, const int32_t* __restrict__ usable,
+__global__ __launch_bounds__(kOwnerThreads) void linkage_cut_kernel(const int32_t* __restrict__ pair, const int32_t* __restrict__ usable,
                                                                    int n, int n_clusters, int32_t* __restrict__ labels,
                                                                    int32_t* cluster_sizes) {
     extern __shared__ int32_t lds[];
@@ -331,35 +311,35 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_cut_kernel(const int32_t
     if (t == 0) ucount = 0;
     __syncthreads();
     int mine = 0;
-    for (int v = t; v < n; v += kLinkThreads) {
+    for (int v = t; v < n; v += kOwnerThreads) {
         parent[v] = v;
         mine += usable[v] != 0 ? 1 : 0;
     }
-    for (int c = t; c < n_clusters; c += kLinkThreads) cluster_sizes[c] = 0;
+    for (int c = t; c < n_clusters; c += kOwnerThreads) cluster_sizes[c] = 0;
     if (mine != 0) atomicAdd(&ucount, mine);
     __syncthreads();
     const int merges = ucount > n_clusters ? ucount - n_clusters : 0;
-    for (int m = t; m < merges; m += kLinkThreads) {
+    for (int m = t; m < merges; m += kOwnerThreads) {
         const int a = pair[2 * m], b = pair[2 * m + 1];
         if (a >= 0 && a < b && b < n) parent[b] = a;  // (every b retires once: no two writers)
     }
     __syncthreads();
     for (int round = 0; round < kJumpRounds; ++round) {
-        for (int v = t; v < n; v += kLinkThreads) other[v] = parent[parent[v]];
+        for (int v = t; v < n; v += kOwnerThreads) other[v] = parent[parent[v]];
         __syncthreads();
         int32_t* swap = parent;
         parent = other;
         other = swap;
     }
     // a cluster's root is its lowest row: the clusters in ascending order of their lowest row are the roots in ascending order
-    const int per = (n + kLinkThreads - 1) / kLinkThreads;
+    const int per = (n + kOwnerThreads - 1) / kOwnerThreads;
     const int lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
     int roots = 0;
     for (int v = lo; v < hi; ++v) roots += (usable[v] != 0 && parent[v] == v) ? 1 : 0;
-    int number = block_exclusive_scan<kLinkThreads>(roots, scan, nullptr);
+    int number = block_exclusive_scan<kOwnerThreads>(roots, scan, nullptr);
     for (int v = lo; v < hi; ++v) other[v] = (usable[v] != 0 && parent[v] == v) ? number++ : -1;
     __syncthreads();
-    for (int v = t; v < n; v += kLinkThreads) {
+    for (int v = t; v < n; v += kOwnerThreads) {
         int label = -1;
         if (usable[v] != 0) label = other[tree_root(parent, v, n)];
         labels[v] = label;
@@ -367,23 +347,23 @@ __global__ __launch_bounds__(kLinkThreads) void linkage_cut_kernel(const int32_t
     }
 }
 
-__global__ __launch_bounds__(kLinkThreads) void linkage_pick_kernel(const int32_t* __restrict__ labels,
+__global__ __launch_bounds__(kOwnerThreads) void linkage_pick_kernel(const int32_t* __restrict__ labels,
                                                                     const int32_t* __restrict__ cluster_sizes,
                                                                     const double* __restrict__ height, int n,
                                                                     int32_t* __restrict__ admitted, int32_t* __restrict__ admitted_out,
                                                                     LinkageInfo* __restrict__ info) {
-    __shared__ int red[kLinkThreads];
+    __shared__ int red[kOwnerThreads];
     const int t = threadIdx.x;
     const int n0 = cluster_sizes[0], n1 = cluster_sizes[1];
     const int winner = n1 > n0 ? 1 : 0;               // a tie: label 0, the cluster of the lowest usable row
     int count = 0;
-    for (int v = t; v < n; v += kLinkThreads) {
+    for (int v = t; v < n; v += kOwnerThreads) {
         const int a = labels[v] == winner ? 1 : 0;
         admitted[v] = a;
         if (admitted_out != nullptr) admitted_out[v] = a;
         count += a;
     }
-    const int total = block_sum<int, kLinkThreads>(count, red);
+    const int total = block_sum<int, kOwnerThreads>(count, red);
     if (t == 0) {
         const int u = n0 + n1;
         info->admitted = total;
@@ -398,13 +378,13 @@ template <int SLOTS>
 int launch_linkage_slots(const LinkageScratch& t, int n, int method, int32_t* pair, double* height, int32_t* size, LinkageInfo* info,
                          hipStream_t stream) {
     if (method == BYZ_LINKAGE_AVERAGE)
-        linkage_kernel<SLOTS, BYZ_LINKAGE_AVERAGE><<<1, kLinkThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height, size,
+        linkage_kernel<SLOTS, BYZ_LINKAGE_AVERAGE><<<1, kOwnerThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height, size,
                                                                                    info);
     else if (method == BYZ_LINKAGE_COMPLETE)
-        linkage_kernel<SLOTS, BYZ_LINKAGE_COMPLETE><<<1, kLinkThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height,
+        linkage_kernel<SLOTS, BYZ_LINKAGE_COMPLETE><<<1, kOwnerThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height,
                                                                                     size, info);
     else
-        linkage_kernel<SLOTS, BYZ_LINKAGE_SINGLE><<<1, kLinkThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height, size,
+        linkage_kernel<SLOTS, BYZ_LINKAGE_SINGLE><<<1, kOwnerThreads, 0, stream>>>(t.W, t.usable, t.near_d, t.near_p, n, pair, height, size,
                                                                                   info);
     return check_launch("linkage_kernel");
 }
@@ -446,7 +426,7 @@ int launch_linkage(byz_ctx* ctx, const LinkageScratch& t, const float* dist, int
             BYZ_HIP(hipMemcpyAsync(usable_out, t.usable, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     }
     KernelTimer timer(ctx, BYZ_K_MISC, stream);
-    const int per = static_cast<int>(ceil_div(n, kLinkThreads));
+    const int per = static_cast<int>(ceil_div(n, kOwnerThreads));
     const int ni = static_cast<int>(n);
     if (per <= 1) return launch_linkage_slots<1>(t, ni, method, pair, height, size, t.info, stream);
     if (per <= 2) return launch_linkage_slots<2>(t, ni, method, pair, height, size, t.info, stream);
@@ -461,9 +441,9 @@ int launch_linkage_cut(byz_ctx* ctx, const int32_t* pair, int64_t n, const int32
     BYZ_REQUIRE(pair && usable && labels && cluster_sizes && n >= 2 && n <= kFlameMaxRows && n_clusters >= 1 && n_clusters <= n,
                 "linkage cut: bad arguments (n = %lld, clusters = %lld)", (long long)n, (long long)n_clusters);
     KernelTimer timer(ctx, BYZ_K_ROW_SORT, stream);
-    const int lds_bytes = static_cast<int>((2 * n + kLinkThreads) * sizeof(int32_t));
+    const int lds_bytes = static_cast<int>((2 * n + kOwnerThreads) * sizeof(int32_t));
     BYZ_HIP(allow_dynamic_lds(ctx, reinterpret_cast<const void*>(linkage_cut_kernel), lds_bytes));
-    linkage_cut_kernel<<<1, kLinkThreads, lds_bytes, stream>>>(pair, usable, static_cast<int>(n), static_cast<int>(n_clusters), labels,
+    linkage_cut_kernel<<<1, kOwnerThreads, lds_bytes, stream>>>(pair, usable, static_cast<int>(n), static_cast<int>(n_clusters), labels,
                                                               cluster_sizes);
     return check_launch("linkage_cut_kernel");
 }
@@ -474,7 +454,7 @@ int launch_clipped_clustering_select(byz_ctx* ctx, const LinkageScratch& t, cons
     BYZ_TRY(launch_linkage(ctx, t, dist, n, method, fill, t.pair, t.height, t.size, nullptr, stream));
     BYZ_TRY(launch_linkage_cut(ctx, t.pair, n, t.usable, 2, t.labels, t.cluster_sizes, stream));
     KernelTimer timer(ctx, BYZ_K_ROW_SORT, stream);
-    linkage_pick_kernel<<<1, kLinkThreads, 0, stream>>>(t.labels, t.cluster_sizes, t.height, static_cast<int>(n), t.admitted,
+    linkage_pick_kernel<<<1, kOwnerThreads, 0, stream>>>(t.labels, t.cluster_sizes, t.height, static_cast<int>(n), t.admitted,
                                                        admitted_out, t.info);
     return check_launch("linkage_pick_kernel");
 }

@@ -14,6 +14,9 @@
 //           otherwise.  For the kernels that RANK by key and never read a value back: Multi-Krum's scores (multi_krum.hip), NNM's
 //           distances (nnm.hip), DnC's fp64 scores (dnc.hip).  Equal values must tie (and fall to the index in the key's low
 //           half) and a NaN must lose to everything, as `<` on the values would have it; not invertible.
+//           The fp64 total map is read back (value_of_total_key) by the two that sort doubles by value: FABA's removal key
+//           (faba.hip, owner_loop.hpp; its sums are never a NaN and never -0.0, so the map is one to one there) and AFA's median
+//           (afa.hip; the zeros' key gives +0.0).
 // Everything but block_exclusive_scan also compiles for the host with a plain C++17 compiler (tests/order_keys_check.cpp).
 #pragma once
 
@@ -41,7 +44,7 @@ BYZ_KEY_FN uint32_t ordered_bits_total(float v) {
     if (v != v) return 0xffffffffu;                    // any NaN: behind +inf (0xff800000)
     return ordered_bits(v == 0.0f ? 0.0f : v);         // -0.0 == +0.0
 }
-BYZ_KEY_FN uint64_t ordered_bits_total(double v) {      // (no plain fp64 map to build on: nothing sorts doubles by value)
+BYZ_KEY_FN uint64_t ordered_bits_total(double v) {      // (no plain fp64 map to build on: FABA and AFA's median use this one)
     constexpr uint64_t kSign = uint64_t{1} << 63;
     if (v != v) return ~uint64_t{0};
     uint64_t b = __builtin_bit_cast(uint64_t, v);

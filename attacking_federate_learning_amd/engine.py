@@ -2842,6 +2842,14 @@ class Engine:
         rows = buf.numpy()[: n.value * 64].reshape(n.value, 64)
         return rows[11:] if reductions else rows[:11]
 
+    def owner_loop_selftest(self):
+        """The rows of 1024 words that owner_loop.hpp's self-test kernel writes, one word a thread of its one workgroup."""
+        buf = DeviceBuffer(self, (64 * 1024,), np.int32)
+        n = ctypes.c_int32(0)
+        _check(self.lib.byz_selftest_owner_loop_dev(self.ctx, buf.ptr, ctypes.byref(n), None))
+        self.synchronize()
+        return buf.numpy()[: n.value * 1024].reshape(n.value, 1024)
+
 
 _default = None
 

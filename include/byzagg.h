@@ -1436,6 +1436,10 @@ const char* byz_kernel_name(int kernel);
 /* after one of lane_exchange.hpp's wave reductions (tests/test_gpu_parity.py has the list). */
 int byz_selftest_lane_exchange_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_patterns_host,
                                    void* stream);
+/* The one-workgroup loops' shared pieces (owner_loop.hpp) on one workgroup of 1024 threads.  out_dev: room for 64 rows of   */
+/* 1024 int32; n_rows (<= 64) rows are written, entry [r*1024 + t] = thread t's word of row r: the generic exchange, the lane */
+/* fold, two block exchanges in a row and the block sum (tests/test_gpu_parity.py has the list).                              */
+int byz_selftest_owner_loop_dev(byz_ctx* ctx, int32_t* out_dev, int32_t* n_rows_host, void* stream);
 
 /* ---- the unit table of the long-K Gram's f16x2 tile kernel (host arithmetic; tests and scripts) -------------------- */
 /* What byz_gram_dev hands its tile kernel for a matrix of n_rows rows (the whole triangle, deferred slab update): one   */

@@ -104,6 +104,60 @@ def test_lane_exchange_patterns(eng):
     assert next(rows, None) is None
 
 
+def test_owner_loop_pieces(eng):
+    """owner_loop.hpp's pieces on one workgroup of 1024 threads, every thread's result against numpy restatements."""
+    got = eng.owner_loop_selftest()
+    assert got.shape == (44, 1024)
+    rows = iter(got)
+    t = np.arange(1024, dtype=np.uint64)
+    lane, wave = (t & np.uint64(63)).astype(np.int64), (t >> np.uint64(6)).astype(np.int64)
+    ti = t.astype(np.int64)
+
+    def u32(what, want):
+        assert next(rows).view(np.uint32).tolist() == np.asarray(want).astype(np.uint32).tolist(), what
+
+    def u64(what, want):                     # the row of low words, then the row of high words
+        lo, hi = next(rows).view(np.uint32).astype(np.uint64), next(rows).view(np.uint32).astype(np.uint64)
+        assert ((hi << np.uint64(32)) | lo).tolist() == np.asarray(want).view(np.uint64).tolist(), what
+
+    def key(what, hi, lo):                   # a three-word key: hi (64 bits), then lo (32)
+        u64(what + ', hi', hi)
+        u32(what + ', lo', lo)
+
+    # (a) the exchange of a 64-bit value and of a three-word struct
+    with np.errstate(over='ignore'):
+        wide = t * np.uint64(0x0001000300050007) + np.uint64(0x1234)
+    three_hi, three_lo = wide ^ np.uint64(0xffff), (t * np.uint64(40503) + np.uint64(7)) & np.uint64(0xffffffff)
+    for m in (1, 2, 4, 8, 16, 32):
+        u64('lane_xor<%d> of 64 bits' % m, wide[ti ^ m])
+        key('lane_xor<%d> of a struct' % m, three_hi[ti ^ m], three_lo[ti ^ m])
+
+    # (b) the maximum of (hi, lo) over the wave and over every 16 lanes: eight-way ties on hi inside a wave
+    hi = ((37 * lane + 11 + wave) % 8).astype(np.uint64)
+    lo = (t * np.uint64(2654435761)) & np.uint64(0xffffffff)
+    assert all((hi[64 * w: 64 * w + 64] == hi[64 * w: 64 * w + 64].max()).sum() == 8 for w in range(16))
+    packed = [(int(h), int(l)) for h, l in zip(hi, lo)]
+    for width in (64, 16):
+        best = [max(packed[i - i % width: i - i % width + width]) for i in range(1024)]
+        key('lanes_fold<%d>' % (width // 2), np.array([b[0] for b in best], np.uint64), np.array([b[1] for b in best], np.uint64))
+
+    # (c) two block exchanges in a row: the minimum of (t ^ c) << 32 | t is thread c's, in wave 5 and then in wave 11
+    for c in (5 * 64 + 17, 11 * 64 + 3):
+        u64('block exchange, winner %d' % c, np.full(1024, c, np.uint64))
+
+    # (d) the block sum: a wave's 64 chains folded 32, 16, ..., 1, the 16 waves' sums 8, 4, 2, 1 (every addition rounds)
+    x = (1.0 + lane / 3.0) * (1 << (wave % 5)).astype(np.float64)
+    for what, chain in (('block sum', x), ('the next block sum', x / 7.0)):
+        v = chain.reshape(16, 64).copy()
+        for m in (32, 16, 8, 4, 2, 1):
+            v = v + v[:, np.arange(64) ^ m]
+        v = v[np.arange(64) & 15, 0].copy()          # what a lane reads back: the sum of wave lane & 15 (the same in every wave)
+        for m in (8, 4, 2, 1):
+            v = v + v[np.arange(64) ^ m]
+        u64(what, np.tile(v, 16))
+    assert next(rows, None) is None
+
+
 # ---- golden vectors minted from the reference -------------------------------------------------------
 def test_golden_no_defense(defences, golden):
     c = golden['nodef_7x130']
