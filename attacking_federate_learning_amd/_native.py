@@ -76,6 +76,12 @@ class AfaParams(ctypes.Structure):
     _fields_ = [('xi0', ctypes.c_double), ('delta_xi', ctypes.c_double), ('max_rounds', c_i64)]
 
 
+class MinmaxParams(ctypes.Structure):
+    """byz_minmax_params: the kind (0 Min-Max, 1 Min-Sum), the perturbation (0 unit, 1 std, 2 sign, 3 custom), partial knowledge,
+    and whether the caller supplies the distance matrix."""
+    _fields_ = [('kind', ctypes.c_int), ('perturbation', ctypes.c_int), ('partial', ctypes.c_int), ('dist_given', ctypes.c_int)]
+
+
 class AurorParams(ctypes.Structure):
     """byz_auror_params: the indicative gap, the share of votes that removes a row, the sweeps' cap and the accumulate switch."""
     _fields_ = [('alpha', ctypes.c_double), ('tau', ctypes.c_double), ('max_iter', c_i64), ('accumulate', c_i64)]
@@ -254,6 +260,11 @@ _PROTOTYPES = {
     'byz_fang_trmean_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(FangParams), c_vp],
     'byz_fang_trmean_attack_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(FangParams), c_vp],
     'byz_fang_krum_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(ctypes.c_double), c_vp, c_vp, c_vp, c_vp],
+    'byz_row_moments_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_minmax_attack_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(MinmaxParams), c_vp, c_vp, c_vp],
+    'byz_minmax_attack_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _P(MinmaxParams), c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_minmax_info': [c_vp, _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(c_i64), _P(c_i64), _P(c_i32), _P(c_i32)],
+    'byz_minmax_attack_host': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(MinmaxParams), c_vp, c_vp],
     'byz_fang_krum_info': [c_vp, _P(ctypes.c_double), _P(ctypes.c_double), _P(c_i64), _P(c_i64), _P(c_i32)],
     'byz_timing_enable': [c_vp, c_int],
     'byz_timing_reset': [c_vp],

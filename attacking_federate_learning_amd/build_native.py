@@ -21,7 +21,7 @@ SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_wind
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip',
            'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip', 'nnm.hip', 'robust_lr.hip', 'topk.hip',
            'bucketing.hip', 'signguard.hip', 'noise.hip', 'flame.hip', 'manhattan.hip', 'multi_metrics.hip', 'linkage.hip',
-           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip', 'auror.hip']
+           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip', 'auror.hip', 'minmax.hip']
 # median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
 # dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
 # LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a
@@ -65,6 +65,8 @@ EXTRA_FLAGS = {'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000
                'auror.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off'],
                # the Fang attacks: no_defense's chain, the draw A + u (B - A) and the Krum attack's distances, every product rounded
                'fang.hip': ['-ffp-contract=off'],
+               # Min-Max / Min-Sum: the roots' stated operations; fl32(mu + gamma p) with the product rounded first
+               'minmax.hip': ['-ffp-contract=off'],
                # bucketing's means are no_defense's chain per bucket
                'bucketing.hip': ['-ffp-contract=off'],
                # SignGuard: q has row_dots' bits; the selection's stated order of operations

@@ -2543,6 +2543,162 @@ int byz_fang_krum_info(byz_ctx* ctx, double* lambda0, double* lambda, int64_t* s
     return BYZ_OK;
 }
 
+// ---- the Min-Max / Min-Sum attacks of Shejwalkar and Houmansadr (NDSS 2021; beyond the reference) ----------------------------------
+namespace {
+
+// What the attacks keep in ctx->minmax.  a, b and c lie behind one another: one all-reduce's worth.
+struct MinmaxScratch {
+    float *mu, *sigma, *p;           // n_cols each
+    double* abc;                     // 2 r + 1: a, b, c
+    double* norm_sq;                 // 1: |mu|^2
+    float *dmax, *dmax_part;         // 1; kMinmaxMaxPartials: the distance maximum and its workgroups' values
+};
+
+int minmax_workspace(byz_ctx* ctx, int64_t n_cols, int64_t r, MinmaxScratch* out) {
+    Carve c;
+    c.take(&out->mu, n_cols);
+    c.take(&out->sigma, n_cols);
+    c.take(&out->p, n_cols);
+    c.take(&out->abc, 2 * r + 1);
+    c.take(&out->norm_sq, 1);
+    c.take(&out->dmax, 1);
+    c.take(&out->dmax_part, kMinmaxMaxPartials);
+    return c.commit(ctx->minmax);
+}
+
+int check_minmax(const char* who, const byz_minmax_params* params, int64_t n_rows, int64_t n_attackers, const void* p_custom) {
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (params->kind != BYZ_MINMAX_KIND_MINMAX && params->kind != BYZ_MINMAX_KIND_MINSUM) {
+        set_error("%s: unknown kind %d", who, params->kind);
+        return BYZ_E_INVALID;
+    }
+    if (params->perturbation < BYZ_MINMAX_PERTURB_UNIT || params->perturbation > BYZ_MINMAX_PERTURB_CUSTOM) {
+        set_error("%s: unknown perturbation %d", who, params->perturbation);
+        return BYZ_E_INVALID;
+    }
+    if ((params->perturbation == BYZ_MINMAX_PERTURB_CUSTOM) != (p_custom != nullptr)) {
+        set_error("%s: the custom perturbation and its vector come together or not at all", who);
+        return BYZ_E_INVALID;
+    }
+    if (n_attackers < 0 || n_attackers > n_rows) {
+        set_error("%s: %lld attacker rows of %lld rows", who, (long long)n_attackers, (long long)n_rows);
+        return BYZ_E_INVALID;
+    }
+    if (params->partial && n_attackers < 1) {
+        set_error("%s: partial knowledge needs an attacker row", who);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// The whole call; allreduce == nullptr: one GPU holds every column.  Nothing here waits for the device but the distances.
+int minmax_attack(byz_ctx* ctx, float* G, int64_t n, int64_t n_cols, int64_t ld, int64_t m, const byz_minmax_params* params,
+                  const float* p_custom, float* dist, byz_allreduce_f64_fn allreduce, void* user, void* stream, const char* who) {
+    BYZ_TRY(check_minmax(who, params, n, m, p_custom));
+    const bool max_kind = params->kind == BYZ_MINMAX_KIND_MINMAX;
+    BYZ_REQUIRE(!(max_kind && params->dist_given) || dist, "%s: dist_given without a distance matrix", who);
+    if (m == 0) return BYZ_OK;
+    const int64_t r = params->partial ? m : n;
+    BYZ_TRY(check_row_ceiling(who, r));
+    hipStream_t s = as_stream(stream);
+    MinmaxScratch w;
+    BYZ_TRY(minmax_workspace(ctx, n_cols, r, &w));
+    RowScratch rows;
+    BYZ_TRY(row_scratch(ctx, r, n_cols, &rows, 2));
+    double *a = w.abc, *b = w.abc + r, *c = w.abc + 2 * r;
+    BYZ_TRY(launch_column_drift(ctx, G, r, n_cols, ld, 0.0f, nullptr, w.mu, w.sigma, s));
+    const float* p = p_custom;
+    if (p == nullptr) {
+        if (params->perturbation == BYZ_MINMAX_PERTURB_UNIT) {
+            BYZ_TRY(launch_row_sqdist(ctx, w.mu, 1, n_cols, n_cols, nullptr, rows.root, w.norm_sq, nullptr, nullptr, s));
+            if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, w.norm_sq, 1, stream, "minmax attack (the mean's norm)"));
+        }
+        BYZ_TRY(launch_perturbation(ctx, w.mu, w.sigma, w.norm_sq, params->perturbation, n_cols, w.p, s));
+        p = w.p;
+    }
+    BYZ_TRY(launch_row_sqdist(ctx, p, 1, n_cols, n_cols, nullptr, rows.root, c, nullptr, nullptr, s));
+    BYZ_TRY(launch_row_moments(ctx, G, r, n_cols, ld, w.mu, p, rows.partials, a, b, s));
+    if (allreduce != nullptr) BYZ_TRY(reduce_over_ranks(allreduce, user, w.abc, 2 * r + 1, stream, "minmax attack (moments)"));
+    if (max_kind) {
+        if (r == 1) {
+            BYZ_HIP(hipMemsetAsync(w.dmax, 0, sizeof(float), s));
+        } else if (params->dist_given) {
+            BYZ_TRY(launch_dist_max(ctx, dist, r, n, w.dmax_part, w.dmax, s));
+        } else {
+            if (dist == nullptr) BYZ_TRY(ctx->dist.ensure(static_cast<size_t>(r) * r * sizeof(float)));      // (distances() sizes the Gram itself)
+            float* d = dist ? dist : ctx->dist.as<float>();
+            BYZ_TRY(distances(ctx, G, r, n_cols, ld, allreduce, user, d, stream));
+            BYZ_TRY(launch_dist_max(ctx, d, r, r, w.dmax_part, w.dmax, s));
+        }
+    }
+    mark(ctx, kReportMinmax, s);
+    BYZ_TRY(launch_minmax_solve(ctx, a, b, c, w.dmax, r, params->kind, s));
+    return launch_minmax_fill(ctx, G, m, n_cols, ld, w.mu, p, s);
+}
+
+}  // namespace
+
+int byz_row_moments_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* z, const float* p,
+                        double* a, double* b, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "row_moments"));
+    BYZ_REQUIRE(z && p && a && b, "row_moments: null vector or output");
+    BYZ_TRY(check_row_ceiling("row_moments", n_rows));
+    RowScratch t;
+    BYZ_TRY(row_scratch(ctx, n_rows, n_cols, &t, 2));
+    return launch_row_moments(ctx, G, n_rows, n_cols, ld, z, p, t.partials, a, b, as_stream(stream));
+}
+
+int byz_minmax_attack_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                          const byz_minmax_params* params, const float* p_custom, float* dist, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "minmax_attack"));
+    return minmax_attack(ctx, G, n_rows, n_cols, ld, n_attackers, params, p_custom, dist, nullptr, nullptr, stream, "minmax_attack");
+}
+
+int byz_minmax_attack_sharded_dev(byz_ctx* ctx, float* G, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                                  const byz_minmax_params* params, const float* p_custom, float* dist, byz_allreduce_f64_fn allreduce,
+                                  void* user, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "minmax_attack_sharded"));
+    BYZ_REQUIRE(allreduce, "minmax_attack_sharded: null all-reduce");
+    return minmax_attack(ctx, G, n_rows, n_cols, ld, n_attackers, params, p_custom, dist, allreduce, user, stream,
+                         "minmax_attack_sharded");
+}
+
+int byz_minmax_info(byz_ctx* ctx, double* gamma, double* bound, double* c, int64_t* binding_row, int64_t* known_rows,
+                    int32_t* degenerate, int32_t* broken) {
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportMinmax, "minmax_info: no Min-Max or Min-Sum attack on this context yet", &all));
+    const MinmaxReport& info = all.minmax;
+    if (gamma) *gamma = info.gamma;
+    if (bound) *bound = info.bound;
+    if (c) *c = info.c;
+    if (binding_row) *binding_row = info.row;
+    if (known_rows) *known_rows = info.r;
+    if (degenerate) *degenerate = info.degenerate;
+    if (broken) *broken = info.broken;
+    return BYZ_OK;
+}
+
+int byz_minmax_attack_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t n_attackers,
+                           const byz_minmax_params* params, const float* p_custom_host, float* vector_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "minmax_attack"));
+    BYZ_TRY(check_minmax("minmax_attack", params, n_rows, n_attackers, p_custom_host));
+    BYZ_REQUIRE(vector_host && n_attackers >= 1, "minmax_attack: null output or no attacker row");
+    HostStage st(ctx);
+    float* p_dev = nullptr;
+    st.in(&p_dev, p_custom_host, n_cols);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_minmax_attack_dev(ctx, st.G(), n_rows, n_cols, n_cols, n_attackers, params, p_dev, nullptr, st.stream()));
+    BYZ_HIP(hipMemcpyAsync(vector_host, st.G(), static_cast<size_t>(n_cols) * sizeof(float), hipMemcpyDeviceToHost, st.stream()));
+    return st.finish();
+}
+
 int byz_column_chain_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* carry_in,
                          const float* mean, float* out_sum, void* stream) {
     BYZ_TRY(enter(ctx));

@@ -175,6 +175,8 @@ struct byz_ctx {
     double fang_lambda0 = 0.0, fang_lambda = 0.0;
     int64_t fang_steps = 0, fang_chosen = -1;
     int32_t fang_succeeded = 0;
+    byz::Buffer minmax;          // the Min-Max / Min-Sum attacks, carved (api.hip: minmax_workspace): mu, sigma and p, the moments a, b
+                                 // and c in one all-reduce's worth, |mu|^2, the distance maximum and its workgroups' values
     byz::Buffer phocas;          // Phocas, carved (api.hip: byz_phocas_dev): the rank-trimmed mean the window is taken around, when the
                                  // caller does not ask for it
     // large_rows.hip: more than 16,384 rows
@@ -427,6 +429,23 @@ double fang_lambda0(double s_min, double q_max, int64_t n, int64_t c, int64_t n_
 // 0 between attackers, +inf on their diagonal
 int launch_fang_krum_fill(byz_ctx* ctx, float* dist, int64_t n, int64_t c, int64_t n_cols, const double* q, const double* t,
                           double lambda, hipStream_t stream);
+// geomed.hip, rowsq's kernel template in its third form: a[i] = sum_c ((double)x_ic - (double)mu_c)^2 (launch_row_sqdist's bits)
+// and b[i] = sum_c (double)p_c ((double)mu_c - (double)x_ic) in one read of G (partials: 2 * chunks * n_rows)
+int launch_row_moments(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* mu, const float* p,
+                       double* partials, double* a, double* b, hipStream_t stream);
+// minmax.hip: the Min-Max / Min-Sum attacks of Shejwalkar & Houmansadr.  The scalars of a call: DeviceScalars::minmax.
+constexpr int kMinmaxMaxPartials = 1024;     // workgroups of the distance maximum's first launch at most
+// p from mu, sigma and *norm_sq = |mu|^2 (minmax_solve.hpp: kPerturbUnit, kPerturbStd, kPerturbSign)
+int launch_perturbation(byz_ctx* ctx, const float* mu, const float* sigma, const double* norm_sq, int kind, int64_t n_cols, float* p,
+                        hipStream_t stream);
+// *dmax = the largest finite entry off the diagonal of the leading r x r block of dist (row stride ld); 0 when there is none
+int launch_dist_max(byz_ctx* ctx, const float* dist, int64_t r, int64_t ld, float* partials, float* dmax, hipStream_t stream);
+// gamma and the report from the r rows' moments, c and (Min-Max) *dmax
+int launch_minmax_solve(byz_ctx* ctx, const double* a, const double* b, const double* c, const float* dmax, int64_t r, int kind,
+                        hipStream_t stream);
+// rows 0 .. n_attackers - 1 = fl32(mu + gamma p) with the report's gamma; nothing when the report says broken
+int launch_minmax_fill(byz_ctx* ctx, float* G, int64_t n_attackers, int64_t n_cols, int64_t ld, const float* mu, const float* p,
+                       hipStream_t stream);
 // flame.hip: FLAME's clustering stage.  The scalars of a call: DeviceScalars::flame.
 constexpr int64_t kFlameMaxRows = kOwnerMaxRows;     // Prim's one workgroup owns 1024 x 16 vertices; the union-find fills the LDS
 constexpr int64_t kFlameMaxSamples = 32;     // rounds of the core distance's selection at most

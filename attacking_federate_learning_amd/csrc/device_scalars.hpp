@@ -100,6 +100,13 @@ struct AurorReport {                 // byz_auror_select_dev and byz_auror_dev: 
     int32_t bad_rows, pad;           // the rows with a non-finite value
     double kept_f64;                 // the divisor of the sum
 };
+struct MinmaxReport {                // byz_minmax_attack_dev: what minmax_solve_kernel decided, what the fill reads
+    double gamma;                    // NaN when broken, 0 when degenerate
+    double bound;                    // Min-Max: T = Dmax^2; Min-Sum: S = r max a_i + A
+    double c;                        // |p|^2
+    int32_t row, r;                  // the binding row (-1: none); the known rows
+    int32_t degenerate, broken;      // c == 0 or r == 1; a moment, c, gamma or the bound is not finite
+};
 
 struct DeviceScalars {
     CoreScalars core;
@@ -118,6 +125,7 @@ struct DeviceScalars {
     FabaReport faba;
     AfaReport afa;
     AurorReport auror;
+    MinmaxReport minmax;
 };
 
 // What a read-back as bytes, and a 64-bit store or atomic of a kernel, rely on.  No member is padded by the compiler: the sizes
@@ -127,7 +135,8 @@ static_assert(sizeof(CoreScalars) % sizeof(int32_t) == 0 && sizeof(DeviceScalars
 static_assert(sizeof(DeviceScalars) == sizeof(CoreScalars) + sizeof(GeomedReport) + sizeof(DncReport) + sizeof(CclipReport) +
                                            sizeof(FltrustReport) + sizeof(NnmReport) + sizeof(RlrReport) + sizeof(SgReport) +
                                            sizeof(TopkReport) + sizeof(WeakDpReport) + sizeof(FlameInfo) + sizeof(MmInfo) +
-                                           sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport) + sizeof(AurorReport),
+                                           sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport) + sizeof(AurorReport) +
+                                           sizeof(MinmaxReport),
               "no padding between the reports");
 #define BYZ_AT(member) offsetof(DeviceScalars, member)
 constexpr size_t kEightByteFields[] = {
@@ -136,7 +145,8 @@ constexpr size_t kEightByteFields[] = {
     BYZ_AT(flame.admitted_f64), BYZ_AT(flame.clip), BYZ_AT(mm.det), BYZ_AT(linkage.top_height), BYZ_AT(linkage.second_height),
     BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64),
     BYZ_AT(afa.mean), BYZ_AT(afa.med), BYZ_AT(afa.sd), BYZ_AT(afa.thr), BYZ_AT(afa.divisor),
-    BYZ_AT(auror.indicative), BYZ_AT(auror.clustered), BYZ_AT(auror.capped), BYZ_AT(auror.kept_f64)};
+    BYZ_AT(auror.indicative), BYZ_AT(auror.clustered), BYZ_AT(auror.capped), BYZ_AT(auror.kept_f64),
+    BYZ_AT(minmax.gamma), BYZ_AT(minmax.bound), BYZ_AT(minmax.c)};
 #undef BYZ_AT
 constexpr bool eight_byte_fields_aligned() {
     for (size_t at : kEightByteFields)
@@ -146,11 +156,11 @@ constexpr bool eight_byte_fields_aligned() {
 static_assert(eight_byte_fields_aligned(), "every double and 64-bit counter sits at an 8-byte offset");
 
 // the reports an info call reads; byz_ctx::last[kind]: the stream of the last call that wrote it, and whether there was one
-// (kReportAuror and kReportAfa stand in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of
+// (kReportMinmax, kReportAuror and kReportAfa stand in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of
 // kReportCount; the kinds index byz_ctx::last and nothing else, so their numbers are free)
 enum ReportKind {
     kReportGeomed, kReportDnc, kReportCclip, kReportFltrust, kReportNnm, kReportRlr, kReportSignguard, kReportTopk, kReportWeakDp,
-    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportAuror, kReportAfa,
+    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportMinmax, kReportAuror, kReportAfa,
     kReportFaba, kReportCount
 };
 struct LastCall { hipStream_t stream = nullptr; bool ran = false; };

@@ -4,7 +4,7 @@
 // Two streaming passes over G, nothing of order N^2.
 //
 //   dots    p_i = x_i . r and q_i = |x_i|^2 in one read of G: rowsq's kernel template with two accumulators a row
-//           (rowsq_partial_kernel<VEC4, true>, geomed.hip, where launch_row_dots lives beside launch_row_sqdist);
+//           (rowsq_partial_kernel<VEC4, kRowsqDots>, geomed.hip, where launch_row_dots lives beside launch_row_sqdist);
 //           q0 = |r|^2 is launch_row_sqdist on the 1 x n_cols matrix r.
 //   trust   one workgroup, here: c_i = p_i / (sqrt(q_i) * sqrt(q0)), ts_i = max(c_i, 0), w_i = ts_i * (sqrt(q0) / sqrt(q_i)),
 //           T = sum ts_i in a fixed order; T and the counts go to the context's report (device_scalars.hpp).

@@ -16,7 +16,9 @@
 //           kRowsCentred): the same walk, the same launch shape, another product and another last line.
 //   dots    FLTrust's first pass (fltrust.hip has its trust scores): p[i] = sum_c (double)x_ic * (double)r_c and
 //           q[i] = sum_c (double)x_ic^2 in one read of G.  rowsq's kernel template with two accumulators a row
-//           (rowsq_partial_kernel<VEC4, true>): the same geometry, the same order of additions, partials[2][chunk][row].
+//           (rowsq_partial_kernel<VEC4, kRowsqDots>): the same geometry, the same order of additions, partials[2][chunk][row].
+//   moments the Min-Max / Min-Sum attacks' pass (minmax.hip): a[i] = sum_c ((double)x_ic - (double)mu_c)^2, rowsq's bits, and
+//           b[i] = sum_c (double)p_c * ((double)mu_c - (double)x_ic) in one read of G: the template's third form.
 //   scaled  FLTrust's second pass: out[c] = T > 0 ? fl32(S_c / T) : 0, S_c as wmean's, T read from one device double.
 //           weighted_rows_kernel's third mode (kRowsScaled).
 //   step    one workgroup: d_i = sqrt(sq_i), F = sum of d over the active rows (fixed order), the stop test
@@ -51,36 +53,50 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int64_t c, in
     }
 }
 
-// DOTS = false: partials[chunk * n_rows + row]; z == nullptr: the distance to the origin.
-// DOTS = true: z is FLTrust's root (never null); partials[chunk * n_rows + row] is the row's dot product with it over the
-// chunk, partials[(chunks + chunk) * n_rows + row] the row's own squared norm (chunks = gridDim.y).
-template <bool VEC4, bool DOTS>
+// The three forms of one (block of 32 rows, chunk of columns) pass; every form has the same geometry and the same order of
+// additions, and the forms with two sums a row write partials[2][chunk][row] (chunks = gridDim.y).
+//   kRowsqDist     partials[chunk * n_rows + row] = the row's squared distance to z over the chunk; z == nullptr: to the origin.
+//   kRowsqDots     z is FLTrust's root (never null): plane 0 the row's dot product with it, plane 1 the row's own squared norm.
+//   kRowsqMoments  z is a centre mu, p a direction (neither null), d = (double)mu - (double)x: plane 0 the sum of d * d -- the
+//                  bits of kRowsqDist's sum, the square of a difference does not see its sign -- plane 1 the sum of (double)p * d.
+//                  A lane keeps its 16 floats of p beside its 16 doubles of mu across the wave's 8 rows and converts them where
+//                  it multiplies: 16 registers instead of 32 (profiles/minmax_timing.md has the counts).
+constexpr int kRowsqDist = 0, kRowsqDots = 1, kRowsqMoments = 2;
+// the direction of the moments form travels behind the arguments that the three forms share
+__device__ __forceinline__ const float* rowsq_direction() { return nullptr; }
+__device__ __forceinline__ const float* rowsq_direction(const float* p_vec) { return p_vec; }
+template <bool VEC4, int FORM, typename... Direction>
 __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __restrict__ G, int64_t n_rows, int64_t n_cols,
                                                                  int64_t ld, const float* __restrict__ z, int64_t chunk_cols,
                                                                  double* __restrict__ partials, const int32_t* skip_if_set,
-                                                                 const int32_t* run_if_set) {
+                                                                 const int32_t* run_if_set, Direction... direction) {
+    static_assert(sizeof...(Direction) == (FORM == kRowsqMoments ? 1 : 0), "the moments form alone takes a direction");
+    constexpr bool TWO = FORM != kRowsqDist;
     if (gated_out(skip_if_set, run_if_set)) return;
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kRowBlock + wave * kRowsPerWave;
     if (row0 >= n_rows) return;
     const int64_t c_begin = static_cast<int64_t>(blockIdx.y) * chunk_cols;
     const int64_t c_end = c_begin + chunk_cols < n_cols ? c_begin + chunk_cols : n_cols;
+    [[maybe_unused]] const float* p_vec = rowsq_direction(direction...);
     double acc[kRowsPerWave];
-    [[maybe_unused]] double acc_q[DOTS ? kRowsPerWave : 1];
+    [[maybe_unused]] double acc_q[TWO ? kRowsPerWave : 1];
 #pragma unroll
     for (int r = 0; r < kRowsPerWave; ++r) acc[r] = 0.0;
-    if constexpr (DOTS) {
+    if constexpr (TWO) {
 #pragma unroll
         for (int r = 0; r < kRowsPerWave; ++r) acc_q[r] = 0.0;
     }
     for (int64_t w0 = c_begin; w0 < c_end; w0 += kWindow) {
         double zs[kSegs][4];
+        [[maybe_unused]] float ps[FORM == kRowsqMoments ? kSegs : 1][4];
 #pragma unroll
         for (int k = 0; k < kSegs; ++k) {
             float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (z != nullptr) load4<VEC4>(z, w0 + k * 256 + lane * 4, c_end, t);
 #pragma unroll
             for (int v = 0; v < 4; ++v) zs[k][v] = static_cast<double>(t[v]);
+            if constexpr (FORM == kRowsqMoments) load4<VEC4>(p_vec, w0 + k * 256 + lane * 4, c_end, ps[k]);
         }
 #pragma unroll
         for (int r = 0; r < kRowsPerWave; ++r) {
@@ -95,17 +111,21 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
                 for (int k = 0; k < kSegs; ++k)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
-                        if constexpr (DOTS) {
+                        if constexpr (FORM == kRowsqDots) {
                             const double xd = static_cast<double>(x[k][v]);
                             s = s + xd * zs[k][v];
                             s_q = s_q + xd * xd;
+                        } else if constexpr (FORM == kRowsqMoments) {
+                            const double d = zs[k][v] - static_cast<double>(x[k][v]);
+                            s = s + d * d;
+                            s_q = s_q + static_cast<double>(ps[k][v]) * d;
                         } else {
                             const double d = static_cast<double>(x[k][v]) - zs[k][v];
                             s = s + d * d;
                         }
                     }
                 acc[r] = acc[r] + s;
-                if constexpr (DOTS) acc_q[r] = acc_q[r] + s_q;
+                if constexpr (TWO) acc_q[r] = acc_q[r] + s_q;
             }
         }
     }
@@ -113,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void rowsq_partial_kernel(const float* __
     for (int r = 0; r < kRowsPerWave; ++r) {
         const double s = wave_sum_shfl(acc[r]);
         if (lane == 0 && row0 + r < n_rows) partials[static_cast<int64_t>(blockIdx.y) * n_rows + row0 + r] = s;
-        if constexpr (DOTS) {
+        if constexpr (TWO) {
             const double s_q = wave_sum_shfl(acc_q[r]);
             if (lane == 0 && row0 + r < n_rows)
                 partials[(static_cast<int64_t>(gridDim.y) + blockIdx.y) * n_rows + row0 + r] = s_q;
@@ -289,8 +309,8 @@ int launch_row_sqdist(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_co
     const bool vec4 = (ld % 4 == 0) && aligned16(G) && (z == nullptr || aligned16(z));
     const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
     KernelTimer t(ctx, BYZ_K_MISC, stream);
-    if (vec4) rowsq_partial_kernel<true, false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
-    else rowsq_partial_kernel<false, false><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    if (vec4) rowsq_partial_kernel<true, kRowsqDist><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
+    else rowsq_partial_kernel<false, kRowsqDist><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, z, chunk, partials, skip_if_set, run_if_set);
     BYZ_TRY(check_launch("rowsq_partial_kernel"));
     rowsq_finish_kernel<<<static_cast<unsigned>(ceil_div(n_rows, 256)), 256, 0, stream>>>(partials, n_rows, chunks, sq, nullptr,
                                                                                         skip_if_set, run_if_set);
@@ -307,12 +327,31 @@ int launch_row_dots(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols
     const bool vec4 = (ld % 4 == 0) && aligned16(G) && aligned16(r);
     const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
     KernelTimer t(ctx, BYZ_K_MISC, stream);
-    if (vec4) rowsq_partial_kernel<true, true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
-    else rowsq_partial_kernel<false, true><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
+    if (vec4) rowsq_partial_kernel<true, kRowsqDots><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
+    else rowsq_partial_kernel<false, kRowsqDots><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, r, chunk, partials, nullptr, nullptr);
     BYZ_TRY(check_launch("rowsq_partial_kernel (dots)"));
     rowsq_finish_kernel<<<dim3(static_cast<unsigned>(ceil_div(n_rows, 256)), 2), 256, 0, stream>>>(partials, n_rows, chunks, dot, sq,
                                                                                                  nullptr, nullptr);
     return check_launch("rowsq_finish_kernel (dots)");
+}
+
+// a[i] = sum_c ((double)x_ic - (double)mu_c)^2 (launch_row_sqdist's bits) and b[i] = sum_c (double)p_c * ((double)mu_c - (double)x_ic)
+// in one read of G; partials: 2 * chunks * n_rows (geomed_chunks' chunks)
+int launch_row_moments(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* mu, const float* p,
+                       double* partials, double* a, double* b, hipStream_t stream) {
+    BYZ_REQUIRE(G && mu && p && partials && a && b && n_rows > 0 && n_rows <= kLargeMaxRows && n_cols > 0 && ld >= n_cols,
+                "row moments: bad arguments");
+    int64_t chunk = 0;
+    const int chunks = geomed_chunks(ctx, n_rows, n_cols, &chunk);
+    const bool vec4 = (ld % 4 == 0) && aligned16(G) && aligned16(mu) && aligned16(p);
+    const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kRowBlock)), static_cast<unsigned>(chunks));
+    KernelTimer t(ctx, BYZ_K_MISC, stream);
+    if (vec4) rowsq_partial_kernel<true, kRowsqMoments><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, mu, chunk, partials, nullptr, nullptr, p);
+    else rowsq_partial_kernel<false, kRowsqMoments><<<grid, kThreads, 0, stream>>>(G, n_rows, n_cols, ld, mu, chunk, partials, nullptr, nullptr, p);
+    BYZ_TRY(check_launch("rowsq_partial_kernel (moments)"));
+    rowsq_finish_kernel<<<dim3(static_cast<unsigned>(ceil_div(n_rows, 256)), 2), 256, 0, stream>>>(partials, n_rows, chunks, a, b,
+                                                                                                 nullptr, nullptr);
+    return check_launch("rowsq_finish_kernel (moments)");
 }
 
 // wmean (v == nullptr), centered clipping's update (v: the centre) or FLTrust's sum (divisor: one device double); one launch

@@ -7,7 +7,7 @@
 //           in one read of G.  rowsq's geometry (geomed.hip): workgroups take (block of 32 rows, chunk of columns), a wave
 //           owns 8 rows and walks its chunk in windows of 1024 columns with dwordx4 loads; every (row, chunk) partial comes
 //           from one wave (lane sums, the fixed butterfly) and the finishing kernel adds a row's chunks in chunk order.  q is
-//           rowsq_partial_kernel<VEC4, true>'s second accumulator operation for operation, so it has byz_row_dots_dev's bits.
+//           rowsq_partial_kernel<VEC4, kRowsqDots>'s second accumulator operation for operation, so it has byz_row_dots_dev's bits.
 //           A value is counted on its BITS, as robust_lr.hip decides its votes: +0.0 and -0.0 are zeros, denormals and
 //           infinities count by their sign, a NaN counts nowhere.  A 1024-column step that does not meet the window does no
 //           counting work (a wave-uniform test).  Lane counters are int32 (a lane sees at most chunk / 64 + 16 columns); they

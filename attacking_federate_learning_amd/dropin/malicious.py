@@ -1,2 +1,2 @@
 """`import malicious` shim: see dropin/defences.py."""
-from attacking_federate_learning_amd.malicious import Attack, DriftAttack, FangKrumAttack, FangTrimmedMeanAttack  # noqa: F401
+from attacking_federate_learning_amd.malicious import Attack, DriftAttack, FangKrumAttack, FangTrimmedMeanAttack, MinMaxAttack, MinSumAttack  # noqa: F401

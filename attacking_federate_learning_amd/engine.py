@@ -128,6 +128,11 @@ def _hp(a):
     return None if a is None else a.ctypes.data
 
 
+# byz_minmax_params' codes (include/byzagg.h: BYZ_MINMAX_KIND_*, BYZ_MINMAX_PERTURB_*)
+MINMAX_KINDS = {'minmax': 0, 'minsum': 1}
+MINMAX_PERTURBATIONS = {'unit': 0, 'std': 1, 'sign': 2, 'custom': 3}
+
+
 class DeviceBuffer:
     """Raw device memory owned through the C ABI (lets a host without torch keep data on the GPU)."""
 
@@ -2586,6 +2591,85 @@ class Engine:
                 info['distances'] = Distances(dist, m.rows)
                 info['t'], info['q'] = c.result((t, q))
             return rows, info
+
+    # ---- the Min-Max / Min-Sum attacks of Shejwalkar & Houmansadr (NDSS 2021; not in the reference) ----
+    def row_moments(self, g, z, p):
+        """(a, b): a[i] = sum_c ((double)g[i, c] - (double)z[c])^2 (row_sqdist's bits) and b[i] = sum_c (double)p[c] *
+        ((double)z[c] - (double)g[i, c]), both fp64 in a fixed order, in ONE read of g: |z + gamma p - g_i|^2 = a_i + 2 gamma b_i
+        + gamma^2 |p|^2.  On one rank of the columns layout, its part over its columns.  fp64 out: torch tensors for a torch
+        input, numpy for a host input, DeviceBuffers otherwise."""
+        with _Call(self) as c:
+            m = c.matrix(g)
+            z = c.operand(z, np.float32, _f32('z has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False)
+            p = c.operand(p, np.float32, _f32('p has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False)
+            a, aptr = c.out(m.rows, np.float64)
+            b, bptr = c.out(m.rows, np.float64)
+            c.run(self.lib.byz_row_moments_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, z.ptr, p.ptr, aptr, bptr, c.stream))
+            return c.result((a, b))
+
+    @staticmethod
+    def _minmax_params(kind, perturbation, partial, p, dist_given=False):
+        """byz_minmax_params; refuses an unknown kind or perturbation, and a custom perturbation without its vector (or a vector
+        without it), before anything is launched."""
+        if kind not in MINMAX_KINDS:
+            raise ValueError('kind = %r: one of %s' % (kind, sorted(MINMAX_KINDS)))
+        if perturbation not in MINMAX_PERTURBATIONS:
+            raise ValueError('perturbation = %r: one of %s' % (perturbation, sorted(MINMAX_PERTURBATIONS)))
+        if (perturbation == 'custom') != (p is not None):
+            raise ValueError("perturbation='custom' and the vector p come together or not at all")
+        return _native.MinmaxParams(MINMAX_KINDS[kind], MINMAX_PERTURBATIONS[perturbation], 1 if partial else 0, 1 if dist_given else 0)
+
+    def minmax_info(self):
+        """{gamma, bound, c, binding_row, known_rows, degenerate, broken} of the last minmax_attack on this engine
+        (synchronises).  bound: T = Dmax^2 for Min-Max, S = r max a_i + A for Min-Sum."""
+        gamma, bound, c, row, r, degenerate, broken = self._read(
+            self.lib.byz_minmax_info, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int32, ctypes.c_int32])
+        return {'gamma': gamma, 'bound': bound, 'c': c, 'binding_row': row, 'known_rows': r, 'degenerate': bool(degenerate),
+                'broken': bool(broken)}
+
+    def minmax_attack(self, g, n_malicious, kind='minmax', perturbation='std', partial=False, p=None, return_info=False,
+                      distances=None, all_reduce=None):
+        """The Min-Max (kind='minmax') and Min-Sum ('minsum') attacks (include/byzagg.h, rule D).  Rows 0 .. n_malicious - 1 of
+        g hold the attackers' honest gradients; the known rows are all of them, or with partial=True the attackers' own.  Every
+        attacker row becomes the ONE vector mu + gamma p: mu the known rows' mean, p the perturbation ('unit': -mu / |mu|,
+        'std': -std, the population estimate, 'sign': -sign(mu), 'custom': the vector `p`), gamma the largest that keeps the
+        vector as close to every known row as they are to each other -- in closed form, no search.  A device-resident g is
+        attacked IN PLACE and its first n_malicious rows are returned as a view (torch) or None (DeviceBuffer); a host matrix
+        is left alone and the ONE attacked vector comes back as numpy.  distances: a Distances handle of ALL rows for Min-Max
+        (skips the Gram).  all_reduce: g is this rank's column slice (columns layout; a device matrix).  return_info=True adds
+        minmax_info().  A broken input (a value that is not finite among the known rows) leaves the rows as they were."""
+        params = self._minmax_params(kind, perturbation, partial, p, dist_given=distances is not None)
+        c_rows = int(n_malicious)
+        dm = self._device_matrix(g)
+        if dm is None and all_reduce is None and distances is None:
+            h = self._host_matrix(g)
+            n, d = h.shape
+            if not 1 <= c_rows <= n:
+                raise ValueError('%d attacker rows of %d rows' % (c_rows, n))
+            pv = None if p is None else np.ascontiguousarray(_to_host(p), dtype=np.float32).reshape(-1)
+            if pv is not None and pv.size != d:
+                raise ValueError('p has %d entries, the matrix %d columns' % (pv.size, d))
+            vec = np.empty(d, dtype=np.float32)
+            _check(self.lib.byz_minmax_attack_host(self.ctx, _hp(h), n, d, c_rows, ctypes.byref(params), _hp(pv), _hp(vec)))
+            return (vec, self.minmax_info()) if return_info else vec
+        with _Call(self) as c:
+            m = c.matrix(g, needs='minmax_attack' if dm is None else None)
+            pv = None
+            if p is not None:
+                pv = c.operand(p, np.float32, _f32('p has %(got)d entries, the matrix %(n)d columns'), m.cols, convert=False).ptr
+            dptr = distances.ptr if distances is not None else None
+            if distances is not None and distances.n != m.rows:
+                raise ValueError('the distance matrix has %d rows, the gradient matrix %d' % (distances.n, m.rows))
+            if all_reduce is None:
+                c.run(self.lib.byz_minmax_attack_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, c_rows, ctypes.byref(params), pv, dptr,
+                                                     c.stream))
+            else:
+                callback = self._allreduce_callback(all_reduce)
+                c.run(self.lib.byz_minmax_attack_sharded_dev(self.ctx, m.ptr, m.rows, m.cols, m.ld, c_rows, ctypes.byref(params), pv,
+                                                             dptr, ctypes.cast(callback, ctypes.c_void_p), None, c.stream))
+            rows = g[:c_rows] if m.torch_like is not None else None
+            return (rows, self.minmax_info()) if return_info else rows
 
     def column_chain(self, rows, carry=None, mean=None):
         """One link of the attack's statistics over rows that several owners hold (sharded.py, clients layout): the running

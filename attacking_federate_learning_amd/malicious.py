@@ -9,6 +9,9 @@ and rebinds every `usr.grads` to the ONE array the hook returned (reference mali
 Beyond the reference: `FangTrimmedMeanAttack` and `FangKrumAttack`, the adaptive attacks of Fang et al. (USENIX Security 2020)
 on the trimmed mean / median and on Krum; they need the benign gradients too and give every malicious user its own row.
 
+`MinMaxAttack` and `MinSumAttack` are the AGR-agnostic attacks of Shejwalkar and Houmansadr (NDSS 2021, section IV-C); like
+`DriftAttack` they give every malicious user the ONE shared array.
+
 The column statistics run in libbyzagg's column kernel; for `DriftAttack` the drift itself is fused into
 that kernel, so the m x D matrix is read once.
 """
@@ -144,3 +147,45 @@ class FangKrumAttack(_FangAttack):
         g = self._matrix(users, benign_users, needs_benign=True)
         attacked, self.info = get_engine().fang_krum_attack(g, len(users), threshold=self.threshold, return_info=True)
         self._hand_out(users, attacked)
+
+
+class _AgnosticAttack(_FangAttack):
+    """What Min-Max and Min-Sum (Shejwalkar and Houmansadr, NDSS 2021, section IV-C) share: every malicious gradient becomes
+    the ONE vector mu + gamma p, gamma in closed form (include/byzagg.h, rule D).  perturbation: 'unit', 'std' (the population
+    std; the authors' torch.std gives the same vector from a gamma smaller by sqrt((r - 1) / r)) or 'sign'.  partial=True knows
+    the malicious clients' gradients alone; otherwise the benign ones come through `attack(users, benign_users=...)` or
+    `bind(matrix)`.  Every malicious `usr.grads` is rebound to ONE array, as DriftAttack does; `info` holds the last call's
+    report.  A broken call (a value that is not finite) leaves the users' gradients as they were."""
+
+    kind = None
+
+    def __init__(self, perturbation='std', partial=False):
+        from .engine import MINMAX_PERTURBATIONS
+        if perturbation not in MINMAX_PERTURBATIONS or perturbation == 'custom':
+            raise ValueError("perturbation = %r: 'unit', 'std' or 'sign'" % (perturbation,))
+        super(_AgnosticAttack, self).__init__()
+        self.perturbation, self.partial, self.info = perturbation, bool(partial), None
+
+    def attack(self, users, benign_users=None):
+        if len(users) == 0:
+            return
+        g = self._matrix(users, None if self.partial else benign_users, needs_benign=not self.partial)
+        _, self.grads_mean, self.grads_stdev = self._statistics(users, 0.0)
+        vector, self.info = get_engine().minmax_attack(g, len(users), kind=self.kind, perturbation=self.perturbation,
+                                                       partial=self.partial, return_info=True)
+        if self.info['broken']:
+            return
+        for usr in users:
+            usr.grads = vector
+
+
+class MinMaxAttack(_AgnosticAttack):
+    """Min-Max: the malicious vector's largest distance to a known gradient stays within the largest distance between two known
+    gradients."""
+    kind = 'minmax'
+
+
+class MinSumAttack(_AgnosticAttack):
+    """Min-Sum: the malicious vector's summed squared distance to the known gradients stays within the largest such sum of a
+    known gradient.  No distance matrix: two reads of the gradients."""
+    kind = 'minsum'

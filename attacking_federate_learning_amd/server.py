@@ -10,6 +10,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     attack(attacker_rows, num_std)  main.py:68 -> malicious.py:10-36 on the first rows, in place
     attack_fang_trimmed_mean(rows)  Fang et al.'s attack on the trimmed mean / median on the same rows, fresh draws every round
     attack_fang_krum(rows)          Fang et al.'s attack on Krum on the same rows
+    attack_minmax(rows)             Shejwalkar and Houmansadr's Min-Max / Min-Sum attack on the same rows
     defend(defence_method)          server.py:86-90  defences.defend[...] on the device matrix + fused momentum step
     defend_centered_clip(tau, iters)  the same step with centered clipping from the previous round's aggregate
     defend_fltrust(root_grad)         the same step with FLTrust against the server's own root gradient
@@ -107,6 +108,17 @@ class DeviceServer:
         if n_malicious <= 0:
             return None
         _, info = self.engine.fang_krum_attack(self.users_grads.data, n_malicious, threshold=threshold, return_info=True)
+        return info
+
+    def attack_minmax(self, n_malicious, kind='minmax', perturbation='std', partial=False):
+        """The Min-Max / Min-Sum attack of Shejwalkar and Houmansadr on rows 0 .. n_malicious-1, in place
+        (engine.minmax_attack): all of them become mu + gamma p.  Returns {gamma, bound, c, binding_row, known_rows, degenerate,
+        broken}; reading it is the call's one synchronisation (Min-Max also waits where the distances wait).  The gradients
+        stay on the GPU."""
+        if n_malicious <= 0:
+            return None
+        _, info = self.engine.minmax_attack(self.users_grads.data, n_malicious, kind=kind, perturbation=perturbation,
+                                            partial=partial, return_info=True)
         return info
 
     # ---- server.py:86-90 ---------------------------------------------------------------------------

@@ -203,6 +203,11 @@ class HipKernels:
         features = self.engine.multi_metrics_features(man, euc, cos)
         return self.engine.multi_metrics_select(features, keep, on_device=True, like=like)
 
+    def minmax_attack(self, g_local, n_malicious, kind, perturbation, partial, all_reduce=None, return_info=False):
+        # in place on this rank's slice; the moments (and with 'unit' the mean's norm) go through all_reduce (None: one rank)
+        return self.engine.minmax_attack(g_local, n_malicious, kind=kind, perturbation=perturbation, partial=partial,
+                                         all_reduce=all_reduce, return_info=return_info)
+
     def drift(self, rows_local, num_std, write_back=False):
         return self.engine.drift_attack(rows_local, num_std, write_back=write_back)
 
@@ -895,6 +900,16 @@ class ShardedAggregator:
         """columns layout.  Rows 0..m-1 are the malicious clients (reference main.py:28); per column, no exchange."""
         drift, mean, std = self.kernels.drift(g_local[:n_malicious], num_std, write_back=write_back)
         return self._maybe_gather(drift, gather, total_columns), mean, std
+
+    def minmax_attack(self, g_local, n_malicious, kind='minmax', perturbation='std', partial=False, return_info=False):
+        """The Min-Max / Min-Sum attacks, columns layout, in place on rows 0..m-1 of this rank's slice.  The statistics, the
+        perturbation and the fill are local to a column; a_i, b_i and c are sums over the columns: ONE all-reduce of 2 r + 1
+        doubles (r: the known rows), with 'unit' one more of 1 double (|mu|^2) before it; Min-Max also takes the sharded
+        distances' all-reduces (the Gram, the near-duplicate pairs).  Every rank solves the same gamma.  The clients layout is
+        NOT offered: the moments of one client's row need every column of it on one rank, and mu needs every client's row."""
+        reduce = (lambda t: self._all_reduce('allreduce_minmax', t)) if self._collective() else None
+        return self.kernels.minmax_attack(g_local, n_malicious, kind=kind, perturbation=perturbation, partial=partial,
+                                          all_reduce=reduce, return_info=return_info)
 
     def drift_attack_clients(self, rows_local, rows_per_rank, n_malicious, num_std, write_back=True):
         """clients layout.  The malicious rows 0..m-1 sit on the first ranks.  numpy's mean / var add in row order

@@ -1325,6 +1325,81 @@ int byz_fang_krum_attack_dev(byz_ctx* ctx, float* G_dev, int64_t n_rows, int64_t
 /* byz_flame_info does: the rows' overwrite is complete when it returns.  BYZ_E_INVALID before the first such call.               */
 int byz_fang_krum_info(byz_ctx* ctx, double* lambda0, double* lambda, int64_t* steps, int64_t* chosen, int32_t* succeeded);
 
+/* ---- The AGR-agnostic attacks of Shejwalkar & Houmansadr, "Manipulating the Byzantine: Optimizing Model Poisoning Attacks and   */
+/* Defenses for Federated Learning" (NDSS 2021, section IV-C): Min-Max and Min-Sum; not in the reference ----                     */
+/* Rows as in the Fang attacks: G is n_rows x n_cols, rows 0 .. m - 1 (m = n_attackers) are the attackers' and hold their honest  */
+/* gradients on entry.  The KNOWN rows are all n_rows (full knowledge) or rows 0 .. m - 1 (partial != 0); r is their number.      */
+/* Every attacker row becomes the ONE vector mal = mu + gamma p with the largest gamma for which                                  */
+/*   Min-Max:  max_i |mal - g_i|   <= max_ij |g_i - g_j|                over the known rows,                                      */
+/*   Min-Sum:  sum_i |mal - g_i|^2 <= max_i sum_j |g_i - g_j|^2         over the known rows.                                      */
+/* D. The rule.  mu, sigma = byz_drift_attack_dev's mean and population std over the known rows (write_back = 0), its bits.       */
+/*   The perturbation p (fp32, n_cols):                                                                                           */
+/*     unit    p_k = fl32(-(double)mu_k / nrm), nrm = sqrt(sum_k (double)mu_k^2) (byz_row_sqdist_dev's order); nrm == 0: p = 0     */
+/*     std     p_k = -sigma_k                                                                                                     */
+/*     sign    p_k = -1 where mu_k > 0, +1 where mu_k < 0, +0.0 otherwise (a zero of either sign, a NaN)                           */
+/*     custom  the caller's vector                                                                                                */
+/*   Only gamma p matters.  The authors' code takes torch.std, the UNBIASED estimate: the same vector, a gamma smaller by         */
+/*   sqrt((r - 1) / r).                                                                                                           */
+/*   The moments, fp64 in byz_row_sqdist_dev's fixed order (byz_row_moments_dev):                                                 */
+/*     a_i = sum_k ((double)x_ik - (double)mu_k)^2,  b_i = sum_k (double)p_k * ((double)mu_k - (double)x_ik),  c = sum_k p_k^2,    */
+/*   so that |mal - g_i|^2 = a_i + 2 gamma b_i + gamma^2 c: the paper's search (Algorithm 1) is the root of a quadratic here.     */
+/*   gamma = 0 is always feasible (mu lies in the rows' convex hull).  The authors' halving search (start 10, threshold 1e-5)     */
+/*   ends within 2e-5 below that root and cannot pass 20 whatever the data; the closed form has no such ceiling.                  */
+/*   Min-Max: T = (double)Dmax^2, Dmax the largest finite entry off the diagonal of the known block of                            */
+/*     byz_pairwise_distances_dev's fp32 matrix (no finite entry: T = 0).  Per known row q = max(T - a_i, 0),                     */
+/*     s = sqrt(b_i^2 + c q), gamma_i = b_i <= 0 ? (s - b_i) / c : q / (s + b_i) -- the form that does not cancel.                */
+/*     gamma = min_i gamma_i; the binding row is the lowest such i.                                                               */
+/*   Min-Sum: A = sum a_i, B = sum b_i, both in row order and kept as computed (B is 0 in exact arithmetic).  Q = r max_i a_i,    */
+/*     s = sqrt(B^2 + (r c) Q), gamma = B <= 0 ? (s - B) / (r c) : Q / (s + B); the bound reported is S = Q + A, which is         */
+/*     max_i sum_j |g_i - g_j|^2 because sum_j |g_i - g_j|^2 = r a_i + A about the rows' mean: no n x n table.  The binding row   */
+/*     is the lowest row of max a_i.                                                                                              */
+/*   Broken (broken = 1, gamma = NaN, the attacker rows are left exactly as they were): some a_i, b_i or c is not finite -- a     */
+/*     value of mu that is not finite makes every a_i so -- or A, B, gamma or the bound is not (b^2 beyond fp64).                 */
+/*   Degenerate (degenerate = 1, gamma = 0, the rows become mu), when not broken: c == 0, or r == 1.                               */
+/*   The rows: fl32((double)mu_k + fl64(gamma * (double)p_k)), no fused multiply-add: numpy reproduces them as bits from the      */
+/*     reported gamma.  No new NaN is ever written.                                                                               */
+/* Not built: the AGR-tailored attacks of section IV-B, and the paper's learned initialisation of gamma (it has no search here).  */
+#define BYZ_MINMAX_KIND_MINMAX 0
+#define BYZ_MINMAX_KIND_MINSUM 1
+#define BYZ_MINMAX_PERTURB_UNIT 0
+#define BYZ_MINMAX_PERTURB_STD 1
+#define BYZ_MINMAX_PERTURB_SIGN 2
+#define BYZ_MINMAX_PERTURB_CUSTOM 3
+typedef struct byz_minmax_params {
+    int kind;               /* BYZ_MINMAX_KIND_*                                                                  */
+    int perturbation;       /* BYZ_MINMAX_PERTURB_*; CUSTOM if and only if the caller passes a vector             */
+    int partial;            /* 0: every row is known; otherwise the attackers' own rows alone (n_attackers >= 1)  */
+    int dist_given;         /* Min-Max: 0: the call computes the known rows' r x r distance matrix (into dist_dev */
+                            /* when that is not NULL); otherwise dist_dev HOLDS the n_rows x n_rows matrix of all */
+                            /* the rows, whose leading r x r block is read: no Gram, and not its wait             */
+} byz_minmax_params;
+/* a_dev[i], b_dev[i] (n_rows doubles each) of rule D about z_dev (the centre, n_cols floats) along p_dev, in ONE read of G.     */
+/* a_dev has byz_row_sqdist_dev's bits.  On one rank of the columns layout: its part over its columns, additive over the ranks.  */
+int byz_row_moments_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, const float* z_dev,
+                        const float* p_dev, double* a_dev, double* b_dev, void* stream);
+/* The attack, in place on rows 0 .. n_attackers - 1.  n_attackers = 0 does nothing (partial needs n_attackers >= 1); an unknown */
+/* kind or perturbation, a custom perturbation without its vector or a vector without it: BYZ_E_INVALID.  More known rows than   */
+/* byz_row_sqdist_dev takes: BYZ_E_UNSUPPORTED; Min-Max beyond what byz_pairwise_distances_dev takes: what that returns.  Every  */
+/* launch is enqueued up front and nothing synchronises with the host, except that Min-Max without dist_given waits where        */
+/* byz_pairwise_distances_dev waits (the Gram's duplicate-row search).  dist_dev_or_null: see dist_given; Min-Sum ignores it.    */
+int byz_minmax_attack_dev(byz_ctx* ctx, float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                          const byz_minmax_params* params, const float* p_custom_dev_or_null, float* dist_dev_or_null, void* stream);
+/* The same on this rank's column slice (columns layout).  mu, sigma, p and the fill are local to a column; a, b and c are sums    */
+/* over the columns: ONE all-reduce of 2 r + 1 doubles, with `unit` one more of 1 double (|mu|^2) before it, and Min-Max the       */
+/* all-reduces of the sharded distances.  Every rank gets the same gamma and report.  The clients layout is not offered: the rows */
+/* of one client would have to meet every other rank's.                                                                           */
+int byz_minmax_attack_sharded_dev(byz_ctx* ctx, float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t n_attackers,
+                                  const byz_minmax_params* params, const float* p_custom_dev_or_null, float* dist_dev_or_null,
+                                  byz_allreduce_f64_fn allreduce, void* user, void* stream);
+/* The last attack on this context: gamma, the bound (T or S), c, the binding row (-1: none), r, and the two flags.  Synchronises */
+/* that call's stream: the rows' overwrite is complete when it returns.  BYZ_E_INVALID before the first such call.                */
+int byz_minmax_info(byz_ctx* ctx, double* gamma, double* bound, double* c, int64_t* binding_row, int64_t* known_rows,
+                    int32_t* degenerate, int32_t* broken);
+/* The same on a host matrix, which is left as it is: vector_host receives the ONE attacked vector (n_cols floats; the first      */
+/* attacker's honest row when the call is broken).  p_custom_host_or_null: n_cols floats.  Synchronous.  n_attackers >= 1.         */
+int byz_minmax_attack_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, int64_t n_attackers,
+                           const byz_minmax_params* params, const float* p_custom_host_or_null, float* vector_host);
+
 /* ---- next row after the path: Server.defend's update (server.py:89-90) ----------------- */
 /* velocity = momentum*velocity - lr*agg ; weights += velocity, fused, in place.            */
 int byz_server_update_dev(byz_ctx* ctx, float* weights_dev, float* velocity_dev,
