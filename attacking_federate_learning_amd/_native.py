@@ -82,6 +82,11 @@ class MinmaxParams(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int), ('perturbation', ctypes.c_int), ('partial', ctypes.c_int), ('dist_given', ctypes.c_int)]
 
 
+class FoolsgoldParams(ctypes.Structure):
+    """byz_foolsgold_params: FoolsGold's confidence and the divisor of its sum (0: the usable count, 1: the weights' sum)."""
+    _fields_ = [('kappa', ctypes.c_double), ('normalise', c_i64)]
+
+
 class AurorParams(ctypes.Structure):
     """byz_auror_params: the indicative gap, the share of votes that removes a row, the sweeps' cap and the accumulate switch."""
     _fields_ = [('alpha', ctypes.c_double), ('tau', ctypes.c_double), ('max_iter', c_i64), ('accumulate', c_i64)]
@@ -247,6 +252,12 @@ _PROTOTYPES = {
     'byz_auror_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, _P(AurorParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_auror_info': [c_vp, _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64), _P(c_i64)],
     'byz_auror_host': [c_vp, c_vp, c_i64, c_i64, _P(AurorParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'byz_rows_add_dev': [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
+    'byz_foolsgold_weights_dev': [c_vp, c_vp, c_i64, _P(FoolsgoldParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_foolsgold_trace_dev': [c_vp, c_i64, c_vp, c_vp, c_vp],
+    'byz_foolsgold_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, _P(FoolsgoldParams), c_vp, c_vp, c_vp, c_vp],
+    'byz_foolsgold_info': [c_vp, _P(c_i64), _P(ctypes.c_double)],
+    'byz_foolsgold_host': [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, _P(FoolsgoldParams), c_vp, c_vp, c_vp],
     'byz_multi_metrics_sharded_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_topk_sparsify_sharded_dev': [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     'byz_dnc_scores_dev': [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],

@@ -21,7 +21,7 @@ SOURCES = ['api.hip', 'column_stats.hip', 'gram.hip', 'select.hip', 'median_wind
            'round_edges.hip', 'dedup.hip', 'gram_planes.hip', 'krum_small.hip', 'window_lean.hip', 'large_rows.hip', 'tall_select.hip',
            'multi_krum.hip', 'geomed.hip', 'rank_select.hip', 'dnc.hip', 'cclip.hip', 'fltrust.hip', 'nnm.hip', 'robust_lr.hip', 'topk.hip',
            'bucketing.hip', 'signguard.hip', 'noise.hip', 'flame.hip', 'manhattan.hip', 'multi_metrics.hip', 'linkage.hip',
-           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip', 'auror.hip', 'minmax.hip']
+           'fang.hip', 'centre_window.hip', 'faba.hip', 'afa.hip', 'auror.hip', 'minmax.hip', 'foolsgold.hip']
 # median_window.hip keeps its tile in registers: every loop over the register array must be fully unrolled (a
 # dynamic index would demote the array to scratch), and the staging loop of the larger instantiations exceeds
 # LLVM's default budget for `#pragma unroll`.  NaN semantics stay on in this file (the padding rows are +inf; a
@@ -60,6 +60,8 @@ EXTRA_FLAGS = {'median_window.hip': ['-mllvm', '-pragma-unroll-threshold=1000000
                'faba.hip': ['-ffp-contract=off'],
                # AFA's u, A, scores and thresholds: every product rounded before the sum or difference that takes it
                'afa.hip': ['-ffp-contract=off'],
+               # FoolsGold's cosines, pardoned cosines and logit: (cs * m_i) / m_j and kappa * (log + 0.5) one operation at a time
+               'foolsgold.hip': ['-ffp-contract=off'],
                # Auror: the resident tile of values lives in registers (full unroll of every loop over it); t = 0.5 * (c0 + c1) and the
                # clusters' fp64 sums are the stated operations
                'auror.hip': ['-mllvm', '-pragma-unroll-threshold=1000000', '-ffp-contract=off'],

@@ -2082,6 +2082,133 @@ int byz_auror_info(byz_ctx* ctx, int64_t* indicative, int64_t* removed_rows, int
     return BYZ_OK;
 }
 
+// ---- FoolsGold (Fung, Yoon & Beschastnikh, arXiv:1808.04866; beyond the reference) -----------------------------------------------
+namespace {
+
+int check_foolsgold(const char* who, int64_t n, const byz_foolsgold_params* params) {
+    if (n < 1) {
+        set_error("%s: at least 1 row, got %lld", who, (long long)n);
+        return BYZ_E_INVALID;
+    }
+    BYZ_TRY(check_row_ceiling(who, n));
+    if (!params) {
+        set_error("%s: null parameters", who);
+        return BYZ_E_INVALID;
+    }
+    if (!(std::isfinite(params->kappa) && params->kappa > 0.0) ||
+        (params->normalise != BYZ_FOOLSGOLD_NORMALISE_COUNT && params->normalise != BYZ_FOOLSGOLD_NORMALISE_SUM)) {
+        set_error("%s: kappa = %g must be finite and > 0, normalise = %lld one of 0 (count) and 1 (sum)", who, params->kappa,
+                  (long long)params->normalise);
+        return BYZ_E_INVALID;
+    }
+    return BYZ_OK;
+}
+
+// the window [col_start, col_start + col_count) inside n_cols columns, and the history beside it
+int check_foolsgold_window(const char* who, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* H, int64_t ld_h,
+                           int64_t col_start, int64_t col_count) {
+    if (col_start < 0 || col_count < 1 || col_start > n_cols - col_count) {
+        set_error("%s: the window [%lld, %lld + %lld) lies outside the %lld columns", who, (long long)col_start, (long long)col_start,
+                  (long long)col_count, (long long)n_cols);
+        return BYZ_E_INVALID;
+    }
+    if (H != nullptr) {
+        if (ld_h < col_count) {
+            set_error("%s: the history's ld %lld is below its %lld columns", who, (long long)ld_h, (long long)col_count);
+            return BYZ_E_INVALID;
+        }
+        const float* g_end = G + (n_rows - 1) * ld + n_cols;
+        const float* h_end = H + (n_rows - 1) * ld_h + col_count;
+        if (H < g_end && h_end > G) {
+            set_error("%s: the history overlaps the matrix", who);
+            return BYZ_E_INVALID;
+        }
+    }
+    return BYZ_OK;
+}
+
+}  // namespace
+
+int byz_rows_add_dev(byz_ctx* ctx, float* H, int64_t ld_h, const float* G, int64_t n_rows, int64_t n_cols_window, int64_t ld_g,
+                     int64_t col_start, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(H && G && n_rows >= 1 && n_cols_window >= 1 && col_start >= 0 && ld_h >= n_cols_window &&
+                    ld_g >= col_start + n_cols_window,
+                "rows_add: bad arguments (%lld x %lld from column %lld, ld %lld and %lld)", (long long)n_rows, (long long)n_cols_window,
+                (long long)col_start, (long long)ld_h, (long long)ld_g);
+    BYZ_TRY(check_foolsgold_window("rows_add", G, n_rows, col_start + n_cols_window, ld_g, H, ld_h, col_start, n_cols_window));
+    return launch_rows_add(ctx, H, ld_h, G + col_start, n_rows, n_cols_window, ld_g, as_stream(stream));
+}
+
+int byz_foolsgold_weights_dev(byz_ctx* ctx, const double* gram, int64_t n_rows, const byz_foolsgold_params* params, double* weights,
+                              double* maxcs, double* alpha, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(gram && weights, "foolsgold_weights: null Gram or output");
+    BYZ_TRY(check_foolsgold("foolsgold_weights", n_rows, params));
+    FoolsgoldScratch t;
+    BYZ_TRY(foolsgold_workspace(ctx, n_rows, &t));
+    mark(ctx, kReportFoolsgold, as_stream(stream));
+    ctx->foolsgold_rows = n_rows;
+    return launch_foolsgold_weights(ctx, t, gram, n_rows, params->kappa, static_cast<int>(params->normalise), weights, maxcs, alpha,
+                                    as_stream(stream));
+}
+
+int byz_foolsgold_trace_dev(byz_ctx* ctx, int64_t n_rows, double* rescaled, int32_t* usable, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_REQUIRE(ctx->last[kReportFoolsgold].ran && n_rows == ctx->foolsgold_rows,
+                "foolsgold_trace: the last FoolsGold weights on this context had %lld rows, not %lld", (long long)ctx->foolsgold_rows,
+                (long long)n_rows);
+    FoolsgoldScratch t;
+    BYZ_TRY(foolsgold_workspace(ctx, n_rows, &t));      // (the same layout in the same buffer: nothing grows)
+    hipStream_t s = as_stream(stream);
+    if (rescaled) BYZ_HIP(hipMemcpyAsync(rescaled, t.rescaled, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (usable) BYZ_HIP(hipMemcpyAsync(usable, t.flags, static_cast<size_t>(n_rows) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return BYZ_OK;
+}
+
+// It waits where byz_gram_dev waits (the Gram's duplicate search), and nowhere when the caller passes the Gram.
+int byz_foolsgold_dev(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, float* H, int64_t ld_h,
+                      int64_t col_start, int64_t col_count, const byz_foolsgold_params* params, const double* gram_in, float* out,
+                      double* weights, void* stream) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G, n_rows, n_cols, ld, "foolsgold"));
+    BYZ_REQUIRE(out, "foolsgold: null output");
+    BYZ_TRY(check_foolsgold("foolsgold", n_rows, params));
+    BYZ_TRY(check_foolsgold_window("foolsgold", G, n_rows, n_cols, ld, H, ld_h, col_start, col_count));
+    BYZ_TRY(check_cclip_output(G, n_rows, n_cols, ld, out, "foolsgold"));
+    if (H != nullptr) BYZ_TRY(check_cclip_output(H, n_rows, col_count, ld_h, out, "foolsgold"));
+    hipStream_t s = as_stream(stream);
+    FoolsgoldScratch t;
+    BYZ_TRY(foolsgold_workspace(ctx, n_rows, &t));
+    mark(ctx, kReportFoolsgold, s);
+    ctx->foolsgold_rows = n_rows;
+    if (H != nullptr) BYZ_TRY(launch_rows_add(ctx, H, ld_h, G + col_start, n_rows, col_count, ld, s));
+    const double* gram = gram_in;
+    if (gram == nullptr) {
+        BYZ_TRY(ctx->gram.ensure(static_cast<size_t>(n_rows) * n_rows * sizeof(double)));
+        if (H != nullptr) BYZ_TRY(launch_gram(ctx, H, n_rows, col_count, ld_h, ctx->gram.as<double>(), s));
+        else BYZ_TRY(launch_gram(ctx, G + col_start, n_rows, col_count, ld, ctx->gram.as<double>(), s));
+        gram = ctx->gram.as<double>();
+    }
+    BYZ_TRY(launch_foolsgold_weights(ctx, t, gram, n_rows, params->kappa, static_cast<int>(params->normalise), weights, nullptr, nullptr, s));
+    return launch_scaled_rows_sum(ctx, G, n_rows, n_cols, ld, t.w, &t.info->divisor, out, s);
+}
+
+int byz_foolsgold_info(byz_ctx* ctx, int64_t* counts5, double* stats2) {
+    DeviceScalars all;
+    BYZ_TRY(read_report(ctx, kReportFoolsgold, "foolsgold_info: no FoolsGold weights on this context yet", &all));
+    const FoolsgoldReport& info = all.foolsgold;
+    if (counts5) {
+        const int32_t counts[5] = {info.usable, info.excluded, info.at_zero, info.at_one, info.degenerate};
+        for (int i = 0; i < 5; ++i) counts5[i] = counts[i];
+    }
+    if (stats2) {
+        stats2[0] = info.top;
+        stats2[1] = info.divisor;
+    }
+    return BYZ_OK;
+}
+
 // ---- Multi-Metrics (Huang et al., ICCV 2023; beyond the reference) ------------------------------------------------------------
 namespace {
 
@@ -3252,6 +3379,27 @@ int byz_auror_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_
     st.inout(&counts, add ? counts_host : nullptr, counts_host, 4);
     BYZ_TRY(st.stage(G_host, n_rows, n_cols));
     BYZ_TRY(byz_auror_dev(ctx, st.G(), n_rows, n_cols, n_cols, params, votes, bad, counts, out, kept, gap, st.stream()));
+    return st.finish();
+}
+
+int byz_foolsgold_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, float* H_host, int64_t col_start,
+                       int64_t col_count, const byz_foolsgold_params* params, const double* gram_host, float* out_host,
+                       double* weights_host) {
+    BYZ_TRY(enter(ctx));
+    BYZ_TRY(check_matrix(G_host, n_rows, n_cols, n_cols, "foolsgold"));
+    BYZ_REQUIRE(out_host, "foolsgold: null output");
+    BYZ_TRY(check_foolsgold("foolsgold", n_rows, params));
+    BYZ_TRY(check_foolsgold_window("foolsgold", G_host, n_rows, n_cols, n_cols, nullptr, 0, col_start, col_count));
+    HostStage st(ctx);
+    float *out, *H = nullptr;
+    double *gram, *weights;
+    st.out(&out, out_host, n_cols);
+    if (H_host != nullptr) st.inout(&H, static_cast<const float*>(H_host), H_host, n_rows * col_count);     // added to in place
+    st.in(&gram, gram_host, n_rows * n_rows);
+    st.out(&weights, weights_host, n_rows);
+    BYZ_TRY(st.stage(G_host, n_rows, n_cols));
+    BYZ_TRY(byz_foolsgold_dev(ctx, st.G(), n_rows, n_cols, n_cols, H, col_count, col_start, col_count, params, gram, out, weights,
+                              st.stream()));
     return st.finish();
 }
 

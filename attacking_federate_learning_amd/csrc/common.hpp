@@ -169,6 +169,9 @@ struct byz_ctx {
                                  // flags, the rounds of removal
     byz::Buffer auror;           // Auror, carved into AurorScratch's arrays (auror.hip: auror_workspace): the weights, and the votes,
                                  // bad flags and counts of a call that carries no history
+    byz::Buffer foolsgold;       // FoolsGold, carved into FoolsgoldScratch's arrays (foolsgold.hip: foolsgold_workspace): the rows' r, m,
+                                 // a, weights and rescaled weights, the usable flags
+    int64_t foolsgold_rows = 0;  // the rows of the last weights stage: what byz_foolsgold_trace_dev may copy
     byz::Buffer fang;            // the Fang attacks, carved (api.hip: fang_workspace): the column vectors (mean, lo or std, hi, the
                                  // direction or the attack vector), the Krum attack's t and q, its benign distance block and bounds
     // the last Krum attack's values (byz_fang_krum_info reports them; last[kReportFangKrum] says whether there was one)
@@ -557,6 +560,20 @@ int launch_auror_votes(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_c
 // the flags into kept_out (optional) and t.w, the counts into t.info
 int launch_auror_select(byz_ctx* ctx, const AurorScratch& t, const long long* votes, const int32_t* bad, const long long* counts,
                         int64_t n, double tau, int32_t* kept_out, hipStream_t stream);
+// foolsgold.hip: FoolsGold's history update and its weights on an fp64 Gram.  The scalars of a call: DeviceScalars::foolsgold.
+struct FoolsgoldScratch {
+    FoolsgoldReport* info;
+    double *r, *m, *a;               // n: sqrt of the diagonal (-1: excluded); the row maximum; the pardoned row maximum
+    double *w, *rescaled;            // n: the weights l (0 for an excluded row); v / top with 1 read as 0.99
+    int32_t* flags;                  // n: 1 usable, 0 excluded
+};
+int foolsgold_workspace(byz_ctx* ctx, int64_t n, FoolsgoldScratch* out);
+// H (n x w, ld_h) += the n x w window that starts at G (ld_g), numpy's float32 += bits; any base alignment, any ld
+int launch_rows_add(byz_ctx* ctx, float* H, int64_t ld_h, const float* G, int64_t n, int64_t w, int64_t ld_g, hipStream_t stream);
+// the norms, the row maxima, the pardoned maxima, the weights: t.w, t.rescaled and t.flags (weights_out, maxcs_out and alpha_out
+// optional), T and the other scalars into t.info
+int launch_foolsgold_weights(byz_ctx* ctx, const FoolsgoldScratch& t, const double* gram, int64_t n, double kappa, int normalise,
+                             double* weights_out, double* maxcs_out, double* alpha_out, hipStream_t stream);
 // geomed.hip, the weighted mean's kernel template: out = v + sum_i s_i (x_i - v) / n (v and out may be one buffer)
 int launch_clip_update(byz_ctx* ctx, const float* G, int64_t n_rows, int64_t n_cols, int64_t ld, const float* v, const double* s,
                        float* out, hipStream_t stream);

@@ -107,6 +107,13 @@ struct MinmaxReport {                // byz_minmax_attack_dev: what minmax_solve
     int32_t row, r;                  // the binding row (-1: none); the known rows
     int32_t degenerate, broken;      // c == 0 or r == 1; a moment, c, gamma or the bound is not finite
 };
+struct FoolsgoldReport {             // byz_foolsgold_weights_dev and byz_foolsgold_dev
+    int32_t usable, excluded;        // the rows with a finite diagonal entry >= 0; the others (they add up to n)
+    int32_t at_zero, at_one;         // the usable rows whose weight is exactly 0, exactly 1
+    int32_t degenerate, pad;         // two or more usable rows and top == 0: everybody's twin, every weight 0
+    double top;                      // the largest raw weight v of a usable row (0 when nobody is usable)
+    double divisor;                  // T, the divisor of the sum: the usable count, or the weights summed in ascending row order
+};
 
 struct DeviceScalars {
     CoreScalars core;
@@ -126,6 +133,7 @@ struct DeviceScalars {
     AfaReport afa;
     AurorReport auror;
     MinmaxReport minmax;
+    FoolsgoldReport foolsgold;
 };
 
 // What a read-back as bytes, and a 64-bit store or atomic of a kernel, rely on.  No member is padded by the compiler: the sizes
@@ -136,7 +144,7 @@ static_assert(sizeof(DeviceScalars) == sizeof(CoreScalars) + sizeof(GeomedReport
                                            sizeof(FltrustReport) + sizeof(NnmReport) + sizeof(RlrReport) + sizeof(SgReport) +
                                            sizeof(TopkReport) + sizeof(WeakDpReport) + sizeof(FlameInfo) + sizeof(MmInfo) +
                                            sizeof(LinkageInfo) + sizeof(FabaReport) + sizeof(AfaReport) + sizeof(AurorReport) +
-                                           sizeof(MinmaxReport),
+                                           sizeof(MinmaxReport) + sizeof(FoolsgoldReport),
               "no padding between the reports");
 #define BYZ_AT(member) offsetof(DeviceScalars, member)
 constexpr size_t kEightByteFields[] = {
@@ -146,7 +154,8 @@ constexpr size_t kEightByteFields[] = {
     BYZ_AT(linkage.admitted_f64), BYZ_AT(linkage.clip), BYZ_AT(faba.last_score), BYZ_AT(faba.kept_f64),
     BYZ_AT(afa.mean), BYZ_AT(afa.med), BYZ_AT(afa.sd), BYZ_AT(afa.thr), BYZ_AT(afa.divisor),
     BYZ_AT(auror.indicative), BYZ_AT(auror.clustered), BYZ_AT(auror.capped), BYZ_AT(auror.kept_f64),
-    BYZ_AT(minmax.gamma), BYZ_AT(minmax.bound), BYZ_AT(minmax.c)};
+    BYZ_AT(minmax.gamma), BYZ_AT(minmax.bound), BYZ_AT(minmax.c),
+    BYZ_AT(foolsgold.top), BYZ_AT(foolsgold.divisor)};
 #undef BYZ_AT
 constexpr bool eight_byte_fields_aligned() {
     for (size_t at : kEightByteFields)
@@ -156,11 +165,11 @@ constexpr bool eight_byte_fields_aligned() {
 static_assert(eight_byte_fields_aligned(), "every double and 64-bit counter sits at an 8-byte offset");
 
 // the reports an info call reads; byz_ctx::last[kind]: the stream of the last call that wrote it, and whether there was one
-// (kReportMinmax, kReportAuror and kReportAfa stand in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of
+// (kReportFoolsgold, kReportMinmax, kReportAuror and kReportAfa stand in front of kReportFaba: tests/test_faba.py holds FABA's kind to the place in front of
 // kReportCount; the kinds index byz_ctx::last and nothing else, so their numbers are free)
 enum ReportKind {
     kReportGeomed, kReportDnc, kReportCclip, kReportFltrust, kReportNnm, kReportRlr, kReportSignguard, kReportTopk, kReportWeakDp,
-    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportMinmax, kReportAuror, kReportAfa,
+    kReportFlame, kReportMultiMetrics, kReportLinkage, kReportClippedClustering, kReportFangKrum, kReportFoolsgold, kReportMinmax, kReportAuror, kReportAfa,
     kReportFaba, kReportCount
 };
 struct LastCall { hipStream_t stream = nullptr; bool ran = false; };

@@ -502,6 +502,73 @@ def auror(users_grads, users_count, corrupted_count, alpha, tau=0.5, max_iter=32
     return (got[0].numpy(), got[1]) if return_info else got.numpy()
 
 
+class FoolsGoldHistory:
+    """FoolsGold's memory of direction: the n x width float32 matrix of every client's updates summed over the rounds, on the
+    device, zero at the start, which every `foolsgold(..., history=)` call adds this round's column window to in place before
+    it takes the Gram.  Row i is client i, by position: every client reports every round.  A client that once sent a
+    non-finite value has a non-finite row, and is excluded, until `reset()`.  `columns` is the (start, stop) window of the
+    gradients the history is taken over (None until the first call fixes it); `rounds` counts the calls."""
+
+    def __init__(self, n, width):
+        engine = get_engine()
+        self.n, self.width = int(n), int(width)
+        if self.n < 1 or self.width < 1:
+            raise ValueError('FoolsGoldHistory: n and width are positive')
+        self.matrix = engine.empty((self.n, self.width), np.float32)
+        self.columns = None
+        self.rounds = 0
+        self.reset()
+
+    def reset(self):
+        """Forget every round: a zero matrix."""
+        self.matrix.upload(np.zeros((self.n, self.width), dtype=np.float32))
+        self.rounds = 0
+
+    def numpy(self):
+        """The history as a host array."""
+        return self.matrix.numpy()
+
+
+def foolsgold(users_grads, users_count, corrupted_count, history=None, columns=None, kappa=1.0, normalise='count', gram=None,
+              return_info=False):
+    """FoolsGold (Fung, Yoon and Beschastnikh, arXiv:1808.04866; not in the reference): the defence against SYBILS, several
+    clients that push one shared poisoning objective round after round.  Every client's largest cosine similarity with
+    another client is taken over the ACCUMULATED updates (`history`: a `FoolsGoldHistory`, added to in place; None: this
+    round's gradients alone), pardoned where the other client's own maximum is larger, and turned into a weight in [0, 1]
+    by the clipped logit with confidence `kappa`; the result is the weighted sum of this round's gradients over the number
+    of usable clients (normalise='count': with every weight 1 the rule is the mean) or over the weights' sum
+    (normalise='sum').  It runs on ONE fp64 Gram matrix (`gram=` replaces that stage).  `columns`: None for all, or
+    (start, stop): the window the similarity is taken over -- the paper uses the output layer on deep nets, and a
+    full-width history of a large model does not fit beside its gradients.  It needs NO count of attackers: users_count
+    and corrupted_count are accepted for the common signature and not used.  What it does NOT do: ONE attacker is
+    invisible to it (it has nobody to resemble); honest clients with IID data point the same way and are penalised as
+    if they were sybils; and it is no answer to the drift attack, whose rows sit inside the honest crowd round by round.
+    A client whose history holds a NaN or an infinity is excluded.  Not built: the paper's feature-importance weighting
+    and partial participation (clients are rows by position).  numpy in -> numpy out, device-resident in ->
+    device-resident out.  return_info=True returns (vector, {weights, usable, excluded, at_zero, at_one, degenerate, top,
+    divisor}).  Usable as `then=` of `nnm`, `bucketing`, `robust_lr`, `sparsefed` and `weak_dp`.  Not one of the `defend`
+    keys: the reference's main.py offers only those four."""
+    engine = get_engine()
+    if history is None:
+        return engine.foolsgold(users_grads, users_count, corrupted_count, columns=columns, kappa=kappa, normalise=normalise,
+                                gram=gram, return_info=return_info)
+    matrix, was_host = engine.stage(users_grads)
+    n, d = (int(v) for v in matrix.shape)
+    start, width = engine._foolsgold_window(d, columns)
+    if (n, width) != (history.n, history.width):
+        raise ValueError('foolsgold: the history holds %d clients x %d columns, the window is %d x %d'
+                         % (history.n, history.width, n, width))
+    if history.columns not in (None, (start, start + width)):
+        raise ValueError('foolsgold: the history was gathered over the columns %r, not %r' % (history.columns, (start, start + width)))
+    got = engine.foolsgold(matrix, users_count, corrupted_count, history=history.matrix, columns=(start, start + width), kappa=kappa,
+                           normalise=normalise, gram=gram, return_info=return_info)
+    history.columns = (start, start + width)
+    history.rounds += 1
+    if not was_host:
+        return got
+    return (got[0].numpy(), got[1]) if return_info else got.numpy()
+
+
 def coordinate_median(users_grads, users_count, corrupted_count):
     """The coordinate-wise median (Yin et al. 2018; not in the reference): np.median of every column, bit for bit.  The
     reference's signature; users_count and corrupted_count are accepted and unused.  Not one of the `defend` keys: the

@@ -131,6 +131,8 @@ def _hp(a):
 # byz_minmax_params' codes (include/byzagg.h: BYZ_MINMAX_KIND_*, BYZ_MINMAX_PERTURB_*)
 MINMAX_KINDS = {'minmax': 0, 'minsum': 1}
 MINMAX_PERTURBATIONS = {'unit': 0, 'std': 1, 'sign': 2, 'custom': 3}
+# byz_foolsgold_params' normalise (include/byzagg.h: BYZ_FOOLSGOLD_NORMALISE_*)
+FOOLSGOLD_NORMALISE = {'count': 0, 'sum': 1}
 
 
 class DeviceBuffer:
@@ -2244,6 +2246,141 @@ class Engine:
         info = self.auror_info()
         info.update(kept_rows=np.flatnonzero(flags).astype(np.int64), votes=np.asarray(v), bad=np.asarray(b), counts=np.asarray(k),
                     gap=np.asarray(gap))
+        return out, info
+
+    # ---- FoolsGold (Fung, Yoon & Beschastnikh, arXiv:1808.04866; not in the reference) ----
+    @staticmethod
+    def _foolsgold_params(n, kappa=1.0, normalise='count'):
+        """byz_foolsgold_params, checked as the library checks them (the refusals that need no GPU)."""
+        n = int(n)
+        if n > 1 << 20:
+            raise NotImplementedError('foolsgold: at most %d rows, got %d' % (1 << 20, n))
+        if n < 1:
+            raise ValueError('foolsgold: at least 1 row, got %d' % n)
+        kappa = float(kappa)
+        if not (np.isfinite(kappa) and kappa > 0.0):
+            raise ValueError('foolsgold: kappa = %r must be finite and > 0' % kappa)
+        if normalise not in FOOLSGOLD_NORMALISE:
+            raise ValueError("foolsgold: normalise = %r is neither 'count' nor 'sum'" % (normalise,))
+        return _native.FoolsgoldParams(kappa, FOOLSGOLD_NORMALISE[normalise])
+
+    @staticmethod
+    def _foolsgold_window(d, columns):
+        """columns (None: all; a (start, stop) pair or a slice of step 1) -> (col_start, col_count) inside d columns."""
+        if columns is None:
+            return 0, int(d)
+        if isinstance(columns, slice):
+            if columns.step not in (None, 1):
+                raise ValueError('foolsgold: the window is contiguous, got step %r' % (columns.step,))
+            columns = (0 if columns.start is None else columns.start, d if columns.stop is None else columns.stop)
+        start, stop = (int(v) for v in columns)
+        if not 0 <= start < stop <= int(d):
+            raise ValueError('foolsgold: the window [%d, %d) lies outside the %d columns' % (start, stop, d))
+        return start, stop - start
+
+    def _foolsgold_history(self, c, history, n, width):
+        """The history as an _Operand: device-resident, n x width float32 with unit column stride (any ld)."""
+        h = self._device_matrix(history)
+        if h is None:
+            raise ValueError('foolsgold: the history lives on the device (defences.FoolsGoldHistory owns one)')
+        if h.shape != (n, width):
+            raise ValueError('foolsgold: the history has shape %r, the window is %d x %d' % (h.shape, n, width))
+        return c._adopt(h, False)
+
+    def foolsgold_info(self):
+        """{usable, excluded, at_zero, at_one, degenerate, top, divisor} of the last foolsgold_weights or foolsgold on this
+        engine (synchronises): the rows with a finite diagonal >= 0 and the others, the usable rows whose weight is exactly 0
+        and exactly 1, whether two or more usable rows all had a raw weight of 0, the largest raw weight, and T."""
+        counts, stats = (ctypes.c_int64 * 5)(), (ctypes.c_double * 2)()
+        _check(self.lib.byz_foolsgold_info(self.ctx, counts, stats))
+        self._unsynced.discard(self._last)
+        info = dict(zip(('usable', 'excluded', 'at_zero', 'at_one', 'degenerate'), (int(v) for v in counts)))
+        info['degenerate'] = bool(info['degenerate'])
+        info['top'], info['divisor'] = float(stats[0]), float(stats[1])
+        return info
+
+    def rows_add(self, history, g, columns=None):
+        """history[i][c] = fl32(history[i][c] + g[i][col_start + c]) in place: numpy's float32 += of g's column window
+        (`columns`: None for all, or (start, stop)) onto a device-resident n x w float32 matrix.  Any leading dimension and any
+        4-byte base alignment on either side.  Returns `history`."""
+        with _Call(self) as c:
+            m = c.matrix(g)
+            start, width = self._foolsgold_window(m.cols, columns)
+            h = self._foolsgold_history(c, history, m.rows, width)
+            c.run(self.lib.byz_rows_add_dev(self.ctx, h.ptr, h.ld, m.ptr, m.rows, width, m.ld, start, c.stream))
+        return history
+
+    def foolsgold_weights(self, gram, kappa=1.0, on_device=False, like=None):
+        """FoolsGold's weights on an fp64 Gram (n x n, as `gram` returns it; taken as symmetric): every row's largest cosine
+        with another row, pardoned where the other row's own maximum is larger, turned into a weight by the clipped logit
+        (include/byzagg.h states the rule).  A row whose diagonal entry is not finite or is negative is excluded: weight 0.
+        Returns (weights, info): n fp64 weights (on_device=True: a DeviceBuffer, or a torch tensor beside `like`) and
+        foolsgold_info()'s fields with `maxcs` (m), `alpha` (a), `rescaled` (w of step 8) and `usable_flags` (int32 0 / 1), host arrays
+        unless on_device.  The `divisor` reported is the usable count."""
+        return self._foolsgold_weights(gram, kappa, 'count', on_device, like)
+
+    def _foolsgold_weights(self, gram, kappa, normalise, on_device, like):
+        """foolsgold_weights with the divisor's kind chosen (the columns layout reads T from it)."""
+        with _Call(self) as c:
+            if on_device and like is not None:
+                c.beside(like, on_its_stream=False)
+            shape = tuple(gram.shape)
+            if len(shape) != 2 or shape[0] != shape[1]:
+                raise ValueError('foolsgold_weights() takes a square fp64 Gram, got shape %r' % (shape,))
+            n = shape[0]
+            params = self._foolsgold_params(n, kappa, normalise)
+            gm = c.operand(gram, np.float64, _F64, n * n)
+            outs = [c.out(n, np.float64) for _ in range(4)] + [c.out(n, np.int32)]
+            (weights, wptr), (maxcs, mptr), (alpha, aptr), (rescaled, rptr), (usable, uptr) = outs
+            c.run(self.lib.byz_foolsgold_weights_dev(self.ctx, gm.ptr, n, ctypes.byref(params), wptr, mptr, aptr, c.stream))
+            c.run(self.lib.byz_foolsgold_trace_dev(self.ctx, n, rptr, uptr, c.stream))
+            info = self.foolsgold_info()
+        if not on_device:
+            weights, maxcs, alpha, rescaled, usable = (v.numpy() for v in (weights, maxcs, alpha, rescaled, usable))
+        info.update(maxcs=maxcs, alpha=alpha, rescaled=rescaled, usable_flags=usable)
+        return weights, info
+
+    def foolsgold(self, g, users_count=None, corrupted_count=None, history=None, columns=None, kappa=1.0, normalise='count',
+                  gram=None, return_info=False):
+        """FoolsGold in one library call: the history update (`history`: a device-resident n x w float32 matrix, added to in
+        place; None: stateless), gram of the history -- or of g's column window without one; `gram` replaces that stage --,
+        foolsgold_weights, and the weighted sum of THIS round's rows over T: scaled_rows_sum's bits with the weights and T read
+        on the device.  normalise='count': T is the number of usable rows, so with every weight 1 the rule is the mean;
+        'sum': T is the weights' sum.  T == 0: the zero vector.  `columns`: None for all, or (start, stop): the window of g the
+        history and the Gram are taken over (the output layer, say).  users_count and corrupted_count are accepted and unused:
+        the rule needs no count.  return_info=True also returns foolsgold_info()'s fields with `weights` (fp64, host)."""
+        dm = self._device_matrix(g)
+        n, d = (dm.rows, dm.cols) if dm is not None else self._host_matrix(g).shape
+        params = self._foolsgold_params(n, kappa, normalise)
+        start, width = self._foolsgold_window(d, columns)
+        if gram is not None and tuple(gram.shape) != (n, n):
+            raise ValueError('the Gram has shape %r, the gradients %d rows' % (tuple(gram.shape), n))
+        if dm is None:
+            if history is not None:
+                raise ValueError('foolsgold: a history lives on the device; pass a device-resident matrix with it')
+            h = self._host_matrix(g)
+            out, weights = np.empty(d, dtype=np.float32), np.zeros(n, dtype=np.float64)
+            if gram is not None:
+                gram = np.ascontiguousarray(gram.numpy() if isinstance(gram, DeviceBuffer) else _to_host(gram), dtype=np.float64)
+            _check(self.lib.byz_foolsgold_host(self.ctx, _hp(h), n, d, None, start, width, ctypes.byref(params), _hp(gram), _hp(out),
+                                               _hp(weights)))
+        else:
+            with _Call(self) as c:
+                dm = c.matrix(dm)
+                hm = self._foolsgold_history(c, history, n, width) if history is not None else None
+                gm = c.operand(gram, np.float64, _F64, n * n) if gram is not None else None
+                out, optr = c.out(d)
+                weights, wptr = c.out(n, np.float64, want=return_info)
+                c.run(self.lib.byz_foolsgold_dev(self.ctx, dm.ptr, n, d, dm.ld, hm.ptr if hm is not None else None,
+                                                 hm.ld if hm is not None else 0, start, width, ctypes.byref(params),
+                                                 gm.ptr if gm is not None else None, optr, wptr, c.stream))
+                self.check(c.stream)      # (a kernel of the Gram can only flag a failure)
+                if return_info:
+                    weights = _to_host(weights) if _is_torch(weights) else weights.numpy()
+        if not return_info:
+            return out
+        info = self.foolsgold_info()
+        info['weights'] = np.asarray(weights)
         return out, info
 
     # ---- Multi-Metrics (Huang et al., ICCV 2023; not in the reference) ----

@@ -25,6 +25,7 @@ arrays on the MI355X and runs the same three steps there, so a round never cross
     defend_faba()                     the same step with FABA: the clients farthest from the running mean dropped one by one
     defend_afa(xi, delta_xi)          the same step with AFA: cosine outliers dropped round after round, reputations kept across rounds
     defend_auror(alpha, tau)          the same step with Auror: per-coordinate 2-means, suspicion votes kept across rounds
+    defend_foolsgold(columns, kappa)  the same step with FoolsGold: sybils' weights cut, the clients' summed updates kept across rounds
     defend_multi_metrics(p)           the same step with Multi-Metrics: the int(p n) clients of smallest Mahalanobis score, averaged
 
 Only what is on the aggregation path is mirrored: evaluation, checkpoints, logging and data loading stay the
@@ -69,6 +70,8 @@ class DeviceServer:
         # Auror's history: the clients' votes and the indicative count summed over the rounds (made by the first defend_auror
         # that asks for it)
         self.auror_history = None
+        # FoolsGold's history: every client's updates summed over the rounds (made by the first defend_foolsgold that asks for it)
+        self.foolsgold_history = None
 
     # ---- server.py:81-83 ---------------------------------------------------------------------------
     def collect_gradients(self, users):
@@ -310,6 +313,23 @@ class DeviceServer:
             self.auror_history = defences.AurorHistory(self.n_users)
         current_grads = defences.auror(self.users_grads.data, self.n_users, int(self.n_users * self.mal_prop), alpha, tau=tau,
                                        max_iter=max_iter, history=self.auror_history if history else None)
+        self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
+                                  self.learning_rate)
+        return current_grads
+
+    # ---- the same step with FoolsGold --------------------------------------------------------------------------------
+    def defend_foolsgold(self, columns=None, kappa=1.0, normalise='count', history=True):
+        """FoolsGold on this round's gradients (defences.foolsgold): the clients whose summed updates point the same way get
+        their weight cut, the weighted sum is taken over the usable clients, and server.py:89-90's momentum step on the result,
+        as `defend` takes it.  history=True keeps ONE `defences.FoolsGoldHistory` across the calls (`foolsgold_history`) over
+        the window `columns` ((start, stop); None: every column) of the first such call; history=False: stateless, this
+        round's cosines."""
+        grads = self.users_grads.data
+        if history and self.foolsgold_history is None:
+            start, width = self.engine._foolsgold_window(grads.shape[1], columns)
+            self.foolsgold_history = defences.FoolsGoldHistory(self.n_users, width)
+        current_grads = defences.foolsgold(grads, self.n_users, int(self.n_users * self.mal_prop), columns=columns, kappa=kappa,
+                                           normalise=normalise, history=self.foolsgold_history if history else None)
         self.engine.server_update(self.current_weights, self.velocity, current_grads, self.momentum,
                                   self.learning_rate)
         return current_grads

@@ -192,6 +192,13 @@ class HipKernels:
         # (0 / 1 flags of the kept rows: an int32 tensor beside `like`; info): the same on every rank
         return self.engine.auror_select(votes, bad, counts, tau=tau, on_device=True, like=like)
 
+    def rows_add(self, history, g_local, columns=None):
+        return self.engine.rows_add(history, g_local, columns=columns)      # history += g_local[:, start:stop], in place
+
+    def foolsgold_weights(self, gram, like, kappa=1.0, normalise='count'):
+        # (n fp64 weights: a tensor beside `like`; info, whose divisor is T): the same on every rank
+        return self.engine._foolsgold_weights(gram, kappa, normalise, True, like)
+
     def manhattan_sums(self, g_local):
         return self.engine.manhattan_sums(g_local)             # (N, N) float64 CUDA tensor: additive over the column slices
 
@@ -644,6 +651,41 @@ class ShardedAggregator:
         if not return_info:
             return out
         return out, dict(info, kept_rows=torch.nonzero(kept).reshape(-1).cpu().numpy(), votes=votes.cpu().numpy())
+
+    def foolsgold(self, g_local, users_count=None, corrupted_count=None, history=None, columns=None, column_offset=0, kappa=1.0,
+                  normalise='count', gather=False, total_columns=None, return_info=False):
+        """FoolsGold (defences.foolsgold's contract), columns layout: every rank holds all rows over its own columns,
+        `column_offset` being the global number of its first column and `total_columns` the full D (needed beyond one rank).
+        Every rank keeps the history of ITS OWN columns: `history` is its device-resident float32 matrix of n x (the columns of
+        the global window `columns` that fall into its slice), added to in place; a rank the window misses passes None and
+        contributes a zero Gram.  ONE all-reduce: the N x N fp64 Gram, the exchange AFA makes.  Everything after it is
+        replicated -- kernels.foolsgold_weights gives the same weights and T on every rank -- or local to the columns: the
+        weighted sum over T.  No new collective.  Returns this rank's columns (gather=True: the whole vector)."""
+        import torch
+        n, d_local = g_local.shape
+        total = d_local if total_columns is None else int(total_columns)
+        c0, c1 = (0, total) if columns is None else (int(columns[0]), int(columns[1]))
+        column_offset = int(column_offset)
+        if not 0 <= c0 < c1 <= total:
+            raise ValueError('foolsgold: the window [%d, %d) lies outside the %d columns' % (c0, c1, total))
+        lo, hi = max(c0, column_offset), min(c1, column_offset + d_local)
+        if hi > lo:
+            local = (lo - column_offset, hi - column_offset)
+            if history is not None:
+                self.kernels.rows_add(history, g_local, columns=local)
+                gram = self.kernels.gram(history)
+            else:
+                gram = self.kernels.gram(g_local[:, local[0]:local[1]])
+        else:
+            gram = torch.zeros((n, n), dtype=torch.float64, device=g_local.device)
+        self._all_reduce('allreduce_gram', gram)
+        weights, info = self.kernels.foolsgold_weights(gram, g_local, kappa=kappa, normalise=normalise)
+        divisor = torch.tensor([info['divisor']], dtype=torch.float64, device=g_local.device)     # (the weights stage's own T)
+        v = self.kernels.scaled_rows_sum(g_local, weights, divisor)
+        out = self._maybe_gather(v, gather, total_columns)
+        if not return_info:
+            return out
+        return out, dict(info, weights=weights.cpu().numpy())
 
     def nnm(self, g_local, users_count, corrupted_count, return_neighbours=False):
         """Nearest-neighbour mixing, columns layout: the distances' one all-reduce and nothing more; the neighbour lists are

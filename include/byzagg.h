@@ -1035,6 +1035,78 @@ int byz_auror_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_
                    int32_t* kept_host_or_null, int64_t* votes_host_or_null, int32_t* bad_host_or_null, int64_t* counts_host_or_null,
                    double* gap_host_or_null);
 
+/* ---- FoolsGold (Fung, Yoon & Beschastnikh, "Mitigating Sybils in Federated Learning Poisoning", arXiv:1808.04866; RAID 2020, "The    */
+/* Limitations of Federated Learning in Sybil Settings"; not in the reference) ----                                                    */
+/* Sybils are several clients that push one shared objective round after round: clients whose ACCUMULATED updates point the same way   */
+/* get their weight cut.  It needs no count of attackers.  The decision runs on ONE n x n fp64 Gram and never on the gradients; the    */
+/* Gram is taken over a per-client history matrix that lives on the device across rounds (or over this round's gradients).             */
+/* The rule (R).  Input: an n x n fp64 Gram C, taken as symmetric (row i is read; C_ii is the diagonal), and kappa, finite and > 0,     */
+/* the paper's confidence (default 1).  All arithmetic is fp64, one operation at a time, no contraction.                               */
+/*   1. Usable rows.  Row i is EXCLUDED if C_ii is not finite or is negative: its weight is 0 and no other row sees it as a j.         */
+/*   2. Norms.  r_i = sqrt(C_ii).  A usable row with C_ii == 0 (a client with no history) has cs_ij = cs_ji = 0 for every j.           */
+/*   3. Cosines.  cs_ij = C_ij / (r_i * r_j) for usable i != j with both norms > 0.  A cs_ij that is NaN is taken as 0 (C_ij          */
+/*      non-finite under finite diagonals).  Nothing is clamped to [-1, 1].                                                            */
+/*   4. Row maximum.  m_i = max(0, max_{j != i} cs_ij): the authors' cosine_similarity - eye, the diagonal takes part as 0, so m_i    */
+/*      >= 0 always.                                                                                                                   */
+/*   5. Pardoning, applied on the fly (no second n x n table).  p_ij = (m_i < m_j) ? (cs_ij * m_i) / m_j : cs_ij, in that order of    */
+/*      operations;  a_i = max(0, max_{j != i} p_ij).  m_j > m_i >= 0, so the divisor is never 0.                                      */
+/*      A maximum, here and in 4, starts from +0.0 and takes x when x > what it holds: a NaN p_ij (-inf * 0) and a -0.0 never enter.   */
+/*   6. Raw weight.  v_i = min(1, max(0, 1 - a_i)).                                                                                    */
+/*   7. Rescale.  top = max_i v_i over the usable rows.  Fewer than 2 usable rows: every usable row gets weight 1, stop.  top == 0:    */
+/*      every weight is 0 and `degenerate` = 1 (everybody's twin; the authors' code yields NaN here), stop.                            */
+/*   8. Logit and clip.  w_i = v_i / top; w_i == 1: w_i = 0.99.  w_i == 0: l_i = 0.  Otherwise l_i = kappa * (log(w_i / (1 - w_i))    */
+/*      + 0.5).  Then l_i = min(1, max(0, l_i)).                                                                                       */
+/*   9. Aggregate.  out[c] = fl32(sum_i l_i * G[i][c] / T) over THIS ROUND's gradients G (not the history), by                        */
+/*      byz_scaled_rows_sum_dev, with its bits.  normalise = COUNT (default): T = the number of usable rows; with every weight 1 the   */
+/*      rule is the mean (no_defense).  normalise = SUM: T = sum_i l_i in ascending row order, from +0.0 (Blades' variant).  T is     */
+/*      formed and read on the device; T == 0 gives the zero vector, never NaN.                                                        */
+/* Steps 4 to 8 are the authors' published foolsgold() with its loop order removed: the pardoned maximum does not depend on the order  */
+/* because m is fixed before the loop.  Not built: the paper's feature-importance weighting of the cosines; partial participation      */
+/* (clients are rows by position and every client reports every round).                                                                */
+/* The history.  H is an n x w fp32 matrix on the device, zero at the start; row i is client i; w is the column window [col_start,    */
+/* col_start + w) of the gradients.  Every call first does H[i][c] = fl32(H[i][c] + G[i][col_start + c]) (numpy's float32 += bits),    */
+/* then the Gram is byz_gram_dev(H).  Without a history the Gram is that of G's window itself.  A non-finite value this round makes   */
+/* the client's history row non-finite for good, and rule 1 excludes it until the caller zeroes H.                                     */
+/* Row limit: 1 <= n_rows <= 2^20, what byz_gram_dev and byz_scaled_rows_sum_dev accept (beyond: BYZ_E_UNSUPPORTED); no kernel here    */
+/* needs a lower cap.  No floating-point atomics; no host synchronisation except in byz_foolsgold_info.  Nothing is written when a     */
+/* call is refused.  Asynchronous on `stream`.  Timers: BYZ_K_MISC: the history update and the weights kernel; BYZ_K_ROW_SORT: the     */
+/* norms, the row maxima and the pardoned maxima.                                                                                      */
+#define BYZ_FOOLSGOLD_NORMALISE_COUNT 0
+#define BYZ_FOOLSGOLD_NORMALISE_SUM 1
+typedef struct byz_foolsgold_params {
+    double kappa;        /* the confidence: finite and > 0 (the paper: 1) */
+    int64_t normalise;   /* BYZ_FOOLSGOLD_NORMALISE_COUNT or _SUM */
+} byz_foolsgold_params;
+/* The history update alone: H (n_rows x n_cols_window, ld_h) += G[:, col_start : col_start + n_cols_window] (G: ld_g).  Any ld and    */
+/* any 4-byte base alignment on either operand: 16-byte accesses on both when both bases (G's at the window) and both ld allow it,     */
+/* otherwise 16-byte accesses on H between its own boundaries and dword reads of G.  H must not overlap G (BYZ_E_INVALID).             */
+int byz_rows_add_dev(byz_ctx* ctx, float* H_dev, int64_t ld_h, const float* G_dev, int64_t n_rows, int64_t n_cols_window, int64_t ld_g,
+                     int64_t col_start, void* stream);
+/* Steps 1 to 8 on a Gram: weights_dev (n_rows fp64) = l, 0 for an excluded row.  maxcs_dev_or_null: n_rows fp64, m.                  */
+/* alpha_dev_or_null: n_rows fp64, a.  Four launches: the norms, the row maxima, the pardoned maxima, one workgroup for the rest.      */
+int byz_foolsgold_weights_dev(byz_ctx* ctx, const double* gram_dev, int64_t n_rows, const byz_foolsgold_params* params,
+                              double* weights_dev, double* maxcs_dev_or_null, double* alpha_dev_or_null, void* stream);
+/* The last weights stage's intermediate vectors, copied on `stream` (tests and diagnosis): rescaled_dev_or_null, n_rows fp64, w of    */
+/* step 8 (1 for the usable rows when fewer than 2 are usable, 0 for an excluded row and when degenerate); usable_dev_or_null, n_rows  */
+/* int32 of 0 / 1.  n_rows must be the last stage's (BYZ_E_INVALID otherwise, and before the first).                                   */
+int byz_foolsgold_trace_dev(byz_ctx* ctx, int64_t n_rows, double* rescaled_dev_or_null, int32_t* usable_dev_or_null, void* stream);
+/* The whole rule: the history update (H_dev_or_null == NULL: none), byz_gram_dev of the history or of G's window (gram_dev_or_null    */
+/* != NULL: that n x n fp64 matrix REPLACES the stage; the history is still updated), the weights, and byz_scaled_rows_sum_dev with    */
+/* them and T.  0 <= col_start, 1 <= col_count, col_start + col_count <= n_cols, ld_h >= col_count (BYZ_E_INVALID otherwise).  It      */
+/* waits as byz_gram_dev does, and not at all when gram_dev_or_null is given.  out_dev (n_cols floats) must overlap neither G nor H.   */
+int byz_foolsgold_dev(byz_ctx* ctx, const float* G_dev, int64_t n_rows, int64_t n_cols, int64_t ld, float* H_dev_or_null, int64_t ld_h,
+                      int64_t col_start, int64_t col_count, const byz_foolsgold_params* params, const double* gram_dev_or_null,
+                      float* out_dev, double* weights_dev_or_null, void* stream);
+/* The last byz_foolsgold_weights_dev or byz_foolsgold_dev on this context.  counts5: usable rows, excluded rows, usable rows at       */
+/* weight 0, usable rows at weight 1, degenerate (0 / 1).  stats2: top (0 when nobody is usable) and T.  Either may be NULL.           */
+/* Synchronises that call's stream.  BYZ_E_INVALID before the first such call.                                                         */
+int byz_foolsgold_info(byz_ctx* ctx, int64_t* counts5, double* stats2);
+/* The same on a host matrix (H_host_or_null: n_rows x col_count floats, contiguous, read and written; gram_host_or_null: n_rows x     */
+/* n_rows fp64; out_host: n_cols floats; weights_host_or_null: n_rows fp64).  Synchronous.                                             */
+int byz_foolsgold_host(byz_ctx* ctx, const float* G_host, int64_t n_rows, int64_t n_cols, float* H_host_or_null, int64_t col_start,
+                       int64_t col_count, const byz_foolsgold_params* params, const double* gram_host_or_null, float* out_host,
+                       double* weights_host_or_null);
+
 /* ---- DnC, the spectral defence (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2; not in the reference) ---- */
 /* Colluding rows that each stay below every distance and per-coordinate threshold still line up along ONE    */
 /* direction of the centred gradient matrix: its top right singular vector.  DnC scores every row by its      */
